@@ -179,10 +179,12 @@ __global__ __launch_bounds__(256) void sample_ids_kernel(int B, int C, const flo
 
 // Scheduled sampling of ONE decoder step in ONE launch (the step chain of nabu_speller_fwd): row b draws the Bernoulli of
 // sample_ids_kernel first and only a row that IS to be sampled (sample_prob = 0.1 in the reference's defaults: one in
-// ten) evaluates its logits [h | ctx] . W_out + b — 25 k slots x (C / 4) class quads, 16-byte loads of the weight rows —
-// and draws from softmax(logits) by the inverse CDF in class order, exactly as sample_ids_kernel does.  Replaces two
+// ten) evaluates its logits [h | ctx] . W_out + b — up to 25 k slots x (C / 4) class quads, 16-byte loads of the weight
+// rows — and draws from softmax(logits) by the inverse CDF in class order, exactly as sample_ids_kernel does.  Replaces two
 // [Bn, C] products through the general GEMM entry point and the sampling launch per step and sub-batch
-// (rnn_decoder.py:59-66, ScheduledEmbeddingTrainingHelper).  Requires C % 4 == 0, C <= 256.
+// (rnn_decoder.py:59-66, ScheduledEmbeddingTrainingHelper).  Requires C % 4 == 0, C <= 256: the 256 threads hold
+// nks = min(25, 256 / (C / 4)) whole k slots (25 up to C = 40, fewer above), slot ks adds k = ks, ks + nks, ... and the
+// trailing partial slot of threads (256 % (C / 4) of them) stays idle.
 constexpr int SAMPLE_KS = 25;
 __global__ __launch_bounds__(256) void sample_step_kernel(int C, int U, int E, const float *__restrict__ h, int ldh,
                                                           const float *__restrict__ ctx, int ldc,
@@ -198,12 +200,12 @@ __global__ __launch_bounds__(256) void sample_step_kernel(int C, int U, int E, c
     if (tid == 0) out[b] = teacher[b];
     return;
   }
-  const int CQ = C / 4, ks = tid / CQ, cq = tid - ks * CQ, K = U + E;
-  if (ks < SAMPLE_KS) {
+  const int CQ = C / 4, ks = tid / CQ, cq = tid - ks * CQ, K = U + E, nks = min(SAMPLE_KS, 256 / CQ);
+  if (ks < nks) {
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     const float *hb = h + (size_t)b * ldh, *cb = ctx + (size_t)b * ldc;
 #pragma unroll 8
-    for (int k = ks; k < K; k += SAMPLE_KS) {
+    for (int k = ks; k < K; k += nks) {
       const float x = k < U ? hb[k] : cb[k - U];
       const float4 wv = *reinterpret_cast<const float4 *>(Wout + (size_t)k * C + 4 * cq);
       acc.x = fmaf(x, wv.x, acc.x); acc.y = fmaf(x, wv.y, acc.y); acc.z = fmaf(x, wv.z, acc.z); acc.w = fmaf(x, wv.w, acc.w);
@@ -213,7 +215,6 @@ __global__ __launch_bounds__(256) void sample_step_kernel(int C, int U, int E, c
   __syncthreads();
   if (tid < C) {
     float v = bias[tid];
-    const int nks = min(SAMPLE_KS, 256 / CQ);
     for (int i = 0; i < nks; ++i) v += part[i][tid];
     lg[tid] = v;
   }
