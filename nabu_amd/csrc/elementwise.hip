@@ -523,6 +523,8 @@ int multi_fill(const FillSeg *segs, int n, hipStream_t stream) {
 int dropout_rows(size_t n, const float *x, float *y, float keep_prob, unsigned long long seed, unsigned long long offset,
                  size_t first_elem, hipStream_t stream) {
   if (n == 0) return 0;
+  // (a start inside a group would read its neighbour's words for the group's other lanes)
+  if (first_elem % 4) return fail(NABU_EINVAL, "dropout_rows: first element %zu is not a multiple of 4", first_elem);
   hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, stream, n, x, y, keep_prob, seed, offset,
                      first_elem / 4);
   NABU_LAUNCH_CHECK();

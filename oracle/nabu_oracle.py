@@ -197,49 +197,67 @@ def pyramid_stack_bwd(dout, T, numsteps):
 # --------------------------------------------------------------------------
 # encoders
 # --------------------------------------------------------------------------
-def listener_fwd(x, lens, layers, pyramid_steps=2):
-    """Listener.encode (listener.py:49-65) with input_noise=0, dropout=1:
-    len(layers)-1 pblstm layers followed by one plain blstm."""
+def _drop(x, m):
+    return x if m is None else x * m
+
+
+def listener_fwd(x, lens, layers, pyramid_steps=2, noise=None, masks=None):
+    """Listener.encode (listener.py:49-65): len(layers)-1 pblstm layers followed
+    by one plain blstm.
+
+    Regularisation given its random numbers (default: none, input_noise=0, dropout=1):
+    noise: added to x (tf.random_normal * input_noise, listener.py:40-45);
+    masks: one per layer (None = no dropout there), the dropout scale factors
+       (0 or 1/keep) of tf.nn.dropout -- after each pblstm's stacking and after
+       the last blstm, in the shape of that layer's output."""
+    masks = [None] * len(layers) if masks is None else list(masks)
+    assert len(masks) == len(layers)
     caches = []
-    h, l = x, np.asarray(lens)
-    for p in layers[:-1]:
+    h, l = (x if noise is None else x + noise), np.asarray(lens)
+    for p, m in zip(layers[:-1], masks[:-1]):
         o, c = blstm_fwd(h, l, p)
         T = o.shape[1]
         h, l2 = pyramid_stack_fwd(o, l, pyramid_steps)
-        caches.append((c, T))
+        h = _drop(h, m)
+        caches.append((c, T, m))
         l = l2
     o, c = blstm_fwd(h, l, layers[-1])
-    caches.append((c, o.shape[1]))
-    return o, l, caches
+    caches.append((c, o.shape[1], masks[-1]))
+    return _drop(o, masks[-1]), l, caches
 
 
 def listener_bwd(dout, caches, pyramid_steps=2):
+    """the masks of listener_fwd travel in caches; the noise adds nothing to the input gradient"""
     grads = []
-    c, _ = caches[-1]
-    d, g = blstm_bwd(dout, c)
+    c, _, m = caches[-1]
+    d, g = blstm_bwd(_drop(dout, m), c)
     grads.append(g)
-    for c, T in reversed(caches[:-1]):
-        d = pyramid_stack_bwd(d, T, pyramid_steps)
+    for c, T, m in reversed(caches[:-1]):
+        d = pyramid_stack_bwd(_drop(d, m), T, pyramid_steps)
         d, g = blstm_bwd(d, c)
         grads.append(g)
     return d, grads[::-1]
 
 
-def dblstm_fwd(x, lens, layers):
-    """DBLSTM.encode (dblstm.py:44-54): stacked blstm at full time resolution."""
+def dblstm_fwd(x, lens, layers, noise=None, masks=None):
+    """DBLSTM.encode (dblstm.py:44-54): stacked blstm at full time resolution.
+    noise, masks: as listener_fwd's, a mask after every layer (dblstm.py:37-54)."""
+    masks = [None] * len(layers) if masks is None else list(masks)
+    assert len(masks) == len(layers)
     caches = []
-    h = x
-    for p in layers:
+    h = x if noise is None else x + noise
+    for p, m in zip(layers, masks):
         h, c = blstm_fwd(h, lens, p)
-        caches.append(c)
+        h = _drop(h, m)
+        caches.append((c, m))
     return h, np.asarray(lens), caches
 
 
 def dblstm_bwd(dout, caches):
     grads = []
     d = dout
-    for c in reversed(caches):
-        d, g = blstm_bwd(d, c)
+    for c, m in reversed(caches):
+        d, g = blstm_bwd(_drop(d, m), c)
         grads.append(g)
     return d, grads[::-1]
 
@@ -477,9 +495,15 @@ def attention_window(prev_align, left, right):
 
 
 def speller_fwd(enc, enc_len, targets, target_len, p, attention='vanilla',
-                probability_fn='softmax', dec_inputs=None, window=None):
+                probability_fn='softmax', dec_inputs=None, window=None, out_masks=None):
     """RNNDecoder._decode (rnn_decoder.py:13-82) with Speller.create_cell
     (speller.py:13-69), sample_prob=0, dropout=1.
+
+    out_masks (optional): out_masks[t][n] [B,U], the output dropout scale factors
+    (0 or 1/keep) of layer n at step t -- DropoutWrapper(output_keep_prob) inside
+    MultiRNNCell (speller.py:30-40): the dropped output feeds the next layer, the
+    attention query and the output projection, while the layer's LSTM state
+    keeps the undropped h.
 
     dec_inputs [B,L] (optional): the decoder input labels to use instead of
     [SOS, targets[:-1]] — the inputs a ScheduledEmbeddingTrainingHelper run with
@@ -534,7 +558,7 @@ def speller_fwd(enc, enc_len, targets, target_len, p, attention='vanilla',
             h = np.tanh(c) * o
             st['lstm'].append(dict(xin=xin, i=i, g=g, f=f, o=o, c=c))
             nh.append(h); nc.append(c)
-            x = h
+            x = h if out_masks is None else h * out_masks[t][n]
         query = x
         q = query @ p['query_kernel']
         s = keys + q[:, None, :]
@@ -562,7 +586,7 @@ def speller_fwd(enc, enc_len, targets, target_len, p, attention='vanilla',
         ctx = np.where(act, cx, ctx)
         align = np.where(act, al, align)
     cache = dict(steps=steps, p=p, values=values, keys=keys, mask=mask, enc=enc,
-                 attention=attention, probability_fn=probability_fn, U=U, C=C)
+                 attention=attention, probability_fn=probability_fn, U=U, C=C, out_masks=out_masks)
     return logits, target_len.copy(), cache
 
 
@@ -571,6 +595,7 @@ def speller_bwd(dlogits, cache):
     p, steps = cache['p'], cache['steps']
     values, keys, mask = cache['values'], cache['keys'], cache['mask']
     att, pf, U, C = cache['attention'], cache['probability_fn'], cache['U'], cache['C']
+    om = cache.get('out_masks')
     B, Te, E = values.shape
     dt = values.dtype
     nl = len(p['lstm'])
@@ -614,6 +639,8 @@ def speller_bwd(dlogits, cache):
             c_ = st['lstm'][n]
             i, gg, f, o, c = c_['i'], c_['g'], c_['f'], c_['o'], c_['c']
             tc = np.tanh(c)
+            if om is not None:
+                dx = dx * om[t][n]                       # d of the dropped output -> d h
             dh = np.where(act, dx + dhs[n], 0)
             dc = np.where(act, dcs[n], 0) + dh * o * (1 - tc * tc)
             dz = np.concatenate([dc * gg * i * (1 - i), dc * i * (1 - gg * gg),

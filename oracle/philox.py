@@ -81,3 +81,48 @@ def reference_draw(logits, prob, seed, offset, teacher, row0=0):
     ids = np.where(selected, drawn, np.asarray(teacher, np.int64))
     margin = np.where(selected, margin, np.inf)
     return ids, selected, margin, np.stack([lo, hi], 1)
+
+
+def _group_words(groups, seed, offset):
+    """words [len(groups), 4] of the element-wise stream: counter (group_lo, group_hi, offset_lo, offset_hi),
+    key (seed_lo, seed_hi) -- dropout_kernel / gaussian_noise_kernel of elementwise.hip, dropout_scale4 of common.h"""
+    groups = np.asarray(groups, np.uint64)
+    ctr = np.zeros(groups.shape + (4,), np.uint32)
+    ctr[..., 0] = (groups & _LO).astype(np.uint32)
+    ctr[..., 1] = (groups >> np.uint64(32)).astype(np.uint32)
+    ctr[..., 2] = np.uint32(offset & 0xFFFFFFFF)
+    ctr[..., 3] = np.uint32((offset >> 32) & 0xFFFFFFFF)
+    key = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], np.uint32)
+    return philox4x32_10(ctr, key)
+
+
+def dropout_scale(n, keep, seed, offset, first_elem=0):
+    """float32 [n]: the dropout scale factors (0 or float32(1) / float32(keep)) of elements first_elem ..
+    first_elem + n - 1 of the array the stream (seed, offset) is defined on.  Element e reads lane e % 4 of the
+    words of group e // 4 and is kept when u01(word) < float32(keep), as the device compares float32 values."""
+    e = np.arange(first_elem, first_elem + n, dtype=np.uint64)
+    if n == 0:
+        return np.zeros(0, np.float32)
+    g0 = int(e[0]) // 4
+    words = _group_words(np.arange(g0, int(e[-1]) // 4 + 1, dtype=np.uint64), seed, offset).reshape(-1)
+    w = words[(e - np.uint64(4 * g0)).astype(np.int64)]
+    k = np.float32(keep)
+    inv = np.float32(1) / k
+    return np.where(u01(w) < np.float64(k), inv, np.float32(0)).astype(np.float32)
+
+
+def gaussian(n, seed, offset, with_radius=False):
+    """float64 [n]: the standard normal values gaussian_noise_kernel adds (times stddev) to elements 0 .. n - 1.
+    Group i's words (x, y, z, w) give Box-Muller pairs on u1 = 1 - u01(x), u2 = u01(y) and u3 = 1 - u01(z),
+    u4 = u01(w), in the order (ra cos 2 pi u2, ra sin 2 pi u2, rb cos 2 pi u4, rb sin 2 pi u4), ra = sqrt(-2 ln u1),
+    rb = sqrt(-2 ln u3) -- in float64 from the device's exact uniforms.  with_radius: also return each element's
+    radius (ra or rb), the factor by which an error in the float32 angle 2 pi u reaches the value."""
+    if n == 0:
+        return (np.zeros(0), np.zeros(0)) if with_radius else np.zeros(0)
+    r = _group_words(np.arange((n + 3) // 4, dtype=np.uint64), seed, offset)
+    u1, u2, u3, u4 = 1.0 - u01(r[:, 0]), u01(r[:, 1]), 1.0 - u01(r[:, 2]), u01(r[:, 3])
+    ra, rb = np.sqrt(-2.0 * np.log(u1)), np.sqrt(-2.0 * np.log(u3))
+    a, b = 2.0 * np.pi * u2, 2.0 * np.pi * u4
+    z = np.stack([ra * np.cos(a), ra * np.sin(a), rb * np.cos(b), rb * np.sin(b)], 1).reshape(-1)[:n]
+    rad = np.stack([ra, ra, rb, rb], 1).reshape(-1)[:n]
+    return (z, rad) if with_radius else z

@@ -401,3 +401,146 @@ def test_ctc_matches_tensorflows_own_known_answer_vectors():
     nll, grad = O.ctc_loss(np.log(fx['prob']), fx['logit_len'], fx['labels'], fx['label_len'])
     assert np.abs(nll - fx['loss']).max() < 1e-5
     assert np.abs(grad - fx['grad']).max() < 2e-6
+
+
+# ------------------------------------------------------------------ regularisation given its random numbers
+
+
+def _masks_like(rng, shapes, keep):
+    return [(rng.random(s) < keep) / keep for s in shapes]
+
+
+def _enc_shapes(x, lens, layers, kind):
+    out, _, caches = (O.listener_fwd if kind == 'listener' else O.dblstm_fwd)(x, lens, layers)
+    if kind == 'dblstm':
+        return [out.shape] * len(layers)
+    B = x.shape[0]
+    return [(B, -(-T // 2), 4 * out.shape[2] // 2) for _, T, _ in caches[:-1]] + [out.shape]
+
+
+def _enc_case(kind, rng):
+    B, T, D, H = 3, 11, 4, 5
+    x = rng.normal(size=(B, T, D))
+    lens = np.array([11, 7, 4])
+    if kind == 'listener':
+        layers = [_blstm_params(rng, D, H), _blstm_params(rng, 4 * H, H), _blstm_params(rng, 4 * H, H)]
+    else:
+        layers = [_blstm_params(rng, D, H), _blstm_params(rng, 2 * H, H)]
+    return x, lens, layers
+
+
+@pytest.mark.parametrize('kind', ['listener', 'dblstm'])
+def test_encoder_all_ones_masks_and_zero_noise_change_nothing(kind):
+    rng = _rng(21)
+    x, lens, layers = _enc_case(kind, rng)
+    fwd, bwd = (O.listener_fwd, O.listener_bwd) if kind == 'listener' else (O.dblstm_fwd, O.dblstm_bwd)
+    o, l, c = fwd(x, lens, layers)
+    ones = [np.ones(s) for s in _enc_shapes(x, lens, layers, kind)]
+    o1, l1, c1 = fwd(x, lens, layers, noise=np.zeros_like(x), masks=ones)
+    np.testing.assert_array_equal(o, o1)
+    np.testing.assert_array_equal(l, l1)
+    d = rng.normal(size=o.shape)
+    dx, g = bwd(d, c)
+    dx1, g1 = bwd(d, c1)
+    np.testing.assert_array_equal(dx, dx1)
+    for a, b_ in zip(g, g1):
+        for k in a:
+            np.testing.assert_array_equal(a[k], b_[k])
+
+
+@pytest.mark.parametrize('kind', ['listener', 'dblstm'])
+def test_encoder_regularised_gradients_finite_difference(kind):
+    """input noise 0.6 (also on the padded frames) and keep-0.5 masks: every parameter's and the input's gradient
+    of sum(out * w) against central differences at a few entries; the masks really act"""
+    rng = _rng(22)
+    x, lens, layers = _enc_case(kind, rng)
+    fwd, bwd = (O.listener_fwd, O.listener_bwd) if kind == 'listener' else (O.dblstm_fwd, O.dblstm_bwd)
+    noise = 0.6 * rng.normal(size=x.shape)
+    masks = _masks_like(rng, _enc_shapes(x, lens, layers, kind), 0.5)
+    o, _, c = fwd(x, lens, layers, noise=noise, masks=masks)
+    assert np.abs(o - fwd(x, lens, layers)[0]).max() > 0.1
+    w = rng.normal(size=o.shape)
+    dx, grads = bwd(w, c)
+    f = lambda xx, ll: float((fwd(xx, lens, ll, noise=noise, masks=masks)[0] * w).sum())
+    eps = 1e-6
+    for idx in [(0, 0, 0), (1, 3, 2), (2, 2, 1), (1, 8, 3)]:      # (1, 8, 3): a padded frame (len 7)
+        a, b_ = x.copy(), x.copy()
+        a[idx] += eps; b_[idx] -= eps
+        np.testing.assert_allclose(dx[idx], (f(a, layers) - f(b_, layers)) / (2 * eps), atol=1e-7)
+    for li, g in enumerate(grads):
+        for k in g:
+            flat = np.unravel_index(rng.integers(0, g[k].size, 3), g[k].shape)
+            for idx in zip(*flat):
+                la = [dict(q) for q in layers]; lb = [dict(q) for q in layers]
+                la[li][k] = la[li][k].copy(); la[li][k][idx] += eps
+                lb[li][k] = lb[li][k].copy(); lb[li][k][idx] -= eps
+                fd = (f(x, la) - f(x, lb)) / (2 * eps)
+                np.testing.assert_allclose(g[k][idx], fd, atol=1e-7, err_msg='%d %s' % (li, k))
+
+
+def _speller_case(rng, nl, attention):
+    B, Te, E, U, C = 3, 7, 6, 5, 6
+    enc = rng.normal(size=(B, Te, E))
+    enc_len = np.array([7, 5, 3])
+    tl = np.array([5, 3, 4])
+    targets = rng.integers(0, C - 1, (B, 5))
+    for b in range(B):
+        targets[b, tl[b] - 1] = C - 1
+    return enc, enc_len, targets, tl, _speller_params(rng, E, U, C, nl, attention)
+
+
+@pytest.mark.parametrize('nl', [1, 2])
+def test_speller_all_ones_masks_change_nothing(nl):
+    rng = _rng(23)
+    enc, enc_len, targets, tl, p = _speller_case(rng, nl, 'location_aware')
+    lg, ll, cache = O.speller_fwd(enc, enc_len, targets, tl, p, 'location_aware')
+    ones = [[np.ones((3, 5)) for _ in range(nl)] for _ in range(5)]
+    lg1, _, cache1 = O.speller_fwd(enc, enc_len, targets, tl, p, 'location_aware', out_masks=ones)
+    np.testing.assert_array_equal(lg, lg1)
+    _, dlg = O.average_cross_entropy(lg, targets, ll, tl)
+    d, g = O.speller_bwd(dlg, cache)
+    d1, g1 = O.speller_bwd(dlg, cache1)
+    np.testing.assert_array_equal(d, d1)
+    for k in g:
+        if k != 'lstm':
+            np.testing.assert_array_equal(g[k], g1[k])
+    for a, b_ in zip(g['lstm'], g1['lstm']):
+        np.testing.assert_array_equal(a['kernel'], b_['kernel'])
+        np.testing.assert_array_equal(a['bias'], b_['bias'])
+
+
+@pytest.mark.parametrize('nl,attention', [(1, 'vanilla'), (2, 'location_aware')])
+def test_speller_output_dropout_gradients_finite_difference(nl, attention):
+    """keep-0.5 output masks of every (step, layer), with sampled decoder inputs: the loss's gradient with respect
+    to the encoder output and to entries of every parameter against central differences"""
+    rng = _rng(24 + nl)
+    enc, enc_len, targets, tl, p = _speller_case(rng, nl, attention)
+    B, L, U, C = 3, 5, 5, 6
+    masks = [[(rng.random((B, U)) < 0.5) / 0.5 for _ in range(nl)] for _ in range(L)]
+    dec_inputs = rng.integers(0, C, (B, L))
+    run = lambda e, q: O.speller_fwd(e, enc_len, targets, tl, q, attention, dec_inputs=dec_inputs, out_masks=masks)
+    loss_of = lambda e, q: O.average_cross_entropy(run(e, q)[0], targets, tl, tl)[0]
+    lg, ll, cache = run(enc, p)
+    assert np.abs(lg - O.speller_fwd(enc, enc_len, targets, tl, p, attention, dec_inputs=dec_inputs)[0]).max() > 0.05
+    _, dlg = O.average_cross_entropy(lg, targets, ll, tl)
+    denc, g = O.speller_bwd(dlg, cache)
+    eps = 1e-6
+    for idx in [(0, 0, 0), (1, 4, 5), (2, 2, 3)]:
+        a, b_ = enc.copy(), enc.copy()
+        a[idx] += eps; b_[idx] -= eps
+        np.testing.assert_allclose(denc[idx], (loss_of(a, p) - loss_of(b_, p)) / (2 * eps), atol=1e-8)
+
+    def perturb(path, idx, delta):
+        q = dict(p, lstm=[dict(d) for d in p['lstm']])
+        holder = q['lstm'][path[1]] if path[0] == 'lstm' else q
+        key = path[-1]
+        holder[key] = holder[key].copy()
+        holder[key][idx] += delta
+        return q
+    paths = [(k,) for k in g if k != 'lstm'] + [('lstm', n, k) for n in range(nl) for k in ('kernel', 'bias')]
+    for path in paths:
+        ga = g['lstm'][path[1]][path[2]] if path[0] == 'lstm' else g[path[0]]
+        flat = np.unravel_index(rng.integers(0, ga.size, 3), ga.shape)
+        for idx in zip(*flat):
+            fd = (loss_of(enc, perturb(path, idx, eps)) - loss_of(enc, perturb(path, idx, -eps))) / (2 * eps)
+            np.testing.assert_allclose(ga[idx], fd, atol=1e-8, err_msg=str(path))

@@ -106,3 +106,88 @@ def test_reference_draw_boundary_margin():
     np.testing.assert_array_equal(ids, (u >= 0.5).astype(np.int64))
     near = np.abs(u - 0.5) <= 1e-5
     assert np.all(bounds[~near, 0] == bounds[~near, 1])
+
+
+# ------------------------------------------------------------------------------------- dropout masks and noise
+
+
+def test_dropout_scale_counter_key_and_lane_layout():
+    """element e: lane e % 4 of Philox((e // 4 lo, hi, offset lo, hi), (seed lo, hi)), kept when u01 < keep"""
+    seed, offset = (9 << 32) | 5, (1 << 32) | 77
+    first = (3 << 32) * 4 + 8                           # a group index whose high word is 3
+    s = P.dropout_scale(8, 0.5, seed, offset, first_elem=first)
+    for j in range(8):
+        g = (first + j) // 4
+        r = P.philox4x32_10(np.array([g & 0xFFFFFFFF, g >> 32, 77, 1], np.uint32), np.array([5, 9], np.uint32))
+        assert s[j] == (np.float32(2) if P.u01(r[j % 4]) < 0.5 else 0), j
+    assert s.dtype == np.float32
+
+
+def test_dropout_scale_keep_one_keeps_everything():
+    s = P.dropout_scale(4099, 1.0, 123, (1 << 32) - 1)
+    assert s.dtype == np.float32 and np.all(s == 1)
+
+
+@pytest.mark.parametrize('keep', [0.9, 0.3])
+def test_dropout_scale_is_float32_reciprocal(keep):
+    s = P.dropout_scale(1000, keep, 1, 2)
+    assert set(np.unique(s)) == {np.float32(0), np.float32(1) / np.float32(keep)}
+
+
+@pytest.mark.parametrize('first', [0, 4, 1000, 4 * (1 << 32) - 8])
+def test_dropout_scale_sub_range_is_the_whole_arrays_slice(first):
+    whole = P.dropout_scale(first + 40, 0.6, 77, 1000003 * 5 + 1) if first < 10000 else None
+    part = P.dropout_scale(40, 0.6, 77, 1000003 * 5 + 1, first_elem=first)
+    if whole is not None:
+        np.testing.assert_array_equal(part, whole[first:])
+    # rows of an unaligned start still read the lanes of their own element index
+    odd = P.dropout_scale(37, 0.6, 77, 1000003 * 5 + 1, first_elem=first + 3)
+    np.testing.assert_array_equal(odd, part[3:])
+
+
+@pytest.mark.parametrize('keep', [0.9, 0.5, 0.1])
+def test_dropout_scale_kept_fraction(keep):
+    """binomial: the kept fraction of 2^20 elements within 6 standard deviations"""
+    n = 1 << 20
+    s = P.dropout_scale(n, keep, (1 << 33) + 1, (1 << 32) + 5)
+    kf = np.float32(keep)
+    sd = np.sqrt(float(kf) * (1 - float(kf)) / n)
+    assert abs((s > 0).mean() - float(kf)) < 6 * sd
+
+
+def test_dropout_scale_different_streams_differ():
+    a = P.dropout_scale(4096, 0.5, 1, 10)
+    assert not np.array_equal(a, P.dropout_scale(4096, 0.5, 1, 11))
+    assert not np.array_equal(a, P.dropout_scale(4096, 0.5, 2, 10))
+    assert not np.array_equal(a, P.dropout_scale(4096, 0.5, 1, 10 + (1 << 32)))    # the high offset word counts
+
+
+def test_gaussian_layout_and_values():
+    """element 4 i + (0, 1, 2, 3) = (ra cos, ra sin, rb cos, rb sin) of group i's words"""
+    seed, offset = 3 | (4 << 32), 9 | (2 << 32)
+    z, rad = P.gaussian(11, seed, offset, with_radius=True)
+    np.testing.assert_array_equal(P.gaussian(11, seed, offset), z)
+    for i in range(3):
+        r = P.philox4x32_10(np.array([i, 0, 9, 2], np.uint32), np.array([3, 4], np.uint32))
+        u = P.u01(r)
+        ra, rb = np.sqrt(-2 * np.log(1 - u[0])), np.sqrt(-2 * np.log(1 - u[2]))
+        want = [ra * np.cos(2 * np.pi * u[1]), ra * np.sin(2 * np.pi * u[1]),
+                rb * np.cos(2 * np.pi * u[3]), rb * np.sin(2 * np.pi * u[3])]
+        for j in range(4):
+            if 4 * i + j < 11:
+                assert z[4 * i + j] == want[j]
+                assert rad[4 * i + j] == (ra if j < 2 else rb)
+    assert np.all(np.isfinite(z))
+
+
+def test_gaussian_moments():
+    """2^20 values: mean, variance, skewness and excess kurtosis within 6 standard errors of N(0, 1)"""
+    n = 1 << 20
+    z = P.gaussian(n, 17, (1 << 32) - 1)
+    assert abs(z.mean()) < 6 / np.sqrt(n)
+    assert abs(z.var() - 1) < 6 * np.sqrt(2.0 / n)
+    assert abs(np.mean(z ** 3)) < 6 * np.sqrt(15.0 / n)
+    assert abs(np.mean(z ** 4) - 3) < 6 * np.sqrt(96.0 / n)
+    # the tails: |z| > 3 with probability 0.0027
+    p = np.mean(np.abs(z) > 3)
+    assert abs(p - 0.0026998) < 6 * np.sqrt(0.0027 / n)
