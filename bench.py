@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — utterances/sec of the Nabu training step on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
   N > 1 either way:
     * python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
       --master-port P bench.py --gpus N ...      (ranks are given: RANK/WORLD_SIZE in the env)
@@ -22,18 +22,22 @@ products on the 16-bit matrix pipe — f16x3: every operand row scaled by a powe
 two fp16 planes, three plane products, 16-k partial sums promoted to fp32 accumulators; measured
 error against float64 at or below the exact-fp32 MFMA kernel's (tests/test_hip_gemm_pk.py), per-step
 loss within 5e-5 of the float64 oracle at the full size (tests/test_hip_golden.py) — everything else
-of the step is fp32.  The same step with the exact six-plane split on the bf16 pipe (bf16x6) and with
-exact-fp32 products (v_mfma_f32_32x32x2_f32) is timed in the same run and printed as the `alt_bf16x6`
+of the step is fp32.  A --full run times the same step with the exact six-plane split on the bf16 pipe (bf16x6)
+and with exact-fp32 products (v_mfma_f32_32x32x2_f32) after the headline and prints them as the `alt_bf16x6`
 and `f32_products` objects of the line, and once more as `fp32_end_to_end`: exact-fp32 products AND the exact-fp32
 recurrent kernels (the headline's recurrent product runs as three fp16 plane products of row-scaled operands).
 
-One JSON line is printed by rank 0.  Extra objects:
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times the K steps, writes its outputs if
+--dump-outputs is given and prints the line; what it reports beyond the headline comes from those steps:
   roofline     — SURVEY.md 8(d): the recurrent LSTM step's ALGORITHMIC bytes (per timestep per
                  direction W_h + x-projection + gate activations + h/c state) of a whole
                  training step over the measured step time = `frac` of the HBM peak; the
                  recurrent kernels alone (HIP events recorded by the library around their
                  launches, inside the timed region, on the launch stream) are the sub-object
                  `recurrent_kernels`.
+--full adds, after the headline, the measurements that take runs of their own: the K steps repeated
+(ms_per_step_repeats), the other arithmetics above, other_configs (cfg1, cfg3, cfg5 and the training-defaults
+legs) and
   roofline_gemm— the dense products of a step at their real shapes, timed with events.
   cpu_baseline — oracle/cpu_baseline.py: the reference graph restated at TF op
                  granularity with PyTorch-CPU float32 ("port"), SURVEY.md 8(d)
@@ -353,8 +357,9 @@ def parse_args(argv=None):
                          'workload\'s RECIPE ships (cfg2: f16x3 = fp32-equivalent three-plane products of row-scaled '
                          'fp16 operands); given, it overrides the recipe\'s encoder.gemm_precision key for this run '
                          '(bf16x6 = fp32-equivalent six-plane products on the bf16 matrix pipe, f32 = exact fp32 '
-                         'MFMA).  The line names the arithmetic in config.gemm_arith and carries the other two, timed '
-                         'with the same steps / warm-up, as `f32_products` / `alt_bf16x6` / `alt_f16x3`, plus `fp32_end_to_end` (exact-fp32 products AND recurrence)')
+                         'MFMA).  The line names the arithmetic in config.gemm_arith and, with --full, carries the other '
+                         'two, timed with the same steps / warm-up, as `f32_products` / `alt_bf16x6` / `alt_f16x3`, plus '
+                         '`fp32_end_to_end` (exact-fp32 products AND recurrence)')
     ap.add_argument('--workload', default='cfg2', choices=['cfg1', 'cfg2', 'cfg3', 'cfg5'],
                     help='cfg2 (default) is the BASELINE.json metric; cfg3 = same encoder + Speller; cfg5 = '
                          'location-aware LAS, batch 64x1600x80, bf16 input GEMMs (BASELINE.json configs[2]/[4]), '
@@ -366,7 +371,7 @@ def parse_args(argv=None):
                          'GPUs than ranks the process group is gloo and the ranks share the devices round-robin.')
     ap.add_argument('--cpu-all-cores', action='store_true',
                     help='ONLY measure one cfg2 training step of the CPU port at ALL physical cores of this host (SURVEY.md '
-                         '8(d) names that setting; it takes ~10 minutes on a 128-core host, which is why the default run '
+                         '8(d) names that setting; it takes ~10 minutes on a 128-core host, which is why the --full run '
                          'reports it as a labelled prediction) and print it as one JSON line; no GPU work')
     ap.add_argument('--shrink', action='store_true',
                     help='NOT a measurement: cfg2\'s recipe at 4 utterances x 64 frames, 64 units — lets the tests run the '
@@ -377,14 +382,21 @@ def parse_args(argv=None):
                          'input_noise 0.6 and dropout keep 0.5 (ed_encoders/defaults/listener.cfg), Speller output dropout keep '
                          '0.5 and sample_prob 0.1 (ed_decoders/defaults/speller.cfg) — instead of the deterministic settings '
                          'the parity configs of SURVEY.md 8(d) prescribe; the line says config.training_defaults = true')
-    ap.add_argument('--repeats', type=int, default=3,
+    ap.add_argument('--full', action='store_true',
+                    help='measure everything beyond the headline after it: the K timed steps repeated (--repeats, default '
+                         '3 here), the other arithmetics of the dense products (alt legs), roofline_gemm, the other '
+                         'single-GPU configs (other_configs) and the CPU baseline; the --no-* options skip single legs.  '
+                         'Without it a run sets up, warms up, times the K steps, dumps its outputs if asked to and prints '
+                         'the line')
+    ap.add_argument('--repeats', type=int, default=None,
                     help='the K timed steps are repeated this many times inside the same command (same bracket each time); '
-                         'the headline value is the FIRST region — warm-up W, then exactly K steps — the line carries all of '
-                         'them as ms_per_step_repeats with their spread, and the shader clock the recurrent kernels ran at '
-                         '(effective_clock), so that a slow box of the pool is visible as such')
+                         'default 3 with --full, else 1.  The headline value is the FIRST region — warm-up W, then exactly K '
+                         'steps — the line carries all of them as ms_per_step_repeats with their spread, and the shader '
+                         'clock the recurrent kernels ran at (effective_clock), so that a slow box of the pool is visible '
+                         'as such')
     ap.add_argument('--no-other-configs', action='store_true',
                     help='skip the other single-GPU BASELINE.json configs (cfg1, cfg3, cfg5\'s per-GPU share) and the '
-                         'training-defaults legs that the default N = 1 cfg2 run times after the headline (other_configs)')
+                         'training-defaults legs that the --full N = 1 cfg2 run times after the headline (other_configs)')
     ap.add_argument('--other-steps', type=int, default=10, help='timed steps of every other_configs leg (3 warm-up steps each)')
     ap.add_argument('--allreduce', default='flat', choices=['flat', 'bucketed', 'both'],
                     help='gradient exchange of the data-parallel mode (trainer cfg key allreduce_buckets).  both: the '
@@ -394,7 +406,12 @@ def parse_args(argv=None):
                     help='after the timed steps, write what the last timed step of the headline region returned to its '
                          'caller as DIR/<name>.npy (rank 0): loss.npy and params.npy, float32; parameters beyond '
                          'DUMP_PARAMS elements are a fixed, seeded sample.  The line lists the files as outputs_dumped')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:
+        args.no_cpu_baseline = args.no_alt = args.no_gemm_roofline = args.no_other_configs = True
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    return args
 
 
 def sample_flat(n):

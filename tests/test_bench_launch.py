@@ -118,10 +118,29 @@ def test_dump_outputs_are_the_last_timed_step(tmp_path):
         assert sorted(os.listdir(d)) == ['params.npy']
         assert json_lines(r.stdout)[-1]['outputs_dumped'] == {'params': list(params.shape)}
         return params
-    a, b = dump('a'), dump('b')
+    a, b = dump('a', '--full'), dump('b', '--full')
     assert a.dtype == np.float32 and a.size > 0 and np.array_equal(a, b)
     assert np.array_equal(a, dump('one_region', '--repeats', '1'))
     assert not np.array_equal(a, dump('four_steps', '--steps', '4', '--repeats', '1'))
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_times_the_headline_only():
+    """without --full a run times its K steps once and skips every leg that takes runs of its own; --full switches them
+    on (the K steps three times by default), and each --no-* option or --repeats still applies there"""
+    a = bench.parse_args(['--steps', '2'])
+    assert (a.full, a.repeats, a.no_alt, a.no_gemm_roofline, a.no_other_configs, a.no_cpu_baseline) == (False, 1, True, True, True, True)
+    a = bench.parse_args(['--full'])
+    assert (a.full, a.repeats, a.no_alt, a.no_gemm_roofline, a.no_other_configs, a.no_cpu_baseline) == (True, 3, False, False, False, False)
+    a = bench.parse_args(['--full', '--no-alt', '--repeats', '2'])
+    assert (a.repeats, a.no_alt, a.no_gemm_roofline) == (2, True, False)
+    for extra, n in (([], 1), (['--full'], 3)):
+        r = subprocess.run([sys.executable, STANDIN, '--steps', '2', '--warmup', '1'] + extra, env=clean_env(),
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json_lines(r.stdout)[-1]
+        check_line(line, 1, 2, 1)
+        assert len(line['ms_per_step_repeats']) == n and line['ms_per_step_repeats'][0] == line['ms_per_step']
 
 
 def test_dump_outputs_sample_and_limits(tmp_path):

@@ -42,7 +42,7 @@ def test_bench_two_rank_dry_run_on_one_gpu():
 
 def _two_rank_line(extra, with_cache=True):
     """python bench.py --gpus 2 --shrink ...: two REAL ranks on the one-GPU test box (they share the device, so the
-    group is gloo and the recurrence runs step-wise), 2 timed training steps, the whole JSON line"""
+    group is gloo and the recurrence runs step-wise), 2 timed training steps, the whole JSON line of a --full run"""
     import json
     import socket
     import time
@@ -59,7 +59,7 @@ def _two_rank_line(extra, with_cache=True):
     try:
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
         r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--shrink', '--steps', '2',
-                            '--warmup', '1', '--no-alt', '--no-gemm-roofline'] + extra, env=env, capture_output=True,
+                            '--warmup', '1', '--full', '--no-alt', '--no-gemm-roofline'] + extra, env=env, capture_output=True,
                            text=True, timeout=900)
     finally:
         if keep is None:
