@@ -69,29 +69,25 @@ def blstm(inputs, sequence_length, num_units, layer_norm=False, scope=None, out_
                                'was modified in place?)' % (worst, ops.value_bound(inputs)))
     out_pk = None
     if PACKED_COMPANIONS[0]:
-        where = (vs.current_scope(), scope or 'BLSTM', B, T, D, H)
         # input: the producer layer's kernel wrote it (ops.packed), if this layer's products read packed operands at all
         x_pk = ops.packed(inputs, 1) if x is inputs else None
         if x_pk is not None and plan.pk_bytes[0] and (x_pk[0].numel(), x_pk[1].numel()) == tuple(plan.pk_bytes[:2]):
             hip.blstm_set_companions(plan, x_pk=x_pk)
         # output, for the consumer behind `out_stack` stacked frames: only if that layer (same units, same arithmetic)
         # would read them
+        want_out = False
         if out_stack in (1, 2) and T % out_stack == 0 and plan.pk_bytes[3]:
             nxt = hip.BlstmPlan(B, T // out_stack, 2 * H * out_stack, H, T // out_stack, LSTM_MODE[0], GEMM_PRECISION[0], x_bound=1.0,
                                 fwd_only=not training, recurrent_precision=RECURRENT_PRECISION[0])
-            if nxt.pk_bytes[0] == plan.pk_bytes[3] and nxt.pk_bytes[1] == plan.pk_bytes[4]:
-                out_pk = (ops.resident_zeros(where + ('rows',), plan.pk_bytes[3], x.device, Tape.current),
-                          ops.resident_zeros(where + ('cols',), plan.pk_bytes[4], x.device, Tape.current))
-                hip.blstm_set_companions(plan, out_pk=out_pk)
-        if training and plan.pk_bytes[2]:
-            hip.blstm_set_companions(plan, hT_pk=ops.resident_zeros(where + ('hT',), plan.pk_bytes[2], x.device, Tape.current))
-        # what the recurrent kernel does not write itself is packed where it is needed, as before (no companion)
-        mask = hip.blstm_emits_packed(plan)
-        if out_pk is not None and (mask & 3) != 3:
-            hip.blstm_drop_companions(plan, out_pk=True)
-            out_pk = None
-        if not mask & 4:
-            hip.blstm_drop_companions(plan, hT_pk=True)
+            want_out = nxt.pk_bytes[0] == plan.pk_bytes[3] and nxt.pk_bytes[1] == plan.pk_bytes[4]
+        # only what the recurrent kernel writes itself is attached; the rest is packed where it is needed, as before.  A
+        # buffer stays busy while its holders (this plan, `out`, the consumer's plan) are alive (ops.BufferPool)
+        mask = hip.blstm_emits_packed(plan, out_pk=want_out, hT_pk=training and plan.pk_bytes[2] > 0)
+
+        def acquire(role, i):
+            return ops.companions.acquire((vs.current_scope(), scope or 'BLSTM', role), plan.pk_bytes[i], x.device, (B, T, D, H))
+        out_pk = (acquire('rows', 3), acquire('cols', 4)) if mask & 3 == 3 else None
+        hip.blstm_set_companions(plan, out_pk=out_pk, hT_pk=acquire('hT', 2) if mask & 4 else None)
     out = torch.empty((B, T, 2 * H), dtype=torch.float32, device=x.device)
     reserve = torch.empty(plan.reserve_bytes, dtype=torch.uint8, device=x.device)
     hip.blstm_fwd(plan, x, lens.dev, kf.data, bf.data, kb.data, bb.data, out, reserve)

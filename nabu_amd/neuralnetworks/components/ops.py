@@ -7,64 +7,68 @@ from nabu_amd import ops as hip
 from nabu_amd.autodiff import record, requires_grad, SeqLen
 
 
-# A-priori magnitude bounds of tensors on the path: id(tensor) -> (weak reference, bound).  layer.blstm records
-# |out| <= 1 (o tanh c), the plumbing ops below carry the bound along, and the next layer hands it to the C ABI
+# A-priori magnitude bound of a tensor on the path, an attribute of the tensor OBJECT: layer.blstm records |out| <= 1
+# (o tanh c), the plumbing ops below carry the bound along, and the next layer hands it to the C ABI
 # (nabu_blstm_desc.x_bound), whose f16x3 operand packs then take their row scales from it instead of measuring x.
-_BOUNDS = {}
-
-
-# The bound is a promise about the tensor OBJECT: tensors that carry one must not be modified in place (a stale bound makes
-# the f16x3 packs overflow fp16 silently).  NABU_CHECK_X_BOUND=1 (layer.CHECK_X_BOUND) measures and asserts at every layer.
+# The bound is a promise: tensors that carry one must not be modified in place (a stale bound makes the f16x3 packs
+# overflow fp16 silently).  NABU_CHECK_X_BOUND=1 (layer.CHECK_X_BOUND) measures and asserts at every layer.
 def set_value_bound(tensor, bound):
-    key = id(tensor)
-    _BOUNDS[key] = (weakref.ref(tensor, lambda _r, k=key: _BOUNDS.pop(k, None)), float(bound))
+    tensor._nabu_value_bound = float(bound)
 
 
 def value_bound(tensor):
     """the recorded bound on |tensor|, 0.0 when nothing is known"""
-    e = _BOUNDS.get(id(tensor))
-    return e[1] if e is not None and e[0]() is tensor else 0.0
+    return getattr(tensor, '_nabu_value_bound', 0.0)
 
 
-# PACKED COMPANIONS of tensors on the path (include/nabu_hip.h, nabu_blstm_desc ABI version 3): id(tensor) -> (weak reference,
-# stack, (rows, cols)) — layer.blstm asks the forward recurrent kernel to write its output ALSO as the next layer's
-# f16x3 operands (for the frame stacking `stack` that pyramid_stack is about to apply), and the next layer.blstm hands
-# them to the C ABI instead of packing its input.  Only the stacking view carries a companion along; any op that makes a
-# new tensor (dropout, noise) drops it, and the next layer packs for itself as before.
-_PACKED = {}
-
-
+# PACKED COMPANION of a tensor on the path (include/nabu_hip.h, nabu_blstm_desc ABI version 3), an attribute of the
+# tensor object like its bound: layer.blstm asks the forward recurrent kernel to write its output ALSO as the next
+# layer's f16x3 operands (rows, cols) for the frame stacking `stack` that pyramid_stack is about to apply, and the next
+# layer.blstm hands them to the C ABI instead of packing its input.  Only the stacking view carries a companion along;
+# any op that makes a new tensor (dropout, noise) drops it, and the next layer packs for itself as before.
 def set_packed(tensor, stack, bufs):
-    key = id(tensor)
-    _PACKED[key] = (weakref.ref(tensor, lambda _r, k=key: _PACKED.pop(k, None)), int(stack), bufs)
+    tensor._nabu_packed = (int(stack), bufs)
 
 
 def packed(tensor, stack):
     """the (rows, cols) companion of `tensor` written for frame stacking `stack`, or None"""
-    e = _PACKED.get(id(tensor))
-    return e[2] if e is not None and e[0]() is tensor and e[1] == stack else None
+    e = getattr(tensor, '_nabu_packed', None)
+    return e[1] if e is not None and e[0] == stack else None
 
 
-# Zero-filled device buffers that live as long as the process, keyed by their user (a layer's scope and shape): a
-# companion is rewritten in full by every forward call and its padding stays zero, so the same buffer serves step after
-# step.  `holder` = the Tape whose backward pass still reads the content (None: nobody behind this call): a forward pass
-# that finds the buffer held by ANOTHER tape whose backward pass has not run yet (two forward passes of one layer before
-# the first backward) gets a buffer of its own instead of overwriting it.
-_RESIDENT = {}
+class BufferPool(object):
+    """Zero-filled uint8 device buffers reused call after call by one user, key = (a layer's scope, role): a companion
+    is rewritten in full by every forward call of one shape and its padding stays zero.  acquire() hands out a fresh
+    view of a slot's buffer, and the slot stays busy exactly as long as that view object is alive: whoever still reads
+    the buffer (a pending backward pass through its plan, a consumer's plan, an output carrying it as its packed()
+    companion) holds the view itself, never a slice of it.  So at most (live holders + 1) buffers per key."""
+
+    def __init__(self):
+        self._slots = {}        # key -> [[buffer, layout, weak reference to the view handed out]]
+
+    def acquire(self, key, nbytes, device, layout=()):
+        """a buffer of `nbytes` zero-filled for `layout` (what, beside its size, decides which bytes a user writes):
+        a free slot of the same size, device and layout, else a new one, after the free slots of `key` are freed"""
+        import torch
+        slots = self._slots.setdefault(key, [])
+        for slot in slots:
+            buf, lay, ref = slot
+            if ref() is None and buf.numel() == nbytes and buf.device == torch.device(device) and lay == layout:
+                view = buf.view(-1)
+                slot[2] = weakref.ref(view)
+                return view
+        slots[:] = [s for s in slots if s[2]() is not None]
+        buf = torch.zeros(int(nbytes), dtype=torch.uint8, device=device)
+        view = buf.view(-1)
+        slots.append([buf, layout, weakref.ref(view)])
+        return view
+
+    def held_bytes(self, role=None):
+        """bytes held (busy or free) in the slots whose key ends in `role`, or in all of them"""
+        return sum(s[0].numel() for key, slots in self._slots.items() if role is None or key[-1] == role for s in slots)
 
 
-def resident_zeros(key, nbytes, device, holder=None):
-    import torch
-    slots = _RESIDENT.setdefault(key, [])
-    for slot in slots:
-        buf, ref = slot
-        h = ref() if ref is not None else None
-        if (h is None or h is holder or not h.ops) and buf.numel() == nbytes and buf.device == device:
-            slot[1] = weakref.ref(holder) if holder is not None else None
-            return buf
-    buf = torch.zeros(int(nbytes), dtype=torch.uint8, device=device)
-    slots.append([buf, weakref.ref(holder) if holder is not None else None])
-    return buf
+companions = BufferPool()
 
 
 def pyramid_stack(inputs, sequence_lengths, numsteps, axis=2, scope=None):

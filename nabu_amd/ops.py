@@ -234,17 +234,20 @@ def blstm_set_companions(plan, x_pk=None, out_pk=None, hT_pk=None):
     plan._keep += [t for t in (x_pk or ()) + (out_pk or ()) + ((hT_pk,) if hT_pk is not None else ())]
 
 
-def blstm_emits_packed(plan):
-    """which companions attached to `plan` nabu_blstm_fwd's recurrent kernel writes itself: bit 0 rows, 1 transposed, 2 h^T"""
-    return int(_hip.lib().nabu_blstm_emits_packed(ctypes.byref(plan.desc)))
-
-
-def blstm_drop_companions(plan, out_pk=False, hT_pk=False):
+def blstm_emits_packed(plan, out_pk=False, hT_pk=False):
+    """which companions nabu_blstm_fwd's recurrent kernel writes itself (bit 0 rows, 1 transposed, 2 h^T): of those
+    attached to `plan`, plus the out_pk / hT_pk ones it would name.  The query reads the descriptor's pointers for null
+    only, so a would-be companion is named by a placeholder for its duration: the caller allocates only what is written."""
     d = plan.desc
+    attached = d.out_pk_rows, d.out_pk_cols, d.hT_pk
     if out_pk:
-        d.out_pk_rows, d.out_pk_cols = None, None
+        d.out_pk_rows, d.out_pk_cols = d.out_pk_rows or 1, d.out_pk_cols or 1
     if hT_pk:
-        d.hT_pk = None
+        d.hT_pk = d.hT_pk or 1
+    try:
+        return int(_hip.lib().nabu_blstm_emits_packed(ctypes.byref(d)))
+    finally:
+        d.out_pk_rows, d.out_pk_cols, d.hT_pk = attached
 
 
 def blstm_fwd(plan, x, lens_dev, k_fw, b_fw, k_bw, b_bw, out, reserve):

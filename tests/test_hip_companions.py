@@ -4,6 +4,7 @@ operand.  What the kernel writes must be, bit for bit, what the pack kernels mak
 (reference semantics: layer.blstm + ops.pyramid_stack, components/layer.py:8-94, components/ops.py:6-60 — the packs are
 operand FORMATS of the dense products, not values of the reference graph), and a model that uses them must train like
 one that packs for itself."""
+import contextlib
 import ctypes
 
 import numpy as np
@@ -151,7 +152,7 @@ def test_all_three_companions_out_of_the_kernel_in_their_own_process():
         pytest.skip('already a process with the switch set')
     e = dict(os.environ)
     e['NABU_PERSIST_EMIT_MASK'] = '7'
-    r = subprocess.run([sys.executable, '-m', 'pytest', os.path.abspath(__file__), '-q', '-x', '-k', 'bit_exactly or step_is_the_same'],
+    r = subprocess.run([sys.executable, '-m', 'pytest', os.path.abspath(__file__), '-q', '-x', '-k', 'bit_exactly or step_is_the_same or held_without_a_tape'],
                        env=e, capture_output=True, text=True, timeout=900, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert r.returncode == 0 and ' passed' in r.stdout, (r.stdout[-3000:], r.stderr[-2000:])
     # ... and the switch at 4, taken literally: h^T also out of the first layer's launch (the default leaves that one to
@@ -160,6 +161,109 @@ def test_all_three_companions_out_of_the_kernel_in_their_own_process():
     r = subprocess.run([sys.executable, '-m', 'pytest', os.path.abspath(__file__), '-q', '-x', '-k', 'bit_exactly and 24-96-40'],
                        env=e, capture_output=True, text=True, timeout=900, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert r.returncode == 0 and '1 passed' in r.stdout, (r.stdout[-3000:], r.stderr[-2000:])
+
+
+@contextlib.contextmanager
+def _f16x3_layers(companions):
+    """components.layer on f16x3 operands (as the encoders set it), with the packed companions on or off"""
+    from nabu_amd.neuralnetworks.components import layer
+    was = layer.PACKED_COMPANIONS[0], layer.GEMM_PRECISION[0]
+    layer.PACKED_COMPANIONS[0], layer.GEMM_PRECISION[0] = companions, 'f16x3'
+    try:
+        yield layer
+    finally:
+        layer.PACKED_COMPANIONS[0], layer.GEMM_PRECISION[0] = was
+
+
+def test_one_layer_called_twice_under_one_tape_keeps_each_calls_h_operand():
+    """the same layer applied to two inputs under one tape (shared weights, an encoder applied twice): the recurrent
+    kernel writes h^T for both calls, and the first call's deferred weight gradient must still read its own h^T after
+    the second forward pass — loss and gradients as with the companions off"""
+    from nabu_amd import ops, variables as vs
+    from nabu_amd.autodiff import Tape, record
+    B, T, D, H = 32, 64, 256, 128
+    lens = np.random.default_rng(3).integers(1, T + 1, B)
+    lens[1] = T
+    plan = ops.BlstmPlan(B, T, D, H, T, ops.LSTM_AUTO, 'f16x3')
+    ops.blstm_set_companions(plan, hT_pk=torch.zeros(plan.pk_bytes[2], dtype=torch.uint8, device=DEV))
+    assert ops.blstm_emits_packed(plan) & 4                 # the layer's kernel writes h^T itself
+    xs = [_case(B, T, D, H, lens, seed=s)[1] for s in (11, 12)]
+    gen = torch.Generator(device=DEV).manual_seed(13)
+    ws = [torch.randn((B, T, 2 * H), generator=gen, device=DEV) for _ in xs]
+
+    def run(on):
+        store = vs.VariableStore(seed=3)
+        with _f16x3_layers(on) as layer, vs.as_default(store):
+            with Tape() as tape:
+                outs = [layer.blstm(x, lens, H, scope='shared') for x in xs]
+                loss = sum((o * w).sum() for o, w in zip(outs, ws))
+                record(outs, [loss], lambda g: list(ws))
+            tape.backward(loss)
+        return float(loss.item()), {v.name: v.grad.cpu().numpy() for v in store.variables()}
+    l_on, g_on = run(True)
+    l_off, g_off = run(False)
+    assert abs(l_on - l_off) <= 2e-6 * abs(l_off), (l_on, l_off)
+    for k in g_on:
+        assert np.abs(g_on[k] - g_off[k]).max() <= 1e-5 * np.abs(g_off[k]).max() + 1e-9, k
+
+
+def test_outputs_held_without_a_tape_keep_their_own_companions():
+    """inference: two outputs of one pyramidal layer are held and then the first is consumed — the next layer reads the
+    first output's packs (written by the kernel under NABU_PERSIST_EMIT_MASK bits 0 and 1), as with the companions off"""
+    import os
+    from nabu_amd import variables as vs
+    from nabu_amd.neuralnetworks.components import ops
+    B, T, D, H = 32, 128, 256, 128
+    lens = np.full(B, T)
+    xs = [_case(B, T, D, H, lens, seed=s)[1] for s in (21, 22)]
+
+    def run(on):
+        with _f16x3_layers(on) as layer, vs.as_default(vs.VariableStore(seed=4)):
+            held = [layer.pblstm(x, lens, H, scope='p') for x in xs]
+            if on and int(os.environ.get('NABU_PERSIST_EMIT_MASK', '4')) & 3 == 3:
+                pk = [ops.packed(o, 1) for o, _ in held]
+                assert pk[0] is not None and pk[1] is not None and pk[0][0].data_ptr() != pk[1][0].data_ptr()
+            return layer.blstm(held[0][0], held[0][1], H, scope='next')
+    assert (run(True) - run(False)).abs().max().item() <= 1e-5
+
+
+def test_variable_length_training_holds_one_step_of_companions(monkeypatch):
+    """real batches are padded to their longest member, so T changes from step to step: what the companion pool holds
+    after a step is that step's companions alone, and device memory does not ratchet up with every new T"""
+    import os
+    from nabu_amd import recipes, ops as hip
+    from nabu_amd.neuralnetworks.components import ops
+    from nabu_amd.neuralnetworks.trainers import trainer_factory
+    from nabu_amd.processing.synthetic import SyntheticData
+    monkeypatch.setattr(ops, 'companions', ops.BufferPool())
+    default = 'NABU_PERSIST_EMIT_MASK' not in os.environ
+    B, H, Ts = 32, 128, (512, 384, 448, 320, 480, 512)
+    mc, tc, ec = recipes.load_recipe('cfg2_listener_ctc', **{'encoder.num_units': H, 'trainer.batch_size': B})
+    tr = None
+    mem, steps = [], []
+    for i, T in enumerate(Ts):
+        data = SyntheticData(B, T, 40, min_frames=T // 2, min_labels=2, max_labels=6, time_reduction=8, seed=40 + i)
+        if tr is None:
+            tr = trainer_factory.factory('standard')(conf=tc, dataconf=data, modelconf=mc, evaluatorconf=ec, expdir=None,
+                                                     server=None, task_index=0)
+        raw = data.batch(0)
+        raw['input_seq_length']['features'][0] = T        # the longest utterance fills the batch (as a padded batch does)
+        assert np.isfinite(float(tr.step(tr.to_device(raw)).item()))
+        torch.cuda.synchronize()
+        mem.append(torch.cuda.memory_allocated())
+        # one step's companions by default: h^T of layers 1..3 (input 4H wide, T / 2^l frames) where their kernel writes
+        # it; none of the first layer, no rows / cols
+        plans = [hip.BlstmPlan(B, T >> l, 4 * H, H, T >> l, hip.LSTM_AUTO, 'f16x3') for l in (1, 2, 3)]
+        steps.append(sum(p.pk_bytes[2] for p in plans if hip.blstm_emits_packed(p, hT_pk=True) & 4))
+        if default:
+            # this step's, and at most one idle buffer of a layer that took none this time (fewer than 2048 frames):
+            # never more than the step of the longest T (the first) holds
+            assert steps[-1] <= ops.companions.held_bytes() == ops.companions.held_bytes('hT') <= steps[0]
+            assert ops.companions.held_bytes('rows') == 0 and ops.companions.held_bytes('cols') == 0
+    if default:
+        assert steps[0] > 0 and ops.companions.held_bytes() == steps[-1] == steps[0]     # the same T again: the same buffers
+    assert max(mem[1:]) <= mem[0] + (1 << 20), mem           # T = 512 first: no later step needs more
+    assert abs(mem[-1] - mem[0]) <= 1 << 20, mem              # the same T again: the same memory
 
 
 @pytest.mark.parametrize('size', [32, 44])
