@@ -592,6 +592,54 @@ int nabu_layer_norm_bwd(int B, int N, int F, const float *x, const float *gamma,
                         float *dbeta_part, nabu_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * DNN encoder and the Kaldi-hybrid recipe (DNN/WSJ): models/ed_encoders/dnn.py:30-66,
+ * components/ops.py:62-118,147-175 (stack_seq, unstack_seq, get_indices), decoders/alignment_decoder.py:32-58.
+ * Frame rows of the stacked matrices lie in batch-major order: utterance b starts at row off_b = sum_{i<b} len[i],
+ * computed on the device from len (the host never synchronises to learn N = sum len; it knows N from its copy).
+ *
+ * nabu_splice_stack_f32: splice + stack_seq in one pass.  With c = context and c' = 2c-1,
+ *   out[off_b + t, j*F + f] = x[b, t + s_j, f] for t < len[b], s = (0, +1, -1, +2, -2, ..., +(c-1), -(c-1)),
+ *   where a source frame outside [0, T) of the PADDED batch tensor reads 0 (dnn.py:36-44 shifts the padded tensor:
+ *   frame t >= len[b] - s of utterance b reads whatever x holds there, zeros in this project's pipelines);
+ *   out[r, c'F .. ld) = 0.  x [B,T,F] contiguous; out [N, ld], 16-byte aligned, ld >= c'F, ld % 4 == 0.
+ * nabu_unstack_rows_f32: unstack_seq: out[b,t,:] = rows[off_b + t, :] for t < len[b], 0 for len[b] <= t < Tm
+ *   (Tm = max len, not the input's T).  rows [N,H], out [B,Tm,H].
+ * nabu_stack_rows_f32: its adjoint: rows[off_b + t, :] = g[b, t, :] for t < len[b].  g [B,Tm,H], rows [N,H].
+ *   (both: lengths are clamped to [0, Tm]; float4 moves when H % 4 == 0 and both operands are 16-byte aligned)
+ * nabu_rows_relu_ln_fwd / _bwd: tf.contrib.layers.fully_connected's ReLU followed by tf.contrib.layers.layer_norm
+ *   on a 2-D input — moments PER ROW over F (unlike nabu_layer_norm_fwd's [B,T,F] semantics above):
+ *     r = max(z, 0); y = (r - mean) * rstd * gamma + beta, rstd = 1/sqrt(var + eps) (var biased)
+ *   fwd reads z once and writes y, mean[N], rstd[N] (of r); bwd writes dz (ReLU mask and layer-norm adjoint) and
+ *   the partial sums dgamma_part/dbeta_part [P, F], P = nabu_rows_relu_ln_bwd_parts(N) (reduce them with
+ *   nabu_colsum_f32; deterministic).  One wave per row.  F % 4 == 0 and F <= 4096, 16-byte aligned operands;
+ *   NABU_EUNSUP for another F (the caller then runs nabu_relu_f32 + nabu_layer_norm_fwd(B = N, N = F, F), the same
+ *   semantics in more launches).
+ * nabu_xent_wide_loss_grad: nabu_xent_loss_grad's contract (same loss, same dlogits) for wide class counts (the
+ *   3100 HMM states of DNN/WSJ): one wave per frame, an online max/sum-exp pass over the row and a second pass that
+ *   writes dlogits while the row is in cache; rows t >= logit_len[b] are zero.  The per-frame terms go to ws and
+ *   loss[b] is their fixed-order sum (a second, small launch): deterministic, no atomics.  Any C >= 1, any
+ *   alignment (float4 body between scalar head and tail when logits and dlogits share their 16-byte phase).
+ *   ws >= nabu_xent_wide_ws_bytes(B, L).
+ * nabu_log_softmax_prior_f32: AlignmentDecoder's pseudo log-likelihoods: out[b,t,:] = x - logsumexp(x[b,t,:]) -
+ *   logprior[:] for t < len[b], 0 elsewhere; x, out [B,T,C], logprior [C].  Same row machinery as above. */
+int nabu_splice_stack_f32(int B, int T, int F, int context, const float *x, const int32_t *len, float *out, int ld,
+                          nabu_stream_t stream);
+int nabu_unstack_rows_f32(int B, int Tm, int H, const int32_t *len, const float *rows, float *out,
+                          nabu_stream_t stream);
+int nabu_stack_rows_f32(int B, int Tm, int H, const int32_t *len, const float *g, float *rows, nabu_stream_t stream);
+int nabu_rows_relu_ln_fwd(int N, int F, const float *z, const float *gamma, const float *beta, float eps, float *y,
+                          float *mean, float *rstd, nabu_stream_t stream);
+int nabu_rows_relu_ln_bwd_parts(int N);
+int nabu_rows_relu_ln_bwd(int N, int F, const float *z, const float *dy, const float *gamma, const float *mean,
+                          const float *rstd, float *dz, float *dgamma_part, float *dbeta_part, nabu_stream_t stream);
+size_t nabu_xent_wide_ws_bytes(int B, int L);
+int nabu_xent_wide_loss_grad(int B, int L, int C, int ldt, const float *logits, const int32_t *targets,
+                             const int32_t *logit_len, const int32_t *target_len, float grad_scale, float *loss,
+                             float *dlogits, void *ws, size_t ws_bytes, nabu_stream_t stream);
+int nabu_log_softmax_prior_f32(int B, int T, int C, const float *x, const int32_t *len, const float *logprior,
+                               float *out, nabu_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Inference decoders — nabu/neuralnetworks/decoders.
  *
  * nabu_ctc_beam_search: CTCDecoder.__call__ (decoders/ctc_decoder.py:44-68) =

@@ -119,6 +119,15 @@ SIGNATURES = {
     'nabu_layer_norm_fwd': (_i, [_i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     'nabu_crc32c_host': (_c.c_uint32, [_c.c_char_p, _sz, _c.c_uint32]),
     'nabu_layer_norm_bwd': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'nabu_splice_stack_f32': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    'nabu_unstack_rows_f32': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+    'nabu_stack_rows_f32': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+    'nabu_rows_relu_ln_fwd': (_i, [_i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    'nabu_rows_relu_ln_bwd_parts': (_i, [_i]),
+    'nabu_rows_relu_ln_bwd': (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'nabu_xent_wide_ws_bytes': (_sz, [_i, _i]),
+    'nabu_xent_wide_loss_grad': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _sz, _vp]),
+    'nabu_log_softmax_prior_f32': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

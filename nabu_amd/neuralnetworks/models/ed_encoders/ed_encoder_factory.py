@@ -5,4 +5,5 @@ _PKG = 'nabu_amd.neuralnetworks.models.ed_encoders.'
 factory = Registry('encoder', {
     'listener': _PKG + 'listener:Listener',
     'dblstm': _PKG + 'dblstm:DBLSTM',
-}, outside=('dummy_encoder', 'dnn', 'hotstart_encoder'))
+    'dnn': _PKG + 'dnn:DNN',
+}, outside=('dummy_encoder', 'hotstart_encoder'))

@@ -12,6 +12,16 @@ from nabu_amd.neuralnetworks.components import ops
 # device status words of the CTC kernels launched since the last check
 pending_status = []
 
+# class counts from which the cross-entropy losses run nabu_xent_wide_loss_grad (one wave per frame) instead of
+# nabu_xent_loss_grad (one thread per frame, written for a few dozen classes): the 3100 HMM states of DNN/WSJ
+WIDE_XENT_MIN_CLASSES = 1024
+
+
+def _xent(logits, targets, logit_len_dev, target_len_dev, grad_scale):
+    '''the cross-entropy kernel for the class count of `logits`'''
+    fn = hip.xent_wide_loss_grad if logits.shape[-1] >= WIDE_XENT_MIN_CLASSES else hip.xent_loss_grad
+    return fn(logits, targets, logit_len_dev, target_len_dev, grad_scale)
+
 
 def factory(loss_function):
     '''get a callable loss(targets, logits, logit_seq_length, target_seq_length)
@@ -72,7 +82,7 @@ def average_cross_entropy(targets, logits, logit_seq_length, target_seq_length):
         lg = logits[t]
         B = lg.shape[0]
         lsl, tsl = SeqLen.wrap(logit_seq_length[t], lg.device), SeqLen.wrap(target_seq_length[t], lg.device)
-        per_utt, dlogits = hip.xent_loss_grad(lg.contiguous(), _labels(targets[t]), lsl.dev, tsl.dev, 1.0 / B)
+        per_utt, dlogits = _xent(lg.contiguous(), _labels(targets[t]), lsl.dev, tsl.dev, 1.0 / B)
         loss = hip.sum_(per_utt, 1.0 / B)
         record([lg], [loss], lambda g, d=dlogits: [d])
         losses.append(loss)
@@ -89,7 +99,7 @@ def sum_cross_entropy(targets, logits, logit_seq_length, target_seq_length):
         B = lg.shape[0]
         tsl = SeqLen.wrap(target_seq_length[t], lg.device)
         ones = torch.ones_like(tsl.dev)
-        per_utt, dlogits = hip.xent_loss_grad(lg.contiguous(), _labels(targets[t]), tsl.dev, ones, 1.0 / B)
+        per_utt, dlogits = _xent(lg.contiguous(), _labels(targets[t]), tsl.dev, ones, 1.0 / B)
         loss = hip.sum_(per_utt, 1.0 / B)
         record([lg], [loss], lambda g, d=dlogits: [d])
         losses.append(loss)

@@ -166,7 +166,14 @@ class Trainer(object, metaclass=ABCMeta):
             return d
         if hasattr(d, 'has_section') and d.has_section('synthetic'):
             from nabu_amd.processing.synthetic import SyntheticData
-            kw = {k: (v == 'True' if v in ('True', 'False') else int(v)) for k, v in d.items('synthetic')}
+            def value(v):
+                if v in ('True', 'False'):
+                    return v == 'True'
+                try:
+                    return int(v)
+                except ValueError:
+                    return v                   # names (input_name, target_name = alignments)
+            kw = {k: value(v) for k, v in d.items('synthetic')}
             kw.setdefault('batch_size', int(self.conf['batch_size']))
             return SyntheticData(**kw)
         # the reference's on-disk data (reference trainer.py:289-340): the trainer conf links the model's

@@ -9,6 +9,7 @@ from . import _hip
 from ._hip import ptr, stream, check, Workspace
 
 LSTM_AUTO, LSTM_STEPWISE, LSTM_PERSISTENT = 0, 1, 2
+NABU_EUNSUP = -2       # include/nabu_hip.h: shape not supported by the requested kernel
 
 
 def _f32(t, name):
@@ -607,6 +608,87 @@ def layer_norm_bwd(x, gamma, dy, mean, rstd):
     check(_hip.lib().nabu_layer_norm_bwd(B, N, F, ptr(x), ptr(gamma), ptr(dy), ptr(mean), ptr(rstd), ptr(dx),
                                          ptr(dgp), ptr(dbp), stream()), 'nabu_layer_norm_bwd')
     return dx, dgp, dbp
+
+
+def splice_stack(x, len_dev, context, N, ld):
+    """[N, ld] = the spliced frames (0, +1, -1, ..., +-(context-1)) of x [B,T,F] stacked batch-major, zero columns
+    from (2 context - 1) F on (nabu_splice_stack_f32); N = sum of the lengths (the caller's host copy)"""
+    B, T, F = x.shape
+    out = torch.empty((N, ld), dtype=torch.float32, device=x.device)
+    if N:
+        check(_hip.lib().nabu_splice_stack_f32(B, T, F, int(context), ptr(_f32(x, 'x')), ptr(len_dev), ptr(out), ld,
+                                               stream()), 'nabu_splice_stack_f32')
+    return out
+
+
+def unstack_rows(rows, len_dev, B, Tm):
+    """rows [N,H] -> [B,Tm,H], zero past each length (nabu_unstack_rows_f32)"""
+    H = rows.shape[1]
+    out = torch.empty((B, Tm, H), dtype=torch.float32, device=rows.device)
+    check(_hip.lib().nabu_unstack_rows_f32(B, Tm, H, ptr(len_dev), ptr(_f32(rows, 'rows')), ptr(out), stream()),
+          'nabu_unstack_rows_f32')
+    return out
+
+
+def stack_rows(g, len_dev, N):
+    """g [B,Tm,H] -> rows [N,H] of the valid frames (nabu_stack_rows_f32, the adjoint of unstack_rows)"""
+    B, Tm, H = g.shape
+    rows = torch.empty((N, H), dtype=torch.float32, device=g.device)
+    if N:
+        check(_hip.lib().nabu_stack_rows_f32(B, Tm, H, ptr(len_dev), ptr(_f32(g, 'g')), ptr(rows), stream()),
+              'nabu_stack_rows_f32')
+    return rows
+
+
+def rows_relu_ln_fwd(z, gamma, beta, eps=1e-12):
+    """(y, mean, rstd) of relu then per-row layer norm of z [N,F] (nabu_rows_relu_ln_fwd), or None when the kernel
+    does not take F (NABU_EUNSUP: the caller composes relu + layer_norm_fwd)"""
+    N, F = z.shape
+    y = torch.empty_like(z)
+    mean = torch.empty(N, dtype=torch.float32, device=z.device)
+    rstd = torch.empty(N, dtype=torch.float32, device=z.device)
+    code = _hip.lib().nabu_rows_relu_ln_fwd(N, F, ptr(_f32(z, 'z')), ptr(gamma), ptr(beta), eps, ptr(y), ptr(mean),
+                                            ptr(rstd), stream())
+    if code == NABU_EUNSUP:
+        return None
+    check(code, 'nabu_rows_relu_ln_fwd')
+    return y, mean, rstd
+
+
+def rows_relu_ln_bwd(z, dy, gamma, mean, rstd):
+    """(dz, dgamma_part [P,F], dbeta_part [P,F]) of rows_relu_ln_fwd (reduce the partials with colsum)"""
+    N, F = z.shape
+    L = _hip.lib()
+    P = L.nabu_rows_relu_ln_bwd_parts(N)
+    dz = torch.empty_like(z)
+    dgp = torch.empty((P, F), dtype=torch.float32, device=z.device)
+    dbp = torch.empty((P, F), dtype=torch.float32, device=z.device)
+    check(L.nabu_rows_relu_ln_bwd(N, F, ptr(z), ptr(_f32(dy, 'dy')), ptr(gamma), ptr(mean), ptr(rstd), ptr(dz),
+                                  ptr(dgp), ptr(dbp), stream()), 'nabu_rows_relu_ln_bwd')
+    return dz, dgp, dbp
+
+
+def xent_wide_loss_grad(logits, targets_dev, logit_len_dev, target_len_dev, grad_scale):
+    """xent_loss_grad's contract on the wide-class kernel (nabu_xent_wide_loss_grad): (loss [B], dlogits [B,L,C])"""
+    B, L, C = logits.shape
+    lib = _hip.lib()
+    loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty_like(logits)
+    ws_bytes = lib.nabu_xent_wide_ws_bytes(B, L)
+    ws = Workspace.get(ws_bytes, logits.device, 'xent_wide')
+    check(lib.nabu_xent_wide_loss_grad(B, L, C, targets_dev.shape[1], ptr(_f32(logits, 'logits')), ptr(targets_dev),
+                                       ptr(logit_len_dev), ptr(target_len_dev), grad_scale, ptr(loss), ptr(dlogits),
+                                       ptr(ws), ws_bytes, stream()), 'nabu_xent_wide_loss_grad')
+    return loss, dlogits
+
+
+def log_softmax_prior(x, len_dev, logprior):
+    """x - logsumexp(x) - logprior over the last axis of x [B,T,C] for t < len[b], 0 elsewhere"""
+    B, T, C = x.shape
+    out = torch.empty_like(x)
+    check(_hip.lib().nabu_log_softmax_prior_f32(B, T, C, ptr(_f32(x, 'x')), ptr(len_dev), ptr(logprior), ptr(out),
+                                                stream()), 'nabu_log_softmax_prior_f32')
+    return out
 
 
 def ceil_div_i32(x, d):

@@ -8,6 +8,11 @@ audio_feature_reader.py:64-78, string_reader.py:76-105, string_reader_eos.py:82-
                                 (string_eos targets carry EOS = C-1 at position len-1)
   target_seq_length['text']     [B] int32
 
+With frame_targets=True (frame-level alignments, the Kaldi-hybrid recipe) the targets are instead
+  targets[target_name]            [B,T_max] int32 labels U{0..num_labels-1}, zero padded past the length
+  target_seq_length[target_name]  [B] int32 = the input length
+drawn from the same target stream k = 2.
+
 Generator: numpy PCG64, independent streams per tensor
 default_rng([seed, step, k]) with k = 0 lengths, 1 features, 2 targets, so a
 batch is a pure function of (seed, step)."""
@@ -17,7 +22,7 @@ import numpy as np
 class SyntheticData(object):
     def __init__(self, batch_size, max_frames, feature_dim, num_labels=39, min_frames=None,
                  min_labels=10, max_labels=40, eos=False, time_reduction=1, seed=1234,
-                 batches_per_epoch=100, input_name='features', target_name='text'):
+                 batches_per_epoch=100, input_name='features', target_name='text', frame_targets=False):
         self.B, self.T, self.D = int(batch_size), int(max_frames), int(feature_dim)
         self.num_labels = int(num_labels)
         self.min_frames = self.T if min_frames is None else int(min_frames)
@@ -27,6 +32,7 @@ class SyntheticData(object):
         self.seed = int(seed)
         self.batches_per_epoch = int(batches_per_epoch)
         self.input_name, self.target_name = input_name, target_name
+        self.frame_targets = bool(frame_targets)
 
     def num_batches(self):
         return self.batches_per_epoch
@@ -36,7 +42,7 @@ class SyntheticData(object):
         sections of the reference's database.conf (evaluators/evaluator.py:37-60)'''
         v = SyntheticData(self.B if batch_size is None else batch_size, self.T, self.D, self.num_labels,
                           self.min_frames, self.min_labels, self.max_labels, self.eos, self.time_reduction,
-                          self.seed + 1000003, numbatches, self.input_name, self.target_name)
+                          self.seed + 1000003, numbatches, self.input_name, self.target_name, self.frame_targets)
         return v
 
     def batch(self, step):
@@ -48,6 +54,11 @@ class SyntheticData(object):
         lens[0] = T                                       # at least one full-length utterance
         feats = r_feat.standard_normal((B, T, D), dtype=np.float32)
         feats *= (np.arange(T)[None, :, None] < lens[:, None, None])
+        if self.frame_targets:
+            targets = r_tgt.integers(0, self.num_labels, (B, T)).astype(np.int32)
+            targets *= (np.arange(T)[None, :] < lens[:, None])
+            return dict(inputs={self.input_name: feats}, input_seq_length={self.input_name: lens},
+                        targets={self.target_name: targets}, target_seq_length={self.target_name: lens.copy()})
         Lcap = self.max_labels + (1 if self.eos else 0)
         targets = np.zeros((B, Lcap), np.int32)
         tlen = np.zeros(B, np.int32)

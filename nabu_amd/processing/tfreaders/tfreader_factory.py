@@ -7,4 +7,5 @@ factory = Registry('data', {
     'audio_feature': _PKG + 'audio_feature_reader:AudioFeatureReader',
     'string': _PKG + 'string_reader:StringReader',
     'string_eos': _PKG + 'string_reader_eos:StringReaderEOS',
-}, outside=('binary', 'alignment'), undefined='unknown %s type: %s')
+    'alignment': _PKG + 'alignment_reader:AlignmentReader',
+}, outside=('binary',), undefined='unknown %s type: %s')

@@ -5,4 +5,5 @@ _PKG = 'nabu_amd.processing.tfwriters.'
 factory = Registry('writer', {
     'array': _PKG + 'array_writer:ArrayWriter',
     'string': _PKG + 'string_writer:StringWriter',
-}, outside=('binary', 'alignment'), undefined='unknown %s type: %s')
+    'alignment': _PKG + 'alignment_writer:AlignmentWriter',
+}, outside=('binary',), undefined='unknown %s type: %s')
