@@ -49,9 +49,6 @@ SIGNATURES = {
                           _vp, _sz, _vp]),
     'nabu_gemm2_ws_bytes': (_sz, [_i, _i, _i, _i]),
     'nabu_gemm2_f32': (_i, [_i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp, _i, _vp, _vp, _sz, _vp]),
-    'nabu_cvt_bf16': (_i, [_sz, _i, _vp, _i, _vp, _i, _i, _vp]),
-    'nabu_gemm_bf16_nt_ws_bytes': (_sz, [_i, _i, _i]),
-    'nabu_gemm_bf16_nt': (_i, [_i, _i, _i, _f, _vp, _i, _vp, _i, _f, _vp, _i, _vp, _vp, _sz, _vp]),
     'nabu_pk_rows_pad': (_i, [_i]),
     'nabu_pk_kblocks': (_i, [_i, _i]),
     'nabu_pk_bytes': (_sz, [_i, _i, _i]),
@@ -199,7 +196,7 @@ class Workspace(object):
 SPELLER_MAX_LAYERS = 4
 GEMM_DEFAULT, GEMM_F32, GEMM_BF16, GEMM_BF16X3, GEMM_BF16X6 = 0, 1, 2, 3, 4
 # NABU_ABI_VERSION of include/nabu_hip.h this binding was written against (lib() refuses another library)
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 GEMM_PRECISIONS = {'default': 0, 'f32': 1, 'bf16': 2, 'bf16x3': 3, 'bf16x6': 4, 'f16x3': 5}
 

@@ -591,29 +591,6 @@ extern "C" int nabu_gemm2_f32(int M, int N, int K1, const float *A, int lda, con
                            reinterpret_cast<float *>(static_cast<char *>(ws) + 4096), static_cast<unsigned *>(ws), s);
 }
 
-// bf16-resident operands (gemm_bf16_pre.hip)
-extern "C" int nabu_cvt_bf16(size_t R, int C, const float *src, int ld, void *dst_bf16, int ldd, int transpose,
-                             nabu_stream_t stream) {
-  NABU_CHECK_ARG(src && dst_bf16 && C > 0, "cvt_bf16: bad argument");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (transpose) return cvt_bf16_t((int)R, C, src, ld, static_cast<unsigned short *>(dst_bf16), ldd, s);
-  return cvt_bf16(R, C, src, ld, static_cast<unsigned short *>(dst_bf16), ldd, s);
-}
-extern "C" size_t nabu_gemm_bf16_nt_ws_bytes(int M, int N, int K) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  return gemm_bf16_pre_ws_bytes(M, N, K);
-}
-extern "C" int nabu_gemm_bf16_nt(int M, int N, int K, float alpha, const void *A_bf16, int lda, const void *B_bf16,
-                                 int ldb, float beta, float *C, int ldc, const float *bias, void *ws, size_t ws_bytes,
-                                 nabu_stream_t stream) {
-  NABU_CHECK_ARG(M >= 0 && N >= 0 && K > 0, "gemm_bf16_nt: bad dimensions");
-  if (M == 0 || N == 0) return 0;
-  NABU_CHECK_ARG(A_bf16 && B_bf16 && C, "gemm_bf16_nt: null pointer");
-  return gemm_bf16_pre(M, N, K, alpha, static_cast<const unsigned short *>(A_bf16), lda,
-                       static_cast<const unsigned short *>(B_bf16), ldb, beta, C, ldc, bias, ws, ws_bytes,
-                       static_cast<hipStream_t>(stream));
-}
-
 static int g_default_precision = 0;   // 0 = not initialised yet
 
 extern "C" int nabu_gemm_get_default_precision(void) {

@@ -110,15 +110,6 @@ int gemm_batched_f32(bool transA, bool transB, int M, int N, int K, const float 
 int gemm_split_for(int M, int N, int K, int kmult, int target, int *ksplit);
 int gemm_splitk_reduce(const GemmArgs &a, hipStream_t s);
 
-// bf16 operands resident in memory (gemm_bf16_pre.hip): C = alpha * A·B^T + beta*C + bias, A [M,lda] and
-// B [N,ldb] bf16 with k contiguous; conversions fp32 -> bf16 (plain / transposed copies)
-bool gemm_bf16_pre_ok(int M, int N, int K, int lda, int ldb);
-size_t gemm_bf16_pre_ws_bytes(int M, int N, int K);
-int gemm_bf16_pre(int M, int N, int K, float alpha, const unsigned short *A, int lda, const unsigned short *B, int ldb,
-                  float beta, float *C, int ldc, const float *bias, void *ws, size_t ws_bytes, hipStream_t s);
-int cvt_bf16(size_t R, int C, const float *src, int ld, unsigned short *dst, int ldd, hipStream_t s);
-int cvt_bf16_t(int R, int C, const float *src, int ld, unsigned short *dst, int ldd, hipStream_t s);
-
 // packed bf16-plane operands (gemm_pk.hip): does the current device offer the tile loop's 144 KiB of LDS?
 bool gemm_pk_device_ok();
 // f16x3 row maxima from per-unit partial maxima [rows][ld] (lstm_persist.hip): amax[n] = bits of max_r |part[r][n]|

@@ -23,9 +23,10 @@
 //
 // Why packed operands.  Round 2's kernels either split fp32 operands inside the k-loop (gemm_bf16.hip:
 // 4-byte operand traffic and ~300 VALU instructions per tile on the critical path, 140-160 TF/s effective)
-// or used 128 x 128 tiles on row-major bf16 copies (gemm_bf16_pre.hip: 64 flop per operand byte, matrix pipe
-// 27 % busy, every operand panel fetched ~5 times).  Here every operand is converted ONCE per use-site into
-// the layout the tile loop wants (pack kernels below, HBM-streaming, ~10 bytes of traffic per element):
+// or used 128 x 128 tiles on row-major bf16 copies (64 flop per operand byte, matrix pipe 27 % busy, every
+// operand panel fetched ~5 times; that kernel has since been removed).  Here every operand is converted ONCE
+// per use-site into the layout the tile loop wants (pack kernels below, HBM-streaming, ~10 bytes of traffic
+// per element):
 //
 //   packed[kb][plane][row][16 k]   bf16, row = the operand's M (resp. N) index padded to a multiple of 256,
 //                                  kb = k / 16; inside a row's 32 bytes the two 16-byte halves are swapped

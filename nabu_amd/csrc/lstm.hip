@@ -187,13 +187,11 @@ struct Layout {
   size_t reserve_bytes;
   // workspace carve
   size_t hstate_off, cstate_off, gemm_off, gemm_bytes, persist_off, persist_bytes, xws_off, xws_bytes, total;
-  // bf16-resident input products (gemm_precision = bf16): converted copies of the operands
-  bool bf16_pre, bf16_fwd;
-  size_t bf16_off, bf16_bytes;
   // packed bf16-plane operands (gemm_pk.hip): planes = 3 (bf16x6) or 1 (bf16); pk_in = the input products
   // X·Wx, dZ·Wx^T, X^T·dZ, pk_rec = the recurrent weight gradient h_{t-1}^T·dZ
   int pk_planes;
   bool pk_in, pk_rec;
+  bool pk_xw;       // the forward product X·Wx: pk_in, or plain bf16 below 256 inputs as well (cfg5's first layer: D = 80)
   bool pk_whole;    // narrow input (D < 256): [x^T ; h^T] is ONE operand and the whole kernel gradient one product
   size_t pk_off, pk_bytes;
   // forward: X [BT, D], W^T of both cells [8H, D]; backward: dZ^T [8H, BT], X^T [D, BT], h^T per cell [H, BT],
@@ -253,27 +251,6 @@ struct DescScope {
   ~DescScope() { lstm_persist_set_exact(prev); }
 };
 
-// the input-to-hidden products X·Wx, dZ·Wx^T, X^T·dZ run on bf16 copies of their operands (converted once per
-// call, gemm_bf16_pre.hip) when bf16 arithmetic is requested and every reduction length is a multiple of 64
-static bool bf16_resident(const nabu_blstm_desc *d) {
-  const int prec = d->gemm_precision == NABU_GEMM_DEFAULT ? nabu_gemm_get_default_precision() : d->gemm_precision;
-  static int env = -1;
-  if (env < 0) { const char *e = getenv("NABU_BF16_RESIDENT"); env = e ? atoi(e) : 1; }
-  const long long BT = (long long)d->B * d->T;
-  return env && prec == NABU_GEMM_BF16 && d->D % 64 == 0 && (4 * d->H) % 64 == 0 && BT % 64 == 0 && BT < (1ll << 31);
-}
-// the forward product alone also takes an input width that is not a multiple of 64 (the first layer: D = 80):
-// the bf16 copies of x and Wx^T are zero-padded to the next multiple of 64 along the reduction index
-static bool bf16_resident_fwd(const nabu_blstm_desc *d) {
-  if (bf16_resident(d)) return true;
-  const int prec = d->gemm_precision == NABU_GEMM_DEFAULT ? nabu_gemm_get_default_precision() : d->gemm_precision;
-  static int env = -1;
-  if (env < 0) { const char *e = getenv("NABU_BF16_RESIDENT"); env = e ? atoi(e) : 1; }
-  const long long BT = (long long)d->B * d->T;
-  return env && prec == NABU_GEMM_BF16 && d->D % 8 == 0 && (4 * d->H) % 64 == 0 && BT < (1ll << 31) && BT >= 2048;
-}
-static int pad64(int x) { return (x + 63) / 64 * 64; }
-
 // planes of the packed-operand path for this layer (0 = not taken): bf16x6 -> 3, f16x3 -> 2, bf16 -> 1
 static int pk_planes_of(const nabu_blstm_desc *d) {
   const int prec = d->gemm_precision == NABU_GEMM_DEFAULT ? nabu_gemm_get_default_precision() : d->gemm_precision;
@@ -318,7 +295,7 @@ static nabu_pk_gemm_desc pk_desc(int planes, int M, int N, int nkb, const void *
 static size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 
 static Layout make_layout(const nabu_blstm_desc *d) {
-  Layout L;
+  Layout L = {};
   const size_t B = d->B, T = d->T, D = d->D, H = d->H;
   L.gates_elems = B * T * 4 * H;
   L.cs_elems = B * T * H;
@@ -338,38 +315,23 @@ static Layout make_layout(const nabu_blstm_desc *d) {
   g = max_sz(g, nabu_gemm_ws_bytes((int)D, (int)(4 * H), M));            // x^T·dz
   if (T > 1) g = max_sz(g, nabu_gemm_ws_bytes((int)H, (int)(4 * H), (int)(B * (T - 1))));
   g = max_sz(g, nabu_colsum_ws_bytes(M, (int)(4 * H)));
-  if (bf16_resident_fwd(d)) g = max_sz(g, gemm_bf16_pre_ws_bytes(M, (int)(4 * H), pad64((int)D)));
-  if (bf16_resident(d)) {
-    g = max_sz(g, gemm_bf16_pre_ws_bytes(M, (int)(4 * H), (int)D));
-    g = max_sz(g, gemm_bf16_pre_ws_bytes(M, (int)D, (int)(4 * H)));
-    g = max_sz(g, gemm_bf16_pre_ws_bytes((int)D, (int)(4 * H), M));
-  }
   L.gemm_off = off; L.gemm_bytes = align_up(g, 256); off += L.gemm_bytes;
   L.persist_bytes = align_up(lstm_persist_ws_bytes(d->B, d->T, d->H), 256);
   L.persist_off = off; off += L.persist_bytes;
   // narrow input projected inside the forward kernel (lstm_persist.h): its plane copy of x
   L.xws_bytes = align_up(lstm_persist_xws_bytes(d->B, d->T, d->D, d->H), 256);
   L.xws_off = off; off += L.xws_bytes;
-  L.bf16_pre = bf16_resident(d);
-  L.bf16_fwd = bf16_resident_fwd(d);
-  L.bf16_off = off;
-  L.bf16_bytes = 0;
-  if (L.bf16_fwd) {
-    const size_t BT = B * T, G = 4 * H, Dp = pad64((int)D);
-    const size_t fwd = 2 * (BT * Dp + G * Dp), bwd = L.bf16_pre ? 2 * (BT * G + G * BT + D * BT + D * G) : 0;
-    L.bf16_bytes = align_up(max_sz(fwd, bwd), 256);
-    off += L.bf16_bytes;
-  }
   L.pk_planes = pk_planes_of(d);
   L.pk_in = L.pk_planes && D >= 256 && D % 4 == 0;
   L.pk_rec = L.pk_planes && T > 1;
   L.pk_whole = L.pk_rec && !L.pk_in && D % 4 == 0;
+  L.pk_xw = L.pk_in || (L.pk_planes == 1 && D % 4 == 0);
   L.pk_off = off; L.pk_bytes = 0;
   if (L.pk_planes) {
     const int P = L.pk_planes, BT = (int)(B * T), G = (int)(4 * H);
     size_t fwd = 0, bwd = 0;
     auto take = [](size_t &o, size_t bytes) { const size_t at = o; o += align_up(bytes, 256); return at; };
-    if (L.pk_in) { L.pk_x = take(fwd, nabu_pk_bytes(BT, (int)D, P)); L.pk_w = take(fwd, nabu_pk_bytes(2 * G, (int)D, P)); }
+    if (L.pk_xw) { L.pk_x = take(fwd, nabu_pk_bytes(BT, (int)D, P)); L.pk_w = take(fwd, nabu_pk_bytes(2 * G, (int)D, P)); }
     if (!L.fwd_only) {
       L.res_dzT_off = align_up(L.reserve_bytes, 256);
       L.res_dzT_bytes = nabu_pk_bytes(2 * G, BT, P);
@@ -413,9 +375,11 @@ static Layout make_layout(const nabu_blstm_desc *d) {
     nabu_pk_gemm_desc g;
     const int rpBT = nabu_pk_rows_pad(BT), rpG = nabu_pk_rows_pad(2 * G), rpD = nabu_pk_rows_pad((int)D);
     float *dummy = reinterpret_cast<float *>(16);
-    if (L.pk_in) {
+    if (L.pk_xw) {
       g = pk_desc(P, BT, 2 * G, nabu_pk_kblocks((int)D, P), dummy, rpBT, dummy, rpG, dummy, G); g.n_split = G; g.C2[0] = dummy;
       gws = max_sz(gws, nabu_gemm_pk_ws_bytes(&g));
+    }
+    if (L.pk_in) {
       g = pk_desc(P, (int)D, 2 * G, nabu_pk_kblocks(BT, P), dummy, rpD, dummy, rpG, dummy, G); g.n_split = G; g.C2[0] = dummy;
       gws = max_sz(gws, nabu_gemm_pk_ws_bytes(&g));
       g = pk_desc(P, BT, (int)D, nabu_pk_kblocks(2 * G, P), dummy, rpBT, dummy, rpD, dummy, (int)D);
@@ -429,7 +393,7 @@ static Layout make_layout(const nabu_blstm_desc *d) {
     }
     if (gws > L.gemm_bytes) {   // the gemm region precedes the persist region: grow it in place
       const size_t grow = align_up(gws, 256) - L.gemm_bytes;
-      L.gemm_bytes += grow; L.persist_off += grow; L.xws_off += grow; L.bf16_off += grow; L.pk_off += grow; off += grow;
+      L.gemm_bytes += grow; L.persist_off += grow; L.xws_off += grow; L.pk_off += grow; off += grow;
     }
   }
   // packed companions (ABI version 3)
@@ -487,7 +451,7 @@ struct ReserveTag {
   const void *reserve;
   uint64_t serial;
   int32_t B, T, D, H, planes, flags, rec;
-  uint8_t pk_in, pk_rec, pk_whole, bf16_pre;
+  uint8_t pk_in, pk_rec, pk_whole;
   size_t reserve_bytes, res_dzT_off;
 };
 static std::mutex g_tag_mutex;
@@ -497,7 +461,7 @@ static ReserveTag tag_of(const nabu_blstm_desc *d, const Layout &L, const void *
   ReserveTag t = {};
   t.reserve = reserve; t.B = d->B; t.T = d->T; t.D = d->D; t.H = d->H; t.planes = L.pk_planes; t.flags = d->flags;
   t.rec = d->recurrent_precision;
-  t.pk_in = L.pk_in; t.pk_rec = L.pk_rec; t.pk_whole = L.pk_whole; t.bf16_pre = L.bf16_pre;
+  t.pk_in = L.pk_in; t.pk_rec = L.pk_rec; t.pk_whole = L.pk_whole;
   t.reserve_bytes = L.reserve_bytes; t.res_dzT_off = L.res_dzT_off;
   return t;
 }
@@ -518,7 +482,7 @@ static int tag_check(const nabu_blstm_desc *d, const Layout &L, const void *rese
   for (const ReserveTag &e : g_tags) {
     if (e.reserve != reserve || !e.serial) continue;
     if (e.B == want.B && e.T == want.T && e.D == want.D && e.H == want.H && e.planes == want.planes && e.flags == want.flags &&
-        e.rec == want.rec && e.pk_in == want.pk_in && e.pk_rec == want.pk_rec && e.pk_whole == want.pk_whole && e.bf16_pre == want.bf16_pre &&
+        e.rec == want.rec && e.pk_in == want.pk_in && e.pk_rec == want.pk_rec && e.pk_whole == want.pk_whole &&
         e.reserve_bytes == want.reserve_bytes && e.res_dzT_off == want.res_dzT_off)
       return 0;
     return fail(NABU_EINVAL, "%s: the reserve was written by nabu_blstm_fwd under another layout (B %d T %d D %d H %d, %d planes, "
@@ -650,7 +614,7 @@ extern "C" int nabu_blstm_fwd(const nabu_blstm_desc *d_in, const float *x, const
   bool ring_with_fill = use_persistent(d) && !fuse_in;   // the projection's fill also clears the exchange ring
   auto input_projection = [&]() -> int {
   // time-batched input projections (MFMA): gates_d = x·Wx_d + b_d
-  if (L.pk_in) {
+  if (L.pk_xw) {
     // packed bf16-plane operands: X once, Wx^T of both cells as the rows of ONE operand; one product fills the
     // gate buffers of both directions
     const int P = L.pk_planes, BT = B * T, G = 4 * H;
@@ -701,20 +665,6 @@ extern "C" int nabu_blstm_fwd(const nabu_blstm_desc *d_in, const float *x, const
     g.C2[0] = gates[1]; g.n_split = G; g.bias = bias[0]; g.bias2 = bias[1];
     if (P == 2) { g.a_amax[0] = ax; g.b_amax[0] = aw; g.direct = 2; }
     if (int e = nabu_gemm_pk(&g, w + L.gemm_off, L.gemm_bytes, stream)) return e;
-  } else if (L.bf16_fwd) {
-    // bf16 copies: x once, Wx_d transposed ([4H, Dp]: the reduction index contiguous, zero-padded to a
-    // multiple of 64), then 2-byte operands
-    const int Dp = pad64(D);
-    unsigned short *xb = reinterpret_cast<unsigned short *>(w + L.bf16_off);
-    unsigned short *wt = xb + (size_t)B * T * Dp;
-    if (Dp != D) NABU_HIP(hipMemsetAsync(xb, 0, ((size_t)B * T + 4 * H) * Dp * 2, s));
-    if (int e = cvt_bf16((size_t)B * T, D, x, D, xb, Dp, s)) return e;
-    for (int dir = 0; dir < 2; ++dir) {
-      if (int e = cvt_bf16_t(D, 4 * H, kern[dir], 4 * H, wt, Dp, s)) return e;
-      if (int e = gemm_bf16_pre(B * T, 4 * H, Dp, 1.f, xb, Dp, wt, Dp, 0.f, gates[dir], 4 * H, bias[dir], w + L.gemm_off,
-                                L.gemm_bytes, s))
-        return e;
-    }
   } else
   for (int dir = 0; dir < 2; ++dir) {
     int e = nabu_gemm_ex(d->gemm_precision, 0, 0, B * T, 4 * H, D, 1.f, x, D, kern[dir], 4 * H, 0.f, gates[dir],
@@ -983,30 +933,13 @@ static int blstm_bwd_parts(int parts, const nabu_blstm_desc *d, const float *x, 
       if ((e = nabu_gemm_pk(&g, w + L.gemm_off, L.gemm_bytes, stream))) return e;
     }
   }
-  unsigned short *dzb = nullptr, *dzT = nullptr, *xT = nullptr, *wb = nullptr;
-  const bool old_bf16 = L.bf16_pre && !L.pk_in;
-  if (old_bf16) {   // bf16 copies of this call's operands: x^T once; dz and dz^T, Wx per direction
-    dzb = reinterpret_cast<unsigned short *>(w + L.bf16_off);
-    dzT = dzb + (size_t)M * 4 * H;
-    xT = dzT + (size_t)4 * H * M;
-    wb = xT + (size_t)D * M;
-    if (parts & 2)
-      if (int e = cvt_bf16_t(M, D, x, D, xT, M, s)) return e;
-  }
   for (int dir = 0; dir < 2; ++dir) {
     int e = 0;
-    if (L.pk_in || L.pk_whole || !(parts & 2)) {
-    } else if (old_bf16) {
-      if ((e = cvt_bf16_t(M, 4 * H, gates[dir], 4 * H, dzT, M, s))) return e;
-      // dWx = x^T · dz = sum over frames of xT[d, k] * dzT[n, k]
-      if ((e = gemm_bf16_pre(D, 4 * H, M, 1.f, xT, M, dzT, M, 0.f, dkern[dir], 4 * H, nullptr, w + L.gemm_off,
-                             L.gemm_bytes, s)))
-        return e;
-    } else {
     // dWx = x^T · dz
-    e = nabu_gemm_ex(d->gemm_precision, 1, 0, D, 4 * H, M, 1.f, x, D, gates[dir], 4 * H, 0.f, dkern[dir], 4 * H,
-                      nullptr, 0, 0, 0, w + L.gemm_off, L.gemm_bytes, stream);
-    if (e) return e;
+    if (!L.pk_in && !L.pk_whole && (parts & 2)) {
+      e = nabu_gemm_ex(d->gemm_precision, 1, 0, D, 4 * H, M, 1.f, x, D, gates[dir], 4 * H, 0.f, dkern[dir], 4 * H,
+                       nullptr, 0, 0, 0, w + L.gemm_off, L.gemm_bytes, stream);
+      if (e) return e;
     }
     // dWh = h_{prev}^T · dz : fw pairs (out[b,t-1,:H], dz[b,t]); bw pairs (out[b,t+1,H:], dz[b,t])
     if (!(L.pk_planes && L.pk_rec) && (parts & 2)) {
@@ -1026,14 +959,7 @@ static int blstm_bwd_parts(int parts, const nabu_blstm_desc *d, const float *x, 
       e = nabu_colsum_f32(M, 4 * H, gates[dir], 4 * H, 0.f, dbias[dir], w + L.gemm_off, L.gemm_bytes, stream);
     if (e) return e;
     // dx (+)= dz · Wx^T
-    if (L.pk_in) {
-    } else if (d_x && old_bf16) {
-      if ((e = cvt_bf16((size_t)M, 4 * H, gates[dir], 4 * H, dzb, 4 * H, s))) return e;
-      if ((e = cvt_bf16((size_t)D, 4 * H, kern[dir], 4 * H, wb, 4 * H, s))) return e;
-      if ((e = gemm_bf16_pre(M, D, 4 * H, 1.f, dzb, 4 * H, wb, 4 * H, dir == 0 ? 0.f : 1.f, d_x, D, nullptr,
-                             w + L.gemm_off, L.gemm_bytes, s)))
-        return e;
-    } else if (d_x) {
+    if (d_x && !L.pk_in) {
       e = nabu_gemm_ex(d->gemm_precision, 0, 1, M, D, 4 * H, 1.f, gates[dir], 4 * H, kern[dir], 4 * H,
                         dir == 0 ? 0.f : 1.f, d_x, D, nullptr, 0, 0, 0, w + L.gemm_off, L.gemm_bytes, stream);
       if (e) return e;

@@ -14,7 +14,7 @@ def _declared():
     return sorted(set(re.findall(r'\b(nabu_[a-z0-9_]+)\s*\(', src)))
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_at_abi_version_4_exports_every_declared_symbol():
     from nabu_amd import build, _hip
     build.build(verbose=False)
     lib = _hip.lib()
@@ -25,7 +25,7 @@ def test_library_exports_every_declared_symbol():
         assert n in _hip.SIGNATURES, 'no ctypes signature for %s' % n
     for n in _hip.SIGNATURES:
         assert n in names, '%s bound in _hip.py but not declared in nabu_hip.h' % n
-    assert lib.nabu_version() == 3 == _hip.ABI_VERSION
+    assert lib.nabu_version() == 4 == _hip.ABI_VERSION
 
 
 def test_graft_entry_build_checks_the_same_version():

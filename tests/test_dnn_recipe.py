@@ -205,7 +205,7 @@ def test_splice_order_on_a_hand_built_input():
     assert dnn.splice_ld(123, 5) == 1120 and dnn.splice_ld(13, 3) == 96
 
 
-def test_new_symbols_declared_bound_and_wrapped():
+def test_dnn_symbols_declared_bound_and_wrapped_at_abi_version_4():
     import re
     from nabu_amd import _hip, ops
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'nabu_hip.h')).read()
@@ -219,7 +219,7 @@ def test_new_symbols_declared_bound_and_wrapped():
     from nabu_amd import build
     build.build(verbose=False)
     lib = _hip.lib()
-    assert lib.nabu_version() == 3
+    assert lib.nabu_version() == 4
     assert lib.nabu_xent_wide_ws_bytes(32, 1000) == 32 * 1000 * 4
     assert lib.nabu_rows_relu_ln_bwd_parts(10) == 10 and lib.nabu_rows_relu_ln_bwd_parts(10 ** 6) == 1024
     # host-side argument checks: no launch

@@ -387,6 +387,8 @@ def test_gemm_pk_f16x3_non_finite_inputs_stay_visible():
     (17, 130, 260, 128, [130, 7, 99, 130, 1, 64, 65, 129, 30, 130, 2, 77, 128, 13, 100, 55, 130]),   # ragged, edge tiles,
                                                                    # B*T and D not multiples of 16
     (16, 160, 40, 64, None),                                       # narrow input: only the recurrent gradient is packed
+    (16, 160, 80, 64, None),                                       # cfg5's first layer (D = 80): bf16's X·Wx packed
+    (16, 160, 128, 64, None),                                      # bf16's dx on nabu_gemm_ex
 ])   # (B*T >= 2048: below that the layer computes f16x3 requests as bf16x6)
 def test_blstm_layer_on_packed_products_matches_oracle(precision, tol, B, T, D, H, lens):
     """nabu_blstm_fwd/_bwd with gemm_precision = bf16x6 / f16x3 (fp32-equivalent, same bounds as the exact-fp32 layer
@@ -416,7 +418,7 @@ def test_blstm_layer_f16x3_is_its_own_arithmetic_above_2048_frames():
 
 
 @pytest.mark.parametrize('precision', ['f32', 'bf16x6', 'f16x3', 'bf16'])
-@pytest.mark.parametrize('B,T,D,H', [(32, 64, 256, 64), (16, 160, 40, 64)])
+@pytest.mark.parametrize('B,T,D,H', [(32, 64, 256, 64), (16, 160, 40, 64), (16, 160, 80, 64), (16, 160, 128, 64)])
 def test_blstm_backward_in_two_calls_equals_one(precision, B, T, D, H):
     """nabu_blstm_bwd_data + nabu_blstm_bwd_weights (the weight-gradient products deferred behind the last recurrence of
     a backward pass) == nabu_blstm_bwd, bit for bit, on every arithmetic of the products"""
