@@ -187,6 +187,7 @@ struct Layout {
   size_t reserve_bytes;
   // workspace carve
   size_t hstate_off, cstate_off, gemm_off, gemm_bytes, persist_off, persist_bytes, xws_off, xws_bytes, total;
+  PersistPlan plan;   // the persistent recurrence's launch plan for this call (lstm_persist.h): decided here, once
   // packed bf16-plane operands (gemm_pk.hip): planes = 3 (bf16x6) or 1 (bf16); pk_in = the input products
   // X·Wx, dZ·Wx^T, X^T·dZ, pk_rec = the recurrent weight gradient h_{t-1}^T·dZ
   int pk_planes;
@@ -239,17 +240,15 @@ static int load_desc(const nabu_blstm_desc *in, nabu_blstm_desc *out) {
     return fail(NABU_EINVAL, "blstm: x_pk_rows and x_pk_cols come as a pair (a forward-only descriptor may give the rows alone)");
   return 0;
 }
-// every entry point works on the normalised copy and, for its duration, tells the persistent-kernel dispatch whether
-// this call asked for the exact-fp32 recurrence (workspace sizes depend on it as well)
+// every entry point works on the normalised copy
 struct DescScope {
   nabu_blstm_desc d;
   int err;
-  bool prev;
-  explicit DescScope(const nabu_blstm_desc *in) : err(load_desc(in, &d)), prev(lstm_persist_exact()) {
-    if (!err) lstm_persist_set_exact(d.recurrent_precision == NABU_REC_F32);
-  }
-  ~DescScope() { lstm_persist_set_exact(prev); }
+  explicit DescScope(const nabu_blstm_desc *in) : err(load_desc(in, &d)) {}
 };
+static PersistPlan plan_of(const nabu_blstm_desc *d) {
+  return lstm_persist_plan(d->B, d->T, d->D, d->H, d->max_len > 0 ? d->max_len : d->T, d->recurrent_precision == NABU_REC_F32);
+}
 
 // planes of the packed-operand path for this layer (0 = not taken): bf16x6 -> 3, f16x3 -> 2, bf16 -> 1
 static int pk_planes_of(const nabu_blstm_desc *d) {
@@ -316,10 +315,11 @@ static Layout make_layout(const nabu_blstm_desc *d) {
   if (T > 1) g = max_sz(g, nabu_gemm_ws_bytes((int)H, (int)(4 * H), (int)(B * (T - 1))));
   g = max_sz(g, nabu_colsum_ws_bytes(M, (int)(4 * H)));
   L.gemm_off = off; L.gemm_bytes = align_up(g, 256); off += L.gemm_bytes;
-  L.persist_bytes = align_up(lstm_persist_ws_bytes(d->B, d->T, d->H), 256);
+  L.plan = plan_of(d);
+  L.persist_bytes = align_up(L.plan.ws_bytes, 256);
   L.persist_off = off; off += L.persist_bytes;
   // narrow input projected inside the forward kernel (lstm_persist.h): its plane copy of x
-  L.xws_bytes = align_up(lstm_persist_xws_bytes(d->B, d->T, d->D, d->H), 256);
+  L.xws_bytes = align_up(L.plan.xws_bytes, 256);
   L.xws_off = off; off += L.xws_bytes;
   L.pk_planes = pk_planes_of(d);
   L.pk_in = L.pk_planes && D >= 256 && D % 4 == 0;
@@ -436,9 +436,8 @@ static thread_local hipEvent_t g_ev_begin = nullptr, g_ev_end = nullptr;
 static thread_local nabu_phase_hook_t g_phase_hook = nullptr;
 static thread_local void *g_phase_user = nullptr;
 
-static bool use_persistent(const nabu_blstm_desc *d) {
-  if (d->mode == NABU_LSTM_STEPWISE) return false;
-  return lstm_persist_supported(d->B, d->T, d->H);
+static bool use_persistent(const nabu_blstm_desc *d, const PersistPlan &plan) {
+  return d->mode != NABU_LSTM_STEPWISE && plan.supported;
 }
 
 // WHAT A RESERVE HOLDS is decided by make_layout from the descriptor AND from process state (the default GEMM
@@ -516,7 +515,7 @@ extern "C" int nabu_blstm_uses_persistent(const nabu_blstm_desc *d_in) {
   DescScope scope(d_in);
   const nabu_blstm_desc *d = &scope.d;
   if (scope.err || check_desc(d)) return 0;
-  return use_persistent(d) ? 1 : 0;
+  return use_persistent(d, plan_of(d)) ? 1 : 0;
 }
 
 extern "C" int nabu_blstm_pk_bytes(const nabu_blstm_desc *d_in, size_t bytes[5]) {
@@ -533,8 +532,7 @@ static bool wants_companions(const nabu_blstm_desc *d, const Layout &L) {
   return ((d->out_pk_rows || d->out_pk_cols) && L.cmp_bytes[3] != 0) || L.hT_ext;
 }
 static bool kernel_emits(const nabu_blstm_desc *d, const Layout &L) {
-  const int max_len = d->max_len > 0 ? d->max_len : d->T;
-  if (!wants_companions(d, L) || !use_persistent(d) || !lstm_persist_emits(d->B, d->T, d->H, max_len)) return false;
+  if (!wants_companions(d, L) || !use_persistent(d, L.plan) || !L.plan.emits) return false;
   for (int i = 2; i < 5; ++i)
     if (L.cmp_bytes[i] >= 0x7FFFFFF0ull) return false;      // 32-bit buffer offsets inside the kernel
   return true;
@@ -556,7 +554,7 @@ static int emitted_by_kernel(const nabu_blstm_desc *d, const Layout &L) {
   if (!kernel_emits(d, L)) return 0;
   bool from_env = false;
   int m = emit_mask_env(&from_env);
-  if (!from_env && lstm_persist_fuses_input(d->B, d->T, d->D, d->H)) m &= ~4;
+  if (!from_env && L.plan.fuses_input) m &= ~4;
   const bool want_out = (d->out_pk_rows || d->out_pk_cols) && L.cmp_bytes[3] != 0;
   if (!want_out || !d->out_pk_rows) m &= ~1;
   if (!want_out || !d->out_pk_cols) m &= ~2;
@@ -595,7 +593,7 @@ extern "C" int nabu_blstm_fwd(const nabu_blstm_desc *d_in, const float *x, const
                  "blstm_fwd: null pointer");
   const Layout L = make_layout(d);
   if (ws_bytes < L.total) return fail(NABU_EWS, "blstm_fwd: workspace %zu < %zu", ws_bytes, L.total);
-  if (d->mode == NABU_LSTM_PERSISTENT && !lstm_persist_supported(d->B, d->T, d->H))
+  if (d->mode == NABU_LSTM_PERSISTENT && !L.plan.supported)
     return fail(NABU_EUNSUP, "blstm_fwd: persistent kernel does not support B=%d H=%d", d->B, d->H);
   tag_store(tag_of(d, L, reserve));
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -609,9 +607,9 @@ extern "C" int nabu_blstm_fwd(const nabu_blstm_desc *d_in, const float *x, const
   const float *bias[2] = {bias_fw, bias_bw};
 
   // narrow input (first layer): the persistent kernel projects its input itself (lstm_persist.hip, XK) — no product here
-  const bool fuse_in = use_persistent(d) && lstm_persist_fuses_input(B, T, D, H);
-  lstm_persist_ring_cleared(nullptr, s);              // (no note from an earlier call that failed half-way)
-  bool ring_with_fill = use_persistent(d) && !fuse_in;   // the projection's fill also clears the exchange ring
+  const bool persistent = use_persistent(d, L.plan);
+  const bool fuse_in = persistent && L.plan.fuses_input;
+  bool ring_cleared = false;      // the projection's fill has also cleared the exchange ring (PersistPlan::caller_ring_words)
   auto input_projection = [&]() -> int {
   // time-batched input projections (MFMA): gates_d = x·Wx_d + b_d
   if (L.pk_xw) {
@@ -632,13 +630,13 @@ extern "C" int nabu_blstm_fwd(const nabu_blstm_desc *d_in, const float *x, const
       const int rpD = nabu_pk_rows_pad(D);
       // (and the backward pass's row bound of h^T, |h| <= 1: a constant it would otherwise fill in a launch of its own)
       uint32_t *ahT = L.res_ahT_off ? reinterpret_cast<uint32_t *>(static_cast<char *>(reserve) + L.res_ahT_off) : nullptr;
-      // and the recurrent launch's exchange ring (lstm_persist.h: lstm_persist_ring_seg) — nothing between here and that
+      // and the recurrent launch's exchange ring (lstm_persist.h: caller_ring_words) — nothing between here and that
       // launch writes the persistent kernels' part of the workspace
       FillSeg fill[6] = {{ax, (size_t)rpBT, xb}, {aw, (size_t)rpG, 0u}, {axT, axT ? (size_t)rpD : 0, xb}, {aw2, aw2 ? (size_t)rpD : 0, 0u},
-                         {ahT, ahT ? (size_t)nabu_pk_rows_pad(H) : 0, L.hT_ext ? CMP_AMAX_BITS : bound_bits(1.0f)}, {nullptr, 0, 0u}};
-      const bool with_ring = ring_with_fill && lstm_persist_ring_seg(true, B, T, H, w + L.persist_off, &fill[5]);
+                         {ahT, ahT ? (size_t)nabu_pk_rows_pad(H) : 0, L.hT_ext ? CMP_AMAX_BITS : bound_bits(1.0f)},
+                         {w + L.persist_off, persistent && !fuse_in ? L.plan.caller_ring_words : 0, 0xFFFFFFFFu}};
       if (int e = multi_fill(fill, 6, s)) return e;
-      if (with_ring) lstm_persist_ring_cleared(&fill[5], s);
+      ring_cleared = fill[5].words > 0;
       if (!xb)
         if (int e = nabu_pk_amax(x, D, BT, D, ax, axT, stream)) return e;
       if (int e = pk_amax_pair(kern[0], kern[1], G, D, G, aw2, aw, aw + G, nullptr, s)) return e;
@@ -721,10 +719,10 @@ extern "C" int nabu_blstm_fwd(const nabu_blstm_desc *d_in, const float *x, const
     em.b0 = 0;
   }
 
-  if (use_persistent(d)) {
+  if (persistent) {
     NABU_PROFILE_MARK(g_ev_begin, s);
-    int e = lstm_persist_fwd(B, T, D, H, max_len, len, kern, gates, cs, out, reinterpret_cast<int *>(w), w + L.persist_off,
-                             L.persist_bytes, s, fuse_in ? x : nullptr, fuse_in ? bias : nullptr,
+    int e = lstm_persist_fwd(L.plan, len, kern, gates, cs, out, reinterpret_cast<int *>(w), w + L.persist_off,
+                             L.persist_bytes, s, ring_cleared, fuse_in ? x : nullptr, fuse_in ? bias : nullptr,
                              L.xws_bytes ? w + L.xws_off : nullptr, emit ? &em : nullptr);
     // the grid cannot be co-resident on this device (occupancy check before the launch): LSTM_AUTO steps instead
     if (!(e == NABU_EUNSUP && d->mode == NABU_LSTM_AUTO)) {
@@ -733,8 +731,6 @@ extern "C" int nabu_blstm_fwd(const nabu_blstm_desc *d_in, const float *x, const
       if (want_cmp) return companions_by_pack_kernels(7 & ~by_kernel);
       return 0;
     }
-    lstm_persist_ring_cleared(nullptr, s);
-    ring_with_fill = false;
     if (fuse_in)      // the step kernels read the projection from the gate buffers
       if (int e2 = input_projection()) return e2;
   }
@@ -775,10 +771,9 @@ static int blstm_bwd_parts(int parts, const nabu_blstm_desc *d, const float *x, 
   const Layout L = make_layout(d);
   if (int e = tag_check(d, L, reserve, parts == 3 ? "blstm_bwd" : parts == 1 ? "blstm_bwd_data" : "blstm_bwd_weights")) return e;
   if (ws_bytes < L.total) return fail(NABU_EWS, "blstm_bwd: workspace %zu < %zu", ws_bytes, L.total);
-  if (d->mode == NABU_LSTM_PERSISTENT && !lstm_persist_supported(d->B, d->T, d->H))
+  if (d->mode == NABU_LSTM_PERSISTENT && !L.plan.supported)
     return fail(NABU_EUNSUP, "blstm_bwd: persistent kernel does not support B=%d H=%d", d->B, d->H);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  lstm_persist_ring_cleared(nullptr, s);
   const int B = d->B, T = d->T, D = d->D, H = d->H;
   const int max_len = d->max_len > 0 ? d->max_len : T;
   float *r = static_cast<float *>(reserve);
@@ -804,9 +799,9 @@ static int blstm_bwd_parts(int parts, const nabu_blstm_desc *d, const float *x, 
                                 0, (size_t)(T - max_len) * 4 * H * sizeof(float), B, s));
 
   NABU_PROFILE_MARK(g_ev_begin, s);
-  bool stepwise = !use_persistent(d);
+  bool stepwise = !use_persistent(d, L.plan);
   if (!stepwise) {
-    int e = lstm_persist_bwd(B, T, D, H, max_len, len, kern, gates, cs, d_out, reinterpret_cast<int *>(w), w + L.persist_off,
+    int e = lstm_persist_bwd(L.plan, len, kern, gates, cs, d_out, reinterpret_cast<int *>(w), w + L.persist_off,
                              L.persist_bytes, &db_part, &db_rows, s, rowmax, &rowmax_done);
     if (e == NABU_EUNSUP && d->mode == NABU_LSTM_AUTO) { stepwise = true; db_part = nullptr; db_rows = 0; rowmax_done = false; }
     else if (e) return e;

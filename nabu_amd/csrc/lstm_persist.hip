@@ -1,9 +1,9 @@
 // lstm_persist.hip — whole-sequence persistent recurrent kernels for one BLSTM
 // layer (both directions in one launch), MI355X / gfx950.
 //
-// THIS FILE: the host side of every persistent recurrent kernel (geometry, workspace, validation, chunking: run /
+// THIS FILE: the host side of every persistent recurrent kernel (the launch plan, validation, chunking: run /
 // run_chunk at the end) and the exact-fp32 kernels of rounds 1-3 (v_mfma_f32_4x4x1, 4 or 8 rows per unit).
-// DISPATCH (run_chunk), three kernel families since round 5:
+// DISPATCH (decided once per call by lstm_persist_plan, launched by run_chunk), three kernel families since round 5:
 //   1. lstm_persist_mxf.hip   fp16-plane product, 32 hidden units per workgroup: 33 .. 64 rows at H = 512 in one launch;
 //   2. lstm_persist_mxh.hip   fp16-plane product, 16 hidden units per workgroup: launches of <= 32 rows, H in {128, 256, 512}
 //                             (larger batches as consecutive launches) — the default on a whole MI355X;
@@ -67,6 +67,8 @@
 // same FLOP rate, but ~3x the VALU instructions, fighting the other workgroup of the CU.)
 #include "lstm_persist.h"
 #include "lstm_persist_dev.h"
+
+#include <assert.h>
 
 namespace nabu {
 
@@ -674,45 +676,37 @@ void lstm_persist_set_timeout_us(long long us) {
   g_timeout_ticks = us > 0 ? (unsigned long long)us * 100ull : 20000000ull;
 }
 
-// compute units of the CURRENT device (partitioned / CPX modes expose fewer than the 256 of a whole
-// MI355X); every geometry decision below uses it, so that a shape whose grid cannot be co-resident
-// is reported as unsupported — LSTM_AUTO then takes the step-wise kernels instead of failing at launch
-static int cu_count() {
-  static thread_local int cached_dev = -1, cached = NCU;
+// compute units of the CURRENT device as the runtime reports them (partitioned / CPX modes expose fewer than the 256
+// of a whole MI355X); 0: unknown
+static int device_cus() {
+  static thread_local int cached_dev = -1, cached = 0;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return NCU; }
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
   if (dev != cached_dev) {
     int v = 0;
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) {
       (void)hipGetLastError();
-      v = NCU;
+      v = 0;
     }
-    cached = v > NCU ? NCU : v;     // block -> CU bookkeeping (block_identity) is written for <= 256 CUs
+    cached = v;
     cached_dev = dev;
   }
   return cached;
 }
 
-// lstm_persist_mxh.hip: the fp16-plane kernels — three fp16 plane products of row-scaled operands, 8 rows per unit, launches
-// of <= 32 rows (the default wherever H is 128, 256 or 512 on a whole MI355X; NABU_PERSIST_MX=0 or
-// nabu_blstm_desc.recurrent_precision = NABU_REC_F32: the exact-fp32 kernels of this file)
-bool lstm_mx_supported(int B, int H);
-int lstm_mx_chunk_rows();
+// geometry constants of the fp16-plane families (pure functions of the shape)
+int lstm_mx_chunk_rows();                                  // lstm_persist_mxh.hip: 32 batch rows per launch (8 per unit)
 size_t lstm_mxh_ring_bytes(bool fwd, int H);
 int lstm_mxh_launch(bool fwd, int H, const PersistArgs &a, hipStream_t stream, bool dry);
 size_t lstm_mxh_xws_bytes(int B, int T);
 int lstm_mxh_prepare_x(int B, int T, int D, const float *x, void *ws, hipStream_t stream, const FillSeg *also);
-// lstm_persist_mxf.hip: the same arithmetic with 32 hidden units per workgroup, two units of 8 rows per XCD: 33 .. 64 batch
-// rows at H = 512 in one launch (NABU_PERSIST_MXF=0: launches of <= 32 rows on the kernels above)
-bool lstm_mxf_supported(int B, int H);
-size_t lstm_mxf_ring_bytes(bool fwd, int H);
+size_t lstm_mxf_ring_bytes(bool fwd, int H);               // lstm_persist_mxf.hip
 int lstm_mxf_launch(bool fwd, int H, const PersistArgs &a, hipStream_t stream, bool dry);
 
-// geometry: BS = 4 (two 256-thread workgroups per CU) when the batch fits, else BS = 8
-bool lstm_persist_fuses_input(int B, int T, int D, int H);
 size_t lstm_persist_db_floats(int B, int H) { return (size_t)((B + 3) / 4) * 2 * 4 * H; }
-static int pick_bs(int B, int H, bool fwd) {
-  const int P = H / UC, ncu = cu_count();
+// exact fp32: BS = 4 (two 256-thread workgroups per CU) when the batch fits, else BS = 8; 0: not in one launch
+static int pick_bs(int B, int H, bool fwd, int ncu) {
+  const int P = H / UC;
   if (2 * ((B + 3) / 4) * P <= 2 * ncu) return 4;
   if (2 * ((B + 7) / 8) * P <= ncu) return 8;          // one 512-thread workgroup per CU
   // two 512-thread workgroups per CU (<= 128 VGPRs): cfg5's B = 64 at H = 512 in ONE launch.  Forward
@@ -722,59 +716,94 @@ static int pick_bs(int B, int H, bool fwd) {
   if (fwd && 2 * ((B + 7) / 8) * P <= 2 * ncu) return 8;
   return 0;
 }
-
-// Batches that need more workgroups than the chip holds run as consecutive launches over
-// chunks of batch rows (the tensors are batch-major, a chunk is a contiguous slab): at H = 512 a
-// launch takes up to 64 rows (BS = 8, two workgroups per CU), B = 96 is a launch of 64 and one of 32.
-static int chunk_rows(int B, int H, bool fwd, int T = 0) {
-  if (lstm_mx_supported(B, H)) {
-    // up to 32 rows: one launch of 8-row units; 33 .. 64 rows at H = 512: one launch of lstm_persist_mxf.hip (unless a slab
-    // of 64 rows x T frames of gates is beyond the 32-bit buffer offsets of one launch); otherwise launches of 32 rows
-    int c = lstm_mx_chunk_rows();
-    if (B > c && lstm_mxf_supported(B > 2 * c ? 2 * c : B, H) && !(T > 0 && (size_t)2 * c * T * 4 * H * 4 >= 0x80000000ull)) c *= 2;
-    return B < c ? B : c;
-  }
-  if (pick_bs(B, H, fwd)) return B;
-  int c = (fwd ? 8 : 4) * (2 * cu_count() / (2 * (H / UC)));   // largest batch of one launch
-  return c < 4 ? 4 : c;
-}
-
-bool lstm_persist_supported(int B, int T, int H) {
-  if (!(H == 64 || H == 128 || H == 256 || H == 512)) return false;
-  if (B <= 0 || T <= 0) return false;
-  if (lstm_mx_supported(B, H)) return (size_t)chunk_rows(B, H, true, T) * T * 4 * H * 4 < 0x80000000ull;
-  if ((size_t)B * T * 4 * H * 4 >= 0x80000000ull && (size_t)chunk_rows(B, H, true) * T * 4 * H * 4 >= 0x80000000ull)
-    return false;   // 32-bit buffer offsets inside one launch
-  return pick_bs(chunk_rows(B, H, true), H, true) != 0 && pick_bs(chunk_rows(B, H, false), H, false) != 0;
-}
-
 // bias-gradient partials of the backward kernel: one row of 2 x 4H per shard (BS = 4 gives the most)
 static size_t db_part_bytes(int B, int H) { return 2 * (size_t)((B + 3) / 4) * 2 * 4 * H * sizeof(float); }   // sums, maxima
-
-static size_t ring_bytes(bool fwd, int BS, int nshard, int H) {
+static size_t f32_ring_bytes(bool fwd, int BS, int nshard, int H) {
   const size_t NU = 2 * (size_t)nshard, P = H / UC;
   return fwd ? NU * RING * (size_t)H * BS * 4 : NU * RINGB * P * P * UC * BS * 4;
 }
 
-size_t lstm_persist_ws_bytes(int B, int T, int H) {
-  if (!lstm_persist_supported(B, T, H)) return 0;
-  size_t m = 0;
-  for (int BS = 4; BS <= 8; BS += 4) {   // either geometry may be selected at run time
+// THE decision (lstm_persist.h).  Batches that need more workgroups than the chip holds run as consecutive launches
+// over chunks of batch rows (the tensors are batch-major, a chunk is a contiguous slab):
+//   fp16 planes (a whole MI355X, H in {128, 256, 512}, not `exact`, NABU_PERSIST_MX != 0): up to 32 rows one launch of
+//     lstm_persist_mxh.hip; 33 .. 64 rows at H = 512 one launch of lstm_persist_mxf.hip (NABU_PERSIST_MXF=0: never, =2:
+//     also batches of <= 32 rows, for measurements) unless a slab of 64 rows x T frames of gates is beyond the 32-bit
+//     buffer offsets of one launch; larger batches as launches of 64 resp. 32 rows and a remainder;
+//   exact fp32 otherwise: at H = 512 a forward launch takes up to 64 rows (BS = 8, two workgroups per CU), B = 96 is a
+//     launch of 64 and one of 32.
+PersistPlan lstm_persist_plan(int B, int T, int D, int H, int max_len, bool exact) {
+  const auto env = [](const char *e, int dflt) { return e ? atoi(e) : dflt; };
+  static const int env_mx = env(getenv("NABU_PERSIST_MX"), 1), env_mxf = env(getenv("NABU_PERSIST_MXF"), 1);
+  static const int env_fuse = env(getenv("NABU_PERSIST_FUSE_INPUT"), 1), env_emit = env(getenv("NABU_PERSIST_EMIT"), 1);
+  const int dbg = env(getenv("NABU_PERSIST_DEBUG"), 0);     // per call: a debug variant writes no companions
+  PersistPlan p = {};
+  p.B = B; p.T = T; p.D = D; p.H = H; p.max_len = max_len;
+  const int cus = device_cus();
+  p.ncu = cus <= 0 || cus > NCU ? NCU : cus;     // block -> CU bookkeeping (block_identity) is written for <= 256 CUs
+  if (!(H == 64 || H == 128 || H == 256 || H == 512) || B <= 0 || T <= 0) return p;
+  const bool mx = env_mx && !exact && cus >= NCU && H != 64;   // (8 XCDs of 32 CUs, one workgroup per CU)
+  const auto mxf_takes = [&](int rows) { return env_mxf != 0 && H == 512 && (rows > 32 || env_mxf == 2) && rows <= 64; };
+  const size_t row_bytes = (size_t)T * 4 * H * 4, LIMIT = 0x80000000ull;   // gates of one batch row; 32-bit offsets inside a launch
+  int rows[2];      // backward, forward
+  if (mx) {
+    int c = lstm_mx_chunk_rows();
+    if (B > c && mxf_takes(B > 2 * c ? 2 * c : B) && 2 * c * row_bytes < LIMIT) c *= 2;
+    rows[0] = rows[1] = B < c ? B : c;
+    if (rows[1] * row_bytes >= LIMIT) return p;
+  } else {
     for (int f = 0; f < 2; ++f) {
-      const int Bc = chunk_rows(B, H, f != 0, T);
-      const int ns = (Bc + BS - 1) / BS;
-      const size_t r = ring_bytes(f != 0, BS, ns, H);
-      if (r > m) m = r;
+      int c = (f ? 8 : 4) * (2 * p.ncu / (2 * (H / UC)));   // largest batch of one launch
+      if (c < 4) c = 4;
+      rows[f] = pick_bs(B, H, f != 0, p.ncu) || c > B ? B : c;
+    }
+    if (B * row_bytes >= LIMIT && rows[1] * row_bytes >= LIMIT) return p;
+  }
+  const auto launch_of = [&](bool fwd, int n) {
+    PersistPlan::Launch l = {PERSIST_F32, n, 0, 0};
+    if (!n) return l;
+    if (mx) {
+      l.family = mxf_takes(n) ? PERSIST_MXF : PERSIST_MXH;
+      l.bs = 8;
+      l.ring_bytes = l.family == PERSIST_MXF ? lstm_mxf_ring_bytes(fwd, H) : lstm_mxh_ring_bytes(fwd, H);
+    } else {
+      l.bs = pick_bs(n, H, fwd, p.ncu);
+      if (l.bs && (dbg & 16) && 2 * ((n + 7) / 8) * (H / UC) <= p.ncu) l.bs = 8;     // (experiment: 8 rows per unit wherever they fit)
+      if (l.bs) l.ring_bytes = f32_ring_bytes(fwd, l.bs, (n + l.bs - 1) / l.bs, H);
+    }
+    return l;
+  };
+  p.bwd.full = launch_of(false, rows[0]); p.bwd.tail = launch_of(false, B % rows[0]);
+  p.fwd.full = launch_of(true, rows[1]);  p.fwd.tail = launch_of(true, B % rows[1]);
+  if (!p.fwd.full.bs || !p.bwd.full.bs) return p;
+  p.supported = true;
+
+  // workspace: XCC table | the largest ring | bias-gradient partials.  The ring region also holds either exact-fp32
+  // geometry of the chunk whichever family runs (sizes callers have cached stay what they were)
+  size_t ring = 0;
+  const auto grow = [&ring](size_t r) { if (r > ring) ring = r; };
+  for (int f = 0; f < 2; ++f) {
+    for (int BS = 4; BS <= 8; BS += 4) grow(f32_ring_bytes(f != 0, BS, (rows[f] + BS - 1) / BS, H));
+    const PersistPlan::Pass &ps = f ? p.fwd : p.bwd;
+    grow(ps.full.ring_bytes); grow(ps.tail.ring_bytes);
+    if (mx) {
+      grow(lstm_mxh_ring_bytes(f != 0, H));
+      if (B > lstm_mx_chunk_rows() && mxf_takes(B > 64 ? 64 : B)) grow(lstm_mxf_ring_bytes(f != 0, H));
     }
   }
-  if (lstm_mx_supported(B, H))
-    for (int f = 0; f < 2; ++f) {
-      if (lstm_mxh_ring_bytes(f != 0, H) > m) m = lstm_mxh_ring_bytes(f != 0, H);
-      // (a batch of more than 64 rows runs as launches of 64 rows and a remainder)
-      if (B > lstm_mx_chunk_rows() && lstm_mxf_supported(B > 64 ? 64 : B, H) && lstm_mxf_ring_bytes(f != 0, H) > m)
-        m = lstm_mxf_ring_bytes(f != 0, H);
-    }
-  return TABLE_BYTES + m + db_part_bytes(B, H);
+  p.ws_bytes = TABLE_BYTES + ring + db_part_bytes(B, H);
+
+  const bool one_fwd = p.fwd.full.rows == B;       // the whole batch in one forward launch
+  const bool one_mxh = one_fwd && p.fwd.full.family == PERSIST_MXH;
+  if (env_fuse)
+    p.fuses_input = mx ? one_mxh && D <= 64 && D % 8 == 0
+                       // narrow input (D = 40: 4 rows x D elements fit the 256 lanes of one prefetch)
+                       : D == 40 && (size_t)B * T * D * 4 < LIMIT && p.fwd.full.bs == 4 && (!p.fwd.tail.rows || p.fwd.tail.bs == 4);
+  // (a frame the recurrence never visits is never written: every frame must be visited)
+  p.emits = !dbg && env_emit && max_len == T && one_mxh;
+  p.xws_bytes = mx && p.fuses_input ? lstm_mxh_xws_bytes(B, T) : 0;
+  // (the fp32 kernels' rings depend on the chunking, and several launches sharing a ring each clear it: not offered)
+  p.caller_ring_words = mx && one_fwd ? (TABLE_BYTES + p.fwd.full.ring_bytes + 3) / 4 : 0;
+  return p;
 }
 
 // Co-residency is a REQUIREMENT of these kernels (every workgroup of a unit polls its peers): the grid is
@@ -788,7 +817,7 @@ size_t lstm_persist_ws_bytes(int B, int T, int H) {
 // co-resident must not leave the earlier chunks' in-place updates of the gate buffers behind — the step-wise fallback
 // of LSTM_AUTO restarts from the untouched buffers)
 template <typename K>
-static int launch(K kernel, const PersistArgs &a, int grid, int threads, size_t lds, hipStream_t stream, bool dry) {
+static int launch(K kernel, const PersistArgs &a, int grid, int threads, size_t lds, int ncu, hipStream_t stream, bool dry) {
   const void *fn = reinterpret_cast<const void *>(kernel);
   struct Seen { const void *fn; int dev, threads, blocks; size_t lds; };
   static thread_local Seen seen[32] = {};
@@ -803,86 +832,141 @@ static int launch(K kernel, const PersistArgs &a, int grid, int threads, size_t 
     for (Seen &c : seen)
       if (!c.fn) { c = Seen{fn, dev, threads, blocks, lds}; break; }
   }
-  if ((long long)blocks * cu_count() < grid)
+  if ((long long)blocks * ncu < grid)
     return fail(NABU_EUNSUP, "persistent LSTM: %d workgroups cannot be co-resident (%d per CU x %d CUs on this device)",
-                grid, blocks, cu_count());
+                grid, blocks, ncu);
   if (dry) return 0;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, stream, a);
   NABU_LAUNCH_CHECK();
   return 0;
 }
 
-struct RowMax { unsigned *part; unsigned stride; bool kept; };   // (lstm_persist.h: rowmax) of the chunk at hand
-static int run_chunk(bool fwd, int B, int T, int D, int H, int max_len, const int32_t *len,
-                     const float *const kernel[2], float *const gates[2], float *const cs[2], float *out,
-                     const float *dout, int *status, void *ws, size_t ws_bytes, float *db_part, float *amax_part,
-                     int *shard_base, hipStream_t stream, const float *x, const float *const bias[2], bool dry, RowMax *rm,
-                     const void *xws, int xrow0, const EmitArgs *emit);
-
 // exchange ring + XCC table back to 0xFF bytes: one small kernel (a hipMemsetAsync is its own kind of dispatch and
-// costs ~6 us of queue gap in front of every recurrent launch)
-// The caller of the forward pass may clear the ring in a fill of its own (it has one anyway: lstm.hip, the maxima of
-// the input projection): lstm_persist_ring_seg names the region the launch will want cleared, and
-// lstm_persist_ring_cleared says that it has been.  The note is consumed by the next reset on this host thread, whatever
-// that launch is, and honoured only if it names the same workspace, stream and at least as many bytes.
-static thread_local struct { void *ws; size_t bytes; hipStream_t stream; } g_ring_cleared = {nullptr, 0, nullptr};
-static int ring_reset(void *ws, size_t bytes, hipStream_t stream) {
-  const bool cleared = g_ring_cleared.ws == ws && g_ring_cleared.stream == stream && g_ring_cleared.bytes >= bytes;
-  g_ring_cleared.ws = nullptr;
+// costs ~6 us of queue gap in front of every recurrent launch).  cleared: a fill in front of this launch, on this
+// stream, has already done it (PersistPlan::caller_ring_words)
+static int ring_reset(void *ws, size_t bytes, hipStream_t stream, bool cleared) {
   if (cleared) return 0;
   const FillSeg seg = {ws, (bytes + 3) / 4, 0xFFFFFFFFu};
   return multi_fill(&seg, 1, stream);
 }
-bool lstm_persist_ring_seg(bool fwd, int B, int T, int H, void *ws, FillSeg *seg) {
-  if (!ws || !lstm_mx_supported(B, H)) return false;      // (the fp32 kernels' rings depend on the chunking: not offered)
-  if (chunk_rows(B, H, fwd, T) < B) return false;          // several launches share the ring: each clears it
-  size_t bytes;
-  if (lstm_mxf_supported(B, H)) bytes = TABLE_BYTES + lstm_mxf_ring_bytes(fwd, H);
-  else if (B <= lstm_mx_chunk_rows()) bytes = TABLE_BYTES + lstm_mxh_ring_bytes(fwd, H);
-  else return false;
-  *seg = FillSeg{ws, (bytes + 3) / 4, 0xFFFFFFFFu};
-  return true;
-}
-void lstm_persist_ring_cleared(const FillSeg *seg, hipStream_t stream) {
-  g_ring_cleared.ws = seg ? seg->ptr : nullptr;
-  g_ring_cleared.bytes = seg ? seg->words * 4 : 0;
-  g_ring_cleared.stream = stream;
+
+struct RowMax { unsigned *part; unsigned stride; bool kept; };   // (lstm_persist.h: rowmax) of the chunk at hand
+// the tensors of one pass as the caller gave them (run) resp. advanced to a chunk's first batch row (run_chunk)
+struct PassArgs {
+  const int32_t *len;
+  const float *const *kernel;
+  float *gates[2], *cs[2];
+  float *out;
+  const float *dout;
+  const float *x;
+  const float *const *bias;
+  void *xws;
+  const EmitArgs *emit;
+};
+
+// one launch of ln.rows batch rows starting at row b0 of the batch
+static int run_chunk(bool fwd, const PersistPlan &plan, const PersistPlan::Launch &ln, int b0, const PassArgs &t, int *status,
+                     void *ws, float *db_part, float *amax_part, int *shard_base, hipStream_t stream, bool ring_cleared,
+                     bool dry, RowMax *rm) {
+  const int B = ln.rows, T = plan.T, H = plan.H;
+  PersistArgs a;
+  a.emit = EmitArgs{};
+  if (t.emit && fwd) {
+    assert(plan.emits && b0 == 0);
+    a.emit = *t.emit;
+    a.emit.b0 = b0;
+  }
+  a.rowmax_part = nullptr; a.rowmax_stride = 0;
+  { const char *e = getenv("NABU_PERSIST_DEBUG"); a.dbg = e ? atoi(e) : 0; }
+  a.B = B; a.T = T; a.D = plan.D; a.H = H; a.max_len = plan.max_len; a.nshard = (B + ln.bs - 1) / ln.bs;
+  a.len = t.len;
+  for (int i = 0; i < 2; ++i) { a.kernel[i] = t.kernel[i]; a.gates[i] = t.gates[i]; a.cs[i] = t.cs[i]; a.bias[i] = nullptr; }
+  a.out = t.out; a.dout = t.dout; a.x = nullptr;
+  a.xplanes = nullptr; a.xscale = nullptr;
+  a.db_part = db_part; a.amax_part = amax_part; a.shard_base = *shard_base;
+  *shard_base += a.nshard;
+  a.status = status;
+  a.table = static_cast<unsigned *>(ws);
+  a.xbuf = static_cast<char *>(ws) + TABLE_BYTES;
+  a.timeout_ticks = g_timeout_ticks;
+  const bool xin = fwd && t.x != nullptr;
+  if (xin) { a.bias[0] = t.bias[0]; a.bias[1] = t.bias[1]; }
+  const size_t ring = TABLE_BYTES + ln.ring_bytes;
+  ring_cleared = ring_cleared && plan.caller_ring_words * 4 >= ring;
+  if (ln.family != PERSIST_F32) {
+    if (xin) {       // (the planes of the whole batch were written by run(); this chunk's rows)
+      a.xscale = static_cast<const float *>(t.xws);
+      a.xplanes = static_cast<const char *>(t.xws) + 1024 + (size_t)b0 * T * 256;
+    }
+    if (!dry)
+      if (int e = ring_reset(ws, ring, stream, ring_cleared)) return e;
+    if (ln.family == PERSIST_MXF)     // 33 .. 64 rows at H = 512: sixteen units of 8 rows, 128 gate columns per workgroup
+      return lstm_mxf_launch(fwd, H, a, stream, dry);
+    if (!fwd && rm->part) {     // the backward kernel keeps the frames' maxima of dz
+      a.rowmax_part = rm->part; a.rowmax_stride = rm->stride;
+      rm->kept = true;
+    }
+    return lstm_mxh_launch(fwd, H, a, stream, dry);
+  }
+  const int BS = ln.bs;
+  a.x = t.x;
+  const int XK = xin ? plan.D / 4 : 0;         // (plan.fuses_input: D = 40 on the 4-row geometry)
+  assert(!xin || (XK == 10 && BS == 4));
+  const int NU = 2 * a.nshard, P = H / UC;
+  const int grid = NU * P;
+  const int per_cu = (BS == 4 || grid > plan.ncu) ? 2 : 1;
+  if (grid > per_cu * plan.ncu)
+    return fail(NABU_EUNSUP, "persistent LSTM: %d workgroups > %d x %d CUs", grid, per_cu, plan.ncu);
+  if (!dry)
+    if (int e = ring_reset(ws, ring, stream, ring_cleared)) return e;
+  // dynamic LDS chosen so that exactly `per_cu` workgroups fit on a CU (160 KiB)
+  const size_t lds = BS == 4 ? 64 * 1024 : (grid > plan.ncu ? 72 * 1024 : 96 * 1024);
+#define NABU_PERSIST_CASE(h)                                                                         \
+  case h:                                                                                            \
+    if (XK == 10) return launch(lstm_persist_fwd_kernel<h / 16, 4, 10>, a, grid, 256, lds, plan.ncu, stream, dry);    \
+    if (BS == 4)                                                                                     \
+      return fwd ? launch(lstm_persist_fwd_kernel<h / 16, 4>, a, grid, 256, lds, plan.ncu, stream, dry)        \
+                 : launch(lstm_persist_bwd_kernel<h, 4>, a, grid, 256, lds, plan.ncu, stream, dry);            \
+    return fwd ? launch(lstm_persist_fwd_kernel<h / 32, 8>, a, grid, 512, lds, plan.ncu, stream, dry)          \
+               : launch(lstm_persist_bwd_kernel<h, 8>, a, grid, 512, lds, plan.ncu, stream, dry);
+  switch (H) {
+    NABU_PERSIST_CASE(64)
+    NABU_PERSIST_CASE(128)
+    NABU_PERSIST_CASE(256)
+    NABU_PERSIST_CASE(512)
+  }
+  return fail(NABU_EUNSUP, "persistent LSTM: unsupported H=%d", H);
 }
 
-static thread_local bool g_exact = false;
-void lstm_persist_set_exact(bool exact) { g_exact = exact; }
-bool lstm_persist_exact() { return g_exact; }
-
-static int run(bool fwd, int B, int T, int D, int H, int max_len, const int32_t *len,
-               const float *const kernel[2], float *const gates[2], float *const cs[2], float *out,
-               const float *dout, int *status, void *ws, size_t ws_bytes, float **db_part_out, int *db_rows_out,
-               hipStream_t stream, const float *x = nullptr, const float *const bias[2] = nullptr, uint32_t *rowmax = nullptr,
-               bool *rowmax_done = nullptr, void *xws = nullptr, const EmitArgs *emit = nullptr) {
-  if (!lstm_persist_supported(B, T, H)) return fail(NABU_EUNSUP, "persistent LSTM: unsupported B=%d H=%d", B, H);
-  const size_t need = lstm_persist_ws_bytes(B, T, H);
-  if (ws_bytes < need) return fail(NABU_EWS, "persistent LSTM: workspace %zu < %zu", ws_bytes, need);
-  float *db_part = reinterpret_cast<float *>(static_cast<char *>(ws) + need - db_part_bytes(B, H));
+static int run(bool fwd, const PersistPlan &plan, const PassArgs &t, int *status, void *ws, size_t ws_bytes,
+               float **db_part_out, int *db_rows_out, hipStream_t stream, bool ring_cleared, uint32_t *rowmax,
+               bool *rowmax_done) {
+  const int B = plan.B, T = plan.T, H = plan.H;
+  if (!plan.supported) return fail(NABU_EUNSUP, "persistent LSTM: unsupported B=%d H=%d", B, H);
+  if (ws_bytes < plan.ws_bytes) return fail(NABU_EWS, "persistent LSTM: workspace %zu < %zu", ws_bytes, plan.ws_bytes);
+  assert(!t.x || (fwd && plan.fuses_input && t.bias && (plan.xws_bytes == 0 || t.xws)));
+  float *db_part = reinterpret_cast<float *>(static_cast<char *>(ws) + plan.ws_bytes - db_part_bytes(B, H));
   float *amax_part = db_part + db_part_bytes(B, H) / (2 * sizeof(float));
+  const PersistPlan::Pass &ps = fwd ? plan.fwd : plan.bwd;
   int shards = 0;
-  const int Bc = chunk_rows(B, H, fwd, T);
   bool kept = rowmax != nullptr;
   for (int pass = 0; pass < 2; ++pass) {     // pass 0 validates every chunk, pass 1 enqueues them
     shards = 0;
-    if (pass == 1 && fwd && x && lstm_mx_supported(B, H)) {
-      FillSeg ring;      // cleared by prepare_x's own fill
-      const bool with_ring = lstm_persist_ring_seg(true, B, T, H, ws, &ring);
-      if (int e = lstm_mxh_prepare_x(B, T, D, x, xws, stream, with_ring ? &ring : nullptr)) return e;
-      if (with_ring) lstm_persist_ring_cleared(&ring, stream);
+    if (pass == 1 && t.x && plan.xws_bytes) {     // the fp16-plane kernels read x as planes; the fill clears the ring too
+      const FillSeg ring = {ws, plan.caller_ring_words, 0xFFFFFFFFu};
+      if (int e = lstm_mxh_prepare_x(B, T, plan.D, t.x, t.xws, stream, ring.words ? &ring : nullptr)) return e;
+      ring_cleared = ring.words > 0;
     }
-    for (int b0 = 0; b0 < B; b0 += Bc) {
+    for (int b0 = 0; b0 < B; b0 += ps.full.rows) {
       RowMax rm = {rowmax ? rowmax + (size_t)b0 * T : nullptr, (unsigned)((size_t)B * T), false};
-      const int nb = B - b0 < Bc ? B - b0 : Bc;
-      float *g2[2] = {gates[0] + (size_t)b0 * T * 4 * H, gates[1] + (size_t)b0 * T * 4 * H};
-      float *c2[2] = {cs[0] + (size_t)b0 * T * H, cs[1] + (size_t)b0 * T * H};
-      const int e = run_chunk(fwd, nb, T, D, H, max_len, len + b0, kernel, g2, c2,
-                              out ? out + (size_t)b0 * T * 2 * H : nullptr,
-                              dout ? dout + (size_t)b0 * T * 2 * H : nullptr, status, ws, ws_bytes, db_part, amax_part, &shards,
-                              stream, x ? x + (size_t)b0 * T * D : nullptr, bias, pass == 0, &rm, xws, b0, emit);
+      PassArgs c = t;
+      c.len = t.len + b0;
+      for (int i = 0; i < 2; ++i) { c.gates[i] = t.gates[i] + (size_t)b0 * T * 4 * H; c.cs[i] = t.cs[i] + (size_t)b0 * T * H; }
+      if (t.out) c.out = t.out + (size_t)b0 * T * 2 * H;
+      if (t.dout) c.dout = t.dout + (size_t)b0 * T * 2 * H;
+      if (t.x) c.x = t.x + (size_t)b0 * T * plan.D;
+      const int e = run_chunk(fwd, plan, B - b0 < ps.full.rows ? ps.tail : ps.full, b0, c, status, ws, db_part, amax_part,
+                              &shards, stream, ring_cleared, pass == 0, &rm);
       if (e) return e;
       kept = kept && rm.kept;
     }
@@ -893,143 +977,20 @@ static int run(bool fwd, int B, int T, int D, int H, int max_len, const int32_t 
   return 0;
 }
 
-static int run_chunk(bool fwd, int B, int T, int D, int H, int max_len, const int32_t *len,
-                     const float *const kernel[2], float *const gates[2], float *const cs[2], float *out,
-                     const float *dout, int *status, void *ws, size_t ws_bytes, float *db_part, float *amax_part,
-                     int *shard_base, hipStream_t stream, const float *x, const float *const bias[2], bool dry, RowMax *rm,
-                     const void *xws, int xrow0, const EmitArgs *emit) {
-  PersistArgs a;
-  a.emit = EmitArgs{};
-  if (emit && fwd) {
-    // only the fp16-plane kernels with 16 units per workgroup write companions (the caller asked lstm_persist_emits)
-    if (!lstm_persist_emits(B, T, H, max_len) || xrow0 != 0)
-      return fail(NABU_EINVAL, "persistent LSTM: this launch cannot write the packed companions");
-    a.emit = *emit;
-    a.emit.b0 = xrow0;
-  }
-  a.rowmax_part = nullptr; a.rowmax_stride = 0;
-  { const char *e = getenv("NABU_PERSIST_DEBUG"); a.dbg = e ? atoi(e) : 0; }
-  if (lstm_mx_supported(B, H)) {
-    const bool xin = fwd && x != nullptr;
-    if (xin && (lstm_mxf_supported(B, H) || B > lstm_mx_chunk_rows() || !bias || !xws || D > 64 || D % 8))
-      return fail(NABU_EINVAL, "persistent LSTM (mxh): the in-kernel input projection does not take this shape");
-    a.B = B; a.T = T; a.D = D; a.H = H; a.max_len = max_len; a.nshard = (B + 7) / 8;
-    a.len = len;
-    for (int i = 0; i < 2; ++i) { a.kernel[i] = kernel[i]; a.gates[i] = gates[i]; a.cs[i] = cs[i]; a.bias[i] = nullptr; }
-    a.out = out; a.dout = dout; a.x = nullptr;
-    a.xplanes = nullptr; a.xscale = nullptr;
-    if (xin) {       // (the planes of the whole batch were written by run(); this chunk's rows)
-      a.xscale = static_cast<const float *>(xws);
-      a.xplanes = static_cast<const char *>(xws) + 1024 + (size_t)xrow0 * T * 256;
-      a.bias[0] = bias[0]; a.bias[1] = bias[1];
-    }
-    a.db_part = db_part; a.amax_part = amax_part; a.shard_base = *shard_base;
-    *shard_base += a.nshard;
-    a.status = status;
-    a.table = static_cast<unsigned *>(ws);
-    a.xbuf = static_cast<char *>(ws) + TABLE_BYTES;
-    a.timeout_ticks = g_timeout_ticks;
-    if (lstm_mxf_supported(B, H)) {     // 33 .. 64 rows at H = 512: sixteen units of 8 rows, 128 gate columns per workgroup
-      if (!dry)
-        if (int e = ring_reset(ws, TABLE_BYTES + lstm_mxf_ring_bytes(fwd, H), stream)) return e;
-      return lstm_mxf_launch(fwd, H, a, stream, dry);
-    }
-    if (B > lstm_mx_chunk_rows()) return fail(NABU_EINVAL, "persistent LSTM (mxh): a launch takes <= %d rows", lstm_mx_chunk_rows());
-    if (!dry)
-      if (int e = ring_reset(ws, TABLE_BYTES + lstm_mxh_ring_bytes(fwd, H), stream)) return e;
-    if (!fwd && rm->part) {     // the backward kernel keeps the frames' maxima of dz
-      a.rowmax_part = rm->part; a.rowmax_stride = rm->stride;
-      rm->kept = true;
-    }
-    return lstm_mxh_launch(fwd, H, a, stream, dry);
-  }
-  int BS = pick_bs(B, H, fwd);
-  if ((a.dbg & 16) && 2 * ((B + 7) / 8) * (H / UC) <= cu_count()) BS = 8;
-  a.B = B; a.T = T; a.D = D; a.H = H; a.max_len = max_len; a.nshard = (B + BS - 1) / BS;
-  a.len = len;
-  for (int i = 0; i < 2; ++i) { a.kernel[i] = kernel[i]; a.gates[i] = gates[i]; a.cs[i] = cs[i]; }
-  a.out = out; a.dout = dout;
-  a.x = x; a.bias[0] = bias ? bias[0] : nullptr; a.bias[1] = bias ? bias[1] : nullptr;
-  a.xplanes = nullptr; a.xscale = nullptr;
-  const int XK = (fwd && x && bias && BS == 4 && lstm_persist_fuses_input(B, T, D, H)) ? D / 4 : 0;
-  if (fwd && x && !XK) return fail(NABU_EINVAL, "persistent LSTM: the in-kernel input projection does not take this shape");
-  a.db_part = db_part; a.shard_base = *shard_base;
-  a.amax_part = amax_part;
-  *shard_base += a.nshard;
-  a.status = status;
-  a.table = static_cast<unsigned *>(ws);
-  a.xbuf = static_cast<char *>(ws) + TABLE_BYTES;
-  a.timeout_ticks = g_timeout_ticks;
-  const int NU = 2 * a.nshard, P = H / UC;
-  const int grid = NU * P;
-  const int per_cu = (BS == 4 || grid > cu_count()) ? 2 : 1;
-  if (grid > per_cu * cu_count())
-    return fail(NABU_EUNSUP, "persistent LSTM: %d workgroups > %d x %d CUs", grid, per_cu, cu_count());
-  if (!dry)
-    if (int e = ring_reset(ws, TABLE_BYTES + ring_bytes(fwd, BS, a.nshard, H), stream)) return e;
-  // dynamic LDS chosen so that exactly `per_cu` workgroups fit on a CU (160 KiB)
-  const size_t lds = BS == 4 ? 64 * 1024 : (grid > cu_count() ? 72 * 1024 : 96 * 1024);
-#define NABU_PERSIST_CASE(h)                                                                         \
-  case h:                                                                                            \
-    if (XK == 10) return launch(lstm_persist_fwd_kernel<h / 16, 4, 10>, a, grid, 256, lds, stream, dry);    \
-    if (BS == 4)                                                                                     \
-      return fwd ? launch(lstm_persist_fwd_kernel<h / 16, 4>, a, grid, 256, lds, stream, dry)        \
-                 : launch(lstm_persist_bwd_kernel<h, 4>, a, grid, 256, lds, stream, dry);            \
-    return fwd ? launch(lstm_persist_fwd_kernel<h / 32, 8>, a, grid, 512, lds, stream, dry)          \
-               : launch(lstm_persist_bwd_kernel<h, 8>, a, grid, 512, lds, stream, dry);
-  switch (H) {
-    NABU_PERSIST_CASE(64)
-    NABU_PERSIST_CASE(128)
-    NABU_PERSIST_CASE(256)
-    NABU_PERSIST_CASE(512)
-  }
-  return fail(NABU_EUNSUP, "persistent LSTM: unsupported H=%d", H);
-}
-
-int lstm_persist_fwd(int B, int T, int D, int H, int max_len, const int32_t *len,
+int lstm_persist_fwd(const PersistPlan &plan, const int32_t *len,
                      const float *const kernel[2], float *const gates[2], float *const cs[2],
-                     float *out, int *status, void *ws, size_t ws_bytes, hipStream_t stream, const float *x,
-                     const float *const bias[2], void *xws, const EmitArgs *emit) {
-  return run(true, B, T, D, H, max_len, len, kernel, gates, cs, out, nullptr, status, ws, ws_bytes, nullptr, nullptr,
-             stream, x, bias, nullptr, nullptr, xws, emit);
-}
-// companions come out of the kernel itself only on the fp16-plane kernels with 16 units per workgroup, ONE launch of
-// <= 32 rows (lstm_persist_mxh.hip), when the recurrence visits every frame (a frame it never visits is never written)
-// and no debug variant is selected
-bool lstm_persist_emits(int B, int T, int H, int max_len) {
-  if (getenv("NABU_PERSIST_DEBUG") && atoi(getenv("NABU_PERSIST_DEBUG"))) return false;
-  static int env = -1;
-  if (env < 0) { const char *e = getenv("NABU_PERSIST_EMIT"); env = e ? atoi(e) : 1; }
-  if (!env || max_len != T || !lstm_persist_supported(B, T, H) || !lstm_mx_supported(B, H)) return false;
-  return B <= lstm_mx_chunk_rows() && !lstm_mxf_supported(B, H);
-}
-// (sized from the ONE eligibility test, lstm_persist_fuses_input: no workspace where the projection is not taken)
-size_t lstm_persist_xws_bytes(int B, int T, int D, int H) {
-  return (lstm_mx_supported(B, H) && lstm_persist_fuses_input(B, T, D, H)) ? lstm_mxh_xws_bytes(B, T) : 0;
+                     float *out, int *status, void *ws, size_t ws_bytes, hipStream_t stream, bool ring_cleared,
+                     const float *x, const float *const bias[2], void *xws, const EmitArgs *emit) {
+  const PassArgs t = {len, kernel, {gates[0], gates[1]}, {cs[0], cs[1]}, out, nullptr, x, bias, xws, emit};
+  return run(true, plan, t, status, ws, ws_bytes, nullptr, nullptr, stream, ring_cleared, nullptr, nullptr);
 }
 
-// narrow input (D = 40: 4 rows x D elements fit the 256 lanes of one prefetch), every launch of the forward pass on the
-// 4-row geometry: the kernel projects the input itself (no x . Wx GEMM in front of it)
-bool lstm_persist_fuses_input(int B, int T, int D, int H) {
-  static int env = -1;
-  if (env < 0) { const char *e = getenv("NABU_PERSIST_FUSE_INPUT"); env = e ? atoi(e) : 1; }
-  if (!env || !lstm_persist_supported(B, T, H)) return false;
-  if (lstm_mx_supported(B, H))     // fp16-plane kernels: any narrow input of <= 64 features, one launch of <= 32 rows
-    return D <= 64 && D % 8 == 0 && B <= lstm_mx_chunk_rows() && !lstm_mxf_supported(B, H);
-  if (D != 40) return false;
-  if ((size_t)B * T * D * 4 >= 0x80000000ull) return false;
-  const int Bc = chunk_rows(B, H, true, T);
-  for (int b0 = 0; b0 < B; b0 += Bc)
-    if (pick_bs(B - b0 < Bc ? B - b0 : Bc, H, true) != 4) return false;
-  return true;
-}
-
-int lstm_persist_bwd(int B, int T, int D, int H, int max_len, const int32_t *len,
+int lstm_persist_bwd(const PersistPlan &plan, const int32_t *len,
                      const float *const kernel[2], float *const gates[2], float *const cs[2],
                      const float *dout, int *status, void *ws, size_t ws_bytes, float **db_part, int *db_rows,
                      hipStream_t stream, uint32_t *rowmax, bool *rowmax_done) {
-  return run(false, B, T, D, H, max_len, len, kernel, gates, cs, nullptr, dout, status, ws, ws_bytes, db_part, db_rows,
-             stream, nullptr, nullptr, rowmax, rowmax_done);
+  const PassArgs t = {len, kernel, {gates[0], gates[1]}, {cs[0], cs[1]}, nullptr, dout, nullptr, nullptr, nullptr, nullptr};
+  return run(false, plan, t, status, ws, ws_bytes, db_part, db_rows, stream, false, rowmax, rowmax_done);
 }
 
 }  // namespace nabu

@@ -641,12 +641,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
 // ===========================================================================
 // host side (called from lstm_persist.hip's run_chunk)
-bool lstm_mxf_supported(int B, int H) {
-  static int env = -1;
-  if (env < 0) { const char *e = getenv("NABU_PERSIST_MXF"); env = e ? atoi(e) : 1; }
-  return env != 0 && H == 512 && (B > 32 || env == 2) && B <= 64;     // 2: also batches of <= 32 rows (measurements)
-}
-
+// (which batches these kernels take: lstm_persist_plan)
 size_t lstm_mxf_ring_bytes(bool fwd, int H) {
   const size_t P = H / MXF_UC;
   return fwd ? (size_t)MXF_NU * RING * 16 * H * 2 : (size_t)MXF_NU * MXHRINGB * P * P * MXR * MXF_UC * 4;

@@ -27,6 +27,8 @@
 // are parked under tools/experiments/variants/.
 #include "lstm_persist_mxh.h"
 
+#include <assert.h>
+
 namespace nabu {
 
 // experiment (off in the library build): the l plane of W_h in accumulation registers, fed to the matrix instruction
@@ -543,34 +545,7 @@ int lstm_mxh_prepare_x(int B, int T, int D, const float *x, void *ws, hipStream_
 
 // ===========================================================================
 // host side (called from lstm_persist.hip's run_chunk)
-// NABU_PERSIST_MX=0: the exact-fp32 kernels of lstm_persist.hip for every shape (a per-call form of the same switch:
-// nabu_blstm_desc.recurrent_precision = NABU_REC_F32, lstm_persist_set_exact)
-static int mx_env() {
-  static int env = -1;
-  if (env < 0) { const char *e = getenv("NABU_PERSIST_MX"); env = e ? atoi(e) : 1; }
-  return env;
-}
-
-// the geometry needs a whole MI355X: 8 XCDs of 32 CUs, one workgroup per CU
-static bool mx_device_ok() {
-  static thread_local int cached_dev = -1;
-  static thread_local bool ok = false;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return false; }
-  if (dev != cached_dev) {
-    int cus = 0;
-    ok = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus >= NCU;
-    if (!ok) (void)hipGetLastError();
-    cached_dev = dev;
-  }
-  return ok;
-}
-
-// do the fp16-plane kernels (this file, lstm_persist_mxf.hip) take the shape?
-bool lstm_mx_supported(int B, int H) {
-  if (!mx_env() || lstm_persist_exact() || !mx_device_ok()) return false;
-  return (H == 128 || H == 256 || H == 512) && B >= 1;
-}
+// (which shapes these kernels take, and on which device: lstm_persist_plan)
 int lstm_mx_chunk_rows() { return MXR * MXNU / 2; }   // 32 batch rows per launch (8 per unit)
 
 size_t lstm_mxh_ring_bytes(bool fwd, int H) {
@@ -595,7 +570,7 @@ int lstm_mxh_launch(bool fwd, int H, const PersistArgs &a, hipStream_t stream, b
     return a.dbg ? mxh_launch(lstm_mxh_fwd_kernel<h, true>, a, grid, MxhFwdLds<h>::TOTAL * sizeof(float), stream, dry) \
                  : mxh_launch(lstm_mxh_fwd_kernel<h, false>, a, grid, MxhFwdLds<h>::TOTAL * sizeof(float), stream, dry);
   const bool emit = a.emit.x_rows || a.emit.x_cols || a.emit.hT[0] || a.emit.hT[1];
-  if (emit && (a.dbg || !fwd)) return fail(NABU_EINVAL, "persistent LSTM (mxh): packed companions are written by the plain forward kernel only");
+  assert(!emit || (fwd && !a.dbg));      // (PersistPlan::emits: the plain forward kernel only)
   if (!fwd) return lstm_mxh_bwd_launch(H, a, stream, dry);      // lstm_persist_mxh_bwd.hip
   switch (H) {
     NABU_MXH_CASE(128)
