@@ -43,8 +43,11 @@ __global__ __launch_bounds__(256) void ctc_kernel(CtcArgs p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int T = p.T, C = p.C, Smax = p.Smax, blank = p.C - 1;
-  float *lse = smem;                       // [T]
-  float *row0 = lse + T;                   // [Smax] alpha/beta ping
+  // log-softmax is (x - mx) - lz: kept apart, a frame whose winning class has probability ~1 keeps its small
+  // -log p to float32 precision (mx + lz would round it to an ulp of the frame maximum)
+  float *mx = smem;                        // [T] frame maximum of the logits
+  float *lz = mx + T;                      // [T] log sum exp(x - mx)
+  float *row0 = lz + T;                    // [Smax] alpha/beta ping
   float *row1 = row0 + Smax;               // [Smax] alpha/beta pong
   float *gam = row1 + Smax;                // [Smax]
   float *csum = gam + Smax;                // [C]
@@ -75,7 +78,8 @@ __global__ __launch_bounds__(256) void ctc_kernel(CtcArgs p) {
     for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
     float z = 0.f;
     for (int c = 0; c < C; ++c) z += expf(x[c] - m);
-    lse[t] = m + logf(z);
+    mx[t] = m;
+    lz[t] = logf(z);
   }
   __syncthreads();
   if (tid == 0) {
@@ -107,20 +111,20 @@ __global__ __launch_bounds__(256) void ctc_kernel(CtcArgs p) {
   float *prev = row0, *cur = row1;
   for (int s = tid; s < S; s += 256) {
     float a = CTC_NEG;
-    if (s < 2) a = lg[ext[s]] - lse[0];
+    if (s < 2) a = (lg[ext[s]] - mx[0]) - lz[0];
     prev[s] = a;
     al[s] = a;
   }
   __syncthreads();
   for (int t = 1; t < Tb; ++t) {
     const float *x = lg + (size_t)t * C;
-    const float z = lse[t];
+    const float m = mx[t], z = lz[t];
     for (int s = tid; s < S; s += 256) {
       const int e = ext[s];
       const float a0 = prev[s];
       const float a1 = s >= 1 ? prev[s - 1] : CTC_NEG;
       const float a2 = (s >= 2 && e != blank && e != ext[s - 2]) ? prev[s - 2] : CTC_NEG;
-      const float a = lse3(a0, a1, a2) + (x[e] - z);
+      const float a = lse3(a0, a1, a2) + ((x[e] - m) - z);
       cur[s] = a;
       al[(size_t)t * Smax + s] = a;
     }
@@ -139,10 +143,10 @@ __global__ __launch_bounds__(256) void ctc_kernel(CtcArgs p) {
   float *bnext = row0, *bcur = row1;
   for (int t = Tb - 1; t >= 0; --t) {
     const float *x = lg + (size_t)t * C;
-    const float z = lse[t];
+    const float m = mx[t], z = lz[t];
     for (int s = tid; s < S; s += 256) {
       const int e = ext[s];
-      const float ye = x[e] - z;
+      const float ye = (x[e] - m) - z;
       float bt;
       if (t == Tb - 1) {
         bt = (s >= S - 2) ? ye : CTC_NEG;
@@ -171,7 +175,7 @@ __global__ __launch_bounds__(256) void ctc_kernel(CtcArgs p) {
     }
     __syncthreads();
     for (int c = tid; c < C; c += 256)
-      dl[(size_t)t * C + c] = p.scale * (expf(x[c] - z) - csum[c]);
+      dl[(size_t)t * C + c] = p.scale * (expf((x[c] - m) - z) - csum[c]);
     float *tmp = bnext; bnext = bcur; bcur = tmp;
   }
 }
@@ -182,9 +186,11 @@ __global__ __launch_bounds__(256) void ctc_kernel(CtcArgs p) {
 // pair (blank 2i, label 2i+1) of the lattice, so a frame of the alpha (beta) recursion needs exactly one
 // (two) neighbour values, fetched with a DPP wave shift; the frame's logits are prefetched one frame
 // ahead, its log-sum-exp is reduced with DPP while the recursion of the current frame waits for its
-// exp/log latencies.  For label sequences of up to 63 symbols and up to 256 classes (cfg1-cfg5:
-// <= 60 phones, 40 classes); longer ones take the workgroup kernel above.  Same arithmetic, same
-// outputs, deterministic (class sums walk fixed occurrence chains).
+// exp/log latencies.  For label sequences of up to 63 symbols whose logits, alpha lattice and class
+// sums fit 150 KiB of LDS (ctc_wave_lds_bytes; cfg1-cfg5: <= 60 phones, 40 classes); any number of classes
+// (every class loop strides over the wave or the workgroup; tests/test_hip_ctc.py runs C = 64 .. 300);
+// everything else takes the workgroup kernel above.  Same recursion in base-2 logarithms, same outputs,
+// deterministic (class sums walk fixed occurrence chains).
 __device__ __forceinline__ float dpp_up(float v, float fill) {     // lane i <- lane i-1 (lane 0 <- fill)
   return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x138, 0xf, 0xf, false));
 }
@@ -237,11 +243,10 @@ __global__ __launch_bounds__(256) void ctc_wave_kernel(CtcArgs p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = threadIdx.x & 63;
   const int T = p.T, C = p.C, Smax = p.Smax, blank = p.C - 1;
-  // everything the two sweeps touch lives in LDS: the utterance's logits, their per-frame
-  // log-sum-exp and the alpha lattice (HBM latency would otherwise sit on every frame)
-  float *xs = smem;                  // [T*C] logits
-  float *lse = xs + (size_t)T * C;   // [T]
-  float *as = lse + T;               // [T*Smax] alpha
+  // everything the two sweeps touch lives in LDS: the utterance's log-probabilities and the
+  // alpha lattice (HBM latency would otherwise sit on every frame)
+  float *xs = smem;                  // [T*C] logits; the prologue turns them into base-2 log-softmax IN PLACE
+  float *as = xs + (size_t)T * C;    // [T*Smax] alpha
   float *csum = as + (size_t)T * Smax;   // [C] per-class occupation of the current frame
   float *gam = csum + C;             // [64]
   int *lbl = reinterpret_cast<int *>(gam + 64);   // [64] labels
@@ -274,13 +279,16 @@ __global__ __launch_bounds__(256) void ctc_wave_kernel(CtcArgs p) {
   const int lab = lane < L ? p.labels[(size_t)b * p.Lmax + lane] : -1;
   if (tid < 64) lbl[lane] = lab;
   __syncthreads();
+  constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
   for (int t = tid; t < Tb; t += 256) {
-    const float *x = xs + (size_t)t * C;
+    float *x = xs + (size_t)t * C;
     float m = x[0];
     for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
     float z = 0.f;
     for (int c = 0; c < C; ++c) z += __expf(x[c] - m);
-    lse[t] = m + __logf(z);
+    // (x - max) - log z, not x - (max + log z): a winning class of probability ~1 keeps its small -log p (ctc_kernel)
+    const float lz = __logf(z);
+    for (int c = 0; c < C; ++c) x[c] = ((x[c] - m) - lz) * LOG2E;
   }
   __syncthreads();
   // ONE wave runs the two sweeps (the dependent chain: 2 T frames of a few dozen instructions); the other three turn the
@@ -305,7 +313,6 @@ __global__ __launch_bounds__(256) void ctc_wave_kernel(CtcArgs p) {
     for (int j = L - 1; j > lane; --j) nxt = lbl[j] == lab ? j : nxt;
   }
   const bool hasB = lane <= L, hasL = lane < L;
-  constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
   if (wv > 0) {
     if (bad) return;                     // (every wave reaches the same verdict from the same LDS contents)
     // (nxtl is written by the sweeping wave below; read here only behind `go`)
@@ -315,7 +322,6 @@ __global__ __launch_bounds__(256) void ctc_wave_kernel(CtcArgs p) {
     for (int i = wv - 1; i < Tb; i += 3) {
       const int t = Tb - 1 - i;
       while (__hip_atomic_load(prog, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= i) __builtin_amdgcn_s_sleep(1);
-      const float z = lse[t];
       const float gB = hasB ? as[(size_t)t * Smax + 2 * lane] : 0.f;
       const float gL = hasL ? as[(size_t)t * Smax + 2 * lane + 1] : 0.f;
       const float sumB = wave_sum_dpp(gB);
@@ -329,7 +335,7 @@ __global__ __launch_bounds__(256) void ctc_wave_kernel(CtcArgs p) {
       if (lane == 0) csum_w[blank] = sumB;
       WSYNC();
       for (int c = lane; c < C; c += 64)
-        dl[(size_t)t * C + c] = p.scale * (__builtin_amdgcn_exp2f((xs[(size_t)t * C + c] - z) * LOG2E) - csum_w[c]);
+        dl[(size_t)t * C + c] = p.scale * (__builtin_amdgcn_exp2f(xs[(size_t)t * C + c]) - csum_w[c]);
       WSYNC();
     }
     return;
@@ -350,11 +356,11 @@ __global__ __launch_bounds__(256) void ctc_wave_kernel(CtcArgs p) {
 
   // ---- alpha sweep --------------------------------------------------------
   float aB = CTC_NEG, aL = CTC_NEG;
-  float yB = (xs[blank] - lse[0]) * LOG2E, yL = (xs[labc] - lse[0]) * LOG2E;     // base-2 from here on
+  float yB = xs[blank], yL = xs[labc];     // base-2 log-probabilities (prologue)
   for (int t = 0; t < Tb; ++t) {
     // next frame's emission log-probabilities: independent of the recursion, issued first
     const int tn = t + 1 < Tb ? t + 1 : t;
-    const float zn = lse[tn], xBn = xs[(size_t)tn * C + blank], xLn = xs[(size_t)tn * C + labc];
+    const float yBn = xs[(size_t)tn * C + blank], yLn = xs[(size_t)tn * C + labc];
     if (t == 0) {
       aB = lane == 0 ? yB : CTC_NEG;
       aL = (lane == 0 && hasL) ? yL : CTC_NEG;
@@ -367,8 +373,8 @@ __global__ __launch_bounds__(256) void ctc_wave_kernel(CtcArgs p) {
     }
     if (hasB) as[(size_t)t * Smax + 2 * lane] = aB;
     if (hasL) as[(size_t)t * Smax + 2 * lane + 1] = aL;
-    yB = (xBn - zn) * LOG2E;
-    yL = (xLn - zn) * LOG2E;
+    yB = yBn;
+    yL = yLn;
   }
   const float ll = L >= 1 ? lse2_fast(__shfl(aB, L), __shfl(aL, L - 1)) : __shfl(aB, 0);
   if (lane == 0) p.nll[b] = -ll * LN2;
@@ -378,9 +384,8 @@ __global__ __launch_bounds__(256) void ctc_wave_kernel(CtcArgs p) {
   // ---- beta sweep: the frame's occupations replace alpha[t], the workers take it from there ----------
   float bB = CTC_NEG, bL = CTC_NEG;
   for (int t = Tb - 1; t >= 0; --t) {
-    const float z = lse[t];
-    yB = (xs[(size_t)t * C + blank] - z) * LOG2E;
-    yL = (xs[(size_t)t * C + labc] - z) * LOG2E;
+    yB = xs[(size_t)t * C + blank];
+    yL = xs[(size_t)t * C + labc];
     const float aB0 = hasB ? as[(size_t)t * Smax + 2 * lane] : 0.f;
     const float aL0 = hasL ? as[(size_t)t * Smax + 2 * lane + 1] : 0.f;
     if (t == Tb - 1) {
@@ -402,11 +407,11 @@ __global__ __launch_bounds__(256) void ctc_wave_kernel(CtcArgs p) {
 
 #undef WSYNC
 static size_t ctc_wave_lds_bytes(int T, int C, int Smax) {
-  return ((size_t)T * C + T + (size_t)T * Smax + C + 64 + 2 + 3 * 64 + 3 * (size_t)C) * sizeof(float) + (128 + 2) * sizeof(int);
+  return ((size_t)T * C + (size_t)T * Smax + C + 64 + 2 + 3 * 64 + 3 * (size_t)C) * sizeof(float) + (128 + 2) * sizeof(int);
 }
 
 static size_t ctc_lds_bytes(int T, int C, int Smax) {
-  return ((size_t)T + 3 * Smax + C) * sizeof(float) + ((size_t)2 * Smax + C) * sizeof(int);
+  return ((size_t)2 * T + 3 * Smax + C) * sizeof(float) + ((size_t)2 * Smax + C) * sizeof(int);
 }
 
 }  // namespace nabu
