@@ -686,12 +686,76 @@ int nabu_beam_gather(int B, int W, int F, const float *fresh, const float *old, 
                      const int32_t *stay, float *dst, nabu_stream_t stream);
 
 /* ------------------------------------------------------------------------
- * Host-side helper of the on-disk data path (the only entry point that takes HOST memory):
+ * Host-side helper of the on-disk data path (host memory, as the `_host` feature queries below):
  * CRC-32C (Castagnoli) of `n` bytes, continuing from `crc` (0 to start) — the checksum of the
  * TFRecord framing of the reference's per-utterance files.
  * Replaces: tf.python_io.TFRecordWriter / tf.TFRecordReader record checks
  * (nabu/processing/tfwriters/tfwriter.py:30-45, nabu/processing/tfreaders/tfreader.py:71-92). */
 uint32_t nabu_crc32c_host(const void *data_host, size_t n, uint32_t crc);
+
+/* ------------------------------------------------------------------------
+ * Feature computation from audio: log mel filterbank (fbank) and MFCC features of a RAGGED BATCH of
+ * utterances in two launches, whatever the number of utterances.
+ * Replaces: nabu/processing/processors/feature_computers/{fbank,mfcc,base,sigproc}.py (numpy/scipy) and
+ * the normalisation of processors/audio_processor.py:49-51.  Per utterance:
+ *   snip:   num = trunc((len - winlen*rate) / (winstep*rate)); the first
+ *           trunc(num*winstep*rate + winlen*rate) samples are kept (all of them if that is more);
+ *   pre-emphasis on the kept samples: y[0] = s[0], y[i] = s[i] - preemph * s[i-1];
+ *   frames of frame_len samples every frame_step samples, the last one zero padded, NO analysis window:
+ *           one frame if kept <= frame_len, else 1 + ceil((kept - frame_len) / frame_step);
+ *   power spectrum |rfft(frame, nfft)|^2 / nfft over nfft/2+1 bins; energy = sum of the bins;
+ *   mel filterbank of nfilt triangles between lowfreq and highfreq (bin edges floor((nfft+1)*hz/rate));
+ *           an energy or a filter output that is exactly 0 is replaced by 2^-52 before the logarithm;
+ *   NABU_FEAT_FBANK: log(filter outputs); NABU_FEAT_MFCC: the first numcep coefficients of their
+ *           orthonormal type-2 DCT, times 1 + (L/2) sin(pi n / L) when L = ceplifter > 0;
+ *   include_energy: log(energy) is one more column behind them;
+ *   dynamic 1 / 2: first (and second) derivative columns behind the static ones,
+ *           d[t] = 2 x[t+2] + x[t+1] - x[t-1] - 2 x[t-2], the sequence reflected at its ends
+ *           (... b a | a b c ... y z | z y ...), as often as a short utterance needs;
+ *   mvn: every column minus its mean over the utterance, over its population standard deviation
+ *           (two passes; a constant column divides by zero, as in the reference).
+ * frame_len and frame_step must be winlen*rate and winstep*rate rounded half away from zero (the
+ * rounding of the reference's Python 2).  nfft is a power of two in 256..2048 and frame_len <= nfft,
+ * anything else is NABU_EUNSUP (numpy's rfft would crop the frame instead).  highfreq < 0 means rate/2.
+ * Every reduction is a fixed tree inside one utterance: an utterance's features do not depend on the
+ * rest of the batch.
+ *
+ * The host-side queries take HOST memory and touch no device:
+ *   nabu_feat_num_frames   frames of an utterance of n_samples (>= 1) samples, or a negative NABU_E*;
+ *   nabu_feat_plan_host    for n_utt utterances whose samples lie at sample_offsets_host[u] ..
+ *                          sample_offsets_host[u+1] of one buffer: frame_offsets_host [n_utt+1] (row of
+ *                          the output matrix each utterance starts at) and kept_host [n_utt] (samples
+ *                          left by the snip);
+ *   nabu_feat_ws_bytes     size of the table workspace (0 and a message for a bad descriptor);
+ *   nabu_feat_tables_host  fills ws_host with the tables (twiddles, filter bands and weights, DCT),
+ *                          computed in double precision; the caller copies them to the device once per
+ *                          descriptor and passes that copy as `ws` of every nabu_feat_compute.
+ * nabu_feat_compute: samples int16 (all utterances concatenated), sample_offsets / frame_offsets
+ * [n_utt+1] and kept [n_utt] as planned above, max_frames = the largest frame count in the batch;
+ * out [frame_offsets[n_utt], dim] float32 with dim = (nfilt or numcep, + include_energy) * (1 + dynamic). */
+enum { NABU_FEAT_FBANK = 0, NABU_FEAT_MFCC = 1 };
+typedef struct {
+  uint32_t size;              /* sizeof(nabu_feat_desc) */
+  int32_t rate;               /* samples per second */
+  int32_t frame_len, frame_step;
+  int32_t nfft, nfilt, numcep;
+  int32_t kind;               /* NABU_FEAT_FBANK / NABU_FEAT_MFCC (numcep is ignored for fbank) */
+  int32_t include_energy;     /* 0 / 1 */
+  int32_t dynamic;            /* 0 nodelta, 1 delta, 2 ddelta */
+  int32_t mvn;                /* 0 / 1 */
+  int32_t lowfreq, highfreq;  /* Hz; highfreq < 0: rate/2 */
+  float preemph, ceplifter;
+  double winlen, winstep;     /* seconds (the snip works on the unrounded products with rate) */
+} nabu_feat_desc;
+int nabu_feat_dim(const nabu_feat_desc *d);
+int nabu_feat_num_frames(const nabu_feat_desc *d, long long n_samples);
+int nabu_feat_plan_host(const nabu_feat_desc *d, int n_utt, const int32_t *sample_offsets_host,
+                        int32_t *frame_offsets_host, int32_t *kept_host);
+size_t nabu_feat_ws_bytes(const nabu_feat_desc *d);
+int nabu_feat_tables_host(const nabu_feat_desc *d, void *ws_host, size_t ws_bytes);
+int nabu_feat_compute(const nabu_feat_desc *d, int n_utt, int max_frames, const int16_t *samples,
+                      const int32_t *sample_offsets, const int32_t *kept, const int32_t *frame_offsets,
+                      float *out, const void *ws, size_t ws_bytes, nabu_stream_t stream);
 
 #ifdef __cplusplus
 }

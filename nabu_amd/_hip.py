@@ -4,6 +4,7 @@ The product path has NO fallback: if the HIP library is missing or a tensor is
 not on the GPU, the call raises.  PyTorch is used only to own device memory and
 to name the HIP stream the kernels are enqueued on."""
 import ctypes
+import math
 import os
 
 import torch
@@ -36,6 +37,31 @@ class PkGemmDesc(_c.Structure):
                 ('b_planes', _c.c_int32), ('C', _c.c_void_p * 2), ('C2', _c.c_void_p * 2),
                 ('ldc', _c.c_int32), ('n_split', _c.c_int32), ('bias', _c.c_void_p), ('bias2', _c.c_void_p),
                 ('alpha', _c.c_float), ('beta', _c.c_float), ('a_amax', _c.c_void_p * 2), ('b_amax', _c.c_void_p * 2), ('direct', _c.c_int32)]
+
+
+class FeatDesc(_c.Structure):
+    """nabu_feat_desc: build one with feat_desc(), which applies the reference's rounding to the frame sizes"""
+    _fields_ = [('size', _c.c_uint32)] + [(n, _c.c_int32) for n in
+                                          ('rate', 'frame_len', 'frame_step', 'nfft', 'nfilt', 'numcep', 'kind',
+                                           'include_energy', 'dynamic', 'mvn', 'lowfreq', 'highfreq')] + \
+               [('preemph', _c.c_float), ('ceplifter', _c.c_float), ('winlen', _c.c_double), ('winstep', _c.c_double)]
+
+
+FEAT_KINDS = {'fbank': 0, 'mfcc': 1}
+FEAT_DYNAMIC = {'nodelta': 0, 'delta': 1, 'ddelta': 2}
+
+
+def round_half_away(x):
+    """Python 2's round() for x >= 0 (Python 3 rounds halves to even): 220.5 -> 221, 1102.5 -> 1103"""
+    return int(math.floor(x + 0.5))
+
+
+def feat_desc(rate, kind='fbank', winlen=0.025, winstep=0.01, nfft=512, nfilt=40, numcep=12, include_energy=True,
+              dynamic='ddelta', mvn=True, lowfreq=0, highfreq=-1, preemph=0.97, ceplifter=22.0):
+    return FeatDesc(_c.sizeof(FeatDesc), int(rate), round_half_away(float(winlen) * rate),
+                    round_half_away(float(winstep) * rate), int(nfft), int(nfilt), int(numcep), FEAT_KINDS[kind],
+                    int(bool(include_energy)), FEAT_DYNAMIC[dynamic], int(bool(mvn)), int(lowfreq), int(highfreq),
+                    float(preemph), float(ceplifter), float(winlen), float(winstep))
 
 
 # name -> (restype, argtypes); must list every symbol of include/nabu_hip.h
@@ -125,6 +151,12 @@ SIGNATURES = {
     'nabu_xent_wide_ws_bytes': (_sz, [_i, _i]),
     'nabu_xent_wide_loss_grad': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _sz, _vp]),
     'nabu_log_softmax_prior_f32': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'nabu_feat_dim': (_i, [_c.POINTER(FeatDesc)]),
+    'nabu_feat_num_frames': (_i, [_c.POINTER(FeatDesc), _ll]),
+    'nabu_feat_plan_host': (_i, [_c.POINTER(FeatDesc), _i, _vp, _vp, _vp]),
+    'nabu_feat_ws_bytes': (_sz, [_c.POINTER(FeatDesc)]),
+    'nabu_feat_tables_host': (_i, [_c.POINTER(FeatDesc), _vp, _sz]),
+    'nabu_feat_compute': (_i, [_c.POINTER(FeatDesc), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None
