@@ -302,6 +302,57 @@ int nabu_blstm_bwd_weights(const nabu_blstm_desc *d, const float *x, const int32
                            void *reserve, float *dkernel_fw, float *dkernel_bw, void *ws, size_t ws_bytes,
                            nabu_stream_t stream);
 
+/* ---- layer-normalised BLSTM layer (lstm_ln.hip): layer.blstm(layer_norm=True) ---------------------------------
+ * tf.contrib.rnn.LayerNormBasicLSTMCell(num_units, layer_norm=True) under bidirectional_dynamic_rnn.  Per direction,
+ * batch row b and step s < len[b]:
+ *   z = [x_t, h] . kernel                       (NO bias: the cell has no bias variable when it normalises)
+ *   LN_k(v) = gamma_k (v - mean v) rsqrt(var v + 1e-12) + beta_k    over the H units of ONE gate (biased variance)
+ *   c' = c sigmoid(LN_f(z_f) + 1) + sigmoid(LN_i(z_i)) tanh(LN_j(z_j));  c = LN_state(c')   (the normalised c is carried)
+ *   h  = tanh(c) sigmoid(LN_o(z_o))
+ * Steps s >= len[b]: output 0, state frozen; the backward direction runs over the reversed valid part (as nabu_blstm_fwd).
+ * The norm parameters come in one struct: index 0..4 = input, transform, forget, output, state (the cell's scopes); every
+ * array is [H].  The gradient pointers are read by the backward calls only and are overwritten.
+ *
+ * These entry points take nabu_blstm_desc as it is.  They are the exact-fp32, launch-per-step family: two launches per
+ * step and pass (the recurrent product; the row statistics and the cell), both directions in each.  mode
+ * NABU_LSTM_PERSISTENT is NABU_EUNSUP (the persistent kernels split H over workgroups and have no per-step
+ * cross-workgroup reduction); AUTO and STEPWISE run the same kernels.  recurrent_precision is accepted and has no effect,
+ * gemm_precision selects the arithmetic of x.Wx, dZ.Wx^T and x^T.dZ as in nabu_blstm_fwd (h^T.dZ is exact fp32), the
+ * packed-companion fields are ignored (nothing is emitted or read packed).  H % 4 != 0 is NABU_EUNSUP.
+ *
+ * reserve = z_hat fw | bw [B,T,4H] (the normalised gate inputs; x.Wx before the recurrence, dZ - the gradient w.r.t. the
+ * PRE-normalisation z - after the backward recurrence) | c_hat fw | bw [B,T,H] | rstd fw | bw [B,T,4] | rstd_c fw | bw
+ * [B,T]; a NABU_BLSTM_FWD_ONLY descriptor's reserve is the gate buffers alone and nothing is saved.  The RESERVE CONTRACT
+ * above holds here too (a table of its own: a reserve of nabu_blstm_fwd is rejected by these calls and vice versa).
+ * The gamma/beta gradients are per-row running sums added up over the batch in a fixed order by one launch (no
+ * floating-point atomics): two identical calls give identical bits. */
+typedef struct nabu_blstm_ln_params {
+  uint32_t size;             /* sizeof(nabu_blstm_ln_params) */
+  uint32_t reserved;         /* 0 */
+  const float *gamma[2][5];  /* [fw, bw][input, transform, forget, output, state], each [H] */
+  const float *beta[2][5];
+  float *dgamma[2][5];       /* backward: overwritten; forward: ignored (may be NULL) */
+  float *dbeta[2][5];
+} nabu_blstm_ln_params;
+size_t nabu_blstm_ln_reserve_bytes(const nabu_blstm_desc *d);
+size_t nabu_blstm_ln_ws_bytes(const nabu_blstm_desc *d);
+int nabu_blstm_ln_fwd(const nabu_blstm_desc *d, const float *x, const int32_t *len, const float *kernel_fw,
+                      const float *kernel_bw, const nabu_blstm_ln_params *ln, float *out, void *reserve, void *ws,
+                      size_t ws_bytes, nabu_stream_t stream);
+/* d_x [B,T,D] is overwritten (may be NULL), dkernel_* [(D+H),4H] and the twenty dgamma / dbeta arrays are overwritten;
+ * reserve is consumed.  _bwd_data (recurrence backwards, norm-parameter gradients, d_x; dZ stays in the reserve) followed
+ * by _bwd_weights (dkernel_*; any time later on the same stream) == _bwd, bit for bit. */
+int nabu_blstm_ln_bwd(const nabu_blstm_desc *d, const float *x, const int32_t *len, const float *kernel_fw,
+                      const float *kernel_bw, const nabu_blstm_ln_params *ln, const float *out, const float *d_out,
+                      void *reserve, float *d_x, float *dkernel_fw, float *dkernel_bw, void *ws, size_t ws_bytes,
+                      nabu_stream_t stream);
+int nabu_blstm_ln_bwd_data(const nabu_blstm_desc *d, const float *x, const int32_t *len, const float *kernel_fw,
+                           const float *kernel_bw, const nabu_blstm_ln_params *ln, const float *out, const float *d_out,
+                           void *reserve, float *d_x, void *ws, size_t ws_bytes, nabu_stream_t stream);
+int nabu_blstm_ln_bwd_weights(const nabu_blstm_desc *d, const float *x, const int32_t *len, const float *out,
+                              void *reserve, float *dkernel_fw, float *dkernel_bw, void *ws, size_t ws_bytes,
+                              nabu_stream_t stream);
+
 /* 1 if nabu_blstm_fwd/bwd will run the persistent whole-sequence kernel for d. */
 int nabu_blstm_uses_persistent(const nabu_blstm_desc *d);
 /* Profiling hook (thread-local): when non-NULL, nabu_blstm_fwd/bwd record the

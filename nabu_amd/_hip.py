@@ -26,6 +26,12 @@ class BlstmDesc(_c.Structure):
                 ('hT_pk', _c.c_void_p), ('x_pk_rows', _c.c_void_p), ('x_pk_cols', _c.c_void_p)]
 
 
+class BlstmLnParams(_c.Structure):
+    """nabu_blstm_ln_params: [fw, bw][input, transform, forget, output, state] pointers to [H] arrays"""
+    _fields_ = [('size', _c.c_uint32), ('reserved', _c.c_uint32), ('gamma', (_c.c_void_p * 5) * 2),
+                ('beta', (_c.c_void_p * 5) * 2), ('dgamma', (_c.c_void_p * 5) * 2), ('dbeta', (_c.c_void_p * 5) * 2)]
+
+
 BLSTM_FWD_ONLY = 1
 REC_PRECISIONS = {'default': 0, 'f32': 1}
 
@@ -95,6 +101,14 @@ SIGNATURES = {
                             _vp, _vp, _vp, _sz, _vp]),
     'nabu_blstm_bwd_data': (_i, [_c.POINTER(BlstmDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nabu_blstm_bwd_weights': (_i, [_c.POINTER(BlstmDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'nabu_blstm_ln_reserve_bytes': (_sz, [_c.POINTER(BlstmDesc)]),
+    'nabu_blstm_ln_ws_bytes': (_sz, [_c.POINTER(BlstmDesc)]),
+    'nabu_blstm_ln_fwd': (_i, [_c.POINTER(BlstmDesc), _vp, _vp, _vp, _vp, _c.POINTER(BlstmLnParams), _vp, _vp, _vp, _sz, _vp]),
+    'nabu_blstm_ln_bwd': (_i, [_c.POINTER(BlstmDesc), _vp, _vp, _vp, _vp, _c.POINTER(BlstmLnParams), _vp, _vp, _vp, _vp, _vp,
+                               _vp, _vp, _sz, _vp]),
+    'nabu_blstm_ln_bwd_data': (_i, [_c.POINTER(BlstmDesc), _vp, _vp, _vp, _vp, _c.POINTER(BlstmLnParams), _vp, _vp, _vp, _vp,
+                                    _vp, _sz, _vp]),
+    'nabu_blstm_ln_bwd_weights': (_i, [_c.POINTER(BlstmDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nabu_blstm_uses_persistent': (_i, [_c.POINTER(BlstmDesc)]),
     'nabu_blstm_pk_bytes': (_i, [_c.POINTER(BlstmDesc), _c.POINTER(_c.c_size_t)]),
     'nabu_blstm_emits_packed': (_i, [_c.POINTER(BlstmDesc)]),

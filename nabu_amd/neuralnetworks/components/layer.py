@@ -43,8 +43,7 @@ def blstm(inputs, sequence_length, num_units, layer_norm=False, scope=None, out_
     <scope>/bidirectional_rnn/{fw,bw}/layer_norm_basic_lstm_cell/{kernel [(D+H),4H], bias [4H]},
     gate order i,j,f,o; both use the scope-default glorot-uniform initialiser."""
     if layer_norm:
-        raise NotImplementedError('layer_norm=True is not on the hot path (the reference '
-                                  'always calls blstm with layer_norm=False)')
+        return _blstm_layer_norm(inputs, sequence_length, num_units, scope)
     lens = SeqLen.wrap(sequence_length, inputs.device)
     B, T, D = inputs.shape
     H = int(num_units)
@@ -115,6 +114,68 @@ def blstm(inputs, sequence_length, num_units, layer_norm=False, scope=None, out_
                           kf.grad, bf.grad, kb.grad, bb.grad)
         return [dx]
     record([inputs], [out], backward, params=(kf, bf, kb, bb))
+    return out
+
+
+def layer_norm_variable_names(direction):
+    """names of one direction's variables of a layer-normalised cell, relative to the layer's scope: kernel, then
+    gamma and beta of the norm scopes in ABI order (hip.LN_SCOPES); there is no bias"""
+    cell = _CELL % direction
+    return [cell + '/kernel'] + ['%s/%s/%s' % (cell, s, w) for s in hip.LN_SCOPES for w in ('gamma', 'beta')]
+
+
+def _blstm_layer_norm(inputs, sequence_length, num_units, scope):
+    """blstm(layer_norm=True): LayerNormBasicLSTMCell(layer_norm=True) in both directions (include/nabu_hip.h,
+    nabu_blstm_ln_fwd).  Variables per direction under the same cell scope: kernel [(D+H),4H] (scope-default
+    initialiser) and {input,transform,forget,output,state}/{gamma,beta} [H] (1 / 0); NO bias.  The exact-fp32 stepwise
+    kernels: LSTM_MODE = PERSISTENT is refused, recurrent_precision has nothing to select, no packed companions are
+    attached (the consumer packs for itself)."""
+    if LSTM_MODE[0] == hip.LSTM_PERSISTENT:
+        raise hip._hip.NabuHipError('blstm(layer_norm=True) with LSTM_MODE = PERSISTENT: the persistent recurrent kernels '
+                                    'split the units of a row over workgroups and have no per-step reduction across them; '
+                                    'layer norm runs in the stepwise family (LSTM_AUTO or LSTM_STEPWISE)')
+    lens = SeqLen.wrap(sequence_length, inputs.device)
+    B, T, D = inputs.shape
+    H = int(num_units)
+    with vs.variable_scope(scope or 'BLSTM'):
+        kernels, gammas, betas = [], [], []
+        for direction in ('fw', 'bw'):
+            names = layer_norm_variable_names(direction)
+            kernels.append(vs.get_variable(names[0], [D + H, 4 * H]))
+            # (created in the cell's order: per norm scope gamma, then beta)
+            norms = [vs.get_variable(n, [H], initializer=vs.ones if n.endswith('gamma') else vs.zeros) for n in names[1:]]
+            gammas.append(norms[0::2])
+            betas.append(norms[1::2])
+    kf, kb = kernels
+    norm = gammas[0] + gammas[1] + betas[0] + betas[1]
+    training = Tape.current is not None
+    plan = hip.BlstmLnPlan(B, T, D, H, min(lens.max(), T), LSTM_MODE[0], GEMM_PRECISION[0], fwd_only=not training)
+    x = inputs if inputs.is_contiguous() else inputs.contiguous()
+    out = torch.empty((B, T, 2 * H), dtype=torch.float32, device=x.device)
+    reserve = torch.empty(plan.reserve_bytes, dtype=torch.uint8, device=x.device)
+
+    def data(group):
+        return [[v.data for v in vars_] for vars_ in group]
+    hip.blstm_ln_fwd(plan, x, lens.dev, kf.data, kb.data, data(gammas), data(betas), out, reserve)
+    ops.set_value_bound(out, 1.0)           # |tanh(c) sigmoid(o)| <= 1 still holds
+    need_dx = requires_grad(inputs)
+
+    def backward(dout):
+        for v in [kf, kb] + norm:
+            if v.grad is None:
+                v.grad = torch.zeros_like(v.data)
+        dx = torch.empty_like(x) if need_dx else None
+        dgam, dbet = [[v.grad for v in g] for g in gammas], [[v.grad for v in g] for g in betas]
+        tape = Tape.current_backward
+        if DEFER_WEIGHT_GRADS[0] and tape is not None:
+            hip.blstm_ln_bwd_data(plan, x, lens.dev, kf.data, kb.data, data(gammas), data(betas), out, dout.contiguous(),
+                                  reserve, dx, dgam, dbet)
+            tape.defer(lambda: hip.blstm_ln_bwd_weights(plan, x, lens.dev, out, reserve, kf.grad, kb.grad), params=(kf, kb))
+        else:
+            hip.blstm_ln_bwd(plan, x, lens.dev, kf.data, kb.data, data(gammas), data(betas), out, dout.contiguous(), reserve,
+                             dx, kf.grad, kb.grad, dgam, dbet)
+        return [dx]
+    record([inputs], [out], backward, params=tuple([kf, kb] + norm))
     return out
 
 

@@ -284,6 +284,72 @@ def blstm_bwd_weights(plan, x, lens_dev, out, reserve, dk_fw, dk_bw):
           'nabu_blstm_bwd_weights')
 
 
+LN_SCOPES = ('input', 'transform', 'forget', 'output', 'state')    # the norm scopes of LayerNormBasicLSTMCell, in ABI order
+
+
+class BlstmLnPlan(object):
+    """Shape descriptor of one layer-normalised BLSTM layer call (include/nabu_hip.h, nabu_blstm_ln_fwd): the descriptor
+    of BlstmPlan, sized by the layer-norm entry points.  LSTM_PERSISTENT is refused there, with the reason."""
+
+    def __init__(self, B, T, D, H, max_len, mode=LSTM_AUTO, gemm_precision='default', fwd_only=False):
+        self.desc = _hip.BlstmDesc(ctypes.sizeof(_hip.BlstmDesc), B, T, D, H, int(max_len), mode,
+                                   _hip.GEMM_PRECISIONS[gemm_precision], 0.0, _hip.BLSTM_FWD_ONLY if fwd_only else 0,
+                                   0, 0, None, None, None, None, None)
+        L = _hip.lib()
+        self.reserve_bytes = L.nabu_blstm_ln_reserve_bytes(ctypes.byref(self.desc))
+        self.ws_bytes = L.nabu_blstm_ln_ws_bytes(ctypes.byref(self.desc))
+        if self.reserve_bytes == 0:
+            raise _hip.NabuHipError('blstm(layer_norm=True): unsupported B=%d T=%d D=%d H=%d mode=%d: %s' % (
+                B, T, D, H, mode, L.nabu_last_error().decode()))
+
+
+def blstm_ln_params(gamma, beta, dgamma=None, dbeta=None):
+    """nabu_blstm_ln_params from [fw, bw] lists of five [H] tensors each (LN_SCOPES order); the gradients for a backward call"""
+    p = _hip.BlstmLnParams(ctypes.sizeof(_hip.BlstmLnParams), 0)
+    for d in range(2):
+        for k in range(5):
+            p.gamma[d][k], p.beta[d][k] = ptr(_f32(gamma[d][k], 'gamma')), ptr(_f32(beta[d][k], 'beta'))
+            if dgamma is not None:
+                p.dgamma[d][k], p.dbeta[d][k] = ptr(_f32(dgamma[d][k], 'dgamma')), ptr(_f32(dbeta[d][k], 'dbeta'))
+    return p
+
+
+def blstm_ln_fwd(plan, x, lens_dev, k_fw, k_bw, gamma, beta, out, reserve):
+    ws = Workspace.get(plan.ws_bytes, x.device, 'blstm_ln')
+    ln = blstm_ln_params(gamma, beta)
+    check(_hip.lib().nabu_blstm_ln_fwd(ctypes.byref(plan.desc), ptr(_f32(x, 'x')), ptr(lens_dev), ptr(k_fw), ptr(k_bw),
+                                       ctypes.byref(ln), ptr(out), ptr(reserve), ptr(ws), plan.ws_bytes, stream()),
+          'nabu_blstm_ln_fwd')
+    return out
+
+
+def blstm_ln_bwd(plan, x, lens_dev, k_fw, k_bw, gamma, beta, out, d_out, reserve, d_x, dk_fw, dk_bw, dgamma, dbeta):
+    ws = Workspace.get(plan.ws_bytes, x.device, 'blstm_ln')
+    ln = blstm_ln_params(gamma, beta, dgamma, dbeta)
+    check(_hip.lib().nabu_blstm_ln_bwd(ctypes.byref(plan.desc), ptr(x), ptr(lens_dev), ptr(k_fw), ptr(k_bw), ctypes.byref(ln),
+                                       ptr(out), ptr(d_out), ptr(reserve), ptr(d_x), ptr(dk_fw), ptr(dk_bw), ptr(ws),
+                                       plan.ws_bytes, stream()), 'nabu_blstm_ln_bwd')
+    return d_x
+
+
+def blstm_ln_bwd_data(plan, x, lens_dev, k_fw, k_bw, gamma, beta, out, d_out, reserve, d_x, dgamma, dbeta):
+    """first half of blstm_ln_bwd: recurrence backwards, the norm-parameter gradients, d_x; dz stays in `reserve`"""
+    ws = Workspace.get(plan.ws_bytes, x.device, 'blstm_ln')
+    ln = blstm_ln_params(gamma, beta, dgamma, dbeta)
+    check(_hip.lib().nabu_blstm_ln_bwd_data(ctypes.byref(plan.desc), ptr(x), ptr(lens_dev), ptr(k_fw), ptr(k_bw),
+                                            ctypes.byref(ln), ptr(out), ptr(d_out), ptr(reserve), ptr(d_x), ptr(ws),
+                                            plan.ws_bytes, stream()), 'nabu_blstm_ln_bwd_data')
+    return d_x
+
+
+def blstm_ln_bwd_weights(plan, x, lens_dev, out, reserve, dk_fw, dk_bw):
+    """second half: the kernel gradients from the dz blstm_ln_bwd_data left in `reserve`"""
+    ws = Workspace.get(plan.ws_bytes, x.device, 'blstm_ln')
+    check(_hip.lib().nabu_blstm_ln_bwd_weights(ctypes.byref(plan.desc), ptr(x), ptr(lens_dev), ptr(out), ptr(reserve),
+                                               ptr(dk_fw), ptr(dk_bw), ptr(ws), plan.ws_bytes, stream()),
+          'nabu_blstm_ln_bwd_weights')
+
+
 def pad_time(x, Tp):
     B, T, F = x.shape
     y = torch.empty((B, Tp, F), dtype=x.dtype, device=x.device)

@@ -75,6 +75,10 @@ def zeros(rng, shape):
     return np.zeros(shape, np.float32)
 
 
+def ones(rng, shape):
+    return np.ones(shape, np.float32)
+
+
 class VariableStore(object):
     """Ordered name -> Variable map with AUTO_REUSE semantics."""
 
