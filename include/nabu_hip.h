@@ -555,6 +555,86 @@ int nabu_speller_bwd(const nabu_speller_desc *d, const float *values, const int3
                      const float *dlogits, void *reserve, const nabu_speller_grads *g,
                      float *dvalues, void *ws, size_t ws_bytes, nabu_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Speller over M encoded inputs, one attention mechanism each — Speller.create_cell with several
+ * entries in `encoded` (nabu/neuralnetworks/models/ed_decoders/speller.py:49-61: one attention.factory
+ * per encoded input, the list handed to tf.contrib.seq2seq.AttentionWrapper, AttentionProjectionWrapper
+ * on [cell_output, contexts]).  Memory m has its own Te[m], E[m], enc_len and variables; the attention
+ * type, probability_fn, K / F and num_units are shared (every mechanism is built from one [decoder] conf).
+ * Per step: cell input [onehot | ctx_0 | .. | ctx_{M-1}], q_m = h_top . query_kernel[m], align_m / ctx_m
+ * exactly as nabu_attn_fwd defines them, logits = [h_top | ctx_0 | .. | ctx_{M-1}] . out_kernel + out_bias.
+ *   lstm_kernel[0] [(C + sum E + U), 4U] (rows: one-hot, contexts in mechanism order, h),
+ *   out_kernel [(U + sum E), C] (rows: h, contexts in mechanism order); the rest per mechanism as nabu_speller_params.
+ *   values / enc_len / dvalues: HOST arrays of M device pointers ([B,Te[m],E[m]] / [B]).
+ * M <= NABU_SPELLER_MAX_MEMORIES = 4 (a launch's mechanism table travels as a kernel argument).
+ * The decoder steps always run as the step chain (nabu_speller_multi_uses_persistent == 0: neither the
+ * persistent decoder nor the matrix-pipe location-aware kernels are extended to several memories).  A step's M
+ * attention mechanisms are ONE launch per pass (a grid dimension selects the mechanism; a workgroup reads
+ * its memory's Te, E and pointers from the table), the contexts live in one [B, sum E] buffer that is the
+ * operand of the next step's cell product and of the projection, and the M queries are one product against
+ * the column-concatenated [U, M U] query kernels.  No floating-point atomics: identical calls, identical bits.
+ * reserve_bytes == 0 together with nabu_last_error() is the "unsupported shape" answer. */
+#define NABU_SPELLER_MAX_MEMORIES 4
+typedef struct {
+  uint32_t size;
+  int32_t M;                                   /* number of encoded inputs, 1..NABU_SPELLER_MAX_MEMORIES */
+  int32_t B, U, C, L, num_layers;
+  int32_t Te[NABU_SPELLER_MAX_MEMORIES], E[NABU_SPELLER_MAX_MEMORIES];
+  int32_t kind, K, F, prob_fn;                 /* attention: see nabu_attn_desc */
+  float keep_prob;
+  unsigned long long seed, seed_offset;
+  float sample_prob;
+  unsigned long long sample_seed, sample_offset;
+} nabu_speller_multi_desc;
+typedef struct {
+  const float *memory_kernel[NABU_SPELLER_MAX_MEMORIES], *query_kernel[NABU_SPELLER_MAX_MEMORIES],
+      *attention_v[NABU_SPELLER_MAX_MEMORIES], *conv_kernel[NABU_SPELLER_MAX_MEMORIES],
+      *conv_proj[NABU_SPELLER_MAX_MEMORIES];
+  const float *out_kernel, *out_bias;
+  const float *lstm_kernel[NABU_SPELLER_MAX_LAYERS], *lstm_bias[NABU_SPELLER_MAX_LAYERS];
+} nabu_speller_multi_params;
+typedef struct {
+  float *memory_kernel[NABU_SPELLER_MAX_MEMORIES], *query_kernel[NABU_SPELLER_MAX_MEMORIES],
+      *attention_v[NABU_SPELLER_MAX_MEMORIES], *conv_kernel[NABU_SPELLER_MAX_MEMORIES],
+      *conv_proj[NABU_SPELLER_MAX_MEMORIES];
+  float *out_kernel, *out_bias;
+  float *lstm_kernel[NABU_SPELLER_MAX_LAYERS], *lstm_bias[NABU_SPELLER_MAX_LAYERS];
+} nabu_speller_multi_grads;
+size_t nabu_speller_multi_reserve_bytes(const nabu_speller_multi_desc *d);
+size_t nabu_speller_multi_ws_bytes(const nabu_speller_multi_desc *d);
+/* always 0 (see above); the query exists so that a caller can ask both decoders the same question */
+int nabu_speller_multi_uses_persistent(const nabu_speller_multi_desc *d, int backward);
+/* frame slices per utterance of mechanism m's attention workgroups (1: the batch alone fills the chip) */
+int nabu_speller_multi_attn_slices(const nabu_speller_multi_desc *d, int m);
+int nabu_speller_multi_fwd(const nabu_speller_multi_desc *d, const float *const *values_host,
+                           const int32_t *const *enc_len_host, const int32_t *ids, const int32_t *dec_len,
+                           const nabu_speller_multi_params *p, float *logits, void *reserve, void *ws,
+                           size_t ws_bytes, nabu_stream_t stream);
+/* every gradient buffer is overwritten; dvalues_host[m] -> [B,Te[m],E[m]] */
+int nabu_speller_multi_bwd(const nabu_speller_multi_desc *d, const float *const *values_host,
+                           const int32_t *const *enc_len_host, const int32_t *ids, const int32_t *dec_len,
+                           const nabu_speller_multi_params *p, const float *dlogits, void *reserve,
+                           const nabu_speller_multi_grads *g, float *const *dvalues_host, void *ws,
+                           size_t ws_bytes, nabu_stream_t stream);
+/* Beam search over M encoded inputs: nabu_speller_beam_search's loop (same pruning, stop test and outputs) with the
+ * cell above on B*beam_width rows; the M alignment states are pruned and gathered per memory and
+ * alignments_host[m] (may be NULL as a whole) receives [B,W,max_steps,Te[m]]. */
+typedef struct {
+  uint32_t size;
+  int32_t M, B, U, C, num_layers;
+  int32_t Te[NABU_SPELLER_MAX_MEMORIES], E[NABU_SPELLER_MAX_MEMORIES];
+  int32_t kind, K, F, prob_fn, beam_width, max_steps;
+  float length_penalty, temperature;
+} nabu_multi_beam_desc;
+size_t nabu_speller_multi_beam_ws_bytes(const nabu_multi_beam_desc *d);
+int nabu_speller_multi_beam_search(const nabu_multi_beam_desc *d, const float *const *values_host,
+                                   const int32_t *const *enc_len_host, const nabu_speller_multi_params *p,
+                                   int32_t *sequences, int32_t *lengths, float *scores,
+                                   float *const *alignments_host, int32_t *num_steps, void *ws, size_t ws_bytes,
+                                   nabu_stream_t stream);
+int nabu_speller_multi_decoder_inputs(const nabu_speller_multi_desc *d, const void *reserve, int32_t *out_ids,
+                                      nabu_stream_t stream);
+
 /* x[b,t,:] = 0 for t >= len[b] (dynamic_decode zeroes the outputs of finished rows). */
 int nabu_mask_time_f32(int B, int L, int F, float *x, const int32_t *len, nabu_stream_t stream);
 /* y[b,l,:] = x[l,b,:] (time-major per-step buffers <-> the batch-major API). */

@@ -134,6 +134,15 @@ SIGNATURES = {
     'nabu_speller_uses_persistent': (_i, [_vp, _i]),
     'nabu_speller_fwd': (_i, [_vp] * 9 + [_sz, _vp]),
     'nabu_speller_bwd': (_i, [_vp] * 11 + [_sz, _vp]),
+    'nabu_speller_multi_reserve_bytes': (_sz, [_vp]),
+    'nabu_speller_multi_ws_bytes': (_sz, [_vp]),
+    'nabu_speller_multi_uses_persistent': (_i, [_vp, _i]),
+    'nabu_speller_multi_attn_slices': (_i, [_vp, _i]),
+    'nabu_speller_multi_decoder_inputs': (_i, [_vp, _vp, _vp, _vp]),
+    'nabu_speller_multi_beam_ws_bytes': (_sz, [_vp]),
+    'nabu_speller_multi_beam_search': (_i, [_vp] * 10 + [_sz, _vp]),
+    'nabu_speller_multi_fwd': (_i, [_vp] * 9 + [_sz, _vp]),
+    'nabu_speller_multi_bwd': (_i, [_vp] * 11 + [_sz, _vp]),
     'nabu_mask_time_f32': (_i, [_i, _i, _i, _vp, _vp, _vp]),
     'nabu_swap01_f32': (_i, [_i, _i, _i, _vp, _vp, _vp]),
     'nabu_scatter_rows_f32': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -265,6 +274,33 @@ class SpellerPtrs(_c.Structure):
     """nabu_speller_params / nabu_speller_grads (same layout, const or not)"""
     _fields_ = [(n, _c.c_void_p) for n in ('memory_kernel', 'query_kernel', 'attention_v', 'conv_kernel',
                                            'conv_proj', 'out_kernel', 'out_bias')] + \
+               [('lstm_kernel', _c.c_void_p * SPELLER_MAX_LAYERS), ('lstm_bias', _c.c_void_p * SPELLER_MAX_LAYERS)]
+
+
+SPELLER_MAX_MEMORIES = 4
+
+
+class SpellerMultiDesc(_c.Structure):
+    """nabu_speller_multi_desc: the Speller over M encoded inputs (Te, E per memory)"""
+    _fields_ = [('size', _c.c_uint32)] + [(n, _c.c_int32) for n in ('M', 'B', 'U', 'C', 'L', 'num_layers')] + \
+               [('Te', _c.c_int32 * SPELLER_MAX_MEMORIES), ('E', _c.c_int32 * SPELLER_MAX_MEMORIES)] + \
+               [(n, _c.c_int32) for n in ('kind', 'K', 'F', 'prob_fn')] + \
+               [('keep_prob', _c.c_float), ('seed', _c.c_ulonglong), ('seed_offset', _c.c_ulonglong),
+                ('sample_prob', _c.c_float), ('sample_seed', _c.c_ulonglong), ('sample_offset', _c.c_ulonglong)]
+
+
+class MultiBeamDesc(_c.Structure):
+    _fields_ = [('size', _c.c_uint32)] + [(n, _c.c_int32) for n in ('M', 'B', 'U', 'C', 'num_layers')] + \
+               [('Te', _c.c_int32 * SPELLER_MAX_MEMORIES), ('E', _c.c_int32 * SPELLER_MAX_MEMORIES)] + \
+               [(n, _c.c_int32) for n in ('kind', 'K', 'F', 'prob_fn', 'beam_width', 'max_steps')] + \
+               [('length_penalty', _c.c_float), ('temperature', _c.c_float)]
+
+
+class SpellerMultiPtrs(_c.Structure):
+    """nabu_speller_multi_params / nabu_speller_multi_grads (same layout, const or not)"""
+    _fields_ = [(n, _c.c_void_p * SPELLER_MAX_MEMORIES) for n in ('memory_kernel', 'query_kernel', 'attention_v',
+                                                                  'conv_kernel', 'conv_proj')] + \
+               [('out_kernel', _c.c_void_p), ('out_bias', _c.c_void_p)] + \
                [('lstm_kernel', _c.c_void_p * SPELLER_MAX_LAYERS), ('lstm_bias', _c.c_void_p * SPELLER_MAX_LAYERS)]
 
 

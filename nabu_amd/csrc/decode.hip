@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "common.h"
+#include "speller_multi.h"
 
 namespace nabu {
 
@@ -772,6 +773,203 @@ extern "C" int nabu_speller_beam_search(const nabu_beam_desc *d, const float *va
     hipLaunchKernelGGL(beam_align_kernel, dim3(N, S), dim3(DT), 0, s, N, W, Tn, S, Te, w + L.hist_align, wi + L.src, alignments);
     NABU_LAUNCH_CHECK();
   }
+  hipLaunchKernelGGL(beam_scores_kernel, dim3(gN), dim3(DT), 0, s, N, d->length_penalty, w + L.logprobs, wi + L.lengths,
+                     scores, lengths);
+  NABU_LAUNCH_CHECK();
+  *num_steps = Tn;
+  return 0;
+}
+
+// ===========================================================================
+// Beam search over M encoded inputs (nabu_speller_multi_beam_search): the loop of nabu_speller_beam_search with the
+// cell of nabu_speller_multi_fwd on B*W rows — contexts of all mechanisms in one [N, sum E] buffer (one gather), M
+// alignment states (pruned and gathered per memory), the step's M attention mechanisms in one launch
+// (speller_multi.hip, unchanged).
+namespace nabu {
+struct MBeamWs {
+  size_t valuesT[NABU_SPELLER_MAX_MEMORIES], keysB[NABU_SPELLER_MAX_MEMORIES], keysT[NABU_SPELLER_MAX_MEMORIES],
+      lenT[NABU_SPELLER_MAX_MEMORIES], part[NABU_SPELLER_MAX_MEMORIES], hist_align[NABU_SPELLER_MAX_MEMORIES],
+      align[3][NABU_SPELLER_MAX_MEMORIES];
+  size_t big, z, q, wqcat, logits, acts, ids, logprobs, lengths, finished, seen, parent, stay, all_seen, scratch, tickets,
+      hist_pred, hist_parent, src, gemm, gemm_bytes, total;
+  size_t h[3][NABU_SPELLER_MAX_LAYERS], c[3][NABU_SPELLER_MAX_LAYERS], ctx[3];
+  int SE, MU;
+};
+static int check_mbeam(const nabu_multi_beam_desc *d) {
+  if (!d || d->size != sizeof(nabu_multi_beam_desc)) return fail(NABU_EINVAL, "multi beam search: bad descriptor size");
+  if (d->M < 1 || d->M > NABU_SPELLER_MAX_MEMORIES) return fail(NABU_EUNSUP, "multi beam search: 1..%d encoded inputs", NABU_SPELLER_MAX_MEMORIES);
+  if (d->B <= 0 || d->U <= 0 || d->C <= 1) return fail(NABU_EINVAL, "multi beam search: bad dimensions");
+  if (d->beam_width <= 0 || d->max_steps <= 0) return fail(NABU_EINVAL, "multi beam search: beam_width and max_steps must be positive");
+  if (!(d->temperature > 0.f)) return fail(NABU_EINVAL, "multi beam search: temperature must be positive");
+  if (d->num_layers < 1 || d->num_layers > NABU_SPELLER_MAX_LAYERS) return fail(NABU_EUNSUP, "multi beam search: 1..%d layers", NABU_SPELLER_MAX_LAYERS);
+  if ((long long)d->B * d->beam_width > (1 << 20)) return fail(NABU_EUNSUP, "multi beam search: B*beam_width too large");
+  for (int m = 0; m < d->M; ++m) {
+    const nabu_attn_desc a = {sizeof(nabu_attn_desc), d->B * d->beam_width, d->Te[m], d->E[m], d->U, d->kind, d->K, d->F, d->prob_fn};
+    if (nabu_attn_bwd_slices(&a) <= 0) return NABU_EUNSUP;       // (dimensions, multiples of 4, LDS: the message is theirs)
+  }
+  return 0;
+}
+static MBeamWs mbeam_ws(const nabu_multi_beam_desc *d) {
+  MBeamWs s;
+  const size_t B = d->B, W = d->beam_width, N = B * W, U = d->U, C = d->C, S = d->max_steps, M = d->M;
+  size_t o = 0, SE = 0, g = 0;
+  auto take = [&](size_t n) { size_t r = o; o += (n + 3) / 4 * 4; return r; };
+  auto mx = [&](size_t v) { if (v > g) g = v; };
+  for (int m = 0; m < d->M; ++m) {
+    const size_t Te = d->Te[m], E = d->E[m];
+    SE += E;
+    s.valuesT[m] = take(N * Te * E); s.keysB[m] = take(B * Te * U); s.keysT[m] = take(N * Te * U); s.lenT[m] = take(N);
+    s.part[m] = take(multi_attn_part_floats((int)N, (int)Te, (int)E, (int)U, d->kind, d->K, d->F, d->prob_fn));
+    s.hist_align[m] = take(S * N * Te);
+    for (int k = 0; k < 3; ++k) s.align[k][m] = take(N * Te);
+    mx(nabu_gemm_ws_bytes((int)(B * Te), (int)U, (int)E));
+  }
+  s.SE = (int)SE; s.MU = (int)(M * U);
+  s.big = take(N); s.z = take(N * 4 * U); s.q = take(N * M * U); s.wqcat = take(U * M * U); s.logits = take(N * C);
+  s.acts = take(N * 4 * U > N * M ? N * 4 * U : N * M);
+  s.ids = take(N); s.logprobs = take(N); s.lengths = take(N); s.finished = take(N); s.seen = take(N);
+  s.parent = take(N); s.stay = take(N); s.all_seen = take(B); s.scratch = take(B * (W * C + W));
+  s.tickets = take(M * N);
+  s.hist_pred = take(S * N); s.hist_parent = take(S * N); s.src = take(N * S);
+  for (int k = 0; k < 3; ++k) {
+    for (int n = 0; n < d->num_layers; ++n) { s.h[k][n] = take(N * U); s.c[k][n] = take(N * U); }
+    s.ctx[k] = take(N * SE);
+  }
+  mx(nabu_gemm_ws_bytes((int)N, (int)(4 * U), (int)SE)); mx(nabu_gemm_ws_bytes((int)N, (int)(4 * U), (int)U));
+  mx(nabu_gemm_ws_bytes((int)N, (int)(M * U), (int)U)); mx(nabu_gemm_ws_bytes((int)N, (int)C, (int)U));
+  mx(nabu_gemm_ws_bytes((int)N, (int)C, (int)SE));
+  s.gemm_bytes = (g + 255) / 256 * 256;
+  s.gemm = take(s.gemm_bytes / 4 + 4);
+  s.total = o;
+  return s;
+}
+__global__ __launch_bounds__(DT) void put_cols_dec_kernel(int R, int Cn, const float *__restrict__ src, float *__restrict__ dst,
+                                                          int ldd, int c0) {
+  const int i = blockIdx.x * DT + threadIdx.x;
+  if (i < R * Cn) dst[(size_t)(i / Cn) * ldd + c0 + i % Cn] = src[i];
+}
+}  // namespace nabu
+
+extern "C" size_t nabu_speller_multi_beam_ws_bytes(const nabu_multi_beam_desc *d) {
+  if (check_mbeam(d)) return 0;
+  return mbeam_ws(d).total * 4;
+}
+
+extern "C" int nabu_speller_multi_beam_search(const nabu_multi_beam_desc *d, const float *const *values,
+                                              const int32_t *const *enc_len, const nabu_speller_multi_params *p,
+                                              int32_t *sequences, int32_t *lengths, float *scores,
+                                              float *const *alignments, int32_t *num_steps, void *ws, size_t ws_bytes,
+                                              nabu_stream_t stream) {
+  if (int e = check_mbeam(d)) return e;
+  NABU_CHECK_ARG(values && enc_len && p && sequences && lengths && scores && num_steps && ws, "speller_multi_beam_search: null pointer");
+  for (int m = 0; m < d->M; ++m)
+    NABU_CHECK_ARG(values[m] && enc_len[m] && p->memory_kernel[m] && p->query_kernel[m] && p->attention_v[m] &&
+                   (d->kind != 1 || (p->conv_kernel[m] && p->conv_proj[m])) && (!alignments || alignments[m]),
+                   "speller_multi_beam_search: null pointer for an encoded input");
+  const MBeamWs L = mbeam_ws(d);
+  if (ws_bytes < L.total * 4) return fail(NABU_EWS, "speller_multi_beam_search: workspace too small");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float *w = static_cast<float *>(ws);
+  int32_t *wi = static_cast<int32_t *>(ws);
+  const int B = d->B, W = d->beam_width, N = B * W, U = d->U, C = d->C, nl = d->num_layers, S = d->max_steps, M = d->M,
+            SE = L.SE, MU = L.MU;
+  float *gw = w + L.gemm;
+  const size_t gwb = L.gemm_bytes;
+  auto tile = [&](const void *src, void *dst, size_t F) {
+    size_t gy = (F + DT * 4 - 1) / (DT * 4);
+    hipLaunchKernelGGL(tile_rows_kernel, dim3(N, gy > 64 ? 64 : (unsigned)gy), dim3(DT), 0, s, W, F,
+                       static_cast<const uint32_t *>(src), static_cast<uint32_t *>(dst));
+  };
+  int cur = 0, fresh = 1, nxt = 2;
+  for (int m = 0; m < M; ++m) {
+    const int Te = d->Te[m], E = d->E[m];
+    DEC_TRY(bmm(B * Te, U, E, values[m], E, p->memory_kernel[m], U, 0.f, w + L.keysB[m], U, nullptr, gw, gwb, stream));
+    tile(values[m], w + L.valuesT[m], (size_t)Te * E);
+    tile(w + L.keysB[m], w + L.keysT[m], (size_t)Te * U);
+    tile(enc_len[m], wi + L.lenT[m], 1);
+    hipLaunchKernelGGL(put_cols_dec_kernel, dim3((U * U + DT - 1) / DT), dim3(DT), 0, s, U, U, p->query_kernel[m], w + L.wqcat, MU, m * U);
+    NABU_LAUNCH_CHECK();
+    NABU_HIP(hipMemsetAsync(w + L.align[cur][m], 0, (size_t)N * Te * 4, s));
+    if (d->kind == 2) DEC_TRY(first_col_one(N, Te, w + L.align[cur][m], s));
+  }
+  const int gN = (N + DT - 1) / DT;
+  hipLaunchKernelGGL(fill_i32_kernel, dim3(gN), dim3(DT), 0, s, (size_t)N, INT_MAX, wi + L.big);
+  hipLaunchKernelGGL(fill_i32_kernel, dim3(gN), dim3(DT), 0, s, (size_t)N, C - 1, wi + L.ids);
+  hipLaunchKernelGGL(beam_init_kernel, dim3(gN), dim3(DT), 0, s, N, W, w + L.logprobs);
+  NABU_LAUNCH_CHECK();
+  NABU_HIP(hipMemsetAsync(wi + L.lengths, 0, (size_t)N * 4, s));
+  NABU_HIP(hipMemsetAsync(wi + L.finished, 0, (size_t)N * 4, s));
+  NABU_HIP(hipMemsetAsync(wi + L.seen, 0, (size_t)N * 4, s));
+  NABU_HIP(hipMemsetAsync(wi + L.tickets, 0, (size_t)M * N * 4, s));
+  for (int n = 0; n < nl; ++n) {
+    NABU_HIP(hipMemsetAsync(w + L.h[cur][n], 0, (size_t)N * U * 4, s));
+    NABU_HIP(hipMemsetAsync(w + L.c[cur][n], 0, (size_t)N * U * 4, s));
+  }
+  NABU_HIP(hipMemsetAsync(w + L.ctx[cur], 0, (size_t)N * SE * 4, s));
+  float *z = w + L.z, *lg = w + L.logits;
+  const int32_t *big = wi + L.big;
+  int32_t *par = wi + L.parent, *stay = wi + L.stay;
+  std::vector<int32_t> done(B);
+  int Tn = 0;
+  for (int t = 0; t < S; ++t) {
+    for (int n = 0; n < nl; ++n) {
+      const float *Kn = p->lstm_kernel[n];
+      if (n == 0) {
+        DEC_TRY(bmm(N, 4 * U, SE, w + L.ctx[cur], SE, Kn + (size_t)C * 4 * U, 4 * U, 0.f, z, 4 * U, nullptr, gw, gwb, stream));
+        DEC_TRY(bmm(N, 4 * U, U, w + L.h[cur][0], U, Kn + (size_t)(C + SE) * 4 * U, 4 * U, 1.f, z, 4 * U, nullptr, gw, gwb, stream));
+        DEC_TRY(nabu_lstm_cell_fwd(N, U, 0, big, z, p->lstm_bias[0], Kn, wi + L.ids, w + L.c[cur][0], w + L.h[cur][0],
+                                   w + L.acts, w + L.c[fresh][0], w + L.h[fresh][0], stream));
+      } else {
+        DEC_TRY(bmm(N, 4 * U, U, w + L.h[fresh][n - 1], U, Kn, 4 * U, 0.f, z, 4 * U, nullptr, gw, gwb, stream));
+        DEC_TRY(bmm(N, 4 * U, U, w + L.h[cur][n], U, Kn + (size_t)U * 4 * U, 4 * U, 1.f, z, 4 * U, nullptr, gw, gwb, stream));
+        DEC_TRY(nabu_lstm_cell_fwd(N, U, 0, big, z, p->lstm_bias[n], nullptr, nullptr, w + L.c[cur][n], w + L.h[cur][n],
+                                   w + L.acts, w + L.c[fresh][n], w + L.h[fresh][n], stream));
+      }
+    }
+    const float *htop = w + L.h[fresh][nl - 1];
+    DEC_TRY(bmm(N, MU, U, htop, U, w + L.wqcat, MU, 0.f, w + L.q, MU, nullptr, gw, gwb, stream));
+    MultiAttnMem mem[NABU_SPELLER_MAX_MEMORIES];
+    for (int m = 0; m < M; ++m) {
+      mem[m] = MultiAttnMem{d->Te[m], d->E[m], wi + L.lenT[m], w + L.keysT[m], w + L.valuesT[m], p->attention_v[m],
+                            p->conv_kernel[m], p->conv_proj[m], w + L.align[cur][m], w + L.align[fresh][m],
+                            w + L.acts + (size_t)m * N /* normaliser scratch */, w + L.part[m],
+                            reinterpret_cast<unsigned *>(wi + L.tickets) + (size_t)m * N};
+    }
+    DEC_TRY(multi_attn_fwd(M, N, U, d->kind, d->K, d->F, d->prob_fn, 0, big, w + L.q, w + L.ctx[cur], w + L.ctx[fresh], mem, s));
+    DEC_TRY(bmm(N, C, U, htop, U, p->out_kernel, C, 0.f, lg, C, p->out_bias, gw, gwb, stream));
+    DEC_TRY(bmm(N, C, SE, w + L.ctx[fresh], SE, p->out_kernel + (size_t)U * C, C, 1.f, lg, C, nullptr, gw, gwb, stream));
+    DEC_TRY(nabu_beam_prune(B, W, C, lg, d->temperature, d->length_penalty, w + L.logprobs, wi + L.lengths,
+                            wi + L.finished, wi + L.seen, wi + L.ids, par, stay, wi + L.all_seen, w + L.scratch, stream));
+    for (int n = 0; n < nl; ++n) {
+      DEC_TRY(nabu_beam_gather(B, W, U, w + L.h[fresh][n], w + L.h[cur][n], par, stay, w + L.h[nxt][n], stream));
+      DEC_TRY(nabu_beam_gather(B, W, U, w + L.c[fresh][n], w + L.c[cur][n], par, stay, w + L.c[nxt][n], stream));
+    }
+    DEC_TRY(nabu_beam_gather(B, W, SE, w + L.ctx[fresh], w + L.ctx[cur], par, stay, w + L.ctx[nxt], stream));
+    for (int m = 0; m < M; ++m) {
+      const int Te = d->Te[m];
+      DEC_TRY(nabu_beam_gather(B, W, Te, w + L.align[fresh][m], w + L.align[cur][m], par, stay, w + L.align[nxt][m], stream));
+      NABU_HIP(hipMemcpyAsync(w + L.hist_align[m] + (size_t)t * N * Te, w + L.align[nxt][m], (size_t)N * Te * 4,
+                              hipMemcpyDeviceToDevice, s));
+    }
+    NABU_HIP(hipMemcpyAsync(wi + L.hist_pred + (size_t)t * N, wi + L.ids, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
+    NABU_HIP(hipMemcpyAsync(wi + L.hist_parent + (size_t)t * N, par, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
+    const int tmp = cur; cur = nxt; nxt = tmp;
+    Tn = t + 1;
+    NABU_HIP(hipMemcpyAsync(done.data(), wi + L.all_seen, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    NABU_HIP(hipStreamSynchronize(s));
+    bool all = true;
+    for (int b = 0; b < B; ++b) all = all && done[b] != 0;
+    if (all) break;
+  }
+  hipLaunchKernelGGL(beam_backtrace_kernel, dim3(gN), dim3(DT), 0, s, N, W, Tn, S, wi + L.hist_pred, wi + L.hist_parent,
+                     sequences, wi + L.src);
+  NABU_LAUNCH_CHECK();
+  if (alignments)
+    for (int m = 0; m < M; ++m) {
+      hipLaunchKernelGGL(beam_align_kernel, dim3(N, S), dim3(DT), 0, s, N, W, Tn, S, d->Te[m], w + L.hist_align[m], wi + L.src,
+                         alignments[m]);
+      NABU_LAUNCH_CHECK();
+    }
   hipLaunchKernelGGL(beam_scores_kernel, dim3(gN), dim3(DT), 0, s, N, d->length_penalty, w + L.logprobs, wi + L.lengths,
                      scores, lengths);
   NABU_LAUNCH_CHECK();

@@ -10,12 +10,15 @@ KINDS = {'vanilla': 0, 'location_aware': 1, 'windowed': 2}
 PROB_FNS = {'softmax': 0, 'sigmoid': 1, 'normalized_sigmoid': 2}
 
 
-def factory(conf, num_units, encoded, encoded_seq_length):
-    '''create the attention mechanism (reference attention.py:6-39)'''
+def factory(conf, num_units, encoded, encoded_seq_length, index=0):
+    '''create the attention mechanism (reference attention.py:6-39).  index = position of the mechanism in the
+    list the Speller hands to the AttentionWrapper (speller.py:49-61): mechanism 0 keeps the plain scope names, mechanism
+    m > 0 gets the suffix _m TF's name uniquification appends to a repeated scope (see BahdanauAttention.variables)'''
     if conf['probability_fn'] not in PROB_FNS:
         raise KeyError(conf['probability_fn'])              # the reference indexes a dict (attention.py:9-13)
     mech = _mechanism(conf, num_units, encoded, encoded_seq_length)
     mech.prob_fn = PROB_FNS[conf['probability_fn']]
+    mech.index = int(index)
     return mech
 
 
@@ -40,6 +43,7 @@ class BahdanauAttention(object):
     kind = 0
     prob_fn = 0                                  # softmax
     scope = 'bahdanau_attention'
+    index = 0                                    # position in the AttentionWrapper's list of mechanisms
 
     def __init__(self, num_units, memory, memory_sequence_length):
         self.num_units = int(num_units)
@@ -47,11 +51,17 @@ class BahdanauAttention(object):
         self.memory_sequence_length = memory_sequence_length
         self.numfilt = self.filtersize = 0
 
+    @property
+    def suffix(self):
+        return '_%d' % self.index if self.index else ''
+
     def variables(self):
-        '''memory_layer / query_layer kernels (Dense, no bias) and attention_v'''
+        '''memory_layer / query_layer kernels (Dense, no bias) and attention_v.  Mechanism m > 0 of one decoder
+        repeats the scopes of mechanism 0, which TF makes unique with the suffix _m: memory_layer_m,
+        <scope>_m [TF-1.8 recalled]'''
         E, U = self.memory.shape[2], self.num_units
-        v = {'memory_kernel': vs.get_variable('memory_layer/kernel', [E, U])}
-        with vs.variable_scope(self.scope):
+        v = {'memory_kernel': vs.get_variable('memory_layer%s/kernel' % self.suffix, [E, U])}
+        with vs.variable_scope(self.scope + self.suffix):
             v['query_kernel'] = vs.get_variable('query_layer/kernel', [U, U])
             v['attention_v'] = vs.get_variable('attention_v', [U])
         return v
@@ -69,7 +79,7 @@ class LocationAwareAttention(BahdanauAttention):
 
     def variables(self):
         v = super(LocationAwareAttention, self).variables()
-        with vs.variable_scope(self.scope):
+        with vs.variable_scope(self.scope + self.suffix):
             # tf.layers.conv1d kernel [filtersize, 1, numfilt] (stored [K,F]) and the Dense on top
             v['conv_kernel'] = vs.get_variable('conv1d/kernel', [self.filtersize, 1, self.numfilt])
             v['conv_proj'] = vs.get_variable('process_conv_features/kernel', [self.numfilt, self.num_units])

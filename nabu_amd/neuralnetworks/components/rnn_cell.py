@@ -21,13 +21,22 @@ class LSTMCell(object):
 
 
 class AttentionWrapper(object):
-    '''tf.contrib.seq2seq.AttentionWrapper(cells, mechanism, output_attention=False):
-    cell input = [inputs, previous context]; query = top cell output; state carries
-    context ("attention") and alignments'''
+    '''tf.contrib.seq2seq.AttentionWrapper(cells, mechanism(s), output_attention=False):
+    cell input = [inputs, previous context(s)]; query = top cell output; state carries
+    context ("attention") and alignments.  attention_mechanism is one mechanism or a list of them (one per
+    encoded input, reference speller.py:49-61): the contexts are concatenated in list order'''
 
     def __init__(self, cells, attention_mechanism):
         self.cells = cells
-        self.attention_mechanism = attention_mechanism
+        self.attention_mechanisms = list(attention_mechanism) if isinstance(attention_mechanism, (list, tuple)) \
+            else [attention_mechanism]
+        if not self.attention_mechanisms:
+            raise ValueError('AttentionWrapper needs at least one attention mechanism')
+
+    @property
+    def attention_mechanism(self):
+        '''the first (for a one-memory decoder: the only) mechanism'''
+        return self.attention_mechanisms[0]
 
     @property
     def output_size(self):
@@ -49,6 +58,7 @@ class AttentionProjectionWrapper(object):
         return self._output_dim
 
     def variables(self, context_dim):
+        '''context_dim: the total width of the concatenated contexts'''
         U = self._cell.output_size
         with vs.variable_scope('dense'):
             return (vs.get_variable('kernel', [U + context_dim, self._output_dim]),

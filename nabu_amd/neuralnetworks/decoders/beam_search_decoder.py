@@ -29,7 +29,8 @@ class BeamSearchDecoder(decoder.Decoder):
 
     def __call__(self, inputs, input_seq_length):
         '''Returns {output: (sequences [B,W,time], lengths [B,W], scores [B,W],
-        alignments [B,W,time,Te] or None)}, beams best first'''
+        alignments [B,W,time,Te] or None)}, beams best first; a model with several inputs gives the alignments as
+        a dict {input name: [B,W,time,Te of that input]}'''
         model = self.model
         output_name = list(model.output_dims.keys())[0]
         with torch.no_grad(), vs.as_default(model.store):
@@ -38,11 +39,14 @@ class BeamSearchDecoder(decoder.Decoder):
             # the decoder's own scope, so the cell's variables are the trained ones
             with vs.variable_scope(model.decoder.scope):
                 cell = model.decoder.create_cell(encoded, encoded_seq_length, False)
-                e = list(encoded.keys())[0]
+                # every encoded input, in the order of the cell's attention mechanisms
+                names = list(encoded.keys())
                 res = rnn_decoder.beam_search(
-                    cell, encoded[e], encoded_seq_length[e], beam_width=int(self.conf['beam_width']),
+                    cell, [encoded[e] for e in names], [encoded_seq_length[e] for e in names], beam_width=int(self.conf['beam_width']),
                     max_steps=int(self.conf['max_steps']), length_penalty=float(self.conf['length_penalty']),
                     temperature=float(self.conf['temperature']), with_alignments=self._keep_alignments())
+        if isinstance(res[3], list):       # several inputs: the alignments per input name
+            res = res[:3] + ({n: a for n, a in zip(names, res[3])},)
         return {output_name: res}
 
     def write(self, outputs, directory, names):
@@ -55,7 +59,10 @@ class BeamSearchDecoder(decoder.Decoder):
                 for b in range(sequences.shape[1]):
                     text = ' '.join(self.alphabet[s] for s in sequences[i, b, :lengths[i, b]])
                     fid.write('%f %s\n' % (scores[i, b], text))
-            if alignments is not None:
+            if isinstance(alignments, dict):
+                for inp, al in alignments.items():
+                    np.save(os.path.join(directory, '%s_alignments_%s.npy' % (name, inp)), al[i].cpu().numpy())
+            elif alignments is not None:
                 np.save(os.path.join(directory, name + '_alignments.npy'), alignments[i].cpu().numpy())
 
     def update_evaluation_loss(self, loss, outputs, references, reference_seq_length):

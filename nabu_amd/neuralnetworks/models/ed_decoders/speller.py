@@ -16,11 +16,10 @@ class Speller(rnn_decoder.RNNDecoder):
             num_units=int(self.conf['num_units']),
             output_keep_prob=keep if (keep < 1 and is_training) else 1.0)
             for _ in range(int(self.conf['num_layers']))]
-        if len(encoded) != 1:
-            raise NotImplementedError('the Speller attends over exactly one encoded sequence here')
-        e = list(encoded.keys())[0]
-        mechanism = attention.factory(conf=self.conf, num_units=rnn_cells[-1].num_units,
-                                      encoded=encoded[e], encoded_seq_length=encoded_seq_length[e])
-        cell = rnn_cell_lib.AttentionWrapper(cells=rnn_cells, attention_mechanism=mechanism)
+        # one mechanism per encoded input, in the order of `encoded` (reference speller.py:49-61)
+        mechanisms = [attention.factory(conf=self.conf, num_units=rnn_cells[-1].num_units, encoded=encoded[e],
+                                        encoded_seq_length=encoded_seq_length[e], index=m)
+                      for m, e in enumerate(encoded)]
+        cell = rnn_cell_lib.AttentionWrapper(cells=rnn_cells, attention_mechanism=mechanisms)
         return rnn_cell_lib.AttentionProjectionWrapper(
             cell=cell, output_dim=list(self.output_dims.values())[0])
