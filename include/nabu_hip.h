@@ -616,8 +616,9 @@ int nabu_speller_multi_bwd(const nabu_speller_multi_desc *d, const float *const 
                            const nabu_speller_multi_params *p, const float *dlogits, void *reserve,
                            const nabu_speller_multi_grads *g, float *const *dvalues_host, void *ws,
                            size_t ws_bytes, nabu_stream_t stream);
-/* Beam search over M encoded inputs: nabu_speller_beam_search's loop (same pruning, stop test and outputs) with the
- * cell above on B*beam_width rows; the M alignment states are pruned and gathered per memory and
+/* Beam search over M encoded inputs: the loop of nabu_speller_beam_search (one function for both entry points: same
+ * pruning, stop test and outputs) with the cell above on B*beam_width rows and the step's M attention mechanisms as
+ * one launch, also for M = 1; the M alignment states are pruned and gathered per memory and
  * alignments_host[m] (may be NULL as a whole) receives [B,W,max_steps,Te[m]]. */
 typedef struct {
   uint32_t size;

@@ -33,6 +33,15 @@ int fail(int code, const char *fmt, ...);
                           __LINE__, hipGetErrorString(e_));                   \
   } while (0)
 
+// a call that reports its own error: pass it on
+#define NABU_TRY(call) do { int e_ = (call); if (e_) return e_; } while (0)
+
+// C = op(A)·op(B) (+ beta*C) (+ bias) on row-major operands (the Speller's drivers and the beam search)
+static inline int mm(bool ta, bool tb, int M, int N, int K, const float *A, int lda, const float *Bm, int ldb, float beta,
+                     float *C, int ldc, const float *bias, float *ws, size_t wsb, nabu_stream_t st) {
+  return nabu_gemm_f32(ta, tb, M, N, K, 1.f, A, lda, Bm, ldb, beta, C, ldc, bias, 0, 0, 0, ws, wsb, st);
+}
+
 // speller.hip: x[r*ld] = 1 for r < rows (initial alignments of the windowed attention)
 int first_col_one(int rows, int ld, float *x, hipStream_t s);
 

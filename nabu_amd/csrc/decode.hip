@@ -8,8 +8,8 @@
 //     keeps the beam (<= beam_width prefixes with their blank/label/total log-probabilities) in
 //     LDS; the prefix tree (parent, label, beam slot, children table) lives in an HBM workspace
 //     that stays L2-resident.
-//   * attention: the per-step cell kernels of speller.hip on B*beam_width rows, then one
-//     pruning workgroup per utterance and row gathers of the cell state.
+//   * attention: the per-step cell kernels of speller.hip / speller_multi.hip on B*beam_width rows, then one
+//     pruning workgroup per utterance and row gathers of the cell state (ONE loop for 1..M encoded inputs: beam_run).
 // Selecting the k best of n candidates, exact and deterministic with ties to the lower candidate
 // index: CTC (k = 100 of ~4000 per frame) uses a radix select of the k-th largest key + compaction +
 // rank sort (select_best); the attention search (k = 16) uses k rounds of a workgroup-wide arg-max
@@ -530,67 +530,244 @@ static int set_lds(const void *fn, size_t bytes, const char *what) {
   return 0;
 }
 
-// workspace of the attention beam search, offsets in 32-bit words
-struct BeamWs {
-  size_t valuesT, keysB, keysT, lenT, big, z, q, logits, acts, ids, logprobs, lengths, finished, seen, parent,
-      stay, all_seen, scratch, hist_pred, hist_parent, hist_align, src, gemm, gemm_bytes, total;
-  size_t h[3][NABU_SPELLER_MAX_LAYERS], c[3][NABU_SPELLER_MAX_LAYERS], ctx[3], align[3];
+// ===========================================================================
+// The attention beam search over M encoded inputs.  ONE loop (beam_run) for both entry points: each fills a BeamGeo and a
+// BeamIO from its own descriptor and parameter struct (nabu_speller_params is the M = 1 case of the arrays).  A step is
+// the cell of the Speller on B*W rows — the contexts of all mechanisms in one [N, sum E] buffer (one product, one
+// gather), M alignment states — then pruning and the row gathers.  The two entry points differ in the attention step:
+//   nabu_speller_beam_search        nabu_attn_fwd (with the kernels it dispatches to; its partials in the pruning scratch),
+//                                   the query product against query_kernel itself;
+//   nabu_speller_multi_beam_search  multi_attn_fwd, ONE launch for the step's M mechanisms (speller_multi.hip), the query
+//                                   product against the column-concatenated [U, M U] kernel — also with M = 1.
+constexpr int MM = NABU_SPELLER_MAX_MEMORIES;
+struct BeamGeo {
+  int M, B, W, U, C, nl, S, kind, K, F, prob_fn, Te[MM], E[MM], SE;
+  float lpw, temperature;
+  bool multi;                 // the step's attention is multi_attn_fwd
+};
+struct BeamIO {
+  const float *values[MM];
+  const int32_t *enc_len[MM];
+  const float *memory_kernel[MM], *query_kernel[MM], *attention_v[MM], *conv_kernel[MM], *conv_proj[MM];
+  const float *out_kernel, *out_bias, *const *lstm_kernel, *const *lstm_bias;
+  float *alignments[MM];      // all null: not wanted
+  int32_t *sequences, *lengths, *num_steps;
+  float *scores;
 };
 
-static BeamWs beam_ws(const nabu_beam_desc *d) {
-  BeamWs s;
-  const size_t B = d->B, W = d->beam_width, N = B * W, U = d->U, E = d->E, Te = d->Te, C = d->C, S = d->max_steps;
-  size_t o = 0;
+// workspace, offsets in 32-bit words
+struct BeamWs {
+  size_t valuesT[MM], keysB[MM], keysT[MM], lenT[MM], hist_align[MM], align[3][MM];
+  size_t part[MM], wqcat, tickets;       // multi_attn_fwd only
+  size_t attn_bytes;                     // nabu_attn_fwd only: its scratch, which is the pruning scratch
+  size_t big, z, q, logits, acts, ids, logprobs, lengths, finished, seen, parent, stay, all_seen, scratch, hist_pred,
+      hist_parent, src, gemm, gemm_bytes, total;
+  size_t h[3][NABU_SPELLER_MAX_LAYERS], c[3][NABU_SPELLER_MAX_LAYERS], ctx[3];
+};
+
+static BeamWs beam_ws(const BeamGeo &g) {
+  BeamWs s = {};
+  const size_t B = g.B, W = g.W, N = B * W, U = g.U, C = g.C, S = g.S, M = g.M, SE = g.SE;
+  size_t o = 0, gb = 0;
   auto take = [&](size_t n) { size_t r = o; o += (n + 3) / 4 * 4; return r; };
-  s.valuesT = take(N * Te * E);
-  s.keysB = take(B * Te * U);
-  s.keysT = take(N * Te * U);
-  s.lenT = take(N); s.big = take(N);
-  s.z = take(N * 4 * U); s.q = take(N * U); s.logits = take(N * C); s.acts = take(N * 4 * U);
+  auto mx = [&](size_t v) { if (v > gb) gb = v; };
+  size_t prune = B * (W * C + W);
+  for (int m = 0; m < g.M; ++m) {
+    const size_t Te = g.Te[m], E = g.E[m];
+    s.valuesT[m] = take(N * Te * E); s.keysB[m] = take(B * Te * U); s.keysT[m] = take(N * Te * U); s.lenT[m] = take(N);
+    if (g.multi) s.part[m] = take(multi_attn_part_floats((int)N, (int)Te, (int)E, (int)U, g.kind, g.K, g.F, g.prob_fn));
+    s.hist_align[m] = take(S * N * Te);
+    for (int k = 0; k < 3; ++k) s.align[k][m] = take(N * Te);
+    mx(nabu_gemm_ws_bytes((int)(B * Te), (int)U, (int)E));
+  }
+  if (g.multi) {
+    s.wqcat = take(U * M * U); s.tickets = take(M * N);
+  } else {
+    const nabu_attn_desc ad = {sizeof(nabu_attn_desc), (int32_t)N, g.Te[0], g.E[0], g.U, g.kind, g.K, g.F, g.prob_fn};
+    s.attn_bytes = nabu_attn_fwd_ws_bytes(&ad);   // sliced forward (small B*W): partials
+    if (s.attn_bytes / 4 > prune) prune = s.attn_bytes / 4;
+  }
+  s.big = take(N); s.z = take(N * 4 * U); s.q = take(N * M * U); s.logits = take(N * C);
+  s.acts = take(N * 4 * U > N * M ? N * 4 * U : N * M);       // (inference: the attention's normaliser scratch, [M, N])
   s.ids = take(N); s.logprobs = take(N); s.lengths = take(N); s.finished = take(N); s.seen = take(N);
-  s.parent = take(N); s.stay = take(N); s.all_seen = take(B);
-  {
-    const nabu_attn_desc ad = {sizeof(nabu_attn_desc), (int32_t)N, d->Te, d->E, d->U, d->kind, d->K, d->F, d->prob_fn};
-    const size_t need = nabu_attn_fwd_ws_bytes(&ad) / 4, prune = B * (W * C + W);
-    s.scratch = take(need > prune ? need : prune);
-  }
-  s.hist_pred = take(S * N); s.hist_parent = take(S * N);
-  s.hist_align = take(S * N * Te);
-  s.src = take(N * S);
+  s.parent = take(N); s.stay = take(N); s.all_seen = take(B); s.scratch = take(prune);
+  s.hist_pred = take(S * N); s.hist_parent = take(S * N); s.src = take(N * S);
   for (int k = 0; k < 3; ++k) {
-    for (int n = 0; n < d->num_layers; ++n) { s.h[k][n] = take(N * U); s.c[k][n] = take(N * U); }
-    s.ctx[k] = take(N * E);
-    s.align[k] = take(N * Te);
+    for (int n = 0; n < g.nl; ++n) { s.h[k][n] = take(N * U); s.c[k][n] = take(N * U); }
+    s.ctx[k] = take(N * SE);
   }
-  size_t g = 0;
-  auto mx = [&](size_t v) { if (v > g) g = v; };
-  mx(nabu_gemm_ws_bytes((int)N, (int)(4 * U), (int)E)); mx(nabu_gemm_ws_bytes((int)N, (int)(4 * U), (int)U));
-  mx(nabu_gemm_ws_bytes((int)N, (int)U, (int)U)); mx(nabu_gemm_ws_bytes((int)N, (int)C, (int)U));
-  mx(nabu_gemm_ws_bytes((int)N, (int)C, (int)E)); mx(nabu_gemm_ws_bytes((int)(B * Te), (int)U, (int)E));
-  s.gemm_bytes = (g + 255) / 256 * 256;
+  mx(nabu_gemm_ws_bytes((int)N, (int)(4 * U), (int)SE)); mx(nabu_gemm_ws_bytes((int)N, (int)(4 * U), (int)U));
+  mx(nabu_gemm_ws_bytes((int)N, (int)(M * U), (int)U)); mx(nabu_gemm_ws_bytes((int)N, (int)C, (int)U));
+  mx(nabu_gemm_ws_bytes((int)N, (int)C, (int)SE));
+  s.gemm_bytes = (gb + 255) / 256 * 256;
   s.gemm = take(s.gemm_bytes / 4 + 4);
   s.total = o;
   return s;
 }
 
-static int check_beam(const nabu_beam_desc *d) {
-  if (!d || d->size != sizeof(nabu_beam_desc)) return fail(NABU_EINVAL, "beam search: bad descriptor size");
-  if (d->B <= 0 || d->Te <= 0 || d->E <= 0 || d->U <= 0 || d->C <= 1) return fail(NABU_EINVAL, "beam search: bad dimensions");
-  if (d->beam_width <= 0 || d->max_steps <= 0) return fail(NABU_EINVAL, "beam search: beam_width and max_steps must be positive");
-  if (!(d->temperature > 0.f)) return fail(NABU_EINVAL, "beam search: temperature must be positive");
-  if (d->kind < 0 || d->kind > 2 || d->prob_fn < 0 || d->prob_fn > 2)
+static int check_beam(const BeamGeo &g) {
+  if (g.B <= 0 || g.U <= 0 || g.C <= 1) return fail(NABU_EINVAL, "beam search: bad dimensions");
+  if (g.W <= 0 || g.S <= 0) return fail(NABU_EINVAL, "beam search: beam_width and max_steps must be positive");
+  if (!(g.temperature > 0.f)) return fail(NABU_EINVAL, "beam search: temperature must be positive");
+  if (g.kind < 0 || g.kind > 2 || g.prob_fn < 0 || g.prob_fn > 2)
     return fail(NABU_EINVAL, "beam search: unknown attention kind or probability_fn");
-  if (d->num_layers < 1 || d->num_layers > NABU_SPELLER_MAX_LAYERS) return fail(NABU_EUNSUP, "beam search: 1..%d layers", NABU_SPELLER_MAX_LAYERS);
-  if (d->U % 4 || d->E % 4) return fail(NABU_EUNSUP, "beam search: num_units and encoder dim must be multiples of 4");
-  if ((long long)d->B * d->beam_width > (1 << 20)) return fail(NABU_EUNSUP, "beam search: B*beam_width too large");
+  if (g.nl < 1 || g.nl > NABU_SPELLER_MAX_LAYERS) return fail(NABU_EUNSUP, "beam search: 1..%d layers", NABU_SPELLER_MAX_LAYERS);
+  if ((long long)g.B * g.W > (1 << 20)) return fail(NABU_EUNSUP, "beam search: B*beam_width too large");
+  for (int m = 0; m < g.M; ++m) {
+    if (g.Te[m] <= 0 || g.E[m] <= 0) return fail(NABU_EINVAL, "beam search: bad dimensions");
+    if (g.U % 4 || g.E[m] % 4) return fail(NABU_EUNSUP, "beam search: num_units and encoder dim must be multiples of 4");
+    const nabu_attn_desc a = {sizeof(nabu_attn_desc), g.B * g.W, g.Te[m], g.E[m], g.U, g.kind, g.K, g.F, g.prob_fn};
+    if (g.multi && nabu_attn_bwd_slices(&a) <= 0) return NABU_EUNSUP;       // (its kernels' LDS: the message is theirs)
+  }
   return 0;
 }
 
-static int bmm(int M, int N, int K, const float *A, int lda, const float *Bm, int ldb, float beta, float *C, int ldc,
-               const float *bias, float *ws, size_t wsb, nabu_stream_t st) {
-  return nabu_gemm_f32(0, 0, M, N, K, 1.f, A, lda, Bm, ldb, beta, C, ldc, bias, 0, 0, 0, ws, wsb, st);
+static int beam_run(const BeamGeo &g, const BeamIO &io, void *ws, size_t ws_bytes, nabu_stream_t stream) {
+  NABU_CHECK_ARG(io.out_kernel && io.out_bias && io.sequences && io.lengths && io.scores && io.num_steps && ws,
+                 "beam search: null pointer");
+  for (int m = 0; m < g.M; ++m)
+    NABU_CHECK_ARG(io.values[m] && io.enc_len[m] && io.memory_kernel[m] && io.query_kernel[m] && io.attention_v[m] &&
+                   (g.kind != 1 || (io.conv_kernel[m] && io.conv_proj[m])) && (!io.alignments[0] || io.alignments[m]),
+                   "beam search: null pointer for an encoded input");
+  const BeamWs L = beam_ws(g);
+  if (ws_bytes < L.total * 4) return fail(NABU_EWS, "beam search: workspace too small");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float *w = static_cast<float *>(ws);
+  int32_t *wi = static_cast<int32_t *>(ws);
+  const int B = g.B, W = g.W, N = B * W, U = g.U, C = g.C, nl = g.nl, S = g.S, M = g.M, SE = g.SE, MU = M * U;
+  float *gw = w + L.gemm;
+  const size_t gwb = L.gemm_bytes;
+  const nabu_attn_desc ad = {sizeof(nabu_attn_desc), N, g.Te[0], g.E[0], U, g.kind, g.K, g.F, g.prob_fn};
+  auto tile = [&](const void *src, void *dst, size_t F) {
+    size_t gy = (F + DT * 4 - 1) / (DT * 4);
+    hipLaunchKernelGGL(tile_rows_kernel, dim3(N, gy > 64 ? 64 : (unsigned)gy), dim3(DT), 0, s, W, F,
+                       static_cast<const uint32_t *>(src), static_cast<uint32_t *>(dst));
+  };
+  // tile_batch of the encoder outputs / their lengths; keys = memory_layer(values) once per utterance
+  for (int m = 0; m < M; ++m) {
+    const int Te = g.Te[m], E = g.E[m];
+    NABU_TRY(mm(0, 0, B * Te, U, E, io.values[m], E, io.memory_kernel[m], U, 0.f, w + L.keysB[m], U, nullptr, gw, gwb, stream));
+    tile(io.values[m], w + L.valuesT[m], (size_t)Te * E);
+    tile(w + L.keysB[m], w + L.keysT[m], (size_t)Te * U);
+    tile(io.enc_len[m], wi + L.lenT[m], 1);
+    NABU_LAUNCH_CHECK();
+    if (g.multi) NABU_TRY(put_cols(U, U, io.query_kernel[m], w + L.wqcat, MU, m * U, s));
+  }
+  const float *wq = g.multi ? w + L.wqcat : io.query_kernel[0];     // [U, M U]
+  const int gN = (N + DT - 1) / DT;
+  hipLaunchKernelGGL(fill_i32_kernel, dim3(gN), dim3(DT), 0, s, (size_t)N, INT_MAX, wi + L.big);
+  hipLaunchKernelGGL(fill_i32_kernel, dim3(gN), dim3(DT), 0, s, (size_t)N, C - 1, wi + L.ids);       // start tokens
+  hipLaunchKernelGGL(beam_init_kernel, dim3(gN), dim3(DT), 0, s, N, W, w + L.logprobs);
+  NABU_LAUNCH_CHECK();
+  NABU_HIP(hipMemsetAsync(wi + L.lengths, 0, (size_t)N * 4, s));
+  NABU_HIP(hipMemsetAsync(wi + L.finished, 0, (size_t)N * 4, s));
+  NABU_HIP(hipMemsetAsync(wi + L.seen, 0, (size_t)N * 4, s));
+  if (g.multi) NABU_HIP(hipMemsetAsync(wi + L.tickets, 0, (size_t)M * N * 4, s));
+  int cur = 0, fresh = 1, nxt = 2;                 // state sets: before the step, after the cell, after pruning
+  for (int n = 0; n < nl; ++n) {
+    NABU_HIP(hipMemsetAsync(w + L.h[cur][n], 0, (size_t)N * U * 4, s));
+    NABU_HIP(hipMemsetAsync(w + L.c[cur][n], 0, (size_t)N * U * 4, s));
+  }
+  NABU_HIP(hipMemsetAsync(w + L.ctx[cur], 0, (size_t)N * SE * 4, s));
+  for (int m = 0; m < M; ++m) {
+    NABU_HIP(hipMemsetAsync(w + L.align[cur][m], 0, (size_t)N * g.Te[m] * 4, s));
+    if (g.kind == 2) NABU_TRY(first_col_one(N, g.Te[m], w + L.align[cur][m], s));
+  }
+  float *z = w + L.z, *lg = w + L.logits;
+  const int32_t *big = wi + L.big;
+  int32_t *par = wi + L.parent, *stay = wi + L.stay;
+  std::vector<int32_t> done(B);
+  int Tn = 0;
+  for (int t = 0; t < S; ++t) {
+    // the cell on all B*W rows (the step of nabu_speller_fwd / nabu_speller_multi_fwd; no dropout at inference)
+    for (int n = 0; n < nl; ++n) {
+      const float *Kn = io.lstm_kernel[n];
+      if (n == 0) {
+        NABU_TRY(mm(0, 0, N, 4 * U, SE, w + L.ctx[cur], SE, Kn + (size_t)C * 4 * U, 4 * U, 0.f, z, 4 * U, nullptr, gw, gwb, stream));
+        NABU_TRY(mm(0, 0, N, 4 * U, U, w + L.h[cur][0], U, Kn + (size_t)(C + SE) * 4 * U, 4 * U, 1.f, z, 4 * U, nullptr, gw, gwb, stream));
+        NABU_TRY(nabu_lstm_cell_fwd(N, U, 0, big, z, io.lstm_bias[0], Kn, wi + L.ids, w + L.c[cur][0], w + L.h[cur][0],
+                                    w + L.acts, w + L.c[fresh][0], w + L.h[fresh][0], stream));
+      } else {
+        NABU_TRY(mm(0, 0, N, 4 * U, U, w + L.h[fresh][n - 1], U, Kn, 4 * U, 0.f, z, 4 * U, nullptr, gw, gwb, stream));
+        NABU_TRY(mm(0, 0, N, 4 * U, U, w + L.h[cur][n], U, Kn + (size_t)U * 4 * U, 4 * U, 1.f, z, 4 * U, nullptr, gw, gwb, stream));
+        NABU_TRY(nabu_lstm_cell_fwd(N, U, 0, big, z, io.lstm_bias[n], nullptr, nullptr, w + L.c[cur][n], w + L.h[cur][n],
+                                    w + L.acts, w + L.c[fresh][n], w + L.h[fresh][n], stream));
+      }
+    }
+    const float *htop = w + L.h[fresh][nl - 1];
+    NABU_TRY(mm(0, 0, N, MU, U, htop, U, wq, MU, 0.f, w + L.q, MU, nullptr, gw, gwb, stream));
+    // (normaliser scratch of the attention: w + L.acts — the saved gate activations are not used at inference)
+    if (g.multi) {
+      MultiAttnMem mem[MM];
+      for (int m = 0; m < M; ++m)
+        mem[m] = MultiAttnMem{g.Te[m], g.E[m], wi + L.lenT[m], w + L.keysT[m], w + L.valuesT[m], io.attention_v[m],
+                              io.conv_kernel[m], io.conv_proj[m], w + L.align[cur][m], w + L.align[fresh][m],
+                              w + L.acts + (size_t)m * N, w + L.part[m],
+                              reinterpret_cast<unsigned *>(wi + L.tickets) + (size_t)m * N};
+      NABU_TRY(multi_attn_fwd(M, N, U, g.kind, g.K, g.F, g.prob_fn, 0, big, w + L.q, w + L.ctx[cur], w + L.ctx[fresh], mem, s));
+    } else {
+      NABU_TRY(nabu_attn_fwd(&ad, 0, big, wi + L.lenT[0], w + L.keysT[0], w + L.valuesT[0], w + L.q, io.attention_v[0],
+                             io.conv_kernel[0], io.conv_proj[0], w + L.align[cur][0], w + L.ctx[cur], w + L.align[fresh][0],
+                             w + L.ctx[fresh], w + L.acts, w + L.scratch, L.attn_bytes, stream));
+    }
+    // AttentionProjectionWrapper: [h, contexts of this step]·W + b (rnn_cell.py:145-155)
+    NABU_TRY(mm(0, 0, N, C, U, htop, U, io.out_kernel, C, 0.f, lg, C, io.out_bias, gw, gwb, stream));
+    NABU_TRY(mm(0, 0, N, C, SE, w + L.ctx[fresh], SE, io.out_kernel + (size_t)U * C, C, 1.f, lg, C, nullptr, gw, gwb, stream));
+    // expand + prune; the predicted ids are the next step's inputs
+    NABU_TRY(nabu_beam_prune(B, W, C, lg, g.temperature, g.lpw, w + L.logprobs, wi + L.lengths, wi + L.finished,
+                             wi + L.seen, wi + L.ids, par, stay, wi + L.all_seen, w + L.scratch, stream));
+    for (int n = 0; n < nl; ++n) {
+      NABU_TRY(nabu_beam_gather(B, W, U, w + L.h[fresh][n], w + L.h[cur][n], par, stay, w + L.h[nxt][n], stream));
+      NABU_TRY(nabu_beam_gather(B, W, U, w + L.c[fresh][n], w + L.c[cur][n], par, stay, w + L.c[nxt][n], stream));
+    }
+    NABU_TRY(nabu_beam_gather(B, W, SE, w + L.ctx[fresh], w + L.ctx[cur], par, stay, w + L.ctx[nxt], stream));
+    for (int m = 0; m < M; ++m)
+      NABU_TRY(nabu_beam_gather(B, W, g.Te[m], w + L.align[fresh][m], w + L.align[cur][m], par, stay, w + L.align[nxt][m], stream));
+    NABU_HIP(hipMemcpyAsync(wi + L.hist_pred + (size_t)t * N, wi + L.ids, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
+    NABU_HIP(hipMemcpyAsync(wi + L.hist_parent + (size_t)t * N, par, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
+    for (int m = 0; m < M; ++m)
+      NABU_HIP(hipMemcpyAsync(w + L.hist_align[m] + (size_t)t * N * g.Te[m], w + L.align[nxt][m], (size_t)N * g.Te[m] * 4,
+                              hipMemcpyDeviceToDevice, s));
+    const int tmp = cur; cur = nxt; nxt = tmp;
+    Tn = t + 1;
+    // dynamic_decode's stop test: every slot has been finished at some step
+    NABU_HIP(hipMemcpyAsync(done.data(), wi + L.all_seen, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    NABU_HIP(hipStreamSynchronize(s));
+    bool all = true;
+    for (int b = 0; b < B; ++b) all = all && done[b] != 0;
+    if (all) break;
+  }
+  // finalize (beam_search_decoder.py:341-451)
+  hipLaunchKernelGGL(beam_backtrace_kernel, dim3(gN), dim3(DT), 0, s, N, W, Tn, S, wi + L.hist_pred, wi + L.hist_parent,
+                     io.sequences, wi + L.src);
+  NABU_LAUNCH_CHECK();
+  for (int m = 0; m < M && io.alignments[0]; ++m) {
+    hipLaunchKernelGGL(beam_align_kernel, dim3(N, S), dim3(DT), 0, s, N, W, Tn, S, g.Te[m], w + L.hist_align[m], wi + L.src,
+                       io.alignments[m]);
+    NABU_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(beam_scores_kernel, dim3(gN), dim3(DT), 0, s, N, g.lpw, w + L.logprobs, wi + L.lengths, io.scores,
+                     io.lengths);
+  NABU_LAUNCH_CHECK();
+  *io.num_steps = Tn;
+  return 0;
 }
-#define DEC_TRY(call) do { int e_ = (call); if (e_) return e_; } while (0)
+
+// the two descriptors as a BeamGeo (checked)
+static int beam_geo(const nabu_beam_desc *d, BeamGeo *g) {
+  if (!d || d->size != sizeof(nabu_beam_desc)) return fail(NABU_EINVAL, "beam search: bad descriptor size");
+  *g = BeamGeo{1, d->B, d->beam_width, d->U, d->C, d->num_layers, d->max_steps, d->kind, d->K, d->F, d->prob_fn,
+               {d->Te}, {d->E}, d->E, d->length_penalty, d->temperature, false};
+  return check_beam(*g);
+}
+static int beam_geo(const nabu_multi_beam_desc *d, BeamGeo *g) {
+  if (!d || d->size != sizeof(nabu_multi_beam_desc)) return fail(NABU_EINVAL, "multi beam search: bad descriptor size");
+  if (d->M < 1 || d->M > MM) return fail(NABU_EUNSUP, "multi beam search: 1..%d encoded inputs", MM);
+  *g = BeamGeo{d->M, d->B, d->beam_width, d->U, d->C, d->num_layers, d->max_steps, d->kind, d->K, d->F, d->prob_fn,
+               {}, {}, 0, d->length_penalty, d->temperature, true};
+  for (int m = 0; m < d->M; ++m) { g->Te[m] = d->Te[m]; g->E[m] = d->E[m]; g->SE += d->E[m]; }
+  return check_beam(*g);
+}
 
 }  // namespace nabu
 
@@ -611,7 +788,7 @@ extern "C" int nabu_ctc_beam_search(int B, int T, int C, int beam_width, int mer
   const size_t need = nabu_ctc_beam_ws_bytes(B, T, C, beam_width);
   if (ws_bytes < need) return fail(NABU_EWS, "ctc_beam_search: workspace too small");
   const size_t lds = ctc_beam_lds(C, beam_width);
-  DEC_TRY(set_lds(reinterpret_cast<const void *>(ctc_beam_kernel), lds, "ctc_beam_search"));
+  NABU_TRY(set_lds(reinterpret_cast<const void *>(ctc_beam_kernel), lds, "ctc_beam_search"));
   hipStream_t s = static_cast<hipStream_t>(stream);
   NABU_HIP(hipMemsetAsync(ws, 0xFF, need, s));   // every tree pointer = -1
   CtcBeamArgs a;
@@ -630,7 +807,7 @@ extern "C" int nabu_edit_distance(int B, const int32_t *hyp, int ldh, const int3
   NABU_CHECK_ARG(B > 0 && ldh >= 0 && ldt >= 0, "edit_distance: bad dimensions");
   NABU_CHECK_ARG(hyp_len && truth_len && dist && (hyp || ldh == 0) && (truth || ldt == 0), "edit_distance: null pointer");
   const size_t lds = 3 * ((size_t)ldh + 1) * 4;
-  DEC_TRY(set_lds(reinterpret_cast<const void *>(edit_distance_kernel), lds, "edit_distance"));
+  NABU_TRY(set_lds(reinterpret_cast<const void *>(edit_distance_kernel), lds, "edit_distance"));
   hipLaunchKernelGGL(edit_distance_kernel, dim3(B), dim3(DT), lds, static_cast<hipStream_t>(stream), B, hyp, ldh,
                      hyp_len, truth, ldt, truth_len, dist);
   NABU_LAUNCH_CHECK();
@@ -645,7 +822,7 @@ extern "C" int nabu_beam_prune(int B, int W, int C, const float *logits, float t
   NABU_CHECK_ARG(logits && logprobs && lengths && finished && seen && pred_ids && parent && stay && all_seen && scratch,
                  "beam_prune: null pointer");
   const size_t lds = 5 * (size_t)W * 4;
-  DEC_TRY(set_lds(reinterpret_cast<const void *>(beam_prune_kernel), lds, "beam_prune"));
+  NABU_TRY(set_lds(reinterpret_cast<const void *>(beam_prune_kernel), lds, "beam_prune"));
   PruneArgs a = {B, W, C, logits, 1.f / temperature, length_penalty_w, logprobs, lengths, finished, seen,
                  pred_ids, parent, stay, all_seen, scratch};
   hipLaunchKernelGGL(beam_prune_kernel, dim3(B), dim3(DT), lds, static_cast<hipStream_t>(stream), a);
@@ -665,194 +842,26 @@ extern "C" int nabu_beam_gather(int B, int W, int F, const float *fresh, const f
 }
 
 extern "C" size_t nabu_speller_beam_ws_bytes(const nabu_beam_desc *d) {
-  if (check_beam(d)) return 0;
-  return beam_ws(d).total * 4;
+  BeamGeo g;
+  return beam_geo(d, &g) ? 0 : beam_ws(g).total * 4;
 }
 
 extern "C" int nabu_speller_beam_search(const nabu_beam_desc *d, const float *values, const int32_t *enc_len,
                                         const nabu_speller_params *p, int32_t *sequences, int32_t *lengths,
                                         float *scores, float *alignments, int32_t *num_steps, void *ws,
                                         size_t ws_bytes, nabu_stream_t stream) {
-  if (int e = check_beam(d)) return e;
-  NABU_CHECK_ARG(values && enc_len && p && sequences && lengths && scores && num_steps && ws, "speller_beam_search: null pointer");
-  const BeamWs L = beam_ws(d);
-  if (ws_bytes < L.total * 4) return fail(NABU_EWS, "speller_beam_search: workspace too small");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  float *w = static_cast<float *>(ws);
-  int32_t *wi = static_cast<int32_t *>(ws);
-  const int B = d->B, W = d->beam_width, N = B * W, U = d->U, E = d->E, Te = d->Te, C = d->C, nl = d->num_layers,
-            S = d->max_steps;
-  float *gw = w + L.gemm;
-  const size_t gwb = L.gemm_bytes;
-  const nabu_attn_desc ad = {sizeof(nabu_attn_desc), N, Te, E, U, d->kind, d->K, d->F, d->prob_fn};
-  const size_t attn_wsb = nabu_attn_fwd_ws_bytes(&ad);   // sliced forward (small B*W): partials in the pruning scratch
-  auto tile = [&](const void *src, void *dst, size_t F) {
-    size_t gy = (F + DT * 4 - 1) / (DT * 4);
-    hipLaunchKernelGGL(tile_rows_kernel, dim3(N, gy > 64 ? 64 : (unsigned)gy), dim3(DT), 0, s, W, F,
-                       static_cast<const uint32_t *>(src), static_cast<uint32_t *>(dst));
-  };
-  // tile_batch of the encoder output / its lengths; keys = memory_layer(values) once per utterance
-  DEC_TRY(bmm(B * Te, U, E, values, E, p->memory_kernel, U, 0.f, w + L.keysB, U, nullptr, gw, gwb, stream));
-  tile(values, w + L.valuesT, (size_t)Te * E);
-  tile(w + L.keysB, w + L.keysT, (size_t)Te * U);
-  tile(enc_len, wi + L.lenT, 1);
-  NABU_LAUNCH_CHECK();
-  const int gN = (N + DT - 1) / DT;
-  hipLaunchKernelGGL(fill_i32_kernel, dim3(gN), dim3(DT), 0, s, (size_t)N, INT_MAX, wi + L.big);
-  hipLaunchKernelGGL(fill_i32_kernel, dim3(gN), dim3(DT), 0, s, (size_t)N, C - 1, wi + L.ids);       // start tokens
-  hipLaunchKernelGGL(beam_init_kernel, dim3(gN), dim3(DT), 0, s, N, W, w + L.logprobs);
-  NABU_LAUNCH_CHECK();
-  NABU_HIP(hipMemsetAsync(wi + L.lengths, 0, (size_t)N * 4, s));
-  NABU_HIP(hipMemsetAsync(wi + L.finished, 0, (size_t)N * 4, s));
-  NABU_HIP(hipMemsetAsync(wi + L.seen, 0, (size_t)N * 4, s));
-  int cur = 0, fresh = 1, nxt = 2;                 // state sets: before the step, after the cell, after pruning
-  for (int n = 0; n < nl; ++n) {
-    NABU_HIP(hipMemsetAsync(w + L.h[cur][n], 0, (size_t)N * U * 4, s));
-    NABU_HIP(hipMemsetAsync(w + L.c[cur][n], 0, (size_t)N * U * 4, s));
-  }
-  NABU_HIP(hipMemsetAsync(w + L.ctx[cur], 0, (size_t)N * E * 4, s));
-  NABU_HIP(hipMemsetAsync(w + L.align[cur], 0, (size_t)N * Te * 4, s));
-  if (d->kind == 2) DEC_TRY(first_col_one(N, Te, w + L.align[cur], s));
-  float *z = w + L.z, *lg = w + L.logits;
-  const int32_t *big = wi + L.big, *lenT = wi + L.lenT;
-  int32_t *par = wi + L.parent, *stay = wi + L.stay;
-  std::vector<int32_t> done(B);
-  int Tn = 0;
-  for (int t = 0; t < S; ++t) {
-    // the cell on all B*W rows (the step of nabu_speller_fwd; no dropout at inference)
-    for (int n = 0; n < nl; ++n) {
-      const float *Kn = p->lstm_kernel[n];
-      if (n == 0) {
-        DEC_TRY(bmm(N, 4 * U, E, w + L.ctx[cur], E, Kn + (size_t)C * 4 * U, 4 * U, 0.f, z, 4 * U, nullptr, gw, gwb, stream));
-        DEC_TRY(bmm(N, 4 * U, U, w + L.h[cur][0], U, Kn + (size_t)(C + E) * 4 * U, 4 * U, 1.f, z, 4 * U, nullptr, gw, gwb, stream));
-        DEC_TRY(nabu_lstm_cell_fwd(N, U, 0, big, z, p->lstm_bias[0], Kn, wi + L.ids, w + L.c[cur][0], w + L.h[cur][0],
-                                   w + L.acts, w + L.c[fresh][0], w + L.h[fresh][0], stream));
-      } else {
-        DEC_TRY(bmm(N, 4 * U, U, w + L.h[fresh][n - 1], U, Kn, 4 * U, 0.f, z, 4 * U, nullptr, gw, gwb, stream));
-        DEC_TRY(bmm(N, 4 * U, U, w + L.h[cur][n], U, Kn + (size_t)U * 4 * U, 4 * U, 1.f, z, 4 * U, nullptr, gw, gwb, stream));
-        DEC_TRY(nabu_lstm_cell_fwd(N, U, 0, big, z, p->lstm_bias[n], nullptr, nullptr, w + L.c[cur][n], w + L.h[cur][n],
-                                   w + L.acts, w + L.c[fresh][n], w + L.h[fresh][n], stream));
-      }
-    }
-    const float *htop = w + L.h[fresh][nl - 1];
-    DEC_TRY(bmm(N, U, U, htop, U, p->query_kernel, U, 0.f, w + L.q, U, nullptr, gw, gwb, stream));
-    DEC_TRY(nabu_attn_fwd(&ad, 0, big, lenT, w + L.keysT, w + L.valuesT, w + L.q, p->attention_v, p->conv_kernel,
-                          p->conv_proj, w + L.align[cur], w + L.ctx[cur], w + L.align[fresh], w + L.ctx[fresh],
-                          w + L.acts /* normaliser scratch: the saved gate activations are not used at inference */,
-                          w + L.scratch, attn_wsb, stream));
-    // AttentionProjectionWrapper: [h, context of this step]·W + b (rnn_cell.py:145-155)
-    DEC_TRY(bmm(N, C, U, htop, U, p->out_kernel, C, 0.f, lg, C, p->out_bias, gw, gwb, stream));
-    DEC_TRY(bmm(N, C, E, w + L.ctx[fresh], E, p->out_kernel + (size_t)U * C, C, 1.f, lg, C, nullptr, gw, gwb, stream));
-    // expand + prune; the predicted ids are the next step's inputs
-    DEC_TRY(nabu_beam_prune(B, W, C, lg, d->temperature, d->length_penalty, w + L.logprobs, wi + L.lengths,
-                            wi + L.finished, wi + L.seen, wi + L.ids, par, stay, wi + L.all_seen, w + L.scratch, stream));
-    for (int n = 0; n < nl; ++n) {
-      DEC_TRY(nabu_beam_gather(B, W, U, w + L.h[fresh][n], w + L.h[cur][n], par, stay, w + L.h[nxt][n], stream));
-      DEC_TRY(nabu_beam_gather(B, W, U, w + L.c[fresh][n], w + L.c[cur][n], par, stay, w + L.c[nxt][n], stream));
-    }
-    DEC_TRY(nabu_beam_gather(B, W, E, w + L.ctx[fresh], w + L.ctx[cur], par, stay, w + L.ctx[nxt], stream));
-    DEC_TRY(nabu_beam_gather(B, W, Te, w + L.align[fresh], w + L.align[cur], par, stay, w + L.align[nxt], stream));
-    NABU_HIP(hipMemcpyAsync(wi + L.hist_pred + (size_t)t * N, wi + L.ids, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
-    NABU_HIP(hipMemcpyAsync(wi + L.hist_parent + (size_t)t * N, par, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
-    NABU_HIP(hipMemcpyAsync(w + L.hist_align + (size_t)t * N * Te, w + L.align[nxt], (size_t)N * Te * 4,
-                            hipMemcpyDeviceToDevice, s));
-    const int tmp = cur; cur = nxt; nxt = tmp;
-    Tn = t + 1;
-    // dynamic_decode's stop test: every slot has been finished at some step
-    NABU_HIP(hipMemcpyAsync(done.data(), wi + L.all_seen, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    NABU_HIP(hipStreamSynchronize(s));
-    bool all = true;
-    for (int b = 0; b < B; ++b) all = all && done[b] != 0;
-    if (all) break;
-  }
-  // finalize (beam_search_decoder.py:341-451)
-  hipLaunchKernelGGL(beam_backtrace_kernel, dim3(gN), dim3(DT), 0, s, N, W, Tn, S, wi + L.hist_pred, wi + L.hist_parent,
-                     sequences, wi + L.src);
-  NABU_LAUNCH_CHECK();
-  if (alignments) {
-    hipLaunchKernelGGL(beam_align_kernel, dim3(N, S), dim3(DT), 0, s, N, W, Tn, S, Te, w + L.hist_align, wi + L.src, alignments);
-    NABU_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(beam_scores_kernel, dim3(gN), dim3(DT), 0, s, N, d->length_penalty, w + L.logprobs, wi + L.lengths,
-                     scores, lengths);
-  NABU_LAUNCH_CHECK();
-  *num_steps = Tn;
-  return 0;
+  BeamGeo g;
+  if (int e = beam_geo(d, &g)) return e;
+  NABU_CHECK_ARG(p, "speller_beam_search: null pointer");
+  const BeamIO io = {{values}, {enc_len}, {p->memory_kernel}, {p->query_kernel}, {p->attention_v}, {p->conv_kernel},
+                     {p->conv_proj}, p->out_kernel, p->out_bias, p->lstm_kernel, p->lstm_bias, {alignments},
+                     sequences, lengths, num_steps, scores};
+  return beam_run(g, io, ws, ws_bytes, stream);
 }
-
-// ===========================================================================
-// Beam search over M encoded inputs (nabu_speller_multi_beam_search): the loop of nabu_speller_beam_search with the
-// cell of nabu_speller_multi_fwd on B*W rows — contexts of all mechanisms in one [N, sum E] buffer (one gather), M
-// alignment states (pruned and gathered per memory), the step's M attention mechanisms in one launch
-// (speller_multi.hip, unchanged).
-namespace nabu {
-struct MBeamWs {
-  size_t valuesT[NABU_SPELLER_MAX_MEMORIES], keysB[NABU_SPELLER_MAX_MEMORIES], keysT[NABU_SPELLER_MAX_MEMORIES],
-      lenT[NABU_SPELLER_MAX_MEMORIES], part[NABU_SPELLER_MAX_MEMORIES], hist_align[NABU_SPELLER_MAX_MEMORIES],
-      align[3][NABU_SPELLER_MAX_MEMORIES];
-  size_t big, z, q, wqcat, logits, acts, ids, logprobs, lengths, finished, seen, parent, stay, all_seen, scratch, tickets,
-      hist_pred, hist_parent, src, gemm, gemm_bytes, total;
-  size_t h[3][NABU_SPELLER_MAX_LAYERS], c[3][NABU_SPELLER_MAX_LAYERS], ctx[3];
-  int SE, MU;
-};
-static int check_mbeam(const nabu_multi_beam_desc *d) {
-  if (!d || d->size != sizeof(nabu_multi_beam_desc)) return fail(NABU_EINVAL, "multi beam search: bad descriptor size");
-  if (d->M < 1 || d->M > NABU_SPELLER_MAX_MEMORIES) return fail(NABU_EUNSUP, "multi beam search: 1..%d encoded inputs", NABU_SPELLER_MAX_MEMORIES);
-  if (d->B <= 0 || d->U <= 0 || d->C <= 1) return fail(NABU_EINVAL, "multi beam search: bad dimensions");
-  if (d->beam_width <= 0 || d->max_steps <= 0) return fail(NABU_EINVAL, "multi beam search: beam_width and max_steps must be positive");
-  if (!(d->temperature > 0.f)) return fail(NABU_EINVAL, "multi beam search: temperature must be positive");
-  if (d->num_layers < 1 || d->num_layers > NABU_SPELLER_MAX_LAYERS) return fail(NABU_EUNSUP, "multi beam search: 1..%d layers", NABU_SPELLER_MAX_LAYERS);
-  if ((long long)d->B * d->beam_width > (1 << 20)) return fail(NABU_EUNSUP, "multi beam search: B*beam_width too large");
-  for (int m = 0; m < d->M; ++m) {
-    const nabu_attn_desc a = {sizeof(nabu_attn_desc), d->B * d->beam_width, d->Te[m], d->E[m], d->U, d->kind, d->K, d->F, d->prob_fn};
-    if (nabu_attn_bwd_slices(&a) <= 0) return NABU_EUNSUP;       // (dimensions, multiples of 4, LDS: the message is theirs)
-  }
-  return 0;
-}
-static MBeamWs mbeam_ws(const nabu_multi_beam_desc *d) {
-  MBeamWs s;
-  const size_t B = d->B, W = d->beam_width, N = B * W, U = d->U, C = d->C, S = d->max_steps, M = d->M;
-  size_t o = 0, SE = 0, g = 0;
-  auto take = [&](size_t n) { size_t r = o; o += (n + 3) / 4 * 4; return r; };
-  auto mx = [&](size_t v) { if (v > g) g = v; };
-  for (int m = 0; m < d->M; ++m) {
-    const size_t Te = d->Te[m], E = d->E[m];
-    SE += E;
-    s.valuesT[m] = take(N * Te * E); s.keysB[m] = take(B * Te * U); s.keysT[m] = take(N * Te * U); s.lenT[m] = take(N);
-    s.part[m] = take(multi_attn_part_floats((int)N, (int)Te, (int)E, (int)U, d->kind, d->K, d->F, d->prob_fn));
-    s.hist_align[m] = take(S * N * Te);
-    for (int k = 0; k < 3; ++k) s.align[k][m] = take(N * Te);
-    mx(nabu_gemm_ws_bytes((int)(B * Te), (int)U, (int)E));
-  }
-  s.SE = (int)SE; s.MU = (int)(M * U);
-  s.big = take(N); s.z = take(N * 4 * U); s.q = take(N * M * U); s.wqcat = take(U * M * U); s.logits = take(N * C);
-  s.acts = take(N * 4 * U > N * M ? N * 4 * U : N * M);
-  s.ids = take(N); s.logprobs = take(N); s.lengths = take(N); s.finished = take(N); s.seen = take(N);
-  s.parent = take(N); s.stay = take(N); s.all_seen = take(B); s.scratch = take(B * (W * C + W));
-  s.tickets = take(M * N);
-  s.hist_pred = take(S * N); s.hist_parent = take(S * N); s.src = take(N * S);
-  for (int k = 0; k < 3; ++k) {
-    for (int n = 0; n < d->num_layers; ++n) { s.h[k][n] = take(N * U); s.c[k][n] = take(N * U); }
-    s.ctx[k] = take(N * SE);
-  }
-  mx(nabu_gemm_ws_bytes((int)N, (int)(4 * U), (int)SE)); mx(nabu_gemm_ws_bytes((int)N, (int)(4 * U), (int)U));
-  mx(nabu_gemm_ws_bytes((int)N, (int)(M * U), (int)U)); mx(nabu_gemm_ws_bytes((int)N, (int)C, (int)U));
-  mx(nabu_gemm_ws_bytes((int)N, (int)C, (int)SE));
-  s.gemm_bytes = (g + 255) / 256 * 256;
-  s.gemm = take(s.gemm_bytes / 4 + 4);
-  s.total = o;
-  return s;
-}
-__global__ __launch_bounds__(DT) void put_cols_dec_kernel(int R, int Cn, const float *__restrict__ src, float *__restrict__ dst,
-                                                          int ldd, int c0) {
-  const int i = blockIdx.x * DT + threadIdx.x;
-  if (i < R * Cn) dst[(size_t)(i / Cn) * ldd + c0 + i % Cn] = src[i];
-}
-}  // namespace nabu
 
 extern "C" size_t nabu_speller_multi_beam_ws_bytes(const nabu_multi_beam_desc *d) {
-  if (check_mbeam(d)) return 0;
-  return mbeam_ws(d).total * 4;
+  BeamGeo g;
+  return beam_geo(d, &g) ? 0 : beam_ws(g).total * 4;
 }
 
 extern "C" int nabu_speller_multi_beam_search(const nabu_multi_beam_desc *d, const float *const *values,
@@ -860,119 +869,19 @@ extern "C" int nabu_speller_multi_beam_search(const nabu_multi_beam_desc *d, con
                                               int32_t *sequences, int32_t *lengths, float *scores,
                                               float *const *alignments, int32_t *num_steps, void *ws, size_t ws_bytes,
                                               nabu_stream_t stream) {
-  if (int e = check_mbeam(d)) return e;
-  NABU_CHECK_ARG(values && enc_len && p && sequences && lengths && scores && num_steps && ws, "speller_multi_beam_search: null pointer");
-  for (int m = 0; m < d->M; ++m)
-    NABU_CHECK_ARG(values[m] && enc_len[m] && p->memory_kernel[m] && p->query_kernel[m] && p->attention_v[m] &&
-                   (d->kind != 1 || (p->conv_kernel[m] && p->conv_proj[m])) && (!alignments || alignments[m]),
-                   "speller_multi_beam_search: null pointer for an encoded input");
-  const MBeamWs L = mbeam_ws(d);
-  if (ws_bytes < L.total * 4) return fail(NABU_EWS, "speller_multi_beam_search: workspace too small");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  float *w = static_cast<float *>(ws);
-  int32_t *wi = static_cast<int32_t *>(ws);
-  const int B = d->B, W = d->beam_width, N = B * W, U = d->U, C = d->C, nl = d->num_layers, S = d->max_steps, M = d->M,
-            SE = L.SE, MU = L.MU;
-  float *gw = w + L.gemm;
-  const size_t gwb = L.gemm_bytes;
-  auto tile = [&](const void *src, void *dst, size_t F) {
-    size_t gy = (F + DT * 4 - 1) / (DT * 4);
-    hipLaunchKernelGGL(tile_rows_kernel, dim3(N, gy > 64 ? 64 : (unsigned)gy), dim3(DT), 0, s, W, F,
-                       static_cast<const uint32_t *>(src), static_cast<uint32_t *>(dst));
-  };
-  int cur = 0, fresh = 1, nxt = 2;
-  for (int m = 0; m < M; ++m) {
-    const int Te = d->Te[m], E = d->E[m];
-    DEC_TRY(bmm(B * Te, U, E, values[m], E, p->memory_kernel[m], U, 0.f, w + L.keysB[m], U, nullptr, gw, gwb, stream));
-    tile(values[m], w + L.valuesT[m], (size_t)Te * E);
-    tile(w + L.keysB[m], w + L.keysT[m], (size_t)Te * U);
-    tile(enc_len[m], wi + L.lenT[m], 1);
-    hipLaunchKernelGGL(put_cols_dec_kernel, dim3((U * U + DT - 1) / DT), dim3(DT), 0, s, U, U, p->query_kernel[m], w + L.wqcat, MU, m * U);
-    NABU_LAUNCH_CHECK();
-    NABU_HIP(hipMemsetAsync(w + L.align[cur][m], 0, (size_t)N * Te * 4, s));
-    if (d->kind == 2) DEC_TRY(first_col_one(N, Te, w + L.align[cur][m], s));
+  BeamGeo g;
+  if (int e = beam_geo(d, &g)) return e;
+  NABU_CHECK_ARG(values && enc_len && p, "speller_multi_beam_search: null pointer");
+  BeamIO io = {{}, {}, {}, {}, {}, {}, {}, p->out_kernel, p->out_bias, p->lstm_kernel, p->lstm_bias, {},
+               sequences, lengths, num_steps, scores};
+  for (int m = 0; m < g.M; ++m) {
+    io.values[m] = values[m]; io.enc_len[m] = enc_len[m];
+    io.memory_kernel[m] = p->memory_kernel[m]; io.query_kernel[m] = p->query_kernel[m];
+    io.attention_v[m] = p->attention_v[m]; io.conv_kernel[m] = p->conv_kernel[m]; io.conv_proj[m] = p->conv_proj[m];
+    if (alignments) {
+      NABU_CHECK_ARG(alignments[m], "speller_multi_beam_search: null pointer for an encoded input");
+      io.alignments[m] = alignments[m];
+    }
   }
-  const int gN = (N + DT - 1) / DT;
-  hipLaunchKernelGGL(fill_i32_kernel, dim3(gN), dim3(DT), 0, s, (size_t)N, INT_MAX, wi + L.big);
-  hipLaunchKernelGGL(fill_i32_kernel, dim3(gN), dim3(DT), 0, s, (size_t)N, C - 1, wi + L.ids);
-  hipLaunchKernelGGL(beam_init_kernel, dim3(gN), dim3(DT), 0, s, N, W, w + L.logprobs);
-  NABU_LAUNCH_CHECK();
-  NABU_HIP(hipMemsetAsync(wi + L.lengths, 0, (size_t)N * 4, s));
-  NABU_HIP(hipMemsetAsync(wi + L.finished, 0, (size_t)N * 4, s));
-  NABU_HIP(hipMemsetAsync(wi + L.seen, 0, (size_t)N * 4, s));
-  NABU_HIP(hipMemsetAsync(wi + L.tickets, 0, (size_t)M * N * 4, s));
-  for (int n = 0; n < nl; ++n) {
-    NABU_HIP(hipMemsetAsync(w + L.h[cur][n], 0, (size_t)N * U * 4, s));
-    NABU_HIP(hipMemsetAsync(w + L.c[cur][n], 0, (size_t)N * U * 4, s));
-  }
-  NABU_HIP(hipMemsetAsync(w + L.ctx[cur], 0, (size_t)N * SE * 4, s));
-  float *z = w + L.z, *lg = w + L.logits;
-  const int32_t *big = wi + L.big;
-  int32_t *par = wi + L.parent, *stay = wi + L.stay;
-  std::vector<int32_t> done(B);
-  int Tn = 0;
-  for (int t = 0; t < S; ++t) {
-    for (int n = 0; n < nl; ++n) {
-      const float *Kn = p->lstm_kernel[n];
-      if (n == 0) {
-        DEC_TRY(bmm(N, 4 * U, SE, w + L.ctx[cur], SE, Kn + (size_t)C * 4 * U, 4 * U, 0.f, z, 4 * U, nullptr, gw, gwb, stream));
-        DEC_TRY(bmm(N, 4 * U, U, w + L.h[cur][0], U, Kn + (size_t)(C + SE) * 4 * U, 4 * U, 1.f, z, 4 * U, nullptr, gw, gwb, stream));
-        DEC_TRY(nabu_lstm_cell_fwd(N, U, 0, big, z, p->lstm_bias[0], Kn, wi + L.ids, w + L.c[cur][0], w + L.h[cur][0],
-                                   w + L.acts, w + L.c[fresh][0], w + L.h[fresh][0], stream));
-      } else {
-        DEC_TRY(bmm(N, 4 * U, U, w + L.h[fresh][n - 1], U, Kn, 4 * U, 0.f, z, 4 * U, nullptr, gw, gwb, stream));
-        DEC_TRY(bmm(N, 4 * U, U, w + L.h[cur][n], U, Kn + (size_t)U * 4 * U, 4 * U, 1.f, z, 4 * U, nullptr, gw, gwb, stream));
-        DEC_TRY(nabu_lstm_cell_fwd(N, U, 0, big, z, p->lstm_bias[n], nullptr, nullptr, w + L.c[cur][n], w + L.h[cur][n],
-                                   w + L.acts, w + L.c[fresh][n], w + L.h[fresh][n], stream));
-      }
-    }
-    const float *htop = w + L.h[fresh][nl - 1];
-    DEC_TRY(bmm(N, MU, U, htop, U, w + L.wqcat, MU, 0.f, w + L.q, MU, nullptr, gw, gwb, stream));
-    MultiAttnMem mem[NABU_SPELLER_MAX_MEMORIES];
-    for (int m = 0; m < M; ++m) {
-      mem[m] = MultiAttnMem{d->Te[m], d->E[m], wi + L.lenT[m], w + L.keysT[m], w + L.valuesT[m], p->attention_v[m],
-                            p->conv_kernel[m], p->conv_proj[m], w + L.align[cur][m], w + L.align[fresh][m],
-                            w + L.acts + (size_t)m * N /* normaliser scratch */, w + L.part[m],
-                            reinterpret_cast<unsigned *>(wi + L.tickets) + (size_t)m * N};
-    }
-    DEC_TRY(multi_attn_fwd(M, N, U, d->kind, d->K, d->F, d->prob_fn, 0, big, w + L.q, w + L.ctx[cur], w + L.ctx[fresh], mem, s));
-    DEC_TRY(bmm(N, C, U, htop, U, p->out_kernel, C, 0.f, lg, C, p->out_bias, gw, gwb, stream));
-    DEC_TRY(bmm(N, C, SE, w + L.ctx[fresh], SE, p->out_kernel + (size_t)U * C, C, 1.f, lg, C, nullptr, gw, gwb, stream));
-    DEC_TRY(nabu_beam_prune(B, W, C, lg, d->temperature, d->length_penalty, w + L.logprobs, wi + L.lengths,
-                            wi + L.finished, wi + L.seen, wi + L.ids, par, stay, wi + L.all_seen, w + L.scratch, stream));
-    for (int n = 0; n < nl; ++n) {
-      DEC_TRY(nabu_beam_gather(B, W, U, w + L.h[fresh][n], w + L.h[cur][n], par, stay, w + L.h[nxt][n], stream));
-      DEC_TRY(nabu_beam_gather(B, W, U, w + L.c[fresh][n], w + L.c[cur][n], par, stay, w + L.c[nxt][n], stream));
-    }
-    DEC_TRY(nabu_beam_gather(B, W, SE, w + L.ctx[fresh], w + L.ctx[cur], par, stay, w + L.ctx[nxt], stream));
-    for (int m = 0; m < M; ++m) {
-      const int Te = d->Te[m];
-      DEC_TRY(nabu_beam_gather(B, W, Te, w + L.align[fresh][m], w + L.align[cur][m], par, stay, w + L.align[nxt][m], stream));
-      NABU_HIP(hipMemcpyAsync(w + L.hist_align[m] + (size_t)t * N * Te, w + L.align[nxt][m], (size_t)N * Te * 4,
-                              hipMemcpyDeviceToDevice, s));
-    }
-    NABU_HIP(hipMemcpyAsync(wi + L.hist_pred + (size_t)t * N, wi + L.ids, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
-    NABU_HIP(hipMemcpyAsync(wi + L.hist_parent + (size_t)t * N, par, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
-    const int tmp = cur; cur = nxt; nxt = tmp;
-    Tn = t + 1;
-    NABU_HIP(hipMemcpyAsync(done.data(), wi + L.all_seen, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    NABU_HIP(hipStreamSynchronize(s));
-    bool all = true;
-    for (int b = 0; b < B; ++b) all = all && done[b] != 0;
-    if (all) break;
-  }
-  hipLaunchKernelGGL(beam_backtrace_kernel, dim3(gN), dim3(DT), 0, s, N, W, Tn, S, wi + L.hist_pred, wi + L.hist_parent,
-                     sequences, wi + L.src);
-  NABU_LAUNCH_CHECK();
-  if (alignments)
-    for (int m = 0; m < M; ++m) {
-      hipLaunchKernelGGL(beam_align_kernel, dim3(N, S), dim3(DT), 0, s, N, W, Tn, S, d->Te[m], w + L.hist_align[m], wi + L.src,
-                         alignments[m]);
-      NABU_LAUNCH_CHECK();
-    }
-  hipLaunchKernelGGL(beam_scores_kernel, dim3(gN), dim3(DT), 0, s, N, d->length_penalty, w + L.logprobs, wi + L.lengths,
-                     scores, lengths);
-  NABU_LAUNCH_CHECK();
-  *num_steps = Tn;
-  return 0;
+  return beam_run(g, io, ws, ws_bytes, stream);
 }

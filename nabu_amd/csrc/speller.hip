@@ -2239,13 +2239,6 @@ static int check_sp(const nabu_speller_desc *d) {
   return check_attn(&a);
 }
 
-// C = A·B (+ beta*C) on row-major contiguous operands
-static int mm(bool ta, bool tb, int M, int N, int K, const float *A, int lda, const float *Bm, int ldb,
-              float beta, float *C, int ldc, const float *bias, float *ws, size_t wsb, nabu_stream_t st) {
-  return nabu_gemm_f32(ta, tb, M, N, K, 1.f, A, lda, Bm, ldb, beta, C, ldc, bias, 0, 0, 0, ws, wsb, st);
-}
-#define SP_TRY(call) do { int e_ = (call); if (e_) return e_; } while (0)
-
 // C[M,N] = A·B + A2·B2 (+ beta*C): ONE launch with the split-K reduction inside it when the shape
 // allows (gemm_skinny.hip), else two plain products
 static bool fused_ok(int M, int N, int K1, int lda, int K2, int lda2) {
@@ -2345,13 +2338,13 @@ extern "C" int nabu_speller_fwd(const nabu_speller_desc *d, const float *values,
   }
   NABU_HIP(hipMemsetAsync(r + R.ctx, 0, (size_t)B * E * 4, s));
   NABU_HIP(hipMemsetAsync(r + R.align, 0, (size_t)B * Te * 4, s));
-  if (d->kind == 2) SP_TRY(first_col_one(B, Te, r + R.align, s));
+  if (d->kind == 2) NABU_TRY(first_col_one(B, Te, r + R.align, s));
   // decoder inputs actually used (scheduled sampling replaces entries of rows 1..L-1 below)
   int32_t *ids_used = reinterpret_cast<int32_t *>(r + R.ids);
   NABU_HIP(hipMemcpyAsync(ids_used, ids, (size_t)L * B * 4, hipMemcpyDeviceToDevice, s));
   const bool sampling = d->sample_prob > 0.f;
   // keys = memory_layer(values)
-  SP_TRY(mm(false, false, B * Te, U, E, values, E, p->memory_kernel, U, 0.f, r + R.keys, U, nullptr, gw, gwb, stream));
+  NABU_TRY(mm(false, false, B * Te, U, E, values, E, p->memory_kernel, U, 0.f, r + R.keys, U, nullptr, gw, gwb, stream));
   const int NS = W.NS, Bn = B / NS;
   const nabu_attn_desc adn = sub_attn_desc(d, Bn);
   const size_t attn_fwd_wsb_n = nabu_attn_fwd_ws_bytes(&adn);
@@ -2380,7 +2373,7 @@ extern "C" int nabu_speller_fwd(const nabu_speller_desc *d, const float *values,
   pd.sample_draws = d->sample_prob > 0.f ? reinterpret_cast<unsigned *>(r + R.sdraw) : nullptr;
   const bool persist = fwd_takes_persistent(d, W);
   if (persist)
-    SP_TRY(speller_persist_fwd(pd, dec_len, enc_len, ids_used, w + W.kperm[0], p->lstm_bias[0], p->lstm_kernel[0],
+    NABU_TRY(speller_persist_fwd(pd, dec_len, enc_len, ids_used, w + W.kperm[0], p->lstm_bias[0], p->lstm_kernel[0],
                                p->query_kernel, p->attention_v, r + R.keys, values, p->conv_kernel, p->conv_proj, r + R.H[0],
                                drop ? r + R.Ho[0] : nullptr, r + R.Cs[0], r + R.acts[0], r + R.q, r + R.ctx, r + R.align,
                                reinterpret_cast<int *>(w + W.status), w + W.persist, W.persist_bytes, s, p->out_kernel,
@@ -2392,12 +2385,12 @@ extern "C" int nabu_speller_fwd(const nabu_speller_desc *d, const float *values,
   const bool r16 = !persist && nl == 1 && cell_epi[0] && env_int("NABU_SPELLER_ROWS16", 1) && E % 16 == 0 &&
                    rows16_ok(Bn, 4 * U, E + U, E) && rows16_ok(Bn, U, U, U);
   if (r16) {
-    SP_TRY(rows16_swizzle_kn(4 * U, E + U, p->lstm_kernel[0] + (size_t)C * 4 * U, 4 * U, w + W.kxh_sw, U, s));
-    SP_TRY(rows16_swizzle_kn(U, U, p->query_kernel, U, w + W.wq_sw, 0, s));
+    NABU_TRY(rows16_swizzle_kn(4 * U, E + U, p->lstm_kernel[0] + (size_t)C * 4 * U, 4 * U, w + W.kxh_sw, U, s));
+    NABU_TRY(rows16_swizzle_kn(U, U, p->query_kernel, U, w + W.wq_sw, 0, s));
   }
   if (!persist) {
-  SP_TRY(sub_streams(NS, s, &ss));
-  SP_TRY(sub_fork(ss));
+  NABU_TRY(sub_streams(NS, s, &ss));
+  NABU_TRY(sub_fork(ss));
   }
   auto fwd_chain = [&](int sub) -> int {
     for (int t = 0; t < L; ++t) {
@@ -2428,33 +2421,33 @@ extern "C" int nabu_speller_fwd(const nabu_speller_desc *d, const float *values,
               ep.keep = d->keep_prob; ep.seed = d->seed; ep.seed_offset = d->seed_offset + (unsigned long long)t * nl + n;
               ep.row0 = b0;
             }
-            SP_TRY(rows16(Bn, 4 * U, E + U, x1, E, w + W.kxh_sw, 0.f, nullptr, 0, ss.st[sub], &ep, nullptr, E, Hn + cur, U));
+            NABU_TRY(rows16(Bn, 4 * U, E + U, x1, E, w + W.kxh_sw, 0.f, nullptr, 0, ss.st[sub], &ep, nullptr, E, Hn + cur, U));
           } else
-          SP_TRY(gemm_skinny_fused(Bn, 4 * U, K1, x1, K1, Kp, 4 * U, U, Hn + cur, U, Kp + (size_t)K1 * 4 * U, 4 * U, 0.f, z,
+          NABU_TRY(gemm_skinny_fused(Bn, 4 * U, K1, x1, K1, Kp, 4 * U, U, Hn + cur, U, Kp + (size_t)K1 * 4 * U, 4 * U, 0.f, z,
                                    4 * U, nullptr, w + W.fpart + (size_t)sub * W.fpart_each,
                                    reinterpret_cast<unsigned *>(w + W.tickets) + (size_t)sub * 1024, ss.st[sub], &ep));
         } else if (n == 0) {
-          SP_TRY(mm2(Bn, 4 * U, E, r + R.ctx + (size_t)t * B * E + (size_t)b0 * E, E, Kn + (size_t)C * 4 * U, 4 * U, U,
+          NABU_TRY(mm2(Bn, 4 * U, E, r + R.ctx + (size_t)t * B * E + (size_t)b0 * E, E, Kn + (size_t)C * 4 * U, 4 * U, U,
                      Hn + cur, U, Kn + (size_t)(C + E) * 4 * U, 4 * U, 0.f, z, 4 * U, w, W, sub, gws, gwb, st));
-          SP_TRY(nabu_lstm_cell_fwd(Bn, U, t, dlen, z, p->lstm_bias[0], Kn, ids_used + (size_t)t * B + b0, Cn + cur,
+          NABU_TRY(nabu_lstm_cell_fwd(Bn, U, t, dlen, z, p->lstm_bias[0], Kn, ids_used + (size_t)t * B + b0, Cn + cur,
                                     Hn + cur, r + R.acts[0] + (size_t)t * B * 4 * U + (size_t)b0 * 4 * U, Cn + nxt,
                                     Hn + nxt, st));
         } else {
-          SP_TRY(mm2(Bn, 4 * U, U, r + R.Ho[n - 1] + nxt + (size_t)b0 * U, U, Kn, 4 * U, U, Hn + cur, U,
+          NABU_TRY(mm2(Bn, 4 * U, U, r + R.Ho[n - 1] + nxt + (size_t)b0 * U, U, Kn, 4 * U, U, Hn + cur, U,
                      Kn + (size_t)U * 4 * U, 4 * U, 0.f, z, 4 * U, w, W, sub, gws, gwb, st));
-          SP_TRY(nabu_lstm_cell_fwd(Bn, U, t, dlen, z, p->lstm_bias[n], nullptr, nullptr, Cn + cur, Hn + cur,
+          NABU_TRY(nabu_lstm_cell_fwd(Bn, U, t, dlen, z, p->lstm_bias[n], nullptr, nullptr, Cn + cur, Hn + cur,
                                     r + R.acts[n] + (size_t)t * B * 4 * U + (size_t)b0 * 4 * U, Cn + nxt, Hn + nxt, st));
         }
         if (drop && !(r16 && cell_epi[n]))
-          SP_TRY(dropout_rows((size_t)Bn * U, Hn + nxt, r + R.Ho[n] + nxt + (size_t)b0 * U, d->keep_prob, d->seed,
+          NABU_TRY(dropout_rows((size_t)Bn * U, Hn + nxt, r + R.Ho[n] + nxt + (size_t)b0 * U, d->keep_prob, d->seed,
                               d->seed_offset + (unsigned long long)t * nl + n, (size_t)b0 * U, ss.st[sub]));
       }
       const float *htop = r + R.Ho[nl - 1] + (size_t)(t + 1) * B * U + (size_t)b0 * U;
       float *qt = r + R.q + (size_t)t * B * U + (size_t)b0 * U;
-      if (r16) SP_TRY(rows16(Bn, U, U, htop, U, w + W.wq_sw, 0.f, qt, U, ss.st[sub]));
+      if (r16) NABU_TRY(rows16(Bn, U, U, htop, U, w + W.wq_sw, 0.f, qt, U, ss.st[sub]));
       else
-      SP_TRY(mm2(Bn, U, U, htop, U, p->query_kernel, U, 0, nullptr, 0, nullptr, 0, 0.f, qt, U, w, W, sub, gws, gwb, st));
-      SP_TRY(attn_fwd_impl(&adn, t, dlen, enc_len + b0, r + R.keys + (size_t)b0 * Te * U, values + (size_t)b0 * Te * E, qt,
+      NABU_TRY(mm2(Bn, U, U, htop, U, p->query_kernel, U, 0, nullptr, 0, nullptr, 0, 0.f, qt, U, w, W, sub, gws, gwb, st));
+      NABU_TRY(attn_fwd_impl(&adn, t, dlen, enc_len + b0, r + R.keys + (size_t)b0 * Te * U, values + (size_t)b0 * Te * E, qt,
                            p->attention_v, p->conv_kernel, p->conv_proj,
                            r + R.align + (size_t)t * B * Te + (size_t)b0 * Te, r + R.ctx + (size_t)t * B * E + (size_t)b0 * E,
                            r + R.align + (size_t)(t + 1) * B * Te + (size_t)b0 * Te,
@@ -2464,15 +2457,15 @@ extern "C" int nabu_speller_fwd(const nabu_speller_desc *d, const float *values,
         // ScheduledEmbeddingTrainingHelper: the step's logits decide the next input of selected rows
         float *lt = r + R.logits_tm + (size_t)t * B * C + (size_t)b0 * C;
         if (sample_step_ok(C)) {     // one launch, logits only for sampled rows
-          SP_TRY(sample_step(Bn, C, U, E, htop, U, r + R.ctx + (size_t)(t + 1) * B * E + (size_t)b0 * E, E, p->out_kernel,
+          NABU_TRY(sample_step(Bn, C, U, E, htop, U, r + R.ctx + (size_t)(t + 1) * B * E + (size_t)b0 * E, E, p->out_kernel,
                              p->out_bias, d->sample_prob, d->sample_seed, d->sample_offset + (unsigned long long)t,
                              ids + (size_t)(t + 1) * B + b0, ids_used + (size_t)(t + 1) * B + b0, b0, ss.st[sub]));
           continue;
         }
-        SP_TRY(mm(false, false, Bn, C, U, htop, U, p->out_kernel, C, 0.f, lt, C, p->out_bias, gws, gwb, st));
-        SP_TRY(mm(false, false, Bn, C, E, r + R.ctx + (size_t)(t + 1) * B * E + (size_t)b0 * E, E,
+        NABU_TRY(mm(false, false, Bn, C, U, htop, U, p->out_kernel, C, 0.f, lt, C, p->out_bias, gws, gwb, st));
+        NABU_TRY(mm(false, false, Bn, C, E, r + R.ctx + (size_t)(t + 1) * B * E + (size_t)b0 * E, E,
                   p->out_kernel + (size_t)U * C, C, 1.f, lt, C, nullptr, gws, gwb, st));
-        SP_TRY(sample_ids_rows(Bn, C, lt, d->sample_prob, d->sample_seed, d->sample_offset + (unsigned long long)t,
+        NABU_TRY(sample_ids_rows(Bn, C, lt, d->sample_prob, d->sample_seed, d->sample_offset + (unsigned long long)t,
                                ids + (size_t)(t + 1) * B + b0, ids_used + (size_t)(t + 1) * B + b0, b0, ss.st[sub]));
       }
     }
@@ -2482,15 +2475,15 @@ extern "C" int nabu_speller_fwd(const nabu_speller_desc *d, const float *values,
   {  // join the side streams before an error is propagated: chains already enqueued must not outlive the call
     const int e_run = run_subs(NS, fwd_chain), e_join = sub_join(ss);
     if (e_run) return e_run;
-    SP_TRY(e_join);
+    NABU_TRY(e_join);
   }
   }
   // output projection of all steps: [h_t, ctx_t]·W + b, then batch-major + impute_finished
   float *ltm = r + R.logits_tm;
-  SP_TRY(mm(false, false, L * B, C, U, r + R.Ho[nl - 1] + (size_t)B * U, U, p->out_kernel, C, 0.f, ltm, C, p->out_bias, gw, gwb, stream));
-  SP_TRY(mm(false, false, L * B, C, E, r + R.ctx + (size_t)B * E, E, p->out_kernel + (size_t)U * C, C, 1.f, ltm, C, nullptr, gw, gwb, stream));
-  SP_TRY(nabu_swap01_f32(L, B, C, ltm, logits, stream));
-  SP_TRY(nabu_mask_time_f32(B, L, C, logits, dec_len, stream));
+  NABU_TRY(mm(false, false, L * B, C, U, r + R.Ho[nl - 1] + (size_t)B * U, U, p->out_kernel, C, 0.f, ltm, C, p->out_bias, gw, gwb, stream));
+  NABU_TRY(mm(false, false, L * B, C, E, r + R.ctx + (size_t)B * E, E, p->out_kernel + (size_t)U * C, C, 1.f, ltm, C, nullptr, gw, gwb, stream));
+  NABU_TRY(nabu_swap01_f32(L, B, C, ltm, logits, stream));
+  NABU_TRY(nabu_mask_time_f32(B, L, C, logits, dec_len, stream));
   (void)s;
   return 0;
 }
@@ -2516,12 +2509,12 @@ extern "C" int nabu_speller_bwd(const nabu_speller_desc *d, const float *values,
   const float *htop_all = r + R.Ho[nl - 1] + (size_t)B * U;   // h_top[t], t = 0..L-1
   const float *ctx1 = r + R.ctx + (size_t)B * E;              // ctx[t]
   // output projection
-  SP_TRY(nabu_swap01_f32(B, L, C, dlogits, dl, stream));      // [B,L,C] -> [L,B,C]
-  SP_TRY(mm(true, false, U, C, BL, htop_all, U, dl, C, 0.f, g->out_kernel, C, nullptr, gw, gwb, stream));
-  SP_TRY(mm(true, false, E, C, BL, ctx1, E, dl, C, 0.f, g->out_kernel + (size_t)U * C, C, nullptr, gw, gwb, stream));
-  SP_TRY(nabu_colsum_f32(BL, C, dl, C, 0.f, g->out_bias, gw, gwb, stream));
-  SP_TRY(mm(false, true, BL, U, C, dl, C, p->out_kernel, C, 0.f, dH, U, nullptr, gw, gwb, stream));
-  SP_TRY(mm(false, true, BL, E, C, dl, C, p->out_kernel + (size_t)U * C, C, 0.f, dCtx, E, nullptr, gw, gwb, stream));
+  NABU_TRY(nabu_swap01_f32(B, L, C, dlogits, dl, stream));      // [B,L,C] -> [L,B,C]
+  NABU_TRY(mm(true, false, U, C, BL, htop_all, U, dl, C, 0.f, g->out_kernel, C, nullptr, gw, gwb, stream));
+  NABU_TRY(mm(true, false, E, C, BL, ctx1, E, dl, C, 0.f, g->out_kernel + (size_t)U * C, C, nullptr, gw, gwb, stream));
+  NABU_TRY(nabu_colsum_f32(BL, C, dl, C, 0.f, g->out_bias, gw, gwb, stream));
+  NABU_TRY(mm(false, true, BL, U, C, dl, C, p->out_kernel, C, 0.f, dH, U, nullptr, gw, gwb, stream));
+  NABU_TRY(mm(false, true, BL, E, C, dl, C, p->out_kernel + (size_t)U * C, C, 0.f, dCtx, E, nullptr, gw, gwb, stream));
   NABU_HIP(hipMemsetAsync(dkeys, 0, (size_t)B * Te * U * 4, s));
   NABU_HIP(hipMemsetAsync(w + W.tickets, 0, ((size_t)W.NS * 1024 + B + 4) * 4, s));
   const int S = W.S;          // per-slice partial rows of the attention backward (slices of a sub-batch's utterances)
@@ -2536,15 +2529,15 @@ extern "C" int nabu_speller_bwd(const nabu_speller_desc *d, const float *values,
   }
   // transposed copies of the weights the per-step gradient products use: dz·W^T becomes a
   // row-major product with M = B rows, which the skinny GEMM kernel streams in a few microseconds
-  SP_TRY(transpose(U, U, p->query_kernel, U, w + W.wqT, s));
+  NABU_TRY(transpose(U, U, p->query_kernel, U, w + W.wqT, s));
   for (int n = 0; n < nl; ++n) {
     const float *Kn = p->lstm_kernel[n];
     if (n == 0) {
-      SP_TRY(transpose(E, 4 * U, Kn + (size_t)C * 4 * U, 4 * U, w + W.kxT[0], s));
-      SP_TRY(transpose(U, 4 * U, Kn + (size_t)(C + E) * 4 * U, 4 * U, w + W.khT[0], s));
+      NABU_TRY(transpose(E, 4 * U, Kn + (size_t)C * 4 * U, 4 * U, w + W.kxT[0], s));
+      NABU_TRY(transpose(U, 4 * U, Kn + (size_t)(C + E) * 4 * U, 4 * U, w + W.khT[0], s));
     } else {
-      SP_TRY(transpose(U, 4 * U, Kn, 4 * U, w + W.kxT[n], s));
-      SP_TRY(transpose(U, 4 * U, Kn + (size_t)U * 4 * U, 4 * U, w + W.khT[n], s));
+      NABU_TRY(transpose(U, 4 * U, Kn, 4 * U, w + W.kxT[n], s));
+      NABU_TRY(transpose(U, 4 * U, Kn + (size_t)U * 4 * U, 4 * U, w + W.khT[n], s));
     }
   }
   const int NS = W.NS, Bn = B / NS;
@@ -2569,21 +2562,21 @@ extern "C" int nabu_speller_bwd(const nabu_speller_desc *d, const float *values,
   const bool r16 = fuse_shapes && !persist && E % 32 == 0 && env_int("NABU_SPELLER_SPLIT", 1) && env_int("NABU_SPELLER_ROWS16", 1) &&
                    rows16_ok(Bn, U, U, U) && rows16_ok(Bn, E + U, 4 * U, 4 * U);
   const bool fuse_b = fuse_shapes && (!drop || persist || r16);      // (gemm_skinny_fused's cell epilogue has no dropout)
-  if (fuse_b) SP_TRY(transpose(E + U, 4 * U, p->lstm_kernel[0] + (size_t)C * 4 * U, 4 * U, w + W.kxhT, s));
+  if (fuse_b) NABU_TRY(transpose(E + U, 4 * U, p->lstm_kernel[0] + (size_t)C * 4 * U, 4 * U, w + W.kxhT, s));
   const bool split_b = fuse_b && E % 32 == 0 && env_int("NABU_SPELLER_SPLIT", 1);
   if (r16) {
-    SP_TRY(rows16_swizzle(U, U, p->query_kernel, U, w + W.wq_sw, s));
-    SP_TRY(rows16_swizzle(E + U, 4 * U, p->lstm_kernel[0] + (size_t)C * 4 * U, 4 * U, w + W.kxh_sw, s));
+    NABU_TRY(rows16_swizzle(U, U, p->query_kernel, U, w + W.wq_sw, s));
+    NABU_TRY(rows16_swizzle(E + U, 4 * U, p->lstm_kernel[0] + (size_t)C * 4 * U, 4 * U, w + W.kxh_sw, s));
   }
   if (persist)
-    SP_TRY(speller_persist_bwd(pd, dec_len, enc_len, w + W.kxhT, p->query_kernel, p->attention_v, r + R.keys, values,
+    NABU_TRY(speller_persist_bwd(pd, dec_len, enc_len, w + W.kxhT, p->query_kernel, p->attention_v, r + R.keys, values,
                                r + R.acts[0], r + R.Cs[0], r + R.q, r + R.ctx, r + R.align, dH, dCtx, dq, w + W.dz[0],
                                dkeys, w + W.dv8, reinterpret_cast<int *>(w + W.status), w + W.persist, W.persist_bytes, s,
                                p->conv_kernel, p->conv_proj, w + W.ds_all, d->kind == 1 ? w + W.cf_all : nullptr,
                                d->kind == 1 ? w + W.dck8 : nullptr));
   if (!persist) {
-    SP_TRY(sub_streams(NS, s, &ss));
-    SP_TRY(sub_fork(ss));
+    NABU_TRY(sub_streams(NS, s, &ss));
+    NABU_TRY(sub_fork(ss));
   }
   // d keys / d attention_v / d conv_proj of all steps in ONE launch after the chain (attn_param_grads_kernel)
   nabu_attn_desc adb = adn;      // the whole batch
@@ -2608,12 +2601,12 @@ extern "C" int nabu_speller_bwd(const nabu_speller_desc *d, const float *values,
                            w + W.dxh[(t + 1) & 1] + (size_t)b0 * (E + U), E + U, dCt, E);
         NABU_LAUNCH_CHECK();
       } else if (have_carry && !fuse_b) {
-        SP_TRY(nabu_axpy_f32((size_t)Bn * E, 1.f, w + W.dctx[(t + 1) & 1] + (size_t)b0 * E, dCt, st));
+        NABU_TRY(nabu_axpy_f32((size_t)Bn * E, 1.f, w + W.dctx[(t + 1) & 1] + (size_t)b0 * E, dCt, st));
       }
       float *dal_out = d->kind == 1 ? w + W.dal[t & 1] + (size_t)b0 * Te : nullptr;
       const float *dal_carry = (d->kind == 1 && have_carry) ? w + W.dal[(t + 1) & 1] + (size_t)b0 * Te : nullptr;
       float *dqt = dq + (size_t)t * B * U + (size_t)b0 * U;
-      SP_TRY(attn_bwd_impl(&adn, t, dlen, enc_len + b0, r + R.keys + (size_t)b0 * Te * U, values + (size_t)b0 * Te * E,
+      NABU_TRY(attn_bwd_impl(&adn, t, dlen, enc_len + b0, r + R.keys + (size_t)b0 * Te * U, values + (size_t)b0 * Te * E,
                            r + R.q + (size_t)t * B * U + (size_t)b0 * U, p->attention_v, p->conv_kernel, p->conv_proj,
                            r + R.align + (size_t)t * B * Te + (size_t)b0 * Te,
                            r + R.align + (size_t)(t + 1) * B * Te + (size_t)b0 * Te,
@@ -2644,57 +2637,57 @@ extern "C" int nabu_speller_bwd(const nabu_speller_desc *d, const float *values,
         float *fp = w + W.fpart + (size_t)sub * W.fpart_each;
         unsigned *tk = reinterpret_cast<unsigned *>(w + W.tickets) + (size_t)sub * 1024;
         if (r16) {
-          SP_TRY(rows16(Bn, U, U, dqt, U, w + W.wq_sw, 1.f, dHt, U, ss.st[sub], &ep));
+          NABU_TRY(rows16(Bn, U, U, dqt, U, w + W.wq_sw, 1.f, dHt, U, ss.st[sub], &ep));
           if (t > 0) {
             SkinnySplit sp = {w + W.dxh[t & 1] + (size_t)b0 * (E + U) + E, E + U, E, 0.f};
-            SP_TRY(rows16(Bn, E + U, 4 * U, dzt, 4 * U, w + W.kxh_sw, 1.f, dCtx + (size_t)(t - 1) * B * E + (size_t)b0 * E, E,
+            NABU_TRY(rows16(Bn, E + U, 4 * U, dzt, 4 * U, w + W.kxh_sw, 1.f, dCtx + (size_t)(t - 1) * B * E + (size_t)b0 * E, E,
                           ss.st[sub], nullptr, &sp));
           }
           have_carry = true;
           cur ^= 1;
           continue;
         }
-        SP_TRY(gemm_skinny_fused(Bn, U, U, dqt, U, w + W.wqT, U, 0, nullptr, 0, nullptr, 0, 1.f, dHt, U, nullptr, fp, tk,
+        NABU_TRY(gemm_skinny_fused(Bn, U, U, dqt, U, w + W.wqT, U, 0, nullptr, 0, nullptr, 0, 1.f, dHt, U, nullptr, fp, tk,
                                  ss.st[sub], &ep));
         if (split_b && t > 0) {
           // d context of step t-1 goes straight into that step's dCtx row block (on top of the output
           // projection's share), d h into the carry: no separate add launch in front of the next attention
           SkinnySplit sp = {w + W.dxh[t & 1] + (size_t)b0 * (E + U) + E, E + U, E, 0.f};
-          SP_TRY(gemm_skinny_fused(Bn, E + U, 4 * U, dzt, 4 * U, w + W.kxhT, E + U, 0, nullptr, 0, nullptr, 0, 1.f,
+          NABU_TRY(gemm_skinny_fused(Bn, E + U, 4 * U, dzt, 4 * U, w + W.kxhT, E + U, 0, nullptr, 0, nullptr, 0, 1.f,
                                    dCtx + (size_t)(t - 1) * B * E + (size_t)b0 * E, E, nullptr, fp, tk, ss.st[sub], nullptr,
                                    &sp));
         } else {
-          SP_TRY(gemm_skinny_fused(Bn, E + U, 4 * U, dzt, 4 * U, w + W.kxhT, E + U, 0, nullptr, 0, nullptr, 0, 0.f,
+          NABU_TRY(gemm_skinny_fused(Bn, E + U, 4 * U, dzt, 4 * U, w + W.kxhT, E + U, 0, nullptr, 0, nullptr, 0, 0.f,
                                    w + W.dxh[t & 1] + (size_t)b0 * (E + U), E + U, nullptr, fp, tk, ss.st[sub], nullptr));
         }
         have_carry = true;
         cur ^= 1;
         continue;
       }
-      SP_TRY(mm2(Bn, U, U, dqt, U, w + W.wqT, U, 0, nullptr, 0, nullptr, 0, 1.f, dHt, U, w, W, sub, gws, gwb, st));
+      NABU_TRY(mm2(Bn, U, U, dqt, U, w + W.wqT, U, 0, nullptr, 0, nullptr, 0, 1.f, dHt, U, w, W, sub, gws, gwb, st));
       const float *dtop = dHt;
       for (int n = nl - 1; n >= 0; --n) {
         const float *dh_in = dtop;
         if (drop) {
-          SP_TRY(dropout_rows((size_t)Bn * U, dtop, w + W.tmp + (size_t)b0 * U, d->keep_prob, d->seed,
+          NABU_TRY(dropout_rows((size_t)Bn * U, dtop, w + W.tmp + (size_t)b0 * U, d->keep_prob, d->seed,
                               d->seed_offset + (unsigned long long)t * nl + n, (size_t)b0 * U, ss.st[sub]));
           dh_in = w + W.tmp + (size_t)b0 * U;
         }
         float *dzt = w + W.dz[n] + (size_t)t * B * 4 * U + (size_t)b0 * 4 * U;
         const float *Cn = r + R.Cs[n] + (size_t)b0 * U;
-        SP_TRY(nabu_lstm_cell_bwd(Bn, U, t, dlen, r + R.acts[n] + (size_t)t * B * 4 * U + (size_t)b0 * 4 * U,
+        NABU_TRY(nabu_lstm_cell_bwd(Bn, U, t, dlen, r + R.acts[n] + (size_t)t * B * 4 * U + (size_t)b0 * 4 * U,
                                   Cn + (size_t)(t + 1) * B * U, Cn + (size_t)t * B * U, dh_in,
                                   w + W.dh[cur][n] + (size_t)b0 * U, w + W.dc[cur][n] + (size_t)b0 * U, dzt,
                                   w + W.dc[cur ^ 1][n] + (size_t)b0 * U, st));
         if (n == 0) {
           float *nx = w + W.dctx[t & 1] + (size_t)b0 * E;
-          SP_TRY(mm2(Bn, E, 4 * U, dzt, 4 * U, w + W.kxT[0], E, 0, nullptr, 0, nullptr, 0, 0.f, nx, E, w, W, sub, gws, gwb, st));
-          SP_TRY(mm2(Bn, U, 4 * U, dzt, 4 * U, w + W.khT[0], U, 0, nullptr, 0, nullptr, 0, 0.f,
+          NABU_TRY(mm2(Bn, E, 4 * U, dzt, 4 * U, w + W.kxT[0], E, 0, nullptr, 0, nullptr, 0, 0.f, nx, E, w, W, sub, gws, gwb, st));
+          NABU_TRY(mm2(Bn, U, 4 * U, dzt, 4 * U, w + W.khT[0], U, 0, nullptr, 0, nullptr, 0, 0.f,
                      w + W.dh[cur ^ 1][0] + (size_t)b0 * U, U, w, W, sub, gws, gwb, st));
         } else {
-          SP_TRY(mm2(Bn, U, 4 * U, dzt, 4 * U, w + W.kxT[n], U, 0, nullptr, 0, nullptr, 0, 0.f, w + W.dx + (size_t)b0 * U, U,
+          NABU_TRY(mm2(Bn, U, 4 * U, dzt, 4 * U, w + W.kxT[n], U, 0, nullptr, 0, nullptr, 0, 0.f, w + W.dx + (size_t)b0 * U, U,
                      w, W, sub, gws, gwb, st));
-          SP_TRY(mm2(Bn, U, 4 * U, dzt, 4 * U, w + W.khT[n], U, 0, nullptr, 0, nullptr, 0, 0.f,
+          NABU_TRY(mm2(Bn, U, 4 * U, dzt, 4 * U, w + W.khT[n], U, 0, nullptr, 0, nullptr, 0, 0.f,
                      w + W.dh[cur ^ 1][n] + (size_t)b0 * U, U, w, W, sub, gws, gwb, st));
           dtop = w + W.dx + (size_t)b0 * U;
         }
@@ -2709,41 +2702,41 @@ extern "C" int nabu_speller_bwd(const nabu_speller_desc *d, const float *values,
   {
     const int e_run = run_subs(NS, bwd_chain), e_join = sub_join(ss);
     if (e_run) return e_run;
-    SP_TRY(e_join);
+    NABU_TRY(e_join);
   }
   }
   if (defer)
-    SP_TRY(attn_param_grads(&adb, Sp, L, dec_len, enc_len, r + R.keys, r + R.q, p->attention_v, p->conv_proj, w + W.ds_all,
+    NABU_TRY(attn_param_grads(&adb, Sp, L, dec_len, enc_len, r + R.keys, r + R.q, p->attention_v, p->conv_proj, w + W.ds_all,
                             w + W.cf_all, dkeys, w + W.dv16, w + W.dwf16, s));
   // sums over steps as single GEMMs
-  SP_TRY(mm(true, false, U, U, BL, htop_all, U, dq, U, 0.f, g->query_kernel, U, nullptr, gw, gwb, stream));
+  NABU_TRY(mm(true, false, U, U, BL, htop_all, U, dq, U, 0.f, g->query_kernel, U, nullptr, gw, gwb, stream));
   for (int n = 0; n < nl; ++n) {
     const float *dzn = w + W.dz[n];
     float *gK = g->lstm_kernel[n];
     if (n == 0) {
-      SP_TRY(nabu_scatter_rows_f32(C, BL, 4 * U, reinterpret_cast<const int32_t *>(r + R.ids), dzn, gK, stream));
-      SP_TRY(mm(true, false, E, 4 * U, BL, r + R.ctx, E, dzn, 4 * U, 0.f, gK + (size_t)C * 4 * U, 4 * U, nullptr, gw, gwb, stream));
-      SP_TRY(mm(true, false, U, 4 * U, BL, r + R.H[0], U, dzn, 4 * U, 0.f, gK + (size_t)(C + E) * 4 * U, 4 * U, nullptr, gw, gwb, stream));
+      NABU_TRY(nabu_scatter_rows_f32(C, BL, 4 * U, reinterpret_cast<const int32_t *>(r + R.ids), dzn, gK, stream));
+      NABU_TRY(mm(true, false, E, 4 * U, BL, r + R.ctx, E, dzn, 4 * U, 0.f, gK + (size_t)C * 4 * U, 4 * U, nullptr, gw, gwb, stream));
+      NABU_TRY(mm(true, false, U, 4 * U, BL, r + R.H[0], U, dzn, 4 * U, 0.f, gK + (size_t)(C + E) * 4 * U, 4 * U, nullptr, gw, gwb, stream));
     } else {
-      SP_TRY(mm(true, false, U, 4 * U, BL, r + R.Ho[n - 1] + (size_t)B * U, U, dzn, 4 * U, 0.f, gK, 4 * U, nullptr, gw, gwb, stream));
-      SP_TRY(mm(true, false, U, 4 * U, BL, r + R.H[n], U, dzn, 4 * U, 0.f, gK + (size_t)U * 4 * U, 4 * U, nullptr, gw, gwb, stream));
+      NABU_TRY(mm(true, false, U, 4 * U, BL, r + R.Ho[n - 1] + (size_t)B * U, U, dzn, 4 * U, 0.f, gK, 4 * U, nullptr, gw, gwb, stream));
+      NABU_TRY(mm(true, false, U, 4 * U, BL, r + R.H[n], U, dzn, 4 * U, 0.f, gK + (size_t)U * 4 * U, 4 * U, nullptr, gw, gwb, stream));
     }
-    SP_TRY(nabu_colsum_f32(BL, 4 * U, dzn, 4 * U, 0.f, g->lstm_bias[n], gw, gwb, stream));
+    NABU_TRY(nabu_colsum_f32(BL, 4 * U, dzn, 4 * U, 0.f, g->lstm_bias[n], gw, gwb, stream));
   }
-  if (persist && !defer) SP_TRY(nabu_colsum_f32(B * 8, U, w + W.dv8, U, 0.f, g->attention_v, gw, gwb, stream));
-  else if (defer)        SP_TRY(nabu_colsum_f32(B * Sp, U, w + W.dv16, U, 0.f, g->attention_v, gw, gwb, stream));
-  else            SP_TRY(nabu_colsum_f32(B * S, U, w + W.dv, U, 0.f, g->attention_v, gw, gwb, stream));
+  if (persist && !defer) NABU_TRY(nabu_colsum_f32(B * 8, U, w + W.dv8, U, 0.f, g->attention_v, gw, gwb, stream));
+  else if (defer)        NABU_TRY(nabu_colsum_f32(B * Sp, U, w + W.dv16, U, 0.f, g->attention_v, gw, gwb, stream));
+  else            NABU_TRY(nabu_colsum_f32(B * S, U, w + W.dv, U, 0.f, g->attention_v, gw, gwb, stream));
   if (d->kind == 1) {
-    if (defer) SP_TRY(nabu_colsum_f32(B * Sp, F * U, w + W.dwf16, F * U, 0.f, g->conv_proj, gw, gwb, stream));
-    else       SP_TRY(nabu_colsum_f32(B * S, F * U, w + W.dwf, F * U, 0.f, g->conv_proj, gw, gwb, stream));
-    if (persist) SP_TRY(nabu_colsum_f32(B * 8, K * F, w + W.dck8, K * F, 0.f, g->conv_kernel, gw, gwb, stream));
-    else         SP_TRY(nabu_colsum_f32(B, K * F, w + W.dck, K * F, 0.f, g->conv_kernel, gw, gwb, stream));
+    if (defer) NABU_TRY(nabu_colsum_f32(B * Sp, F * U, w + W.dwf16, F * U, 0.f, g->conv_proj, gw, gwb, stream));
+    else       NABU_TRY(nabu_colsum_f32(B * S, F * U, w + W.dwf, F * U, 0.f, g->conv_proj, gw, gwb, stream));
+    if (persist) NABU_TRY(nabu_colsum_f32(B * 8, K * F, w + W.dck8, K * F, 0.f, g->conv_kernel, gw, gwb, stream));
+    else         NABU_TRY(nabu_colsum_f32(B, K * F, w + W.dck, K * F, 0.f, g->conv_kernel, gw, gwb, stream));
   }
   // keys = values·Wmem ; context_t = align_t^T·values
-  SP_TRY(mm(true, false, E, U, B * Te, values, E, dkeys, U, 0.f, g->memory_kernel, U, nullptr, gw, gwb, stream));
-  SP_TRY(mm(false, true, B * Te, E, U, dkeys, U, p->memory_kernel, U, 0.f, dvalues, E, nullptr, gw, gwb, stream));
+  NABU_TRY(mm(true, false, E, U, B * Te, values, E, dkeys, U, 0.f, g->memory_kernel, U, nullptr, gw, gwb, stream));
+  NABU_TRY(mm(false, true, B * Te, E, U, dkeys, U, p->memory_kernel, U, 0.f, dvalues, E, nullptr, gw, gwb, stream));
   const float *al1 = r + R.align + (size_t)B * Te;
   // dvalues[b] += align[:, b, :]^T · dCtx[:, b, :] for every utterance: one batched launch
-  SP_TRY(gemm_batched_f32(true, false, Te, E, L, al1, B * Te, Te, dCtx, B * E, E, 1.f, dvalues, E, (long long)Te * E, B, s));
+  NABU_TRY(gemm_batched_f32(true, false, Te, E, L, al1, B * Te, Te, dCtx, B * E, E, 1.f, dvalues, E, (long long)Te * E, B, s));
   return 0;
 }

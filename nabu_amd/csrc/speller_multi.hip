@@ -698,12 +698,6 @@ static MWs m_ws(const nabu_speller_multi_desc *d, const Geo &g) {
   return s;
 }
 
-static int mm(bool ta, bool tb, int M, int N, int K, const float *A, int lda, const float *Bm, int ldb, float beta,
-              float *C, int ldc, const float *bias, float *ws, size_t wsb, nabu_stream_t st) {
-  return nabu_gemm_f32(ta, tb, M, N, K, 1.f, A, lda, Bm, ldb, beta, C, ldc, bias, 0, 0, 0, ws, wsb, st);
-}
-#define SP_TRY(call) do { int e_ = (call); if (e_) return e_; } while (0)
-
 template <typename Kern>
 static int launch_attn(Kern kern, const Geo &g, int B, size_t shm, const MArgs &a, hipStream_t s) {
   if (shm > 64 * 1024)
@@ -727,6 +721,12 @@ static int check_ptrs(const nabu_speller_multi_desc *d, const float *const *valu
 }
 
 }  // namespace
+
+int put_cols(int R, int Cn, const float *src, float *dst, int ldd, int c0, hipStream_t s) {
+  hipLaunchKernelGGL(put_cols_kernel, dim3((R * Cn + 255) / 256), dim3(256), 0, s, R, Cn, src, dst, ldd, c0);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
 
 size_t multi_attn_part_floats(int B, int Te, int E, int U, int kind, int K, int F, int prob_fn) {
   const nabu_attn_desc a = {sizeof(nabu_attn_desc), B, Te, E, U, kind, K, F, prob_fn};
@@ -798,7 +798,7 @@ extern "C" int nabu_speller_multi_fwd(const nabu_speller_multi_desc *d, const fl
   Geo g;
   if (int e = check_md(d, &g)) return e;
   NABU_CHECK_ARG(values && enc_len && ids && dec_len && p && logits && reserve && ws, "speller_multi_fwd: null pointer");
-  SP_TRY(check_ptrs(d, values, enc_len, p));
+  NABU_TRY(check_ptrs(d, values, enc_len, p));
   const MLayout R = m_layout(d, g);
   const MWs W = m_ws(d, g);
   if (ws_bytes < W.total * sizeof(float)) return fail(NABU_EWS, "speller_multi_fwd: workspace too small");
@@ -820,11 +820,10 @@ extern "C" int nabu_speller_multi_fwd(const nabu_speller_multi_desc *d, const fl
   for (int m = 0; m < M; ++m) {
     const int Te = d->Te[m], E = d->E[m];
     NABU_HIP(hipMemsetAsync(r + R.align[m], 0, (size_t)B * Te * 4, s));
-    if (d->kind == 2) SP_TRY(first_col_one(B, Te, r + R.align[m], s));
+    if (d->kind == 2) NABU_TRY(first_col_one(B, Te, r + R.align[m], s));
     // keys_m = memory_layer_m(values_m); the query kernels side by side: q of all mechanisms is one product
-    SP_TRY(mm(false, false, B * Te, U, E, values[m], E, p->memory_kernel[m], U, 0.f, r + R.keys[m], U, nullptr, gw, gwb, stream));
-    hipLaunchKernelGGL(put_cols_kernel, dim3((U * U + 255) / 256), dim3(256), 0, s, U, U, p->query_kernel[m], w + W.wqcat, MU, m * U);
-    NABU_LAUNCH_CHECK();
+    NABU_TRY(mm(false, false, B * Te, U, E, values[m], E, p->memory_kernel[m], U, 0.f, r + R.keys[m], U, nullptr, gw, gwb, stream));
+    NABU_TRY(put_cols(U, U, p->query_kernel[m], w + W.wqcat, MU, m * U, s));
   }
   MArgs a = {};
   a.B = B; a.U = U; a.SE = SE; a.MU = MU; a.kind = d->kind; a.K = d->K; a.F = d->F; a.prob_fn = d->prob_fn;
@@ -846,23 +845,23 @@ extern "C" int nabu_speller_multi_fwd(const nabu_speller_multi_desc *d, const fl
       float *Hn = r + R.H[n], *Cn = r + R.Cs[n];
       if (n == 0) {
         // [ctx_0 | .. | ctx_{M-1}] . kernel rows C .. C + sum E: one product on the shared context rows
-        SP_TRY(mm(false, false, B, 4 * U, SE, r + R.ctx + (size_t)t * B * SE, SE, K0 + (size_t)C * 4 * U, 4 * U, 0.f, z, 4 * U, nullptr, gw, gwb, stream));
-        SP_TRY(mm(false, false, B, 4 * U, U, Hn + cur, U, K0 + (size_t)(C + SE) * 4 * U, 4 * U, 1.f, z, 4 * U, nullptr, gw, gwb, stream));
-        SP_TRY(nabu_lstm_cell_fwd(B, U, t, dec_len, z, p->lstm_bias[0], K0, ids_used + (size_t)t * B, Cn + cur, Hn + cur,
+        NABU_TRY(mm(false, false, B, 4 * U, SE, r + R.ctx + (size_t)t * B * SE, SE, K0 + (size_t)C * 4 * U, 4 * U, 0.f, z, 4 * U, nullptr, gw, gwb, stream));
+        NABU_TRY(mm(false, false, B, 4 * U, U, Hn + cur, U, K0 + (size_t)(C + SE) * 4 * U, 4 * U, 1.f, z, 4 * U, nullptr, gw, gwb, stream));
+        NABU_TRY(nabu_lstm_cell_fwd(B, U, t, dec_len, z, p->lstm_bias[0], K0, ids_used + (size_t)t * B, Cn + cur, Hn + cur,
                                   r + R.acts[0] + (size_t)t * B * 4 * U, Cn + nxt, Hn + nxt, stream));
       } else {
-        SP_TRY(mm(false, false, B, 4 * U, U, r + R.Ho[n - 1] + nxt, U, Kn, 4 * U, 0.f, z, 4 * U, nullptr, gw, gwb, stream));
-        SP_TRY(mm(false, false, B, 4 * U, U, Hn + cur, U, Kn + (size_t)U * 4 * U, 4 * U, 1.f, z, 4 * U, nullptr, gw, gwb, stream));
-        SP_TRY(nabu_lstm_cell_fwd(B, U, t, dec_len, z, p->lstm_bias[n], nullptr, nullptr, Cn + cur, Hn + cur,
+        NABU_TRY(mm(false, false, B, 4 * U, U, r + R.Ho[n - 1] + nxt, U, Kn, 4 * U, 0.f, z, 4 * U, nullptr, gw, gwb, stream));
+        NABU_TRY(mm(false, false, B, 4 * U, U, Hn + cur, U, Kn + (size_t)U * 4 * U, 4 * U, 1.f, z, 4 * U, nullptr, gw, gwb, stream));
+        NABU_TRY(nabu_lstm_cell_fwd(B, U, t, dec_len, z, p->lstm_bias[n], nullptr, nullptr, Cn + cur, Hn + cur,
                                   r + R.acts[n] + (size_t)t * B * 4 * U, Cn + nxt, Hn + nxt, stream));
       }
       if (drop)
-        SP_TRY(dropout_rows((size_t)B * U, Hn + nxt, r + R.Ho[n] + nxt, d->keep_prob, d->seed,
+        NABU_TRY(dropout_rows((size_t)B * U, Hn + nxt, r + R.Ho[n] + nxt, d->keep_prob, d->seed,
                             d->seed_offset + (unsigned long long)t * nl + n, 0, s));
     }
     const float *htop = r + R.Ho[nl - 1] + nxt;
     float *qt = r + R.q + (size_t)t * B * MU;
-    SP_TRY(mm(false, false, B, MU, U, htop, U, w + W.wqcat, MU, 0.f, qt, MU, nullptr, gw, gwb, stream));
+    NABU_TRY(mm(false, false, B, MU, U, htop, U, w + W.wqcat, MU, 0.f, qt, MU, nullptr, gw, gwb, stream));
     a.step = t; a.q = qt;
     a.ctx_prev = r + R.ctx + (size_t)t * B * SE;
     a.ctx = r + R.ctx + (size_t)(t + 1) * B * SE;
@@ -871,29 +870,29 @@ extern "C" int nabu_speller_multi_fwd(const nabu_speller_multi_desc *d, const fl
       a.m[m].align = r + R.align[m] + (size_t)(t + 1) * B * d->Te[m];
       a.m[m].znorm = r + R.znorm[m] + (size_t)t * B;
     }
-    if (d->kind == 1) SP_TRY(launch_attn(attn_multi_fwd_kernel<true>, g, B, g.lds_f, a, s));
-    else              SP_TRY(launch_attn(attn_multi_fwd_kernel<false>, g, B, g.lds_f, a, s));
+    if (d->kind == 1) NABU_TRY(launch_attn(attn_multi_fwd_kernel<true>, g, B, g.lds_f, a, s));
+    else              NABU_TRY(launch_attn(attn_multi_fwd_kernel<false>, g, B, g.lds_f, a, s));
     if (sampling && t + 1 < L) {
       // ScheduledEmbeddingTrainingHelper: the step's logits decide the next input of selected rows (the draws are
       // those of the one-memory decoder: counter (row, sample_offset + t))
       if (sample_step_ok(C)) {
-        SP_TRY(sample_step(B, C, U, SE, htop, U, a.ctx, SE, p->out_kernel, p->out_bias, d->sample_prob, d->sample_seed,
+        NABU_TRY(sample_step(B, C, U, SE, htop, U, a.ctx, SE, p->out_kernel, p->out_bias, d->sample_prob, d->sample_seed,
                            d->sample_offset + (unsigned long long)t, ids + (size_t)(t + 1) * B, ids_used + (size_t)(t + 1) * B, 0, s));
         continue;
       }
       float *lt = r + R.logits_tm + (size_t)t * B * C;
-      SP_TRY(mm(false, false, B, C, U, htop, U, p->out_kernel, C, 0.f, lt, C, p->out_bias, gw, gwb, stream));
-      SP_TRY(mm(false, false, B, C, SE, a.ctx, SE, p->out_kernel + (size_t)U * C, C, 1.f, lt, C, nullptr, gw, gwb, stream));
-      SP_TRY(sample_ids_rows(B, C, lt, d->sample_prob, d->sample_seed, d->sample_offset + (unsigned long long)t,
+      NABU_TRY(mm(false, false, B, C, U, htop, U, p->out_kernel, C, 0.f, lt, C, p->out_bias, gw, gwb, stream));
+      NABU_TRY(mm(false, false, B, C, SE, a.ctx, SE, p->out_kernel + (size_t)U * C, C, 1.f, lt, C, nullptr, gw, gwb, stream));
+      NABU_TRY(sample_ids_rows(B, C, lt, d->sample_prob, d->sample_seed, d->sample_offset + (unsigned long long)t,
                              ids + (size_t)(t + 1) * B, ids_used + (size_t)(t + 1) * B, 0, s));
     }
   }
   // output projection of all steps: [h_t | contexts_t] . W + b, then batch-major + impute_finished
   float *ltm = r + R.logits_tm;
-  SP_TRY(mm(false, false, L * B, C, U, r + R.Ho[nl - 1] + (size_t)B * U, U, p->out_kernel, C, 0.f, ltm, C, p->out_bias, gw, gwb, stream));
-  SP_TRY(mm(false, false, L * B, C, SE, r + R.ctx + (size_t)B * SE, SE, p->out_kernel + (size_t)U * C, C, 1.f, ltm, C, nullptr, gw, gwb, stream));
-  SP_TRY(nabu_swap01_f32(L, B, C, ltm, logits, stream));
-  SP_TRY(nabu_mask_time_f32(B, L, C, logits, dec_len, stream));
+  NABU_TRY(mm(false, false, L * B, C, U, r + R.Ho[nl - 1] + (size_t)B * U, U, p->out_kernel, C, 0.f, ltm, C, p->out_bias, gw, gwb, stream));
+  NABU_TRY(mm(false, false, L * B, C, SE, r + R.ctx + (size_t)B * SE, SE, p->out_kernel + (size_t)U * C, C, 1.f, ltm, C, nullptr, gw, gwb, stream));
+  NABU_TRY(nabu_swap01_f32(L, B, C, ltm, logits, stream));
+  NABU_TRY(nabu_mask_time_f32(B, L, C, logits, dec_len, stream));
   return 0;
 }
 
@@ -906,8 +905,8 @@ extern "C" int nabu_speller_multi_bwd(const nabu_speller_multi_desc *d, const fl
   if (int e = check_md(d, &g)) return e;
   NABU_CHECK_ARG(values && enc_len && ids && dec_len && p && dlogits && reserve && gr && dvalues && ws,
                  "speller_multi_bwd: null pointer");
-  SP_TRY(check_ptrs(d, values, enc_len, p));
-  SP_TRY(check_ptrs(d, dvalues, enc_len, reinterpret_cast<const nabu_speller_multi_params *>(gr)));
+  NABU_TRY(check_ptrs(d, values, enc_len, p));
+  NABU_TRY(check_ptrs(d, dvalues, enc_len, reinterpret_cast<const nabu_speller_multi_params *>(gr)));
   const MLayout R = m_layout(d, g);
   const MWs W = m_ws(d, g);
   if (ws_bytes < W.total * sizeof(float)) return fail(NABU_EWS, "speller_multi_bwd: workspace too small");
@@ -923,12 +922,12 @@ extern "C" int nabu_speller_multi_bwd(const nabu_speller_multi_desc *d, const fl
   const float *htop_all = r + R.Ho[nl - 1] + (size_t)B * U;
   const float *ctx1 = r + R.ctx + (size_t)B * SE;
   // output projection
-  SP_TRY(nabu_swap01_f32(B, L, C, dlogits, dl, stream));
-  SP_TRY(mm(true, false, U, C, BL, htop_all, U, dl, C, 0.f, gr->out_kernel, C, nullptr, gw, gwb, stream));
-  SP_TRY(mm(true, false, SE, C, BL, ctx1, SE, dl, C, 0.f, gr->out_kernel + (size_t)U * C, C, nullptr, gw, gwb, stream));
-  SP_TRY(nabu_colsum_f32(BL, C, dl, C, 0.f, gr->out_bias, gw, gwb, stream));
-  SP_TRY(mm(false, true, BL, U, C, dl, C, p->out_kernel, C, 0.f, dH, U, nullptr, gw, gwb, stream));
-  SP_TRY(mm(false, true, BL, SE, C, dl, C, p->out_kernel + (size_t)U * C, C, 0.f, dCtx, SE, nullptr, gw, gwb, stream));
+  NABU_TRY(nabu_swap01_f32(B, L, C, dlogits, dl, stream));
+  NABU_TRY(mm(true, false, U, C, BL, htop_all, U, dl, C, 0.f, gr->out_kernel, C, nullptr, gw, gwb, stream));
+  NABU_TRY(mm(true, false, SE, C, BL, ctx1, SE, dl, C, 0.f, gr->out_kernel + (size_t)U * C, C, nullptr, gw, gwb, stream));
+  NABU_TRY(nabu_colsum_f32(BL, C, dl, C, 0.f, gr->out_bias, gw, gwb, stream));
+  NABU_TRY(mm(false, true, BL, U, C, dl, C, p->out_kernel, C, 0.f, dH, U, nullptr, gw, gwb, stream));
+  NABU_TRY(mm(false, true, BL, SE, C, dl, C, p->out_kernel + (size_t)U * C, C, 0.f, dCtx, SE, nullptr, gw, gwb, stream));
   NABU_HIP(hipMemsetAsync(w + W.tickets, 0, (size_t)MM * B * 4, s));
   for (int n = 0; n < nl; ++n) {
     NABU_HIP(hipMemsetAsync(w + W.dh[0][n], 0, (size_t)B * U * 4, s));
@@ -945,8 +944,7 @@ extern "C" int nabu_speller_multi_bwd(const nabu_speller_multi_desc *d, const fl
       NABU_HIP(hipMemsetAsync(w + W.dwf[m], 0, (size_t)B * S * F * U * 4, s));
       NABU_HIP(hipMemsetAsync(w + W.dck[m], 0, (size_t)B * K * F * 4, s));
     }
-    hipLaunchKernelGGL(put_cols_kernel, dim3((U * U + 255) / 256), dim3(256), 0, s, U, U, p->query_kernel[m], w + W.wqcat, MU, m * U);
-    NABU_LAUNCH_CHECK();
+    NABU_TRY(put_cols(U, U, p->query_kernel[m], w + W.wqcat, MU, m * U, s));
     MMem &x = a.m[m];
     x.Te = Te; x.E = d->E[m]; x.coff = g.coff[m]; x.S = S;
     x.enc_len = enc_len[m]; x.keys = r + R.keys[m]; x.values = values[m]; x.v = p->attention_v[m];
@@ -961,7 +959,7 @@ extern "C" int nabu_speller_multi_bwd(const nabu_speller_multi_desc *d, const fl
   bool have_carry = false;
   for (int t = L - 1; t >= 0; --t) {
     float *dCt = dCtx + (size_t)t * B * SE;
-    if (have_carry) SP_TRY(nabu_axpy_f32((size_t)B * SE, 1.f, w + W.dctxc, dCt, stream));
+    if (have_carry) NABU_TRY(nabu_axpy_f32((size_t)B * SE, 1.f, w + W.dctxc, dCt, stream));
     float *dqt = dq + (size_t)t * B * MU;
     a.step = t; a.q = r + R.q + (size_t)t * B * MU;
     a.ctx = r + R.ctx + (size_t)(t + 1) * B * SE;
@@ -974,31 +972,31 @@ extern "C" int nabu_speller_multi_bwd(const nabu_speller_multi_desc *d, const fl
       x.dalign_out = d->kind == 1 ? w + W.dal[t & 1][m] : nullptr;
       x.dalign_in = (d->kind == 1 && have_carry) ? w + W.dal[(t + 1) & 1][m] : nullptr;
     }
-    if (d->kind == 1) SP_TRY(launch_attn(attn_multi_bwd_kernel<true>, g, B, g.lds_b, a, s));
-    else              SP_TRY(launch_attn(attn_multi_bwd_kernel<false>, g, B, g.lds_b, a, s));
+    if (d->kind == 1) NABU_TRY(launch_attn(attn_multi_bwd_kernel<true>, g, B, g.lds_b, a, s));
+    else              NABU_TRY(launch_attn(attn_multi_bwd_kernel<false>, g, B, g.lds_b, a, s));
     // d h_top += [dq_0 | .. | dq_{M-1}] . [Wq_0 | .. | Wq_{M-1}]^T: one product
     float *dHt = dH + (size_t)t * B * U;
-    SP_TRY(mm(false, true, B, U, MU, dqt, MU, w + W.wqcat, MU, 1.f, dHt, U, nullptr, gw, gwb, stream));
+    NABU_TRY(mm(false, true, B, U, MU, dqt, MU, w + W.wqcat, MU, 1.f, dHt, U, nullptr, gw, gwb, stream));
     const float *dtop = dHt;
     for (int n = nl - 1; n >= 0; --n) {
       const float *dh_in = dtop;
       if (drop) {
-        SP_TRY(dropout_rows((size_t)B * U, dtop, w + W.tmp, d->keep_prob, d->seed,
+        NABU_TRY(dropout_rows((size_t)B * U, dtop, w + W.tmp, d->keep_prob, d->seed,
                             d->seed_offset + (unsigned long long)t * nl + n, 0, s));
         dh_in = w + W.tmp;
       }
       float *dzt = w + W.dz[n] + (size_t)t * B * 4 * U;
       const float *Cn = r + R.Cs[n];
-      SP_TRY(nabu_lstm_cell_bwd(B, U, t, dec_len, r + R.acts[n] + (size_t)t * B * 4 * U, Cn + (size_t)(t + 1) * B * U,
+      NABU_TRY(nabu_lstm_cell_bwd(B, U, t, dec_len, r + R.acts[n] + (size_t)t * B * 4 * U, Cn + (size_t)(t + 1) * B * U,
                                 Cn + (size_t)t * B * U, dh_in, w + W.dh[cur][n], w + W.dc[cur][n], dzt, w + W.dc[cur ^ 1][n],
                                 stream));
       const float *Kn = p->lstm_kernel[n];
       if (n == 0) {
-        SP_TRY(mm(false, true, B, SE, 4 * U, dzt, 4 * U, K0 + (size_t)C * 4 * U, 4 * U, 0.f, w + W.dctxc, SE, nullptr, gw, gwb, stream));
-        SP_TRY(mm(false, true, B, U, 4 * U, dzt, 4 * U, K0 + (size_t)(C + SE) * 4 * U, 4 * U, 0.f, w + W.dh[cur ^ 1][0], U, nullptr, gw, gwb, stream));
+        NABU_TRY(mm(false, true, B, SE, 4 * U, dzt, 4 * U, K0 + (size_t)C * 4 * U, 4 * U, 0.f, w + W.dctxc, SE, nullptr, gw, gwb, stream));
+        NABU_TRY(mm(false, true, B, U, 4 * U, dzt, 4 * U, K0 + (size_t)(C + SE) * 4 * U, 4 * U, 0.f, w + W.dh[cur ^ 1][0], U, nullptr, gw, gwb, stream));
       } else {
-        SP_TRY(mm(false, true, B, U, 4 * U, dzt, 4 * U, Kn, 4 * U, 0.f, w + W.dx, U, nullptr, gw, gwb, stream));
-        SP_TRY(mm(false, true, B, U, 4 * U, dzt, 4 * U, Kn + (size_t)U * 4 * U, 4 * U, 0.f, w + W.dh[cur ^ 1][n], U, nullptr, gw, gwb, stream));
+        NABU_TRY(mm(false, true, B, U, 4 * U, dzt, 4 * U, Kn, 4 * U, 0.f, w + W.dx, U, nullptr, gw, gwb, stream));
+        NABU_TRY(mm(false, true, B, U, 4 * U, dzt, 4 * U, Kn + (size_t)U * 4 * U, 4 * U, 0.f, w + W.dh[cur ^ 1][n], U, nullptr, gw, gwb, stream));
         dtop = w + W.dx;
       }
     }
@@ -1007,33 +1005,33 @@ extern "C" int nabu_speller_multi_bwd(const nabu_speller_multi_desc *d, const fl
   }
   // sums over steps as single products over all steps
   for (int m = 0; m < M; ++m)
-    SP_TRY(mm(true, false, U, U, BL, htop_all, U, dq + (size_t)m * U, MU, 0.f, gr->query_kernel[m], U, nullptr, gw, gwb, stream));
+    NABU_TRY(mm(true, false, U, U, BL, htop_all, U, dq + (size_t)m * U, MU, 0.f, gr->query_kernel[m], U, nullptr, gw, gwb, stream));
   for (int n = 0; n < nl; ++n) {
     const float *dzn = w + W.dz[n];
     float *gK = gr->lstm_kernel[n];
     if (n == 0) {
-      SP_TRY(nabu_scatter_rows_f32(C, BL, 4 * U, reinterpret_cast<const int32_t *>(r + R.ids), dzn, gK, stream));
-      SP_TRY(mm(true, false, SE, 4 * U, BL, r + R.ctx, SE, dzn, 4 * U, 0.f, gK + (size_t)C * 4 * U, 4 * U, nullptr, gw, gwb, stream));
-      SP_TRY(mm(true, false, U, 4 * U, BL, r + R.H[0], U, dzn, 4 * U, 0.f, gK + (size_t)(C + SE) * 4 * U, 4 * U, nullptr, gw, gwb, stream));
+      NABU_TRY(nabu_scatter_rows_f32(C, BL, 4 * U, reinterpret_cast<const int32_t *>(r + R.ids), dzn, gK, stream));
+      NABU_TRY(mm(true, false, SE, 4 * U, BL, r + R.ctx, SE, dzn, 4 * U, 0.f, gK + (size_t)C * 4 * U, 4 * U, nullptr, gw, gwb, stream));
+      NABU_TRY(mm(true, false, U, 4 * U, BL, r + R.H[0], U, dzn, 4 * U, 0.f, gK + (size_t)(C + SE) * 4 * U, 4 * U, nullptr, gw, gwb, stream));
     } else {
-      SP_TRY(mm(true, false, U, 4 * U, BL, r + R.Ho[n - 1] + (size_t)B * U, U, dzn, 4 * U, 0.f, gK, 4 * U, nullptr, gw, gwb, stream));
-      SP_TRY(mm(true, false, U, 4 * U, BL, r + R.H[n], U, dzn, 4 * U, 0.f, gK + (size_t)U * 4 * U, 4 * U, nullptr, gw, gwb, stream));
+      NABU_TRY(mm(true, false, U, 4 * U, BL, r + R.Ho[n - 1] + (size_t)B * U, U, dzn, 4 * U, 0.f, gK, 4 * U, nullptr, gw, gwb, stream));
+      NABU_TRY(mm(true, false, U, 4 * U, BL, r + R.H[n], U, dzn, 4 * U, 0.f, gK + (size_t)U * 4 * U, 4 * U, nullptr, gw, gwb, stream));
     }
-    SP_TRY(nabu_colsum_f32(BL, 4 * U, dzn, 4 * U, 0.f, gr->lstm_bias[n], gw, gwb, stream));
+    NABU_TRY(nabu_colsum_f32(BL, 4 * U, dzn, 4 * U, 0.f, gr->lstm_bias[n], gw, gwb, stream));
   }
   for (int m = 0; m < M; ++m) {
     const int Te = d->Te[m], E = d->E[m], S = g.S[m];
     float *dkeys = w + W.dkeys[m];
-    SP_TRY(nabu_colsum_f32(B * S, U, w + W.dv[m], U, 0.f, gr->attention_v[m], gw, gwb, stream));
+    NABU_TRY(nabu_colsum_f32(B * S, U, w + W.dv[m], U, 0.f, gr->attention_v[m], gw, gwb, stream));
     if (d->kind == 1) {
-      SP_TRY(nabu_colsum_f32(B * S, F * U, w + W.dwf[m], F * U, 0.f, gr->conv_proj[m], gw, gwb, stream));
-      SP_TRY(nabu_colsum_f32(B, K * F, w + W.dck[m], K * F, 0.f, gr->conv_kernel[m], gw, gwb, stream));
+      NABU_TRY(nabu_colsum_f32(B * S, F * U, w + W.dwf[m], F * U, 0.f, gr->conv_proj[m], gw, gwb, stream));
+      NABU_TRY(nabu_colsum_f32(B, K * F, w + W.dck[m], K * F, 0.f, gr->conv_kernel[m], gw, gwb, stream));
     }
     // keys = values . Wmem ; context_t = align_t^T . values
-    SP_TRY(mm(true, false, E, U, B * Te, values[m], E, dkeys, U, 0.f, gr->memory_kernel[m], U, nullptr, gw, gwb, stream));
-    SP_TRY(mm(false, true, B * Te, E, U, dkeys, U, p->memory_kernel[m], U, 0.f, dvalues[m], E, nullptr, gw, gwb, stream));
+    NABU_TRY(mm(true, false, E, U, B * Te, values[m], E, dkeys, U, 0.f, gr->memory_kernel[m], U, nullptr, gw, gwb, stream));
+    NABU_TRY(mm(false, true, B * Te, E, U, dkeys, U, p->memory_kernel[m], U, 0.f, dvalues[m], E, nullptr, gw, gwb, stream));
     // dvalues_m[b] += align_m[:, b, :]^T . dCtx[:, b, columns of m]: one batched launch over the utterances
-    SP_TRY(gemm_batched_f32(true, false, Te, E, L, r + R.align[m] + (size_t)B * Te, B * Te, Te, dCtx + g.coff[m], B * SE, SE, 1.f,
+    NABU_TRY(gemm_batched_f32(true, false, Te, E, L, r + R.align[m] + (size_t)B * Te, B * Te, Te, dCtx + g.coff[m], B * SE, SE, 1.f,
                             dvalues[m], E, (long long)Te * E, B, s));
   }
   return 0;

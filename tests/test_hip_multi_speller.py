@@ -207,8 +207,7 @@ def test_one_memory_through_the_new_entry_points_equals_the_existing_ones(attent
     lg0, loss0, d0, store = run_device(dec, encs, SMALL['enc_lens'][:1], tg, tlen)
     assert not hasattr(rnn_decoder.dynamic_decode.last[0], 'M')          # the one-memory descriptor
     g0 = {n: v.grad.cpu().numpy().copy() for n, v in store.vars.items()}
-    multi = rnn_decoder._dynamic_decode_multi
-    monkeypatch.setattr(rnn_decoder, 'dynamic_decode', _through_multi(rnn_decoder.dynamic_decode, multi))
+    monkeypatch.setattr(rnn_decoder, '_force_multi', True)
     lg1, loss1, d1, _ = run_device(dec, encs, SMALL['enc_lens'][:1], tg, tlen, store=store)
     assert rnn_decoder.dynamic_decode.last[0].M == 1
     assert np.abs(lg1 - lg0).max() < 2e-5
@@ -216,14 +215,6 @@ def test_one_memory_through_the_new_entry_points_equals_the_existing_ones(attent
     assert rel(d1[0], d0[0]) < 2e-4
     for n, v in store.vars.items():
         assert rel(v.grad.cpu().numpy(), g0[n]) < 2e-4, n
-
-
-def _through_multi(orig, multi):
-    def f(cell, encoded, encoded_seq_length, targets, target_seq_length, sample_prob, is_training):
-        return multi(cell, list(encoded), list(encoded_seq_length), targets, target_seq_length, sample_prob)
-    f.events = None
-    f.last = None
-    return f
 
 
 @pytest.mark.parametrize('attention,K,F', [('location_aware', 3, 2), ('vanilla', 0, 0)])
@@ -333,6 +324,58 @@ def test_beam_search_over_two_memories_against_brute_force(attention, K, F, seed
                 a = aligns[m][b, w].cpu().numpy()
                 for t in range(len(als[m])):
                     np.testing.assert_allclose(a[t], als[m][t], atol=2e-5)
+
+
+# the BEAM case restricted to its first memory, and 40 frames with lengths (40, 20): more than the 32 frames of a slice,
+# so both attention implementations run frame-sliced (tests/test_hip_decode.py uses 40 frames for the same purpose)
+ONE_BEAM = dict(BEAM, Tes=BEAM['Tes'][:1], Es=BEAM['Es'][:1], enc_lens=BEAM['enc_lens'][:1])
+ONE_BEAM_40 = dict(ONE_BEAM, Tes=(40,), enc_lens=[np.array([40, 20])])
+
+
+@pytest.mark.parametrize('attention,K,F,case,seed,sliced', [('vanilla', 0, 0, ONE_BEAM, 40, False),
+                                                            ('location_aware', 3, 2, ONE_BEAM, 36, False),
+                                                            ('location_aware', 3, 2, ONE_BEAM_40, 49, True)])
+def test_one_memory_through_both_beam_search_entry_points(attention, K, F, case, seed, sliced, monkeypatch):
+    """guards the shared beam-search loop: the same decoder and the same single memory once through
+    nabu_speller_beam_search (nabu_attn_fwd) and once through nabu_speller_multi_beam_search with M = 1
+    (multi_attn_fwd).  The two attention kernels round differently, so a near-tie between candidates could order
+    differently: the float64 enumeration must keep neighbouring candidate scores more than 100 x the score bound apart
+    (seeds chosen on the CPU for that, asserted below)."""
+    from nabu_amd import _hip, variables as vs
+    from nabu_amd.autodiff import SeqLen
+    from nabu_amd.neuralnetworks.models.ed_decoders import rnn_decoder
+    c = dict(case, seed=seed)
+    dev = torch.device('cuda')
+    # the geometry of the B * W rows in both implementations: one workgroup per row, or frame slices with partials
+    N, kind = c['B'] * c['W'], {'vanilla': 0, 'location_aware': 1}[attention]
+    ad = _hip.AttnDesc(ctypes.sizeof(_hip.AttnDesc), N, c['Tes'][0], c['Es'][0], c['U'], kind, K, F, 0)
+    assert (_hip.lib().nabu_attn_fwd_ws_bytes(ctypes.byref(ad)) > 0) == sliced
+    assert (slices_of(N, c['U'], c['C'], 1, 1, c['Tes'], c['Es'], kind, K, F)[0] > 1) == sliced
+    dec, encs = beam_cell(c, attention, K, F)
+    store = vs.VariableStore(seed=c['seed'])
+    enc_d = {'features': torch.tensor(encs[0], device=dev)}
+    lens = {'features': SeqLen(c['enc_lens'][0].astype(np.int32), dev)}
+    with torch.no_grad(), vs.as_default(store), vs.variable_scope('Speller'):
+        cell = dec.create_cell(enc_d, lens, False)
+        args = (cell, list(enc_d.values()), list(lens.values()), c['W'], c['S'], 0.0, 1.0)
+        seqs0, lengths0, scores0, aligns0 = rnn_decoder.beam_search(*args)
+        monkeypatch.setattr(rnn_decoder, '_force_multi', True)
+        seqs1, lengths1, scores1, aligns1 = rnn_decoder.beam_search(*args)
+    # the one-memory entry point returns the alignments as a tensor, the multi one as a list per memory
+    assert torch.is_tensor(aligns0) and isinstance(aligns1, list) and len(aligns1) == 1
+    p = ref_params(store.state_dict(), 1, attention, 1)
+    _, gap, steps = MR.brute_force_beam_search([encs[0].astype(np.float64)], c['enc_lens'], p, c['W'], c['S'], attention)
+    print('smallest gap between neighbouring candidates %.4f, steps %d' % (gap, steps))
+    assert gap > 100 * BEAM_BOUND, gap
+    assert seqs0.shape == seqs1.shape == (c['B'], c['W'], steps)
+    np.testing.assert_array_equal(seqs1.cpu().numpy(), seqs0.cpu().numpy())
+    np.testing.assert_array_equal(lengths1.cpu().numpy(), lengths0.cpu().numpy())
+    err = np.abs(scores1.cpu().numpy() - scores0.cpu().numpy()).max()
+    aerr = np.abs(aligns1[0].cpu().numpy() - aligns0.cpu().numpy()).max()
+    print('scores abs diff %.3g, alignments abs diff %.3g' % (err, aerr))
+    np.testing.assert_allclose(scores1.cpu().numpy(), scores0.cpu().numpy(), rtol=BEAM_BOUND, atol=BEAM_BOUND)
+    assert tuple(aligns0.shape) == tuple(aligns1[0].shape) == (c['B'], c['W'], steps, c['Tes'][0])
+    np.testing.assert_allclose(aligns1[0].cpu().numpy(), aligns0.cpu().numpy(), atol=2e-5)
 
 
 def test_beam_search_decoder_gives_alignments_per_input_name():
