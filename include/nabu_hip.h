@@ -302,7 +302,7 @@ int nabu_blstm_bwd_weights(const nabu_blstm_desc *d, const float *x, const int32
                            void *reserve, float *dkernel_fw, float *dkernel_bw, void *ws, size_t ws_bytes,
                            nabu_stream_t stream);
 
-/* ---- layer-normalised BLSTM layer (lstm_ln.hip): layer.blstm(layer_norm=True) ---------------------------------
+/* ---- layer-normalised BLSTM layer (lstm.hip's driver, lstm_ln.hip's recurrence): layer.blstm(layer_norm=True) ----
  * tf.contrib.rnn.LayerNormBasicLSTMCell(num_units, layer_norm=True) under bidirectional_dynamic_rnn.  Per direction,
  * batch row b and step s < len[b]:
  *   z = [x_t, h] . kernel                       (NO bias: the cell has no bias variable when it normalises)

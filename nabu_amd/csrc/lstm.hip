@@ -1,17 +1,24 @@
-// lstm.hip — one bidirectional LSTM layer (layer.blstm of the reference):
-// orchestration of the input-projection GEMMs, the recurrent kernels and the
-// weight-gradient GEMMs, plus the one-launch-per-timestep recurrent kernels.
+// lstm.hip — one bidirectional LSTM layer (layer.blstm of the reference), for both cells: the plain cell
+// (nabu_blstm_*) and the layer-normalised one (nabu_blstm_ln_*, layer.blstm(layer_norm=True)).  The entry points are
+// adapters around ONE forward and ONE backward driver that take the cell as an argument and read as a sequence of stages:
+//   forward   input projection (packed-plane operands | plain) · zeroing of frames >= max_len · companions ·
+//             recurrence (persistent, with its fallback | stepwise plain | stepwise layer-norm)
+//   backward  zeroing · recurrence · norm-parameter gradients · packed products · plain products and bias gradients
+// What the layer-normalised cell does NOT take (packed products, bias, companions, a persistent plan, the profiling
+// hooks) is decided in one place, ln_layout; the stages read the layout.  The plain cell's step kernels are here, the
+// layer-normalised cell's in lstm_ln.hip; both use the product tiles of lstm_step.h.
 //
 // Data layout in HBM (all fp32, batch-major):
 //   x      [B,T,D]        layer input
 //   out    [B,T,2H]       fw | bw hidden states, 0 for t >= len
-//   reserve = gates_fw [B,T,4H] | gates_bw [B,T,4H] | cs_fw [B,T,H] | cs_bw [B,T,H]
+//   reserve = gates_fw [B,T,4H] | gates_bw [B,T,4H] | cs_fw [B,T,H] | cs_bw [B,T,H]   (layer norm: lstm_ln.hip)
 //     gates_* first holds x·Wx+b (GEMM output), is overwritten in place by the
 //     activations (i,g,f,o) in the forward recurrence and again in place by the
 //     pre-activation gradients dz in the backward recurrence.
 // The TF kernel [(D+H),4H] is used as stored: rows [0,D) = Wx, rows [D,D+H) = Wh.
 #include "common.h"
 #include "lstm_persist.h"
+#include "lstm_step.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -32,50 +39,19 @@ struct StepArgs {
   float *cstate;       // fwd: c state [2][B][H]; bwd: dc carry [2][B][H]
 };
 
-constexpr int SB = 16;  // batch rows per block
-constexpr int SU = 16;  // hidden units per block
-
 // ---------------------------------------------------------------------------
 // forward, one timestep, both directions.  grid (H/16, B/16, 2), 256 threads.
-__global__ __launch_bounds__(256) void lstm_step_fwd_kernel(StepArgs p, int s) {
+__global__ __launch_bounds__(STEP_NT) void lstm_step_fwd_kernel(StepArgs p, int s) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int H = p.H, B = p.B, T = p.T;
   float *hs = smem;               // [SB][H]
   float *zs = smem + SB * H;      // [SB][4][SU]
   const int dir = blockIdx.z, u0 = blockIdx.x * SU, b0 = blockIdx.y * SB;
   const int tid = threadIdx.x;
+  // the cell is fused behind the product: h ping-pongs between two buffers
   const float *hprev = p.hstate + ((size_t)((s & 1) * 2 + dir) * B) * H;
   float *hnext = p.hstate + ((size_t)(((s & 1) ^ 1) * 2 + dir) * B) * H;
-
-  // stage h_{s-1} of this block's batch rows
-  for (int i = tid; i < SB * H / 4; i += 256) {
-    const int bl = i / (H / 4), k4 = i % (H / 4);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (b0 + bl < B) v = reinterpret_cast<const float4 *>(hprev + (size_t)(b0 + bl) * H)[k4];
-    reinterpret_cast<float4 *>(hs + bl * H)[k4] = v;
-  }
-  __syncthreads();
-
-  {  // recurrent product: thread = (batch row bl, gate g, unit quad q)
-    const int q = tid & 3, g = (tid >> 2) & 3, bl = tid >> 4;
-    const int ucol = u0 + 4 * q;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ucol < H) {
-      const float *W = p.kernel[dir] + (size_t)p.D * 4 * H + (size_t)g * H + ucol;
-      const float *hrow = hs + bl * H;
-#pragma unroll 4
-      for (int k = 0; k < H; ++k) {
-        const float4 w = *reinterpret_cast<const float4 *>(W + (size_t)k * 4 * H);
-        const float hv = hrow[k];
-        acc.x = fmaf(hv, w.x, acc.x);
-        acc.y = fmaf(hv, w.y, acc.y);
-        acc.z = fmaf(hv, w.z, acc.z);
-        acc.w = fmaf(hv, w.w, acc.w);
-      }
-    }
-    *reinterpret_cast<float4 *>(zs + (bl * 4 + g) * SU + 4 * q) = acc;
-  }
-  __syncthreads();
+  rec_fwd_tile(p, hprev, dir, b0, u0, hs, zs);
 
   {  // gates + state update: thread = (batch row bl, unit u)
     const int u = tid & 15, bl = tid >> 4;
@@ -112,9 +88,7 @@ __global__ __launch_bounds__(256) void lstm_step_fwd_kernel(StepArgs p, int s) {
 // backward, one timestep (s descending), both directions.
 //   dh_carry[b,u] = sum_col dz_{s+1}[b,col] * Wh[u,col]      (block-local)
 //   dz_s from saved activations, written in place over the activations.
-constexpr int DZC = 512;  // dz columns staged per LDS chunk
-
-__global__ __launch_bounds__(256) void lstm_step_bwd_kernel(StepArgs p, int s) {
+__global__ __launch_bounds__(STEP_NT) void lstm_step_bwd_kernel(StepArgs p, int s) {
   __shared__ __attribute__((aligned(16))) float dzs[SB][DZC];
   const int H = p.H, B = p.B, T = p.T;
   const int dir = blockIdx.z, u0 = blockIdx.x * SU, b0 = blockIdx.y * SB;
@@ -125,38 +99,8 @@ __global__ __launch_bounds__(256) void lstm_step_bwd_kernel(StepArgs p, int s) {
   const int n = b < B ? p.len[b] : 0;
 
   float dh = 0.f;
-  if (s + 1 < p.max_len) {
-    const float *Wrow = p.kernel[dir] + (size_t)(p.D + (hu < H ? hu : 0)) * 4 * H;
-    for (int c0 = 0; c0 < 4 * H; c0 += DZC) {
-      const int cw = min(DZC, 4 * H - c0);
-      __syncthreads();
-      for (int i = tid; i < SB * (DZC / 4); i += 256) {
-        const int r = i / (DZC / 4), c4 = i % (DZC / 4);
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        const int bb = b0 + r;
-        if (bb < B && 4 * c4 < cw) {
-          const int nn = p.len[bb];
-          if (s + 1 < nn) {
-            const int t1 = dir ? nn - 2 - s : s + 1;
-            v = *reinterpret_cast<const float4 *>(p.gates[dir] + ((size_t)bb * T + t1) * 4 * H + c0 + 4 * c4);
-          }
-        }
-        *reinterpret_cast<float4 *>(&dzs[r][4 * c4]) = v;
-      }
-      __syncthreads();
-      if (valid) {
-#pragma unroll 4
-        for (int c = 0; c < cw; c += 4) {
-          const float4 w = *reinterpret_cast<const float4 *>(Wrow + c0 + c);
-          const float4 d = *reinterpret_cast<const float4 *>(&dzs[bl][c]);
-          dh = fmaf(d.x, w.x, dh);
-          dh = fmaf(d.y, w.y, dh);
-          dh = fmaf(d.z, w.z, dh);
-          dh = fmaf(d.w, w.w, dh);
-        }
-      }
-    }
-  }
+  if (s + 1 < p.max_len)
+    dh = rec_bwd_tile(p, dir, s, b0, u0, dzs);
   if (!valid) return;
   if (s < n) {
     const int t = dir ? n - 1 - s : s;
@@ -220,31 +164,65 @@ struct Layout {
   // dZ^T packed [8H, BT] lives in the layer's RESERVE (behind the activations): it is written by the data part of
   // the backward pass and read by the weight-gradient part, which may run later (nabu_blstm_bwd_weights)
   size_t res_dzT_off, res_dzT_bytes;
+  // the layer-normalised cell (ln_layout): its statistics in the reserve behind cs (which holds the normalised state)
+  // and, in the workspace, the recurrent product's dh and the per-row sums of the norm-parameter gradients
+  bool ln;
+  size_t rstd_elems, rstdc_elems, dh_off, part_off, part_bytes;
+  size_t hstate_bytes;   // of the stepwise kernels' h state: ping-pong [2][2][B][H] (plain), [2][B][H] (layer norm)
+  bool hooks;            // the profile events and the phase hook fire in this call
 };
 
-// ABI version 1 callers pass the 32-byte descriptor (everything up to gemm_precision): the later fields read as 0
-static int load_desc(const nabu_blstm_desc *in, nabu_blstm_desc *out) {
+// ---------------------------------------------------------------------------
+// THE DESCRIPTOR as every entry point reads it: ABI version 1 callers pass the 32-byte descriptor (everything up to
+// gemm_precision), version 2 callers 44 bytes: the later fields read as 0.  The common checks, then those of the family.
+// (The layer-normalised entry points do not look at the packed-companion fields, x_bound and out_stack.)
+constexpr size_t LDS_MAX = 160 * 1024;   // gfx950: LDS of one workgroup
+static int check_units(const nabu_blstm_desc *d, const char *who) {
+  return d->H % 4 != 0 ? fail(NABU_EUNSUP, "%s: num_units must be a multiple of 4 (got %d)", who, d->H) : 0;
+}
+static int check_max_len(const nabu_blstm_desc *d, const char *who) {
+  return d->max_len < 0 || d->max_len > d->T ? fail(NABU_EINVAL, "%s: max_len out of range", who) : 0;
+}
+static int load_desc(const nabu_blstm_desc *in, nabu_blstm_desc *out, bool ln) {
+  const char *who = ln ? "blstm_ln" : "blstm";
   constexpr uint32_t V1 = 8 * sizeof(int32_t), V2 = 11 * sizeof(int32_t);
   if (!in || (in->size != sizeof(nabu_blstm_desc) && in->size != V1 && in->size != V2))
-    return fail(NABU_EINVAL, "blstm: bad descriptor size");
+    return fail(NABU_EINVAL, "%s: bad descriptor size", who);
   *out = nabu_blstm_desc{};
   memcpy(out, in, in->size);
   out->size = sizeof(nabu_blstm_desc);
-  if (!(out->x_bound >= 0.f) || out->x_bound > 3.0e38f) return fail(NABU_EINVAL, "blstm: x_bound must be finite and >= 0");
-  if (out->flags & ~NABU_BLSTM_FWD_ONLY) return fail(NABU_EINVAL, "blstm: unknown flag bits %d", out->flags);
-  if (out->recurrent_precision != NABU_REC_DEFAULT && out->recurrent_precision != NABU_REC_F32)
-    return fail(NABU_EINVAL, "blstm: recurrent_precision must be NABU_REC_DEFAULT or NABU_REC_F32");
-  if (out->out_stack < 0 || out->out_stack > 2) return fail(NABU_EINVAL, "blstm: out_stack must be 0, 1 or 2");
-  if (out->out_stack == 0) out->out_stack = 1;
-  if ((out->x_pk_rows == nullptr) != (out->x_pk_cols == nullptr) && !(out->flags & NABU_BLSTM_FWD_ONLY))
-    return fail(NABU_EINVAL, "blstm: x_pk_rows and x_pk_cols come as a pair (a forward-only descriptor may give the rows alone)");
+  nabu_blstm_desc *d = out;
+  if (d->flags & ~NABU_BLSTM_FWD_ONLY) return fail(NABU_EINVAL, "%s: unknown flag bits %d", who, d->flags);
+  if (d->recurrent_precision != NABU_REC_DEFAULT && d->recurrent_precision != NABU_REC_F32)
+    return fail(NABU_EINVAL, "%s: recurrent_precision must be NABU_REC_DEFAULT or NABU_REC_F32", who);
+  if (d->B <= 0 || d->T <= 0 || d->D <= 0 || d->H <= 0) return fail(NABU_EINVAL, "%s: non-positive dimension", who);
+  if (!ln) {
+    if (!(d->x_bound >= 0.f) || d->x_bound > 3.0e38f) return fail(NABU_EINVAL, "blstm: x_bound must be finite and >= 0");
+    if (d->out_stack < 0 || d->out_stack > 2) return fail(NABU_EINVAL, "blstm: out_stack must be 0, 1 or 2");
+    if (d->out_stack == 0) d->out_stack = 1;
+    if ((d->x_pk_rows == nullptr) != (d->x_pk_cols == nullptr) && !(d->flags & NABU_BLSTM_FWD_ONLY))
+      return fail(NABU_EINVAL, "blstm: x_pk_rows and x_pk_cols come as a pair (a forward-only descriptor may give the rows alone)");
+    NABU_TRY(check_units(d, who));
+    return check_max_len(d, who);
+  }
+  d->recurrent_precision = NABU_REC_DEFAULT;     // nothing of this family depends on it (nor the reserve's tag)
+  NABU_TRY(check_max_len(d, who));
+  if (d->mode != NABU_LSTM_AUTO && d->mode != NABU_LSTM_STEPWISE && d->mode != NABU_LSTM_PERSISTENT)
+    return fail(NABU_EINVAL, "blstm_ln: unknown mode %d", d->mode);
+  NABU_TRY(check_units(d, who));
+  if (d->mode == NABU_LSTM_PERSISTENT)
+    return fail(NABU_EUNSUP, "blstm_ln: the persistent recurrent kernels split the units of a row over workgroups and have "
+                "no per-step reduction across them — layer norm runs in the stepwise family (NABU_LSTM_AUTO or _STEPWISE)");
+  if (ln_lds_bytes(d->H) > LDS_MAX)
+    return fail(NABU_EUNSUP, "blstm_ln: num_units %d does not fit a workgroup's LDS (a row of 16 H resp. 11 H floats)", d->H);
   return 0;
 }
 // every entry point works on the normalised copy
 struct DescScope {
   nabu_blstm_desc d;
+  bool ln;
   int err;
-  explicit DescScope(const nabu_blstm_desc *in) : err(load_desc(in, &d)) {}
+  DescScope(const nabu_blstm_desc *in, bool ln_) : ln(ln_), err(load_desc(in, &d, ln_)) {}
 };
 static PersistPlan plan_of(const nabu_blstm_desc *d) {
   return lstm_persist_plan(d->B, d->T, d->D, d->H, d->max_len > 0 ? d->max_len : d->T, d->recurrent_precision == NABU_REC_F32);
@@ -293,8 +271,48 @@ static nabu_pk_gemm_desc pk_desc(int planes, int M, int N, int nkb, const void *
 
 static size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 
-static Layout make_layout(const nabu_blstm_desc *d) {
+// workspace of the plain-arithmetic dense products of a layer
+static size_t dense_ws_bytes(size_t B, size_t T, size_t D, size_t H) {
+  const int M = (int)(B * T);
+  size_t g = 0;
+  g = max_sz(g, nabu_gemm_ws_bytes(M, (int)(4 * H), (int)D));            // x·Wx
+  g = max_sz(g, nabu_gemm_ws_bytes(M, (int)D, (int)(4 * H)));            // dz·Wx^T
+  g = max_sz(g, nabu_gemm_ws_bytes((int)D, (int)(4 * H), M));            // x^T·dz
+  if (T > 1) g = max_sz(g, nabu_gemm_ws_bytes((int)H, (int)(4 * H), (int)(B * (T - 1))));
+  return g;
+}
+
+// THE LAYER-NORMALISED CELL'S PATH through the driver, stated once: plain products (no packed planes), no companions,
+// no persistent plan (the recurrence is the stepwise family of lstm_ln.hip), no profile events and no phase hook —
+// every field of those stays 0 — and its own reserve and workspace carve.  (No bias: nabu_blstm_ln_* pass none.)
+static Layout ln_layout(const nabu_blstm_desc *d) {
   Layout L = {};
+  const size_t B = d->B, T = d->T, D = d->D, H = d->H;
+  L.ln = true;
+  L.out_stack = 1;
+  L.fwd_only = (d->flags & NABU_BLSTM_FWD_ONLY) != 0;
+  L.gates_elems = B * T * 4 * H;
+  L.cs_elems = L.fwd_only ? 0 : B * T * H;
+  L.rstd_elems = L.fwd_only ? 0 : B * T * 4;
+  L.rstdc_elems = L.fwd_only ? 0 : B * T;
+  L.reserve_bytes = 2 * (L.gates_elems + L.cs_elems + L.rstd_elems + L.rstdc_elems) * sizeof(float);
+  size_t off = 0;
+  const size_t st = align_up(2 * B * H * sizeof(float), 256);
+  L.hstate_bytes = 2 * B * H * sizeof(float);
+  L.hstate_off = off; off += st;
+  L.cstate_off = off; off += st;
+  L.dh_off = off; off += st;
+  L.part_bytes = 20 * B * H * sizeof(float);
+  L.part_off = off; off += align_up(L.part_bytes, 256);
+  L.gemm_off = off; L.gemm_bytes = align_up(dense_ws_bytes(B, T, D, H), 256); off += L.gemm_bytes;
+  L.total = off;
+  return L;
+}
+
+static Layout make_layout(const nabu_blstm_desc *d, bool ln) {
+  if (ln) return ln_layout(d);
+  Layout L = {};
+  L.hooks = true;
   const size_t B = d->B, T = d->T, D = d->D, H = d->H;
   L.gates_elems = B * T * 4 * H;
   L.cs_elems = B * T * H;
@@ -307,13 +325,9 @@ static Layout make_layout(const nabu_blstm_desc *d) {
                       // ws[64..64+4*grid): XCC id of every block of the last forward launch (diagnostic)
   L.hstate_off = off; off += align_up(4 * B * H * sizeof(float), 256);
   L.cstate_off = off; off += align_up(2 * B * H * sizeof(float), 256);
-  size_t g = 0;
+  L.hstate_bytes = 4 * B * H * sizeof(float);
   const int M = (int)(B * T);
-  g = max_sz(g, nabu_gemm_ws_bytes(M, (int)(4 * H), (int)D));            // x·Wx
-  g = max_sz(g, nabu_gemm_ws_bytes(M, (int)D, (int)(4 * H)));            // dz·Wx^T
-  g = max_sz(g, nabu_gemm_ws_bytes((int)D, (int)(4 * H), M));            // x^T·dz
-  if (T > 1) g = max_sz(g, nabu_gemm_ws_bytes((int)H, (int)(4 * H), (int)(B * (T - 1))));
-  g = max_sz(g, nabu_colsum_ws_bytes(M, (int)(4 * H)));
+  const size_t g = max_sz(dense_ws_bytes(B, T, D, H), nabu_colsum_ws_bytes(M, (int)(4 * H)));
   L.gemm_off = off; L.gemm_bytes = align_up(g, 256); off += L.gemm_bytes;
   L.plan = plan_of(d);
   L.persist_bytes = align_up(L.plan.ws_bytes, 256);
@@ -422,16 +436,8 @@ static Layout make_layout(const nabu_blstm_desc *d) {
 // the row "maximum" of a packed companion: |h| <= 1 at the scale 2^14 the recurrent kernel splits its planes at
 static constexpr unsigned CMP_AMAX_BITS = 0x3F800000u;
 
-static int check_desc(const nabu_blstm_desc *d) {
-  if (d->B <= 0 || d->T <= 0 || d->D <= 0 || d->H <= 0) return fail(NABU_EINVAL, "blstm: non-positive dimension");
-  if (d->H % 4 != 0) return fail(NABU_EUNSUP, "blstm: num_units must be a multiple of 4 (got %d)", d->H);
-  if (d->max_len < 0 || d->max_len > d->T) return fail(NABU_EINVAL, "blstm: max_len out of range");
-  return 0;
-}
-
 // optional profiling hook: caller-owned events recorded around the recurrent kernels
 static thread_local hipEvent_t g_ev_begin = nullptr, g_ev_end = nullptr;
-#define NABU_PROFILE_MARK(ev, s) do { if (ev) NABU_HIP(hipEventRecord(ev, s)); } while (0)
 // optional hook between the recurrent kernel(s) and the dense products of nabu_blstm_bwd
 static thread_local nabu_phase_hook_t g_phase_hook = nullptr;
 static thread_local void *g_phase_user = nullptr;
@@ -453,9 +459,6 @@ struct ReserveTag {
   uint8_t pk_in, pk_rec, pk_whole;
   size_t reserve_bytes, res_dzT_off;
 };
-static std::mutex g_tag_mutex;
-static ReserveTag g_tags[4096];   // (least recently written is replaced: a reserve whose tag fell out is rejected, see nabu_hip.h)
-static uint64_t g_tag_serial = 0;
 static ReserveTag tag_of(const nabu_blstm_desc *d, const Layout &L, const void *reserve) {
   ReserveTag t = {};
   t.reserve = reserve; t.B = d->B; t.T = d->T; t.D = d->D; t.H = d->H; t.planes = L.pk_planes; t.flags = d->flags;
@@ -464,70 +467,197 @@ static ReserveTag tag_of(const nabu_blstm_desc *d, const Layout &L, const void *
   t.reserve_bytes = L.reserve_bytes; t.res_dzT_off = L.res_dzT_off;
   return t;
 }
-static void tag_store(const ReserveTag &t) {
-  std::lock_guard<std::mutex> lock(g_tag_mutex);
-  ReserveTag *slot = &g_tags[0];
-  for (ReserveTag &e : g_tags) {
-    if (e.reserve == t.reserve) { slot = &e; break; }
-    if (e.serial < slot->serial) slot = &e;          // least recently written
+// one table per family of entry points: the least recently written tag is replaced (a reserve whose tag fell out is
+// rejected, see nabu_hip.h), and a reserve of the other family's forward call is "not written" by this one's
+struct TagTable {
+  const char *writer;
+  ReserveTag *tags;
+  int n;
+  std::mutex mutex;
+  uint64_t serial;
+  void store(const ReserveTag &t) {
+    std::lock_guard<std::mutex> lock(mutex);
+    ReserveTag *slot = &tags[0];
+    for (ReserveTag *e = tags; e < tags + n; ++e) {
+      if (e->reserve == t.reserve) { slot = e; break; }
+      if (e->serial < slot->serial) slot = e;          // least recently written
+    }
+    *slot = t;
+    slot->serial = ++serial;
   }
-  *slot = t;
-  slot->serial = ++g_tag_serial;
-}
+  int check(const ReserveTag &want, const char *who) {
+    std::lock_guard<std::mutex> lock(mutex);
+    for (const ReserveTag *it = tags; it < tags + n; ++it) {
+      const ReserveTag &e = *it;
+      if (e.reserve != want.reserve || !e.serial) continue;
+      if (e.B == want.B && e.T == want.T && e.D == want.D && e.H == want.H && e.planes == want.planes && e.flags == want.flags &&
+          e.rec == want.rec && e.pk_in == want.pk_in && e.pk_rec == want.pk_rec && e.pk_whole == want.pk_whole &&
+          e.reserve_bytes == want.reserve_bytes && e.res_dzT_off == want.res_dzT_off)
+        return 0;
+      return fail(NABU_EINVAL, "%s: the reserve was written by %s under another layout (B %d T %d D %d H %d, %d planes, "
+                  "%zu bytes, flags %d; this call: B %d T %d D %d H %d, %d planes, %zu bytes) — descriptor or process precision "
+                  "changed between the passes", who, writer, e.B, e.T, e.D, e.H, e.planes, e.reserve_bytes, e.flags, want.B,
+                  want.T, want.D, want.H, want.planes, want.reserve_bytes);
+    }
+    return fail(NABU_EINVAL, "%s: no %s call of this process wrote this reserve (%p)", who, writer, want.reserve);
+  }
+};
+static ReserveTag g_tag_slots[4096], g_ln_tag_slots[1024];
+static TagTable g_tags = {"nabu_blstm_fwd", g_tag_slots, 4096}, g_ln_tags = {"nabu_blstm_ln_fwd", g_ln_tag_slots, 1024};
+static TagTable &tags_of(const Layout &L) { return L.ln ? g_ln_tags : g_tags; }
+static void tag_store(const nabu_blstm_desc *d, const Layout &L, const void *reserve) { tags_of(L).store(tag_of(d, L, reserve)); }
 static int tag_check(const nabu_blstm_desc *d, const Layout &L, const void *reserve, const char *who) {
   if (L.fwd_only) return fail(NABU_EINVAL, "%s: the descriptor says NABU_BLSTM_FWD_ONLY — its reserve has no room for a backward pass", who);
   const ReserveTag want = tag_of(d, L, reserve);
-  std::lock_guard<std::mutex> lock(g_tag_mutex);
-  for (const ReserveTag &e : g_tags) {
-    if (e.reserve != reserve || !e.serial) continue;
-    if (e.B == want.B && e.T == want.T && e.D == want.D && e.H == want.H && e.planes == want.planes && e.flags == want.flags &&
-        e.rec == want.rec && e.pk_in == want.pk_in && e.pk_rec == want.pk_rec && e.pk_whole == want.pk_whole &&
-        e.reserve_bytes == want.reserve_bytes && e.res_dzT_off == want.res_dzT_off)
-      return 0;
-    return fail(NABU_EINVAL, "%s: the reserve was written by nabu_blstm_fwd under another layout (B %d T %d D %d H %d, %d planes, "
-                "%zu bytes, flags %d; this call: B %d T %d D %d H %d, %d planes, %zu bytes) — descriptor or process precision "
-                "changed between the passes", who, e.B, e.T, e.D, e.H, e.planes, e.reserve_bytes, e.flags, want.B, want.T, want.D,
-                want.H, want.planes, want.reserve_bytes);
+  return tags_of(L).check(want, who);
+}
+
+// ---------------------------------------------------------------------------
+// THE CELL'S OWN ARGUMENTS of a layer call: bias and bias gradients (plain), or gamma / beta and their gradients (ln; null
+// in nabu_blstm_ln_bwd_weights, which reads none of them).  WHICH cell a call runs is said once, by the entry point's
+// DescScope, and kept in Layout::ln.
+struct Cell {
+  const nabu_blstm_ln_params *ln;
+  const float *bias[2];
+  float *dbias[2];
+};
+static Cell plain_cell(const float *bias_fw, const float *bias_bw, float *dbias_fw, float *dbias_bw) {
+  return Cell{nullptr, {bias_fw, bias_bw}, {dbias_fw, dbias_bw}};
+}
+static Cell ln_cell(const nabu_blstm_ln_params *ln) { return Cell{ln, {nullptr, nullptr}, {nullptr, nullptr}}; }
+
+// grads = a call that writes the bias resp. gamma / beta gradients
+static int check_cell(const Layout &L, const Cell &cell, bool grads, const char *who) {
+  if (!L.ln) {
+    NABU_CHECK_ARG(grads ? cell.dbias[0] && cell.dbias[1] : cell.bias[0] && cell.bias[1], "%s: null pointer", who);
+    return 0;
   }
-  return fail(NABU_EINVAL, "%s: no nabu_blstm_fwd call of this process wrote this reserve (%p)", who, reserve);
-}
-
-}  // namespace nabu
-
-using namespace nabu;
-
-extern "C" int nabu_blstm_set_profile_events(void *ev_begin, void *ev_end) {
-  g_ev_begin = static_cast<hipEvent_t>(ev_begin);
-  g_ev_end = static_cast<hipEvent_t>(ev_end);
-  return 0;
-}
-extern "C" int nabu_blstm_set_phase_hook(nabu_phase_hook_t fn, void *user) {
-  g_phase_hook = fn;
-  g_phase_user = user;
-  return 0;
-}
-extern "C" int nabu_persist_set_timeout_us(long long us) {
-  nabu::lstm_persist_set_timeout_us(us);
+  const nabu_blstm_ln_params *ln = cell.ln;
+  if (!ln || ln->size != sizeof(nabu_blstm_ln_params)) return fail(NABU_EINVAL, "%s: bad nabu_blstm_ln_params size", who);
+  for (int dir = 0; dir < 2; ++dir)
+    for (int k = 0; k < 5; ++k) {
+      if (!ln->gamma[dir][k] || !ln->beta[dir][k]) return fail(NABU_EINVAL, "%s: null gamma/beta pointer", who);
+      if (grads && (!ln->dgamma[dir][k] || !ln->dbeta[dir][k])) return fail(NABU_EINVAL, "%s: null dgamma/dbeta pointer", who);
+    }
   return 0;
 }
 
-extern "C" int nabu_blstm_uses_persistent(const nabu_blstm_desc *d_in) {
-  DescScope scope(d_in);
-  const nabu_blstm_desc *d = &scope.d;
-  if (scope.err || check_desc(d)) return 0;
-  return use_persistent(d, plan_of(d)) ? 1 : 0;
-}
+// one layer call as its stages see it
+struct Call {
+  const nabu_blstm_desc *d;
+  const Layout &L;
+  const Cell &cell;
+  int B, T, D, H, max_len;
+  const float *x;
+  const int32_t *len;
+  const float *kern[2];
+  float *gates[2], *cs[2];
+  char *reserve, *w;       // the reserve and the workspace, as bytes
+  nabu_stream_t stream;
+  hipStream_t s;
+  float *out;              // forward
+  const float *h, *d_out;  // backward: the forward call's out, its gradient
+  float *d_x, *dkern[2];
 
-extern "C" int nabu_blstm_pk_bytes(const nabu_blstm_desc *d_in, size_t bytes[5]) {
-  DescScope scope(d_in);
-  if (scope.err) return scope.err;
-  const nabu_blstm_desc *d = &scope.d;
-  if (int e = check_desc(d)) return e;
-  NABU_CHECK_ARG(bytes, "blstm_pk_bytes: null pointer");
-  const Layout L = make_layout(d);
-  for (int i = 0; i < 5; ++i) bytes[i] = L.cmp_bytes[i];
+  Call(const nabu_blstm_desc *d_, const Layout &L_, const Cell &cell_, const float *x_, const int32_t *len_,
+       const float *kernel_fw, const float *kernel_bw, void *reserve_, void *ws, nabu_stream_t stream_)
+      : d(d_), L(L_), cell(cell_), B(d_->B), T(d_->T), D(d_->D), H(d_->H), max_len(d_->max_len > 0 ? d_->max_len : d_->T),
+        x(x_), len(len_), kern{kernel_fw, kernel_bw}, reserve(static_cast<char *>(reserve_)), w(static_cast<char *>(ws)),
+        stream(stream_), s(static_cast<hipStream_t>(stream_)), out(nullptr), h(nullptr), d_out(nullptr), d_x(nullptr),
+        dkern{nullptr, nullptr} {
+    float *r = static_cast<float *>(reserve_);
+    gates[0] = r; gates[1] = r + L.gates_elems;
+    cs[0] = r + 2 * L.gates_elems; cs[1] = cs[0] + L.cs_elems;
+  }
+  float *gemm_ws() const { return reinterpret_cast<float *>(w + L.gemm_off); }
+  template <typename Tp> Tp *in_reserve(size_t off) const { return reinterpret_cast<Tp *>(reserve + off); }
+  int mark(hipEvent_t ev) const {     // profile event
+    if (L.hooks && ev) NABU_HIP(hipEventRecord(ev, s));
+    return 0;
+  }
+};
+
+// ---------------------------------------------------------------------------
+// stage: rows [max_len, T) of a [B, T, width] tensor, which the recurrence never visits, are zero
+static int zero_unvisited_frames(const Call &c, float *base, size_t width) {
+  if (c.max_len < c.T)
+    NABU_HIP(hipMemset2DAsync(base + (size_t)c.max_len * width, (size_t)c.T * width * sizeof(float), 0,
+                              (size_t)(c.T - c.max_len) * width * sizeof(float), c.B, c.s));
   return 0;
 }
+
+// stage: the time-batched input projections gates_d = x·Wx_d (+ b_d), on row-major operands
+static int project_input_plain(const Call &c) {
+  for (int dir = 0; dir < 2; ++dir)
+    NABU_TRY(nabu_gemm_ex(c.d->gemm_precision, 0, 0, c.B * c.T, 4 * c.H, c.D, 1.f, c.x, c.D, c.kern[dir], 4 * c.H, 0.f,
+                          c.gates[dir], 4 * c.H, c.cell.bias[dir], 0, 0, 0, c.gemm_ws(), c.L.gemm_bytes, c.stream));
+  return 0;
+}
+
+// ... on packed bf16-plane operands: X once, Wx^T of both cells as the rows of ONE operand; one product fills the gate
+// buffers of both directions.  clear_ring: the fill launch also clears the persistent launch's exchange ring
+// (PersistPlan::caller_ring_words); *ring_cleared says whether it did
+static int project_input_packed(const Call &c, bool clear_ring, bool *ring_cleared) {
+  const Layout &L = c.L;
+  const nabu_blstm_desc *d = c.d;
+  const int B = c.B, T = c.T, D = c.D, H = c.H;
+  const float *x = c.x;
+  hipStream_t s = c.s;
+  const int P = L.pk_planes, BT = B * T, G = 4 * H;
+  char *pk = c.w + L.pk_off;
+  const int rpBT = nabu_pk_rows_pad(BT), rpG = nabu_pk_rows_pad(2 * G), nkb = nabu_pk_kblocks(D, P);
+  uint32_t *ax = reinterpret_cast<uint32_t *>(pk + L.pk_ax), *aw = reinterpret_cast<uint32_t *>(pk + L.pk_aw);
+  if (P == 2) {
+    // f16x3: the frames' and the gate columns' largest magnitudes first.  The input: from the caller's bound where
+    // one is given (x_bound: the previous layer's LSTM outputs — no pass over x), measured otherwise (the features).
+    // The maxima the BACKWARD pass needs of the same tensors (columns of x, rows of Wx) come out of the same reads
+    // and wait in the reserve — unless no backward pass follows.
+    uint32_t *axT = L.fwd_only ? nullptr : c.in_reserve<uint32_t>(L.res_axT_off);
+    uint32_t *aw2 = L.fwd_only ? nullptr : c.in_reserve<uint32_t>(L.res_aw2_off);
+    const unsigned xb = L.x_pk ? CMP_AMAX_BITS : bound_bits(d->x_bound);     // (a packed companion: scale 2^14)
+    const int rpD = nabu_pk_rows_pad(D);
+    // (and the backward pass's row bound of h^T, |h| <= 1: a constant it would otherwise fill in a launch of its own)
+    uint32_t *ahT = L.res_ahT_off ? c.in_reserve<uint32_t>(L.res_ahT_off) : nullptr;
+    // and the recurrent launch's exchange ring (lstm_persist.h: caller_ring_words) — nothing between here and that
+    // launch writes the persistent kernels' part of the workspace
+    FillSeg fill[6] = {{ax, (size_t)rpBT, xb}, {aw, (size_t)rpG, 0u}, {axT, axT ? (size_t)rpD : 0, xb}, {aw2, aw2 ? (size_t)rpD : 0, 0u},
+                       {ahT, ahT ? (size_t)nabu_pk_rows_pad(H) : 0, L.hT_ext ? CMP_AMAX_BITS : bound_bits(1.0f)},
+                       {c.w + L.persist_off, clear_ring ? L.plan.caller_ring_words : 0, 0xFFFFFFFFu}};
+    NABU_TRY(multi_fill(fill, 6, s));
+    *ring_cleared = fill[5].words > 0;
+    if (!xb) NABU_TRY(nabu_pk_amax(x, D, BT, D, ax, axT, c.stream));
+    NABU_TRY(pk_amax_pair(c.kern[0], c.kern[1], G, D, G, aw2, aw, aw + G, nullptr, s));
+  }
+  // the input operand: the producer layer's forward kernel wrote it (x_pk_rows) — or one pass over x here
+  const void *xop = L.x_pk ? d->x_pk_rows : pk + L.pk_x;
+  if (!L.x_pk && L.res_xT_off) {
+    // ... and x^T for the backward pass's weight-gradient product out of the same read (kept in the reserve)
+    const int rpDx = nabu_pk_rows_pad(D);
+    NABU_TRY(pk_pack_both(P, x, D, BT, D, pk + L.pk_x, rpBT, 0, rpBT, nkb, c.reserve + L.res_xT_off, rpDx, 0, rpDx,
+                          nabu_pk_kblocks(BT, P), s, P == 2 ? ax : nullptr,
+                          P == 2 ? c.in_reserve<uint32_t>(L.res_axT_off) : nullptr));
+  } else if (!L.x_pk) {
+    NABU_TRY(pk_pack_any(P, 0, x, D, BT, D, pk + L.pk_x, rpBT, 0, 0, rpBT, nkb, 0, 0, ax, c.stream));
+  }
+  {   // Wx^T of both cells: one launch
+    PkPackReq rq[2];
+    for (int dir = 0; dir < 2; ++dir)
+      rq[dir] = PkPackReq{c.kern[dir], G, D, G, pk + L.pk_w, rpG, dir * G, 0, dir ? rpG - G : G, nkb, 0, 0, P == 2 ? aw : nullptr};
+    NABU_TRY(pk_pack_multi(P, 1, rq, 2, s));
+  }
+  nabu_pk_gemm_desc g = pk_desc(P, BT, 2 * G, nkb, xop, rpBT, pk + L.pk_w, rpG, c.gates[0], G);
+  g.C2[0] = c.gates[1]; g.n_split = G; g.bias = c.cell.bias[0]; g.bias2 = c.cell.bias[1];
+  if (P == 2) { g.a_amax[0] = ax; g.b_amax[0] = aw; g.direct = 2; }
+  return nabu_gemm_pk(&g, c.w + L.gemm_off, L.gemm_bytes, c.stream);
+}
+
+static int project_input(const Call &c, bool clear_ring, bool *ring_cleared) {
+  return c.L.pk_xw ? project_input_packed(c, clear_ring, ring_cleared) : project_input_plain(c);
+}
+
+// ---------------------------------------------------------------------------
+// stage: packed companions of the output (ABI version 3): out of the recurrent kernel itself where that is possible, by
+// the pack kernels behind the recurrence otherwise — complete on return either way
 static bool wants_companions(const nabu_blstm_desc *d, const Layout &L) {
   return ((d->out_pk_rows || d->out_pk_cols) && L.cmp_bytes[3] != 0) || L.hT_ext;
 }
@@ -561,435 +691,538 @@ static int emitted_by_kernel(const nabu_blstm_desc *d, const Layout &L) {
   if (!L.hT_ext) m &= ~4;
   return m;
 }
-extern "C" int nabu_blstm_emits_packed(const nabu_blstm_desc *d_in) {
-  DescScope scope(d_in);
-  const nabu_blstm_desc *d = &scope.d;
-  if (scope.err || check_desc(d)) return 0;
-  return emitted_by_kernel(d, make_layout(d));
+// which companions this call owes, who writes them and where
+struct Companions {
+  bool wanted;
+  bool want_out;
+  int by_kernel;      // bits written by the recurrent kernel itself (emitted_by_kernel)
+  int S, rpW, r0;
+  char *hTp[2];
+  EmitArgs em;
+};
+static Companions plan_companions(const Call &c) {
+  const Layout &L = c.L;
+  const nabu_blstm_desc *d = c.d;
+  Companions m = {};
+  m.wanted = wants_companions(d, L);
+  m.S = L.out_stack; m.rpW = nabu_pk_rows_pad(L.pk_whole ? c.D + c.H : c.H); m.r0 = L.pk_whole ? c.D : 0;
+  if (L.hT_ext) { m.hTp[0] = static_cast<char *>(d->hT_pk); m.hTp[1] = m.hTp[0] + L.cmp_bytes[2] / 2; }
+  m.want_out = (d->out_pk_rows || d->out_pk_cols) && L.cmp_bytes[3] != 0;
+  m.by_kernel = emitted_by_kernel(d, L);
+  if (m.by_kernel) {
+    EmitArgs &em = m.em;
+    em.x_rows = (m.want_out && (m.by_kernel & 1)) ? static_cast<char *>(d->out_pk_rows) : nullptr;
+    em.x_cols = (m.want_out && (m.by_kernel & 2)) ? static_cast<char *>(d->out_pk_cols) : nullptr;
+    em.hT[0] = (m.by_kernel & 4) ? m.hTp[0] : nullptr; em.hT[1] = (m.by_kernel & 4) ? m.hTp[1] : nullptr;
+    em.x_rows_pad = (unsigned)nabu_pk_rows_pad(c.B * c.T / m.S);
+    em.x_cols_pad = (unsigned)nabu_pk_rows_pad(2 * c.H * m.S);
+    em.hT_rows_pad = (unsigned)m.rpW;
+    em.hT_row0 = m.r0;
+    em.stack_shift = m.S == 2 ? 1 : 0;
+    em.b0 = 0;
+  }
+  return m;
+}
+// todo: the bits (0 rows, 1 transposed, 2 h^T) the recurrent kernel did not write
+static int companions_by_pack_kernels(const Call &c, const Companions &m, int todo) {
+  const Layout &L = c.L;
+  const nabu_blstm_desc *d = c.d;
+  const int B = c.B, T = c.T, H = c.H, S = m.S;
+  if (!m.wanted) return 0;
+  todo &= ((m.want_out && d->out_pk_rows) ? 1 : 0) | ((m.want_out && d->out_pk_cols) ? 2 : 0) | (L.hT_ext ? 4 : 0);
+  if (!todo) return 0;
+  uint32_t *am = reinterpret_cast<uint32_t *>(c.w + L.cmp_amax_off);
+  const FillSeg fill = {am, L.cmp_amax_bytes / 4, CMP_AMAX_BITS};
+  NABU_TRY(multi_fill(&fill, 1, c.s));
+  const int R = B * T / S, C = 2 * H * S;
+  if (todo & 1)
+    NABU_TRY(pk_pack_any(2, 0, c.out, C, R, C, d->out_pk_rows, nabu_pk_rows_pad(R), 0, 0, nabu_pk_rows_pad(R), nabu_pk_kblocks(C, 2), 0, 0, am, c.stream));
+  if (todo & 2)
+    NABU_TRY(pk_pack_any(2, 1, c.out, C, R, C, d->out_pk_cols, nabu_pk_rows_pad(C), 0, 0, nabu_pk_rows_pad(C), nabu_pk_kblocks(R, 2), 0, 0, am, c.stream));
+  if (todo & 4) {
+    PkPackReq rq[2];
+    for (int dir = 0; dir < 2; ++dir)
+      rq[dir] = PkPackReq{c.out + (size_t)dir * H, 2 * H, B * T, H, m.hTp[dir], m.rpW, m.r0, 0, m.rpW - m.r0, nabu_pk_kblocks(B * T, 2), T, dir ? 1 : -1, am};
+    NABU_TRY(pk_pack_multi(2, 1, rq, 2, c.s));
+  }
+  return 0;
 }
 
-extern "C" size_t nabu_blstm_reserve_bytes(const nabu_blstm_desc *d_in) {
-  DescScope scope(d_in);
+// ---------------------------------------------------------------------------
+// stage: the stepwise recurrence, one (plain) resp. two (layer norm) launches per timestep over zeroed states
+static LnArgs ln_args(const Call &c) {
+  const Layout &L = c.L;
+  LnArgs p = {};
+  p.B = c.B; p.T = c.T; p.D = c.D; p.H = c.H; p.max_len = c.max_len;
+  p.save = L.fwd_only ? 0 : 1;
+  p.len = c.len;
+  for (int dir = 0; dir < 2; ++dir) { p.kernel[dir] = c.kern[dir]; p.gates[dir] = c.gates[dir]; p.cs[dir] = c.cs[dir]; }
+  p.rstd[0] = c.cs[1] + L.cs_elems; p.rstd[1] = p.rstd[0] + L.rstd_elems;
+  p.rstdc[0] = p.rstd[1] + L.rstd_elems; p.rstdc[1] = p.rstdc[0] + L.rstdc_elems;
+  if (c.cell.ln)
+    for (int dir = 0; dir < 2; ++dir)
+      for (int k = 0; k < 5; ++k) { p.gamma[dir][k] = c.cell.ln->gamma[dir][k]; p.beta[dir][k] = c.cell.ln->beta[dir][k]; }
+  p.out = c.out; p.dout = c.d_out;
+  p.hstate = reinterpret_cast<float *>(c.w + L.hstate_off);
+  p.cstate = reinterpret_cast<float *>(c.w + L.cstate_off);
+  p.dh = reinterpret_cast<float *>(c.w + L.dh_off);
+  p.part = reinterpret_cast<float *>(c.w + L.part_off);
+  return p;
+}
+static StepArgs step_args(const Call &c) {
+  StepArgs p;
+  p.B = c.B; p.T = c.T; p.D = c.D; p.H = c.H; p.max_len = c.max_len; p.len = c.len;
+  for (int i = 0; i < 2; ++i) { p.kernel[i] = c.kern[i]; p.gates[i] = c.gates[i]; p.cs[i] = c.cs[i]; }
+  p.out = c.out; p.dout = c.d_out;
+  p.hstate = reinterpret_cast<float *>(c.w + c.L.hstate_off);
+  p.cstate = reinterpret_cast<float *>(c.w + c.L.cstate_off);
+  return p;
+}
+static dim3 step_grid(const Call &c) { return dim3((c.H + SU - 1) / SU, (c.B + SB - 1) / SB, 2); }
+
+static int stepwise_fwd(const Call &c) {
+  const size_t state = 2 * (size_t)c.B * c.H * sizeof(float);
+  NABU_HIP(hipMemsetAsync(c.w + c.L.hstate_off, 0, c.L.hstate_bytes, c.s));
+  NABU_HIP(hipMemsetAsync(c.w + c.L.cstate_off, 0, state, c.s));
+  if (c.L.ln) return ln_recurrence_fwd(ln_args(c), c.s);
+  const StepArgs p = step_args(c);
+  const size_t shm = ((size_t)SB * c.H + SB * 4 * SU) * sizeof(float);
+  if (shm > 64 * 1024)
+    NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(lstm_step_fwd_kernel),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+  NABU_TRY(c.mark(g_ev_begin));
+  for (int t = 0; t < c.max_len; ++t) hipLaunchKernelGGL(lstm_step_fwd_kernel, step_grid(c), dim3(STEP_NT), shm, c.s, p, t);
+  NABU_LAUNCH_CHECK();
+  return c.mark(g_ev_end);
+}
+
+static int stepwise_bwd(const Call &c) {
+  NABU_HIP(hipMemsetAsync(c.w + c.L.cstate_off, 0, 2 * (size_t)c.B * c.H * sizeof(float), c.s));   // the dc carry
+  if (c.L.ln) {
+    NABU_HIP(hipMemsetAsync(c.w + c.L.part_off, 0, c.L.part_bytes, c.s));
+    return ln_recurrence_bwd(ln_args(c), c.s);
+  }
+  const StepArgs p = step_args(c);
+  for (int t = c.max_len - 1; t >= 0; --t) hipLaunchKernelGGL(lstm_step_bwd_kernel, step_grid(c), dim3(STEP_NT), 0, c.s, p, t);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
+
+// stage: the forward recurrence and the companions behind it.  Persistent where the plan has a kernel for the shape;
+// a grid that cannot be co-resident on this device (the occupancy check before the launch says NABU_EUNSUP) steps
+// instead under NABU_LSTM_AUTO
+static int recurrence_fwd(const Call &c, bool projected, bool ring_cleared) {
+  const Layout &L = c.L;
+  const Companions m = plan_companions(c);
+  if (use_persistent(c.d, L.plan)) {
+    const bool fuse_in = L.plan.fuses_input;
+    NABU_TRY(c.mark(g_ev_begin));
+    const int e = lstm_persist_fwd(L.plan, c.len, c.kern, c.gates, c.cs, c.out, reinterpret_cast<int *>(c.w), c.w + L.persist_off,
+                                   L.persist_bytes, c.s, ring_cleared, fuse_in ? c.x : nullptr, fuse_in ? c.cell.bias : nullptr,
+                                   L.xws_bytes ? c.w + L.xws_off : nullptr, m.by_kernel ? &m.em : nullptr);
+    if (!(e == NABU_EUNSUP && c.d->mode == NABU_LSTM_AUTO)) {
+      if (e) return e;
+      NABU_TRY(c.mark(g_ev_end));
+      return companions_by_pack_kernels(c, m, 7 & ~m.by_kernel);
+    }
+    if (!projected) {   // the step kernels read the projection from the gate buffers
+      bool unused = false;
+      NABU_TRY(project_input(c, false, &unused));
+    }
+  }
+  NABU_TRY(stepwise_fwd(c));
+  return companions_by_pack_kernels(c, m, 7);
+}
+
+static const char *const ENTRY[2][4] = {{"blstm_fwd", "blstm_bwd_data", "blstm_bwd_weights", "blstm_bwd"},
+                                        {"blstm_ln_fwd", "blstm_ln_bwd_data", "blstm_ln_bwd_weights", "blstm_ln_bwd"}};
+
+// THE FORWARD PASS of a layer, either cell
+static int blstm_forward(const DescScope &scope, const Cell &cell, const float *x, const int32_t *len, const float *kernel_fw,
+                         const float *kernel_bw, float *out, void *reserve, void *ws, size_t ws_bytes, nabu_stream_t stream) {
+  if (scope.err) return scope.err;
   const nabu_blstm_desc *d = &scope.d;
-  if (scope.err || check_desc(d)) return 0;
-  return make_layout(d).reserve_bytes;
+  const char *who = ENTRY[scope.ln][0];
+  const Layout L = make_layout(d, scope.ln);
+  NABU_CHECK_ARG(x && len && kernel_fw && kernel_bw && out && reserve && ws, "%s: null pointer", who);
+  NABU_TRY(check_cell(L, cell, false, who));
+  if (ws_bytes < L.total) return fail(NABU_EWS, "%s: workspace %zu < %zu", who, ws_bytes, L.total);
+  if (d->mode == NABU_LSTM_PERSISTENT && !L.plan.supported)
+    return fail(NABU_EUNSUP, "%s: persistent kernel does not support B=%d H=%d", who, d->B, d->H);
+  tag_store(d, L, reserve);
+  Call c(d, L, cell, x, len, kernel_fw, kernel_bw, reserve, ws, stream);
+  c.out = out;
+  // narrow input (first layer): the persistent kernel projects its input itself (lstm_persist.hip, XK) — no product here
+  const bool persistent = use_persistent(d, L.plan);
+  const bool projected = !(persistent && L.plan.fuses_input);
+  bool ring_cleared = false;
+  if (projected) NABU_TRY(project_input(c, persistent, &ring_cleared));
+  NABU_TRY(zero_unvisited_frames(c, out, 2 * (size_t)c.H));
+  return recurrence_fwd(c, projected, ring_cleared);
+}
+
+// ---------------------------------------------------------------------------
+// what the persistent backward kernels leave behind besides dz
+struct PersistOut {
+  float *db_part;     // bias-gradient partials [db_rows][2][4H]; null: the recurrence stepped
+  int db_rows;
+  bool db_done;       // the bias gradients were summed by the launch that read the maxima
+  uint32_t *rowmax;   // f16x3 with an input gradient: every workgroup's row maxima of dz, asked for in the workspace
+  bool rowmax_done;
+};
+
+// stage: the backward recurrence (dz in place over the activations), with the forward pass's fallback rule
+static int recurrence_bwd(const Call &c, PersistOut *po) {
+  const Layout &L = c.L;
+  NABU_TRY(c.mark(g_ev_begin));
+  bool stepwise = !use_persistent(c.d, L.plan);
+  if (!stepwise) {
+    const int e = lstm_persist_bwd(L.plan, c.len, c.kern, c.gates, c.cs, c.d_out, reinterpret_cast<int *>(c.w), c.w + L.persist_off,
+                                   L.persist_bytes, &po->db_part, &po->db_rows, c.s, po->rowmax, &po->rowmax_done);
+    if (e == NABU_EUNSUP && c.d->mode == NABU_LSTM_AUTO) { stepwise = true; po->db_part = nullptr; po->db_rows = 0; po->rowmax_done = false; }
+    else if (e) return e;
+  }
+  if (stepwise) NABU_TRY(stepwise_bwd(c));
+  NABU_TRY(c.mark(g_ev_end));
+  if (L.hooks && g_phase_hook) g_phase_hook(g_phase_user);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// stages: the backward products on packed bf16-plane operands (gemm_pk.hip).  dZ^T of both cells is one operand
+// [8H, BT] (in the reserve): the weight gradients of both cells are column ranges of one product (input part) resp. a
+// batch of two (recurrent part)
+struct PackedBwd {
+  int P, G, M, rpBT, rpG, rpD, nkbT, nkb2, kbG;
+  char *pk, *dzTp;
+  // f16x3 (P = 2): row maxima of every operand — measured (dz, the weights, x) or known (|h| < 1)
+  uint32_t *adz, *axT, *aw2, *ahT[2], *adzT;
+  explicit PackedBwd(const Call &c) {
+    const Layout &L = c.L;
+    P = L.pk_planes; G = 4 * c.H; M = c.B * c.T;
+    pk = c.w + L.pk_off;
+    dzTp = c.reserve + L.res_dzT_off;
+    rpBT = nabu_pk_rows_pad(M); rpG = nabu_pk_rows_pad(2 * G); rpD = nabu_pk_rows_pad(c.D);
+    nkbT = nabu_pk_kblocks(M, P);
+    nkb2 = nabu_pk_kblocks(2 * G, P); kbG = G / 16;
+    adz = reinterpret_cast<uint32_t *>(pk + L.pk_adz);
+    axT = c.in_reserve<uint32_t>(L.res_axT_off);    // from the forward pass
+    aw2 = c.in_reserve<uint32_t>(L.res_aw2_off);
+    ahT[0] = reinterpret_cast<uint32_t *>(pk + L.pk_ahT[0]); ahT[1] = reinterpret_cast<uint32_t *>(pk + L.pk_ahT[1]);
+    adzT = c.in_reserve<uint32_t>(L.res_adzT_off);
+  }
+};
+
+// data part: dz packed transposed (and row-major where dx follows: both packs from one read of dz)
+static int pack_dz(const Call &c, const PackedBwd &k, PersistOut *po) {
+  const Layout &L = c.L;
+  const int P = k.P, G = k.G, M = k.M, H = c.H;
+  const bool both = c.d_x && L.pk_in;
+  if (P == 2) {
+    // the maxima of dz: its rows' over BOTH cells (the row scale of dZ as [BT, 8H]) and its columns'
+    if (po->db_part && (!both || po->rowmax_done)) {
+      // the persistent kernel kept them: the gate columns' maxima per unit next to its bias-gradient partials, the
+      // frames' per workgroup in the workspace (only asked for where an input gradient follows) — no read of dz
+      // (the bias gradients — the sum of the same units' partial rows — come out of the same launch)
+      NABU_TRY(pk_amax_from_persist(M, k.rpBT, c.T, c.max_len, 2 * (H / 16), po->rowmax, both ? k.adz : nullptr, po->db_rows,
+                                    2 * G, po->db_part + lstm_persist_db_floats(c.B, H), 2 * G, k.adzT, c.s, po->db_part,
+                                    c.cell.dbias[0], c.cell.dbias[1]));
+      po->db_done = true;
+    } else {
+      const FillSeg fill[2] = {{k.adz, both ? (size_t)k.rpBT : 0, 0u}, {k.adzT, (size_t)k.rpG, 0u}};
+      NABU_TRY(multi_fill(fill, 2, c.s));
+      NABU_TRY(pk_amax_pair(c.gates[0], c.gates[1], G, M, G, both ? k.adz : nullptr, k.adzT, k.adzT + G, nullptr, c.s));
+    }
+  }
+  for (int dir = 0; dir < 2; ++dir) {
+    if (both)
+      NABU_TRY(pk_pack_both(P, c.gates[dir], G, M, G, k.pk + L.pk_dz, k.rpBT, dir * k.kbG, k.rpBT, dir ? k.nkb2 - k.kbG : k.kbG,
+                            k.dzTp, k.rpG, dir * G, dir ? k.rpG - G : G, k.nkbT, c.s, k.adz, k.adzT));
+    else
+      NABU_TRY(pk_pack_any(P, 1, c.gates[dir], G, M, G, k.dzTp, k.rpG, dir * G, 0, dir ? k.rpG - G : G, k.nkbT, 0, 0, k.adzT,
+                           c.stream));
+  }
+  return 0;
+}
+
+// dx = [dZ_fw | dZ_bw] · [Wx_fw | Wx_bw]^T: the two cells are two ranges of ONE reduction
+static int packed_dx(const Call &c, const PackedBwd &k) {
+  const Layout &L = c.L;
+  const int P = k.P, G = k.G, D = c.D;
+  PkPackReq rq[2];
+  for (int dir = 0; dir < 2; ++dir)
+    rq[dir] = PkPackReq{c.kern[dir], G, D, G, k.pk + L.pk_w2, k.rpD, 0, dir * k.kbG, k.rpD, dir ? k.nkb2 - k.kbG : k.kbG, 0, 0,
+                        P == 2 ? k.aw2 : nullptr};
+  NABU_TRY(pk_pack_multi(P, 0, rq, 2, c.s));
+  nabu_pk_gemm_desc g = pk_desc(P, k.M, D, k.nkb2, k.pk + L.pk_dz, k.rpBT, k.pk + L.pk_w2, k.rpD, c.d_x, D);
+  if (P == 2) { g.a_amax[0] = k.adz; g.b_amax[0] = k.aw2; g.direct = 2; }
+  return nabu_gemm_pk(&g, c.w + L.gemm_off, L.gemm_bytes, c.stream);
+}
+
+// dWx of both cells = x^T · dZ^T's two column ranges
+static int packed_dWx(const Call &c, const PackedBwd &k) {
+  const Layout &L = c.L;
+  const int P = k.P, G = k.G, D = c.D;
+  // x^T: the producer layer's forward kernel wrote it (x_pk_cols; its row maxima were set by this layer's forward
+  // call) — or, since the forward call packs x anyway, from that call (res_xT_off) — or one transposing pass over x here
+  const void *xTop = L.x_pk ? c.d->x_pk_cols : L.res_xT_off ? c.reserve + L.res_xT_off : k.pk + L.pk_xT;
+  if (!L.x_pk && !L.res_xT_off)
+    NABU_TRY(pk_pack_any(P, 1, c.x, D, k.M, D, k.pk + L.pk_xT, k.rpD, 0, 0, k.rpD, k.nkbT, 0, 0, k.axT, c.stream));
+  nabu_pk_gemm_desc g = pk_desc(P, D, 2 * G, k.nkbT, xTop, k.rpD, k.dzTp, k.rpG, c.dkern[0], G);
+  g.C2[0] = c.dkern[1]; g.n_split = G;
+  // direct = 2: the three plane products chained directly into the accumulators wherever that rounds less often
+  // than the exact-fp32 kernel would (gemm_pk.hip; 0.6-0.8 x its error at these shapes, tests/test_hip_gemm_pk.py)
+  if (P == 2) { g.a_amax[0] = k.axT; g.b_amax[0] = k.adzT; g.direct = 2; }
+  return nabu_gemm_pk(&g, c.w + L.gemm_off, L.gemm_bytes, c.stream);
+}
+
+// dWh = h_{t-1}^T · dZ: the forward cell pairs dz[b,t] with out[b,t-1,:H], the backward cell with out[b,t+1,H:].
+// Narrow input (the first layer, D = 40; pk_whole): x^T sits in front of h^T in the same operand and the whole kernel
+// gradient [(D+H), 4H] of a cell is ONE product (its dWx alone cost more on the in-kernel-split kernel)
+static int packed_dWh(const Call &c, const PackedBwd &k) {
+  const Layout &L = c.L;
+  const int P = k.P, G = k.G, M = k.M, D = c.D, H = c.H, T = c.T;
+  const float *x = c.x, *out = c.h;
+  const int r0 = L.pk_whole ? D : 0, Mw = r0 + H, rpW = nabu_pk_rows_pad(Mw);
+  // h^T: in the caller's hT_pk, written by the forward call (ABI version 3) — or packed here from `out`
+  char *hTb[2] = {k.pk + L.pk_hT[0], k.pk + L.pk_hT[1]};
+  if (L.hT_ext) { hTb[0] = static_cast<char *>(c.d->hT_pk); hTb[1] = hTb[0] + L.cmp_bytes[2] / 2; }
+  uint32_t *ahT[2] = {k.ahT[0], k.ahT[1]};
+  if (P == 2 && L.res_ahT_off) {   // |h| <= 1: the bound sits in the reserve since the forward call (both cells share it)
+    ahT[0] = ahT[1] = c.in_reserve<uint32_t>(L.res_ahT_off);
+  } else if (P == 2) {   // |h| <= 1 by construction (o · tanh c): one fill for both cells; the input features are measured
+    const unsigned hb = L.hT_ext ? CMP_AMAX_BITS : bound_bits(1.0f);
+    const FillSeg fill[4] = {{ahT[0], (size_t)r0, 0u}, {ahT[0] + r0, (size_t)(rpW - r0), hb},
+                             {ahT[1], (size_t)r0, 0u}, {ahT[1] + r0, (size_t)(rpW - r0), hb}};
+    // (r0 = D is a multiple of 4: every region starts 16-byte aligned)
+    NABU_TRY(multi_fill(fill, 4, c.s));
+    if (L.pk_whole) NABU_TRY(pk_amax_pair(x, nullptr, D, M, D, nullptr, ahT[0], nullptr, ahT[1], c.s));
+  }
+  {   // [x^T ;] h^T of both cells: one launch
+    PkPackReq rq[4];
+    int n = 0;
+    for (int dir = 0; dir < 2; ++dir) {
+      const uint32_t *am = P == 2 ? ahT[dir] : nullptr;
+      if (L.pk_whole) rq[n++] = PkPackReq{x, D, M, D, hTb[dir], rpW, 0, 0, D, k.nkbT, 0, 0, am};
+      if (!L.hT_ext)
+        rq[n++] = PkPackReq{out + (size_t)dir * H, 2 * H, M, H, hTb[dir], rpW, r0, 0, rpW - r0, k.nkbT, T, dir ? 1 : -1, am};
+    }
+    if (n) NABU_TRY(pk_pack_multi(P, 1, rq, n, c.s));
+  }
+  nabu_pk_gemm_desc g = pk_desc(P, Mw, G, k.nkbT, hTb[0], rpW, k.dzTp, k.rpG, c.dkern[0] + (size_t)(D - r0) * G, G);
+  g.nbatch = 2; g.A[1] = hTb[1]; g.B[1] = k.dzTp + (size_t)G * 32; g.C[1] = c.dkern[1] + (size_t)(D - r0) * G;
+  if (P == 2) { g.a_amax[0] = ahT[0]; g.a_amax[1] = ahT[1]; g.b_amax[0] = k.adzT; g.b_amax[1] = k.adzT + G; g.direct = 2; }
+  return nabu_gemm_pk(&g, c.w + L.gemm_off, L.gemm_bytes, c.stream);
+}
+
+static int packed_products(int parts, const Call &c, PersistOut *po) {
+  const Layout &L = c.L;
+  const PackedBwd k(c);
+  if (parts & 1) {
+    NABU_TRY(pack_dz(c, k, po));
+    if (c.d_x && L.pk_in) NABU_TRY(packed_dx(c, k));
+  }
+  if ((parts & 2) && L.pk_in) NABU_TRY(packed_dWx(c, k));
+  if ((parts & 2) && L.pk_rec) NABU_TRY(packed_dWh(c, k));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// stages: one direction's products on row-major operands — whatever of them the packed path did not take — and the
+// plain cell's bias gradient
+static int plain_weight_products(const Call &c, int dir) {
+  const Layout &L = c.L;
+  const int B = c.B, T = c.T, D = c.D, H = c.H, M = B * T;
+  // dWx = x^T · dz
+  if (!L.pk_in && !L.pk_whole)
+    NABU_TRY(nabu_gemm_ex(c.d->gemm_precision, 1, 0, D, 4 * H, M, 1.f, c.x, D, c.gates[dir], 4 * H, 0.f, c.dkern[dir], 4 * H,
+                          nullptr, 0, 0, 0, c.gemm_ws(), L.gemm_bytes, c.stream));
+  // dWh = h_{prev}^T · dz : fw pairs (out[b,t-1,:H], dz[b,t]); bw pairs (out[b,t+1,H:], dz[b,t]); no pair at T = 1
+  if (L.pk_rec) return 0;
+  float *dWh = c.dkern[dir] + (size_t)D * 4 * H;
+  if (T == 1) {
+    NABU_HIP(hipMemsetAsync(dWh, 0, (size_t)H * 4 * H * sizeof(float), c.s));
+    return 0;
+  }
+  const float *A = dir == 0 ? c.h : c.h + H + (size_t)2 * H;
+  const float *Bm = dir == 0 ? c.gates[0] + (size_t)4 * H : c.gates[1];
+  return nabu_gemm_f32(1, 0, H, 4 * H, B * (T - 1), 1.f, A, 2 * H, Bm, 4 * H, 0.f, dWh, 4 * H, nullptr, T - 1,
+                       (long long)T * 2 * H, (long long)T * 4 * H, c.gemm_ws(), L.gemm_bytes, c.stream);
+}
+static int plain_data_products(const Call &c, int dir, const PersistOut &po) {
+  const Layout &L = c.L;
+  const int D = c.D, H = c.H, M = c.B * c.T;
+  if (!c.L.ln) {
+    // db = column sums of dz: the persistent kernel already summed them per unit (one launch adds the few partial
+    // rows of both cells)
+    if (po.db_part) {
+      if (!dir && !po.db_done) NABU_TRY(colsum_pair(po.db_rows, 4 * H, po.db_part, 2 * 4 * H, c.cell.dbias[0], c.cell.dbias[1], c.s));
+    } else {
+      NABU_TRY(nabu_colsum_f32(M, 4 * H, c.gates[dir], 4 * H, 0.f, c.cell.dbias[dir], c.gemm_ws(), L.gemm_bytes, c.stream));
+    }
+  }
+  // dx (+)= dz · Wx^T
+  if (c.d_x && !L.pk_in)
+    NABU_TRY(nabu_gemm_ex(c.d->gemm_precision, 0, 1, M, D, 4 * H, 1.f, c.gates[dir], 4 * H, c.kern[dir], 4 * H,
+                          dir == 0 ? 0.f : 1.f, c.d_x, D, nullptr, 0, 0, 0, c.gemm_ws(), L.gemm_bytes, c.stream));
+  return 0;
+}
+
+// THE BACKWARD PASS of a layer, either cell.  parts: 1 = data (recurrence backward, bias resp. norm-parameter
+// gradients, input gradient, the packs of dz), 2 = weights (dWx, dWh from the dz the data part left in the reserve),
+// 3 = both
+static int blstm_backward(int parts, const DescScope &scope, const Cell &cell, const float *x, const int32_t *len,
+                          const float *kernel_fw, const float *kernel_bw, const float *out, const float *d_out, void *reserve,
+                          float *d_x, float *dkernel_fw, float *dkernel_bw, void *ws, size_t ws_bytes, nabu_stream_t stream) {
+  if (scope.err) return scope.err;
+  const nabu_blstm_desc *d = &scope.d;
+  const char *who = ENTRY[scope.ln][parts];
+  const Layout L = make_layout(d, scope.ln);
+  NABU_CHECK_ARG(x && len && out && reserve && ws, "%s: null pointer", who);
+  if (parts & 1) {
+    NABU_CHECK_ARG(kernel_fw && kernel_bw && d_out, "%s: null pointer", who);
+    NABU_TRY(check_cell(L, cell, true, who));
+  }
+  if (parts & 2) NABU_CHECK_ARG(dkernel_fw && dkernel_bw, "%s: null pointer", who);
+  NABU_TRY(tag_check(d, L, reserve, who));
+  if (ws_bytes < L.total) return fail(NABU_EWS, "%s: workspace %zu < %zu", who, ws_bytes, L.total);
+  if (d->mode == NABU_LSTM_PERSISTENT && !L.plan.supported)
+    return fail(NABU_EUNSUP, "%s: persistent kernel does not support B=%d H=%d", who, d->B, d->H);
+  Call c(d, L, cell, x, len, kernel_fw, kernel_bw, reserve, ws, stream);
+  c.h = out; c.d_out = d_out; c.d_x = d_x; c.dkern[0] = dkernel_fw; c.dkern[1] = dkernel_bw;
+
+  PersistOut po = {};
+  if (L.pk_planes == 2 && L.pk_in && d_x && L.pk_rowmax_bytes) po.rowmax = reinterpret_cast<uint32_t *>(c.w + L.pk_off + L.pk_rowmax);
+  if (parts & 1) {
+    // dz rows of frames never visited by the recurrence must be zero
+    for (int dir = 0; dir < 2; ++dir) NABU_TRY(zero_unvisited_frames(c, c.gates[dir], 4 * (size_t)c.H));
+    NABU_TRY(recurrence_bwd(c, &po));
+    if (L.ln) NABU_TRY(ln_param_grads(ln_args(c), cell.ln, c.s));
+  }
+  // weight / input gradients from dz (now stored in gates[])
+  if (L.pk_planes) NABU_TRY(packed_products(parts, c, &po));
+  // The same two per-direction functions in two orders, ONLY so that every launch stays where the two former drivers
+  // had it (LABNOTES.md, section 15): the layer-norm driver finished the data part before the weight part, the plain
+  // one walked the directions once.  All of these products are independent but for dx of the second direction, which
+  // accumulates onto the first's in either order.
+  if (L.ln) {
+    for (int dir = 0; dir < 2 && (parts & 1); ++dir) NABU_TRY(plain_data_products(c, dir, po));
+    for (int dir = 0; dir < 2 && (parts & 2); ++dir) NABU_TRY(plain_weight_products(c, dir));
+  } else {                  // one walk over the directions
+    for (int dir = 0; dir < 2; ++dir) {
+      if (parts & 2) NABU_TRY(plain_weight_products(c, dir));
+      if (parts & 1) NABU_TRY(plain_data_products(c, dir, po));
+    }
+  }
+  return 0;
+}
+
+}  // namespace nabu
+
+using namespace nabu;
+
+extern "C" int nabu_blstm_set_profile_events(void *ev_begin, void *ev_end) {
+  g_ev_begin = static_cast<hipEvent_t>(ev_begin);
+  g_ev_end = static_cast<hipEvent_t>(ev_end);
+  return 0;
+}
+extern "C" int nabu_blstm_set_phase_hook(nabu_phase_hook_t fn, void *user) {
+  g_phase_hook = fn;
+  g_phase_user = user;
+  return 0;
+}
+extern "C" int nabu_persist_set_timeout_us(long long us) {
+  nabu::lstm_persist_set_timeout_us(us);
+  return 0;
+}
+
+// ---- the queries: 0 for a descriptor the family refuses
+extern "C" int nabu_blstm_uses_persistent(const nabu_blstm_desc *d_in) {
+  const DescScope scope(d_in, false);
+  return !scope.err && use_persistent(&scope.d, plan_of(&scope.d)) ? 1 : 0;
+}
+extern "C" int nabu_blstm_pk_bytes(const nabu_blstm_desc *d_in, size_t bytes[5]) {
+  const DescScope scope(d_in, false);
+  if (scope.err) return scope.err;
+  NABU_CHECK_ARG(bytes, "blstm_pk_bytes: null pointer");
+  const Layout L = make_layout(&scope.d, false);
+  for (int i = 0; i < 5; ++i) bytes[i] = L.cmp_bytes[i];
+  return 0;
+}
+extern "C" int nabu_blstm_emits_packed(const nabu_blstm_desc *d_in) {
+  const DescScope scope(d_in, false);
+  return scope.err ? 0 : emitted_by_kernel(&scope.d, make_layout(&scope.d, false));
+}
+extern "C" size_t nabu_blstm_reserve_bytes(const nabu_blstm_desc *d_in) {
+  const DescScope scope(d_in, false);
+  return scope.err ? 0 : make_layout(&scope.d, false).reserve_bytes;
 }
 extern "C" size_t nabu_blstm_ws_bytes(const nabu_blstm_desc *d_in) {
-  DescScope scope(d_in);
-  const nabu_blstm_desc *d = &scope.d;
-  if (scope.err || check_desc(d)) return 0;
-  return make_layout(d).total;
+  const DescScope scope(d_in, false);
+  return scope.err ? 0 : make_layout(&scope.d, false).total;
+}
+extern "C" size_t nabu_blstm_ln_reserve_bytes(const nabu_blstm_desc *d_in) {
+  const DescScope scope(d_in, true);
+  return scope.err ? 0 : make_layout(&scope.d, true).reserve_bytes;
+}
+extern "C" size_t nabu_blstm_ln_ws_bytes(const nabu_blstm_desc *d_in) {
+  const DescScope scope(d_in, true);
+  return scope.err ? 0 : make_layout(&scope.d, true).total;
 }
 
+// ---- the plain cell
 extern "C" int nabu_blstm_fwd(const nabu_blstm_desc *d_in, const float *x, const int32_t *len,
                               const float *kernel_fw, const float *bias_fw,
                               const float *kernel_bw, const float *bias_bw, float *out,
                               void *reserve, void *ws, size_t ws_bytes, nabu_stream_t stream) {
-  DescScope scope(d_in);
-  if (scope.err) return scope.err;
-  const nabu_blstm_desc *d = &scope.d;
-  if (int e = check_desc(d)) return e;
-  NABU_CHECK_ARG(x && len && kernel_fw && bias_fw && kernel_bw && bias_bw && out && reserve && ws,
-                 "blstm_fwd: null pointer");
-  const Layout L = make_layout(d);
-  if (ws_bytes < L.total) return fail(NABU_EWS, "blstm_fwd: workspace %zu < %zu", ws_bytes, L.total);
-  if (d->mode == NABU_LSTM_PERSISTENT && !L.plan.supported)
-    return fail(NABU_EUNSUP, "blstm_fwd: persistent kernel does not support B=%d H=%d", d->B, d->H);
-  tag_store(tag_of(d, L, reserve));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int B = d->B, T = d->T, D = d->D, H = d->H;
-  const int max_len = d->max_len > 0 ? d->max_len : T;
-  float *r = static_cast<float *>(reserve);
-  float *gates[2] = {r, r + L.gates_elems};
-  float *cs[2] = {r + 2 * L.gates_elems, r + 2 * L.gates_elems + L.cs_elems};
-  char *w = static_cast<char *>(ws);
-  const float *kern[2] = {kernel_fw, kernel_bw};
-  const float *bias[2] = {bias_fw, bias_bw};
-
-  // narrow input (first layer): the persistent kernel projects its input itself (lstm_persist.hip, XK) — no product here
-  const bool persistent = use_persistent(d, L.plan);
-  const bool fuse_in = persistent && L.plan.fuses_input;
-  bool ring_cleared = false;      // the projection's fill has also cleared the exchange ring (PersistPlan::caller_ring_words)
-  auto input_projection = [&]() -> int {
-  // time-batched input projections (MFMA): gates_d = x·Wx_d + b_d
-  if (L.pk_xw) {
-    // packed bf16-plane operands: X once, Wx^T of both cells as the rows of ONE operand; one product fills the
-    // gate buffers of both directions
-    const int P = L.pk_planes, BT = B * T, G = 4 * H;
-    char *pk = w + L.pk_off;
-    const int rpBT = nabu_pk_rows_pad(BT), rpG = nabu_pk_rows_pad(2 * G), nkb = nabu_pk_kblocks(D, P);
-    uint32_t *ax = reinterpret_cast<uint32_t *>(pk + L.pk_ax), *aw = reinterpret_cast<uint32_t *>(pk + L.pk_aw);
-    if (P == 2) {
-      // f16x3: the frames' and the gate columns' largest magnitudes first.  The input: from the caller's bound where
-      // one is given (x_bound: the previous layer's LSTM outputs — no pass over x), measured otherwise (the features).
-      // The maxima the BACKWARD pass needs of the same tensors (columns of x, rows of Wx) come out of the same reads
-      // and wait in the reserve — unless no backward pass follows.
-      uint32_t *axT = L.fwd_only ? nullptr : reinterpret_cast<uint32_t *>(static_cast<char *>(reserve) + L.res_axT_off);
-      uint32_t *aw2 = L.fwd_only ? nullptr : reinterpret_cast<uint32_t *>(static_cast<char *>(reserve) + L.res_aw2_off);
-      const unsigned xb = L.x_pk ? CMP_AMAX_BITS : bound_bits(d->x_bound);     // (a packed companion: scale 2^14)
-      const int rpD = nabu_pk_rows_pad(D);
-      // (and the backward pass's row bound of h^T, |h| <= 1: a constant it would otherwise fill in a launch of its own)
-      uint32_t *ahT = L.res_ahT_off ? reinterpret_cast<uint32_t *>(static_cast<char *>(reserve) + L.res_ahT_off) : nullptr;
-      // and the recurrent launch's exchange ring (lstm_persist.h: caller_ring_words) — nothing between here and that
-      // launch writes the persistent kernels' part of the workspace
-      FillSeg fill[6] = {{ax, (size_t)rpBT, xb}, {aw, (size_t)rpG, 0u}, {axT, axT ? (size_t)rpD : 0, xb}, {aw2, aw2 ? (size_t)rpD : 0, 0u},
-                         {ahT, ahT ? (size_t)nabu_pk_rows_pad(H) : 0, L.hT_ext ? CMP_AMAX_BITS : bound_bits(1.0f)},
-                         {w + L.persist_off, persistent && !fuse_in ? L.plan.caller_ring_words : 0, 0xFFFFFFFFu}};
-      if (int e = multi_fill(fill, 6, s)) return e;
-      ring_cleared = fill[5].words > 0;
-      if (!xb)
-        if (int e = nabu_pk_amax(x, D, BT, D, ax, axT, stream)) return e;
-      if (int e = pk_amax_pair(kern[0], kern[1], G, D, G, aw2, aw, aw + G, nullptr, s)) return e;
-    }
-    // the input operand: the producer layer's forward kernel wrote it (x_pk_rows) — or one pass over x here
-    const void *xop = L.x_pk ? d->x_pk_rows : pk + L.pk_x;
-    if (!L.x_pk && L.res_xT_off) {
-      // ... and x^T for the backward pass's weight-gradient product out of the same read (kept in the reserve)
-      const int rpDx = nabu_pk_rows_pad(D);
-      if (int e = pk_pack_both(P, x, D, BT, D, pk + L.pk_x, rpBT, 0, rpBT, nkb, static_cast<char *>(reserve) + L.res_xT_off, rpDx, 0,
-                               rpDx, nabu_pk_kblocks(BT, P), s, P == 2 ? ax : nullptr,
-                               P == 2 ? reinterpret_cast<uint32_t *>(static_cast<char *>(reserve) + L.res_axT_off) : nullptr))
-        return e;
-    } else if (!L.x_pk) {
-      if (int e = pk_pack_any(P, 0, x, D, BT, D, pk + L.pk_x, rpBT, 0, 0, rpBT, nkb, 0, 0, ax, stream)) return e;
-    }
-    {   // Wx^T of both cells: one launch
-      PkPackReq rq[2];
-      for (int dir = 0; dir < 2; ++dir)
-        rq[dir] = PkPackReq{kern[dir], G, D, G, pk + L.pk_w, rpG, dir * G, 0, dir ? rpG - G : G, nkb, 0, 0, P == 2 ? aw : nullptr};
-      if (int e = pk_pack_multi(P, 1, rq, 2, s)) return e;
-    }
-    nabu_pk_gemm_desc g = pk_desc(P, BT, 2 * G, nkb, xop, rpBT, pk + L.pk_w, rpG, gates[0], G);
-    g.C2[0] = gates[1]; g.n_split = G; g.bias = bias[0]; g.bias2 = bias[1];
-    if (P == 2) { g.a_amax[0] = ax; g.b_amax[0] = aw; g.direct = 2; }
-    if (int e = nabu_gemm_pk(&g, w + L.gemm_off, L.gemm_bytes, stream)) return e;
-  } else
-  for (int dir = 0; dir < 2; ++dir) {
-    int e = nabu_gemm_ex(d->gemm_precision, 0, 0, B * T, 4 * H, D, 1.f, x, D, kern[dir], 4 * H, 0.f, gates[dir],
-                          4 * H, bias[dir], 0, 0, 0, w + L.gemm_off, L.gemm_bytes, stream);
-    if (e) return e;
-  }
-  return 0;
-  };
-  if (!fuse_in)
-    if (int e = input_projection()) return e;
-  // frames t in [max_len, T) are never visited by the recurrence
-  if (max_len < T)
-    NABU_HIP(hipMemset2DAsync(out + (size_t)max_len * 2 * H, (size_t)T * 2 * H * sizeof(float), 0,
-                              (size_t)(T - max_len) * 2 * H * sizeof(float), B, s));
-
-  // packed companions of the output (ABI version 3): out of the recurrent kernel itself where that is possible, by the
-  // pack kernels behind the recurrence otherwise — complete on return either way
-  const bool want_cmp = wants_companions(d, L);
-  const int S = L.out_stack, rpW = nabu_pk_rows_pad(L.pk_whole ? D + H : H), r0 = L.pk_whole ? D : 0;
-  char *hTp[2] = {nullptr, nullptr};
-  if (L.hT_ext) { hTp[0] = static_cast<char *>(d->hT_pk); hTp[1] = hTp[0] + L.cmp_bytes[2] / 2; }
-  const bool want_out = (d->out_pk_rows || d->out_pk_cols) && L.cmp_bytes[3] != 0;
-  const int by_kernel = emitted_by_kernel(d, L);
-  const bool emit = by_kernel != 0;
-  auto companions_by_pack_kernels = [&](int todo) -> int {
-    todo &= ((want_out && d->out_pk_rows) ? 1 : 0) | ((want_out && d->out_pk_cols) ? 2 : 0) | (L.hT_ext ? 4 : 0);
-    if (!todo) return 0;
-    uint32_t *am = reinterpret_cast<uint32_t *>(w + L.cmp_amax_off);
-    const FillSeg fill = {am, L.cmp_amax_bytes / 4, CMP_AMAX_BITS};
-    if (int e = multi_fill(&fill, 1, s)) return e;
-    const int R = B * T / S, C = 2 * H * S;
-    if (want_out && d->out_pk_rows && (todo & 1))
-      if (int e = pk_pack_any(2, 0, out, C, R, C, d->out_pk_rows, nabu_pk_rows_pad(R), 0, 0, nabu_pk_rows_pad(R), nabu_pk_kblocks(C, 2), 0, 0, am, stream)) return e;
-    if (want_out && d->out_pk_cols && (todo & 2))
-      if (int e = pk_pack_any(2, 1, out, C, R, C, d->out_pk_cols, nabu_pk_rows_pad(C), 0, 0, nabu_pk_rows_pad(C), nabu_pk_kblocks(R, 2), 0, 0, am, stream)) return e;
-    if (L.hT_ext && (todo & 4)) {
-      PkPackReq rq[2];
-      for (int dir = 0; dir < 2; ++dir)
-        rq[dir] = PkPackReq{out + (size_t)dir * H, 2 * H, B * T, H, hTp[dir], rpW, r0, 0, rpW - r0, nabu_pk_kblocks(B * T, 2), T, dir ? 1 : -1, am};
-      if (int e = pk_pack_multi(2, 1, rq, 2, s)) return e;
-    }
-    return 0;
-  };
-  EmitArgs em = {};
-  if (emit) {
-    em.x_rows = (want_out && (by_kernel & 1)) ? static_cast<char *>(d->out_pk_rows) : nullptr;
-    em.x_cols = (want_out && (by_kernel & 2)) ? static_cast<char *>(d->out_pk_cols) : nullptr;
-    em.hT[0] = (by_kernel & 4) ? hTp[0] : nullptr; em.hT[1] = (by_kernel & 4) ? hTp[1] : nullptr;
-    em.x_rows_pad = (unsigned)nabu_pk_rows_pad(B * T / S);
-    em.x_cols_pad = (unsigned)nabu_pk_rows_pad(2 * H * S);
-    em.hT_rows_pad = (unsigned)rpW;
-    em.hT_row0 = r0;
-    em.stack_shift = S == 2 ? 1 : 0;
-    em.b0 = 0;
-  }
-
-  if (persistent) {
-    NABU_PROFILE_MARK(g_ev_begin, s);
-    int e = lstm_persist_fwd(L.plan, len, kern, gates, cs, out, reinterpret_cast<int *>(w), w + L.persist_off,
-                             L.persist_bytes, s, ring_cleared, fuse_in ? x : nullptr, fuse_in ? bias : nullptr,
-                             L.xws_bytes ? w + L.xws_off : nullptr, emit ? &em : nullptr);
-    // the grid cannot be co-resident on this device (occupancy check before the launch): LSTM_AUTO steps instead
-    if (!(e == NABU_EUNSUP && d->mode == NABU_LSTM_AUTO)) {
-      if (e) return e;
-      NABU_PROFILE_MARK(g_ev_end, s);
-      if (want_cmp) return companions_by_pack_kernels(7 & ~by_kernel);
-      return 0;
-    }
-    if (fuse_in)      // the step kernels read the projection from the gate buffers
-      if (int e2 = input_projection()) return e2;
-  }
-  StepArgs p;
-  p.B = B; p.T = T; p.D = D; p.H = H; p.max_len = max_len; p.len = len;
-  for (int i = 0; i < 2; ++i) { p.kernel[i] = kern[i]; p.gates[i] = gates[i]; p.cs[i] = cs[i]; }
-  p.out = out; p.dout = nullptr;
-  p.hstate = reinterpret_cast<float *>(w + L.hstate_off);
-  p.cstate = reinterpret_cast<float *>(w + L.cstate_off);
-  NABU_HIP(hipMemsetAsync(p.hstate, 0, 4 * (size_t)B * H * sizeof(float), s));
-  NABU_HIP(hipMemsetAsync(p.cstate, 0, 2 * (size_t)B * H * sizeof(float), s));
-  const dim3 grid((H + SU - 1) / SU, (B + SB - 1) / SB, 2);
-  const size_t shm = ((size_t)SB * H + SB * 4 * SU) * sizeof(float);
-  if (shm > 64 * 1024)
-    NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(lstm_step_fwd_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  NABU_PROFILE_MARK(g_ev_begin, s);
-  for (int t = 0; t < max_len; ++t) {
-    hipLaunchKernelGGL(lstm_step_fwd_kernel, grid, dim3(256), shm, s, p, t);
-  }
-  NABU_LAUNCH_CHECK();
-  NABU_PROFILE_MARK(g_ev_end, s);
-  if (want_cmp) return companions_by_pack_kernels(7);
-  return 0;
+  return blstm_forward(DescScope(d_in, false), plain_cell(bias_fw, bias_bw, nullptr, nullptr), x, len, kernel_fw, kernel_bw, out,
+                       reserve, ws, ws_bytes, stream);
 }
-
-// parts: 1 = data (recurrence backward, bias gradients, input gradient, the packs of dz), 2 = weights (dWx, dWh from
-// the dz the data part left in the reserve), 3 = both (nabu_blstm_bwd)
-static int blstm_bwd_parts(int parts, const nabu_blstm_desc *d, const float *x, const int32_t *len,
-                           const float *kernel_fw, const float *kernel_bw, const float *out,
-                           const float *d_out, void *reserve, float *d_x, float *dkernel_fw,
-                           float *dbias_fw, float *dkernel_bw, float *dbias_bw, void *ws,
-                           size_t ws_bytes, nabu_stream_t stream) {
-  if (int e = check_desc(d)) return e;
-  NABU_CHECK_ARG(x && len && out && reserve && ws, "blstm_bwd: null pointer");
-  if (parts & 1) NABU_CHECK_ARG(kernel_fw && kernel_bw && d_out && dbias_fw && dbias_bw, "blstm_bwd: null pointer");
-  if (parts & 2) NABU_CHECK_ARG(dkernel_fw && dkernel_bw, "blstm_bwd: null pointer");
-  const Layout L = make_layout(d);
-  if (int e = tag_check(d, L, reserve, parts == 3 ? "blstm_bwd" : parts == 1 ? "blstm_bwd_data" : "blstm_bwd_weights")) return e;
-  if (ws_bytes < L.total) return fail(NABU_EWS, "blstm_bwd: workspace %zu < %zu", ws_bytes, L.total);
-  if (d->mode == NABU_LSTM_PERSISTENT && !L.plan.supported)
-    return fail(NABU_EUNSUP, "blstm_bwd: persistent kernel does not support B=%d H=%d", d->B, d->H);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int B = d->B, T = d->T, D = d->D, H = d->H;
-  const int max_len = d->max_len > 0 ? d->max_len : T;
-  float *r = static_cast<float *>(reserve);
-  float *gates[2] = {r, r + L.gates_elems};
-  float *cs[2] = {r + 2 * L.gates_elems, r + 2 * L.gates_elems + L.cs_elems};
-  char *w = static_cast<char *>(ws);
-  const float *kern[2] = {kernel_fw, kernel_bw};
-  float *dkern[2] = {dkernel_fw, dkernel_bw};
-  float *dbias[2] = {dbias_fw, dbias_bw};
-
-  float *db_part = nullptr;   // persistent path: bias-gradient partials [db_rows][2][4H]
-  int db_rows = 0;
-  bool db_done = false;       // the bias gradients were summed by the launch that read the maxima
-  // f16x3 with an input gradient: the persistent kernel leaves every workgroup's row maxima of dz in the workspace
-  uint32_t *rowmax = (L.pk_planes == 2 && L.pk_in && d_x && L.pk_rowmax_bytes)
-                         ? reinterpret_cast<uint32_t *>(w + L.pk_off + L.pk_rowmax) : nullptr;
-  bool rowmax_done = false;
-  if (parts & 1) {
-  // dz rows of frames never visited by the recurrence must be zero
-  if (max_len < T)
-    for (int dir = 0; dir < 2; ++dir)
-      NABU_HIP(hipMemset2DAsync(gates[dir] + (size_t)max_len * 4 * H, (size_t)T * 4 * H * sizeof(float),
-                                0, (size_t)(T - max_len) * 4 * H * sizeof(float), B, s));
-
-  NABU_PROFILE_MARK(g_ev_begin, s);
-  bool stepwise = !use_persistent(d, L.plan);
-  if (!stepwise) {
-    int e = lstm_persist_bwd(L.plan, len, kern, gates, cs, d_out, reinterpret_cast<int *>(w), w + L.persist_off,
-                             L.persist_bytes, &db_part, &db_rows, s, rowmax, &rowmax_done);
-    if (e == NABU_EUNSUP && d->mode == NABU_LSTM_AUTO) { stepwise = true; db_part = nullptr; db_rows = 0; rowmax_done = false; }
-    else if (e) return e;
-  }
-  if (stepwise) {
-    StepArgs p;
-    p.B = B; p.T = T; p.D = D; p.H = H; p.max_len = max_len; p.len = len;
-    for (int i = 0; i < 2; ++i) { p.kernel[i] = kern[i]; p.gates[i] = gates[i]; p.cs[i] = cs[i]; }
-    p.out = nullptr; p.dout = d_out;
-    p.hstate = nullptr;
-    p.cstate = reinterpret_cast<float *>(w + L.cstate_off);  // dc carry
-    NABU_HIP(hipMemsetAsync(p.cstate, 0, 2 * (size_t)B * H * sizeof(float), s));
-    const dim3 grid((H + SU - 1) / SU, (B + SB - 1) / SB, 2);
-    for (int t = max_len - 1; t >= 0; --t)
-      hipLaunchKernelGGL(lstm_step_bwd_kernel, grid, dim3(256), 0, s, p, t);
-    NABU_LAUNCH_CHECK();
-  }
-  NABU_PROFILE_MARK(g_ev_end, s);
-  if (g_phase_hook) g_phase_hook(g_phase_user);
-  }
-
-  // weight / input gradients from dz (now stored in gates[])
-  const int M = B * T;
-  if (L.pk_planes) {
-    // packed bf16-plane operands (gemm_pk.hip).  dZ^T of both cells is one operand [8H, BT] (in the reserve): the
-    // weight gradients of both cells are column ranges of one product (input part) resp. a batch of two (recurrent part)
-    const int P = L.pk_planes, G = 4 * H;
-    char *pk = w + L.pk_off;
-    char *dzTp = static_cast<char *>(reserve) + L.res_dzT_off;
-    const int rpBT = nabu_pk_rows_pad(M), rpG = nabu_pk_rows_pad(2 * G), rpD = nabu_pk_rows_pad(D);
-    const int nkbT = nabu_pk_kblocks(M, P);
-    const int nkb2 = nabu_pk_kblocks(2 * G, P), kbG = G / 16;
-    int e;
-    // f16x3 (P = 2): row maxima of every operand — measured (dz, the weights, x) or known (|h| < 1)
-    uint32_t *adz = reinterpret_cast<uint32_t *>(pk + L.pk_adz);
-    uint32_t *axT = reinterpret_cast<uint32_t *>(static_cast<char *>(reserve) + L.res_axT_off);    // from the forward pass
-    uint32_t *aw2 = reinterpret_cast<uint32_t *>(static_cast<char *>(reserve) + L.res_aw2_off);
-    uint32_t *ahT[2] = {reinterpret_cast<uint32_t *>(pk + L.pk_ahT[0]), reinterpret_cast<uint32_t *>(pk + L.pk_ahT[1])};
-    uint32_t *adzT = reinterpret_cast<uint32_t *>(static_cast<char *>(reserve) + L.res_adzT_off);
-    if (parts & 1) {
-      const bool both = d_x && L.pk_in;    // dz is also needed row-major (dx): both packs from one read of dz
-      if (P == 2) {
-        // the maxima of dz: its rows' over BOTH cells (the row scale of dZ as [BT, 8H]) and its columns'
-        if (db_part && (!both || rowmax_done)) {
-          // the persistent kernel kept them: the gate columns' maxima per unit next to its bias-gradient partials, the
-          // frames' per workgroup in the workspace (only asked for where an input gradient follows) — no read of dz
-          // (the bias gradients — the sum of the same units' partial rows — come out of the same launch)
-          if ((e = pk_amax_from_persist(M, rpBT, T, max_len, 2 * (H / 16), rowmax, both ? adz : nullptr, db_rows, 2 * G,
-                                        db_part + lstm_persist_db_floats(B, H), 2 * G, adzT, s, db_part, dbias[0], dbias[1])))
-            return e;
-          db_done = true;
-        } else {
-          const FillSeg fill[2] = {{adz, both ? (size_t)rpBT : 0, 0u}, {adzT, (size_t)rpG, 0u}};
-          if ((e = multi_fill(fill, 2, s))) return e;
-          if ((e = pk_amax_pair(gates[0], gates[1], G, M, G, both ? adz : nullptr, adzT, adzT + G, nullptr, s))) return e;
-        }
-      }
-      for (int dir = 0; dir < 2; ++dir) {
-        if (both)
-          e = pk_pack_both(P, gates[dir], G, M, G, pk + L.pk_dz, rpBT, dir * kbG, rpBT, dir ? nkb2 - kbG : kbG, dzTp,
-                           rpG, dir * G, dir ? rpG - G : G, nkbT, s, adz, adzT);
-        else
-          e = pk_pack_any(P, 1, gates[dir], G, M, G, dzTp, rpG, dir * G, 0, dir ? rpG - G : G, nkbT, 0, 0, adzT, stream);
-        if (e) return e;
-      }
-      if (d_x && L.pk_in) {
-        // dx = [dZ_fw | dZ_bw] · [Wx_fw | Wx_bw]^T: the two cells are two ranges of ONE reduction
-        PkPackReq rq[2];
-        for (int dir = 0; dir < 2; ++dir)
-          rq[dir] = PkPackReq{kern[dir], G, D, G, pk + L.pk_w2, rpD, 0, dir * kbG, rpD, dir ? nkb2 - kbG : kbG, 0, 0,
-                              P == 2 ? aw2 : nullptr};
-        if ((e = pk_pack_multi(P, 0, rq, 2, s))) return e;
-        nabu_pk_gemm_desc g = pk_desc(P, M, D, nkb2, pk + L.pk_dz, rpBT, pk + L.pk_w2, rpD, d_x, D);
-        if (P == 2) { g.a_amax[0] = adz; g.b_amax[0] = aw2; g.direct = 2; }
-        if ((e = nabu_gemm_pk(&g, w + L.gemm_off, L.gemm_bytes, stream))) return e;
-      }
-    }
-    if ((parts & 2) && L.pk_in) {
-      // x^T: the producer layer's forward kernel wrote it (x_pk_cols; its row maxima were set by this layer's forward
-      // call) — or one transposing pass over x here
-      // (... or, since the forward call packs x anyway, from that call: res_xT_off)
-      const void *xTop = L.x_pk ? d->x_pk_cols : L.res_xT_off ? static_cast<const char *>(reserve) + L.res_xT_off : pk + L.pk_xT;
-      if (!L.x_pk && !L.res_xT_off)
-        if ((e = pk_pack_any(P, 1, x, D, M, D, pk + L.pk_xT, rpD, 0, 0, rpD, nkbT, 0, 0, axT, stream))) return e;
-      nabu_pk_gemm_desc g = pk_desc(P, D, 2 * G, nkbT, xTop, rpD, dzTp, rpG, dkern[0], G);
-      g.C2[0] = dkern[1]; g.n_split = G;
-      // direct = 2: the three plane products chained directly into the accumulators wherever that rounds less often
-      // than the exact-fp32 kernel would (gemm_pk.hip; 0.6-0.8 x its error at these shapes, tests/test_hip_gemm_pk.py)
-      if (P == 2) { g.a_amax[0] = axT; g.b_amax[0] = adzT; g.direct = 2; }
-      if ((e = nabu_gemm_pk(&g, w + L.gemm_off, L.gemm_bytes, stream))) return e;
-    }
-    if ((parts & 2) && L.pk_rec) {
-      // h_{t-1}^T: the forward cell pairs dz[b,t] with out[b,t-1,:H], the backward cell with out[b,t+1,H:].
-      // Narrow input (the first layer, D = 40): x^T sits in front of h^T in the same operand and the whole kernel
-      // gradient [(D+H), 4H] of a cell is ONE product (its dWx alone cost more on the in-kernel-split kernel)
-      const int r0 = L.pk_whole ? D : 0, Mw = r0 + H, rpW = nabu_pk_rows_pad(Mw);
-      // h^T: in the caller's hT_pk, written by the forward call (ABI version 3) — or packed here from `out`
-      char *hTb[2] = {pk + L.pk_hT[0], pk + L.pk_hT[1]};
-      if (L.hT_ext) { hTb[0] = static_cast<char *>(d->hT_pk); hTb[1] = hTb[0] + L.cmp_bytes[2] / 2; }
-      if (P == 2 && L.res_ahT_off) {   // |h| <= 1: the bound sits in the reserve since the forward call (both cells share it)
-        ahT[0] = ahT[1] = reinterpret_cast<uint32_t *>(static_cast<char *>(reserve) + L.res_ahT_off);
-      } else if (P == 2) {   // |h| <= 1 by construction (o · tanh c): one fill for both cells; the input features are measured
-        const unsigned hb = L.hT_ext ? CMP_AMAX_BITS : bound_bits(1.0f);
-        const FillSeg fill[4] = {{ahT[0], (size_t)r0, 0u}, {ahT[0] + r0, (size_t)(rpW - r0), hb},
-                                 {ahT[1], (size_t)r0, 0u}, {ahT[1] + r0, (size_t)(rpW - r0), hb}};
-        // (r0 = D is a multiple of 4: every region starts 16-byte aligned)
-        if ((e = multi_fill(fill, 4, s))) return e;
-        if (L.pk_whole && (e = pk_amax_pair(x, nullptr, D, M, D, nullptr, ahT[0], nullptr, ahT[1], s))) return e;
-      }
-      {   // [x^T ;] h^T of both cells: one launch
-        PkPackReq rq[4];
-        int n = 0;
-        for (int dir = 0; dir < 2; ++dir) {
-          const uint32_t *am = P == 2 ? ahT[dir] : nullptr;
-          if (L.pk_whole) rq[n++] = PkPackReq{x, D, M, D, hTb[dir], rpW, 0, 0, D, nkbT, 0, 0, am};
-          if (!L.hT_ext)
-            rq[n++] = PkPackReq{out + (size_t)dir * H, 2 * H, M, H, hTb[dir], rpW, r0, 0, rpW - r0, nkbT, T, dir ? 1 : -1, am};
-        }
-        if (n && (e = pk_pack_multi(P, 1, rq, n, s))) return e;
-      }
-      nabu_pk_gemm_desc g = pk_desc(P, Mw, G, nkbT, hTb[0], rpW, dzTp, rpG, dkern[0] + (size_t)(D - r0) * G, G);
-      g.nbatch = 2; g.A[1] = hTb[1]; g.B[1] = dzTp + (size_t)G * 32; g.C[1] = dkern[1] + (size_t)(D - r0) * G;
-      if (P == 2) { g.a_amax[0] = ahT[0]; g.a_amax[1] = ahT[1]; g.b_amax[0] = adzT; g.b_amax[1] = adzT + G; g.direct = 2; }
-      if ((e = nabu_gemm_pk(&g, w + L.gemm_off, L.gemm_bytes, stream))) return e;
-    }
-  }
-  for (int dir = 0; dir < 2; ++dir) {
-    int e = 0;
-    // dWx = x^T · dz
-    if (!L.pk_in && !L.pk_whole && (parts & 2)) {
-      e = nabu_gemm_ex(d->gemm_precision, 1, 0, D, 4 * H, M, 1.f, x, D, gates[dir], 4 * H, 0.f, dkern[dir], 4 * H,
-                       nullptr, 0, 0, 0, w + L.gemm_off, L.gemm_bytes, stream);
-      if (e) return e;
-    }
-    // dWh = h_{prev}^T · dz : fw pairs (out[b,t-1,:H], dz[b,t]); bw pairs (out[b,t+1,H:], dz[b,t])
-    if (!(L.pk_planes && L.pk_rec) && (parts & 2)) {
-    const float *A = dir == 0 ? out : out + H + (size_t)2 * H;
-    const float *Bm = dir == 0 ? gates[0] + (size_t)4 * H : gates[1];
-    e = nabu_gemm_f32(1, 0, H, 4 * H, B * (T - 1), 1.f, A, 2 * H, Bm, 4 * H, 0.f,
-                      dkern[dir] + (size_t)D * 4 * H, 4 * H, nullptr, T > 1 ? T - 1 : 0,
-                      (long long)T * 2 * H, (long long)T * 4 * H, w + L.gemm_off, L.gemm_bytes, stream);
-    if (e) return e;
-    }
-    if (!(parts & 1)) continue;
-    // db = column sums of dz: the persistent kernel already summed them per unit (one launch adds the few partial
-    // rows of both cells)
-    if (db_part)
-      e = (dir || db_done) ? 0 : colsum_pair(db_rows, 4 * H, db_part, 2 * 4 * H, dbias[0], dbias[1], s);
-    else
-      e = nabu_colsum_f32(M, 4 * H, gates[dir], 4 * H, 0.f, dbias[dir], w + L.gemm_off, L.gemm_bytes, stream);
-    if (e) return e;
-    // dx (+)= dz · Wx^T
-    if (d_x && !L.pk_in) {
-      e = nabu_gemm_ex(d->gemm_precision, 0, 1, M, D, 4 * H, 1.f, gates[dir], 4 * H, kern[dir], 4 * H,
-                        dir == 0 ? 0.f : 1.f, d_x, D, nullptr, 0, 0, 0, w + L.gemm_off, L.gemm_bytes, stream);
-      if (e) return e;
-    }
-  }
-  return 0;
-}
-
 extern "C" int nabu_blstm_bwd(const nabu_blstm_desc *d_in, const float *x, const int32_t *len,
                               const float *kernel_fw, const float *kernel_bw, const float *out,
                               const float *d_out, void *reserve, float *d_x, float *dkernel_fw,
                               float *dbias_fw, float *dkernel_bw, float *dbias_bw, void *ws,
                               size_t ws_bytes, nabu_stream_t stream) {
-  DescScope scope(d_in);
-  if (scope.err) return scope.err;
-  const nabu_blstm_desc *d = &scope.d;
-  return blstm_bwd_parts(3, d, x, len, kernel_fw, kernel_bw, out, d_out, reserve, d_x, dkernel_fw, dbias_fw, dkernel_bw,
-                         dbias_bw, ws, ws_bytes, stream);
+  return blstm_backward(3, DescScope(d_in, false), plain_cell(nullptr, nullptr, dbias_fw, dbias_bw), x, len, kernel_fw, kernel_bw,
+                        out, d_out, reserve, d_x, dkernel_fw, dkernel_bw, ws, ws_bytes, stream);
 }
 extern "C" int nabu_blstm_bwd_data(const nabu_blstm_desc *d_in, const float *x, const int32_t *len,
                                    const float *kernel_fw, const float *kernel_bw, const float *out,
                                    const float *d_out, void *reserve, float *d_x, float *dbias_fw, float *dbias_bw,
                                    void *ws, size_t ws_bytes, nabu_stream_t stream) {
-  DescScope scope(d_in);
-  if (scope.err) return scope.err;
-  const nabu_blstm_desc *d = &scope.d;
-  return blstm_bwd_parts(1, d, x, len, kernel_fw, kernel_bw, out, d_out, reserve, d_x, nullptr, dbias_fw, nullptr, dbias_bw,
-                         ws, ws_bytes, stream);
+  return blstm_backward(1, DescScope(d_in, false), plain_cell(nullptr, nullptr, dbias_fw, dbias_bw), x, len, kernel_fw, kernel_bw,
+                        out, d_out, reserve, d_x, nullptr, nullptr, ws, ws_bytes, stream);
 }
 extern "C" int nabu_blstm_bwd_weights(const nabu_blstm_desc *d_in, const float *x, const int32_t *len, const float *out,
                                       void *reserve, float *dkernel_fw, float *dkernel_bw, void *ws, size_t ws_bytes,
                                       nabu_stream_t stream) {
-  DescScope scope(d_in);
-  if (scope.err) return scope.err;
-  const nabu_blstm_desc *d = &scope.d;
-  return blstm_bwd_parts(2, d, x, len, nullptr, nullptr, out, nullptr, reserve, nullptr, dkernel_fw, nullptr, dkernel_bw,
-                         nullptr, ws, ws_bytes, stream);
+  return blstm_backward(2, DescScope(d_in, false), plain_cell(nullptr, nullptr, nullptr, nullptr), x, len, nullptr, nullptr, out,
+                        nullptr, reserve, nullptr, dkernel_fw, dkernel_bw, ws, ws_bytes, stream);
+}
+
+// ---- the layer-normalised cell
+extern "C" int nabu_blstm_ln_fwd(const nabu_blstm_desc *d_in, const float *x, const int32_t *len, const float *kernel_fw,
+                                 const float *kernel_bw, const nabu_blstm_ln_params *ln, float *out, void *reserve,
+                                 void *ws, size_t ws_bytes, nabu_stream_t stream) {
+  return blstm_forward(DescScope(d_in, true), ln_cell(ln), x, len, kernel_fw, kernel_bw, out, reserve, ws, ws_bytes, stream);
+}
+extern "C" int nabu_blstm_ln_bwd(const nabu_blstm_desc *d_in, const float *x, const int32_t *len, const float *kernel_fw,
+                                 const float *kernel_bw, const nabu_blstm_ln_params *ln, const float *out,
+                                 const float *d_out, void *reserve, float *d_x, float *dkernel_fw, float *dkernel_bw,
+                                 void *ws, size_t ws_bytes, nabu_stream_t stream) {
+  return blstm_backward(3, DescScope(d_in, true), ln_cell(ln), x, len, kernel_fw, kernel_bw, out, d_out, reserve, d_x, dkernel_fw,
+                        dkernel_bw, ws, ws_bytes, stream);
+}
+extern "C" int nabu_blstm_ln_bwd_data(const nabu_blstm_desc *d_in, const float *x, const int32_t *len,
+                                      const float *kernel_fw, const float *kernel_bw, const nabu_blstm_ln_params *ln,
+                                      const float *out, const float *d_out, void *reserve, float *d_x, void *ws,
+                                      size_t ws_bytes, nabu_stream_t stream) {
+  return blstm_backward(1, DescScope(d_in, true), ln_cell(ln), x, len, kernel_fw, kernel_bw, out, d_out, reserve, d_x, nullptr,
+                        nullptr, ws, ws_bytes, stream);
+}
+extern "C" int nabu_blstm_ln_bwd_weights(const nabu_blstm_desc *d_in, const float *x, const int32_t *len, const float *out,
+                                         void *reserve, float *dkernel_fw, float *dkernel_bw, void *ws, size_t ws_bytes,
+                                         nabu_stream_t stream) {
+  return blstm_backward(2, DescScope(d_in, true), ln_cell(nullptr), x, len, nullptr, nullptr, out, nullptr, reserve, nullptr,
+                        dkernel_fw, dkernel_bw, ws, ws_bytes, stream);
 }

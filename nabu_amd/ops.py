@@ -169,7 +169,8 @@ def colsum(a, out, beta=0.0):
 
 
 class BlstmPlan(object):
-    """Shape descriptor + buffers of one BLSTM layer call."""
+    """Shape descriptor + buffers of one BLSTM layer call (plain cell: the nabu_blstm_* entry points)."""
+    ENTRY, WS_TAG, LAYER_NORM = 'nabu_blstm', 'blstm', False
 
     def __init__(self, B, T, D, H, max_len, mode=LSTM_AUTO, gemm_precision='default', x_bound=0.0, fwd_only=False,
                  recurrent_precision='default', out_stack=0):
@@ -178,7 +179,10 @@ class BlstmPlan(object):
         recurrent_precision 'f32': the exact-fp32 recurrent kernels (include/nabu_hip.h, nabu_blstm_desc)"""
         import os
         # (NABU_DESC_V1=1: the 32-byte ABI-version-1 descriptor — A/B runs against a library built before round 5)
-        self.desc = _hip.BlstmDesc(32 if os.environ.get('NABU_DESC_V1') == '1' else ctypes.sizeof(_hip.BlstmDesc), B, T, D, H, int(max_len), mode,
+        v1 = os.environ.get('NABU_DESC_V1') == '1' and not self.LAYER_NORM
+        if self.LAYER_NORM:
+            x_bound, recurrent_precision, out_stack = 0.0, 'default', 0
+        self.desc = _hip.BlstmDesc(32 if v1 else ctypes.sizeof(_hip.BlstmDesc), B, T, D, H, int(max_len), mode,
                                    _hip.GEMM_PRECISIONS[gemm_precision], float(x_bound),
                                    _hip.BLSTM_FWD_ONLY if fwd_only else 0, _hip.REC_PRECISIONS[recurrent_precision],
                                    int(out_stack), None, None, None, None, None)
@@ -187,14 +191,21 @@ class BlstmPlan(object):
         # (0 = the layer would not use that companion); the buffers themselves are attached by the caller (set_companions)
         pkb = (ctypes.c_size_t * 5)()
         self.pk_bytes = [0] * 5
-        if self.desc.size == ctypes.sizeof(_hip.BlstmDesc) and L.nabu_blstm_pk_bytes(ctypes.byref(self.desc), pkb) == 0:
+        if not (v1 or self.LAYER_NORM) and L.nabu_blstm_pk_bytes(ctypes.byref(self.desc), pkb) == 0:
             self.pk_bytes = [int(v) for v in pkb]
         self._keep = []
-        self.reserve_bytes = L.nabu_blstm_reserve_bytes(ctypes.byref(self.desc))
-        self.ws_bytes = L.nabu_blstm_ws_bytes(ctypes.byref(self.desc))
+        self.reserve_bytes = getattr(L, self.ENTRY + '_reserve_bytes')(ctypes.byref(self.desc))
+        self.ws_bytes = getattr(L, self.ENTRY + '_ws_bytes')(ctypes.byref(self.desc))
         if self.reserve_bytes == 0:
-            raise _hip.NabuHipError('blstm: unsupported shape B=%d T=%d D=%d H=%d: %s' % (
-                B, T, D, H, L.nabu_last_error().decode()))
+            raise _hip.NabuHipError('%s: unsupported shape B=%d T=%d D=%d H=%d mode=%d: %s' % (
+                self.ENTRY, B, T, D, H, mode, L.nabu_last_error().decode()))
+
+
+class BlstmLnPlan(BlstmPlan):
+    """... of one layer-normalised BLSTM layer call (nabu_blstm_ln_*): the same descriptor, sized by those entry points,
+    which do not look at x_bound, recurrent_precision, out_stack and the companions (left 0).  LSTM_PERSISTENT is refused
+    there, with the reason."""
+    ENTRY, WS_TAG, LAYER_NORM = 'nabu_blstm_ln', 'blstm_ln', True
 
 
 def blstm_set_companions(plan, x_pk=None, out_pk=None, hT_pk=None):
@@ -230,77 +241,44 @@ def blstm_emits_packed(plan, out_pk=False, hT_pk=False):
         d.out_pk_rows, d.out_pk_cols, d.hT_pk = attached
 
 
-def blstm_fwd(plan, x, lens_dev, k_fw, b_fw, k_bw, b_bw, out, reserve):
-    L = _hip.lib()
-    ws = Workspace.get(plan.ws_bytes, x.device, 'blstm')
-    if BEFORE_RECURRENT[0] is not None:
+def _blstm_call(plan, part, x, *args, **kw):
+    """<plan.ENTRY>_<part>(descriptor, x, args..., workspace, its size, stream): tensors (or None) go as pointers, anything
+    else as it is.  profile = 'fwd' | 'bwd': the call runs a plain recurrence — BEFORE_RECURRENT and the PROFILER fire."""
+    profile = kw.get('profile')
+    name = '%s_%s' % (plan.ENTRY, part)
+    ws = Workspace.get(plan.ws_bytes, x.device, plan.WS_TAG)
+    if profile and BEFORE_RECURRENT[0] is not None:
         BEFORE_RECURRENT[0]()
-    if PROFILER is not None:
-        PROFILER.arm('fwd', plan)
-    check(L.nabu_blstm_fwd(ctypes.byref(plan.desc), ptr(_f32(x, 'x')), ptr(lens_dev), ptr(k_fw), ptr(b_fw),
-                           ptr(k_bw), ptr(b_bw), ptr(out), ptr(reserve), ptr(ws), plan.ws_bytes,
-                           stream()), 'nabu_blstm_fwd')
-    if PROFILER is not None:
+    if profile and PROFILER is not None:
+        PROFILER.arm(profile, plan)
+    argv = [ptr(a) if a is None or torch.is_tensor(a) else a for a in (_f32(x, 'x'),) + args]
+    check(getattr(_hip.lib(), name)(ctypes.byref(plan.desc), *(argv + [ptr(ws), plan.ws_bytes, stream()])), name)
+    if profile and PROFILER is not None:
         PROFILER.disarm()
+
+
+def blstm_fwd(plan, x, lens_dev, k_fw, b_fw, k_bw, b_bw, out, reserve):
+    _blstm_call(plan, 'fwd', x, lens_dev, k_fw, b_fw, k_bw, b_bw, out, reserve, profile='fwd')
     return out
 
 
 def blstm_bwd(plan, x, lens_dev, k_fw, k_bw, out, d_out, reserve, d_x, dk_fw, db_fw, dk_bw, db_bw):
-    L = _hip.lib()
-    ws = Workspace.get(plan.ws_bytes, x.device, 'blstm')
-    if BEFORE_RECURRENT[0] is not None:
-        BEFORE_RECURRENT[0]()
-    if PROFILER is not None:
-        PROFILER.arm('bwd', plan)
-    check(L.nabu_blstm_bwd(ctypes.byref(plan.desc), ptr(x), ptr(lens_dev), ptr(k_fw), ptr(k_bw), ptr(out),
-                           ptr(d_out), ptr(reserve), ptr(d_x), ptr(dk_fw), ptr(db_fw), ptr(dk_bw),
-                           ptr(db_bw), ptr(ws), plan.ws_bytes, stream()), 'nabu_blstm_bwd')
-    if PROFILER is not None:
-        PROFILER.disarm()
+    _blstm_call(plan, 'bwd', x, lens_dev, k_fw, k_bw, out, d_out, reserve, d_x, dk_fw, db_fw, dk_bw, db_bw, profile='bwd')
     return d_x
 
 
 def blstm_bwd_data(plan, x, lens_dev, k_fw, k_bw, out, d_out, reserve, d_x, db_fw, db_bw):
     """first half of blstm_bwd (nabu_blstm_bwd_data): recurrence backward, bias gradients, d_x; dz stays in `reserve`"""
-    L = _hip.lib()
-    ws = Workspace.get(plan.ws_bytes, x.device, 'blstm')
-    if BEFORE_RECURRENT[0] is not None:
-        BEFORE_RECURRENT[0]()
-    if PROFILER is not None:
-        PROFILER.arm('bwd', plan)
-    check(L.nabu_blstm_bwd_data(ctypes.byref(plan.desc), ptr(x), ptr(lens_dev), ptr(k_fw), ptr(k_bw), ptr(out),
-                                ptr(d_out), ptr(reserve), ptr(d_x), ptr(db_fw), ptr(db_bw), ptr(ws), plan.ws_bytes,
-                                stream()), 'nabu_blstm_bwd_data')
-    if PROFILER is not None:
-        PROFILER.disarm()
+    _blstm_call(plan, 'bwd_data', x, lens_dev, k_fw, k_bw, out, d_out, reserve, d_x, db_fw, db_bw, profile='bwd')
     return d_x
 
 
 def blstm_bwd_weights(plan, x, lens_dev, out, reserve, dk_fw, dk_bw):
-    """second half (nabu_blstm_bwd_weights): the kernel gradients from the dz blstm_bwd_data left in `reserve`"""
-    ws = Workspace.get(plan.ws_bytes, x.device, 'blstm')
-    check(_hip.lib().nabu_blstm_bwd_weights(ctypes.byref(plan.desc), ptr(x), ptr(lens_dev), ptr(out), ptr(reserve),
-                                            ptr(dk_fw), ptr(dk_bw), ptr(ws), plan.ws_bytes, stream()),
-          'nabu_blstm_bwd_weights')
+    """second half (nabu_blstm[_ln]_bwd_weights): the kernel gradients from the dz the data half left in `reserve`"""
+    _blstm_call(plan, 'bwd_weights', x, lens_dev, out, reserve, dk_fw, dk_bw)
 
 
 LN_SCOPES = ('input', 'transform', 'forget', 'output', 'state')    # the norm scopes of LayerNormBasicLSTMCell, in ABI order
-
-
-class BlstmLnPlan(object):
-    """Shape descriptor of one layer-normalised BLSTM layer call (include/nabu_hip.h, nabu_blstm_ln_fwd): the descriptor
-    of BlstmPlan, sized by the layer-norm entry points.  LSTM_PERSISTENT is refused there, with the reason."""
-
-    def __init__(self, B, T, D, H, max_len, mode=LSTM_AUTO, gemm_precision='default', fwd_only=False):
-        self.desc = _hip.BlstmDesc(ctypes.sizeof(_hip.BlstmDesc), B, T, D, H, int(max_len), mode,
-                                   _hip.GEMM_PRECISIONS[gemm_precision], 0.0, _hip.BLSTM_FWD_ONLY if fwd_only else 0,
-                                   0, 0, None, None, None, None, None)
-        L = _hip.lib()
-        self.reserve_bytes = L.nabu_blstm_ln_reserve_bytes(ctypes.byref(self.desc))
-        self.ws_bytes = L.nabu_blstm_ln_ws_bytes(ctypes.byref(self.desc))
-        if self.reserve_bytes == 0:
-            raise _hip.NabuHipError('blstm(layer_norm=True): unsupported B=%d T=%d D=%d H=%d mode=%d: %s' % (
-                B, T, D, H, mode, L.nabu_last_error().decode()))
 
 
 def blstm_ln_params(gamma, beta, dgamma=None, dbeta=None):
@@ -315,39 +293,24 @@ def blstm_ln_params(gamma, beta, dgamma=None, dbeta=None):
 
 
 def blstm_ln_fwd(plan, x, lens_dev, k_fw, k_bw, gamma, beta, out, reserve):
-    ws = Workspace.get(plan.ws_bytes, x.device, 'blstm_ln')
-    ln = blstm_ln_params(gamma, beta)
-    check(_hip.lib().nabu_blstm_ln_fwd(ctypes.byref(plan.desc), ptr(_f32(x, 'x')), ptr(lens_dev), ptr(k_fw), ptr(k_bw),
-                                       ctypes.byref(ln), ptr(out), ptr(reserve), ptr(ws), plan.ws_bytes, stream()),
-          'nabu_blstm_ln_fwd')
+    _blstm_call(plan, 'fwd', x, lens_dev, k_fw, k_bw, ctypes.byref(blstm_ln_params(gamma, beta)), out, reserve)
     return out
 
 
 def blstm_ln_bwd(plan, x, lens_dev, k_fw, k_bw, gamma, beta, out, d_out, reserve, d_x, dk_fw, dk_bw, dgamma, dbeta):
-    ws = Workspace.get(plan.ws_bytes, x.device, 'blstm_ln')
-    ln = blstm_ln_params(gamma, beta, dgamma, dbeta)
-    check(_hip.lib().nabu_blstm_ln_bwd(ctypes.byref(plan.desc), ptr(x), ptr(lens_dev), ptr(k_fw), ptr(k_bw), ctypes.byref(ln),
-                                       ptr(out), ptr(d_out), ptr(reserve), ptr(d_x), ptr(dk_fw), ptr(dk_bw), ptr(ws),
-                                       plan.ws_bytes, stream()), 'nabu_blstm_ln_bwd')
+    _blstm_call(plan, 'bwd', x, lens_dev, k_fw, k_bw, ctypes.byref(blstm_ln_params(gamma, beta, dgamma, dbeta)), out, d_out,
+                reserve, d_x, dk_fw, dk_bw)
     return d_x
 
 
 def blstm_ln_bwd_data(plan, x, lens_dev, k_fw, k_bw, gamma, beta, out, d_out, reserve, d_x, dgamma, dbeta):
     """first half of blstm_ln_bwd: recurrence backwards, the norm-parameter gradients, d_x; dz stays in `reserve`"""
-    ws = Workspace.get(plan.ws_bytes, x.device, 'blstm_ln')
-    ln = blstm_ln_params(gamma, beta, dgamma, dbeta)
-    check(_hip.lib().nabu_blstm_ln_bwd_data(ctypes.byref(plan.desc), ptr(x), ptr(lens_dev), ptr(k_fw), ptr(k_bw),
-                                            ctypes.byref(ln), ptr(out), ptr(d_out), ptr(reserve), ptr(d_x), ptr(ws),
-                                            plan.ws_bytes, stream()), 'nabu_blstm_ln_bwd_data')
+    _blstm_call(plan, 'bwd_data', x, lens_dev, k_fw, k_bw, ctypes.byref(blstm_ln_params(gamma, beta, dgamma, dbeta)), out,
+                d_out, reserve, d_x)
     return d_x
 
 
-def blstm_ln_bwd_weights(plan, x, lens_dev, out, reserve, dk_fw, dk_bw):
-    """second half: the kernel gradients from the dz blstm_ln_bwd_data left in `reserve`"""
-    ws = Workspace.get(plan.ws_bytes, x.device, 'blstm_ln')
-    check(_hip.lib().nabu_blstm_ln_bwd_weights(ctypes.byref(plan.desc), ptr(x), ptr(lens_dev), ptr(out), ptr(reserve),
-                                               ptr(dk_fw), ptr(dk_bw), ptr(ws), plan.ws_bytes, stream()),
-          'nabu_blstm_ln_bwd_weights')
+blstm_ln_bwd_weights = blstm_bwd_weights     # (the plan names the family)
 
 
 def pad_time(x, Tp):

@@ -1,4 +1,4 @@
-"""GPU tests of the layer-normalised BLSTM layer (nabu_amd/csrc/lstm_ln.hip, layer.blstm(layer_norm=True)) against the
+"""GPU tests of the layer-normalised BLSTM layer (nabu_amd/csrc/lstm.hip + lstm_ln.hip, layer.blstm(layer_norm=True)) against the
 float64 NumPy restatement tests/lnlstm_ref.py.
 
 Kernel parity: forward output, dx, both dkernel and the twenty gamma/beta gradients through the C ABI.  The yardstick
@@ -87,9 +87,9 @@ def relerr(a, ref):
     return float(np.abs(a.astype(np.float64) - ref).max() / np.abs(ref).max())
 
 
-@pytest.mark.parametrize('B,T,D,H', SHAPES)
-def test_kernels_match_the_float64_restatement(B, T, D, H):
-    p, x, lens, dout = case(B, T, D, H)
+def assert_parity(p, x, lens, dout):
+    """every tensor of the kernels within PARITY_MULTIPLE of the float32 restatement's error; padded frames exactly 0.
+    Returns the kernels' results."""
     # the yardstick: the same restatement in float32 (from the float32 roundings of the same inputs, as the kernel sees them)
     p32, x32, d32 = R.cast(p, np.float32), x.astype(np.float32), dout.astype(np.float32)
     out32, cache32 = R.blstm_fwd(x32, lens, p32)
@@ -107,6 +107,9 @@ def test_kernels_match_the_float64_restatement(B, T, D, H):
         if name.endswith('gamma') or name.endswith('beta'):       # each of the twenty norm gradients on its own
             tensors = [('%s[%s]' % (name, R.SCOPES[i]), got[name][i], f32[name][i], ref[name][i]) for i in range(5)]
         for label, k_, f_, r_ in tensors:
+            if not r_.any():     # identically 0 (T = 1: the forget gate meets no earlier state): no relative error, exactly 0
+                assert not k_.any() and not f_.any(), label
+                continue
             ek, ef = relerr(k_, r_), relerr(f_, r_)
             print('%-22s kernel %.3e  float32 %.3e  ratio %.2f' % (label, ek, ef, ek / max(ef, 1e-300)))
             if not ek <= PARITY_MULTIPLE * ef:
@@ -114,6 +117,28 @@ def test_kernels_match_the_float64_restatement(B, T, D, H):
     assert not failures, failures
     for b, n in enumerate(lens):                                  # padded frames: exactly 0
         assert not got['out'][b, n:].any() and not got['dx'][b, n:].any()
+    return got
+
+
+@pytest.mark.parametrize('B,T,D,H', SHAPES)
+def test_kernels_match_the_float64_restatement(B, T, D, H):
+    assert_parity(*case(B, T, D, H))
+
+
+# the edges of the product tiles the layer shares with the plain cell (lstm_step.h), and of the layer driver around them
+TILE_EDGES = [((2, 9, 4, 20), [9, 5]),            # H % 16 != 0: the unit tile is cut by H (the ucol < H guard)
+              ((3, 1, 8, 16), [1, 1, 1]),         # T = 1: no recurrent launch, no pair of frames for dWh
+              ((4, 10, 8, 16), [6, 4, 6, 3])]     # max(len) < T: the driver zeroes the frames nobody visits (out, dz)
+
+
+@pytest.mark.parametrize('shape,lens', TILE_EDGES)
+def test_kernels_match_the_restatement_at_the_edges_of_the_shared_tiles(shape, lens):
+    B, T, D, H = shape
+    p, x, _, dout = case(B, T, D, H)
+    got = assert_parity(p, x, np.array(lens, np.int32), dout)
+    if T == 1:
+        for d in ('fw', 'bw'):
+            assert not got[d + '_kernel'][D:].any()                  # dWh: exactly 0
 
 
 def test_two_identical_calls_give_identical_bits_and_split_equals_fused():
