@@ -13,12 +13,7 @@
 // Layouts: keys [B,Te,U], values [B,Te,E] batch-major; per-step state time-major.
 #include "common.h"
 #include "gemm_args.h"
-#include "speller_persist.h"
-
-#include <stdlib.h>
-
-#include <string>
-#include <thread>
+#include "speller_attn.h"
 
 namespace nabu {
 
@@ -1676,7 +1671,7 @@ __global__ __launch_bounds__(256) void transpose_kernel(int R, int C, const floa
     if (c0 + i < C && r0 + tx < R) out[(size_t)(c0 + i) * R + r0 + tx] = tile[tx][i];
 }
 
-static int transpose(int R, int C, const float *in, int ldin, float *out, hipStream_t s) {
+int transpose(int R, int C, const float *in, int ldin, float *out, hipStream_t s) {
   hipLaunchKernelGGL(transpose_kernel, dim3((C + 31) / 32, (R + 31) / 32), dim3(256), 0, s, R, C, in, ldin, out);
   NABU_LAUNCH_CHECK();
   return 0;
@@ -1718,6 +1713,17 @@ static int grid1(size_t n) {
   return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
 }
 
+int permute_gates(int R, int U, const float *in, float *out, hipStream_t s) {
+  hipLaunchKernelGGL(permute_gates_kernel, dim3(grid1((size_t)R * 4 * U)), dim3(256), 0, s, R, U, in, out);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
+int add_rows(int R, int Cn, const float *src, int lds, float *dst, int ldd, hipStream_t s) {
+  hipLaunchKernelGGL(add_rows_kernel, dim3(grid1((size_t)R * Cn)), dim3(256), 0, s, R, Cn, src, lds, dst, ldd);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
+
 static size_t attn_lds(const nabu_attn_desc *d, bool bwd) {
   size_t f = 2 * (size_t)d->Te + (d->kind == 1 ? (size_t)d->Te * d->F * (bwd ? 2 : 1) : 0);
   f += bwd ? 4 + (size_t)(AT / 64) * d->U : 64 + 4 + 4 * (size_t)AT;
@@ -1727,7 +1733,7 @@ static size_t attn_lds(const nabu_attn_desc *d, bool bwd) {
 
 // Backward: frame slices per utterance so that the launch has ~256 workgroups (one per CU); a slice
 // keeps at least 16 encoder frames (8 waves x 2 frames in flight)
-static int attn_bwd_nslices(const nabu_attn_desc *d) {
+int attn_bwd_nslices(const nabu_attn_desc *d) {
   int S = (512 + d->B - 1) / d->B;      // two 512-thread workgroups per CU: four waves per SIMD hide the frame latency
   const int cap = (d->Te + 15) / 16;
   if (S > cap) S = cap;
@@ -1735,7 +1741,7 @@ static int attn_bwd_nslices(const nabu_attn_desc *d) {
   return S < 1 ? 1 : S;
 }
 
-static int check_attn(const nabu_attn_desc *d) {
+int check_attn(const nabu_attn_desc *d) {
   if (!d || d->size != sizeof(nabu_attn_desc)) return fail(NABU_EINVAL, "attention: bad descriptor size");
   if (d->B <= 0 || d->Te <= 0 || d->E <= 0 || d->U <= 0) return fail(NABU_EINVAL, "attention: bad dimensions");
   if (d->U > 1024) return fail(NABU_EUNSUP, "attention: num_units > 1024");
@@ -1780,7 +1786,7 @@ extern "C" int nabu_lstm_cell_bwd(int B, int U, int step, const int32_t *seq_len
 }
 
 // tickets: B zeroed counters (left zero) -> the finish steps run inside the attention launches
-static int attn_fwd_impl(const nabu_attn_desc *d, int step, const int32_t *dec_len,
+int nabu::attn_fwd_impl(const nabu_attn_desc *d, int step, const int32_t *dec_len,
                          const int32_t *enc_len, const float *keys, const float *values,
                          const float *q, const float *v, const float *conv_kernel,
                          const float *conv_proj, const float *align_prev, const float *ctx_prev,
@@ -1849,15 +1855,15 @@ extern "C" size_t nabu_attn_bwd_ws_bytes(const nabu_attn_desc *d) {
   return ((size_t)d->B * S * d->U + (d->kind == 1 ? (size_t)d->B * d->Te * d->F : 0) + 4) * sizeof(float);
 }
 
-static int attn_bwd_impl(const nabu_attn_desc *d, int step, const int32_t *dec_len,
+int nabu::attn_bwd_impl(const nabu_attn_desc *d, int step, const int32_t *dec_len,
                          const int32_t *enc_len, const float *keys, const float *values,
                          const float *q, const float *v, const float *conv_kernel,
                          const float *conv_proj, const float *align_prev, const float *align,
                          const float *ctx, const float *dctx, const float *dalign_in, float *dq,
                          float *dkeys, float *dv_part, float *dconv_proj_part,
                          float *dconv_kernel_part, float *dalign_out, const float *znorm, void *ws,
-                         size_t ws_bytes, nabu_stream_t stream, unsigned *tickets, float *ds_out = nullptr,
-                         float *cf_out = nullptr) {
+                         size_t ws_bytes, nabu_stream_t stream, unsigned *tickets, float *ds_out,
+                         float *cf_out) {
   if (int e = check_attn(d)) return e;
   NABU_CHECK_ARG(dec_len && enc_len && keys && values && q && v && align && ctx && dctx && dq && dkeys && dv_part && ws,
                  "attn_bwd: null pointer");
@@ -1939,7 +1945,7 @@ extern "C" int nabu_attn_bwd(const nabu_attn_desc *d, int step, const int32_t *d
 
 // attn_param_grads_kernel has its own frame partition: enough slices that a thread keeps at most 4 frames (more, smaller
 // workgroups balance utterances of different lengths better), at most 16
-static int attn_defer_slices(const nabu_attn_desc *d) {
+int nabu::attn_defer_slices(const nabu_attn_desc *d) {
   if (d->U % 4 || d->U / 4 > PT || PT % (d->U / 4)) return 0;
   if (d->kind == 1 && d->F > PNF) return 0;
   const int NG = PT / (d->U / 4);
@@ -1949,7 +1955,7 @@ static int attn_defer_slices(const nabu_attn_desc *d) {
   const int per = (d->Te + S - 1) / S;
   return (per + NG - 1) / NG <= 8 ? S : 0;
 }
-static int attn_param_grads(const nabu_attn_desc *d, int S, int L, const int32_t *dec_len, const int32_t *enc_len,
+int nabu::attn_param_grads(const nabu_attn_desc *d, int S, int L, const int32_t *dec_len, const int32_t *enc_len,
                             const float *keys, const float *q_all, const float *v, const float *wf, const float *ds_all,
                             const float *cf_all, float *dkeys, float *dv_part, float *dwf_part, hipStream_t s) {
   const int per = (d->Te + S - 1) / S, NG = PT / (d->U / 4);
@@ -1993,750 +1999,5 @@ extern "C" int nabu_scatter_rows_f32(int C, int N, int W, const int32_t *ids, co
   hipLaunchKernelGGL(scatter_rows_kernel, dim3((W + 255) / 256, C), dim3(256), 0,
                      static_cast<hipStream_t>(stream), C, N, W, ids, dz, dK);
   NABU_LAUNCH_CHECK();
-  return 0;
-}
-
-// ===========================================================================
-// Whole-sequence decoder driver: the per-step launch sequence of
-// RNNDecoder._decode runs here, in C++, so that a decoder step costs its kernel
-// launches only (a Python/ctypes loop spent ~15 us of host time per launch).
-namespace nabu {
-
-// experiment / test switches, read at every call (a decoder call is milliseconds)
-static int env_int(const char *name, int dflt) {
-  const char *e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
-struct SpLayout {
-  size_t H[NABU_SPELLER_MAX_LAYERS], Cs[NABU_SPELLER_MAX_LAYERS], Ho[NABU_SPELLER_MAX_LAYERS],
-      acts[NABU_SPELLER_MAX_LAYERS];
-  size_t ctx, align, q, keys, logits_tm, ids, znorm, total;   // offsets in floats (ids: [L,B] int32)
-  size_t dscale, sdraw;    // persistent decoder (speller_persist.h): dropout scale factors [L,B,U], sampling draws [L,B,2]
-};
-
-static SpLayout sp_layout(const nabu_speller_desc *d) {
-  SpLayout s;
-  const size_t B = d->B, L = d->L, U = d->U, E = d->E, Te = d->Te, C = d->C;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t r = o; o += (n + 3) / 4 * 4; return r; };
-  for (int n = 0; n < d->num_layers; ++n) {
-    s.H[n] = take((L + 1) * B * U);
-    s.Cs[n] = take((L + 1) * B * U);
-    s.Ho[n] = d->keep_prob < 1.f ? take((L + 1) * B * U) : s.H[n];
-    s.acts[n] = take(L * B * 4 * U);
-  }
-  s.ctx = take((L + 1) * B * E);
-  s.align = take((L + 1) * B * Te);
-  s.q = take(L * B * U);
-  s.keys = take(B * Te * U);
-  s.logits_tm = take(L * B * C);
-  s.ids = take(L * B);
-  s.znorm = take(L * B);
-  s.dscale = d->keep_prob < 1.f ? take(L * B * U) : 0;
-  s.sdraw = d->sample_prob > 0.f ? take(2 * L * B) : 0;
-  s.total = o;
-  return s;
-}
-
-struct SpWs {
-  size_t z, dl, dH, dCtx, dkeys, dv, dwf, dck, attn, dq, dz[NABU_SPELLER_MAX_LAYERS], dh[2][NABU_SPELLER_MAX_LAYERS],
-      dc[2][NABU_SPELLER_MAX_LAYERS], dctx[2], dal[2], dx, tmp, gemm, gemm_bytes, total;
-  size_t wqT, kxT[NABU_SPELLER_MAX_LAYERS], khT[NABU_SPELLER_MAX_LAYERS];   // transposed weights (backward)
-  size_t kperm[NABU_SPELLER_MAX_LAYERS];   // gate-interleaved copies of the cell kernels' dense rows (forward)
-  size_t kxhT, dxh[2];     // [4U, E+U] transposed rows of layer 0's kernel; [B, E+U] carries d(context | h) of a step
-  size_t wq_sw, kxh_sw;    // the same two weights re-blocked for rows16_kernel (gemm_skinny.hip): [U, U], [E+U, 4U]
-  size_t tickets, fpart;   // fused skinny products: per-column-slice tickets (zeroed per call), partial tiles
-  size_t status, persist, persist_bytes;   // persistent decoder kernel: status word (ws[0]), XCC table + exchange rings
-  size_t dv8;                              // its d attention_v partial rows [B*8, U]
-  size_t dck8;                             // ... location-aware: conv kernel gradient partial rows [B*8, K*F]
-  size_t ds_all, cf_all;                   // deferred attention gradients: d scores [L,B,Te], location features [L,B,Te,F]
-  size_t dv16, dwf16;                      // ... and the partial rows of attn_param_grads_kernel [B*Sp, U], [B*Sp, F*U]
-  // the decoder steps run as NS independent sub-batches on NS streams: per sub-batch slices of
-  // the scratch that a step's kernels share
-  int NS, S;               // sub-batches; attention-backward slices per utterance (of a sub-batch)
-  size_t attn_each, gemm_each, fpart_each, z_each;
-};
-
-// The L decoder steps are a chain of small dependent kernels (each ~5 us of launch + memory latency,
-// whatever its size).  Utterances are independent of each other until the weight gradients are summed, so
-// the batch is cut into NS sub-batches whose chains run concurrently on NS streams (forked from / joined
-// to the caller's stream by events); what one chain leaves idle the others use.  NABU_SPELLER_STREAMS=n
-// overrides (1 = off).
-static int sp_nsub(const nabu_speller_desc *d) {
-  const int env = env_int("NABU_SPELLER_STREAMS", 0);
-  int want = env > 0 ? env : 4;
-  while (want > 1 && (d->B % want != 0 || d->B / want < (env > 0 ? 1 : 16))) want /= 2;
-  return want < 1 ? 1 : want;
-}
-
-struct SubStreams {
-  int n;
-  hipStream_t st[8];
-  hipEvent_t fork, done[8];
-};
-static int sub_streams(int n, hipStream_t main, SubStreams *out) {
-  static thread_local hipStream_t side[8] = {nullptr};
-  static thread_local hipEvent_t ev[9] = {nullptr};
-  out->n = n;
-  out->st[0] = main;
-  for (int i = 1; i < n; ++i) {
-    if (!side[i]) NABU_HIP(hipStreamCreateWithFlags(&side[i], hipStreamNonBlocking));
-    out->st[i] = side[i];
-  }
-  for (int i = 0; i <= n && i < 9; ++i)
-    if (!ev[i]) NABU_HIP(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-  out->fork = ev[0];
-  for (int i = 1; i < n; ++i) out->done[i] = ev[i];
-  return 0;
-}
-static int sub_fork(const SubStreams &ss) {
-  if (ss.n == 1) return 0;
-  NABU_HIP(hipEventRecord(ss.fork, ss.st[0]));
-  for (int i = 1; i < ss.n; ++i) NABU_HIP(hipStreamWaitEvent(ss.st[i], ss.fork, 0));
-  return 0;
-}
-static int sub_join(const SubStreams &ss) {
-  for (int i = 1; i < ss.n; ++i) {
-    NABU_HIP(hipEventRecord(ss.done[i], ss.st[i]));
-    NABU_HIP(hipStreamWaitEvent(ss.st[0], ss.done[i], 0));
-  }
-  return 0;
-}
-// Enqueue the sub-batch chains from one host thread each: a chain is thousands of launches, and ONE thread
-// feeding four streams is about as fast as the GPU drains them (2.5 us per launch against ~10 us kernels, four at a
-// time) — measured: with a single enqueuing thread every queue sat idle ~45% of the time waiting for its next
-// step.  body(sub) enqueues ALL steps of one sub-batch on its stream and returns a NABU_E* / hipError_t code.
-template <typename F>
-static int run_subs(int NS, F body) {
-  if (NS == 1) return body(0);
-  const int threads_env = env_int("NABU_SPELLER_THREADS", 0);
-  int codes[8] = {0};
-  std::string texts[8];
-  if (!threads_env) {
-    int first = 0;                       // every chain is enqueued even after a failure: the caller joins the streams
-    for (int i = 0; i < NS; ++i) {
-      const int e = body(i);
-      if (e && !first) first = e;
-    }
-    return first;
-  }
-  int dev = 0;
-  NABU_HIP(hipGetDevice(&dev));
-  std::thread th[8];
-  for (int i = 1; i < NS; ++i)
-    th[i] = std::thread([&, i]() {
-      if (hipSetDevice(dev) != hipSuccess) { codes[i] = (int)hipErrorInvalidDevice; texts[i] = "hipSetDevice failed in a decoder enqueue thread"; return; }
-      codes[i] = body(i);
-      if (codes[i]) texts[i] = err_buf();        // the error text is thread-local: hand it to the caller's thread
-    });
-  codes[0] = body(0);
-  for (int i = 1; i < NS; ++i) th[i].join();
-  if (codes[0]) return codes[0];
-  for (int i = 1; i < NS; ++i)
-    if (codes[i]) return fail(codes[i], "%s", texts[i].c_str());
-  return 0;
-}
-
-static nabu_attn_desc sub_attn_desc(const nabu_speller_desc *d, int Bn) {
-  nabu_attn_desc a = {sizeof(nabu_attn_desc), Bn, d->Te, d->E, d->U, d->kind, d->K, d->F, d->prob_fn};
-  return a;
-}
-
-static SpWs sp_ws(const nabu_speller_desc *d) {
-  SpWs s;
-  const size_t B = d->B, L = d->L, U = d->U, E = d->E, Te = d->Te, C = d->C, F = d->F, K = d->K;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t r = o; o += (n + 3) / 4 * 4; return r; };
-  s.NS = sp_nsub(d);
-  const size_t NS = s.NS, Bn = B / NS;
-  // ws[0]: status word of the persistent decoder kernel (0 = ok; sticky, the caller provides the workspace
-  // zero-initialised once, like the recurrent layers' workspace), then its XCC table and exchange rings
-  s.status = take(64);
-  {
-    SpPersistDesc pd = {(int)B, (int)L, (int)U, (int)E, (int)Te, (int)C};
-    pd.kind = d->kind; pd.K = d->K; pd.F = d->F;
-    s.persist_bytes = speller_persist_ws_bytes(pd);
-    if (speller_persist_bwd_ws_bytes(pd) > s.persist_bytes) s.persist_bytes = speller_persist_bwd_ws_bytes(pd);
-    s.persist = take(s.persist_bytes / 4 + 4);
-    s.dv8 = take(speller_persist_bwd_ws_bytes(pd) ? B * 8 * U : 0);
-    s.dck8 = take((speller_persist_bwd_ws_bytes(pd) && d->kind == 1) ? B * 8 * K * F : 0);
-    s.ds_all = take(L * B * Te);
-    s.cf_all = take(d->kind == 1 ? L * B * Te * F : 0);
-    s.dv16 = take(B * 16 * U);
-    s.dwf16 = take(d->kind == 1 ? B * 16 * F * U : 0);
-  }
-  s.z_each = Bn * 4 * U;
-  s.z = take(B * 4 * U);
-  s.dl = take(L * B * C);
-  s.dH = take(L * B * U);
-  s.dCtx = take(L * B * E);
-  s.dkeys = take(B * Te * U);
-  const nabu_attn_desc adesc = sub_attn_desc(d, (int)Bn);
-  const size_t S = attn_bwd_nslices(&adesc);
-  s.S = (int)S;
-  s.dv = take(B * S * U);
-  s.dwf = take(B * S * F * U + 4);
-  s.attn_each = ((nabu_attn_bwd_ws_bytes(&adesc) > nabu_attn_fwd_ws_bytes(&adesc) ? nabu_attn_bwd_ws_bytes(&adesc)
-                                                                                    : nabu_attn_fwd_ws_bytes(&adesc)) / 4 + 4 + 3) / 4 * 4;
-  s.attn = take(NS * s.attn_each);
-  s.dck = take(B * K * F + 4);
-  s.dq = take(L * B * U);
-  for (int n = 0; n < d->num_layers; ++n) {
-    s.dz[n] = take(L * B * 4 * U);
-    for (int i = 0; i < 2; ++i) { s.dh[i][n] = take(B * U); s.dc[i][n] = take(B * U); }
-  }
-  for (int i = 0; i < 2; ++i) { s.dctx[i] = take(B * E); s.dal[i] = take(B * Te); }
-  s.dx = take(B * U);
-  s.tmp = take(B * U);
-  s.wqT = take(U * U);
-  for (int n = 0; n < d->num_layers; ++n) {
-    s.kxT[n] = take(4 * U * (n == 0 ? E : U));
-    s.khT[n] = take(4 * U * U);
-  }
-  for (int n = 0; n < d->num_layers; ++n) s.kperm[n] = take((n == 0 ? E + U : 2 * U) * 4 * U);
-  s.kxhT = take(4 * U * (E + U));
-  s.wq_sw = take(U * U);
-  s.kxh_sw = take(4 * U * (E + U));
-  for (int i = 0; i < 2; ++i) s.dxh[i] = take(B * (E + U));
-  s.tickets = take(NS * 1024 + B + 4);   // + one counter per utterance for the attention launches
-  {
-    size_t kmax = E + U > 4 * U ? E + U : 4 * U, nmax = 4 * U > E ? 4 * U : E;
-    s.fpart_each = ((kmax / 64 + 1) * Bn * nmax + 3) / 4 * 4;
-    s.fpart = take(NS * s.fpart_each);
-  }
-  size_t g = 0;
-  auto mx = [&](size_t v) { if (v > g) g = v; };
-  const int BL = (int)(B * L), BT = (int)(B * Te);
-  mx(nabu_gemm_ws_bytes((int)B, (int)(4 * U), (int)E)); mx(nabu_gemm_ws_bytes((int)B, (int)(4 * U), (int)U));
-  mx(nabu_gemm_ws_bytes((int)B, (int)U, (int)U)); mx(nabu_gemm_ws_bytes((int)B, (int)E, (int)(4 * U)));
-  mx(nabu_gemm_ws_bytes((int)B, (int)U, (int)(4 * U)));
-  mx(nabu_gemm_ws_bytes((int)B, (int)C, (int)U)); mx(nabu_gemm_ws_bytes((int)B, (int)C, (int)E));
-  mx(nabu_gemm_ws_bytes(BT, (int)U, (int)E)); mx(nabu_gemm_ws_bytes(BT, (int)E, (int)U));
-  mx(nabu_gemm_ws_bytes((int)E, (int)U, BT));
-  mx(nabu_gemm_ws_bytes(BL, (int)C, (int)U)); mx(nabu_gemm_ws_bytes(BL, (int)C, (int)E));
-  mx(nabu_gemm_ws_bytes((int)U, (int)C, BL)); mx(nabu_gemm_ws_bytes((int)E, (int)C, BL));
-  mx(nabu_gemm_ws_bytes(BL, (int)U, (int)C)); mx(nabu_gemm_ws_bytes(BL, (int)E, (int)C));
-  mx(nabu_gemm_ws_bytes((int)U, (int)U, BL)); mx(nabu_gemm_ws_bytes((int)E, (int)(4 * U), BL));
-  mx(nabu_gemm_ws_bytes((int)U, (int)(4 * U), BL)); mx(nabu_gemm_ws_bytes((int)Te, (int)E, (int)L));
-  mx(nabu_colsum_ws_bytes(BL, (int)(4 * U))); mx(nabu_colsum_ws_bytes((int)(B * 16), (int)(F * U + K * F + U)));
-  s.gemm_bytes = (g + 255) / 256 * 256;
-  s.gemm_each = s.gemm_bytes / 4 + 4;
-  s.gemm = take(NS * s.gemm_each);
-  s.total = o;
-  return s;
-}
-
-static int check_sp(const nabu_speller_desc *d) {
-  if (!d || d->size != sizeof(nabu_speller_desc)) return fail(NABU_EINVAL, "speller: bad descriptor size");
-  if (d->B <= 0 || d->Te <= 0 || d->E <= 0 || d->U <= 0 || d->C <= 1 || d->L <= 0)
-    return fail(NABU_EINVAL, "speller: bad dimensions");
-  if (d->num_layers < 1 || d->num_layers > NABU_SPELLER_MAX_LAYERS) return fail(NABU_EUNSUP, "speller: 1..%d layers", NABU_SPELLER_MAX_LAYERS);
-  if (d->U % 4 || d->E % 4) return fail(NABU_EUNSUP, "speller: num_units and encoder dim must be multiples of 4");
-  if (!(d->keep_prob > 0.f && d->keep_prob <= 1.f)) return fail(NABU_EINVAL, "speller: keep_prob out of (0,1]");
-  if (!(d->sample_prob >= 0.f && d->sample_prob <= 1.f)) return fail(NABU_EINVAL, "speller: sample_prob out of [0,1]");
-  nabu_attn_desc a = {sizeof(nabu_attn_desc), d->B, d->Te, d->E, d->U, d->kind, d->K, d->F, d->prob_fn};
-  return check_attn(&a);
-}
-
-// C[M,N] = A·B + A2·B2 (+ beta*C): ONE launch with the split-K reduction inside it when the shape
-// allows (gemm_skinny.hip), else two plain products
-static bool fused_ok(int M, int N, int K1, int lda, int K2, int lda2) {
-  return env_int("NABU_SPELLER_FUSED", 1) && M <= 64 && N % 32 == 0 && K1 > 0 && K1 % 64 == 0 && K2 % 64 == 0 && lda % 4 == 0 && (K2 == 0 || lda2 % 4 == 0);
-}
-static int mm2(int M, int N, int K1, const float *A, int lda, const float *Bm, int ldb, int K2, const float *A2, int lda2,
-               const float *B2, int ldb2, float beta, float *C, int ldc, float *w, const SpWs &W, int sub, float *gw,
-               size_t gwb, nabu_stream_t st) {
-  if (fused_ok(M, N, K1, lda, K2, lda2))
-    return gemm_skinny_fused(M, N, K1, A, lda, Bm, ldb, K2, A2, lda2, B2, ldb2, beta, C, ldc, nullptr,
-                             w + W.fpart + (size_t)sub * W.fpart_each,
-                             reinterpret_cast<unsigned *>(w + W.tickets) + (size_t)sub * 1024, static_cast<hipStream_t>(st));
-  if (int e = mm(false, false, M, N, K1, A, lda, Bm, ldb, beta, C, ldc, nullptr, gw, gwb, st)) return e;
-  if (K2 > 0) return mm(false, false, M, N, K2, A2, lda2, B2, ldb2, 1.f, C, ldc, nullptr, gw, gwb, st);
-  return 0;
-}
-
-}  // namespace nabu
-
-extern "C" size_t nabu_speller_reserve_bytes(const nabu_speller_desc *d) {
-  if (check_sp(d)) return 0;
-  return sp_layout(d).total * sizeof(float);
-}
-extern "C" int nabu_speller_decoder_inputs(const nabu_speller_desc *d, const void *reserve, int32_t *out_ids,
-                                           nabu_stream_t stream) {
-  if (int e = check_sp(d)) return e;
-  NABU_CHECK_ARG(reserve && out_ids, "speller_decoder_inputs: null pointer");
-  const SpLayout R = sp_layout(d);
-  NABU_HIP(hipMemcpyAsync(out_ids, static_cast<const float *>(reserve) + R.ids, (size_t)d->L * d->B * 4,
-                          hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-  return 0;
-}
-extern "C" size_t nabu_speller_ws_bytes(const nabu_speller_desc *d) {
-  if (check_sp(d)) return 0;
-  return sp_ws(d).total * sizeof(float);
-}
-
-// Which decoder steps run as ONE persistent launch (speller_persist.hip) instead of the step chain; the same
-// predicates drive nabu_speller_fwd / _bwd and the query nabu_speller_uses_persistent.
-static bool fwd_takes_persistent(const nabu_speller_desc *d, const SpWs &W) {
-  const int B = d->B, U = d->U, E = d->E, Bn = B / W.NS;
-  const bool cell_epi0 = env_int("NABU_SPELLER_EPILOGUE", 1) && fused_ok(Bn, 4 * U, E, E, U, U);
-  SpPersistDesc pd = {B, d->L, U, E, d->Te, d->C};
-  pd.kind = d->kind; pd.K = d->K; pd.F = d->F;
-  pd.sample_prob = d->sample_prob;
-  if (!(d->num_layers == 1 && (d->kind == 0 || d->kind == 1) && d->prob_fn == 0 && cell_epi0 && W.persist_bytes > 0 &&
-        speller_persist_ok(pd)))
-    return false;
-  // Location-aware attention, more than one launch of 32 utterances, values streamed from L2 (cfg5's geometry): the step
-  // chain on sub-batches of 16 with its round-5 kernels (rows16_kernel, attn_fwd_loc_mfma_kernel) is faster than two
-  // persistent launches (cfg5: 41.0 against 42.7 ms per training step).  NABU_SPELLER_PERSIST=2: the persistent kernel anyway.
-  const char *env = getenv("NABU_SPELLER_PERSIST");
-  const bool chain_fast = d->kind == 1 && B > 32 && Bn <= 64 && E % 16 == 0 && (d->sample_prob == 0.f || sample_step_ok(d->C)) && rows16_ok(Bn, 4 * U, E + U, E) &&
-                          rows16_ok(Bn, U, U, U) && env_int("NABU_SPELLER_ROWS16", 1) && speller_persist_streams_values(pd);
-  return !(chain_fast && !(env && atoi(env) == 2));
-}
-static bool bwd_takes_persistent(const nabu_speller_desc *d, const SpWs &W) {
-  const int B = d->B, U = d->U, E = d->E, Bn = B / W.NS;
-  const bool fuse_shapes = env_int("NABU_SPELLER_EPILOGUE", 1) && d->num_layers == 1 && fused_ok(Bn, U, U, U, 0, 0) &&
-                           fused_ok(Bn, E + U, 4 * U, 4 * U, 0, 0) && (E + U) / 32 <= 1024;
-  SpPersistDesc pd = {B, d->L, U, E, d->Te, d->C};
-  pd.kind = d->kind; pd.K = d->K; pd.F = d->F;
-  // (location-aware attention: the kernel leaves d keys / d attention_v / d conv_proj to attn_param_grads_kernel)
-  if (d->kind == 1) {
-    const nabu_attn_desc adb = sub_attn_desc(d, B);
-    if (!env_int("NABU_SPELLER_DEFER", 1) || attn_defer_slices(&adb) <= 0) return false;
-  }
-  return fuse_shapes && (d->kind == 0 || d->kind == 1) && d->prob_fn == 0 && W.persist_bytes > 0 && speller_persist_bwd_ok(pd);
-}
-extern "C" int nabu_speller_uses_persistent(const nabu_speller_desc *d, int backward) {
-  if (check_sp(d)) return 0;
-  const SpWs W = sp_ws(d);
-  return (backward ? bwd_takes_persistent(d, W) : fwd_takes_persistent(d, W)) ? 1 : 0;
-}
-
-extern "C" int nabu_speller_fwd(const nabu_speller_desc *d, const float *values, const int32_t *enc_len,
-                                const int32_t *ids, const int32_t *dec_len, const nabu_speller_params *p,
-                                float *logits, void *reserve, void *ws, size_t ws_bytes,
-                                nabu_stream_t stream) {
-  if (int e = check_sp(d)) return e;
-  NABU_CHECK_ARG(values && enc_len && ids && dec_len && p && logits && reserve && ws, "speller_fwd: null pointer");
-  const SpLayout R = sp_layout(d);
-  const SpWs W = sp_ws(d);
-  if (ws_bytes < W.total * sizeof(float)) return fail(NABU_EWS, "speller_fwd: workspace too small");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  float *r = static_cast<float *>(reserve), *w = static_cast<float *>(ws);
-  const int B = d->B, L = d->L, U = d->U, E = d->E, Te = d->Te, C = d->C, nl = d->num_layers;
-  float *gw = w + W.gemm;
-  const size_t gwb = W.gemm_bytes;
-  const bool drop = d->keep_prob < 1.f;
-  NABU_HIP(hipMemsetAsync(w + W.tickets, 0, ((size_t)W.NS * 1024 + B + 4) * 4, s));
-  // zero initial state (index 0 of every time-major array)
-  for (int n = 0; n < nl; ++n) {
-    NABU_HIP(hipMemsetAsync(r + R.H[n], 0, (size_t)B * U * 4, s));
-    NABU_HIP(hipMemsetAsync(r + R.Cs[n], 0, (size_t)B * U * 4, s));
-    if (drop) NABU_HIP(hipMemsetAsync(r + R.Ho[n], 0, (size_t)B * U * 4, s));
-  }
-  NABU_HIP(hipMemsetAsync(r + R.ctx, 0, (size_t)B * E * 4, s));
-  NABU_HIP(hipMemsetAsync(r + R.align, 0, (size_t)B * Te * 4, s));
-  if (d->kind == 2) NABU_TRY(first_col_one(B, Te, r + R.align, s));
-  // decoder inputs actually used (scheduled sampling replaces entries of rows 1..L-1 below)
-  int32_t *ids_used = reinterpret_cast<int32_t *>(r + R.ids);
-  NABU_HIP(hipMemcpyAsync(ids_used, ids, (size_t)L * B * 4, hipMemcpyDeviceToDevice, s));
-  const bool sampling = d->sample_prob > 0.f;
-  // keys = memory_layer(values)
-  NABU_TRY(mm(false, false, B * Te, U, E, values, E, p->memory_kernel, U, 0.f, r + R.keys, U, nullptr, gw, gwb, stream));
-  const int NS = W.NS, Bn = B / NS;
-  const nabu_attn_desc adn = sub_attn_desc(d, Bn);
-  const size_t attn_fwd_wsb_n = nabu_attn_fwd_ws_bytes(&adn);
-  // LSTM cell folded into the step product's last workgroup (gemm_skinny.hip) when the shapes allow:
-  // the product then runs against gate-interleaved copies of the kernels' dense rows
-  const int epi_env = env_int("NABU_SPELLER_EPILOGUE", 1);
-  bool cell_epi[NABU_SPELLER_MAX_LAYERS];
-  for (int n = 0; n < nl; ++n) {
-    const int K1 = n == 0 ? E : U;
-    cell_epi[n] = epi_env && fused_ok(Bn, 4 * U, K1, K1, U, U);
-    if (cell_epi[n]) {
-      const int rows = K1 + U;
-      const float *src = p->lstm_kernel[n] + (n == 0 ? (size_t)C * 4 * U : 0);
-      hipLaunchKernelGGL(permute_gates_kernel, dim3(grid1((size_t)rows * 4 * U)), dim3(256), 0, s, rows, U, src,
-                         w + W.kperm[n]);
-      NABU_LAUNCH_CHECK();
-    }
-  }
-  // the whole step loop as ONE persistent launch (speller_persist.hip) where the geometry allows:
-  // one LSTM layer, vanilla softmax attention, teacher forcing, no dropout, B = 32 (cfg3)
-  SpPersistDesc pd = {B, L, U, E, Te, C};
-  pd.kind = d->kind; pd.K = d->K; pd.F = d->F;
-  pd.keep_prob = d->keep_prob; pd.seed = d->seed; pd.seed_offset = d->seed_offset;     // nl == 1: offset + t*nl + n = offset + t
-  pd.sample_prob = d->sample_prob; pd.sample_seed = d->sample_seed; pd.sample_offset = d->sample_offset;
-  pd.drop_scale = drop ? r + R.dscale : nullptr;
-  pd.sample_draws = d->sample_prob > 0.f ? reinterpret_cast<unsigned *>(r + R.sdraw) : nullptr;
-  const bool persist = fwd_takes_persistent(d, W);
-  if (persist)
-    NABU_TRY(speller_persist_fwd(pd, dec_len, enc_len, ids_used, w + W.kperm[0], p->lstm_bias[0], p->lstm_kernel[0],
-                               p->query_kernel, p->attention_v, r + R.keys, values, p->conv_kernel, p->conv_proj, r + R.H[0],
-                               drop ? r + R.Ho[0] : nullptr, r + R.Cs[0], r + R.acts[0], r + R.q, r + R.ctx, r + R.align,
-                               reinterpret_cast<int *>(w + W.status), w + W.persist, W.persist_bytes, s, p->out_kernel,
-                               p->out_bias, ids_used));
-  unsigned *atk = env_int("NABU_SPELLER_ATTN_FUSED", 1) ? reinterpret_cast<unsigned *>(w + W.tickets) + (size_t)NS * 1024 : nullptr;
-  SubStreams ss;
-  // sub-batches of <= 16 utterances: the cell's product ([context | h] . kernel with the cell as epilogue) and the query
-  // by rows16_kernel (gemm_skinny.hip) over weights re-blocked once per pass; NABU_SPELLER_ROWS16=0: gemm_skinny_fused
-  const bool r16 = !persist && nl == 1 && cell_epi[0] && env_int("NABU_SPELLER_ROWS16", 1) && E % 16 == 0 &&
-                   rows16_ok(Bn, 4 * U, E + U, E) && rows16_ok(Bn, U, U, U);
-  if (r16) {
-    NABU_TRY(rows16_swizzle_kn(4 * U, E + U, p->lstm_kernel[0] + (size_t)C * 4 * U, 4 * U, w + W.kxh_sw, U, s));
-    NABU_TRY(rows16_swizzle_kn(U, U, p->query_kernel, U, w + W.wq_sw, 0, s));
-  }
-  if (!persist) {
-  NABU_TRY(sub_streams(NS, s, &ss));
-  NABU_TRY(sub_fork(ss));
-  }
-  auto fwd_chain = [&](int sub) -> int {
-    for (int t = 0; t < L; ++t) {
-      const int b0 = sub * Bn;
-      nabu_stream_t st = static_cast<nabu_stream_t>(ss.st[sub]);
-      float *gws = gw + (size_t)sub * W.gemm_each;
-      float *z = w + W.z + (size_t)b0 * 4 * U;
-      const int32_t *dlen = dec_len + b0;
-      for (int n = 0; n < nl; ++n) {
-        const float *Kn = p->lstm_kernel[n];
-        float *Hn = r + R.H[n] + (size_t)b0 * U, *Cn = r + R.Cs[n] + (size_t)b0 * U;
-        const size_t cur = (size_t)t * B * U, nxt = (size_t)(t + 1) * B * U;
-        if (cell_epi[n]) {   // product + cell in one launch
-          SkinnyEpilogue ep = {};
-          ep.kind = 1; ep.U = U; ep.step = t; ep.seq_len = dlen;
-          ep.bias = p->lstm_bias[n];
-          ep.emb = n == 0 ? Kn : nullptr;
-          ep.ids = n == 0 ? ids_used + (size_t)t * B + b0 : nullptr;
-          ep.c_prev = Cn + cur; ep.h_prev = Hn + cur;
-          ep.acts = r + R.acts[n] + (size_t)t * B * 4 * U + (size_t)b0 * 4 * U;
-          ep.c_new = Cn + nxt; ep.h_new = Hn + nxt;
-          const int K1 = n == 0 ? E : U;
-          const float *x1 = n == 0 ? r + R.ctx + (size_t)t * B * E + (size_t)b0 * E : r + R.Ho[n - 1] + nxt + (size_t)b0 * U;
-          const float *Kp = w + W.kperm[n];
-          if (r16) {
-            if (drop) {      // the cell's output dropout in the same launch (the mask of dropout_rows below)
-              ep.ho_new = r + R.Ho[n] + nxt + (size_t)b0 * U;
-              ep.keep = d->keep_prob; ep.seed = d->seed; ep.seed_offset = d->seed_offset + (unsigned long long)t * nl + n;
-              ep.row0 = b0;
-            }
-            NABU_TRY(rows16(Bn, 4 * U, E + U, x1, E, w + W.kxh_sw, 0.f, nullptr, 0, ss.st[sub], &ep, nullptr, E, Hn + cur, U));
-          } else
-          NABU_TRY(gemm_skinny_fused(Bn, 4 * U, K1, x1, K1, Kp, 4 * U, U, Hn + cur, U, Kp + (size_t)K1 * 4 * U, 4 * U, 0.f, z,
-                                   4 * U, nullptr, w + W.fpart + (size_t)sub * W.fpart_each,
-                                   reinterpret_cast<unsigned *>(w + W.tickets) + (size_t)sub * 1024, ss.st[sub], &ep));
-        } else if (n == 0) {
-          NABU_TRY(mm2(Bn, 4 * U, E, r + R.ctx + (size_t)t * B * E + (size_t)b0 * E, E, Kn + (size_t)C * 4 * U, 4 * U, U,
-                     Hn + cur, U, Kn + (size_t)(C + E) * 4 * U, 4 * U, 0.f, z, 4 * U, w, W, sub, gws, gwb, st));
-          NABU_TRY(nabu_lstm_cell_fwd(Bn, U, t, dlen, z, p->lstm_bias[0], Kn, ids_used + (size_t)t * B + b0, Cn + cur,
-                                    Hn + cur, r + R.acts[0] + (size_t)t * B * 4 * U + (size_t)b0 * 4 * U, Cn + nxt,
-                                    Hn + nxt, st));
-        } else {
-          NABU_TRY(mm2(Bn, 4 * U, U, r + R.Ho[n - 1] + nxt + (size_t)b0 * U, U, Kn, 4 * U, U, Hn + cur, U,
-                     Kn + (size_t)U * 4 * U, 4 * U, 0.f, z, 4 * U, w, W, sub, gws, gwb, st));
-          NABU_TRY(nabu_lstm_cell_fwd(Bn, U, t, dlen, z, p->lstm_bias[n], nullptr, nullptr, Cn + cur, Hn + cur,
-                                    r + R.acts[n] + (size_t)t * B * 4 * U + (size_t)b0 * 4 * U, Cn + nxt, Hn + nxt, st));
-        }
-        if (drop && !(r16 && cell_epi[n]))
-          NABU_TRY(dropout_rows((size_t)Bn * U, Hn + nxt, r + R.Ho[n] + nxt + (size_t)b0 * U, d->keep_prob, d->seed,
-                              d->seed_offset + (unsigned long long)t * nl + n, (size_t)b0 * U, ss.st[sub]));
-      }
-      const float *htop = r + R.Ho[nl - 1] + (size_t)(t + 1) * B * U + (size_t)b0 * U;
-      float *qt = r + R.q + (size_t)t * B * U + (size_t)b0 * U;
-      if (r16) NABU_TRY(rows16(Bn, U, U, htop, U, w + W.wq_sw, 0.f, qt, U, ss.st[sub]));
-      else
-      NABU_TRY(mm2(Bn, U, U, htop, U, p->query_kernel, U, 0, nullptr, 0, nullptr, 0, 0.f, qt, U, w, W, sub, gws, gwb, st));
-      NABU_TRY(attn_fwd_impl(&adn, t, dlen, enc_len + b0, r + R.keys + (size_t)b0 * Te * U, values + (size_t)b0 * Te * E, qt,
-                           p->attention_v, p->conv_kernel, p->conv_proj,
-                           r + R.align + (size_t)t * B * Te + (size_t)b0 * Te, r + R.ctx + (size_t)t * B * E + (size_t)b0 * E,
-                           r + R.align + (size_t)(t + 1) * B * Te + (size_t)b0 * Te,
-                           r + R.ctx + (size_t)(t + 1) * B * E + (size_t)b0 * E, r + R.znorm + (size_t)t * B + b0,
-                           w + W.attn + (size_t)sub * W.attn_each, attn_fwd_wsb_n, st, atk ? atk + b0 : nullptr));
-      if (sampling && t + 1 < L) {
-        // ScheduledEmbeddingTrainingHelper: the step's logits decide the next input of selected rows
-        float *lt = r + R.logits_tm + (size_t)t * B * C + (size_t)b0 * C;
-        if (sample_step_ok(C)) {     // one launch, logits only for sampled rows
-          NABU_TRY(sample_step(Bn, C, U, E, htop, U, r + R.ctx + (size_t)(t + 1) * B * E + (size_t)b0 * E, E, p->out_kernel,
-                             p->out_bias, d->sample_prob, d->sample_seed, d->sample_offset + (unsigned long long)t,
-                             ids + (size_t)(t + 1) * B + b0, ids_used + (size_t)(t + 1) * B + b0, b0, ss.st[sub]));
-          continue;
-        }
-        NABU_TRY(mm(false, false, Bn, C, U, htop, U, p->out_kernel, C, 0.f, lt, C, p->out_bias, gws, gwb, st));
-        NABU_TRY(mm(false, false, Bn, C, E, r + R.ctx + (size_t)(t + 1) * B * E + (size_t)b0 * E, E,
-                  p->out_kernel + (size_t)U * C, C, 1.f, lt, C, nullptr, gws, gwb, st));
-        NABU_TRY(sample_ids_rows(Bn, C, lt, d->sample_prob, d->sample_seed, d->sample_offset + (unsigned long long)t,
-                               ids + (size_t)(t + 1) * B + b0, ids_used + (size_t)(t + 1) * B + b0, b0, ss.st[sub]));
-      }
-    }
-    return 0;
-  };
-  if (!persist) {
-  {  // join the side streams before an error is propagated: chains already enqueued must not outlive the call
-    const int e_run = run_subs(NS, fwd_chain), e_join = sub_join(ss);
-    if (e_run) return e_run;
-    NABU_TRY(e_join);
-  }
-  }
-  // output projection of all steps: [h_t, ctx_t]·W + b, then batch-major + impute_finished
-  float *ltm = r + R.logits_tm;
-  NABU_TRY(mm(false, false, L * B, C, U, r + R.Ho[nl - 1] + (size_t)B * U, U, p->out_kernel, C, 0.f, ltm, C, p->out_bias, gw, gwb, stream));
-  NABU_TRY(mm(false, false, L * B, C, E, r + R.ctx + (size_t)B * E, E, p->out_kernel + (size_t)U * C, C, 1.f, ltm, C, nullptr, gw, gwb, stream));
-  NABU_TRY(nabu_swap01_f32(L, B, C, ltm, logits, stream));
-  NABU_TRY(nabu_mask_time_f32(B, L, C, logits, dec_len, stream));
-  (void)s;
-  return 0;
-}
-
-extern "C" int nabu_speller_bwd(const nabu_speller_desc *d, const float *values, const int32_t *enc_len,
-                                const int32_t *ids, const int32_t *dec_len, const nabu_speller_params *p,
-                                const float *dlogits, void *reserve, const nabu_speller_grads *g,
-                                float *dvalues, void *ws, size_t ws_bytes, nabu_stream_t stream) {
-  if (int e = check_sp(d)) return e;
-  NABU_CHECK_ARG(values && enc_len && ids && dec_len && p && dlogits && reserve && g && dvalues && ws,
-                 "speller_bwd: null pointer");
-  const SpLayout R = sp_layout(d);
-  const SpWs W = sp_ws(d);
-  if (ws_bytes < W.total * sizeof(float)) return fail(NABU_EWS, "speller_bwd: workspace too small");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  float *r = static_cast<float *>(reserve), *w = static_cast<float *>(ws);
-  const int B = d->B, L = d->L, U = d->U, E = d->E, Te = d->Te, C = d->C, nl = d->num_layers, F = d->F, K = d->K;
-  float *gw = w + W.gemm;
-  const size_t gwb = W.gemm_bytes;
-  const bool drop = d->keep_prob < 1.f;
-  const int BL = B * L;
-  float *dl = w + W.dl, *dH = w + W.dH, *dCtx = w + W.dCtx, *dkeys = w + W.dkeys, *dq = w + W.dq;
-  const float *htop_all = r + R.Ho[nl - 1] + (size_t)B * U;   // h_top[t], t = 0..L-1
-  const float *ctx1 = r + R.ctx + (size_t)B * E;              // ctx[t]
-  // output projection
-  NABU_TRY(nabu_swap01_f32(B, L, C, dlogits, dl, stream));      // [B,L,C] -> [L,B,C]
-  NABU_TRY(mm(true, false, U, C, BL, htop_all, U, dl, C, 0.f, g->out_kernel, C, nullptr, gw, gwb, stream));
-  NABU_TRY(mm(true, false, E, C, BL, ctx1, E, dl, C, 0.f, g->out_kernel + (size_t)U * C, C, nullptr, gw, gwb, stream));
-  NABU_TRY(nabu_colsum_f32(BL, C, dl, C, 0.f, g->out_bias, gw, gwb, stream));
-  NABU_TRY(mm(false, true, BL, U, C, dl, C, p->out_kernel, C, 0.f, dH, U, nullptr, gw, gwb, stream));
-  NABU_TRY(mm(false, true, BL, E, C, dl, C, p->out_kernel + (size_t)U * C, C, 0.f, dCtx, E, nullptr, gw, gwb, stream));
-  NABU_HIP(hipMemsetAsync(dkeys, 0, (size_t)B * Te * U * 4, s));
-  NABU_HIP(hipMemsetAsync(w + W.tickets, 0, ((size_t)W.NS * 1024 + B + 4) * 4, s));
-  const int S = W.S;          // per-slice partial rows of the attention backward (slices of a sub-batch's utterances)
-  NABU_HIP(hipMemsetAsync(w + W.dv, 0, (size_t)B * S * U * 4, s));
-  if (d->kind == 1) {
-    NABU_HIP(hipMemsetAsync(w + W.dwf, 0, (size_t)B * S * F * U * 4, s));
-    NABU_HIP(hipMemsetAsync(w + W.dck, 0, (size_t)B * K * F * 4, s));
-  }
-  for (int n = 0; n < nl; ++n) {
-    NABU_HIP(hipMemsetAsync(w + W.dh[0][n], 0, (size_t)B * U * 4, s));
-    NABU_HIP(hipMemsetAsync(w + W.dc[0][n], 0, (size_t)B * U * 4, s));
-  }
-  // transposed copies of the weights the per-step gradient products use: dz·W^T becomes a
-  // row-major product with M = B rows, which the skinny GEMM kernel streams in a few microseconds
-  NABU_TRY(transpose(U, U, p->query_kernel, U, w + W.wqT, s));
-  for (int n = 0; n < nl; ++n) {
-    const float *Kn = p->lstm_kernel[n];
-    if (n == 0) {
-      NABU_TRY(transpose(E, 4 * U, Kn + (size_t)C * 4 * U, 4 * U, w + W.kxT[0], s));
-      NABU_TRY(transpose(U, 4 * U, Kn + (size_t)(C + E) * 4 * U, 4 * U, w + W.khT[0], s));
-    } else {
-      NABU_TRY(transpose(U, 4 * U, Kn, 4 * U, w + W.kxT[n], s));
-      NABU_TRY(transpose(U, 4 * U, Kn + (size_t)U * 4 * U, 4 * U, w + W.khT[n], s));
-    }
-  }
-  const int NS = W.NS, Bn = B / NS;
-  const nabu_attn_desc adn = sub_attn_desc(d, Bn);
-  const size_t attn_wsb_n = nabu_attn_bwd_ws_bytes(&adn);
-  SubStreams ss;
-  // single-layer decoder without dropout (the BASELINE recipes): the cell's backward pass is folded into the
-  // last workgroup of dq·Wq^T, and dz·[Kx^T | Kh^T] is ONE product whose [B, E+U] result carries d context and
-  // d h to the next step — 4 dependent launches per step instead of 7
-  const int epi_env_b = env_int("NABU_SPELLER_EPILOGUE", 1);
-  const bool fuse_shapes = epi_env_b && nl == 1 && fused_ok(Bn, U, U, U, 0, 0) && fused_ok(Bn, E + U, 4 * U, 4 * U, 0, 0) &&
-                           (E + U) / 32 <= 1024;
-  // the whole step loop as ONE persistent launch (speller_persist.hip), as in the forward pass (output dropout is
-  // applied inside it: the scale factors are drawn again from the Philox stream by a small launch in front of it)
-  SpPersistDesc pd = {B, L, U, E, Te, C};
-  pd.kind = d->kind; pd.K = d->K; pd.F = d->F;
-  pd.keep_prob = d->keep_prob; pd.seed = d->seed; pd.seed_offset = d->seed_offset;
-  pd.drop_scale = drop ? const_cast<float *>(r + R.dscale) : nullptr;
-  const bool persist = bwd_takes_persistent(d, W);
-  // sub-batches of <= 16 utterances: both products of a step by rows16_kernel (no split-K hand-off between workgroups:
-  // 13 -> 7 us per launch; its cell epilogue applies the output dropout's mask); NABU_SPELLER_ROWS16=0: gemm_skinny_fused
-  const bool r16 = fuse_shapes && !persist && E % 32 == 0 && env_int("NABU_SPELLER_SPLIT", 1) && env_int("NABU_SPELLER_ROWS16", 1) &&
-                   rows16_ok(Bn, U, U, U) && rows16_ok(Bn, E + U, 4 * U, 4 * U);
-  const bool fuse_b = fuse_shapes && (!drop || persist || r16);      // (gemm_skinny_fused's cell epilogue has no dropout)
-  if (fuse_b) NABU_TRY(transpose(E + U, 4 * U, p->lstm_kernel[0] + (size_t)C * 4 * U, 4 * U, w + W.kxhT, s));
-  const bool split_b = fuse_b && E % 32 == 0 && env_int("NABU_SPELLER_SPLIT", 1);
-  if (r16) {
-    NABU_TRY(rows16_swizzle(U, U, p->query_kernel, U, w + W.wq_sw, s));
-    NABU_TRY(rows16_swizzle(E + U, 4 * U, p->lstm_kernel[0] + (size_t)C * 4 * U, 4 * U, w + W.kxh_sw, s));
-  }
-  if (persist)
-    NABU_TRY(speller_persist_bwd(pd, dec_len, enc_len, w + W.kxhT, p->query_kernel, p->attention_v, r + R.keys, values,
-                               r + R.acts[0], r + R.Cs[0], r + R.q, r + R.ctx, r + R.align, dH, dCtx, dq, w + W.dz[0],
-                               dkeys, w + W.dv8, reinterpret_cast<int *>(w + W.status), w + W.persist, W.persist_bytes, s,
-                               p->conv_kernel, p->conv_proj, w + W.ds_all, d->kind == 1 ? w + W.cf_all : nullptr,
-                               d->kind == 1 ? w + W.dck8 : nullptr));
-  if (!persist) {
-    NABU_TRY(sub_streams(NS, s, &ss));
-    NABU_TRY(sub_fork(ss));
-  }
-  // d keys / d attention_v / d conv_proj of all steps in ONE launch after the chain (attn_param_grads_kernel)
-  nabu_attn_desc adb = adn;      // the whole batch
-  adb.B = B;
-  // (the persistent kernel accumulates them itself for vanilla attention and leaves them to that launch for
-  // location-aware attention)
-  const int Sp = ((!persist || d->kind == 1) && env_int("NABU_SPELLER_DEFER", 1)) ? attn_defer_slices(&adb) : 0;
-  const bool defer = Sp > 0;
-  unsigned *atk = env_int("NABU_SPELLER_ATTN_FUSED", 1) ? reinterpret_cast<unsigned *>(w + W.tickets) + (size_t)NS * 1024 : nullptr;
-  auto bwd_chain = [&](int sub) -> int {
-  int cur = 0;   // index of the carries coming from step t+1
-  bool have_carry = false;
-  for (int t = L - 1; t >= 0; --t) {
-    {
-      const int b0 = sub * Bn;
-      nabu_stream_t st = static_cast<nabu_stream_t>(ss.st[sub]);
-      float *gws = gw + (size_t)sub * W.gemm_each;
-      const int32_t *dlen = dec_len + b0;
-      float *dCt = dCtx + (size_t)t * B * E + (size_t)b0 * E;
-      if (have_carry && fuse_b && !split_b) {
-        hipLaunchKernelGGL(add_rows_kernel, dim3(grid1((size_t)Bn * E)), dim3(256), 0, ss.st[sub], Bn, E,
-                           w + W.dxh[(t + 1) & 1] + (size_t)b0 * (E + U), E + U, dCt, E);
-        NABU_LAUNCH_CHECK();
-      } else if (have_carry && !fuse_b) {
-        NABU_TRY(nabu_axpy_f32((size_t)Bn * E, 1.f, w + W.dctx[(t + 1) & 1] + (size_t)b0 * E, dCt, st));
-      }
-      float *dal_out = d->kind == 1 ? w + W.dal[t & 1] + (size_t)b0 * Te : nullptr;
-      const float *dal_carry = (d->kind == 1 && have_carry) ? w + W.dal[(t + 1) & 1] + (size_t)b0 * Te : nullptr;
-      float *dqt = dq + (size_t)t * B * U + (size_t)b0 * U;
-      NABU_TRY(attn_bwd_impl(&adn, t, dlen, enc_len + b0, r + R.keys + (size_t)b0 * Te * U, values + (size_t)b0 * Te * E,
-                           r + R.q + (size_t)t * B * U + (size_t)b0 * U, p->attention_v, p->conv_kernel, p->conv_proj,
-                           r + R.align + (size_t)t * B * Te + (size_t)b0 * Te,
-                           r + R.align + (size_t)(t + 1) * B * Te + (size_t)b0 * Te,
-                           r + R.ctx + (size_t)(t + 1) * B * E + (size_t)b0 * E, dCt, dal_carry, dqt,
-                           dkeys + (size_t)b0 * Te * U, w + W.dv + (size_t)b0 * S * U,
-                           d->kind == 1 ? w + W.dwf + (size_t)b0 * S * F * U : nullptr,
-                           d->kind == 1 ? w + W.dck + (size_t)b0 * K * F : nullptr, dal_out,
-                           r + R.znorm + (size_t)t * B + b0, w + W.attn + (size_t)sub * W.attn_each, attn_wsb_n, st,
-                           atk ? atk + b0 : nullptr,
-                           defer ? w + W.ds_all + ((size_t)t * B + b0) * Te : nullptr,
-                           (defer && d->kind == 1) ? w + W.cf_all + ((size_t)t * B + b0) * Te * F : nullptr));
-      float *dHt = dH + (size_t)t * B * U + (size_t)b0 * U;
-      if (fuse_b) {
-        float *dzt = w + W.dz[0] + (size_t)t * B * 4 * U + (size_t)b0 * 4 * U;
-        const float *Cn = r + R.Cs[0] + (size_t)b0 * U;
-        SkinnyEpilogue ep = {};
-        ep.kind = 2; ep.U = U; ep.step = t; ep.seq_len = dlen;
-        ep.acts = r + R.acts[0] + (size_t)t * B * 4 * U + (size_t)b0 * 4 * U;
-        ep.c_new = const_cast<float *>(Cn + (size_t)(t + 1) * B * U);
-        ep.c_prev = Cn + (size_t)t * B * U;
-        ep.dh2 = have_carry ? w + W.dxh[(t + 1) & 1] + (size_t)b0 * (E + U) + E : nullptr;
-        ep.ld_dh2 = E + U;
-        ep.dc_in = w + W.dc[cur][0] + (size_t)b0 * U;
-        ep.dz = dzt;
-        ep.dc_out = w + W.dc[cur ^ 1][0] + (size_t)b0 * U;
-        ep.keep = drop ? d->keep_prob : 1.f; ep.seed = d->seed; ep.seed_offset = d->seed_offset + (unsigned long long)t;
-        ep.row0 = b0;
-        float *fp = w + W.fpart + (size_t)sub * W.fpart_each;
-        unsigned *tk = reinterpret_cast<unsigned *>(w + W.tickets) + (size_t)sub * 1024;
-        if (r16) {
-          NABU_TRY(rows16(Bn, U, U, dqt, U, w + W.wq_sw, 1.f, dHt, U, ss.st[sub], &ep));
-          if (t > 0) {
-            SkinnySplit sp = {w + W.dxh[t & 1] + (size_t)b0 * (E + U) + E, E + U, E, 0.f};
-            NABU_TRY(rows16(Bn, E + U, 4 * U, dzt, 4 * U, w + W.kxh_sw, 1.f, dCtx + (size_t)(t - 1) * B * E + (size_t)b0 * E, E,
-                          ss.st[sub], nullptr, &sp));
-          }
-          have_carry = true;
-          cur ^= 1;
-          continue;
-        }
-        NABU_TRY(gemm_skinny_fused(Bn, U, U, dqt, U, w + W.wqT, U, 0, nullptr, 0, nullptr, 0, 1.f, dHt, U, nullptr, fp, tk,
-                                 ss.st[sub], &ep));
-        if (split_b && t > 0) {
-          // d context of step t-1 goes straight into that step's dCtx row block (on top of the output
-          // projection's share), d h into the carry: no separate add launch in front of the next attention
-          SkinnySplit sp = {w + W.dxh[t & 1] + (size_t)b0 * (E + U) + E, E + U, E, 0.f};
-          NABU_TRY(gemm_skinny_fused(Bn, E + U, 4 * U, dzt, 4 * U, w + W.kxhT, E + U, 0, nullptr, 0, nullptr, 0, 1.f,
-                                   dCtx + (size_t)(t - 1) * B * E + (size_t)b0 * E, E, nullptr, fp, tk, ss.st[sub], nullptr,
-                                   &sp));
-        } else {
-          NABU_TRY(gemm_skinny_fused(Bn, E + U, 4 * U, dzt, 4 * U, w + W.kxhT, E + U, 0, nullptr, 0, nullptr, 0, 0.f,
-                                   w + W.dxh[t & 1] + (size_t)b0 * (E + U), E + U, nullptr, fp, tk, ss.st[sub], nullptr));
-        }
-        have_carry = true;
-        cur ^= 1;
-        continue;
-      }
-      NABU_TRY(mm2(Bn, U, U, dqt, U, w + W.wqT, U, 0, nullptr, 0, nullptr, 0, 1.f, dHt, U, w, W, sub, gws, gwb, st));
-      const float *dtop = dHt;
-      for (int n = nl - 1; n >= 0; --n) {
-        const float *dh_in = dtop;
-        if (drop) {
-          NABU_TRY(dropout_rows((size_t)Bn * U, dtop, w + W.tmp + (size_t)b0 * U, d->keep_prob, d->seed,
-                              d->seed_offset + (unsigned long long)t * nl + n, (size_t)b0 * U, ss.st[sub]));
-          dh_in = w + W.tmp + (size_t)b0 * U;
-        }
-        float *dzt = w + W.dz[n] + (size_t)t * B * 4 * U + (size_t)b0 * 4 * U;
-        const float *Cn = r + R.Cs[n] + (size_t)b0 * U;
-        NABU_TRY(nabu_lstm_cell_bwd(Bn, U, t, dlen, r + R.acts[n] + (size_t)t * B * 4 * U + (size_t)b0 * 4 * U,
-                                  Cn + (size_t)(t + 1) * B * U, Cn + (size_t)t * B * U, dh_in,
-                                  w + W.dh[cur][n] + (size_t)b0 * U, w + W.dc[cur][n] + (size_t)b0 * U, dzt,
-                                  w + W.dc[cur ^ 1][n] + (size_t)b0 * U, st));
-        if (n == 0) {
-          float *nx = w + W.dctx[t & 1] + (size_t)b0 * E;
-          NABU_TRY(mm2(Bn, E, 4 * U, dzt, 4 * U, w + W.kxT[0], E, 0, nullptr, 0, nullptr, 0, 0.f, nx, E, w, W, sub, gws, gwb, st));
-          NABU_TRY(mm2(Bn, U, 4 * U, dzt, 4 * U, w + W.khT[0], U, 0, nullptr, 0, nullptr, 0, 0.f,
-                     w + W.dh[cur ^ 1][0] + (size_t)b0 * U, U, w, W, sub, gws, gwb, st));
-        } else {
-          NABU_TRY(mm2(Bn, U, 4 * U, dzt, 4 * U, w + W.kxT[n], U, 0, nullptr, 0, nullptr, 0, 0.f, w + W.dx + (size_t)b0 * U, U,
-                     w, W, sub, gws, gwb, st));
-          NABU_TRY(mm2(Bn, U, 4 * U, dzt, 4 * U, w + W.khT[n], U, 0, nullptr, 0, nullptr, 0, 0.f,
-                     w + W.dh[cur ^ 1][n] + (size_t)b0 * U, U, w, W, sub, gws, gwb, st));
-          dtop = w + W.dx + (size_t)b0 * U;
-        }
-      }
-    }
-    have_carry = true;
-    cur ^= 1;
-  }
-  return 0;
-  };
-  if (!persist) {
-  {
-    const int e_run = run_subs(NS, bwd_chain), e_join = sub_join(ss);
-    if (e_run) return e_run;
-    NABU_TRY(e_join);
-  }
-  }
-  if (defer)
-    NABU_TRY(attn_param_grads(&adb, Sp, L, dec_len, enc_len, r + R.keys, r + R.q, p->attention_v, p->conv_proj, w + W.ds_all,
-                            w + W.cf_all, dkeys, w + W.dv16, w + W.dwf16, s));
-  // sums over steps as single GEMMs
-  NABU_TRY(mm(true, false, U, U, BL, htop_all, U, dq, U, 0.f, g->query_kernel, U, nullptr, gw, gwb, stream));
-  for (int n = 0; n < nl; ++n) {
-    const float *dzn = w + W.dz[n];
-    float *gK = g->lstm_kernel[n];
-    if (n == 0) {
-      NABU_TRY(nabu_scatter_rows_f32(C, BL, 4 * U, reinterpret_cast<const int32_t *>(r + R.ids), dzn, gK, stream));
-      NABU_TRY(mm(true, false, E, 4 * U, BL, r + R.ctx, E, dzn, 4 * U, 0.f, gK + (size_t)C * 4 * U, 4 * U, nullptr, gw, gwb, stream));
-      NABU_TRY(mm(true, false, U, 4 * U, BL, r + R.H[0], U, dzn, 4 * U, 0.f, gK + (size_t)(C + E) * 4 * U, 4 * U, nullptr, gw, gwb, stream));
-    } else {
-      NABU_TRY(mm(true, false, U, 4 * U, BL, r + R.Ho[n - 1] + (size_t)B * U, U, dzn, 4 * U, 0.f, gK, 4 * U, nullptr, gw, gwb, stream));
-      NABU_TRY(mm(true, false, U, 4 * U, BL, r + R.H[n], U, dzn, 4 * U, 0.f, gK + (size_t)U * 4 * U, 4 * U, nullptr, gw, gwb, stream));
-    }
-    NABU_TRY(nabu_colsum_f32(BL, 4 * U, dzn, 4 * U, 0.f, g->lstm_bias[n], gw, gwb, stream));
-  }
-  if (persist && !defer) NABU_TRY(nabu_colsum_f32(B * 8, U, w + W.dv8, U, 0.f, g->attention_v, gw, gwb, stream));
-  else if (defer)        NABU_TRY(nabu_colsum_f32(B * Sp, U, w + W.dv16, U, 0.f, g->attention_v, gw, gwb, stream));
-  else            NABU_TRY(nabu_colsum_f32(B * S, U, w + W.dv, U, 0.f, g->attention_v, gw, gwb, stream));
-  if (d->kind == 1) {
-    if (defer) NABU_TRY(nabu_colsum_f32(B * Sp, F * U, w + W.dwf16, F * U, 0.f, g->conv_proj, gw, gwb, stream));
-    else       NABU_TRY(nabu_colsum_f32(B * S, F * U, w + W.dwf, F * U, 0.f, g->conv_proj, gw, gwb, stream));
-    if (persist) NABU_TRY(nabu_colsum_f32(B * 8, K * F, w + W.dck8, K * F, 0.f, g->conv_kernel, gw, gwb, stream));
-    else         NABU_TRY(nabu_colsum_f32(B, K * F, w + W.dck, K * F, 0.f, g->conv_kernel, gw, gwb, stream));
-  }
-  // keys = values·Wmem ; context_t = align_t^T·values
-  NABU_TRY(mm(true, false, E, U, B * Te, values, E, dkeys, U, 0.f, g->memory_kernel, U, nullptr, gw, gwb, stream));
-  NABU_TRY(mm(false, true, B * Te, E, U, dkeys, U, p->memory_kernel, U, 0.f, dvalues, E, nullptr, gw, gwb, stream));
-  const float *al1 = r + R.align + (size_t)B * Te;
-  // dvalues[b] += align[:, b, :]^T · dCtx[:, b, :] for every utterance: one batched launch
-  NABU_TRY(gemm_batched_f32(true, false, Te, E, L, al1, B * Te, Te, dCtx, B * E, E, 1.f, dvalues, E, (long long)Te * E, B, s));
   return 0;
 }

@@ -33,30 +33,6 @@ __device__ __forceinline__ float wave_max(float m) {
   return m;
 }
 
-// one mechanism of a launch
-struct MMem {
-  int Te, E, coff, S;            // encoder frames, encoder dim, column offset in the [B, sum E] buffers, frame slices
-  const int32_t *enc_len;
-  const float *keys, *values, *v, *ck, *wf;
-  const float *align_prev, *align_c;   // [B,Te]: previous alignment; this step's alignment (backward)
-  float *align;                  // forward output
-  float *znorm;                  // [B] normaliser of normalized_sigmoid
-  float *part;                   // forward: [B,S,E+4] partial context + (local max, local sum); backward: [B,S,U] dq
-  unsigned *tickets;             // [B] zeroed counters (left zero)
-  // backward
-  const float *dalign_in;
-  float *dalign_out, *dkeys, *dv_part, *dwf_part, *dck_part, *dcf_g;
-};
-struct MArgs {
-  int B, U, SE, MU, kind, K, F, step, prob_fn;
-  const int32_t *dec_len;
-  const float *q;                // [B, M U]
-  const float *ctx_prev;         // [B, sum E]
-  float *ctx;                    // [B, sum E] (backward: this step's contexts, read only)
-  const float *dctx;             // [B, sum E]
-  float *dq;                     // [B, M U]
-  MMem m[MM];
-};
 
 // hand-off between workgroups inside a launch: write-through store, L1-bypassing load
 __device__ __forceinline__ void xst(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -576,17 +552,15 @@ __global__ __launch_bounds__(256) void put_cols_kernel(int R, int Cn, const floa
 }
 
 // ---------------------------------------------------------------------------
-struct Geo {
-  int M, SE, MU, S[MM], Smax, coff[MM];
-  size_t lds_f, lds_b;
-};
 
 static nabu_attn_desc mem_desc(const nabu_speller_multi_desc *d, int m) {
   nabu_attn_desc a = {sizeof(nabu_attn_desc), d->B, d->Te[m], d->E[m], d->U, d->kind, d->K, d->F, d->prob_fn};
   return a;
 }
 
-static int check_md(const nabu_speller_multi_desc *d, Geo *g) {
+}  // namespace
+
+int multi_attn_geo(const nabu_speller_multi_desc *d, MultiAttnGeo *g) {
   if (!d || d->size != sizeof(nabu_speller_multi_desc)) return fail(NABU_EINVAL, "speller_multi: bad descriptor size");
   if (d->M < 1 || d->M > MM) return fail(NABU_EUNSUP, "speller_multi: 1..%d encoded inputs", MM);
   if (d->B <= 0 || d->U <= 0 || d->C <= 1 || d->L <= 0) return fail(NABU_EINVAL, "speller_multi: bad dimensions");
@@ -614,109 +588,14 @@ static int check_md(const nabu_speller_multi_desc *d, Geo *g) {
   return 0;
 }
 
-struct MLayout {
-  size_t H[NABU_SPELLER_MAX_LAYERS], Cs[NABU_SPELLER_MAX_LAYERS], Ho[NABU_SPELLER_MAX_LAYERS], acts[NABU_SPELLER_MAX_LAYERS];
-  size_t ctx, q, logits_tm, ids, align[MM], keys[MM], znorm[MM], total;     // offsets in floats
-};
-static MLayout m_layout(const nabu_speller_multi_desc *d, const Geo &g) {
-  MLayout s;
-  const size_t B = d->B, L = d->L, U = d->U, C = d->C;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t r = o; o += (n + 3) / 4 * 4; return r; };
-  for (int n = 0; n < d->num_layers; ++n) {
-    s.H[n] = take((L + 1) * B * U);
-    s.Cs[n] = take((L + 1) * B * U);
-    s.Ho[n] = d->keep_prob < 1.f ? take((L + 1) * B * U) : s.H[n];
-    s.acts[n] = take(L * B * 4 * U);
-  }
-  s.ctx = take((L + 1) * B * g.SE);
-  s.q = take(L * B * g.MU);
-  s.logits_tm = take(L * B * C);
-  s.ids = take(L * B);
-  for (int m = 0; m < d->M; ++m) {
-    s.align[m] = take((L + 1) * B * d->Te[m]);
-    s.keys[m] = take(B * d->Te[m] * U);
-    s.znorm[m] = take(L * B);
-  }
-  s.total = o;
-  return s;
-}
-
-struct MWs {
-  size_t z, dl, dH, dCtx, dq, dz[NABU_SPELLER_MAX_LAYERS], dh[2][NABU_SPELLER_MAX_LAYERS], dc[2][NABU_SPELLER_MAX_LAYERS];
-  size_t dctxc, dx, tmp, wqcat, tickets;
-  size_t dkeys[MM], dv[MM], dwf[MM], dck[MM], dal[2][MM], part[MM], dcf[MM];
-  size_t gemm, gemm_bytes, total;
-};
-static MWs m_ws(const nabu_speller_multi_desc *d, const Geo &g) {
-  MWs s;
-  const size_t B = d->B, L = d->L, U = d->U, C = d->C, SE = g.SE, MU = g.MU;
-  const size_t F = d->kind == 1 ? d->F : 0, K = d->kind == 1 ? d->K : 0;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t r = o; o += (n + 3) / 4 * 4; return r; };
-  s.z = take(B * 4 * U);
-  s.dl = take(L * B * C);
-  s.dH = take(L * B * U);
-  s.dCtx = take(L * B * SE);
-  s.dq = take(L * B * MU);
-  for (int n = 0; n < d->num_layers; ++n) {
-    s.dz[n] = take(L * B * 4 * U);
-    for (int i = 0; i < 2; ++i) { s.dh[i][n] = take(B * U); s.dc[i][n] = take(B * U); }
-  }
-  s.dctxc = take(B * SE);
-  s.dx = take(B * U);
-  s.tmp = take(B * U);
-  s.wqcat = take(U * MU);
-  s.tickets = take((size_t)MM * B);
-  size_t gw = 0;
-  auto mx = [&](size_t v) { if (v > gw) gw = v; };
-  const int Bi = (int)B, Ui = (int)U, Ci = (int)C, BL = (int)(B * L), SEi = (int)SE, MUi = (int)MU;
-  for (int m = 0; m < d->M; ++m) {
-    const size_t Te = d->Te[m], E = d->E[m], S = g.S[m];
-    s.dkeys[m] = take(B * Te * U);
-    s.dv[m] = take(B * S * U);
-    s.dwf[m] = take(B * S * F * U + 4);
-    s.dck[m] = take(B * K * F + 4);
-    for (int i = 0; i < 2; ++i) s.dal[i][m] = take(B * Te);
-    s.part[m] = take(B * S * (E + 4 > U ? E + 4 : U));
-    s.dcf[m] = take(B * Te * F + 4);
-    const int BT = (int)(B * Te), Ei = (int)E;
-    mx(nabu_gemm_ws_bytes(BT, Ui, Ei)); mx(nabu_gemm_ws_bytes(BT, Ei, Ui)); mx(nabu_gemm_ws_bytes(Ei, Ui, BT));
-    mx(nabu_colsum_ws_bytes((int)(B * S), (int)(F * U + U))); mx(nabu_colsum_ws_bytes(Bi, (int)(K * F + 4)));
-  }
-  mx(nabu_gemm_ws_bytes(Bi, 4 * Ui, SEi)); mx(nabu_gemm_ws_bytes(Bi, 4 * Ui, Ui)); mx(nabu_gemm_ws_bytes(Bi, MUi, Ui));
-  mx(nabu_gemm_ws_bytes(Bi, Ui, MUi)); mx(nabu_gemm_ws_bytes(Bi, SEi, 4 * Ui)); mx(nabu_gemm_ws_bytes(Bi, Ui, 4 * Ui));
-  mx(nabu_gemm_ws_bytes(Bi, Ci, Ui)); mx(nabu_gemm_ws_bytes(Bi, Ci, SEi));
-  mx(nabu_gemm_ws_bytes(BL, Ci, Ui)); mx(nabu_gemm_ws_bytes(BL, Ci, SEi));
-  mx(nabu_gemm_ws_bytes(Ui, Ci, BL)); mx(nabu_gemm_ws_bytes(SEi, Ci, BL));
-  mx(nabu_gemm_ws_bytes(BL, Ui, Ci)); mx(nabu_gemm_ws_bytes(BL, SEi, Ci));
-  mx(nabu_gemm_ws_bytes(Ui, Ui, BL)); mx(nabu_gemm_ws_bytes(SEi, 4 * Ui, BL)); mx(nabu_gemm_ws_bytes(Ui, 4 * Ui, BL));
-  mx(nabu_colsum_ws_bytes(BL, 4 * Ui)); mx(nabu_colsum_ws_bytes(BL, Ci));
-  s.gemm_bytes = (gw + 255) / 256 * 256;
-  s.gemm = take(s.gemm_bytes / 4 + 4);
-  s.total = o;
-  return s;
-}
+namespace {
 
 template <typename Kern>
-static int launch_attn(Kern kern, const Geo &g, int B, size_t shm, const MArgs &a, hipStream_t s) {
+static int launch_attn(Kern kern, const MultiAttnGeo &g, int B, size_t shm, const MArgs &a, hipStream_t s) {
   if (shm > 64 * 1024)
     NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
   hipLaunchKernelGGL(kern, dim3(B, g.Smax, g.M), dim3(AT), shm, s, a);
   NABU_LAUNCH_CHECK();
-  return 0;
-}
-
-static int check_ptrs(const nabu_speller_multi_desc *d, const float *const *values, const int32_t *const *enc_len,
-                      const nabu_speller_multi_params *p) {
-  for (int m = 0; m < d->M; ++m) {
-    NABU_CHECK_ARG(values[m] && enc_len[m] && p->memory_kernel[m] && p->query_kernel[m] && p->attention_v[m],
-                   "speller_multi: null pointer for an encoded input");
-    NABU_CHECK_ARG(d->kind != 1 || (p->conv_kernel[m] && p->conv_proj[m]),
-                   "speller_multi: location-aware attention needs its kernels");
-  }
-  NABU_CHECK_ARG(p->out_kernel && p->out_bias, "speller_multi: null pointer");
-  for (int n = 0; n < d->num_layers; ++n) NABU_CHECK_ARG(p->lstm_kernel[n] && p->lstm_bias[n], "speller_multi: null pointer");
   return 0;
 }
 
@@ -734,6 +613,15 @@ size_t multi_attn_part_floats(int B, int Te, int E, int U, int kind, int K, int 
   return S > 0 ? (size_t)B * S * ((size_t)E + 4) : 0;
 }
 
+int multi_attn_launch(bool backward, const MultiAttnGeo &g, const MArgs &a, hipStream_t s) {
+  if (backward) {
+    if (a.kind == 1) return launch_attn(attn_multi_bwd_kernel<true>, g, a.B, g.lds_b, a, s);
+    return launch_attn(attn_multi_bwd_kernel<false>, g, a.B, g.lds_b, a, s);
+  }
+  if (a.kind == 1) return launch_attn(attn_multi_fwd_kernel<true>, g, a.B, g.lds_f, a, s);
+  return launch_attn(attn_multi_fwd_kernel<false>, g, a.B, g.lds_f, a, s);
+}
+
 int multi_attn_fwd(int M, int B, int U, int kind, int K, int F, int prob_fn, int step, const int32_t *dec_len, const float *q,
                    const float *ctx_prev, float *ctx, const MultiAttnMem *mems, hipStream_t s) {
   NABU_CHECK_ARG(M >= 1 && M <= MM && mems && dec_len && q && ctx_prev && ctx, "multi_attn_fwd: bad argument");
@@ -741,8 +629,8 @@ int multi_attn_fwd(int M, int B, int U, int kind, int K, int F, int prob_fn, int
   d.size = sizeof(d); d.M = M; d.B = B; d.U = U; d.C = 2; d.L = 1; d.num_layers = 1;
   d.kind = kind; d.K = K; d.F = F; d.prob_fn = prob_fn; d.keep_prob = 1.f;
   for (int m = 0; m < M; ++m) { d.Te[m] = mems[m].Te; d.E[m] = mems[m].E; }
-  Geo g;
-  if (int e = check_md(&d, &g)) return e;
+  MultiAttnGeo g;
+  if (int e = multi_attn_geo(&d, &g)) return e;
   MArgs a = {};
   a.B = B; a.U = U; a.SE = g.SE; a.MU = g.MU; a.kind = kind; a.K = K; a.F = F; a.prob_fn = prob_fn; a.step = step;
   a.dec_len = dec_len; a.q = q; a.ctx_prev = ctx_prev; a.ctx = ctx;
@@ -753,286 +641,7 @@ int multi_attn_fwd(int M, int B, int U, int kind, int K, int F, int prob_fn, int
     x.enc_len = y.enc_len; x.keys = y.keys; x.values = y.values; x.v = y.v; x.ck = y.ck; x.wf = y.wf;
     x.align_prev = y.align_prev; x.align = y.align; x.znorm = y.znorm; x.part = y.part; x.tickets = y.tickets;
   }
-  if (kind == 1) return launch_attn(attn_multi_fwd_kernel<true>, g, B, g.lds_f, a, s);
-  return launch_attn(attn_multi_fwd_kernel<false>, g, B, g.lds_f, a, s);
+  return multi_attn_launch(false, g, a, s);
 }
 
 }  // namespace nabu
-
-using namespace nabu;
-
-extern "C" size_t nabu_speller_multi_reserve_bytes(const nabu_speller_multi_desc *d) {
-  Geo g;
-  if (check_md(d, &g)) return 0;
-  return m_layout(d, g).total * sizeof(float);
-}
-extern "C" size_t nabu_speller_multi_ws_bytes(const nabu_speller_multi_desc *d) {
-  Geo g;
-  if (check_md(d, &g)) return 0;
-  return m_ws(d, g).total * sizeof(float);
-}
-extern "C" int nabu_speller_multi_uses_persistent(const nabu_speller_multi_desc *d, int backward) {
-  (void)d; (void)backward;
-  return 0;
-}
-extern "C" int nabu_speller_multi_attn_slices(const nabu_speller_multi_desc *d, int m) {
-  Geo g;
-  if (check_md(d, &g) || m < 0 || m >= d->M) return 0;
-  return g.S[m];
-}
-extern "C" int nabu_speller_multi_decoder_inputs(const nabu_speller_multi_desc *d, const void *reserve, int32_t *out_ids,
-                                                 nabu_stream_t stream) {
-  Geo g;
-  if (int e = check_md(d, &g)) return e;
-  NABU_CHECK_ARG(reserve && out_ids, "speller_multi_decoder_inputs: null pointer");
-  const MLayout R = m_layout(d, g);
-  NABU_HIP(hipMemcpyAsync(out_ids, static_cast<const float *>(reserve) + R.ids, (size_t)d->L * d->B * 4,
-                          hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-  return 0;
-}
-
-extern "C" int nabu_speller_multi_fwd(const nabu_speller_multi_desc *d, const float *const *values,
-                                      const int32_t *const *enc_len, const int32_t *ids, const int32_t *dec_len,
-                                      const nabu_speller_multi_params *p, float *logits, void *reserve, void *ws,
-                                      size_t ws_bytes, nabu_stream_t stream) {
-  Geo g;
-  if (int e = check_md(d, &g)) return e;
-  NABU_CHECK_ARG(values && enc_len && ids && dec_len && p && logits && reserve && ws, "speller_multi_fwd: null pointer");
-  NABU_TRY(check_ptrs(d, values, enc_len, p));
-  const MLayout R = m_layout(d, g);
-  const MWs W = m_ws(d, g);
-  if (ws_bytes < W.total * sizeof(float)) return fail(NABU_EWS, "speller_multi_fwd: workspace too small");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  float *r = static_cast<float *>(reserve), *w = static_cast<float *>(ws);
-  const int B = d->B, L = d->L, U = d->U, C = d->C, nl = d->num_layers, M = d->M, SE = g.SE, MU = g.MU;
-  float *gw = w + W.gemm;
-  const size_t gwb = W.gemm_bytes;
-  const bool drop = d->keep_prob < 1.f, sampling = d->sample_prob > 0.f;
-  NABU_HIP(hipMemsetAsync(w + W.tickets, 0, (size_t)MM * B * 4, s));
-  for (int n = 0; n < nl; ++n) {
-    NABU_HIP(hipMemsetAsync(r + R.H[n], 0, (size_t)B * U * 4, s));
-    NABU_HIP(hipMemsetAsync(r + R.Cs[n], 0, (size_t)B * U * 4, s));
-    if (drop) NABU_HIP(hipMemsetAsync(r + R.Ho[n], 0, (size_t)B * U * 4, s));
-  }
-  NABU_HIP(hipMemsetAsync(r + R.ctx, 0, (size_t)B * SE * 4, s));
-  int32_t *ids_used = reinterpret_cast<int32_t *>(r + R.ids);
-  NABU_HIP(hipMemcpyAsync(ids_used, ids, (size_t)L * B * 4, hipMemcpyDeviceToDevice, s));
-  for (int m = 0; m < M; ++m) {
-    const int Te = d->Te[m], E = d->E[m];
-    NABU_HIP(hipMemsetAsync(r + R.align[m], 0, (size_t)B * Te * 4, s));
-    if (d->kind == 2) NABU_TRY(first_col_one(B, Te, r + R.align[m], s));
-    // keys_m = memory_layer_m(values_m); the query kernels side by side: q of all mechanisms is one product
-    NABU_TRY(mm(false, false, B * Te, U, E, values[m], E, p->memory_kernel[m], U, 0.f, r + R.keys[m], U, nullptr, gw, gwb, stream));
-    NABU_TRY(put_cols(U, U, p->query_kernel[m], w + W.wqcat, MU, m * U, s));
-  }
-  MArgs a = {};
-  a.B = B; a.U = U; a.SE = SE; a.MU = MU; a.kind = d->kind; a.K = d->K; a.F = d->F; a.prob_fn = d->prob_fn;
-  a.dec_len = dec_len;
-  for (int m = 0; m < M; ++m) {
-    MMem &x = a.m[m];
-    x.Te = d->Te[m]; x.E = d->E[m]; x.coff = g.coff[m]; x.S = g.S[m];
-    x.enc_len = enc_len[m]; x.keys = r + R.keys[m]; x.values = values[m]; x.v = p->attention_v[m];
-    x.ck = p->conv_kernel[m]; x.wf = p->conv_proj[m];
-    x.part = w + W.part[m];
-    x.tickets = reinterpret_cast<unsigned *>(w + W.tickets) + (size_t)m * B;
-  }
-  const float *K0 = p->lstm_kernel[0];
-  for (int t = 0; t < L; ++t) {
-    const size_t cur = (size_t)t * B * U, nxt = (size_t)(t + 1) * B * U;
-    float *z = w + W.z;
-    for (int n = 0; n < nl; ++n) {
-      const float *Kn = p->lstm_kernel[n];
-      float *Hn = r + R.H[n], *Cn = r + R.Cs[n];
-      if (n == 0) {
-        // [ctx_0 | .. | ctx_{M-1}] . kernel rows C .. C + sum E: one product on the shared context rows
-        NABU_TRY(mm(false, false, B, 4 * U, SE, r + R.ctx + (size_t)t * B * SE, SE, K0 + (size_t)C * 4 * U, 4 * U, 0.f, z, 4 * U, nullptr, gw, gwb, stream));
-        NABU_TRY(mm(false, false, B, 4 * U, U, Hn + cur, U, K0 + (size_t)(C + SE) * 4 * U, 4 * U, 1.f, z, 4 * U, nullptr, gw, gwb, stream));
-        NABU_TRY(nabu_lstm_cell_fwd(B, U, t, dec_len, z, p->lstm_bias[0], K0, ids_used + (size_t)t * B, Cn + cur, Hn + cur,
-                                  r + R.acts[0] + (size_t)t * B * 4 * U, Cn + nxt, Hn + nxt, stream));
-      } else {
-        NABU_TRY(mm(false, false, B, 4 * U, U, r + R.Ho[n - 1] + nxt, U, Kn, 4 * U, 0.f, z, 4 * U, nullptr, gw, gwb, stream));
-        NABU_TRY(mm(false, false, B, 4 * U, U, Hn + cur, U, Kn + (size_t)U * 4 * U, 4 * U, 1.f, z, 4 * U, nullptr, gw, gwb, stream));
-        NABU_TRY(nabu_lstm_cell_fwd(B, U, t, dec_len, z, p->lstm_bias[n], nullptr, nullptr, Cn + cur, Hn + cur,
-                                  r + R.acts[n] + (size_t)t * B * 4 * U, Cn + nxt, Hn + nxt, stream));
-      }
-      if (drop)
-        NABU_TRY(dropout_rows((size_t)B * U, Hn + nxt, r + R.Ho[n] + nxt, d->keep_prob, d->seed,
-                            d->seed_offset + (unsigned long long)t * nl + n, 0, s));
-    }
-    const float *htop = r + R.Ho[nl - 1] + nxt;
-    float *qt = r + R.q + (size_t)t * B * MU;
-    NABU_TRY(mm(false, false, B, MU, U, htop, U, w + W.wqcat, MU, 0.f, qt, MU, nullptr, gw, gwb, stream));
-    a.step = t; a.q = qt;
-    a.ctx_prev = r + R.ctx + (size_t)t * B * SE;
-    a.ctx = r + R.ctx + (size_t)(t + 1) * B * SE;
-    for (int m = 0; m < M; ++m) {
-      a.m[m].align_prev = r + R.align[m] + (size_t)t * B * d->Te[m];
-      a.m[m].align = r + R.align[m] + (size_t)(t + 1) * B * d->Te[m];
-      a.m[m].znorm = r + R.znorm[m] + (size_t)t * B;
-    }
-    if (d->kind == 1) NABU_TRY(launch_attn(attn_multi_fwd_kernel<true>, g, B, g.lds_f, a, s));
-    else              NABU_TRY(launch_attn(attn_multi_fwd_kernel<false>, g, B, g.lds_f, a, s));
-    if (sampling && t + 1 < L) {
-      // ScheduledEmbeddingTrainingHelper: the step's logits decide the next input of selected rows (the draws are
-      // those of the one-memory decoder: counter (row, sample_offset + t))
-      if (sample_step_ok(C)) {
-        NABU_TRY(sample_step(B, C, U, SE, htop, U, a.ctx, SE, p->out_kernel, p->out_bias, d->sample_prob, d->sample_seed,
-                           d->sample_offset + (unsigned long long)t, ids + (size_t)(t + 1) * B, ids_used + (size_t)(t + 1) * B, 0, s));
-        continue;
-      }
-      float *lt = r + R.logits_tm + (size_t)t * B * C;
-      NABU_TRY(mm(false, false, B, C, U, htop, U, p->out_kernel, C, 0.f, lt, C, p->out_bias, gw, gwb, stream));
-      NABU_TRY(mm(false, false, B, C, SE, a.ctx, SE, p->out_kernel + (size_t)U * C, C, 1.f, lt, C, nullptr, gw, gwb, stream));
-      NABU_TRY(sample_ids_rows(B, C, lt, d->sample_prob, d->sample_seed, d->sample_offset + (unsigned long long)t,
-                             ids + (size_t)(t + 1) * B, ids_used + (size_t)(t + 1) * B, 0, s));
-    }
-  }
-  // output projection of all steps: [h_t | contexts_t] . W + b, then batch-major + impute_finished
-  float *ltm = r + R.logits_tm;
-  NABU_TRY(mm(false, false, L * B, C, U, r + R.Ho[nl - 1] + (size_t)B * U, U, p->out_kernel, C, 0.f, ltm, C, p->out_bias, gw, gwb, stream));
-  NABU_TRY(mm(false, false, L * B, C, SE, r + R.ctx + (size_t)B * SE, SE, p->out_kernel + (size_t)U * C, C, 1.f, ltm, C, nullptr, gw, gwb, stream));
-  NABU_TRY(nabu_swap01_f32(L, B, C, ltm, logits, stream));
-  NABU_TRY(nabu_mask_time_f32(B, L, C, logits, dec_len, stream));
-  return 0;
-}
-
-extern "C" int nabu_speller_multi_bwd(const nabu_speller_multi_desc *d, const float *const *values,
-                                      const int32_t *const *enc_len, const int32_t *ids, const int32_t *dec_len,
-                                      const nabu_speller_multi_params *p, const float *dlogits, void *reserve,
-                                      const nabu_speller_multi_grads *gr, float *const *dvalues, void *ws,
-                                      size_t ws_bytes, nabu_stream_t stream) {
-  Geo g;
-  if (int e = check_md(d, &g)) return e;
-  NABU_CHECK_ARG(values && enc_len && ids && dec_len && p && dlogits && reserve && gr && dvalues && ws,
-                 "speller_multi_bwd: null pointer");
-  NABU_TRY(check_ptrs(d, values, enc_len, p));
-  NABU_TRY(check_ptrs(d, dvalues, enc_len, reinterpret_cast<const nabu_speller_multi_params *>(gr)));
-  const MLayout R = m_layout(d, g);
-  const MWs W = m_ws(d, g);
-  if (ws_bytes < W.total * sizeof(float)) return fail(NABU_EWS, "speller_multi_bwd: workspace too small");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  float *r = static_cast<float *>(reserve), *w = static_cast<float *>(ws);
-  const int B = d->B, L = d->L, U = d->U, C = d->C, nl = d->num_layers, M = d->M, SE = g.SE, MU = g.MU;
-  const int F = d->kind == 1 ? d->F : 0, K = d->kind == 1 ? d->K : 0;
-  float *gw = w + W.gemm;
-  const size_t gwb = W.gemm_bytes;
-  const bool drop = d->keep_prob < 1.f;
-  const int BL = B * L;
-  float *dl = w + W.dl, *dH = w + W.dH, *dCtx = w + W.dCtx, *dq = w + W.dq;
-  const float *htop_all = r + R.Ho[nl - 1] + (size_t)B * U;
-  const float *ctx1 = r + R.ctx + (size_t)B * SE;
-  // output projection
-  NABU_TRY(nabu_swap01_f32(B, L, C, dlogits, dl, stream));
-  NABU_TRY(mm(true, false, U, C, BL, htop_all, U, dl, C, 0.f, gr->out_kernel, C, nullptr, gw, gwb, stream));
-  NABU_TRY(mm(true, false, SE, C, BL, ctx1, SE, dl, C, 0.f, gr->out_kernel + (size_t)U * C, C, nullptr, gw, gwb, stream));
-  NABU_TRY(nabu_colsum_f32(BL, C, dl, C, 0.f, gr->out_bias, gw, gwb, stream));
-  NABU_TRY(mm(false, true, BL, U, C, dl, C, p->out_kernel, C, 0.f, dH, U, nullptr, gw, gwb, stream));
-  NABU_TRY(mm(false, true, BL, SE, C, dl, C, p->out_kernel + (size_t)U * C, C, 0.f, dCtx, SE, nullptr, gw, gwb, stream));
-  NABU_HIP(hipMemsetAsync(w + W.tickets, 0, (size_t)MM * B * 4, s));
-  for (int n = 0; n < nl; ++n) {
-    NABU_HIP(hipMemsetAsync(w + W.dh[0][n], 0, (size_t)B * U * 4, s));
-    NABU_HIP(hipMemsetAsync(w + W.dc[0][n], 0, (size_t)B * U * 4, s));
-  }
-  MArgs a = {};
-  a.B = B; a.U = U; a.SE = SE; a.MU = MU; a.kind = d->kind; a.K = d->K; a.F = d->F; a.prob_fn = d->prob_fn;
-  a.dec_len = dec_len;
-  for (int m = 0; m < M; ++m) {
-    const int Te = d->Te[m], S = g.S[m];
-    NABU_HIP(hipMemsetAsync(w + W.dkeys[m], 0, (size_t)B * Te * U * 4, s));
-    NABU_HIP(hipMemsetAsync(w + W.dv[m], 0, (size_t)B * S * U * 4, s));
-    if (d->kind == 1) {
-      NABU_HIP(hipMemsetAsync(w + W.dwf[m], 0, (size_t)B * S * F * U * 4, s));
-      NABU_HIP(hipMemsetAsync(w + W.dck[m], 0, (size_t)B * K * F * 4, s));
-    }
-    NABU_TRY(put_cols(U, U, p->query_kernel[m], w + W.wqcat, MU, m * U, s));
-    MMem &x = a.m[m];
-    x.Te = Te; x.E = d->E[m]; x.coff = g.coff[m]; x.S = S;
-    x.enc_len = enc_len[m]; x.keys = r + R.keys[m]; x.values = values[m]; x.v = p->attention_v[m];
-    x.ck = p->conv_kernel[m]; x.wf = p->conv_proj[m];
-    x.part = w + W.part[m];
-    x.tickets = reinterpret_cast<unsigned *>(w + W.tickets) + (size_t)m * B;
-    x.dkeys = w + W.dkeys[m]; x.dv_part = w + W.dv[m]; x.dwf_part = w + W.dwf[m]; x.dck_part = w + W.dck[m];
-    x.dcf_g = w + W.dcf[m];
-  }
-  const float *K0 = p->lstm_kernel[0];
-  int cur = 0;
-  bool have_carry = false;
-  for (int t = L - 1; t >= 0; --t) {
-    float *dCt = dCtx + (size_t)t * B * SE;
-    if (have_carry) NABU_TRY(nabu_axpy_f32((size_t)B * SE, 1.f, w + W.dctxc, dCt, stream));
-    float *dqt = dq + (size_t)t * B * MU;
-    a.step = t; a.q = r + R.q + (size_t)t * B * MU;
-    a.ctx = r + R.ctx + (size_t)(t + 1) * B * SE;
-    a.dctx = dCt; a.dq = dqt;
-    for (int m = 0; m < M; ++m) {
-      MMem &x = a.m[m];
-      x.align_prev = r + R.align[m] + (size_t)t * B * d->Te[m];
-      x.align_c = r + R.align[m] + (size_t)(t + 1) * B * d->Te[m];
-      x.znorm = r + R.znorm[m] + (size_t)t * B;
-      x.dalign_out = d->kind == 1 ? w + W.dal[t & 1][m] : nullptr;
-      x.dalign_in = (d->kind == 1 && have_carry) ? w + W.dal[(t + 1) & 1][m] : nullptr;
-    }
-    if (d->kind == 1) NABU_TRY(launch_attn(attn_multi_bwd_kernel<true>, g, B, g.lds_b, a, s));
-    else              NABU_TRY(launch_attn(attn_multi_bwd_kernel<false>, g, B, g.lds_b, a, s));
-    // d h_top += [dq_0 | .. | dq_{M-1}] . [Wq_0 | .. | Wq_{M-1}]^T: one product
-    float *dHt = dH + (size_t)t * B * U;
-    NABU_TRY(mm(false, true, B, U, MU, dqt, MU, w + W.wqcat, MU, 1.f, dHt, U, nullptr, gw, gwb, stream));
-    const float *dtop = dHt;
-    for (int n = nl - 1; n >= 0; --n) {
-      const float *dh_in = dtop;
-      if (drop) {
-        NABU_TRY(dropout_rows((size_t)B * U, dtop, w + W.tmp, d->keep_prob, d->seed,
-                            d->seed_offset + (unsigned long long)t * nl + n, 0, s));
-        dh_in = w + W.tmp;
-      }
-      float *dzt = w + W.dz[n] + (size_t)t * B * 4 * U;
-      const float *Cn = r + R.Cs[n];
-      NABU_TRY(nabu_lstm_cell_bwd(B, U, t, dec_len, r + R.acts[n] + (size_t)t * B * 4 * U, Cn + (size_t)(t + 1) * B * U,
-                                Cn + (size_t)t * B * U, dh_in, w + W.dh[cur][n], w + W.dc[cur][n], dzt, w + W.dc[cur ^ 1][n],
-                                stream));
-      const float *Kn = p->lstm_kernel[n];
-      if (n == 0) {
-        NABU_TRY(mm(false, true, B, SE, 4 * U, dzt, 4 * U, K0 + (size_t)C * 4 * U, 4 * U, 0.f, w + W.dctxc, SE, nullptr, gw, gwb, stream));
-        NABU_TRY(mm(false, true, B, U, 4 * U, dzt, 4 * U, K0 + (size_t)(C + SE) * 4 * U, 4 * U, 0.f, w + W.dh[cur ^ 1][0], U, nullptr, gw, gwb, stream));
-      } else {
-        NABU_TRY(mm(false, true, B, U, 4 * U, dzt, 4 * U, Kn, 4 * U, 0.f, w + W.dx, U, nullptr, gw, gwb, stream));
-        NABU_TRY(mm(false, true, B, U, 4 * U, dzt, 4 * U, Kn + (size_t)U * 4 * U, 4 * U, 0.f, w + W.dh[cur ^ 1][n], U, nullptr, gw, gwb, stream));
-        dtop = w + W.dx;
-      }
-    }
-    have_carry = true;
-    cur ^= 1;
-  }
-  // sums over steps as single products over all steps
-  for (int m = 0; m < M; ++m)
-    NABU_TRY(mm(true, false, U, U, BL, htop_all, U, dq + (size_t)m * U, MU, 0.f, gr->query_kernel[m], U, nullptr, gw, gwb, stream));
-  for (int n = 0; n < nl; ++n) {
-    const float *dzn = w + W.dz[n];
-    float *gK = gr->lstm_kernel[n];
-    if (n == 0) {
-      NABU_TRY(nabu_scatter_rows_f32(C, BL, 4 * U, reinterpret_cast<const int32_t *>(r + R.ids), dzn, gK, stream));
-      NABU_TRY(mm(true, false, SE, 4 * U, BL, r + R.ctx, SE, dzn, 4 * U, 0.f, gK + (size_t)C * 4 * U, 4 * U, nullptr, gw, gwb, stream));
-      NABU_TRY(mm(true, false, U, 4 * U, BL, r + R.H[0], U, dzn, 4 * U, 0.f, gK + (size_t)(C + SE) * 4 * U, 4 * U, nullptr, gw, gwb, stream));
-    } else {
-      NABU_TRY(mm(true, false, U, 4 * U, BL, r + R.Ho[n - 1] + (size_t)B * U, U, dzn, 4 * U, 0.f, gK, 4 * U, nullptr, gw, gwb, stream));
-      NABU_TRY(mm(true, false, U, 4 * U, BL, r + R.H[n], U, dzn, 4 * U, 0.f, gK + (size_t)U * 4 * U, 4 * U, nullptr, gw, gwb, stream));
-    }
-    NABU_TRY(nabu_colsum_f32(BL, 4 * U, dzn, 4 * U, 0.f, gr->lstm_bias[n], gw, gwb, stream));
-  }
-  for (int m = 0; m < M; ++m) {
-    const int Te = d->Te[m], E = d->E[m], S = g.S[m];
-    float *dkeys = w + W.dkeys[m];
-    NABU_TRY(nabu_colsum_f32(B * S, U, w + W.dv[m], U, 0.f, gr->attention_v[m], gw, gwb, stream));
-    if (d->kind == 1) {
-      NABU_TRY(nabu_colsum_f32(B * S, F * U, w + W.dwf[m], F * U, 0.f, gr->conv_proj[m], gw, gwb, stream));
-      NABU_TRY(nabu_colsum_f32(B, K * F, w + W.dck[m], K * F, 0.f, gr->conv_kernel[m], gw, gwb, stream));
-    }
-    // keys = values . Wmem ; context_t = align_t^T . values
-    NABU_TRY(mm(true, false, E, U, B * Te, values[m], E, dkeys, U, 0.f, gr->memory_kernel[m], U, nullptr, gw, gwb, stream));
-    NABU_TRY(mm(false, true, B * Te, E, U, dkeys, U, p->memory_kernel[m], U, 0.f, dvalues[m], E, nullptr, gw, gwb, stream));
-    // dvalues_m[b] += align_m[:, b, :]^T . dCtx[:, b, columns of m]: one batched launch over the utterances
-    NABU_TRY(gemm_batched_f32(true, false, Te, E, L, r + R.align[m] + (size_t)B * Te, B * Te, Te, dCtx + g.coff[m], B * SE, SE, 1.f,
-                            dvalues[m], E, (long long)Te * E, B, s));
-  }
-  return 0;
-}

@@ -445,6 +445,72 @@ def test_persistent_decoder_status_word_is_sticky_and_reported():
     np.testing.assert_array_equal(check_speller('vanilla', 1, 64, 0, 0, enc_len, tlen, E=64), ref)
 
 
+# (descriptor overrides, switches) -> nabu_speller_uses_persistent(d, 0), (d, 1).  Base descriptor: B = 32, Te = 40,
+# E = U = 64, C = 8, L = 9, one layer, vanilla softmax attention, no dropout, no sampling.  The values were read from
+# the library of the commit BEFORE the driver became one plan (speller_train.hip), on an MI355X.
+LOC = dict(kind=1, K=5, F=3)
+CFG5ISH = dict(B=64, E=512, U=512, Te=200, **LOC)      # values streamed from L2, four chains of 16 rows
+PLAN_TABLE = [
+    (dict(), {}, (1, 1)),
+    (LOC, {}, (1, 1)),
+    (dict(num_layers=2), {}, (0, 0)),
+    (dict(num_layers=2, **LOC), {}, (0, 0)),
+    (dict(prob_fn=1), {}, (0, 0)),
+    (dict(prob_fn=1, **LOC), {}, (0, 0)),
+    (dict(), {'NABU_SPELLER_PERSIST': '0'}, (0, 1)),
+    (dict(), {'NABU_SPELLER_PERSIST_BWD': '0'}, (1, 0)),
+    (dict(), {'NABU_SPELLER_EPILOGUE': '0'}, (0, 0)),
+    (dict(U=60), {}, (0, 0)),                          # no fused shape: 4U = 240 is no multiple of 32
+    (dict(B=64), {}, (1, 1)),
+    (dict(B=64, **LOC), {}, (1, 1)),                   # values LDS-resident: two persistent launches
+    (CFG5ISH, {}, (0, 0)),                             # the rows16 chain is preferred over two persistent launches
+    (CFG5ISH, {'NABU_SPELLER_PERSIST': '2'}, (1, 0)),  # ... unless asked for
+]
+
+
+def test_plan_decisions_are_those_of_the_two_inline_drivers(monkeypatch):
+    """speller_train.hip decides the path of a call in ONE function (speller_plan); nabu_speller_uses_persistent
+    returns two of its fields.  Pins them where a decision flips — layers, probability function, each switch, a shape
+    that is not fused, the 64-row location-aware geometry where the chain is preferred — and the multi family (never
+    persistent).  For two settings a forward + backward call runs under them: logits and every gradient against the
+    oracle (check_speller), the logits against the step chain on the same inputs within 2e-5, the bound of
+    test_persistent_decoder_forward."""
+    import ctypes
+    from nabu_amd import _hip, ops as hip
+    from nabu_amd.neuralnetworks.models.ed_decoders import rnn_decoder
+    from tests.test_hip_multi_speller import slices_of
+    lib = _hip.lib()
+    base = dict(B=32, Te=40, E=64, U=64, C=8, L=9, num_layers=1, kind=0, K=0, F=0, prob_fn=0)
+    for over, env, want in PLAN_TABLE:
+        f = dict(base, **over)
+        d = _hip.SpellerDesc(ctypes.sizeof(_hip.SpellerDesc), *[f[k] for k in base], 1.0, 0, 0, 0.0, 0, 0)
+        with monkeypatch.context() as mp:
+            for k, v in env.items():
+                mp.setenv(k, v)
+            got = tuple(lib.nabu_speller_uses_persistent(ctypes.byref(d), b) for b in (0, 1))
+        assert got == want, (over, env, got, want)
+    assert slices_of(32, 64, 8, 9, 1, (40, 40), (64, 64)) == [3, 3]       # (asserts uses_persistent == 0 for both passes)
+    rng = np.random.default_rng(21)
+    enc_len = rng.integers(20, 41, 32).astype(np.int32)
+    enc_len[0] = 40
+    tlen = rng.integers(1, 9, 32).astype(np.int32)
+    tlen[3] = 8
+    for attention, K, F, env, want in [('vanilla', 0, 0, {}, (1, 1)),
+                                       ('location_aware', 5, 3, {'NABU_SPELLER_PERSIST_BWD': '0'}, (1, 0))]:
+        with monkeypatch.context() as mp:
+            for k, v in env.items():
+                mp.setenv(k, v)
+            got = check_speller(attention, 1, 64, K, F, enc_len, tlen, E=64)
+            assert rnn_decoder.dynamic_decode.last_paths == want
+        with monkeypatch.context() as mp:
+            mp.setenv('NABU_SPELLER_PERSIST', '0')
+            mp.setenv('NABU_SPELLER_PERSIST_BWD', '0')
+            ref = check_speller(attention, 1, 64, K, F, enc_len, tlen, E=64)
+            assert rnn_decoder.dynamic_decode.last_paths == (0, 0)
+        assert np.abs(got - ref).max() < 2e-5
+    hip.check_persist_status()
+
+
 def check_speller(attention, nl, U, K, F, enc_len, tlen, E=24):
     from nabu_amd import variables as vs
     from nabu_amd.autodiff import Tape, SeqLen
