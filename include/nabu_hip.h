@@ -633,6 +633,14 @@ int nabu_speller_multi_beam_search(const nabu_multi_beam_desc *d, const float *c
                                    int32_t *sequences, int32_t *lengths, float *scores,
                                    float *const *alignments_host, int32_t *num_steps, void *ws, size_t ws_bytes,
                                    nabu_stream_t stream);
+/* Sampled decoding over M encoded inputs: nabu_speller_sample (below) with the cell and the attention launch of the
+ * search above, also for M = 1; alignments_host[m] (may be NULL as a whole) receives [B,max_steps,Te[m]]. */
+size_t nabu_speller_multi_sample_ws_bytes(const nabu_multi_beam_desc *d);
+int nabu_speller_multi_sample(const nabu_multi_beam_desc *d, const float *const *values_host,
+                              const int32_t *const *enc_len_host, const nabu_speller_multi_params *p,
+                              unsigned long long seed, unsigned long long offset0, int32_t *sequences,
+                              int32_t *lengths, float *nll, float *const *alignments_host, int32_t *num_steps,
+                              void *ws, size_t ws_bytes, nabu_stream_t stream);
 int nabu_speller_multi_decoder_inputs(const nabu_speller_multi_desc *d, const void *reserve, int32_t *out_ids,
                                       nabu_stream_t stream);
 
@@ -813,6 +821,31 @@ int nabu_beam_prune(int B, int W, int C, const float *logits, float temperature,
                     float *logprobs, int32_t *lengths, int32_t *finished, int32_t *seen,
                     int32_t *pred_ids, int32_t *parent, int32_t *stay, int32_t *all_seen,
                     float *scratch, nabu_stream_t stream);
+/* One sampled step on its own (testable without a model): the sampling counterpart of nabu_beam_prune.  Row b of
+ * logits [B,C] at step t draws id ~ Categorical(softmax(logits[b])) — the draw of nabu_sample_ids at prob = 1 with the
+ * same seed and offset, bit for bit (Philox4x32-10, counter (b, offset), key seed; one inverse-CDF walk for both).
+ *   a row not yet finished: sequences[b,t] = id; nll[b] += logsumexp(logits[b]) - logits[b,id] (fp32, max-subtracted,
+ *     a fixed reduction order); with id == C-1 (the end token) or t + 1 >= max_steps: finished[b] = 1, lengths[b] = t+1;
+ *   a finished row: sequences[b,t] = 0, nll[b] unchanged;
+ *   every row: next_ids[b] = id (SampleEmbeddingHelper keeps feeding samples: impute_finished is off);
+ *   all_finished[0] = AND of finished over the batch.
+ * sequences [B,max_steps]; lengths, finished, nll [B] are updated in place; 0 <= t < max_steps. */
+int nabu_sample_advance(int B, int C, const float *logits, unsigned long long seed, unsigned long long offset,
+                        int t, int max_steps, int32_t *sequences, int32_t *lengths, int32_t *finished,
+                        float *nll, int32_t *next_ids, int32_t *all_finished, nabu_stream_t stream);
+/* Sampled decoding — RandomDecoder.__call__ (decoders/random_decoder.py:26-122): SampleEmbeddingHelper + BasicDecoder
+ * under dynamic_decode(maximum_iterations = max_steps), TF-1.8 recalled.  The loop of nabu_speller_beam_search on B
+ * rows (beam_width must be 1; length_penalty and temperature are ignored) with nabu_sample_advance where the search
+ * prunes and gathers; step t draws at offset0 + t.  The start input is the one-hot of C-1; a row finishes at the step
+ * where it draws C-1; the loop ends when every row has finished or after max_steps.
+ *   sequences [B,max_steps] int32, zero beyond lengths; lengths [B] counts the end token and is max_steps for a row
+ *   that never drew it; nll [B] = the summed cross-entropy of the sample (positive); alignments [B,max_steps,Te] or
+ *   NULL (zero from step *num_steps on).  SYNCHRONISES the stream once per step (the stop test). */
+size_t nabu_speller_sample_ws_bytes(const nabu_beam_desc *d);
+int nabu_speller_sample(const nabu_beam_desc *d, const float *values, const int32_t *enc_len,
+                        const nabu_speller_params *p, unsigned long long seed, unsigned long long offset0,
+                        int32_t *sequences, int32_t *lengths, float *nll, float *alignments, int32_t *num_steps,
+                        void *ws, size_t ws_bytes, nabu_stream_t stream);
 /* dst[b,w,:] = (stay[b,w] ? old : fresh)[b, parent[b,w], :]  for [B,W,F] float rows */
 int nabu_beam_gather(int B, int W, int F, const float *fresh, const float *old, const int32_t *parent,
                      const int32_t *stay, float *dst, nabu_stream_t stream);

@@ -160,6 +160,11 @@ SIGNATURES = {
     'nabu_speller_beam_search': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nabu_beam_prune': (_i, [_i, _i, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'nabu_beam_gather': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'nabu_sample_advance': (_i, [_i, _i, _vp, _c.c_ulonglong, _c.c_ulonglong, _i, _i] + [_vp] * 6 + [_vp]),
+    'nabu_speller_sample_ws_bytes': (_sz, [_vp]),
+    'nabu_speller_sample': (_i, [_vp] * 4 + [_c.c_ulonglong, _c.c_ulonglong] + [_vp] * 6 + [_sz, _vp]),
+    'nabu_speller_multi_sample_ws_bytes': (_sz, [_vp]),
+    'nabu_speller_multi_sample': (_i, [_vp] * 4 + [_c.c_ulonglong, _c.c_ulonglong] + [_vp] * 6 + [_sz, _vp]),
     'nabu_relu_f32': (_i, [_sz, _vp, _vp, _vp]),
     'nabu_relu_bwd_f32': (_i, [_sz, _vp, _vp, _vp, _vp]),
     'nabu_layer_norm_fwd': (_i, [_i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),

@@ -91,6 +91,22 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
   return c;
 }
 __device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
+// One draw from Categorical(softmax(l[0..C))) by the inverse CDF in class order, u in [0, 1): ONE thread walks the row,
+// so the order of every sum is fixed.  The walk of nabu_sample_ids, the step chain's sample_step and nabu_sample_advance
+// — the same logits and the same u give the same class in all three, bit for bit.
+__device__ __forceinline__ int softmax_draw(const float *l, int C, float u) {
+  float m = l[0];
+  for (int c = 1; c < C; ++c) m = fmaxf(m, l[c]);
+  float tot = 0.f;
+  for (int c = 0; c < C; ++c) tot += expf(l[c] - m);
+  const float target = u * tot;        // inverse CDF of softmax(l)
+  float acc = 0.f;
+  for (int c = 0; c < C; ++c) {
+    acc += expf(l[c] - m);
+    if (acc > target) return c;
+  }
+  return C - 1;
+}
 // dropout scale factors (0 or 1/keep) of the 4-element group `group` of the array the stream is defined on
 // (dropout_kernel of elementwise.hip: element e = 4 group + j keeps its value when u01(r[j]) < keep)
 __device__ __forceinline__ float4 dropout_scale4(unsigned long long group, float keep, unsigned long long seed,

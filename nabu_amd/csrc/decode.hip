@@ -10,6 +10,8 @@
 //     that stays L2-resident.
 //   * attention: the per-step cell kernels of speller.hip / speller_multi.hip on B*beam_width rows, then one
 //     pruning workgroup per utterance and row gathers of the cell state (ONE loop for 1..M encoded inputs: beam_run).
+//     The sampled decode (the reference's RandomDecoder) is a mode of that loop: beam_width 1, and one wave per row
+//     draws the next label (sample_advance_kernel) where the beam search prunes and gathers.
 // Selecting the k best of n candidates, exact and deterministic with ties to the lower candidate
 // index: CTC (k = 100 of ~4000 per frame) uses a radix select of the k-th largest key + compaction +
 // rank sort (select_best); the attention search (k = 16) uses k rounds of a workgroup-wide arg-max
@@ -453,6 +455,54 @@ __global__ __launch_bounds__(DT) void beam_prune_kernel(PruneArgs p) {
   if (tid == 0) p.all_seen[b] = s_all;
 }
 
+// ===========================================================================
+// sampled decoding: one step of SampleEmbeddingHelper + BasicDecoder under dynamic_decode.  One wave per row; the logits
+// are read once (into LDS up to SAMPLE_LDS_C classes; wider rows are walked in place).  The wave reduces the row's
+// log-sum-exp (strided partials, then the xor butterfly: a fixed order); lane 0 draws with softmax_draw — the walk and
+// the Philox word of nabu_sample_ids at prob = 1 — and does the row's bookkeeping.
+constexpr int SAMPLE_LDS_C = 4096;
+struct SampleArgs {
+  int C, t, max_steps;
+  const float *logits;
+  unsigned long long seed, offset;
+  int32_t *sequences, *lengths, *finished, *next_ids, *all_finished;
+  float *nll;
+};
+
+__global__ __launch_bounds__(64) void sample_advance_kernel(SampleArgs p) {
+  extern __shared__ __attribute__((aligned(16))) float dsm[];
+  const int b = blockIdx.x, lane = threadIdx.x, C = p.C;
+  const float *x = p.logits + (size_t)b * C;
+  const bool staged = C <= SAMPLE_LDS_C;
+  float m = -INFINITY;
+  for (int c = lane; c < C; c += 64) {
+    const float v = x[c];
+    if (staged) dsm[c] = v;
+    m = fmaxf(m, v);
+  }
+  m = wave_max(m);
+  __syncthreads();
+  const float *l = staged ? dsm : x;
+  float s = 0.f;
+  for (int c = lane; c < C; c += 64) s += expf(l[c] - m);
+  s = wave_sum(s);
+  if (lane) return;
+  const uint4 r = philox4x32_10(make_uint4((unsigned)b, 0u, (unsigned)p.offset, (unsigned)(p.offset >> 32)),
+                                make_uint2((unsigned)p.seed, (unsigned)(p.seed >> 32)));
+  const int id = softmax_draw(l, C, u01(r.y));
+  p.next_ids[b] = id;                  // fed to the cell also after the end token (impute_finished is off)
+  int32_t *out = p.sequences + (size_t)b * p.max_steps + p.t;
+  if (p.finished[b]) { *out = 0; return; }
+  *out = id;
+  p.nll[b] += logf(s) + (m - l[id]);     // logsumexp - logit, the two large terms subtracted first
+  if (id == C - 1 || p.t + 1 >= p.max_steps) {
+    p.finished[b] = 1;
+    p.lengths[b] = p.t + 1;
+  } else {
+    atomicAnd(p.all_finished, 0);      // (set to 1 before the launch: the AND of `finished` over the batch)
+  }
+}
+
 __global__ __launch_bounds__(DT) void beam_gather_kernel(int W, int F, const float *__restrict__ fresh,
                                                          const float *__restrict__ old,
                                                          const int32_t *__restrict__ parent,
@@ -544,6 +594,8 @@ struct BeamGeo {
   int M, B, W, U, C, nl, S, kind, K, F, prob_fn, Te[MM], E[MM], SE;
   float lpw, temperature;
   bool multi;                 // the step's attention is multi_attn_fwd
+  bool sample;                // sampled decoding (W = 1): nabu_sample_advance where the search prunes and gathers
+  unsigned long long seed, offset0;
 };
 struct BeamIO {
   const float *values[MM];
@@ -552,7 +604,7 @@ struct BeamIO {
   const float *out_kernel, *out_bias, *const *lstm_kernel, *const *lstm_bias;
   float *alignments[MM];      // all null: not wanted
   int32_t *sequences, *lengths, *num_steps;
-  float *scores;
+  float *scores;              // (sampled decoding: nll)
 };
 
 // workspace, offsets in 32-bit words
@@ -608,7 +660,8 @@ static BeamWs beam_ws(const BeamGeo &g) {
 static int check_beam(const BeamGeo &g) {
   if (g.B <= 0 || g.U <= 0 || g.C <= 1) return fail(NABU_EINVAL, "beam search: bad dimensions");
   if (g.W <= 0 || g.S <= 0) return fail(NABU_EINVAL, "beam search: beam_width and max_steps must be positive");
-  if (!(g.temperature > 0.f)) return fail(NABU_EINVAL, "beam search: temperature must be positive");
+  if (g.sample && g.W != 1) return fail(NABU_EINVAL, "sampled decoding: beam_width must be 1");
+  if (!g.sample && !(g.temperature > 0.f)) return fail(NABU_EINVAL, "beam search: temperature must be positive");
   if (g.kind < 0 || g.kind > 2 || g.prob_fn < 0 || g.prob_fn > 2)
     return fail(NABU_EINVAL, "beam search: unknown attention kind or probability_fn");
   if (g.nl < 1 || g.nl > NABU_SPELLER_MAX_LAYERS) return fail(NABU_EUNSUP, "beam search: 1..%d layers", NABU_SPELLER_MAX_LAYERS);
@@ -663,6 +716,12 @@ static int beam_run(const BeamGeo &g, const BeamIO &io, void *ws, size_t ws_byte
   NABU_HIP(hipMemsetAsync(wi + L.finished, 0, (size_t)N * 4, s));
   NABU_HIP(hipMemsetAsync(wi + L.seen, 0, (size_t)N * 4, s));
   if (g.multi) NABU_HIP(hipMemsetAsync(wi + L.tickets, 0, (size_t)M * N * 4, s));
+  if (g.sample) {                                  // written in place by every step: sequences [B,S], lengths, nll [B]
+    NABU_HIP(hipMemsetAsync(io.sequences, 0, (size_t)N * S * 4, s));
+    NABU_HIP(hipMemsetAsync(io.lengths, 0, (size_t)N * 4, s));
+    NABU_HIP(hipMemsetAsync(io.scores, 0, (size_t)N * 4, s));
+    NABU_HIP(hipMemsetAsync(wi + L.src, 0, (size_t)N * S * 4, s));       // (beam_align_kernel: slot 0 at every step)
+  }
   int cur = 0, fresh = 1, nxt = 2;                 // state sets: before the step, after the cell, after pruning
   for (int n = 0; n < nl; ++n) {
     NABU_HIP(hipMemsetAsync(w + L.h[cur][n], 0, (size_t)N * U * 4, s));
@@ -676,7 +735,8 @@ static int beam_run(const BeamGeo &g, const BeamIO &io, void *ws, size_t ws_byte
   float *z = w + L.z, *lg = w + L.logits;
   const int32_t *big = wi + L.big;
   int32_t *par = wi + L.parent, *stay = wi + L.stay;
-  std::vector<int32_t> done(B);
+  const int ndone = g.sample ? 1 : B;              // flags of the stop test: all_finished[0], or all_seen [B]
+  std::vector<int32_t> done(ndone);
   int Tn = 0;
   for (int t = 0; t < S; ++t) {
     // the cell on all B*W rows (the step of nabu_speller_fwd / nabu_speller_multi_fwd; no dropout at inference)
@@ -713,58 +773,70 @@ static int beam_run(const BeamGeo &g, const BeamIO &io, void *ws, size_t ws_byte
     // AttentionProjectionWrapper: [h, contexts of this step]·W + b (rnn_cell.py:145-155)
     NABU_TRY(mm(0, 0, N, C, U, htop, U, io.out_kernel, C, 0.f, lg, C, io.out_bias, gw, gwb, stream));
     NABU_TRY(mm(0, 0, N, C, SE, w + L.ctx[fresh], SE, io.out_kernel + (size_t)U * C, C, 1.f, lg, C, nullptr, gw, gwb, stream));
-    // expand + prune; the predicted ids are the next step's inputs
-    NABU_TRY(nabu_beam_prune(B, W, C, lg, g.temperature, g.lpw, w + L.logprobs, wi + L.lengths, wi + L.finished,
-                             wi + L.seen, wi + L.ids, par, stay, wi + L.all_seen, w + L.scratch, stream));
-    for (int n = 0; n < nl; ++n) {
-      NABU_TRY(nabu_beam_gather(B, W, U, w + L.h[fresh][n], w + L.h[cur][n], par, stay, w + L.h[nxt][n], stream));
-      NABU_TRY(nabu_beam_gather(B, W, U, w + L.c[fresh][n], w + L.c[cur][n], par, stay, w + L.c[nxt][n], stream));
+    const int adv = g.sample ? fresh : nxt;        // the state set the next step starts from
+    if (g.sample) {
+      // draw the next input of every row; no parent and no stay: the cell's fresh state is the next step's
+      NABU_TRY(nabu_sample_advance(B, C, lg, g.seed, g.offset0 + (unsigned long long)t, t, S, io.sequences, io.lengths,
+                                   wi + L.finished, io.scores, wi + L.ids, wi + L.all_seen, stream));
+    } else {
+      // expand + prune; the predicted ids are the next step's inputs
+      NABU_TRY(nabu_beam_prune(B, W, C, lg, g.temperature, g.lpw, w + L.logprobs, wi + L.lengths, wi + L.finished,
+                               wi + L.seen, wi + L.ids, par, stay, wi + L.all_seen, w + L.scratch, stream));
+      for (int n = 0; n < nl; ++n) {
+        NABU_TRY(nabu_beam_gather(B, W, U, w + L.h[fresh][n], w + L.h[cur][n], par, stay, w + L.h[nxt][n], stream));
+        NABU_TRY(nabu_beam_gather(B, W, U, w + L.c[fresh][n], w + L.c[cur][n], par, stay, w + L.c[nxt][n], stream));
+      }
+      NABU_TRY(nabu_beam_gather(B, W, SE, w + L.ctx[fresh], w + L.ctx[cur], par, stay, w + L.ctx[nxt], stream));
+      for (int m = 0; m < M; ++m)
+        NABU_TRY(nabu_beam_gather(B, W, g.Te[m], w + L.align[fresh][m], w + L.align[cur][m], par, stay, w + L.align[nxt][m], stream));
+      NABU_HIP(hipMemcpyAsync(wi + L.hist_pred + (size_t)t * N, wi + L.ids, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
+      NABU_HIP(hipMemcpyAsync(wi + L.hist_parent + (size_t)t * N, par, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
     }
-    NABU_TRY(nabu_beam_gather(B, W, SE, w + L.ctx[fresh], w + L.ctx[cur], par, stay, w + L.ctx[nxt], stream));
     for (int m = 0; m < M; ++m)
-      NABU_TRY(nabu_beam_gather(B, W, g.Te[m], w + L.align[fresh][m], w + L.align[cur][m], par, stay, w + L.align[nxt][m], stream));
-    NABU_HIP(hipMemcpyAsync(wi + L.hist_pred + (size_t)t * N, wi + L.ids, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
-    NABU_HIP(hipMemcpyAsync(wi + L.hist_parent + (size_t)t * N, par, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
-    for (int m = 0; m < M; ++m)
-      NABU_HIP(hipMemcpyAsync(w + L.hist_align[m] + (size_t)t * N * g.Te[m], w + L.align[nxt][m], (size_t)N * g.Te[m] * 4,
+      NABU_HIP(hipMemcpyAsync(w + L.hist_align[m] + (size_t)t * N * g.Te[m], w + L.align[adv][m], (size_t)N * g.Te[m] * 4,
                               hipMemcpyDeviceToDevice, s));
-    const int tmp = cur; cur = nxt; nxt = tmp;
+    int &old = g.sample ? fresh : nxt;             // cur and the advanced set change places
+    const int tmp = cur; cur = adv; old = tmp;
     Tn = t + 1;
     // dynamic_decode's stop test: every slot has been finished at some step
-    NABU_HIP(hipMemcpyAsync(done.data(), wi + L.all_seen, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    NABU_HIP(hipMemcpyAsync(done.data(), wi + L.all_seen, (size_t)ndone * 4, hipMemcpyDeviceToHost, s));
     NABU_HIP(hipStreamSynchronize(s));
     bool all = true;
-    for (int b = 0; b < B; ++b) all = all && done[b] != 0;
+    for (int b = 0; b < ndone; ++b) all = all && done[b] != 0;
     if (all) break;
   }
-  // finalize (beam_search_decoder.py:341-451)
-  hipLaunchKernelGGL(beam_backtrace_kernel, dim3(gN), dim3(DT), 0, s, N, W, Tn, S, wi + L.hist_pred, wi + L.hist_parent,
-                     io.sequences, wi + L.src);
-  NABU_LAUNCH_CHECK();
+  // finalize (beam_search_decoder.py:341-451); a sampled decode has its sequences, lengths and nll already
+  if (!g.sample) {
+    hipLaunchKernelGGL(beam_backtrace_kernel, dim3(gN), dim3(DT), 0, s, N, W, Tn, S, wi + L.hist_pred, wi + L.hist_parent,
+                       io.sequences, wi + L.src);
+    NABU_LAUNCH_CHECK();
+  }
   for (int m = 0; m < M && io.alignments[0]; ++m) {
     hipLaunchKernelGGL(beam_align_kernel, dim3(N, S), dim3(DT), 0, s, N, W, Tn, S, g.Te[m], w + L.hist_align[m], wi + L.src,
                        io.alignments[m]);
     NABU_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(beam_scores_kernel, dim3(gN), dim3(DT), 0, s, N, g.lpw, w + L.logprobs, wi + L.lengths, io.scores,
-                     io.lengths);
-  NABU_LAUNCH_CHECK();
+  if (!g.sample) {
+    hipLaunchKernelGGL(beam_scores_kernel, dim3(gN), dim3(DT), 0, s, N, g.lpw, w + L.logprobs, wi + L.lengths, io.scores,
+                       io.lengths);
+    NABU_LAUNCH_CHECK();
+  }
   *io.num_steps = Tn;
   return 0;
 }
 
 // the two descriptors as a BeamGeo (checked)
-static int beam_geo(const nabu_beam_desc *d, BeamGeo *g) {
+static int beam_geo(const nabu_beam_desc *d, BeamGeo *g, bool sample = false) {
   if (!d || d->size != sizeof(nabu_beam_desc)) return fail(NABU_EINVAL, "beam search: bad descriptor size");
   *g = BeamGeo{1, d->B, d->beam_width, d->U, d->C, d->num_layers, d->max_steps, d->kind, d->K, d->F, d->prob_fn,
-               {d->Te}, {d->E}, d->E, d->length_penalty, d->temperature, false};
+               {d->Te}, {d->E}, d->E, d->length_penalty, d->temperature, false, sample};
   return check_beam(*g);
 }
-static int beam_geo(const nabu_multi_beam_desc *d, BeamGeo *g) {
+static int beam_geo(const nabu_multi_beam_desc *d, BeamGeo *g, bool sample = false) {
   if (!d || d->size != sizeof(nabu_multi_beam_desc)) return fail(NABU_EINVAL, "multi beam search: bad descriptor size");
   if (d->M < 1 || d->M > MM) return fail(NABU_EUNSUP, "multi beam search: 1..%d encoded inputs", MM);
   *g = BeamGeo{d->M, d->B, d->beam_width, d->U, d->C, d->num_layers, d->max_steps, d->kind, d->K, d->F, d->prob_fn,
-               {}, {}, 0, d->length_penalty, d->temperature, true};
+               {}, {}, 0, d->length_penalty, d->temperature, true, sample};
   for (int m = 0; m < d->M; ++m) { g->Te[m] = d->Te[m]; g->E[m] = d->E[m]; g->SE += d->E[m]; }
   return check_beam(*g);
 }
@@ -841,9 +913,35 @@ extern "C" int nabu_beam_gather(int B, int W, int F, const float *fresh, const f
   return 0;
 }
 
+extern "C" int nabu_sample_advance(int B, int C, const float *logits, unsigned long long seed, unsigned long long offset,
+                                   int t, int max_steps, int32_t *sequences, int32_t *lengths, int32_t *finished,
+                                   float *nll, int32_t *next_ids, int32_t *all_finished, nabu_stream_t stream) {
+  if (B == 0) return 0;
+  NABU_CHECK_ARG(B > 0 && C > 0 && t >= 0 && t < max_steps, "sample_advance: bad arguments");
+  NABU_CHECK_ARG(logits && sequences && lengths && finished && nll && next_ids && all_finished,
+                 "sample_advance: null pointer");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(DT), 0, s, (size_t)1, 1, all_finished);
+  const SampleArgs a = {C, t, max_steps, logits, seed, offset, sequences, lengths, finished, next_ids, all_finished, nll};
+  hipLaunchKernelGGL(sample_advance_kernel, dim3(B), dim3(64), C <= SAMPLE_LDS_C ? (size_t)C * 4 : 0, s, a);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" size_t nabu_speller_beam_ws_bytes(const nabu_beam_desc *d) {
   BeamGeo g;
   return beam_geo(d, &g) ? 0 : beam_ws(g).total * 4;
+}
+
+// the search (sample = false: scores) or the sampled decode (nll) of one encoded input
+static int decode_one(BeamGeo &g, const float *values, const int32_t *enc_len, const nabu_speller_params *p,
+                      int32_t *sequences, int32_t *lengths, float *scores, float *alignments, int32_t *num_steps, void *ws,
+                      size_t ws_bytes, nabu_stream_t stream) {
+  NABU_CHECK_ARG(p, "speller_beam_search: null pointer");
+  const BeamIO io = {{values}, {enc_len}, {p->memory_kernel}, {p->query_kernel}, {p->attention_v}, {p->conv_kernel},
+                     {p->conv_proj}, p->out_kernel, p->out_bias, p->lstm_kernel, p->lstm_bias, {alignments},
+                     sequences, lengths, num_steps, scores};
+  return beam_run(g, io, ws, ws_bytes, stream);
 }
 
 extern "C" int nabu_speller_beam_search(const nabu_beam_desc *d, const float *values, const int32_t *enc_len,
@@ -852,11 +950,22 @@ extern "C" int nabu_speller_beam_search(const nabu_beam_desc *d, const float *va
                                         size_t ws_bytes, nabu_stream_t stream) {
   BeamGeo g;
   if (int e = beam_geo(d, &g)) return e;
-  NABU_CHECK_ARG(p, "speller_beam_search: null pointer");
-  const BeamIO io = {{values}, {enc_len}, {p->memory_kernel}, {p->query_kernel}, {p->attention_v}, {p->conv_kernel},
-                     {p->conv_proj}, p->out_kernel, p->out_bias, p->lstm_kernel, p->lstm_bias, {alignments},
-                     sequences, lengths, num_steps, scores};
-  return beam_run(g, io, ws, ws_bytes, stream);
+  return decode_one(g, values, enc_len, p, sequences, lengths, scores, alignments, num_steps, ws, ws_bytes, stream);
+}
+
+extern "C" size_t nabu_speller_sample_ws_bytes(const nabu_beam_desc *d) {
+  BeamGeo g;
+  return beam_geo(d, &g, true) ? 0 : beam_ws(g).total * 4;
+}
+
+extern "C" int nabu_speller_sample(const nabu_beam_desc *d, const float *values, const int32_t *enc_len,
+                                   const nabu_speller_params *p, unsigned long long seed, unsigned long long offset0,
+                                   int32_t *sequences, int32_t *lengths, float *nll, float *alignments,
+                                   int32_t *num_steps, void *ws, size_t ws_bytes, nabu_stream_t stream) {
+  BeamGeo g;
+  if (int e = beam_geo(d, &g, true)) return e;
+  g.seed = seed; g.offset0 = offset0;
+  return decode_one(g, values, enc_len, p, sequences, lengths, nll, alignments, num_steps, ws, ws_bytes, stream);
 }
 
 extern "C" size_t nabu_speller_multi_beam_ws_bytes(const nabu_multi_beam_desc *d) {
@@ -864,13 +973,10 @@ extern "C" size_t nabu_speller_multi_beam_ws_bytes(const nabu_multi_beam_desc *d
   return beam_geo(d, &g) ? 0 : beam_ws(g).total * 4;
 }
 
-extern "C" int nabu_speller_multi_beam_search(const nabu_multi_beam_desc *d, const float *const *values,
-                                              const int32_t *const *enc_len, const nabu_speller_multi_params *p,
-                                              int32_t *sequences, int32_t *lengths, float *scores,
-                                              float *const *alignments, int32_t *num_steps, void *ws, size_t ws_bytes,
-                                              nabu_stream_t stream) {
-  BeamGeo g;
-  if (int e = beam_geo(d, &g)) return e;
+// the same over M encoded inputs
+static int decode_multi(BeamGeo &g, const float *const *values, const int32_t *const *enc_len,
+                        const nabu_speller_multi_params *p, int32_t *sequences, int32_t *lengths, float *scores,
+                        float *const *alignments, int32_t *num_steps, void *ws, size_t ws_bytes, nabu_stream_t stream) {
   NABU_CHECK_ARG(values && enc_len && p, "speller_multi_beam_search: null pointer");
   BeamIO io = {{}, {}, {}, {}, {}, {}, {}, p->out_kernel, p->out_bias, p->lstm_kernel, p->lstm_bias, {},
                sequences, lengths, num_steps, scores};
@@ -884,4 +990,30 @@ extern "C" int nabu_speller_multi_beam_search(const nabu_multi_beam_desc *d, con
     }
   }
   return beam_run(g, io, ws, ws_bytes, stream);
+}
+
+extern "C" int nabu_speller_multi_beam_search(const nabu_multi_beam_desc *d, const float *const *values,
+                                              const int32_t *const *enc_len, const nabu_speller_multi_params *p,
+                                              int32_t *sequences, int32_t *lengths, float *scores,
+                                              float *const *alignments, int32_t *num_steps, void *ws, size_t ws_bytes,
+                                              nabu_stream_t stream) {
+  BeamGeo g;
+  if (int e = beam_geo(d, &g)) return e;
+  return decode_multi(g, values, enc_len, p, sequences, lengths, scores, alignments, num_steps, ws, ws_bytes, stream);
+}
+
+extern "C" size_t nabu_speller_multi_sample_ws_bytes(const nabu_multi_beam_desc *d) {
+  BeamGeo g;
+  return beam_geo(d, &g, true) ? 0 : beam_ws(g).total * 4;
+}
+
+extern "C" int nabu_speller_multi_sample(const nabu_multi_beam_desc *d, const float *const *values,
+                                         const int32_t *const *enc_len, const nabu_speller_multi_params *p,
+                                         unsigned long long seed, unsigned long long offset0, int32_t *sequences,
+                                         int32_t *lengths, float *nll, float *const *alignments, int32_t *num_steps,
+                                         void *ws, size_t ws_bytes, nabu_stream_t stream) {
+  BeamGeo g;
+  if (int e = beam_geo(d, &g, true)) return e;
+  g.seed = seed; g.offset0 = offset0;
+  return decode_multi(g, values, enc_len, p, sequences, lengths, nll, alignments, num_steps, ws, ws_bytes, stream);
 }

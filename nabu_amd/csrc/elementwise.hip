@@ -160,20 +160,7 @@ __global__ __launch_bounds__(256) void sample_ids_kernel(int B, int C, const flo
   const uint4 r = philox4x32_10(make_uint4((unsigned)(b + b0), 0u, (unsigned)offset, (unsigned)(offset >> 32)),
                                 make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
   int id = teacher[b];
-  if (u01(r.x) < prob) {
-    const float *l = logits + (size_t)b * C;
-    float m = l[0];
-    for (int c = 1; c < C; ++c) m = fmaxf(m, l[c]);
-    float tot = 0.f;
-    for (int c = 0; c < C; ++c) tot += expf(l[c] - m);
-    const float target = u01(r.y) * tot;        // inverse CDF of softmax(l)
-    float acc = 0.f;
-    id = C - 1;
-    for (int c = 0; c < C; ++c) {
-      acc += expf(l[c] - m);
-      if (acc > target) { id = c; break; }
-    }
-  }
+  if (u01(r.x) < prob) id = softmax_draw(logits + (size_t)b * C, C, u01(r.y));
   out[b] = id;
 }
 
@@ -219,20 +206,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(int C, int U, int E, c
     lg[tid] = v;
   }
   __syncthreads();
-  if (tid == 0) {
-    float m = lg[0];
-    for (int c = 1; c < C; ++c) m = fmaxf(m, lg[c]);
-    float tot = 0.f;
-    for (int c = 0; c < C; ++c) tot += expf(lg[c] - m);
-    const float target = u01(r.y) * tot;        // inverse CDF of softmax(l)
-    float acc = 0.f;
-    int id = C - 1;
-    for (int c = 0; c < C; ++c) {
-      acc += expf(lg[c] - m);
-      if (acc > target) { id = c; break; }
-    }
-    out[b] = id;
-  }
+  if (tid == 0) out[b] = softmax_draw(lg, C, u01(r.y));
 }
 
 __global__ __launch_bounds__(256) void gaussian_noise_kernel(size_t n, const float *__restrict__ x,

@@ -5,5 +5,6 @@ factory = Registry('decoder', {
     'ctc_decoder': 'nabu_amd.neuralnetworks.decoders.ctc_decoder:CTCDecoder',
     'beam_search_decoder': 'nabu_amd.neuralnetworks.decoders.beam_search_decoder:BeamSearchDecoder',
     'alignment_decoder': 'nabu_amd.neuralnetworks.decoders.alignment_decoder:AlignmentDecoder',
-}, outside=('max_decoder', 'threshold_decoder', 'feature_decoder', 'random_decoder'),
+    'random_decoder': 'nabu_amd.neuralnetworks.decoders.random_decoder:RandomDecoder',
+}, outside=('max_decoder', 'threshold_decoder', 'feature_decoder'),
     undefined='Undefined %s type: %s')

@@ -37,7 +37,7 @@ class _Binding(object):
         self.desc_cls, self.beam_desc_cls, self.ws_key, self.beam_ws_key = desc_cls, beam_desc_cls, ws_key, beam_ws_key
 
     def fn(self, name):
-        """one of reserve_bytes, ws_bytes, uses_persistent, fwd, bwd, beam_ws_bytes, beam_search"""
+        """one of reserve_bytes, ws_bytes, uses_persistent, fwd, bwd, beam_ws_bytes, beam_search, sample_ws_bytes, sample"""
         return getattr(_hip.lib(), self.prefix + name)
 
     def desc(self, cls, Tes, Es, **fields):
@@ -208,15 +208,11 @@ def dynamic_decode(cell, encoded, encoded_seq_length, targets, target_seq_length
 dynamic_decode.events = None
 
 
-def beam_search(cell, encoded, encoded_seq_length, beam_width, max_steps, length_penalty=0.0,
-                temperature=1.0, with_alignments=True):
-    """Beam search over the projected attention cell (components/beam_search_decoder.py:68-451
-    under dynamic_decode): ONE call into the C ABI (nabu_speller_beam_search), whose C++ driver runs
-    the cell kernels on B*beam_width rows, prunes and gathers on the device, and stops as the
-    reference's dynamic_decode does.  encoded [B,Te,E] (rows >= length zero).
-    Returns (sequences [B,W,time] int32, lengths [B,W] int32, scores [B,W], alignments
-    [B,W,time,Te] or None).  encoded / encoded_seq_length may be lists (one entry per attention mechanism): several
-    memories run nabu_speller_multi_beam_search and return the alignments as a list of [B,W,time,Te_m], one per memory."""
+def _free_run(which, cell, encoded, encoded_seq_length, beam_width, max_steps, length_penalty, temperature,
+              with_alignments, *extra):
+    """The call beam_search and sample share: `which` is 'beam' (nabu_speller[_multi]_beam_search) or 'sample'
+    (nabu_speller[_multi]_sample, beam_width 1, `extra` = seed, offset).  Returns (sequences [B,W,time] int32,
+    lengths [B,W] int32, scores or nll [B,W], [alignments [B,W,time,Te_m] per memory] or None, the binding)."""
     abi, encoded, encoded_seq_length = _memories(encoded, encoded_seq_length)
     dev = encoded[0].device
     B = encoded[0].shape[0]
@@ -228,9 +224,10 @@ def beam_search(cell, encoded, encoded_seq_length, beam_width, max_steps, length
     desc = abi.desc(abi.beam_desc_cls, Tes, Es, B=B, U=U, C=C, num_layers=nl, kind=mech.kind, K=mech.filtersize,
                     F=mech.numfilt, prob_fn=mech.prob_fn, beam_width=W, max_steps=S,
                     length_penalty=float(length_penalty), temperature=float(temperature))
-    ws_bytes = abi.fn('beam_ws_bytes')(ctypes.byref(desc))
+    name = 'beam_search' if which == 'beam' else which
+    ws_bytes = abi.fn(which + '_ws_bytes')(ctypes.byref(desc))
     if ws_bytes == 0:
-        raise _hip.NabuHipError('beam search: unsupported shape: %s' % _hip.lib().nabu_last_error().decode())
+        raise _hip.NabuHipError('%s: unsupported shape: %s' % (name, _hip.lib().nabu_last_error().decode()))
     values = [e if e.is_contiguous() else e.contiguous() for e in encoded]
     seq = torch.empty((B, W, S), dtype=torch.int32, device=dev)
     lengths = torch.empty((B, W), dtype=torch.int32, device=dev)
@@ -239,12 +236,39 @@ def beam_search(cell, encoded, encoded_seq_length, beam_width, max_steps, length
     ws = _hip.Workspace.get(ws_bytes, dev, abi.beam_ws_key)
     params = abi.params(named, lstm, grad=False)
     steps = ctypes.c_int32(0)
-    _hip.check(abi.fn('beam_search')(ctypes.byref(desc), abi.pointers(values), abi.pointers([l.dev for l in elens]),
-                                     ctypes.byref(params), _hip.ptr(seq), _hip.ptr(lengths), _hip.ptr(scores),
-                                     abi.pointers(aligns), ctypes.byref(steps), _hip.ptr(ws), ws_bytes, _hip.stream()),
-               abi.prefix + 'beam_search')
+    _hip.check(abi.fn(name)(ctypes.byref(desc), abi.pointers(values), abi.pointers([l.dev for l in elens]),
+                            ctypes.byref(params), *extra, _hip.ptr(seq), _hip.ptr(lengths), _hip.ptr(scores),
+                            abi.pointers(aligns), ctypes.byref(steps), _hip.ptr(ws), ws_bytes, _hip.stream()),
+               abi.prefix + name)
     n = steps.value
-    return seq[:, :, :n], lengths, scores, (abi.per_memory([a[:, :, :n] for a in aligns]) if with_alignments else None)
+    return seq[:, :, :n], lengths, scores, ([a[:, :, :n] for a in aligns] if with_alignments else None), abi
+
+
+def beam_search(cell, encoded, encoded_seq_length, beam_width, max_steps, length_penalty=0.0,
+                temperature=1.0, with_alignments=True):
+    """Beam search over the projected attention cell (components/beam_search_decoder.py:68-451
+    under dynamic_decode): ONE call into the C ABI (nabu_speller_beam_search), whose C++ driver runs
+    the cell kernels on B*beam_width rows, prunes and gathers on the device, and stops as the
+    reference's dynamic_decode does.  encoded [B,Te,E] (rows >= length zero).
+    Returns (sequences [B,W,time] int32, lengths [B,W] int32, scores [B,W], alignments
+    [B,W,time,Te] or None).  encoded / encoded_seq_length may be lists (one entry per attention mechanism): several
+    memories run nabu_speller_multi_beam_search and return the alignments as a list of [B,W,time,Te_m], one per memory."""
+    seq, lengths, scores, aligns, abi = _free_run('beam', cell, encoded, encoded_seq_length, beam_width, max_steps,
+                                                  length_penalty, temperature, with_alignments)
+    return seq, lengths, scores, (abi.per_memory(aligns) if with_alignments else None)
+
+
+def sample(cell, encoded, encoded_seq_length, max_steps, seed, offset, with_alignments=False):
+    """One sample per utterance from the projected attention cell run free on its own draws (SampleEmbeddingHelper +
+    BasicDecoder under dynamic_decode(maximum_iterations=max_steps)): ONE call into the C ABI (nabu_speller_sample:
+    the beam search's loop on B rows with nabu_sample_advance in the place of pruning and gathering).  Step t draws
+    with the device Philox at (seed, offset + t).  encoded / encoded_seq_length as for beam_search, lists included.
+    Returns (sequences [B,time] int32, zero beyond lengths; lengths [B] int32, which count the end label and are
+    max_steps for a row that never drew it; nll [B], the summed cross-entropy of the sample; alignments [B,time,Te],
+    a list of them for several memories, or None)."""
+    seq, lengths, nll, aligns, abi = _free_run('sample', cell, encoded, encoded_seq_length, 1, max_steps, 0.0, 1.0,
+                                               with_alignments, int(seed), int(offset))
+    return seq[:, 0], lengths[:, 0], nll[:, 0], (abi.per_memory([a[:, 0] for a in aligns]) if with_alignments else None)
 
 
 def decoder_inputs():

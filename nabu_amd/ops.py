@@ -759,6 +759,18 @@ def beam_gather(fresh, old, parent, stay):
     return dst
 
 
+def sample_advance(logits, seed, offset, t, sequences, lengths, finished, nll):
+    """one step of the sampled decode on its own; logits [B,C]; sequences [B,max_steps], lengths, finished and
+    nll [B] are updated in place.  Returns (next_ids [B], all_finished [1])"""
+    B, C = logits.shape
+    next_ids = torch.empty((B,), dtype=torch.int32, device=logits.device)
+    all_finished = torch.empty((1,), dtype=torch.int32, device=logits.device)
+    check(_hip.lib().nabu_sample_advance(B, C, ptr(logits.contiguous()), seed, offset, int(t), sequences.shape[1],
+                                         ptr(sequences), ptr(lengths), ptr(finished), ptr(nll), ptr(next_ids),
+                                         ptr(all_finished), stream()), 'nabu_sample_advance')
+    return next_ids, all_finished
+
+
 def persist_clocks(device=None):
     """{'fwd': GHz, 'bwd': GHz} — the shader clock the chip sustained under the LAST fp16-plane recurrent launch of each
     pass on this device's 'blstm' workspace (lstm_persist_dev.h, clock_stamp: shader-cycle and 100 MHz wall-clock ticks
