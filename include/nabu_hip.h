@@ -694,6 +694,37 @@ int nabu_axpy_f32(size_t n, float a, const float *x, float *y, nabu_stream_t str
 int nabu_ceil_div_i32(int n, const int32_t *in, int d, int32_t *out, nabu_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Batch input: one packed buffer -> every padded tensor of a batch, in one launch.  Replaces the dynamic_pad of the
+ * reference's batch queues (processing/input_pipeline.py:121-174, tf.train.batch / bucket_by_sequence_length) plus
+ * the per-tensor feeds: the host packs the utterances WITHOUT padding, uploads the buffer with one copy and this call
+ * writes each tensor padded, with its length vector.
+ *
+ * `packed` (device, 16-byte aligned, packed_bytes long) holds, per tensor of the batch (a segment), at byte offsets
+ * the descriptor names:
+ *   len_off   rows int32 lengths (4-byte aligned);
+ *   row_off   rows + 1 int32 ELEMENT offsets of the rows into the segment's data: the prefix sum of len[b] * width,
+ *             computed by the packer (4-byte aligned);
+ *   data_off  the rows back to back, len[b] * width 4-byte elements each — float32 features or int32 labels, the
+ *             kernel moves bits (16-byte aligned).
+ * Result, per segment: out[b, t, :] = row b's element t for t < len[b] and 0 for len[b] <= t < max_len — EVERY element
+ * of out [rows, max_len, width] is written — and out_len[b] = len[b] clamped to [0, max_len].  The clamp comes before
+ * any use of the length, and a row whose offsets leave the packed buffer is written as zeros: a corrupt header cannot
+ * make the kernel read or write out of bounds.  Segments with width % 4 == 0 and a 16-byte aligned out move 16 bytes per
+ * lane, all others 4.
+ * segs_host: nseg descriptors in HOST memory (copied into the kernel arguments; free to reuse when the call returns).
+ * NABU_EINVAL before any launch: a null pointer, nseg outside 1..NABU_BATCH_MAX_SEGS, rows / width / max_len <= 0,
+ * rows * max_len * width >= 2^31, a misaligned offset or pointer, an offset or extent outside packed_bytes. */
+typedef struct {
+  int32_t rows, width, max_len, reserved;     /* B, F (1 for label vectors), padded time extent; reserved = 0 */
+  uint64_t len_off, row_off, data_off;        /* byte offsets into `packed` */
+  void *out;                                  /* [rows, max_len, width] 4-byte elements */
+  int32_t *out_len;                           /* [rows] */
+} nabu_batch_seg;
+#define NABU_BATCH_MAX_SEGS 8
+int nabu_batch_unpack(int nseg, const nabu_batch_seg *segs_host, const void *packed_dev, size_t packed_bytes,
+                      nabu_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * DNNDecoder hidden layers (models/ed_decoders/dnn_decoder.py:40-51):
  * tf.contrib.layers.fully_connected = linear + ReLU, optional
  * tf.contrib.layers.layer_norm, dropout.  The linear part is nabu_gemm_f32.

@@ -53,6 +53,15 @@ class FeatDesc(_c.Structure):
                [('preemph', _c.c_float), ('ceplifter', _c.c_float), ('winlen', _c.c_double), ('winstep', _c.c_double)]
 
 
+class BatchSeg(_c.Structure):
+    """nabu_batch_seg: one tensor of a packed batch (nabu_batch_unpack)"""
+    _fields_ = [('rows', _c.c_int32), ('width', _c.c_int32), ('max_len', _c.c_int32), ('reserved', _c.c_int32),
+                ('len_off', _c.c_uint64), ('row_off', _c.c_uint64), ('data_off', _c.c_uint64),
+                ('out', _c.c_void_p), ('out_len', _c.c_void_p)]
+
+
+BATCH_MAX_SEGS = 8
+
 FEAT_KINDS = {'fbank': 0, 'mfcc': 1}
 FEAT_DYNAMIC = {'nodelta': 0, 'delta': 1, 'ddelta': 2}
 
@@ -153,6 +162,7 @@ SIGNATURES = {
     'nabu_sum_f32': (_i, [_sz, _vp, _f, _vp, _vp]),
     'nabu_axpy_f32': (_i, [_sz, _f, _vp, _vp, _vp]),
     'nabu_ceil_div_i32': (_i, [_i, _vp, _i, _vp, _vp]),
+    'nabu_batch_unpack': (_i, [_i, _vp, _vp, _sz, _vp]),
     'nabu_ctc_beam_ws_bytes': (_sz, [_i, _i, _i, _i]),
     'nabu_ctc_beam_search': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nabu_edit_distance': (_i, [_i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),

@@ -106,15 +106,26 @@ def sum_cross_entropy(targets, logits, logit_seq_length, target_seq_length):
     return _total(losses)
 
 
-def check_status():
-    '''raise (as tf.nn.ctc_loss does) if any CTC utterance had no valid alignment'''
+def ctc_status_error(code):
+    '''the exception a non-zero status word of the CTC kernel stands for'''
+    return Exception('CTC: Not enough time for target transition sequence '
+                     '(utterance %d of the batch)' % (code - 1))
+
+
+def take_pending_status():
+    '''the status words of the CTC kernels launched since the last check; the caller reads them (the overlapped
+    training loop does, one step late: trainers/readback.py)'''
     global pending_status
     todo, pending_status = pending_status, []
-    for s in todo:
+    return todo
+
+
+def check_status():
+    '''raise (as tf.nn.ctc_loss does) if any CTC utterance had no valid alignment'''
+    for s in take_pending_status():
         code = int(s.item())
         if code:
-            raise Exception('CTC: Not enough time for target transition sequence '
-                            '(utterance %d of the batch)' % (code - 1))
+            raise ctc_status_error(code)
     # a persistent recurrent kernel that gave up (bounded-spin timeout) leaves the results of the
     # step invalid and its status word set: raise here, where the training / validation loops
     # already synchronise

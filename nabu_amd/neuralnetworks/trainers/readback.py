@@ -1,0 +1,57 @@
+"""The lagged read-back of the overlapped training loop (Trainer._train_overlapped).
+
+What the synchronous loop reads from the device after every step — the loss, one status word per CTC kernel
+(loss_functions.pending_status) and the status word of every persistent-kernel workspace (ops.check_persist_status) —
+lands in ONE pinned record per step: a few asynchronous copies on the launch stream, closed by an event.  The record of
+step s is read after step s + 1 has been enqueued, so the host never waits for the step it has just launched."""
+import numpy as np
+import torch
+
+from nabu_amd import ops as hip
+from nabu_amd.neuralnetworks.trainers import loss_functions
+
+WORDS = 32          # 1 loss word + CTC status words (one per output) + one word per persistent-kernel workspace
+
+
+class StepRecord(object):
+    '''host words of one step: [0] the loss (float32 bits), [1 : 1 + n_ctc] the CTC status words, then one status word
+    per workspace of `workspaces`'''
+
+    def __init__(self, pinned=False):
+        self.host = torch.zeros(WORDS, dtype=torch.int32, pin_memory=pinned)
+        self.event = None
+        self.step, self.n_ctc, self.workspaces = None, 0, []
+
+    def fill(self, step, loss, ctc_status, workspaces):
+        '''enqueue the copies of this step's words behind the step (device tensors: asynchronous, closed by an event)'''
+        if 1 + len(ctc_status) + len(workspaces) > WORDS:
+            raise Exception('a step record holds %d words, this step has %d' % (WORDS, 1 + len(ctc_status) + len(workspaces)))
+        self.step, self.n_ctc, self.workspaces = step, len(ctc_status), list(workspaces)
+        self.host[0:1].view(torch.float32).copy_(loss.detach().reshape(1).to(torch.float32), non_blocking=True)
+        for i, s in enumerate(ctc_status):
+            self.host[1 + i:2 + i].copy_(s.reshape(1), non_blocking=True)
+        for i, (tag, buf) in enumerate(self.workspaces):
+            self.host[1 + self.n_ctc + i:2 + self.n_ctc + i].copy_(buf[:4].view(torch.int32), non_blocking=True)
+        self.event = None
+        if loss.is_cuda:
+            self.event = torch.cuda.Event()
+            self.event.record()
+        return self
+
+    def read(self):
+        '''wait for the step and return its loss; raises what the synchronous loop raises for a non-zero status word,
+        with the step it belongs to (a persistent kernel's word is cleared, as ops.check_persist_status clears it)'''
+        if self.event is not None:
+            self.event.synchronize()
+            self.event = None
+        words = self.host.numpy()
+        for code in words[1:1 + self.n_ctc]:
+            if code:
+                raise Exception('%s [step %d]' % (loss_functions.ctc_status_error(int(code)), self.step))
+        for (tag, buf), code in zip(self.workspaces, words[1 + self.n_ctc:]):
+            if code:
+                if buf is not None:
+                    buf[:4].zero_()
+                err = hip.persist_status_error(tag, int(code))
+                raise type(err)('%s [step %d]' % (err, self.step))
+        return float(words[0:1].view(np.float32)[0])

@@ -456,6 +456,8 @@ class Trainer(object, metaclass=ABCMeta):
             self._ensure_variables()
             self.load_state(torch.load(ckpt, weights_only=False))
             print('WORKER %d: resumed from %s at step %d' % (self.task_index, ckpt, self.global_step))
+        if int(self.conf.get('prefetch_batches', 0)) > 0:      # extension key: batches staged ahead, losses read one step late
+            return self._train_overlapped(num_steps, ckpt, history, int(self.conf['prefetch_batches']))
         last_ckpt = time.time()
         while self.global_step < num_steps:
             if (self.evaluator is not None
@@ -488,6 +490,109 @@ class Trainer(object, metaclass=ABCMeta):
                     time.time() - last_ckpt > CHECKPOINT_SECS or (every and self.global_step % every == 0)):
                 self.save_checkpoint(ckpt)
                 last_ckpt = time.time()
+        if is_chief and self.expdir is not None:
+            self.save_checkpoint(ckpt)
+            self.save()
+        return history
+
+    # ------------------------------------------------- overlapped loop (prefetch_batches >= 1)
+    def stage(self, batch, slot=None):
+        '''numpy batch -> packed batch (processing/prefetch.py), written into the pinned `slot` when one is given.
+        Runs on a prefetcher thread: no device call in here.'''
+        from nabu_amd.processing import prefetch
+        return prefetch.stage(batch, slot)
+
+    def to_device_staged(self, staged, device=None):
+        '''packed batch -> what to_device returns for the same batch: ONE asynchronous upload on the launch stream
+        and ONE launch (nabu_batch_unpack) that writes every padded tensor and length vector'''
+        if device is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        n = staged.nbytes
+        src = staged.slot.tensor if staged.slot is not None else torch.from_numpy(staged.array)
+        packed = hip.Workspace.get(n, device, 'batch')
+        packed[:n].copy_(src[:n], non_blocking=True)
+        if staged.slot is not None:                       # the slot is free again once this copy has read it
+            uploaded = torch.cuda.Event()
+            uploaded.record()
+            staged.slot.uploaded(uploaded)
+        out = dict(inputs={}, targets={}, input_seq_length={}, target_seq_length={})
+        segs = []
+        for s in staged.segments:
+            data = torch.empty(s.shape, dtype=torch.float32 if s.key == 'inputs' else torch.int32, device=device)
+            lens = torch.empty(s.rows, dtype=torch.int32, device=device)
+            segs.append(s.describe() + (data, lens))
+            out[s.key][s.name] = data
+            out['input_seq_length' if s.key == 'inputs' else 'target_seq_length'][s.name] = SeqLen(
+                np.clip(s.lengths, 0, s.max_len), dev_tensor=lens)
+        for i in range(0, len(segs), 8):                  # NABU_BATCH_MAX_SEGS per launch
+            hip.batch_unpack(segs[i:i + 8], packed, n)
+        return out
+
+    def _train_overlapped(self, num_steps, ckpt, history, depth):
+        '''train()'s loop with the host work taken off the step's critical path: batches come staged from a
+        BatchPrefetcher (`depth` ahead), are uploaded with one copy and unpacked by one launch, and the loss and
+        status words of step s are read after step s + 1 has been enqueued (trainers/readback.py).  Pending records
+        are drained before every validation point, before every checkpoint and at the end, so history, validation
+        decisions and checkpoints are those of the synchronous loop; an infeasible CTC batch or a persistent kernel's
+        time-out raises one iteration late, naming its step.'''
+        from nabu_amd.processing.prefetch import BatchPrefetcher, PinnedRing
+        from nabu_amd.neuralnetworks.trainers.readback import StepRecord
+        is_chief = self.task_index == 0
+        on_gpu = torch.cuda.is_available()
+        pending, spare = [], []                # records enqueued and not read yet / read and free to reuse
+
+        def finish(rec):
+            loss_value = rec.read() / self.world
+            mem_used = torch.cuda.max_memory_allocated() if on_gpu else 0
+            mem_total = torch.cuda.get_device_properties(0).total_memory if on_gpu else 0
+            print(('WORKER %d: step %d/%d loss: %f, learning rate: %f \n\t time elapsed: %f sec'
+                   '\n\t peak memory usage: %d/%d MB')
+                  % (self.task_index, rec.step, num_steps, loss_value, rec.lr,
+                     time.time() - rec.start, mem_used / 1e6, mem_total / 1e6))
+            history.append((rec.step, loss_value, rec.lr))
+            spare.append(rec)
+
+        def drain(keep=0):
+            while len(pending) > keep:
+                finish(pending.pop(0))
+
+        def shard():
+            return self.global_step * self.world + self.task_index
+
+        self._prefetcher = BatchPrefetcher(self.data, shard(), self.world, depth,
+                                           int(self.conf.get('prefetch_workers', 2)), self.stage,
+                                           PinnedRing(depth + 1) if on_gpu else None)
+        try:
+            last_ckpt = time.time()
+            while self.global_step < num_steps:
+                if (self.evaluator is not None
+                        and self.global_step - self.validated_step >= int(self.conf['valid_frequency'])):
+                    drain()
+                    self._ensure_variables()
+                    if self._validation_point():
+                        break
+                if self._prefetcher.next_step != shard():      # a go-back restored an earlier global step
+                    self._prefetcher.reset(shard())
+                start = time.time()
+                batch = self.to_device_staged(self._prefetcher.get())
+                loss = self.step(batch)
+                if self.world > 1:
+                    loss = self.server.all_reduce_sum_(loss.clone())
+                rec = spare.pop() if spare else StepRecord(pinned=on_gpu)
+                rec.fill(self.global_step, loss, loss_functions.take_pending_status(), hip.persist_workspaces())
+                rec.lr, rec.start = self.last_lr, start
+                pending.append(rec)
+                self.global_step += 1
+                drain(keep=1)                                   # read step s now that step s + 1 is enqueued
+                every = getattr(self, 'checkpoint_steps', None)
+                if is_chief and ckpt is not None and (
+                        time.time() - last_ckpt > CHECKPOINT_SECS or (every and self.global_step % every == 0)):
+                    drain()
+                    self.save_checkpoint(ckpt)
+                    last_ckpt = time.time()
+            drain()
+        finally:
+            self._prefetcher.close()
         if is_chief and self.expdir is not None:
             self.save_checkpoint(ckpt)
             self.save()

@@ -496,20 +496,29 @@ def set_persist_timeout_ms(ms):
     check(_hip.lib().nabu_persist_set_timeout_us(int(ms * 1000)), 'nabu_persist_set_timeout_us')
 
 
+def persist_workspaces():
+    """[(tag, buffer)] of the workspaces whose first int32 is a persistent kernel's status word"""
+    # 'speller': the persistent decoder kernel (speller_persist.hip)
+    return [(tag, buf) for (dev, tag), buf in list(Workspace._bufs.items()) if tag in ('blstm', 'speller')]
+
+
+def persist_status_error(tag, code):
+    """the exception a non-zero status word of the `tag` workspace stands for"""
+    return _hip.NabuHipError(
+        'persistent %s kernel timed out waiting for a peer workgroup (code %d: block %d, %s); '
+        'results of this step are invalid' % ('LSTM' if tag == 'blstm' else 'decoder', code, code // 4,
+                                              {1: 'forward pass', 2: 'backward pass',
+                                               3: 'start-up handshake'}.get(code % 4, '?')))
+
+
 def check_persist_status(device=None):
     """Raise if a persistent recurrent kernel gave up (bounded-spin timeout); the
     status word is the first int32 of the 'blstm' / 'speller' workspace.  Synchronises."""
-    for (dev, tag), buf in list(Workspace._bufs.items()):
-        if tag not in ('blstm', 'speller'):     # 'speller': the persistent decoder kernel (speller_persist.hip)
-            continue
+    for tag, buf in persist_workspaces():
         code = int(buf[:4].view(torch.int32).item())
         if code:
             buf[:4].zero_()
-            raise _hip.NabuHipError(
-                'persistent %s kernel timed out waiting for a peer workgroup (code %d: block %d, %s); '
-                'results of this step are invalid' % ('LSTM' if tag == 'blstm' else 'decoder', code, code // 4,
-                                                      {1: 'forward pass', 2: 'backward pass',
-                                                       3: 'start-up handshake'}.get(code % 4, '?')))
+            raise persist_status_error(tag, code)
 
 
 # ---------------------------------------------------------------- speller step kernels
@@ -703,6 +712,26 @@ def ceil_div_i32(x, d):
     out = torch.empty_like(x)
     check(_hip.lib().nabu_ceil_div_i32(x.numel(), ptr(x), int(d), ptr(out), stream()), 'nabu_ceil_div_i32')
     return out
+
+
+def batch_unpack(segs, packed, packed_bytes=None):
+    """One launch writes every padded tensor of a packed batch (processing/prefetch.py lays the buffer out).
+    segs: up to 8 (rows, width, max_len, len_off, row_off, data_off, out, out_len) with out a contiguous
+    [rows, max_len * width] (any shape of that size) float32 or int32 device tensor and out_len a [rows] int32 one;
+    packed: the uint8 device buffer the batch was uploaded into."""
+    if packed_bytes is None:
+        packed_bytes = packed.numel() * packed.element_size()
+    arr = (_hip.BatchSeg * len(segs))()
+    for d, (rows, width, max_len, len_off, row_off, data_off, out, out_len) in zip(arr, segs):
+        if out.element_size() != 4 or out.numel() != rows * max_len * width:
+            raise _hip.NabuHipError('batch_unpack: out must hold rows * max_len * width 4-byte elements')
+        if out_len.dtype != torch.int32 or out_len.numel() != rows:
+            raise _hip.NabuHipError('batch_unpack: out_len must be [rows] int32')
+        d.rows, d.width, d.max_len, d.reserved = int(rows), int(width), int(max_len), 0
+        d.len_off, d.row_off, d.data_off = int(len_off), int(row_off), int(data_off)
+        d.out, d.out_len = ptr(out), ptr(out_len)
+    check(_hip.lib().nabu_batch_unpack(len(segs), ctypes.cast(arr, ctypes.c_void_p), ptr(packed), int(packed_bytes),
+                                       stream()), 'nabu_batch_unpack')
 
 
 # --------------------------------------------------------------------------

@@ -196,6 +196,11 @@ class RecordData(object):
         except Exception:
             pass
 
+    def assemble(self, step):
+        '''batch number `step`, like batch(step) but without its look-ahead bookkeeping: safe to call from several
+        threads at once (processing.prefetch.BatchPrefetcher does), in any order of steps'''
+        return self._assemble(step)
+
     def _assemble(self, step):
         with self._lock:                                   # the schedule and the carries are shared state
             indices = list(self._indices(step))
