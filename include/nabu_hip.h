@@ -682,6 +682,40 @@ int nabu_gaussian_noise_f32(size_t n, const float *x, float *y, float stddev,
                             unsigned long long seed, unsigned long long offset,
                             nabu_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * SpecAugment of the encoder's input features (a build addition: the reference has no counterpart): a linear time
+ * warp about one random anchor frame, then time_masks time masks and freq_masks frequency masks that write zeros.
+ * Out of place, one launch: x [B, T, D] batch-major, len [B] (device; a length outside 0..T is clamped), y [B, T, D].
+ * Utterance b of n = len[b] frames draws Philox4x32-10 words (x, y, ., .) with key (seed_lo, seed_hi) and counter
+ * (b, k, offset_lo, offset_hi); below(w, m) = ((w >> 8) * m) >> 24 in 64 bits is a uniform integer in [0, m):
+ *   k = 0, only if W = time_warp > 0 and n >= 2 W + 3: anchor c = W + 1 + below(x, n - 2 W - 2) moves to
+ *     c' = c - W + below(y, 2 W + 1).  Output frame t reads source position p / q = t c / c' for t < c' and
+ *     (c (n-1-c') + (t-c') (n-1-c)) / (n-1-c') otherwise: i = p div q, r = p mod q (64-bit integers),
+ *     out = fmaf((float)r / (float)q, in[i+1] - in[i], in[i]) when r > 0 and in[i] when r = 0 (frames 0, c', n - 1 are
+ *     frames 0, c, n - 1 exactly);
+ *   k = 1 + j, time mask j: t = below(x, min(time_mask_width, (int)(time_mask_ratio * (float)n)) + 1) frames from
+ *     t0 = below(y, n - t + 1) become 0;
+ *   k = 1 + time_masks + j, frequency mask j: with Dblk = D / feature_blocks, f = below(x, min(freq_mask_width,
+ *     Dblk) + 1) columns from f0 = below(y, Dblk - f + 1) of EVERY block become 0 in the frames t < n.
+ * Frames t >= n are copied.  Neither x nor y needs any alignment beyond a float's.
+ * params: NULL or int32 [B, 2 + 2 time_masks + 2 freq_masks], written (c, c', t0_0, t_0, ..., f0_0, f_0, ...) per
+ *   utterance ((c, c') = (0, 0) for an utterance that is not warped).
+ * NABU_EINVAL: a null pointer, overlapping x and y, negative values, more than 8 masks of a kind, time_mask_ratio
+ *   outside (0, 1], feature_blocks < 1 or not a divisor of D, time_warp >= 2^24.  NABU_EUNSUP: T >= 2^24 (lengths and
+ *   remainders must be exact in float32), T * D >= 2^31 - 16, B > 65535. */
+typedef struct nabu_specaug_desc {
+  uint32_t size;            /* sizeof(nabu_specaug_desc) */
+  int32_t B, T, D;
+  int32_t feature_blocks;   /* equal column blocks of the feature vector (3 for static + delta + delta-delta) */
+  int32_t time_warp;        /* W */
+  int32_t time_masks, time_mask_width;
+  int32_t freq_masks, freq_mask_width;
+  float time_mask_ratio;
+} nabu_specaug_desc;
+int nabu_spec_augment_f32(const nabu_specaug_desc *desc, const float *x, const int32_t *len, float *y,
+                          int32_t *params, unsigned long long seed, unsigned long long offset,
+                          nabu_stream_t stream);
+
 /* out[0] = scale * sum(x) (deterministic single-block tree): tf.reduce_mean of
  * the per-utterance losses (trainers/loss_functions.py:161,206-212). */
 int nabu_sum_f32(size_t n, const float *x, float scale, float *out, nabu_stream_t stream);

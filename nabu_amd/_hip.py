@@ -62,6 +62,16 @@ class BatchSeg(_c.Structure):
 
 BATCH_MAX_SEGS = 8
 
+
+class SpecAugDesc(_c.Structure):
+    """nabu_specaug_desc (nabu_spec_augment_f32)"""
+    _fields_ = [('size', _c.c_uint32)] + [(n, _c.c_int32) for n in
+                                          ('B', 'T', 'D', 'feature_blocks', 'time_warp', 'time_masks', 'time_mask_width',
+                                           'freq_masks', 'freq_mask_width')] + [('time_mask_ratio', _c.c_float)]
+
+
+SPECAUG_MAX_MASKS = 8
+
 FEAT_KINDS = {'fbank': 0, 'mfcc': 1}
 FEAT_DYNAMIC = {'nodelta': 0, 'delta': 1, 'ddelta': 2}
 
@@ -159,6 +169,7 @@ SIGNATURES = {
     'nabu_clip_f32': (_i, [_sz, _vp, _f, _vp]),
     'nabu_dropout_f32': (_i, [_sz, _vp, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _vp]),
     'nabu_gaussian_noise_f32': (_i, [_sz, _vp, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _vp]),
+    'nabu_spec_augment_f32': (_i, [_c.POINTER(SpecAugDesc), _vp, _vp, _vp, _vp, _c.c_ulonglong, _c.c_ulonglong, _vp]),
     'nabu_sum_f32': (_i, [_sz, _vp, _f, _vp, _vp]),
     'nabu_axpy_f32': (_i, [_sz, _f, _vp, _vp, _vp]),
     'nabu_ceil_div_i32': (_i, [_i, _vp, _i, _vp, _vp]),

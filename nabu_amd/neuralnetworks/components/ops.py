@@ -134,6 +134,25 @@ def input_noise(x, stddev, rng_state):
     return y
 
 
+def spec_augment(x, lengths, policy, rng_state):
+    """SpecAugment of the features x [B, T, D] (hip.SpecAugmentPolicy; the rules: DESIGN.md): a time warp about a random
+    anchor frame, then time and frequency masks of zeros, drawn per utterance from ONE rng_state.next().  A policy
+    that is off makes no call and consumes no offset."""
+    if not policy.on:
+        return x
+    if requires_grad(x):     # (interpolation has a gradient, and nothing here computes it: features are leaves)
+        raise Exception('spec_augment: the features depend on a parameter; the augmentation computes no input gradient')
+    if x.shape[2] % policy.feature_blocks:
+        raise ValueError('feature_blocks = %d does not divide the feature dimension %d' % (policy.feature_blocks,
+                                                                                          x.shape[2]))
+    lens = SeqLen.wrap(lengths, x.device)
+    seed, offset = rng_state.next()
+    y = hip.spec_augment(x if x.is_contiguous() else x.contiguous(), lens.dev, policy, seed, offset)
+    if value_bound(x):       # (a convex combination of two frames, or zero: no larger than its inputs)
+        set_value_bound(y, value_bound(x))
+    return y
+
+
 class RngState(object):
     """Seed + running offset for the counter-based device RNG."""
 

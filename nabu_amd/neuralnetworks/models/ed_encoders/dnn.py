@@ -30,6 +30,7 @@ from nabu_amd.autodiff import record, requires_grad, SeqLen
 from nabu_amd.neuralnetworks.components import ops
 from nabu_amd.neuralnetworks.models.ed_decoders import dnn_decoder
 from nabu_amd.neuralnetworks.models.ed_encoders import ed_encoder
+from nabu_amd.neuralnetworks.models.ed_encoders.listener import SPEC_AUGMENT_KEYS
 
 SPLICE_LD_MULTIPLE = 32     # the bf16 product kernels' reduction tile
 
@@ -109,7 +110,15 @@ def splice_ld(width, context):
 
 class DNN(ed_encoder.EDEncoder):
     """cfg keys: num_units, num_layers, input_noise (ignored, as in the reference), dropout (keep probability),
-    context, layer_norm, gemm_precision (build addition)"""
+    context, layer_norm, gemm_precision (build addition).  The SpecAugment keys of the recurrent encoders are refused:
+    the targets are frame-synchronous alignments, which a time warp would break."""
+
+    def __init__(self, conf, constraint, name=None):
+        super(DNN, self).__init__(conf, constraint, name)
+        found = [k for k in SPEC_AUGMENT_KEYS if k in self.conf]
+        if found:
+            raise Exception('DNN encoder: the SpecAugment keys (%s) are not supported: the targets are alignments, one '
+                            'per frame, and the augmentation moves and masks frames' % ', '.join(found))
 
     def encode(self, inputs, input_seq_length, is_training):
         precision = self.conf.get('gemm_precision', 'default')

@@ -1,6 +1,7 @@
 """Typed Python wrappers over the C ABI (one function per entry point of
 include/nabu_hip.h).  Tensors are torch CUDA tensors used as device-memory
 handles; all arithmetic happens inside libnabu_hip.so."""
+import collections
 import ctypes
 
 import torch
@@ -373,6 +374,51 @@ def gaussian_noise(x, stddev, seed, offset):
     y = torch.empty_like(x)
     check(_hip.lib().nabu_gaussian_noise_f32(x.numel(), ptr(x), ptr(y), stddev, seed, offset, stream()),
           'nabu_gaussian_noise_f32')
+    return y
+
+
+SPECAUG_MAX_MASKS = _hip.SPECAUG_MAX_MASKS       # masks of one kind per utterance (include/nabu_hip.h)
+
+
+class SpecAugmentPolicy(collections.namedtuple('SpecAugmentPolicy', [
+        'time_warp', 'time_masks', 'time_mask_width', 'time_mask_ratio', 'freq_masks', 'freq_mask_width',
+        'feature_blocks'])):
+    """what nabu_spec_augment_f32 does to every utterance (include/nabu_hip.h): the anchor's largest shift W, the
+    number and the largest width of the time masks (a width is also capped at time_mask_ratio times the length) and of
+    the frequency masks, and the number of equal column blocks a frequency mask repeats in"""
+    __slots__ = ()
+
+    def __new__(cls, time_warp=0, time_masks=0, time_mask_width=0, time_mask_ratio=1.0, freq_masks=0,
+                freq_mask_width=0, feature_blocks=1):
+        return super(SpecAugmentPolicy, cls).__new__(cls, int(time_warp), int(time_masks), int(time_mask_width),
+                                                     float(time_mask_ratio), int(freq_masks), int(freq_mask_width),
+                                                     int(feature_blocks))
+
+    @property
+    def on(self):
+        """False: the policy draws nothing and changes nothing"""
+        return self.time_warp > 0 or self.time_masks > 0 or self.freq_masks > 0
+
+    @property
+    def param_width(self):
+        """ints per utterance of the parameter buffer: (c, c'), (t0, t) per time mask, (f0, f) per frequency mask"""
+        return 2 + 2 * self.time_masks + 2 * self.freq_masks
+
+
+def spec_augment(x, len_dev, policy, seed, offset, params=None):
+    """SpecAugment of x [B, T, D] with the device lengths len_dev [B] at the stream (seed, offset); params: an int32
+    [B, policy.param_width] device tensor that receives what was drawn, or None"""
+    B, T, D = x.shape
+    y = torch.empty_like(x)
+    if params is not None and (params.dtype != torch.int32 or tuple(params.shape) != (B, policy.param_width)):
+        raise _hip.NabuHipError('spec_augment: params must be int32 [%d, %d]' % (B, policy.param_width))
+    if len_dev.dtype != torch.int32 or len_dev.numel() != B:
+        raise _hip.NabuHipError('spec_augment: the lengths must be int32 [%d]' % B)
+    d = _hip.SpecAugDesc(ctypes.sizeof(_hip.SpecAugDesc), B, T, D, policy.feature_blocks, policy.time_warp,
+                         policy.time_masks, policy.time_mask_width, policy.freq_masks, policy.freq_mask_width,
+                         policy.time_mask_ratio)
+    check(_hip.lib().nabu_spec_augment_f32(ctypes.byref(d), ptr(_f32(x, 'x')), ptr(len_dev), ptr(y), ptr(params), seed,
+                                           offset, stream()), 'nabu_spec_augment_f32')
     return y
 
 
