@@ -414,6 +414,20 @@ int nabu_xent_loss_grad(int B, int L, int C, int ldt, const float *logits,
                         const int32_t *target_len, float grad_scale, float *loss,
                         float *dlogits, nabu_stream_t stream);
 
+/* The same loss against label-smoothed targets (the [trainer] key label_smoothing; the rule of
+ * tf.losses.softmax_cross_entropy(label_smoothing=...)): with C classes the target of a frame with label y is
+ *   q = (1 - smoothing) * onehot(y) + smoothing / C          (the mass is spread over all C classes, y included)
+ * and per frame t inside the mask, lz = logsumexp(x), xm = mean_c x_c, s = grad_scale / target_len[b]:
+ *   loss_t = lz - (1 - smoothing) * x_y - smoothing * xm
+ *   d_c    = s * (softmax_c - (1 - smoothing) * [c = y] - smoothing / C)
+ * Mask, divisor and the zero rows past the mask are nabu_xent_loss_grad's; the row sum rides in the kernel's sum-exp
+ * loop.  0 <= smoothing < 1, NABU_EINVAL otherwise (and for NaN); smoothing = 0 launches nabu_xent_loss_grad's own
+ * instantiation: bit-identical loss and dlogits. */
+int nabu_xent_smooth_loss_grad(int B, int L, int C, int ldt, const float *logits,
+                               const int32_t *targets, const int32_t *logit_len,
+                               const int32_t *target_len, float grad_scale, float smoothing,
+                               float *loss, float *dlogits, nabu_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Speller decoder step kernels — RNNDecoder._decode / Speller.create_cell
  * (nabu/neuralnetworks/models/ed_decoders/rnn_decoder.py:13-82, speller.py:13-69):
@@ -806,6 +820,11 @@ int nabu_layer_norm_bwd(int B, int N, int F, const float *x, const float *gamma,
  *   loss[b] is their fixed-order sum (a second, small launch): deterministic, no atomics.  Any C >= 1, any
  *   alignment (float4 body between scalar head and tail when logits and dlogits share their 16-byte phase).
  *   ws >= nabu_xent_wide_ws_bytes(B, L).
+ * nabu_xent_wide_smooth_loss_grad: nabu_xent_smooth_loss_grad's contract (q = (1 - smoothing) * onehot(y) +
+ *   smoothing / C; loss_t = lz - (1 - smoothing) * x_y - smoothing * mean(x); d_c = s * (softmax_c - q_c)) on the wide
+ *   kernel: the row sum is accumulated in the online max/sum-exp pass from the values it loads, so it is the same two
+ *   passes over the row, the same two launches, the same workspace and the same alignment rule.  smoothing outside
+ *   [0, 1) or NaN: NABU_EINVAL; smoothing = 0: nabu_xent_wide_loss_grad's own instantiation, bit-identical.
  * nabu_log_softmax_prior_f32: AlignmentDecoder's pseudo log-likelihoods: out[b,t,:] = x - logsumexp(x[b,t,:]) -
  *   logprior[:] for t < len[b], 0 elsewhere; x, out [B,T,C], logprior [C].  Same row machinery as above. */
 int nabu_splice_stack_f32(int B, int T, int F, int context, const float *x, const int32_t *len, float *out, int ld,
@@ -822,6 +841,10 @@ size_t nabu_xent_wide_ws_bytes(int B, int L);
 int nabu_xent_wide_loss_grad(int B, int L, int C, int ldt, const float *logits, const int32_t *targets,
                              const int32_t *logit_len, const int32_t *target_len, float grad_scale, float *loss,
                              float *dlogits, void *ws, size_t ws_bytes, nabu_stream_t stream);
+int nabu_xent_wide_smooth_loss_grad(int B, int L, int C, int ldt, const float *logits, const int32_t *targets,
+                                    const int32_t *logit_len, const int32_t *target_len, float grad_scale,
+                                    float smoothing, float *loss, float *dlogits, void *ws, size_t ws_bytes,
+                                    nabu_stream_t stream);
 int nabu_log_softmax_prior_f32(int B, int T, int C, const float *x, const int32_t *len, const float *logprior,
                                float *out, nabu_stream_t stream);
 

@@ -139,6 +139,7 @@ SIGNATURES = {
     'nabu_ctc_ws_bytes': (_sz, [_i, _i, _i]),
     'nabu_ctc_loss_grad': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nabu_xent_loss_grad': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
+    'nabu_xent_smooth_loss_grad': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp]),
     'nabu_lstm_cell_fwd': (_i, [_i, _i, _i] + [_vp] * 10 + [_vp]),
     'nabu_lstm_cell_bwd': (_i, [_i, _i, _i] + [_vp] * 9 + [_vp]),
     'nabu_attn_fwd': (_i, [_vp, _i] + [_vp] * 14 + [_sz, _vp]),
@@ -199,6 +200,7 @@ SIGNATURES = {
     'nabu_rows_relu_ln_bwd': (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'nabu_xent_wide_ws_bytes': (_sz, [_i, _i]),
     'nabu_xent_wide_loss_grad': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _sz, _vp]),
+    'nabu_xent_wide_smooth_loss_grad': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _sz, _vp]),
     'nabu_log_softmax_prior_f32': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'nabu_feat_dim': (_i, [_c.POINTER(FeatDesc)]),
     'nabu_feat_num_frames': (_i, [_c.POINTER(FeatDesc), _ll]),

@@ -469,18 +469,26 @@ extern "C" int nabu_ctc_loss_grad(int B, int T, int C, int Lmax, const float *lo
 //   loss[b] = sum_{t < logit_len[b]} -log softmax(logits[b,t])[targets[b,t]] / target_len[b]
 //   dlogits[b,t,:] = grad_scale * (softmax - onehot) / target_len[b]   (0 for t >= logit_len[b])
 // One workgroup per utterance, one thread per frame, fixed-order block reduction.
+// SMOOTH: the target is q = (1 - smoothing) * onehot + smoothing / C (label smoothing over all C classes):
+//   loss term = logsumexp - (1 - smoothing) * x[y] - smoothing * mean(x), dlogits = scale * (softmax - q);
+// the term is summed as (1 - smoothing) * (lz - x[y]) + smoothing * (lz - mean(x)), two non-negative parts, and the
+// gradient as (softmax - smoothing / C) - (1 - smoothing) * [c = y]: both are exactly 0 where the exact result is
+// (C = 1).  The sum of the row rides in the sum-exp loop.  SMOOTH = false is the expression order the kernel always
+// had.
 namespace nabu {
+template <bool SMOOTH>
 __global__ __launch_bounds__(256) void xent_kernel(int B, int L, int C, int ldt,
                                                    const float *__restrict__ logits,
                                                    const int32_t *__restrict__ targets,
                                                    const int32_t *__restrict__ logit_len,
                                                    const int32_t *__restrict__ target_len,
-                                                   float grad_scale, float *__restrict__ loss,
-                                                   float *__restrict__ dlogits) {
+                                                   float grad_scale, float smoothing,
+                                                   float *__restrict__ loss, float *__restrict__ dlogits) {
   __shared__ float red[256];
   const int b = blockIdx.x;
   const int n = min(max(logit_len[b], 0), L);
   const float inv = 1.0f / (float)target_len[b];
+  const float keep = 1.0f - smoothing, spread = smoothing / (float)C;      // q = keep * onehot + spread
   float acc = 0.f;
   for (int t = threadIdx.x; t < L; t += 256) {
     const float *x = logits + ((size_t)b * L + t) * C;
@@ -491,13 +499,21 @@ __global__ __launch_bounds__(256) void xent_kernel(int B, int L, int C, int ldt,
     }
     float m = x[0];
     for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
-    float z = 0.f;
-    for (int c = 0; c < C; ++c) z += expf(x[c] - m);
+    float z = 0.f, sx = 0.f;
+    for (int c = 0; c < C; ++c) {
+      z += expf(x[c] - m);
+      if (SMOOTH) sx += x[c];
+    }
     const float lz = m + logf(z);
     const int y = targets[(size_t)b * ldt + t];
-    acc += lz - x[y];
     const float s = grad_scale * inv;
-    for (int c = 0; c < C; ++c) d[c] = s * (expf(x[c] - lz) - (c == y ? 1.f : 0.f));
+    if (SMOOTH) {
+      acc += keep * (lz - x[y]) + smoothing * (lz - sx / (float)C);
+      for (int c = 0; c < C; ++c) d[c] = s * ((expf(x[c] - lz) - spread) - (c == y ? keep : 0.f));
+    } else {
+      acc += lz - x[y];
+      for (int c = 0; c < C; ++c) d[c] = s * (expf(x[c] - lz) - (c == y ? 1.f : 0.f));
+    }
   }
   red[threadIdx.x] = acc;
   __syncthreads();
@@ -509,14 +525,35 @@ __global__ __launch_bounds__(256) void xent_kernel(int B, int L, int C, int ldt,
 }
 }  // namespace nabu
 
+static int xent_launch(int B, int L, int C, int ldt, const float *logits, const int32_t *targets,
+                       const int32_t *logit_len, const int32_t *target_len, float grad_scale, float smoothing,
+                       float *loss, float *dlogits, nabu_stream_t stream) {
+  NABU_CHECK_ARG(B > 0 && L > 0 && C > 0 && ldt >= L, "xent: bad dimensions");
+  NABU_CHECK_ARG(logits && targets && logit_len && target_len && loss && dlogits, "xent: null pointer");
+  NABU_CHECK_ARG(smoothing >= 0.f && smoothing < 1.f, "xent: smoothing must be in [0, 1)");      // (false for NaN)
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (smoothing > 0.f)
+    hipLaunchKernelGGL(nabu::xent_kernel<true>, dim3(B), dim3(256), 0, s, B, L, C, ldt, logits, targets, logit_len,
+                       target_len, grad_scale, smoothing, loss, dlogits);
+  else
+    hipLaunchKernelGGL(nabu::xent_kernel<false>, dim3(B), dim3(256), 0, s, B, L, C, ldt, logits, targets, logit_len,
+                       target_len, grad_scale, 0.f, loss, dlogits);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int nabu_xent_loss_grad(int B, int L, int C, int ldt, const float *logits,
                                    const int32_t *targets, const int32_t *logit_len,
                                    const int32_t *target_len, float grad_scale, float *loss,
                                    float *dlogits, nabu_stream_t stream) {
-  NABU_CHECK_ARG(B > 0 && L > 0 && C > 0 && ldt >= L, "xent: bad dimensions");
-  NABU_CHECK_ARG(logits && targets && logit_len && target_len && loss && dlogits, "xent: null pointer");
-  hipLaunchKernelGGL(nabu::xent_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), B, L, C,
-                     ldt, logits, targets, logit_len, target_len, grad_scale, loss, dlogits);
-  NABU_LAUNCH_CHECK();
-  return 0;
+  return xent_launch(B, L, C, ldt, logits, targets, logit_len, target_len, grad_scale, 0.f, loss, dlogits,
+                     stream);
+}
+
+extern "C" int nabu_xent_smooth_loss_grad(int B, int L, int C, int ldt, const float *logits,
+                                          const int32_t *targets, const int32_t *logit_len,
+                                          const int32_t *target_len, float grad_scale, float smoothing,
+                                          float *loss, float *dlogits, nabu_stream_t stream) {
+  return xent_launch(B, L, C, ldt, logits, targets, logit_len, target_len, grad_scale, smoothing, loss,
+                     dlogits, stream);
 }

@@ -218,6 +218,11 @@ __global__ __launch_bounds__(64) void relu_ln_bwd_kernel(int N, int F, const flo
 // One wave per frame row of C logits: pass 1 = online max / sum-exp over the row (head to 16-byte alignment, float4
 // body, scalar tail), pass 2 re-reads the row (still in cache) and writes the output row.
 //   XENT: out = grad_scale / target_len[b] * (softmax - onehot(y)); term[b*L+t] = logsumexp - x[y]
+//   XENT, SMOOTH: the target is q = (1 - smoothing) * onehot(y) + smoothing / C: out = scale * (softmax - q),
+//     term = logsumexp - (1 - smoothing) * x[y] - smoothing * mean(x); the row sum is taken in pass 1, from the values
+//     that pass loads anyway.  The term is summed as (1 - smoothing) * (lz - x[y]) + smoothing * (lz - mean(x)) and
+//     the gradient as (softmax - smoothing / C) - (1 - smoothing) * [c = y], as in xent_kernel.  SMOOTH = false is
+//     the expression order the kernel always had.
 //   PRIOR: out = x - logsumexp - logprior
 // Rows t >= len[b] are written as zeros (term 0).
 struct OnlineLse {
@@ -238,12 +243,13 @@ struct OnlineLse {
   }
 };
 
-template <bool XENT, bool VEC>
+template <bool XENT, bool VEC, bool SMOOTH = false>
 __global__ __launch_bounds__(256) void wide_rows_kernel(int B, int L, int C, int ldt, const float *__restrict__ logits,
                                                         const int32_t *__restrict__ targets,
                                                         const int32_t *__restrict__ len,
                                                         const int32_t *__restrict__ target_len, float grad_scale,
-                                                        const float *__restrict__ logprior, float *__restrict__ term,
+                                                        float smoothing, const float *__restrict__ logprior,
+                                                        float *__restrict__ term,
                                                         float *__restrict__ out) {
   const size_t frame = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -264,27 +270,49 @@ __global__ __launch_bounds__(256) void wide_rows_kernel(int B, int L, int C, int
     return;
   }
   OnlineLse acc{-INFINITY, 0.f};
-  for (int c = lane; c < head; c += 64) acc.add(x[c]);
+  float sx = 0.f;                                  // SMOOTH: this lane's part of the row sum
+  for (int c = lane; c < head; c += 64) {
+    const float v = x[c];
+    acc.add(v);
+    if (SMOOTH) sx += v;
+  }
   const float4 *x4 = reinterpret_cast<const float4 *>(x + head);
-  for (int q = lane; q < body4; q += 64) acc.add4(x4[q]);
-  for (int c = tail0 + lane; c < C; c += 64) acc.add(x[c]);
+  for (int q = lane; q < body4; q += 64) {
+    const float4 v = x4[q];
+    acc.add4(v);
+    if (SMOOTH) sx += (v.x + v.y) + (v.z + v.w);
+  }
+  for (int c = tail0 + lane; c < C; c += 64) {
+    const float v = x[c];
+    acc.add(v);
+    if (SMOOTH) sx += v;
+  }
   const float m = wave_max(acc.m);
   const float s = wave_sum(acc.s == 0.f ? 0.f : acc.s * expf(acc.m - m));
   const float lz = m + logf(s);
   if (XENT) {
     const int y = targets[(size_t)b * ldt + t];
     const float scale = grad_scale / (float)target_len[b];
+    const float keep = 1.0f - smoothing, spread = smoothing / (float)C;      // SMOOTH: q = keep * onehot + spread
+    const float mean = SMOOTH ? wave_sum(sx) / (float)C : 0.f;
     // (a label outside [0, C) is not read: its term is NaN, as the reference's op would fail on it)
-    if (lane == 0) term[frame] = (unsigned)y < (unsigned)C ? lz - x[y] : __int_as_float(0x7fc00000);
-    for (int c = lane; c < head; c += 64) o[c] = scale * (expf(x[c] - lz) - (c == y ? 1.f : 0.f));
+    if (lane == 0) {
+      float v = __int_as_float(0x7fc00000);
+      if ((unsigned)y < (unsigned)C) v = SMOOTH ? keep * (lz - x[y]) + smoothing * (lz - mean) : lz - x[y];
+      term[frame] = v;
+    }
+    auto grad = [&](float v, int c) {
+      return SMOOTH ? scale * ((expf(v - lz) - spread) - (c == y ? keep : 0.f))
+                    : scale * (expf(v - lz) - (c == y ? 1.f : 0.f));
+    };
+    for (int c = lane; c < head; c += 64) o[c] = grad(x[c], c);
     float4 *o4 = reinterpret_cast<float4 *>(o + head);
     for (int q = lane; q < body4; q += 64) {
       const float4 v = x4[q];
       const int c = head + 4 * q;
-      o4[q] = make_float4(scale * (expf(v.x - lz) - (c == y ? 1.f : 0.f)), scale * (expf(v.y - lz) - (c + 1 == y ? 1.f : 0.f)),
-                          scale * (expf(v.z - lz) - (c + 2 == y ? 1.f : 0.f)), scale * (expf(v.w - lz) - (c + 3 == y ? 1.f : 0.f)));
+      o4[q] = make_float4(grad(v.x, c), grad(v.y, c + 1), grad(v.z, c + 2), grad(v.w, c + 3));
     }
-    for (int c = tail0 + lane; c < C; c += 64) o[c] = scale * (expf(x[c] - lz) - (c == y ? 1.f : 0.f));
+    for (int c = tail0 + lane; c < C; c += 64) o[c] = grad(x[c], c);
   } else {
     for (int c = lane; c < head; c += 64) o[c] = x[c] - lz - logprior[c];
     float4 *o4 = reinterpret_cast<float4 *>(o + head);
@@ -410,11 +438,12 @@ extern "C" size_t nabu_xent_wide_ws_bytes(int B, int L) {
   return (size_t)B * L * sizeof(float);
 }
 
-extern "C" int nabu_xent_wide_loss_grad(int B, int L, int C, int ldt, const float *logits, const int32_t *targets,
-                                        const int32_t *logit_len, const int32_t *target_len, float grad_scale,
-                                        float *loss, float *dlogits, void *ws, size_t ws_bytes, nabu_stream_t stream) {
+static int xent_wide_launch(int B, int L, int C, int ldt, const float *logits, const int32_t *targets,
+                            const int32_t *logit_len, const int32_t *target_len, float grad_scale, float smoothing,
+                            float *loss, float *dlogits, void *ws, size_t ws_bytes, nabu_stream_t stream) {
   NABU_CHECK_ARG(B > 0 && L > 0 && C > 0 && ldt >= L, "xent_wide: bad dimensions");
   NABU_CHECK_ARG(logits && targets && logit_len && target_len && loss && dlogits && ws, "xent_wide: null pointer");
+  NABU_CHECK_ARG(smoothing >= 0.f && smoothing < 1.f, "xent_wide: smoothing must be in [0, 1)");      // (false for NaN)
   const size_t need = nabu_xent_wide_ws_bytes(B, L);
   if (ws_bytes < need) return fail(NABU_EWS, "xent_wide: workspace %zu < %zu", ws_bytes, need);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -422,16 +451,31 @@ extern "C" int nabu_xent_wide_loss_grad(int B, int L, int C, int ldt, const floa
   const size_t frames = (size_t)B * L;
   const dim3 grid((unsigned)((frames + 3) / 4));
   // the float4 body needs logits and dlogits equally placed against a 16-byte boundary
-  if (((reinterpret_cast<uintptr_t>(logits) ^ reinterpret_cast<uintptr_t>(dlogits)) & 15) == 0)
-    hipLaunchKernelGGL((wide_rows_kernel<true, true>), grid, dim3(256), 0, s, B, L, C, ldt, logits, targets, logit_len,
-                       target_len, grad_scale, nullptr, term, dlogits);
-  else
-    hipLaunchKernelGGL((wide_rows_kernel<true, false>), grid, dim3(256), 0, s, B, L, C, ldt, logits, targets, logit_len,
-                       target_len, grad_scale, nullptr, term, dlogits);
+  const bool vec = ((reinterpret_cast<uintptr_t>(logits) ^ reinterpret_cast<uintptr_t>(dlogits)) & 15) == 0;
+  auto kern = smoothing > 0.f ? (vec ? wide_rows_kernel<true, true, true> : wide_rows_kernel<true, false, true>)
+                              : (vec ? wide_rows_kernel<true, true> : wide_rows_kernel<true, false>);
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, B, L, C, ldt, logits, targets, logit_len, target_len, grad_scale,
+                     smoothing, nullptr, term, dlogits);
   NABU_LAUNCH_CHECK();
   hipLaunchKernelGGL(wide_loss_sum_kernel, dim3(B), dim3(256), 0, s, L, term, target_len, loss);
   NABU_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int nabu_xent_wide_loss_grad(int B, int L, int C, int ldt, const float *logits, const int32_t *targets,
+                                        const int32_t *logit_len, const int32_t *target_len, float grad_scale,
+                                        float *loss, float *dlogits, void *ws, size_t ws_bytes, nabu_stream_t stream) {
+  return xent_wide_launch(B, L, C, ldt, logits, targets, logit_len, target_len, grad_scale, 0.f, loss, dlogits, ws,
+                          ws_bytes, stream);
+}
+
+extern "C" int nabu_xent_wide_smooth_loss_grad(int B, int L, int C, int ldt, const float *logits,
+                                               const int32_t *targets, const int32_t *logit_len,
+                                               const int32_t *target_len, float grad_scale, float smoothing,
+                                               float *loss, float *dlogits, void *ws, size_t ws_bytes,
+                                               nabu_stream_t stream) {
+  return xent_wide_launch(B, L, C, ldt, logits, targets, logit_len, target_len, grad_scale, smoothing, loss, dlogits,
+                          ws, ws_bytes, stream);
 }
 
 extern "C" int nabu_log_softmax_prior_f32(int B, int T, int C, const float *x, const int32_t *len,
@@ -443,10 +487,10 @@ extern "C" int nabu_log_softmax_prior_f32(int B, int T, int C, const float *x, c
   const dim3 grid((unsigned)(((size_t)B * T + 3) / 4));
   if (((reinterpret_cast<uintptr_t>(x) ^ reinterpret_cast<uintptr_t>(out)) & 15) == 0)
     hipLaunchKernelGGL((wide_rows_kernel<false, true>), grid, dim3(256), 0, s, B, T, C, T, x, nullptr, len, nullptr,
-                       0.f, logprior, nullptr, out);
+                       0.f, 0.f, logprior, nullptr, out);
   else
     hipLaunchKernelGGL((wide_rows_kernel<false, false>), grid, dim3(256), 0, s, B, T, C, T, x, nullptr, len, nullptr,
-                       0.f, logprior, nullptr, out);
+                       0.f, 0.f, logprior, nullptr, out);
   NABU_LAUNCH_CHECK();
   return 0;
 }

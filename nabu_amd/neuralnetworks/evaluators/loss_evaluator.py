@@ -1,6 +1,10 @@
 """LossEvaluator (reference: nabu/neuralnetworks/evaluators/loss_evaluator.py:8-64): the
 validation loss is the utterance-weighted running mean of the training loss function
-evaluated with is_training=False, on the HIP forward path (no tape, no backward)."""
+evaluated with is_training=False, on the HIP forward path (no tape, no backward).
+
+The loss is never label-smoothed: the evaluator's conf does not carry the trainer's `label_smoothing` key and
+factory() is asked without it, so validation losses of runs trained with different smoothing are the same quantity
+and stay comparable."""
 import torch
 
 from nabu_amd.autodiff import SeqLen

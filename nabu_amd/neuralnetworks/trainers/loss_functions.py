@@ -3,6 +3,8 @@
 Each loss is one fused HIP kernel that produces the per-utterance loss AND the
 gradient w.r.t. the logits in the same pass (as tf.nn.ctc_loss does); the
 gradient is handed to the tape."""
+import functools
+
 import torch
 
 from nabu_amd import ops as hip
@@ -17,20 +19,52 @@ pending_status = []
 WIDE_XENT_MIN_CLASSES = 1024
 
 
-def _xent(logits, targets, logit_len_dev, target_len_dev, grad_scale):
-    '''the cross-entropy kernel for the class count of `logits`'''
-    fn = hip.xent_wide_loss_grad if logits.shape[-1] >= WIDE_XENT_MIN_CLASSES else hip.xent_loss_grad
-    return fn(logits, targets, logit_len_dev, target_len_dev, grad_scale)
+def _xent(logits, targets, logit_len_dev, target_len_dev, grad_scale, label_smoothing=0.0):
+    '''the cross-entropy kernel for the class count of `logits`; without smoothing the entry points (and so the
+    launches and their arguments) are the ones a configuration without the label_smoothing key always had'''
+    wide = logits.shape[-1] >= WIDE_XENT_MIN_CLASSES
+    if label_smoothing == 0:
+        fn = hip.xent_wide_loss_grad if wide else hip.xent_loss_grad
+        return fn(logits, targets, logit_len_dev, target_len_dev, grad_scale)
+    fn = hip.xent_wide_smooth_loss_grad if wide else hip.xent_smooth_loss_grad
+    return fn(logits, targets, logit_len_dev, target_len_dev, grad_scale, label_smoothing)
 
 
-def factory(loss_function):
+def label_smoothing_key(conf):
+    """the `label_smoothing` key of the [trainer] section (a build addition like layer_norm and the SpecAugment keys:
+    absent from the defaults file, 0 when absent): the probability mass spread uniformly over the classes of every
+    output, 0 <= value < 1"""
+    text = str(conf.get('label_smoothing', '0')).strip()
+    try:
+        value = float(text)
+    except ValueError:
+        raise ValueError('label_smoothing must be a number, got %r' % text)
+    if not 0.0 <= value < 1.0:                     # (false for nan)
+        raise ValueError('label_smoothing must be in [0, 1), got %r' % text)
+    return value
+
+
+def factory(loss_function, label_smoothing=0.0):
     '''get a callable loss(targets, logits, logit_seq_length, target_seq_length)
-    (reference loss_functions.py:7-28)'''
+    (reference loss_functions.py:7-28).  label_smoothing (not the reference's: the [trainer] key of that name) is
+    bound into the cross-entropy losses: every output is scored against (1 - e) * onehot + e / C over its own C
+    classes.  The LossEvaluator asks for its loss without it, so validation losses are the unsmoothed quantity
+    whatever the training run smooths with.'''
+    label_smoothing = float(label_smoothing)
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError('label_smoothing must be in [0, 1), got %r' % label_smoothing)
     if loss_function == 'average_cross_entropy':
+        if label_smoothing:
+            return functools.partial(average_cross_entropy, label_smoothing=label_smoothing)
         return average_cross_entropy
     elif loss_function == 'CTC':
+        if label_smoothing:
+            raise ValueError('label_smoothing is defined for the cross-entropy losses only (average_cross_entropy, '
+                             'sum_cross_entropy), not for CTC')
         return CTC
     elif loss_function == 'sum_cross_entropy':
+        if label_smoothing:
+            return functools.partial(sum_cross_entropy, label_smoothing=label_smoothing)
         return sum_cross_entropy
     elif loss_function in ('average_sigmoid_cross_entropy', 'marigin'):
         raise Exception('loss function %s is outside the MI355X hot path' % loss_function)
@@ -74,32 +108,32 @@ def CTC(targets, logits, logit_seq_length, target_seq_length):
     return _total(losses)
 
 
-def average_cross_entropy(targets, logits, logit_seq_length, target_seq_length):
+def average_cross_entropy(targets, logits, logit_seq_length, target_seq_length, label_smoothing=0.0):
     '''cross entropy averaged over timesteps (reference loss_functions.py:155-165):
-    mean_b( sum_{t<logit_len} xent / target_len ), summed over the outputs.'''
+    mean_b( sum_{t<logit_len} xent / target_len ), summed over the outputs.  label_smoothing: see factory.'''
     losses = []
     for t in targets:
         lg = logits[t]
         B = lg.shape[0]
         lsl, tsl = SeqLen.wrap(logit_seq_length[t], lg.device), SeqLen.wrap(target_seq_length[t], lg.device)
-        per_utt, dlogits = _xent(lg.contiguous(), _labels(targets[t]), lsl.dev, tsl.dev, 1.0 / B)
+        per_utt, dlogits = _xent(lg.contiguous(), _labels(targets[t]), lsl.dev, tsl.dev, 1.0 / B, label_smoothing)
         loss = hip.sum_(per_utt, 1.0 / B)
         record([lg], [loss], lambda g, d=dlogits: [d])
         losses.append(loss)
     return _total(losses)
 
 
-def sum_cross_entropy(targets, logits, logit_seq_length, target_seq_length):
+def sum_cross_entropy(targets, logits, logit_seq_length, target_seq_length, label_smoothing=0.0):
     '''cross entropy summed over timesteps (reference loss_functions.py:142-153): the mask is the
     TARGET length here and nothing is divided: mean_b( sum_{t<target_len} xent ), summed over the
-    outputs.  Same kernel as average_cross_entropy with a divisor of one.'''
+    outputs.  Same kernel as average_cross_entropy with a divisor of one.  label_smoothing: see factory.'''
     losses = []
     for t in targets:
         lg = logits[t]
         B = lg.shape[0]
         tsl = SeqLen.wrap(target_seq_length[t], lg.device)
         ones = torch.ones_like(tsl.dev)
-        per_utt, dlogits = _xent(lg.contiguous(), _labels(targets[t]), tsl.dev, ones, 1.0 / B)
+        per_utt, dlogits = _xent(lg.contiguous(), _labels(targets[t]), tsl.dev, ones, 1.0 / B, label_smoothing)
         loss = hip.sum_(per_utt, 1.0 / B)
         record([lg], [loss], lambda g, d=dlogits: [d])
         losses.append(loss)

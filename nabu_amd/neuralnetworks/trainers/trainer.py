@@ -100,6 +100,11 @@ class Trainer(object, metaclass=ABCMeta):
             # floor division, trainer.py:929) -- a non-zero key raises there too
             raise Exception('cut_sequence_length is not supported (it requires inputs and targets of equal '
                             'lengths and fails at graph construction in the reference, DESIGN.md section 8)')
+        # label_smoothing (an extension key, absent from the defaults file, 0 when absent): validated here, and
+        # together with the loss it cannot apply to (CTC), so that a bad configuration fails before the first step
+        self.label_smoothing = loss_functions.label_smoothing_key(self.conf)
+        if self.label_smoothing:
+            loss_functions.factory(self.conf['loss'], self.label_smoothing)
         self.model = Model(conf=modelconf, trainlabels=int(self.conf['trainlabels']), constraint=None)
         if bool(getattr(server, 'shared_devices', False)):
             # ranks that share a GPU (more ranks than devices on this node: first-contact runs, tests): the persistent
@@ -124,7 +129,7 @@ class Trainer(object, metaclass=ABCMeta):
         self.learning_rate_fact = 1.0
         self.data = self._data()
         outputs['num_steps'] = self.data.num_batches() * int(self.conf['num_epochs'])
-        self.loss_fn = loss_functions.factory(self.conf['loss'])
+        self.loss_fn = loss_functions.factory(self.conf['loss'], self.label_smoothing)
         self.world = self.server.world_size if self.server is not None else 1
         self.flat = self.flat_grad = self.adam_m = self.adam_v = None
         self.buckets = None

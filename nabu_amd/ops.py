@@ -445,6 +445,19 @@ def xent_loss_grad(logits, targets_dev, logit_len_dev, target_len_dev, grad_scal
     return loss, dlogits
 
 
+def xent_smooth_loss_grad(logits, targets_dev, logit_len_dev, target_len_dev, grad_scale, smoothing):
+    """xent_loss_grad against the smoothed targets (1 - smoothing) * onehot + smoothing / C
+    (nabu_xent_smooth_loss_grad): (loss [B], dlogits [B,L,C])"""
+    B, L, C = logits.shape
+    loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty_like(logits)
+    check(_hip.lib().nabu_xent_smooth_loss_grad(B, L, C, targets_dev.shape[1], ptr(_f32(logits, 'logits')),
+                                                ptr(targets_dev), ptr(logit_len_dev), ptr(target_len_dev),
+                                                grad_scale, smoothing, ptr(loss), ptr(dlogits), stream()),
+          'nabu_xent_smooth_loss_grad')
+    return loss, dlogits
+
+
 class RecurrentProfiler(object):
     """Times the recurrent kernel(s) of every BLSTM call with HIP events recorded by
     the library on the launch stream (nabu_blstm_set_profile_events).  Used by
@@ -742,6 +755,21 @@ def xent_wide_loss_grad(logits, targets_dev, logit_len_dev, target_len_dev, grad
     check(lib.nabu_xent_wide_loss_grad(B, L, C, targets_dev.shape[1], ptr(_f32(logits, 'logits')), ptr(targets_dev),
                                        ptr(logit_len_dev), ptr(target_len_dev), grad_scale, ptr(loss), ptr(dlogits),
                                        ptr(ws), ws_bytes, stream()), 'nabu_xent_wide_loss_grad')
+    return loss, dlogits
+
+
+def xent_wide_smooth_loss_grad(logits, targets_dev, logit_len_dev, target_len_dev, grad_scale, smoothing):
+    """xent_smooth_loss_grad's contract on the wide-class kernel (nabu_xent_wide_smooth_loss_grad)"""
+    B, L, C = logits.shape
+    lib = _hip.lib()
+    loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty_like(logits)
+    ws_bytes = lib.nabu_xent_wide_ws_bytes(B, L)
+    ws = Workspace.get(ws_bytes, logits.device, 'xent_wide')
+    check(lib.nabu_xent_wide_smooth_loss_grad(B, L, C, targets_dev.shape[1], ptr(_f32(logits, 'logits')),
+                                              ptr(targets_dev), ptr(logit_len_dev), ptr(target_len_dev), grad_scale,
+                                              smoothing, ptr(loss), ptr(dlogits), ptr(ws), ws_bytes, stream()),
+          'nabu_xent_wide_smooth_loss_grad')
     return loss, dlogits
 
 
