@@ -676,6 +676,15 @@ int nabu_scatter_rows_f32(int C, int N, int W, const int32_t *ids, const float *
 int nabu_adam_clip_step(size_t n, float *param, const float *grad, float *m,
                         float *v, float lr_t, float b1, float b2, float eps,
                         float clip, float grad_scale, nabu_stream_t stream);
+/* The same update with the parameter read from a separate, read-only source:
+ *   param_out = src - lr_t * m / (sqrt(v) + eps)
+ * (m, v updated in place as above; src and param_out must not overlap).  The optimiser of a weight-noise step
+ * (nabu_weight_noise_f32 below): the gradient was taken at param_out = src + noise, the update starts from the clean
+ * src — no restoring pass and no (w + n) - n arithmetic, which is not exact in float32.  With src a copy of param the
+ * results equal nabu_adam_clip_step's bit for bit. */
+int nabu_adam_clip_step_from(size_t n, float *param_out, const float *src, const float *grad, float *m,
+                             float *v, float lr_t, float b1, float b2, float eps,
+                             float clip, float grad_scale, nabu_stream_t stream);
 /* g = clamp(g, -clip, clip) in place (data-parallel mode clips per replica
  * BEFORE the all-reduce, trainer.py:556-569). */
 int nabu_clip_f32(size_t n, float *g, float clip, nabu_stream_t stream);
@@ -695,6 +704,25 @@ int nabu_dropout_f32(size_t n, const float *x, float *y, float keep_prob,
 int nabu_gaussian_noise_f32(size_t n, const float *x, float *y, float stddev,
                             unsigned long long seed, unsigned long long offset,
                             nabu_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Variational weight noise of one training step (the [trainer] key weight_noise; a build addition: the reference has
+ * no counterpart), ONE launch over the flat parameter buffer in 16-byte groups, n % 4 == 0:
+ *   clean[e] = param[e] for every e < n;
+ *   param[4 i + j] = fmaf(stddev, z[4 i + j], param[4 i + j]) for every group i inside a range of the table,
+ * z = the standard normal values nabu_gaussian_noise_f32 draws for an array of n elements at (seed, offset): Philox
+ * counter (i_lo, i_hi, offset_lo, offset_hi), key seed, Box-Muller — independent of the table.  A group outside every
+ * range is neither stored to param nor drawn for.
+ * ranges: nranges pairs [first_group, end_group) of int32 in DEVICE memory (8-byte aligned), sorted, disjoint (ranges
+ *   may touch), inside [0, n / 4); ranges_host: the same table in host memory, which is what the call validates on
+ *   every call (the host never reads the device copy).  nranges = 0 is legal (a copy only; both pointers may be NULL).
+ * NABU_EINVAL: n % 4 != 0 or n >= 2^33, a null, unaligned (16 bytes) or overlapping param / clean, stddev negative or
+ *   not finite, nranges outside 0..NABU_WEIGHT_NOISE_MAX_RANGES (the table is searched from LDS), a table that is
+ *   unsorted, overlapping, empty in an entry or past the buffer. */
+#define NABU_WEIGHT_NOISE_MAX_RANGES 1024
+int nabu_weight_noise_f32(size_t n, float *param, float *clean, const int32_t *ranges,
+                          const int32_t *ranges_host, int nranges, float stddev,
+                          unsigned long long seed, unsigned long long offset, nabu_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * SpecAugment of the encoder's input features (a build addition: the reference has no counterpart): a linear time

@@ -167,9 +167,11 @@ SIGNATURES = {
     'nabu_swap01_f32': (_i, [_i, _i, _i, _vp, _vp, _vp]),
     'nabu_scatter_rows_f32': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     'nabu_adam_clip_step': (_i, [_sz, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp]),
+    'nabu_adam_clip_step_from': (_i, [_sz, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp]),
     'nabu_clip_f32': (_i, [_sz, _vp, _f, _vp]),
     'nabu_dropout_f32': (_i, [_sz, _vp, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _vp]),
     'nabu_gaussian_noise_f32': (_i, [_sz, _vp, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _vp]),
+    'nabu_weight_noise_f32': (_i, [_sz, _vp, _vp, _vp, _vp, _i, _f, _c.c_ulonglong, _c.c_ulonglong, _vp]),
     'nabu_spec_augment_f32': (_i, [_c.POINTER(SpecAugDesc), _vp, _vp, _vp, _vp, _c.c_ulonglong, _c.c_ulonglong, _vp]),
     'nabu_sum_f32': (_i, [_sz, _vp, _f, _vp, _vp]),
     'nabu_axpy_f32': (_i, [_sz, _f, _vp, _vp, _vp]),

@@ -117,5 +117,18 @@ __device__ __forceinline__ float4 dropout_scale4(unsigned long long group, float
   return make_float4(u01(r.x) < keep ? inv : 0.f, u01(r.y) < keep ? inv : 0.f, u01(r.z) < keep ? inv : 0.f,
                      u01(r.w) < keep ? inv : 0.f);
 }
+// the four standard normal values of the 4-element group `group` of the array the stream is defined on: Box-Muller on
+// (0,1] uniforms, element 4 group + j takes lane j (gaussian_noise_kernel and weight_noise_kernel of elementwise.hip,
+// oracle/philox.py: gaussian)
+__device__ __forceinline__ float4 gaussian4(unsigned long long group, unsigned long long seed, unsigned long long offset) {
+  const uint4 r = philox4x32_10(make_uint4((unsigned)group, (unsigned)(group >> 32), (unsigned)offset, (unsigned)(offset >> 32)),
+                                make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
+  const float u1 = 1.0f - u01(r.x), u2 = u01(r.y), u3 = 1.0f - u01(r.z), u4 = u01(r.w);
+  const float ra = sqrtf(-2.0f * logf(u1)), rb = sqrtf(-2.0f * logf(u3));
+  float sa, ca, sb, cb;
+  sincosf(6.283185307179586f * u2, &sa, &ca);
+  sincosf(6.283185307179586f * u4, &sb, &cb);
+  return make_float4(ra * ca, ra * sa, rb * cb, rb * sb);
+}
 
 }  // namespace nabu

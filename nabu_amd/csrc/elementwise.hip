@@ -1,5 +1,7 @@
 // elementwise.hip — HBM-bound helpers: fused clip+Adam, bias-gradient column
 // sums, time padding for odd-length pyramid stacks.
+#include <float.h>
+
 #include "common.h"
 
 namespace nabu {
@@ -13,7 +15,11 @@ __device__ __forceinline__ float clip_value(float x, float clip) {
 // ---------------------------------------------------------------------------
 // fused clip + TF-style Adam: 4 streams read (param, grad, m, v), 3 written.
 // 16-byte accesses, grid-stride, 7*4 = 28 algorithmic bytes per parameter.
+// FROM: the parameter is read from `src` instead of p (nabu_adam_clip_step_from: the update of a step whose forward and
+// backward passes ran at p = src + noise); the one difference, every other expression is the plain kernel's.
+template <bool FROM>
 __global__ __launch_bounds__(256) void adam_clip_kernel(size_t n, float *__restrict__ p,
+                                                        const float *__restrict__ src,
                                                         const float *__restrict__ g,
                                                         float *__restrict__ m,
                                                         float *__restrict__ v, float lr_t,
@@ -23,7 +29,7 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(size_t n, float *__restr
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (size_t i = tid; i < n4; i += stride) {
-    float4 pp = reinterpret_cast<float4 *>(p)[i];
+    float4 pp = FROM ? reinterpret_cast<const float4 *>(src)[i] : reinterpret_cast<float4 *>(p)[i];
     float4 gg = reinterpret_cast<const float4 *>(g)[i];
     float4 mm = reinterpret_cast<float4 *>(m)[i];
     float4 vv = reinterpret_cast<float4 *>(v)[i];
@@ -45,7 +51,9 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(size_t n, float *__restr
     float vv = b2 * v[i] + (1.f - b2) * x * x;
     m[i] = mm;
     v[i] = vv;
-    p[i] -= lr_t * mm / (sqrtf(vv) + eps);
+    float pp = FROM ? src[i] : p[i];
+    pp -= lr_t * mm / (sqrtf(vv) + eps);
+    p[i] = pp;
   }
 }
 
@@ -215,21 +223,45 @@ __global__ __launch_bounds__(256) void gaussian_noise_kernel(size_t n, const flo
                                                              unsigned long long offset) {
   const size_t n4 = (n + 3) / 4;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    const uint4 r = philox4x32_10(make_uint4((unsigned)i, (unsigned)(i >> 32), (unsigned)offset,
-                                             (unsigned)(offset >> 32)),
-                                  make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
-    // Box-Muller on (0,1] uniforms
-    const float u1 = 1.0f - u01(r.x), u2 = u01(r.y), u3 = 1.0f - u01(r.z), u4 = u01(r.w);
-    const float ra = sqrtf(-2.0f * logf(u1)), rb = sqrtf(-2.0f * logf(u3));
-    float sa, ca, sb, cb;
-    sincosf(6.283185307179586f * u2, &sa, &ca);
-    sincosf(6.283185307179586f * u4, &sb, &cb);
-    const float z[4] = {ra * ca, ra * sa, rb * cb, rb * sb};
+    const float4 z4 = gaussian4(i, seed, offset);      // (common.h)
+    const float z[4] = {z4.x, z4.y, z4.z, z4.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const size_t e = 4 * i + j;
       if (e < n) y[e] = x[e] + stddev * z[j];
     }
+  }
+}
+
+// Variational weight noise of one training step in ONE launch over the flat parameter buffer (n4 groups of 16 bytes):
+// every group is copied to `clean`; a group inside one of the `nranges` sorted, disjoint [first, end) group ranges of
+// `ranges` (the matrices: trainer.py, weight_noise_ranges) also becomes p = fmaf(stddev, z, p) in place, with z the
+// gaussian4 values of that group of an n-element array, whatever the table.  A group outside every range is not stored to
+// p and runs no Philox.  The table is searched from LDS (the last range that starts at or before the group).
+constexpr int WN_MAX_RANGES = NABU_WEIGHT_NOISE_MAX_RANGES;
+__global__ __launch_bounds__(256) void weight_noise_kernel(size_t n4, float *__restrict__ p, float *__restrict__ clean,
+                                                           const int2 *__restrict__ ranges, int nranges, float stddev,
+                                                           unsigned long long seed, unsigned long long offset) {
+  __shared__ int2 tab[WN_MAX_RANGES];
+  for (int k = threadIdx.x; k < nranges; k += 256) tab[k] = ranges[k];
+  __syncthreads();
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    float4 v = reinterpret_cast<const float4 *>(p)[i];
+    reinterpret_cast<float4 *>(clean)[i] = v;
+    const int g = (int)i;                      // (n4 <= INT32_MAX: checked by the host)
+    int lo = 0, hi = nranges;                  // lo = number of ranges that start at or before g
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (tab[mid].x <= g) lo = mid + 1;
+      else hi = mid;
+    }
+    if (lo == 0 || g >= tab[lo - 1].y) continue;
+    const float4 z = gaussian4(i, seed, offset);
+    v.x = fmaf(stddev, z.x, v.x);
+    v.y = fmaf(stddev, z.y, v.y);
+    v.z = fmaf(stddev, z.z, v.z);
+    v.w = fmaf(stddev, z.w, v.w);
+    reinterpret_cast<float4 *>(p)[i] = v;
   }
 }
 
@@ -395,9 +427,52 @@ extern "C" int nabu_adam_clip_step(size_t n, float *param, const float *grad, fl
   NABU_CHECK_ARG(param && grad && m && v, "adam: null pointer");
   NABU_CHECK_ARG(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)m | (uintptr_t)v) % 16 == 0,
                  "adam: buffers must be 16-byte aligned");
-  hipLaunchKernelGGL(adam_clip_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), n, param, grad, m, v, lr_t, b1, b2, eps,
+  hipLaunchKernelGGL(adam_clip_kernel<false>, dim3(grid_for(n / 4 + 1)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), n, param, (const float *)nullptr, grad, m, v, lr_t, b1, b2, eps,
                      clip, grad_scale);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int nabu_adam_clip_step_from(size_t n, float *param_out, const float *src, const float *grad, float *m,
+                                        float *v, float lr_t, float b1, float b2, float eps, float clip,
+                                        float grad_scale, nabu_stream_t stream) {
+  if (n == 0) return 0;
+  NABU_CHECK_ARG(param_out && src && grad && m && v, "adam_from: null pointer");
+  NABU_CHECK_ARG(((uintptr_t)param_out | (uintptr_t)src | (uintptr_t)grad | (uintptr_t)m | (uintptr_t)v) % 16 == 0,
+                 "adam_from: buffers must be 16-byte aligned");
+  NABU_CHECK_ARG(src + n <= param_out || param_out + n <= src,
+                 "adam_from: src and param_out overlap (the in-place update is nabu_adam_clip_step)");
+  hipLaunchKernelGGL(adam_clip_kernel<true>, dim3(grid_for(n / 4 + 1)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), n, param_out, src, grad, m, v, lr_t, b1, b2, eps, clip,
+                     grad_scale);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int nabu_weight_noise_f32(size_t n, float *param, float *clean, const int32_t *ranges,
+                                     const int32_t *ranges_host, int nranges, float stddev, unsigned long long seed,
+                                     unsigned long long offset, nabu_stream_t stream) {
+  if (n == 0) return 0;
+  NABU_CHECK_ARG(param && clean, "weight_noise: null pointer");
+  NABU_CHECK_ARG(n % 4 == 0 && n / 4 <= (size_t)INT32_MAX, "weight_noise: n = %zu must be a multiple of 4 below 2^33", n);
+  NABU_CHECK_ARG(((uintptr_t)param | (uintptr_t)clean) % 16 == 0, "weight_noise: buffers must be 16-byte aligned");
+  NABU_CHECK_ARG(param + n <= clean || clean + n <= param, "weight_noise: param and clean overlap");
+  NABU_CHECK_ARG(stddev >= 0.f && stddev <= FLT_MAX, "weight_noise: stddev must be finite and >= 0");      // (false for NaN)
+  NABU_CHECK_ARG(nranges >= 0 && nranges <= WN_MAX_RANGES, "weight_noise: nranges = %d is outside 0..%d", nranges,
+                 WN_MAX_RANGES);
+  NABU_CHECK_ARG(nranges == 0 || (ranges && ranges_host && (uintptr_t)ranges % 8 == 0),
+                 "weight_noise: the range table needs its device copy (8-byte aligned) and its host copy");
+  long long prev_end = 0;
+  for (int k = 0; k < nranges; ++k) {
+    const long long first = ranges_host[2 * k], end = ranges_host[2 * k + 1];
+    NABU_CHECK_ARG(first >= prev_end && first < end && end <= (long long)(n / 4),
+                   "weight_noise: range %d = [%lld, %lld) is empty, unsorted, overlaps its predecessor or ends past %zu groups",
+                   k, first, end, n / 4);
+    prev_end = end;
+  }
+  hipLaunchKernelGGL(weight_noise_kernel, dim3(grid_for(n / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), n / 4,
+                     param, clean, reinterpret_cast<const int2 *>(ranges), nranges, stddev, seed, offset);
   NABU_LAUNCH_CHECK();
   return 0;
 }

@@ -38,6 +38,49 @@ CLIP = 1.0                                         # tf.clip_by_value(grad, -1.,
 CHECKPOINT_SECS = 600                              # MonitoredTrainingSession default
 
 
+def weight_noise_keys(conf):
+    """the `weight_noise` and `weight_noise_start_step` keys of the [trainer] section (build additions like
+    label_smoothing: absent from defaults/standardtrainer.cfg, 0 when absent) -> (stddev, start_step).  A step is noisy
+    when stddev > 0 and global_step >= start_step."""
+    text = str(conf.get('weight_noise', '0')).strip()
+    try:
+        stddev = float(text)
+    except ValueError:
+        raise ValueError('weight_noise must be a number, got %r' % text)
+    if not (0.0 <= stddev < float('inf')):                      # (false for NaN)
+        raise ValueError('weight_noise must be a finite standard deviation >= 0, got %r' % text)
+    text = str(conf.get('weight_noise_start_step', '0')).strip()
+    try:
+        start = int(text)
+    except ValueError:
+        raise ValueError('weight_noise_start_step must be an integer, got %r' % text)
+    if start < 0:
+        raise ValueError('weight_noise_start_step must be >= 0, got %r' % text)
+    return stddev, start
+
+
+def weight_noise_ranges(variables):
+    """the range table of hip.weight_noise for variables laid out by VariableStore.flatten (each has .shape, .numel()
+    and its .offset, a multiple of 4): sorted, disjoint [first_group, end_group) pairs in units of 4 elements over the
+    variables with two or more dimensions — vectors (biases, layer-norm gains and offsets, attention_v) stay clean.
+    Ranges that meet are joined.  A group holds one variable or padding: the last group of a matrix whose size is no
+    multiple of 4 also holds padding and stays clean with it.  Host arithmetic only."""
+    ranges = []
+    for v in sorted(variables, key=lambda v: v.offset):
+        if len(v.shape) < 2:
+            continue
+        if v.offset % 4:
+            raise ValueError('variable %s starts at element %d of the flat buffer, not on a 16-byte group' % (v.name, v.offset))
+        first, end = v.offset // 4, (v.offset + v.numel()) // 4
+        if end <= first:
+            continue
+        if ranges and ranges[-1][1] == first:
+            ranges[-1][1] = end
+        else:
+            ranges.append([first, end])
+    return [tuple(r) for r in ranges]
+
+
 class ValidationSaveHook(object):
     '''saves and restores the validated model (reference components/hooks.py:54-86: a
     tf.train.Saver over ALL global variables, i.e. weights, Adam slots, global step,
@@ -105,6 +148,11 @@ class Trainer(object, metaclass=ABCMeta):
         self.label_smoothing = loss_functions.label_smoothing_key(self.conf)
         if self.label_smoothing:
             loss_functions.factory(self.conf['loss'], self.label_smoothing)
+        # weight_noise / weight_noise_start_step (extension keys as well): validated here for the same reason
+        self.weight_noise, self.weight_noise_start_step = weight_noise_keys(self.conf)
+        self.flat_clean = self.noise_table = None
+        self.last_weight_noise = None      # the (seed, offset) of the latest noisy step
+        self._noisy = False                # True from a step's noise launch until its optimiser has run
         self.model = Model(conf=modelconf, trainlabels=int(self.conf['trainlabels']), constraint=None)
         if bool(getattr(server, 'shared_devices', False)):
             # ranks that share a GPU (more ranks than devices on this node: first-contact runs, tests): the persistent
@@ -223,19 +271,48 @@ class Trainer(object, metaclass=ABCMeta):
         '''one training update on a device batch; returns the loss as a 1-element
         device tensor (no host synchronisation)'''
         self._create_graph()
-        with Tape() as tape:
-            logits, logit_seq_length = self.model(
-                inputs=batch['inputs'], input_seq_length=batch['input_seq_length'],
-                targets=batch['targets'], target_seq_length=batch['target_seq_length'],
-                is_training=True)
-            loss = self.loss_fn(batch['targets'], logits, logit_seq_length, batch['target_seq_length'])
-            extra = self.aditional_loss()
-            if extra is not None:
-                loss = hip.axpy_(loss, extra)
-        if self.flat is None:
-            self._init_optimizer()
-        self._backward_and_update(tape, loss)
+        if self.weight_noise > 0 and self.global_step >= self.weight_noise_start_step:
+            self._add_weight_noise(batch)
+        try:
+            with Tape() as tape:
+                logits, logit_seq_length = self.model(
+                    inputs=batch['inputs'], input_seq_length=batch['input_seq_length'],
+                    targets=batch['targets'], target_seq_length=batch['target_seq_length'],
+                    is_training=True)
+                loss = self.loss_fn(batch['targets'], logits, logit_seq_length, batch['target_seq_length'])
+                extra = self.aditional_loss()
+                if extra is not None:
+                    loss = hip.axpy_(loss, extra)
+            if self.flat is None:
+                self._init_optimizer()
+            self._backward_and_update(tape, loss)
+        finally:
+            if self._noisy:            # raised between the noise launch and the optimiser: back to the clean parameters
+                self._noisy = False
+                self.flat.copy_(self.flat_clean)
         return loss
+
+    def _add_weight_noise(self, batch):
+        '''a noisy step (the keys weight_noise / weight_noise_start_step): ONE offset of the global stream, taken before
+        the model's own draws, then ONE launch that saves the flat parameters to flat_clean and adds
+        weight_noise * N(0, 1) to every matrix in place.  The forward and backward passes of this step run at the noisy
+        values; _update computes the new parameters from flat_clean, so between steps flat is always clean.'''
+        from nabu_amd.neuralnetworks.components import ops as nops
+        seed, offset = nops.global_rng().next()
+        if self.flat is None:
+            if not self.model.store.order:
+                # the noise needs the variables before the training forward pass that would create them: created as
+                # _ensure_variables does (a forward pass that is not training, here on the step's own batch), and
+                # the stream stays where it was
+                kept = nops.global_rng().offset
+                with torch.no_grad():
+                    self.model(batch['inputs'], batch['input_seq_length'], batch['targets'],
+                               batch['target_seq_length'], False)
+                nops.global_rng().offset = kept
+            self._init_optimizer()
+        hip.weight_noise(self.flat, self.flat_clean, self.noise_table, self.weight_noise, seed, offset)
+        self._noisy = True
+        self.last_weight_noise = (seed, offset)
 
     def _backward_and_update(self, tape, loss):
         if self.buckets is not None:
@@ -261,6 +338,12 @@ class Trainer(object, metaclass=ABCMeta):
         self.buckets = None
         if self.world > 1 and self.conf.get('allreduce_buckets', 'False') == 'True':
             self.buckets = self._make_buckets()
+        if self.weight_noise > 0:          # (a configuration without the key allocates neither)
+            self.flat_clean = torch.empty_like(self.flat)
+            self.noise_table = hip.WeightNoiseTable(weight_noise_ranges(store.trainable_variables()), self.flat.device)
+            if self.noise_table.n > hip.WEIGHT_NOISE_MAX_RANGES:
+                raise ValueError('weight_noise: the matrices form %d separate ranges of the flat parameter buffer, the '
+                                 'kernel takes %d' % (self.noise_table.n, hip.WEIGHT_NOISE_MAX_RANGES))
 
     # ----------------------------------------------------- bucketed gradient exchange
     @staticmethod
@@ -342,20 +425,28 @@ class Trainer(object, metaclass=ABCMeta):
             self._join_comm()
             if ev is not None:
                 ev[1].record()
-            hip.adam_clip_step(self.flat, self.flat_grad, self.adam_m, self.adam_v, lr_t,
-                               ADAM_B1, ADAM_B2, ADAM_EPS, CLIP, 1.0 / self.world)
+            self._adam(lr_t, 1.0 / self.world)
         elif self.world > 1:
             hip.clip_(self.flat_grad, CLIP)                      # clip per replica ...
             ev = self._allreduce_events()
             self.server.all_reduce_sum_(self.flat_grad)          # ... sum over xGMI ...
             if ev is not None:
                 ev[1].record()
-            hip.adam_clip_step(self.flat, self.flat_grad, self.adam_m, self.adam_v, lr_t,
-                               ADAM_B1, ADAM_B2, ADAM_EPS, CLIP, 1.0 / self.world)   # ... mean, Adam
+            self._adam(lr_t, 1.0 / self.world)                   # ... mean, Adam
+        else:
+            self._adam(lr_t, 1.0)
+        self.last_lr = lr
+
+    def _adam(self, lr_t, grad_scale):
+        '''the fused clip + Adam launch; after a noisy step (_add_weight_noise) the parameter is read from the clean
+        copy, so the noise leaves with the update and nothing has to be subtracted again'''
+        if self._noisy:
+            hip.adam_clip_step_from(self.flat, self.flat_clean, self.flat_grad, self.adam_m, self.adam_v, lr_t,
+                                    ADAM_B1, ADAM_B2, ADAM_EPS, CLIP, grad_scale)
+            self._noisy = False
         else:
             hip.adam_clip_step(self.flat, self.flat_grad, self.adam_m, self.adam_v, lr_t,
-                               ADAM_B1, ADAM_B2, ADAM_EPS, CLIP, 1.0)
-        self.last_lr = lr
+                               ADAM_B1, ADAM_B2, ADAM_EPS, CLIP, grad_scale)
 
     def _allreduce_events(self):
         '''bench.py sets ``time_allreduce``: a pair of events on the launch stream around the

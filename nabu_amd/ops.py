@@ -4,6 +4,7 @@ handles; all arithmetic happens inside libnabu_hip.so."""
 import collections
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _hip
@@ -349,6 +350,16 @@ def adam_clip_step(param, grad, m, v, lr_t, b1=0.9, b2=0.999, eps=1e-8, clip=1.0
                                          eps, clip, grad_scale, stream()), 'nabu_adam_clip_step')
 
 
+def adam_clip_step_from(param_out, src, grad, m, v, lr_t, b1=0.9, b2=0.999, eps=1e-8, clip=1.0, grad_scale=1.0):
+    """adam_clip_step with the parameter read from `src` (read-only, no overlap with param_out):
+    param_out = src - lr_t * m / (sqrt(v) + eps) — the update of a weight-noise step from the clean parameters"""
+    if src.numel() != param_out.numel():
+        raise _hip.NabuHipError('adam_clip_step_from: src holds %d elements, param_out %d' % (src.numel(), param_out.numel()))
+    check(_hip.lib().nabu_adam_clip_step_from(param_out.numel(), ptr(_f32(param_out, 'param_out')), ptr(_f32(src, 'src')),
+                                              ptr(grad), ptr(m), ptr(v), lr_t, b1, b2, eps, clip, grad_scale, stream()),
+          'nabu_adam_clip_step_from')
+
+
 def clip_(g, clip=1.0):
     check(_hip.lib().nabu_clip_f32(g.numel(), ptr(g), clip, stream()), 'nabu_clip_f32')
     return g
@@ -375,6 +386,30 @@ def gaussian_noise(x, stddev, seed, offset):
     check(_hip.lib().nabu_gaussian_noise_f32(x.numel(), ptr(x), ptr(y), stddev, seed, offset, stream()),
           'nabu_gaussian_noise_f32')
     return y
+
+
+WEIGHT_NOISE_MAX_RANGES = 1024      # NABU_WEIGHT_NOISE_MAX_RANGES of include/nabu_hip.h
+
+
+class WeightNoiseTable(object):
+    """the range table of nabu_weight_noise_f32: [first_group, end_group) pairs in units of 4 elements, kept as the int32
+    host array the call validates and as its device copy the kernel reads (uploaded once, here)"""
+
+    def __init__(self, ranges, device):
+        self.host = np.ascontiguousarray(np.asarray(list(ranges), np.int64).reshape(-1, 2).astype(np.int32))
+        self.n = int(self.host.shape[0])
+        self.dev = torch.from_numpy(self.host).to(device) if self.n else None
+
+
+def weight_noise(param, clean, table, stddev, seed, offset):
+    """in place: clean = param, then param += stddev * N(0, 1) inside the ranges of `table` (a WeightNoiseTable), with the
+    values gaussian_noise draws for an array of param.numel() elements at (seed, offset) (nabu_weight_noise_f32)"""
+    if clean.numel() != param.numel():
+        raise _hip.NabuHipError('weight_noise: clean holds %d elements, param %d' % (clean.numel(), param.numel()))
+    check(_hip.lib().nabu_weight_noise_f32(param.numel(), ptr(_f32(param, 'param')), ptr(_f32(clean, 'clean')),
+                                           ptr(table.dev), table.host.ctypes.data if table.n else None, table.n,
+                                           stddev, seed, offset, stream()), 'nabu_weight_noise_f32')
+    return param
 
 
 SPECAUG_MAX_MASKS = _hip.SPECAUG_MAX_MASKS       # masks of one kind per utterance (include/nabu_hip.h)
