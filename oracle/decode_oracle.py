@@ -79,72 +79,131 @@ class _Entry(object):
         return labels[::-1]
 
 
-def ctc_beam_search(logits, beam_width=100, merge_repeated=True, blank=None):
+def _alive(v):
+    """a finite-or-+inf log-probability; -inf and NaN are dead (the kernel's key_image maps both to 0)"""
+    return v > LOG_ZERO
+
+
+def ctc_beam_search(logits, beam_width=100, merge_repeated=True, blank=None, details=False, dtype=np.float64):
     """One utterance: logits [T,C] (T = its logit_seq_length).  Returns the label list of the
     most probable leaf.  Ties (equal float totals) are resolved in favour of the earlier
-    insertion, as a bounded top-N container with a strict `>` admission test does."""
+    insertion, as a bounded top-N container with a strict `>` admission test does.
+
+    Dead candidates.  A candidate whose total is -inf (or NaN: a frame of -inf logits has no
+    log-softmax) never enters or stays in the beam, and a leaf's parent contributes exactly when it
+    was in the beam at the previous frame.  When a frame leaves no live candidate the search ends
+    there with the empty labelling and total -inf.  This corner is the DEFINITION OF THE KERNEL
+    (decode.hip: key_image, `nl == 0`), restated here so that the two can be compared; it is not a
+    recalled TensorFlow behaviour (TF keeps dead entries in its top-N container and tests
+    Active() on a parent that the same frame may already have updated).  With finite logits
+    nothing is ever dead and the two descriptions coincide.
+
+    details=True returns a dict instead of the labels:
+      labels         the merged (per merge_repeated) labelling of the best leaf
+      total          its newp.total (log-probability of the prefix), a float of `dtype`
+      beam           the final beam, best first: [(labels WITHOUT merging, total)]
+      select_gap     over all frames at which a live candidate was dropped: the smallest difference
+                     between the last kept and the best dropped total (inf if nothing ever was).
+                     A frame whose last kept and best dropped totals are EQUAL counts in select_ties
+                     instead, and contributes the distances from that tied value to the nearest
+                     different total above it among the kept and below it among the dropped.
+      select_ties    the number of such frames
+      order_gap      the smallest non-zero difference between neighbours of a kept beam (their order
+                     decides later ties only)
+      top_gap        best minus second-best total of the final beam (inf with fewer than two)
+      max_abs_total  the largest |total| of a live candidate at any frame
+    `dtype` is the type the recurrence runs in: float32 restates the kernel's arithmetic on the
+    host, for measuring what float32 costs against float64 on the same inputs."""
     T, C = logits.shape
     blank = C - 1 if blank is None else blank
-    x = np.asarray(logits, np.float64)
-    x = x - x.max(1, keepdims=True)
-    x = x - np.log(np.exp(x).sum(1, keepdims=True))        # per-frame constants do not change ranks
+    x = np.asarray(logits, dtype)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        x = x - x.max(1, keepdims=True)
+        x = x - np.log(np.exp(x).sum(1, keepdims=True))    # per-frame constants do not change ranks
     root = _Entry(None, -1)
-    root.newp.total = root.newp.blank = 0.0
+    root.newp.total = root.newp.blank = dtype(0.0)
     leaves = [root]
+    select_gap = order_gap = np.inf
+    select_ties, max_abs = 0, 0.0
     for t in range(T):
         inp = x[t]
         branches = sorted(leaves, key=lambda e: -e.newp.total)          # stable: earlier first
         for b in branches:
             b.oldp.assign(b.newp)
         cands = []                                                      # (entry, total) in insertion order
-        for b in branches:
-            if b.parent is not None:
-                if b.parent.active():
-                    prev = b.parent.oldp.blank if b.label == b.parent.label else b.parent.oldp.total
-                    b.newp.label = _lse(b.newp.label, prev)
-                b.newp.label += inp[b.label]
-            b.newp.blank = b.oldp.total + inp[blank]
-            b.newp.total = _lse(b.newp.blank, b.newp.label)
-            cands.append(b)
-        fresh = []
-        for b in branches:
-            if b.oldp.total == LOG_ZERO:
-                continue
-            if b.children is None:
-                b.children = {}
-            for c in range(C):
-                if c == blank:
-                    continue
-                ch = b.children.get(c)
-                if ch is not None and ch.active():
-                    continue                                            # already a leaf, updated above
-                if ch is None:
-                    ch = b.children[c] = _Entry(b, c)
-                prev = b.oldp.blank if c == b.label else b.oldp.total
-                ch.newp.blank = LOG_ZERO
-                ch.newp.label = inp[c] + prev
-                ch.newp.total = ch.newp.label
-                if ch.newp.total > LOG_ZERO:
-                    cands.append(ch)
-                    fresh.append(ch)
-                else:
-                    ch.newp.reset()
+        with np.errstate(invalid='ignore'):
+            for b in branches:
+                if b.parent is not None:
+                    if b.parent.oldp.total != LOG_ZERO:                 # the parent was in the beam at t-1
+                        prev = b.parent.oldp.blank if b.label == b.parent.label else b.parent.oldp.total
+                        b.newp.label = _lse(b.newp.label, prev)
+                    b.newp.label += inp[b.label]
+                b.newp.blank = b.oldp.total + inp[blank]
+                b.newp.total = _lse(b.newp.blank, b.newp.label)
+                cands.append(b)
+            for b in branches:
+                if b.children is None:
+                    b.children = {}
+                for c in range(C):
+                    if c == blank:
+                        continue
+                    ch = b.children.get(c)
+                    if ch is not None and ch.active():
+                        continue                                        # already a leaf, updated above
+                    if ch is None:
+                        ch = b.children[c] = _Entry(b, c)
+                    prev = b.oldp.blank if c == b.label else b.oldp.total
+                    ch.newp.blank = LOG_ZERO
+                    ch.newp.label = inp[c] + prev
+                    ch.newp.total = ch.newp.label
+                    if _alive(ch.newp.total):
+                        cands.append(ch)
+                    else:
+                        ch.newp.reset()
         for i, e in enumerate(cands):
             e.order = i
-        keep = heapq.nsmallest(beam_width, cands, key=lambda e: (-e.newp.total, e.order))
+        live = [e for e in cands if _alive(e.newp.total)]
+        keep = heapq.nsmallest(beam_width, live, key=lambda e: (-e.newp.total, e.order))
         kept = set(id(e) for e in keep)
+        if details and live:
+            max_abs = max(max_abs, max(abs(float(e.newp.total)) for e in live))
+            tot = [float(e.newp.total) for e in keep]
+            for d in np.diff(tot):
+                if d != 0:
+                    order_gap = min(order_gap, -d)
+            drop = [float(e.newp.total) for e in live if id(e) not in kept]
+            if drop:
+                thr = tot[-1]
+                if max(drop) == thr:
+                    select_ties += 1
+                    near = [v - thr for v in tot if v != thr] + [thr - v for v in drop if v != thr]
+                else:
+                    near = [thr - max(drop)]
+                if near:
+                    select_gap = min(select_gap, min(near))
         for e in cands:
             if id(e) not in kept:
                 e.newp.reset()                                          # left the beam: inactive
                 e.oldp.reset()
         leaves = keep
-    best = min(leaves, key=lambda e: (-e.newp.total,))
-    return best.label_seq(merge_repeated)
+        if not leaves:
+            break
+    best = min(leaves, key=lambda e: (-e.newp.total,)) if leaves else None
+    labels = best.label_seq(merge_repeated) if leaves else []
+    if not details:
+        return labels
+    final = sorted(leaves, key=lambda e: -e.newp.total)
+    return dict(labels=labels, total=best.newp.total if leaves else dtype(LOG_ZERO),
+                beam=[(e.label_seq(False), e.newp.total) for e in final],
+                select_gap=float(select_gap), select_ties=select_ties, order_gap=float(order_gap),
+                top_gap=float(final[0].newp.total - final[1].newp.total) if len(final) > 1 else np.inf,
+                max_abs_total=max_abs)
 
 
-def ctc_decode_batch(logits, lens, beam_width=100, merge_repeated=True):
-    """CTCDecoder.__call__ (ctc_decoder.py:44-68) for a batch: list of label lists"""
-    return [ctc_beam_search(np.asarray(logits[b][:int(lens[b])]), beam_width, merge_repeated)
+def ctc_decode_batch(logits, lens, beam_width=100, merge_repeated=True, details=False):
+    """CTCDecoder.__call__ (ctc_decoder.py:44-68) for a batch: list of label lists (of the
+    dicts of ctc_beam_search with details=True)"""
+    return [ctc_beam_search(np.asarray(logits[b][:int(lens[b])]), beam_width, merge_repeated, details=details)
             for b in range(len(lens))]
 
 

@@ -65,6 +65,88 @@ def test_ctc_decode_batch_respects_lengths():
     assert out[2] == D.ctc_beam_search(logits[2, :3], 8)
 
 
+def _prefix_prob(logits, prefix):
+    """log of the probability that the collapsed labelling of the T frames is exactly `prefix` — at the last frame a
+    leaf's newp.total is that of its own labelling, by brute force over all paths"""
+    return D.ctc_label_prob_bruteforce(logits, list(prefix))
+
+
+@pytest.mark.parametrize('seed', range(4))
+@pytest.mark.parametrize('T,C', [(4, 3), (3, 4)])
+def test_ctc_details_of_an_exact_beam_equal_brute_force(seed, T, C):
+    """a beam wide enough to hold every prefix drops nothing: every kept prefix's total is the brute-force
+    probability of its labelling, the beam is sorted, the margins are those of its totals"""
+    rng = np.random.default_rng(100 + seed)
+    logits = rng.normal(0, 2.0, (T, C))
+    det = D.ctc_beam_search(logits, beam_width=1000, merge_repeated=False, details=True)
+    seqs = [s for s in _all_label_seqs(C, T, C - 1) if D.ctc_label_prob_bruteforce(logits, s) > -np.inf]
+    assert sorted(l for l, _ in det['beam']) == sorted(seqs)
+    for labels, total in det['beam']:
+        assert abs(total - _prefix_prob(logits, labels)) < 1e-12, labels
+    totals = [v for _, v in det['beam']]
+    assert totals == sorted(totals, reverse=True)
+    assert det['labels'] == det['beam'][0][0] and det['total'] == totals[0]
+    assert det['top_gap'] == totals[0] - totals[1]
+    assert det['select_gap'] == np.inf and det['select_ties'] == 0
+    assert det['max_abs_total'] >= max(abs(v) for v in totals)
+    assert det['labels'] == D.ctc_beam_search(logits, beam_width=1000, merge_repeated=False)
+
+
+def test_ctc_details_margins_of_a_narrow_beam():
+    """W = 2 on three frames worked by hand: after frame 0 the candidates are '', 'a', 'b' with log-probabilities
+    ln 0.5, ln 0.3, ln 0.2 — 'b' is dropped with a gap of ln 1.5"""
+    p = np.array([[0.3, 0.2, 0.5], [0.3, 0.2, 0.5], [0.3, 0.2, 0.5]])
+    det = D.ctc_beam_search(np.log(p), 2, False, details=True)
+    assert det['select_gap'] <= np.log(0.3 / 0.2) + 1e-12 and det['select_ties'] == 0 and len(det['beam']) == 2
+    one = D.ctc_beam_search(np.log(p[:1]), 2, False, details=True)
+    assert abs(one['select_gap'] - np.log(1.5)) < 1e-12 and abs(one['top_gap'] - np.log(0.5 / 0.3)) < 1e-12
+    assert abs(one['max_abs_total'] + np.log(0.2)) < 1e-12 and one['beam'][0][0] == [] and one['beam'][1][0] == [0]
+    # the threshold of frame 0 falls inside the tie of the two labels; then the nearest other totals count: 0.4 above
+    tie = D.ctc_beam_search(np.zeros((1, 3)), 2, False, details=True)
+    assert tie['select_ties'] == 1 and tie['select_gap'] == np.inf and tie['beam'][1][0] == [0]
+    tie = D.ctc_beam_search(np.log(np.array([[0.25, 0.25, 0.4, 0.1]])), 2, False, blank=2, details=True)
+    assert tie['select_ties'] == 1 and abs(tie['select_gap'] - np.log(0.4 / 0.25)) < 1e-12
+
+
+def test_ctc_default_return_is_unchanged_and_float32_restates():
+    rng = np.random.default_rng(8)
+    logits = rng.normal(0, 1.5, (3, 9, 5)).astype(np.float32)
+    lens = [9, 0, 6]
+    plain = D.ctc_decode_batch(logits, lens, 6)
+    assert all(isinstance(x, list) for x in plain) and plain[1] == []
+    dets = D.ctc_decode_batch(logits, lens, 6, details=True)
+    assert [d['labels'] for d in dets] == plain
+    assert dets[1]['total'] == 0.0 and dets[1]['beam'] == [([], 0.0)] and dets[1]['top_gap'] == np.inf
+    # pinned before `details` existed (seed 8, beam 6, merge_repeated)
+    assert plain == [D.ctc_beam_search(logits[0], 6), [], D.ctc_beam_search(logits[2, :6], 6)]
+    d32 = D.ctc_beam_search(logits[0], 6, details=True, dtype=np.float32)
+    assert isinstance(d32['total'], np.float32) and d32['labels'] == dets[0]['labels']
+    assert abs(float(d32['total']) - dets[0]['total']) < 9 * 2 * 2.0 ** -23 * abs(dets[0]['total'])
+
+
+def test_ctc_dead_candidates_leave_the_beam():
+    """the kernel's definition: -inf (and NaN) totals never stay in the beam; a frame that kills every candidate
+    ends the search with the empty labelling and total -inf"""
+    ninf = -np.inf
+    x = np.zeros((4, 3))
+    x[2] = ninf                                                # no log-softmax: every candidate is NaN
+    det = D.ctc_beam_search(x, 4, details=True)
+    assert det['labels'] == [] and det['total'] == ninf and det['beam'] == [] and det['top_gap'] == np.inf
+    assert D.ctc_beam_search(x, 4) == []
+    # only label 0 is possible at frame 0, only the blank afterwards: one live prefix, probability 1
+    x = np.full((3, 3), ninf)
+    x[0, 0] = x[1, 2] = x[2, 2] = 0.0
+    det = D.ctc_beam_search(x, 4, details=True)
+    assert det['beam'] == [([0], 0.0)] and det['select_gap'] == np.inf
+    # blank impossible at frame 1: the empty prefix dies there and does not come back
+    with np.errstate(divide='ignore'):
+        x = np.log(np.array([[0.2, 0.2, 0.6], [0.5, 0.5, 0.0], [0.2, 0.2, 0.6]]))
+    det = D.ctc_beam_search(x, 100, False, details=True)
+    assert [] not in [l for l, _ in det['beam']]
+    for labels, total in det['beam']:
+        assert abs(total - D.ctc_label_prob_bruteforce(x, labels)) < 1e-12, labels
+
+
 @pytest.mark.parametrize('a,b,d', [('kitten', 'sitting', 3), ('', 'abc', 3), ('abc', '', 3), ('abc', 'abc', 0),
                                    ('flaw', 'lawn', 2), ('intention', 'execution', 5)])
 def test_edit_distance_known_answers(a, b, d):

@@ -10,6 +10,7 @@ import torch
 
 from oracle import decode_oracle as D
 from nabu_amd import ops, recipes
+from tests import decode_cases as dc
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -25,6 +26,35 @@ def _ctc_case(rng, B, T, C, peaky):
     return logits, lens
 
 
+def t(a):
+    return torch.tensor(a, device=DEV)
+
+
+def check_ctc(logits, lens, W, merge, dets, what):
+    """the kernel on logits [B,T,C] / lens [B] against the oracle's details `dets` (tests.decode_cases.oracle): the
+    labelling, the -1 padding and the log-probability of the best leaf, |lp - total| <= 2 T eps32 max(1, |total|);
+    an utterance without frames has exactly 0.0, one whose beam died -inf.  Returns (ids, out_len, lp) as arrays."""
+    B, T, _ = logits.shape
+    ids, out_len, lp = (x.cpu().numpy() for x in ops.ctc_beam_search(t(logits), t(lens), W, merge))
+    worst = 0.0
+    for b, det in enumerate(dets):
+        assert list(ids[b, :out_len[b]]) == det['labels'], (what, b)
+        assert np.all(ids[b, out_len[b]:] == -1), (what, b)
+        total = float(det['total'])
+        if lens[b] <= 0:
+            assert lp[b] == 0.0 and total == 0.0, (what, b, lp[b])
+        elif total == -np.inf:
+            assert lp[b] == -np.inf, (what, b, lp[b])
+        else:
+            bound = dc.lp_bound(T, total)
+            err = abs(float(lp[b]) - total)
+            worst = max(worst, err / bound)
+            assert err <= bound, '%s, utterance %d: lp %.9g, oracle %.12g, error %.3g > %.3g' % (
+                what, b, lp[b], total, err, bound)
+    print('%s: log-probability error at most %.3f of its bound' % (what, worst))
+    return ids, out_len, lp
+
+
 @pytest.mark.parametrize('B,T,C,W,peaky,merge', [
     (4, 12, 5, 8, 0.0, True), (4, 12, 5, 8, 0.0, False), (6, 40, 40, 100, 3.0, True),
     (3, 60, 12, 16, 2.0, True), (2, 25, 3, 100, 0.0, False), (5, 33, 40, 100, 0.5, True)])
@@ -33,13 +63,8 @@ def test_ctc_beam_search_matches_oracle(B, T, C, W, peaky, merge):
     logits, lens = _ctc_case(rng, B, T, C, peaky)
     if B > 2:
         lens[1] = 0                                       # an empty utterance decodes to nothing
-    ids, out_len, lp = ops.ctc_beam_search(torch.tensor(logits, device=DEV), torch.tensor(lens, device=DEV), W, merge)
-    ids, out_len = ids.cpu().numpy(), out_len.cpu().numpy()
-    want = D.ctc_decode_batch(logits, lens, W, merge)
-    for b in range(B):
-        assert list(ids[b, :out_len[b]]) == want[b], b
-        assert np.all(ids[b, out_len[b]:] == -1)
-    assert np.all(np.isfinite(lp.cpu().numpy()))
+    dets = D.ctc_decode_batch(logits, lens, W, merge, details=True)
+    check_ctc(logits, lens, W, merge, dets, 'B %d T %d C %d W %d' % (B, T, C, W))
 
 
 def test_ctc_beam_search_cfg2_shape_and_exhaustive_small():
@@ -90,6 +115,55 @@ def test_edit_distance_matches_oracle():
     assert int(got[0]) == D.edit_distance(list(h[0]), list(r[0]))
 
 
+def prune_reference(logits, logprobs, lengths, finished, temp, lpw):
+    """a direct numpy restatement of beam_search_decoder.py:233-318 (float32 like TF): all_lp, all_ids, all_len
+    [B, W*C + W] of the candidates — the expansions, then the 'stay' of every beam — and order [B, W], the selected"""
+    B, W, C = logits.shape
+    FMAX = np.finfo(np.float32).max
+    with np.errstate(invalid='ignore'):
+        x = logits / np.float32(temp)
+        nlp = (x - x.max(-1, keepdims=True))
+        nlp = nlp - np.log(np.exp(nlp).sum(-1, keepdims=True))
+        nlp = np.where(finished[:, :, None] > 0, -FMAX, nlp).astype(np.float32)
+        cand_lp = (logprobs[:, :, None] + nlp).reshape(B, W * C)
+    cand_ids = np.tile(np.arange(C), (B, W))
+    cand_len = np.repeat(lengths, C, 1) + (cand_ids != C - 1)
+    all_lp = np.concatenate([cand_lp, np.where(finished > 0, logprobs, -FMAX)], 1).astype(np.float32)
+    all_ids = np.concatenate([cand_ids, np.full((B, W), C - 1)], 1)
+    all_len = np.concatenate([cand_len, lengths], 1)
+    with np.errstate(over='ignore'):
+        scores = (all_lp / D._length_penalty(all_len, lpw)).astype(np.float32)
+    order = np.argsort(-scores, 1, kind='stable')[:, :W]
+    return dict(all_lp=all_lp, all_ids=all_ids, all_len=all_len, order=order)
+
+
+def check_prune(logits, logprobs, lengths, finished, seen, temp, lpw, rows=None, want_only=False):
+    """one expand+prune step on the device against prune_reference, on every output (pred, lengths, logprobs, stay,
+    parent, finished, seen, all_seen) of the utterances `rows` (default: all).  Returns the device's outputs as
+    arrays (want_only: the reference, without a launch)."""
+    B, W, C = logits.shape
+    ref = prune_reference(logits, logprobs, lengths, finished, temp, lpw)
+    if want_only:
+        return ref
+    all_lp, all_ids, all_len, order = ref['all_lp'], ref['all_ids'], ref['all_len'], ref['order']
+    lp_d, len_d, fin_d, seen_d = t(logprobs), t(lengths), t(finished), t(seen)
+    pred, parent, stay, all_seen = ops.beam_prune(t(logits), lp_d, len_d, fin_d, seen_d, temp, lpw)
+    r = slice(None) if rows is None else rows
+    bi = np.arange(B)[:, None]
+    np.testing.assert_array_equal(pred.cpu().numpy()[r], all_ids[bi, order][r])
+    np.testing.assert_array_equal(len_d.cpu().numpy()[r], all_len[bi, order][r])
+    np.testing.assert_allclose(lp_d.cpu().numpy()[r], all_lp[bi, order][r], rtol=1e-5, atol=1e-5)
+    st = order >= W * C
+    np.testing.assert_array_equal(stay.cpu().numpy()[r], st.astype(np.int32)[r])
+    np.testing.assert_array_equal(parent.cpu().numpy()[r], np.where(st, order - W * C, order // C)[r])
+    np.testing.assert_array_equal(fin_d.cpu().numpy()[r], (all_ids[bi, order] == C - 1).astype(np.int32)[r])
+    np.testing.assert_array_equal(seen_d.cpu().numpy()[r], (seen | (all_ids[bi, order] == C - 1))[r])
+    np.testing.assert_array_equal(all_seen.cpu().numpy()[r], seen_d.cpu().numpy().all(1).astype(np.int32)[r])
+    return dict(pred=pred.cpu().numpy(), parent=parent.cpu().numpy(), stay=stay.cpu().numpy(),
+                all_seen=all_seen.cpu().numpy(), logprobs=lp_d.cpu().numpy(), lengths=len_d.cpu().numpy(),
+                finished=fin_d.cpu().numpy(), seen=seen_d.cpu().numpy(), parent_d=parent, stay_d=stay)
+
+
 @pytest.mark.parametrize('W,C,lpw,temp', [(4, 6, 0.0, 1.0), (16, 40, 1.0, 1.0), (8, 5, 0.7, 2.0)])
 def test_beam_prune_and_gather(W, C, lpw, temp):
     """one expand+prune step against a direct numpy restatement of beam_search_decoder.py:233-318"""
@@ -100,41 +174,14 @@ def test_beam_prune_and_gather(W, C, lpw, temp):
     lengths = rng.integers(0, 7, (B, W)).astype(np.int32)
     finished = (rng.uniform(size=(B, W)) < 0.3).astype(np.int32)
     seen = finished.copy()
-    t = lambda a: torch.tensor(a, device=DEV)
-    lp_d, len_d, fin_d, seen_d = t(logprobs), t(lengths), t(finished), t(seen)
-    pred, parent, stay, all_seen = ops.beam_prune(t(logits), lp_d, len_d, fin_d, seen_d, temp, lpw)
-    # numpy restatement (float32 like TF)
-    FMAX = np.finfo(np.float32).max
-    x = logits / np.float32(temp)
-    nlp = (x - x.max(-1, keepdims=True))
-    nlp = nlp - np.log(np.exp(nlp).sum(-1, keepdims=True))
-    nlp = np.where(finished[:, :, None] > 0, -FMAX, nlp).astype(np.float32)
-    cand_lp = (logprobs[:, :, None] + nlp).reshape(B, W * C)
-    cand_ids = np.tile(np.arange(C), (B, W))
-    cand_len = np.repeat(lengths, C, 1) + (cand_ids != C - 1)
-    all_lp = np.concatenate([cand_lp, np.where(finished > 0, logprobs, -FMAX)], 1).astype(np.float32)
-    all_ids = np.concatenate([cand_ids, np.full((B, W), C - 1)], 1)
-    all_len = np.concatenate([cand_len, lengths], 1)
-    with np.errstate(over='ignore'):
-        scores = (all_lp / D._length_penalty(all_len, lpw)).astype(np.float32)
-    order = np.argsort(-scores, 1, kind='stable')[:, :W]
-    bi = np.arange(B)[:, None]
-    np.testing.assert_array_equal(pred.cpu().numpy(), all_ids[bi, order])
-    np.testing.assert_array_equal(len_d.cpu().numpy(), all_len[bi, order])
-    np.testing.assert_allclose(lp_d.cpu().numpy(), all_lp[bi, order], rtol=1e-5, atol=1e-5)
-    st = order >= W * C
-    np.testing.assert_array_equal(stay.cpu().numpy(), st.astype(np.int32))
-    np.testing.assert_array_equal(parent.cpu().numpy(), np.where(st, order - W * C, order // C))
-    np.testing.assert_array_equal(fin_d.cpu().numpy(), (all_ids[bi, order] == C - 1).astype(np.int32))
-    np.testing.assert_array_equal(seen_d.cpu().numpy(), seen | (all_ids[bi, order] == C - 1))
-    np.testing.assert_array_equal(all_seen.cpu().numpy(), seen_d.cpu().numpy().all(1).astype(np.int32))
+    got = check_prune(logits, logprobs, lengths, finished, seen, temp, lpw)
     F = 37
     fresh = rng.normal(size=(B, W, F)).astype(np.float32)
     old = rng.normal(size=(B, W, F)).astype(np.float32)
-    got = ops.beam_gather(t(fresh), t(old), parent, stay).cpu().numpy()
-    par = parent.cpu().numpy()
-    want = np.where(st[:, :, None], old[bi, par], fresh[bi, par])
-    np.testing.assert_array_equal(got, want)
+    out = ops.beam_gather(t(fresh), t(old), got['parent_d'], got['stay_d']).cpu().numpy()
+    bi = np.arange(B)[:, None]
+    want = np.where(got['stay'][:, :, None] > 0, old[bi, got['parent']], fresh[bi, got['parent']])
+    np.testing.assert_array_equal(out, want)
 
 
 def _speller(attention, nl, U, C, E, K=5, F=3, seed=5, prob_fn='softmax'):
