@@ -78,11 +78,22 @@ __device__ __forceinline__ float dpp_f(float v, const int ctrl_sel) {
 // So: one Newton step behind the reciprocal (two fused multiply-adds: centred again, mean as the division's), and tanh
 // as (1 - e) / (1 + e), whose numerator cancels nothing behind the reciprocal (half the rms error of 2 r - 1 besides);
 // the clamp keeps e = exp(-2x) finite (|tanh| = 1 to the last bit beyond |x| = 9 already).
+// The Newton step cannot take d = inf (r = 0, and -inf * 0 + 1 is NaN), and exp(-x) is inf below x = -88.73: a gate
+// pre-activation that low (a large negative bias, a saturating weight column) turned the gate, the rest of the sequence
+// and every gradient into NaN where the function is 0 (tests/test_hip_recurrence_range.py).  So x < -88.7 (exp still
+// finite there: 3.3e38, sigmoid 3.0e-39) takes 0 — the input the select is for is a gate pre-activation below -88.7,
+// -inf included.  A compare that fails for NaN, so a NaN argument stays NaN, and every x >= -88.7 gives the bits it always
+// gave.  The RESULT is selected, not the argument clamped: the compare then runs beside the exponential and one
+// v_cndmask_b32 per gate is all the chain sees; compare + select in front of v_exp_f32 cost 0.2 ms of cfg2's 12.0 ms
+// step (LABNOTES section 23).  speller_persist.hip (fsig) has a copy: keep the two in step.
 __device__ __forceinline__ float rcp_newton(float d) {
   const float r = __builtin_amdgcn_rcpf(d);
   return fmaf(fmaf(-d, r, 1.0f), r, r);
 }
-__device__ __forceinline__ float fast_sigmoid(float x) { return rcp_newton(1.0f + __expf(-x)); }
+__device__ __forceinline__ float fast_sigmoid(float x) {
+  const float s = rcp_newton(1.0f + __expf(-x));
+  return x < -88.7f ? 0.0f : s;
+}
 __device__ __forceinline__ float fast_tanh(float x) {
   const float e = __expf(-2.0f * __builtin_amdgcn_fmed3f(x, -30.0f, 30.0f));
   return (1.0f - e) * rcp_newton(1.0f + e);

@@ -118,12 +118,18 @@ __device__ __forceinline__ float quad_bcast(float v, int i) {
   }
 }
 // gate functions as in lstm_persist_dev.h (round 5): v_rcp_f32 is not centred and 2 r - 1 amplifies its bias into a relative
-// bias of tanh — one Newton step behind the reciprocal, tanh as (1 - e) / (1 + e)
+// bias of tanh — one Newton step behind the reciprocal, tanh as (1 - e) / (1 + e); the sigmoid takes 0 for a gate
+// pre-activation below -88.7 (below -88.73 exp(-x) is inf, and the Newton step makes NaN of 1 + inf, not 0): a select of
+// the result by a compare that fails for NaN, so NaN stays NaN and every x >= -88.7 gives the bits it always gave — keep
+// in step with fast_sigmoid (lstm_persist_dev.h: why the result and not the argument)
 __device__ __forceinline__ float rcpn(float d) {
   const float r = __builtin_amdgcn_rcpf(d);
   return fmaf(fmaf(-d, r, 1.0f), r, r);
 }
-__device__ __forceinline__ float fsig(float x) { return rcpn(1.0f + __expf(-x)); }
+__device__ __forceinline__ float fsig(float x) {
+  const float s = rcpn(1.0f + __expf(-x));
+  return x < -88.7f ? 0.0f : s;
+}
 __device__ __forceinline__ float ftanh(float x) {
   const float e = __expf(-2.0f * __builtin_amdgcn_fmed3f(x, -30.0f, 30.0f));
   return (1.0f - e) * rcpn(1.0f + e);

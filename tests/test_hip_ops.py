@@ -109,18 +109,31 @@ def _blstm_params(rng, D, H, scale=0.2):
                 bw_kernel=rng.normal(0, scale, (D + H, 4 * H)), bw_bias=rng.normal(0, scale, 4 * H))
 
 
-def _run_blstm(B, T, D, H, lens, mode, seed=0, need_dx=True, precision='default'):
-    from nabu_amd import ops
+def _blstm_operands(B, T, D, H, lens, seed=0, edit=None):
+    """the seeded operands of _run_blstm, rounded through float32, and the float64 oracle's results on them;
+    edit(x, p, dout), if given, changes the draws in place before the rounding (tests/test_hip_recurrence_range.py)"""
     rng = np.random.default_rng(seed)
     x = rng.normal(size=(B, T, D)).astype(np.float32).astype(np.float64)
-    for b in range(B):
-        x[b, lens[b]:] = 0
     p = {k: v.astype(np.float32).astype(np.float64) for k, v in _blstm_params(rng, D, H).items()}
     dout = rng.normal(size=(B, T, 2 * H)).astype(np.float32).astype(np.float64)
+    if edit is not None:
+        edit(x, p, dout)
+        x, dout = (a.astype(np.float32).astype(np.float64) for a in (x, dout))
+        p = {k: v.astype(np.float32).astype(np.float64) for k, v in p.items()}
+    for b in range(B):
+        x[b, lens[b]:] = 0
     ref_out, cache = O.blstm_fwd(x, np.asarray(lens), p)
     ref_dx, ref_g = O.blstm_bwd(dout, cache)
+    return x, p, dout, ref_out, ref_dx, ref_g
 
-    plan = ops.BlstmPlan(B, T, D, H, int(max(lens)), mode, precision)
+
+def _run_blstm(B, T, D, H, lens, mode, seed=0, need_dx=True, precision='default', recurrent_precision='default',
+               operands=None):
+    """operands: what _blstm_operands returned for this shape (a reference shared by several runs: never written)"""
+    from nabu_amd import ops
+    x, p, dout, ref_out, ref_dx, ref_g = operands or _blstm_operands(B, T, D, H, lens, seed)
+
+    plan = ops.BlstmPlan(B, T, D, H, int(max(lens)), mode, precision, recurrent_precision=recurrent_precision)
     xd, ld = dev(x), dev(np.asarray(lens), torch.int32)
     pd = {k: dev(v) for k, v in p.items()}
     out = torch.full((B, T, 2 * H), float('nan'), device='cuda')

@@ -210,6 +210,34 @@ def test_persistent_decoder_forward(U, E, Te):
     hip.check_persist_status()
 
 
+@pytest.mark.parametrize('attention,K,F', [('vanilla', 0, 0), ('location_aware', 5, 3)])
+def test_persistent_decoder_with_saturated_gates(attention, K, F):
+    """the decoder cell's bias holds, for each gate on ten units of its own, -88, -89, -104, -300, -690 and the same
+    positive (tests/test_hip_recurrence_range.py, case a): below -88.73 exp(-z) is inf in float32, and the persistent
+    kernels' sigmoid (fsig: a Newton step behind v_rcp_f32) made NaN of it where the step chain's division gives 0 —
+    logits, loss and every gradient against the oracle at check_speller's tolerances, on the persistent kernels"""
+    import ctypes
+    from nabu_amd import _hip, ops as hip
+    from nabu_amd.neuralnetworks.models.ed_decoders import rnn_decoder
+    from tests.test_hip_recurrence_range import saturating_bias
+    U, E, Te = 64, 64, 40
+    rng = np.random.default_rng(5 + U)
+    enc_len = rng.integers(Te // 2, Te + 1, 32).astype(np.int32)
+    enc_len[0] = Te
+    enc_len[5] = 3
+    tlen = rng.integers(1, 9, 32).astype(np.int32)
+    tlen[3] = 8
+    d = _hip.SpellerDesc(ctypes.sizeof(_hip.SpellerDesc), 32, Te, E, U, 8, 9, 1, int(attention == 'location_aware'), K, F, 0,
+                         1.0, 0, 0, 0.0, 0, 0)
+    assert [_hip.lib().nabu_speller_uses_persistent(ctypes.byref(d), b) for b in (0, 1)] == [1, 1]
+    bias = np.zeros(4 * U, np.float32)                 # (the cell's own initialiser is zeros too)
+    saturating_bias(bias, U)
+    check_speller(attention, 1, U, K, F, enc_len, tlen, E=E,
+                  restore={PRE + 'attention_wrapper/multi_rnn_cell/cell_0/lstm_cell/bias': bias})
+    assert rnn_decoder.dynamic_decode.last_paths == (1, 1)
+    hip.check_persist_status()
+
+
 def test_persistent_decoder_batch_of_64_runs_as_two_launches():
     """vanilla attention, 64 utterances: forward AND backward as two persistent launches of 32 rows each (row offset,
     whole-batch strides of the time-major tensors) — logits and every gradient against the oracle"""
@@ -511,7 +539,9 @@ def test_plan_decisions_are_those_of_the_two_inline_drivers(monkeypatch):
     hip.check_persist_status()
 
 
-def check_speller(attention, nl, U, K, F, enc_len, tlen, E=24):
+def check_speller(attention, nl, U, K, F, enc_len, tlen, E=24, restore=None):
+    """restore: name -> value of variables that take that value instead of their initialiser's (the draws of the others
+    stay what they are)"""
     from nabu_amd import variables as vs
     from nabu_amd.autodiff import Tape, SeqLen
     from nabu_amd.neuralnetworks.models.ed_decoders import ed_decoder_factory
@@ -536,6 +566,7 @@ def check_speller(attention, nl, U, K, F, enc_len, tlen, E=24):
         tg[b, tlen[b] - 1] = C - 1
         tg[b, tlen[b]:] = 0
     store = vs.VariableStore(seed=3)
+    store.restore_from(restore or {})
     dev = torch.device('cuda')
     enc_d = torch.tensor(enc, device=dev)
     from nabu_amd.autodiff import record
