@@ -689,6 +689,27 @@ int nabu_adam_clip_step_from(size_t n, float *param_out, const float *src, const
  * BEFORE the all-reduce, trainer.py:556-569). */
 int nabu_clip_f32(size_t n, float *g, float clip, nabu_stream_t stream);
 
+/* Gradient accumulation (numbatches_to_aggregate = A * replicas, A > 1: Trainer.step_accumulated).  Every backward
+ * pass OVERWRITES the flat gradient buffer (the weight-gradient products run with beta = 0, the bias and norm-parameter
+ * gradients are plain column sums, nothing is added to what the buffer held), so the sum over an update's micro-batches
+ * is kept in a second flat buffer.  Each micro-batch's gradient is clipped as a replica's is before the exchange and
+ * added in the fixed order j = 0, 1, ...:
+ *   out[i] = clamp(g[i], -clip, clip) + (acc ? acc[i] : 0)
+ * acc = NULL is the first micro-batch: a pure write, the accumulator is neither cleared nor read.  out may be acc (the
+ * usual case) or g (the last micro-batch of a data-parallel update, whose local sum is exchanged from the gradient
+ * buffer) or a buffer of its own; a shifted overlap is an argument error.  8 bytes per parameter moved without acc,
+ * 12 with it (28 for nabu_adam_clip_step).  NaN stays NaN, as in nabu_clip_f32. */
+int nabu_clip_accumulate_f32(size_t n, float *out, const float *acc, const float *g, float clip,
+                             nabu_stream_t stream);
+/* The update of the last micro-batch on one replica: nabu_adam_clip_step (src = NULL, param_out updated in place) or
+ * nabu_adam_clip_step_from (src read-only, no overlap with param_out) on the gradient
+ *   x = clamp(grad_scale * (acc[i] + clamp(g[i], -clip, clip)), -clip, clip)
+ * without the last accumulate pass and the re-read of its result: bit for bit what nabu_clip_accumulate_f32 followed
+ * by nabu_adam_clip_step{,_from} on its output gives.  acc and g are read-only and do not overlap. */
+int nabu_adam_clip_step_acc(size_t n, float *param_out, const float *src, const float *acc, const float *g,
+                            float *m, float *v, float lr_t, float b1, float b2, float eps,
+                            float clip, float grad_scale, nabu_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Regularisation noise (Philox4x32-10, counter = element index, key = seed):
  *   dropout: y = x * mask / keep_prob, mask ~ Bernoulli(keep_prob) —

@@ -169,6 +169,8 @@ SIGNATURES = {
     'nabu_adam_clip_step': (_i, [_sz, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp]),
     'nabu_adam_clip_step_from': (_i, [_sz, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp]),
     'nabu_clip_f32': (_i, [_sz, _vp, _f, _vp]),
+    'nabu_clip_accumulate_f32': (_i, [_sz, _vp, _vp, _vp, _f, _vp]),
+    'nabu_adam_clip_step_acc': (_i, [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp]),
     'nabu_dropout_f32': (_i, [_sz, _vp, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _vp]),
     'nabu_gaussian_noise_f32': (_i, [_sz, _vp, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _vp]),
     'nabu_weight_noise_f32': (_i, [_sz, _vp, _vp, _vp, _vp, _i, _f, _c.c_ulonglong, _c.c_ulonglong, _vp]),

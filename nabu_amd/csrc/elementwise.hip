@@ -12,25 +12,43 @@ __device__ __forceinline__ float clip_value(float x, float clip) {
   return x != x ? x : fminf(fmaxf(x, -clip), clip);
 }
 
+// the trailing `acc` argument of adam_clip_kernel, when it has one
+__device__ __forceinline__ const float *acc_of() { return nullptr; }
+__device__ __forceinline__ const float *acc_of(const float *acc) { return acc; }
+
 // ---------------------------------------------------------------------------
 // fused clip + TF-style Adam: 4 streams read (param, grad, m, v), 3 written.
 // 16-byte accesses, grid-stride, 7*4 = 28 algorithmic bytes per parameter.
 // FROM: the parameter is read from `src` instead of p (nabu_adam_clip_step_from: the update of a step whose forward and
 // backward passes ran at p = src + noise); the one difference, every other expression is the plain kernel's.
-template <bool FROM>
+// ACC...: empty, or one `float` for a trailing argument `acc`: the gradient is then acc + clamp(g, +-clip), the sum of an
+// update's earlier clipped micro-batch gradients and the last one (nabu_adam_clip_step_acc): one more stream read,
+// 32 bytes per parameter, and no accumulate pass before it.  A pack, not a bool: with it empty the kernel has the
+// arguments, and so the code, it always had.
+template <bool FROM, typename... ACC>
 __global__ __launch_bounds__(256) void adam_clip_kernel(size_t n, float *__restrict__ p,
                                                         const float *__restrict__ src,
                                                         const float *__restrict__ g,
                                                         float *__restrict__ m,
                                                         float *__restrict__ v, float lr_t,
                                                         float b1, float b2, float eps,
-                                                        float clip, float gscale) {
+                                                        float clip, float gscale,
+                                                        const ACC *__restrict__... acc_arg) {
+  constexpr bool WITH_ACC = sizeof...(ACC) == 1;
+  const float *__restrict__ acc = acc_of(acc_arg...);
   const size_t n4 = n / 4;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (size_t i = tid; i < n4; i += stride) {
     float4 pp = FROM ? reinterpret_cast<const float4 *>(src)[i] : reinterpret_cast<float4 *>(p)[i];
     float4 gg = reinterpret_cast<const float4 *>(g)[i];
+    if (WITH_ACC) {
+      const float4 aa = reinterpret_cast<const float4 *>(acc)[i];
+      gg.x = aa.x + clip_value(gg.x, clip);
+      gg.y = aa.y + clip_value(gg.y, clip);
+      gg.z = aa.z + clip_value(gg.z, clip);
+      gg.w = aa.w + clip_value(gg.w, clip);
+    }
     float4 mm = reinterpret_cast<float4 *>(m)[i];
     float4 vv = reinterpret_cast<float4 *>(v)[i];
 #define NABU_ADAM1(c)                                           \
@@ -46,7 +64,7 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(size_t n, float *__restr
     reinterpret_cast<float4 *>(v)[i] = vv;
   }
   for (size_t i = n4 * 4 + tid; i < n; i += stride) {
-    float x = clip_value(g[i] * gscale, clip);
+    float x = clip_value((WITH_ACC ? acc[i] + clip_value(g[i], clip) : g[i]) * gscale, clip);
     float mm = b1 * m[i] + (1.f - b1) * x;
     float vv = b2 * v[i] + (1.f - b2) * x * x;
     m[i] = mm;
@@ -70,6 +88,36 @@ __global__ __launch_bounds__(256) void clip_kernel(size_t n, float *__restrict__
     reinterpret_cast<float4 *>(g)[i] = x;
   }
   for (size_t i = n4 * 4 + tid; i < n; i += stride) g[i] = clip_value(g[i], clip);
+}
+
+// out = clamp(g, +-clip) (+ acc): one micro-batch's clipped gradient added to the sum of the earlier ones.  ACC false is
+// the first micro-batch: a pure write, the accumulator is neither cleared nor read (8 bytes per parameter, 12 with acc).
+// out may BE acc or g (no __restrict__: every thread reads its elements before it writes them, nobody else touches them).
+template <bool ACC>
+__global__ __launch_bounds__(256) void clip_accumulate_kernel(size_t n, float *out, const float *acc, const float *g,
+                                                              float clip) {
+  const size_t n4 = n / 4;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (size_t i = tid; i < n4; i += stride) {
+    float4 x = reinterpret_cast<const float4 *>(g)[i];
+    x.x = clip_value(x.x, clip);
+    x.y = clip_value(x.y, clip);
+    x.z = clip_value(x.z, clip);
+    x.w = clip_value(x.w, clip);
+    if (ACC) {
+      const float4 a = reinterpret_cast<const float4 *>(acc)[i];
+      x.x += a.x;
+      x.y += a.y;
+      x.z += a.z;
+      x.w += a.w;
+    }
+    reinterpret_cast<float4 *>(out)[i] = x;
+  }
+  for (size_t i = n4 * 4 + tid; i < n; i += stride) {
+    const float x = clip_value(g[i], clip);
+    out[i] = ACC ? x + acc[i] : x;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -450,6 +498,31 @@ extern "C" int nabu_adam_clip_step_from(size_t n, float *param_out, const float 
   return 0;
 }
 
+// true when [a, a + n) and [b, b + n) are the same range or share no element
+static bool same_or_disjoint(const float *a, const float *b, size_t n) { return a == b || a + n <= b || b + n <= a; }
+
+extern "C" int nabu_adam_clip_step_acc(size_t n, float *param_out, const float *src, const float *acc, const float *g,
+                                       float *m, float *v, float lr_t, float b1, float b2, float eps, float clip,
+                                       float grad_scale, nabu_stream_t stream) {
+  if (n == 0) return 0;
+  NABU_CHECK_ARG(param_out && acc && g && m && v, "adam_acc: null pointer");
+  NABU_CHECK_ARG(((uintptr_t)param_out | (uintptr_t)src | (uintptr_t)acc | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0,
+                 "adam_acc: buffers must be 16-byte aligned");
+  NABU_CHECK_ARG(!src || src + n <= param_out || param_out + n <= src,
+                 "adam_acc: src and param_out overlap (src = NULL is the in-place update)");
+  NABU_CHECK_ARG(acc + n <= g || g + n <= acc, "adam_acc: acc and g overlap");
+  if (src)
+    hipLaunchKernelGGL((adam_clip_kernel<true, float>), dim3(grid_for(n / 4 + 1)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), n, param_out, src, g, m, v, lr_t, b1, b2, eps, clip, grad_scale,
+                       acc);
+  else
+    hipLaunchKernelGGL((adam_clip_kernel<false, float>), dim3(grid_for(n / 4 + 1)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), n, param_out, (const float *)nullptr, g, m, v, lr_t, b1, b2, eps,
+                       clip, grad_scale, acc);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int nabu_weight_noise_f32(size_t n, float *param, float *clean, const int32_t *ranges,
                                      const int32_t *ranges_host, int nranges, float stddev, unsigned long long seed,
                                      unsigned long long offset, nabu_stream_t stream) {
@@ -482,6 +555,24 @@ extern "C" int nabu_clip_f32(size_t n, float *g, float clip, nabu_stream_t strea
   NABU_CHECK_ARG(g && (uintptr_t)g % 16 == 0, "clip: null or unaligned pointer");
   hipLaunchKernelGGL(clip_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), n, g, clip);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int nabu_clip_accumulate_f32(size_t n, float *out, const float *acc, const float *g, float clip,
+                                        nabu_stream_t stream) {
+  if (n == 0) return 0;
+  NABU_CHECK_ARG(out && g, "clip_accumulate: null pointer (only acc may be NULL)");
+  NABU_CHECK_ARG(((uintptr_t)out | (uintptr_t)acc | (uintptr_t)g) % 16 == 0,
+                 "clip_accumulate: buffers must be 16-byte aligned");
+  NABU_CHECK_ARG(same_or_disjoint(out, g, n) && (!acc || same_or_disjoint(out, acc, n)),
+                 "clip_accumulate: out must be acc, g or a buffer of its own, not a shifted overlap of either");
+  if (acc)
+    hipLaunchKernelGGL(clip_accumulate_kernel<true>, dim3(grid_for(n / 4 + 1)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), n, out, acc, g, clip);
+  else
+    hipLaunchKernelGGL(clip_accumulate_kernel<false>, dim3(grid_for(n / 4 + 1)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), n, out, (const float *)nullptr, g, clip);
   NABU_LAUNCH_CHECK();
   return 0;
 }

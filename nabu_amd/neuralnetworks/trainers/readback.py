@@ -10,7 +10,8 @@ import torch
 from nabu_amd import ops as hip
 from nabu_amd.neuralnetworks.trainers import loss_functions
 
-WORDS = 32          # 1 loss word + CTC status words (one per output) + one word per persistent-kernel workspace
+WORDS = 32          # 1 loss word + CTC status words (one per output and micro-batch) + one word per persistent-kernel
+                    # workspace; a record that needs more grows by this many
 
 
 class StepRecord(object):
@@ -24,8 +25,9 @@ class StepRecord(object):
 
     def fill(self, step, loss, ctc_status, workspaces):
         '''enqueue the copies of this step's words behind the step (device tensors: asynchronous, closed by an event)'''
-        if 1 + len(ctc_status) + len(workspaces) > WORDS:
-            raise Exception('a step record holds %d words, this step has %d' % (WORDS, 1 + len(ctc_status) + len(workspaces)))
+        need = 1 + len(ctc_status) + len(workspaces)
+        if need > self.host.numel():       # an accumulated update brings the CTC words of all its micro-batches
+            self.host = torch.zeros((need + WORDS - 1) // WORDS * WORDS, dtype=torch.int32, pin_memory=self.host.is_pinned())
         self.step, self.n_ctc, self.workspaces = step, len(ctc_status), list(workspaces)
         self.host[0:1].view(torch.float32).copy_(loss.detach().reshape(1).to(torch.float32), non_blocking=True)
         for i, s in enumerate(ctc_status):

@@ -12,7 +12,17 @@ underneath:
     RCCL all-reduce of the flat gradient buffer per step: every replica clips its
     own gradient, the clipped gradients are averaged, one Adam update is applied —
     the synchronous semantics the reference's SyncReplicasOptimizer branch
-    intends with numbatches_to_aggregate = number of workers.  Optional
+    intends with numbatches_to_aggregate = number of workers.
+    ``numbatches_to_aggregate = A * replicas`` with A > 1 accumulates gradients on
+    the device: every replica takes A batches per update, clips each one's gradient
+    as a replica's is clipped before the exchange, sums them in a second flat
+    buffer (nabu_clip_accumulate_f32), exchanges the local sum once and applies one
+    Adam step on the mean of all A * replicas clipped gradients — the update
+    A * replicas replicas make, on the batches they would read (step_accumulated;
+    DESIGN.md section 6).  0 (the default) and ``replicas`` itself are the plain
+    step; any other value is an error, the stale-gradient dropping of a
+    SyncReplicasOptimizer that aggregates fewer gradients than it has workers is
+    not reproduced.  Optional
     (``allreduce_buckets = True``, an extension key; default False): the same sum
     exchanged as one bucket per encoder layer (+ one for the decoder), each started
     as soon as its gradients are final and overlapped with the dense products of the
@@ -57,6 +67,24 @@ def weight_noise_keys(conf):
     if start < 0:
         raise ValueError('weight_noise_start_step must be >= 0, got %r' % text)
     return stddev, start
+
+
+def aggregate_key(conf, world):
+    """the `numbatches_to_aggregate` key of the [trainer] section with `world` replicas -> A, the batches every replica
+    takes per update.  0 (the default: defaults/standardtrainer.cfg) and `world` are the plain step (A = 1), A * world
+    with A > 1 accumulates A clipped gradients per replica; everything else raises."""
+    text = str(conf.get('numbatches_to_aggregate', '0')).strip()
+    try:
+        k = int(text)
+    except ValueError:
+        raise ValueError('numbatches_to_aggregate must be an integer, got %r (with %d replica%s)'
+                         % (text, world, '' if world == 1 else 's'))
+    if k < 0 or k % world:
+        raise ValueError('numbatches_to_aggregate = %s with world = %d replica%s: the value must be 0 or a multiple of the '
+                         'number of replicas (every replica then takes value / world batches per update); fewer '
+                         'aggregated gradients than replicas would drop stale gradients as the reference\'s '
+                         'SyncReplicasOptimizer does, which is not reproduced' % (text, world, '' if world == 1 else 's'))
+    return max(k // world, 1)
 
 
 def weight_noise_ranges(variables):
@@ -151,6 +179,10 @@ class Trainer(object, metaclass=ABCMeta):
         # weight_noise / weight_noise_start_step (extension keys as well): validated here for the same reason
         self.weight_noise, self.weight_noise_start_step = weight_noise_keys(self.conf)
         self.flat_clean = self.noise_table = None
+        # numbatches_to_aggregate: A batches per replica and update (1: the plain step), validated here as well
+        self.accumulate = aggregate_key(self.conf, server.world_size if server is not None else 1)
+        self.flat_acc = None               # the sum of an update's clipped micro-batch gradients (allocated when A > 1)
+        self._micro = 0                    # micro-batches of the current update already in flat_acc
         self.last_weight_noise = None      # the (seed, offset) of the latest noisy step
         self._noisy = False                # True from a step's noise launch until its optimiser has run
         self.model = Model(conf=modelconf, trainlabels=int(self.conf['trainlabels']), constraint=None)
@@ -177,6 +209,8 @@ class Trainer(object, metaclass=ABCMeta):
         self.learning_rate_fact = 1.0
         self.data = self._data()
         outputs['num_steps'] = self.data.num_batches() * int(self.conf['num_epochs'])
+        if self.accumulate > 1:            # updates, A batches each: the data seen stays that of num_epochs
+            outputs['num_steps'] = max(1, outputs['num_steps'] // self.accumulate)
         self.loss_fn = loss_functions.factory(self.conf['loss'], self.label_smoothing)
         self.world = self.server.world_size if self.server is not None else 1
         self.flat = self.flat_grad = self.adam_m = self.adam_v = None
@@ -292,6 +326,47 @@ class Trainer(object, metaclass=ABCMeta):
                 self.flat.copy_(self.flat_clean)
         return loss
 
+    def step_accumulated(self, batches):
+        '''one training update on numbatches_to_aggregate / replicas = A device batches (A > 1), taken one after another:
+        each micro-batch runs the forward pass, the loss and the backward pass of step(), its gradient is clipped and
+        added to flat_acc in the order of the list, the last one ends in the exchange and ONE Adam step on the mean.
+        Weight noise is drawn once, before the first micro-batch; the model's own draws come per micro-batch.  Returns
+        the mean of the A losses as a 1-element device tensor (no host synchronisation).'''
+        self._create_graph()
+        if self.accumulate < 2:
+            raise ValueError('step_accumulated needs numbatches_to_aggregate = A * replicas with A > 1; this trainer '
+                             'takes one batch per update: call step()')
+        if len(batches) != self.accumulate:
+            raise ValueError('step_accumulated takes %d batches per update (numbatches_to_aggregate = %s with %d '
+                             'replicas), got %d' % (self.accumulate, self.conf['numbatches_to_aggregate'], self.world,
+                                                    len(batches)))
+        if self._micro:
+            raise Exception('an update is under way (%d micro-batches accumulated)' % self._micro)
+        if self.weight_noise > 0 and self.global_step >= self.weight_noise_start_step:
+            self._add_weight_noise(batches[0])
+        total = None
+        try:
+            for batch in batches:
+                with Tape() as tape:
+                    logits, logit_seq_length = self.model(
+                        inputs=batch['inputs'], input_seq_length=batch['input_seq_length'],
+                        targets=batch['targets'], target_seq_length=batch['target_seq_length'],
+                        is_training=True)
+                    loss = self.loss_fn(batch['targets'], logits, logit_seq_length, batch['target_seq_length'])
+                    extra = self.aditional_loss()
+                    if extra is not None:
+                        loss = hip.axpy_(loss, extra)
+                if self.flat is None:
+                    self._init_optimizer()
+                self._backward_and_update(tape, loss)          # accumulates; the last one updates
+                total = loss if total is None else hip.axpy_(total, loss)
+            return hip.sum_(total, 1.0 / self.accumulate)
+        finally:
+            self._micro = 0            # (an exception: the partial sum is dropped, micro-batch 0 overwrites flat_acc)
+            if self._noisy:
+                self._noisy = False
+                self.flat.copy_(self.flat_clean)
+
     def _add_weight_noise(self, batch):
         '''a noisy step (the keys weight_noise / weight_noise_start_step): ONE offset of the global stream, taken before
         the model's own draws, then ONE launch that saves the flat parameters to flat_clean and adds
@@ -315,18 +390,34 @@ class Trainer(object, metaclass=ABCMeta):
         self.last_weight_noise = (seed, offset)
 
     def _backward_and_update(self, tape, loss):
-        if self.buckets is not None:
+        last = self._micro == self.accumulate - 1          # (always, without accumulation)
+        hooked = self.buckets is not None and last         # buckets travel under the LAST micro-batch's backward pass
+        if hooked:
             self._begin_bucketed(tape)
         try:
             tape.backward(loss)
         finally:
-            if self.buckets is not None:
+            if hooked:
                 self._end_backward()
                 failed = hip.take_phase_hook_error()      # raised inside the C -> Python hook of nabu_blstm_bwd
                 if failed is not None:
                     self._join_comm()                     # no collective outlives the step
                     raise failed
-        self._update()
+        if last:
+            self._update()
+        else:
+            self._accumulate(self._micro)
+
+    def _accumulate(self, j):
+        '''micro-batch j < A - 1 of an update: flat_acc (+)= clip(flat_grad), one launch; j = 0 writes the accumulator
+        without reading it.  The last micro-batch goes to _update.'''
+        if self.accumulate < 2 or j != self._micro or j >= self.accumulate - 1:
+            raise Exception('micro-batch %d cannot be accumulated: %d of %d are in, the last one belongs to the update'
+                            % (j, self._micro, self.accumulate))
+        if self.flat_acc is None:
+            self.flat_acc = torch.empty_like(self.flat_grad)
+        hip.clip_accumulate(self.flat_acc, self.flat_acc if j else None, self.flat_grad, CLIP)
+        self._micro = j + 1
 
     def _init_optimizer(self):
         store = self.model.store
@@ -398,7 +489,10 @@ class Trainer(object, metaclass=ABCMeta):
             if not everything and not all(id(v) in self._ready and id(v) in self._declared for v in b['vars']):
                 continue
             view = self.flat_grad[b['start']:b['end']]
-            hip.clip_(view, CLIP)
+            if self.accumulate > 1:        # the local sum of A clipped gradients, left in the gradient buffer
+                hip.clip_accumulate(view, self.flat_acc[b['start']:b['end']], view, CLIP)
+            else:
+                hip.clip_(view, CLIP)
             self._works.append(self.server.all_reduce_sum_async(view))
             self._sent.add(i)
             if self.schedule_log is not None:       # (bench.py / tests: which bucket went on the wire at which call)
@@ -415,6 +509,8 @@ class Trainer(object, metaclass=ABCMeta):
     def _update(self):
         '''clip + Adam (reference trainer.py:512-580), with the gradient exchange of
         the data-parallel mode in between'''
+        if self.accumulate > 1:
+            return self._update_accumulated()
         lr = self.learning_rate()
         self.adam_step += 1
         t = self.adam_step
@@ -435,6 +531,37 @@ class Trainer(object, metaclass=ABCMeta):
             self._adam(lr_t, 1.0 / self.world)                   # ... mean, Adam
         else:
             self._adam(lr_t, 1.0)
+        self.last_lr = lr
+
+    def _update_accumulated(self):
+        '''_update for the last of A > 1 micro-batches: flat_acc holds the first A - 1 clipped gradients, flat_grad the
+        last one as the backward pass left it.  One replica: ONE launch clips it, adds it and applies Adam.  Several:
+        the local sum is completed in flat_grad (per bucket by _launch_ready_buckets), exchanged ONCE, and Adam runs at
+        1 / (A * world): the mean of A * world clipped gradients, what A * world replicas compute.'''
+        A = self.accumulate
+        if self._micro != A - 1:
+            raise Exception('the update needs %d accumulated micro-batches, %d are in' % (A - 1, self._micro))
+        lr = self.learning_rate()
+        self.adam_step += 1
+        t = self.adam_step
+        lr_t = lr * math.sqrt(1.0 - ADAM_B2 ** t) / (1.0 - ADAM_B1 ** t)
+        scale = 1.0 / (A * self.world)
+        if self.world > 1:
+            ev = self._allreduce_events()
+            if self.buckets is not None:
+                self._launch_ready_buckets(everything=True)
+                self._join_comm()
+            else:
+                hip.clip_accumulate(self.flat_grad, self.flat_acc, self.flat_grad, CLIP)
+                self.server.all_reduce_sum_(self.flat_grad)
+            if ev is not None:
+                ev[1].record()
+            self._adam(lr_t, scale)
+        else:
+            hip.adam_clip_step_acc(self.flat, self.flat_clean if self._noisy else None, self.flat_acc, self.flat_grad,
+                                   self.adam_m, self.adam_v, lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, CLIP, scale)
+            self._noisy = False
+        self._micro = 0
         self.last_lr = lr
 
     def _adam(self, lr_t, grad_scale):
@@ -464,6 +591,9 @@ class Trainer(object, metaclass=ABCMeta):
     def state(self):
         '''everything tf.train.Saver() of the reference's session would write: model
         variables, Adam slots, global step, learning-rate factor, validation bookkeeping'''
+        if self._micro:
+            raise Exception('state() in the middle of an update (%d of %d micro-batches accumulated): checkpoints fall '
+                            'on update boundaries' % (self._micro, self.accumulate))
         if self.flat is None:
             self._init_optimizer()
         from nabu_amd.neuralnetworks.components import ops as nops
@@ -564,8 +694,14 @@ class Trainer(object, metaclass=ABCMeta):
             start = time.time()
             # each replica reads its own shard of the epoch (replaces the shared
             # filename queue on ps:0, trainer.py:342-351)
-            batch = self.to_device(self.data.batch(self.global_step * self.world + self.task_index))
-            loss = self.step(batch)
+            if self.accumulate == 1:
+                batch = self.to_device(self.data.batch(self.global_step * self.world + self.task_index))
+                loss = self.step(batch)
+            else:
+                # update s, micro-batch j, rank r: batch (s * A + j) * world + r, what A * world replicas read
+                first = self.global_step * self.accumulate * self.world + self.task_index
+                loss = self.step_accumulated([self.to_device(self.data.batch(first + j * self.world))
+                                              for j in range(self.accumulate)])
             loss_functions.check_status()
             if self.world > 1:
                 loss = self.server.all_reduce_sum_(loss.clone())
@@ -627,7 +763,9 @@ class Trainer(object, metaclass=ABCMeta):
     def _train_overlapped(self, num_steps, ckpt, history, depth):
         '''train()'s loop with the host work taken off the step's critical path: batches come staged from a
         BatchPrefetcher (`depth` ahead), are uploaded with one copy and unpacked by one launch, and the loss and
-        status words of step s are read after step s + 1 has been enqueued (trainers/readback.py).  Pending records
+        status words of step s are read after step s + 1 has been enqueued (trainers/readback.py); with
+        numbatches_to_aggregate a step is an update of A batches and its record holds the status words of all of them.
+        Pending records
         are drained before every validation point, before every checkpoint and at the end, so history, validation
         decisions and checkpoints are those of the synchronous loop; an infeasible CTC batch or a persistent kernel's
         time-out raises one iteration late, naming its step.'''
@@ -652,8 +790,8 @@ class Trainer(object, metaclass=ABCMeta):
             while len(pending) > keep:
                 finish(pending.pop(0))
 
-        def shard():
-            return self.global_step * self.world + self.task_index
+        def shard():                          # the first batch of update global_step (A batches each, `world` apart)
+            return self.global_step * self.accumulate * self.world + self.task_index
 
         self._prefetcher = BatchPrefetcher(self.data, shard(), self.world, depth,
                                            int(self.conf.get('prefetch_workers', 2)), self.stage,
@@ -670,8 +808,12 @@ class Trainer(object, metaclass=ABCMeta):
                 if self._prefetcher.next_step != shard():      # a go-back restored an earlier global step
                     self._prefetcher.reset(shard())
                 start = time.time()
-                batch = self.to_device_staged(self._prefetcher.get())
-                loss = self.step(batch)
+                if self.accumulate == 1:
+                    batch = self.to_device_staged(self._prefetcher.get())
+                    loss = self.step(batch)
+                else:
+                    loss = self.step_accumulated([self.to_device_staged(self._prefetcher.get())
+                                                  for _ in range(self.accumulate)])
                 if self.world > 1:
                     loss = self.server.all_reduce_sum_(loss.clone())
                 rec = spare.pop() if spare else StepRecord(pinned=on_gpu)

@@ -365,6 +365,31 @@ def clip_(g, clip=1.0):
     return g
 
 
+def clip_accumulate(out, acc, g, clip=1.0):
+    """out = clamp(g, +-clip) + acc (acc None: out = clamp(g, +-clip), nothing read but g); out may be acc or g
+    (nabu_clip_accumulate_f32): one micro-batch of an accumulated update.  A None out or g reaches the entry point as
+    NULL and is its argument error."""
+    given = [(name, _f32(t, name)) for name, t in (('g', g), ('out', out), ('acc', acc)) if t is not None]
+    n = given[0][1].numel() if given else 0
+    for name, t in given:
+        if t.numel() != n:
+            raise _hip.NabuHipError('clip_accumulate: %s holds %d elements, %s %d' % (name, t.numel(), given[0][0], n))
+    check(_hip.lib().nabu_clip_accumulate_f32(n, ptr(out), ptr(acc), ptr(g), clip, stream()), 'nabu_clip_accumulate_f32')
+    return out
+
+
+def adam_clip_step_acc(param_out, src, acc, g, m, v, lr_t, b1=0.9, b2=0.999, eps=1e-8, clip=1.0, grad_scale=1.0):
+    """adam_clip_step (src None) or adam_clip_step_from (src: the clean parameters) on the gradient
+    acc + clamp(g, +-clip): the update of an accumulated step's last micro-batch (nabu_adam_clip_step_acc)"""
+    for name, t in (('src', src), ('acc', acc), ('g', g)):
+        if t is not None and t.numel() != param_out.numel():
+            raise _hip.NabuHipError('adam_clip_step_acc: %s holds %d elements, param_out %d'
+                                    % (name, t.numel(), param_out.numel()))
+    check(_hip.lib().nabu_adam_clip_step_acc(param_out.numel(), ptr(_f32(param_out, 'param_out')), ptr(src),
+                                             ptr(_f32(acc, 'acc')), ptr(_f32(g, 'g')), ptr(m), ptr(v), lr_t, b1, b2, eps,
+                                             clip, grad_scale, stream()), 'nabu_adam_clip_step_acc')
+
+
 def dropout(x, keep_prob, seed, offset):
     y = torch.empty_like(x)
     check(_hip.lib().nabu_dropout_f32(x.numel(), ptr(x), ptr(y), keep_prob, seed, offset, stream()),
