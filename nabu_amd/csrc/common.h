@@ -36,6 +36,44 @@ int fail(int code, const char *fmt, ...);
 // a call that reports its own error: pass it on
 #define NABU_TRY(call) do { int e_ = (call); if (e_) return e_; } while (0)
 
+// ---- launching a kernel with a large dynamic-LDS request (common.hip) --------------------------------------------------
+// Makes sure `fn` may be launched with `bytes` of dynamic LDS on the CURRENT device.  Up to 64 KiB is the runtime's default
+// and needs nothing; up to 160 KiB (what a CU has) hipFuncAttributeMaxDynamicSharedMemorySize is raised; more is
+// NABU_EUNSUP.  The attribute belongs to the function object on a device, not to the calling thread, so the largest size
+// granted per (function, device) is kept in ONE process-wide table behind a mutex and only ever grows: a later, smaller
+// request (of any thread) finds the grant and leaves it alone.  A request that finds no room in the table sets the
+// attribute on every call.
+int ensure_dynamic_lds(const void *fn, size_t bytes);
+template <typename K, typename... Args>
+static inline int launch_lds(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
+  if (int e = ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), lds)) return e;
+  hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
+// compute units of the CURRENT device as the runtime reports them (partitioned / CPX modes expose fewer than the 256 of a
+// whole MI355X), and the LDS a workgroup may use there (the runtime reports it under one of three attribute names
+// depending on its version: the largest answer).  Cached per thread and device; 0: the query failed
+int device_cus();
+int device_lds_bytes();
+// the runtime's occupancy answer for (fn, threads, lds) on the current device, the LDS request granted first; cached
+int max_blocks_per_cu(const void *fn, int threads, size_t lds, int *blocks);
+// Launch of a kernel whose workgroups poll each other, so that co-residency of the whole grid is a REQUIREMENT: the grid
+// is validated against the occupancy answer before it is launched — what hipLaunchCooperativeKernel would check,
+// without its +15-19 us per launch.  admit(blocks_per_cu) is the caller's rule: 0, or the error it reports.
+// dry: validate only (every chunk of a call is validated before the first one is enqueued)
+template <typename K, typename A, typename Admit>
+static inline int launch_coresident(K kernel, const A &args, int grid, int threads, size_t lds, Admit admit,
+                                    hipStream_t stream, bool dry) {
+  int blocks = 0;
+  if (int e = max_blocks_per_cu(reinterpret_cast<const void *>(kernel), threads, lds, &blocks)) return e;
+  if (int e = admit(blocks)) return e;
+  if (dry) return 0;
+  return launch_lds(kernel, dim3(grid), dim3(threads), lds, stream, args);
+}
+// an integer environment switch, read on every call (a site that reads its switch once keeps the result in a static)
+int env_int(const char *name, int dflt);
+
 // C = op(A)·op(B) (+ beta*C) (+ bias) on row-major operands (the Speller's drivers and the beam search)
 static inline int mm(bool ta, bool tb, int M, int N, int K, const float *A, int lda, const float *Bm, int ldb, float beta,
                      float *C, int ldc, const float *bias, float *ws, size_t wsb, nabu_stream_t st) {
@@ -67,6 +105,25 @@ static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; 
 int colsum_pair(int rows, int N, const float *part, int ld, float *out0, float *out1, hipStream_t stream);
 struct FillSeg { void *ptr; size_t words; unsigned value; };
 int multi_fill(const FillSeg *segs, int n, hipStream_t stream);
+
+// wave64 reductions through the lane exchange; every lane gets the result
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// wave_max written out.  The compiler schedules the two forms differently: the softmax kernels of speller.hip were
+// tuned with this one and keep it
+__device__ __forceinline__ float wave_max_unrolled(float v) {
+  v = fmaxf(v, __shfl_xor(v, 32)); v = fmaxf(v, __shfl_xor(v, 16)); v = fmaxf(v, __shfl_xor(v, 8));
+  v = fmaxf(v, __shfl_xor(v, 4)); v = fmaxf(v, __shfl_xor(v, 2)); v = fmaxf(v, __shfl_xor(v, 1));
+  return v;
+}
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 // tanh through one exp: 2*sigmoid(2x)-1 (abs error ~1e-7)

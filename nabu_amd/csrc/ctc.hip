@@ -163,8 +163,7 @@ __global__ __launch_bounds__(256) void ctc_kernel(CtcArgs p) {
     if (tid < 64) {  // blank: even states, fixed-shape tree
       float v = 0.f;
       for (int s = 2 * tid; s < S; s += 128) v += gam[s];
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+      v = wave_sum(v);
       if (tid == 0) csum[blank] = v;
     } else {
       for (int c = tid - 64; c < blank; c += 192) {
@@ -224,16 +223,6 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
   return __shfl(v, 63);
 }
 #undef NABU_DPP_ADD
-__device__ __forceinline__ float wave_max64(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // One wave per workgroup: LDS traffic between its lanes needs no s_barrier (LDS operations of a wave
 // execute in order, so a read issued after a write of another lane sees it) — only that the compiler
@@ -303,7 +292,7 @@ __global__ __launch_bounds__(256) void ctc_wave_kernel(CtcArgs p) {
   float *csumw = gamw + 3 * 64;          // [3][C]  class sums of the worker's current frame
   const int lab_up = lane >= 1 ? lbl[lane - 1] : -1, lab_dn = lane < 63 ? lbl[lane + 1] : -1;
   const bool badl = lane < L && (lab < 0 || lab >= blank);
-  const int rep = (int)wave_sum64((lane >= 1 && lane < L && lab == lab_up) ? 1.f : 0.f);
+  const int rep = (int)wave_sum((lane >= 1 && lane < L && lab == lab_up) ? 1.f : 0.f);
   const bool bad = __any(badl) || Tb <= 0 || L + rep > Tb;   // tf: "Not enough time for target transition sequence"
   // occurrence chains of the labels (fixed order -> deterministic class sums); every wave keeps its own copy in registers
   bool first = lane < L;
@@ -441,26 +430,13 @@ extern "C" int nabu_ctc_loss_grad(int B, int T, int C, int Lmax, const float *lo
   p.scale = grad_scale; p.nll = nll; p.dlogits = dlogits; p.status = status;
   p.alpha = static_cast<float *>(ws);
   NABU_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
-  static int force_wg = -1;            // NABU_CTC_WORKGROUP=1: the workgroup kernel for every shape (A/B tests)
-  if (force_wg < 0) { const char *e = getenv("NABU_CTC_WORKGROUP"); force_wg = e ? atoi(e) : 0; }
+  static const int force_wg = env_int("NABU_CTC_WORKGROUP", 0);   // 1: the workgroup kernel for every shape (A/B tests)
   const size_t wshm = ctc_wave_lds_bytes(T, C, Smax);
-  if (!force_wg && Lmax <= 63 && wshm <= 150 * 1024) {
-    // wave-synchronous kernel: one wave64 per utterance
-    auto kern = ctc_wave_kernel;
-    if (wshm > 64 * 1024)
-      NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wshm));
-    hipLaunchKernelGGL(kern, dim3(B), dim3(256), wshm, s, p);
-    NABU_LAUNCH_CHECK();
-    return 0;
-  }
+  if (!force_wg && Lmax <= 63 && wshm <= 150 * 1024)     // wave-synchronous kernel: one wave64 per utterance
+    return launch_lds(ctc_wave_kernel, dim3(B), dim3(256), wshm, s, p);
   const size_t shm = ctc_lds_bytes(T, C, Smax);
   if (shm > 150 * 1024) return fail(NABU_EUNSUP, "ctc: T=%d, Lmax=%d, C=%d need %zu B of LDS", T, Lmax, C, shm);
-  if (shm > 64 * 1024)
-    NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ctc_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  hipLaunchKernelGGL(ctc_kernel, dim3(B), dim3(256), shm, s, p);
-  NABU_LAUNCH_CHECK();
-  return 0;
+  return launch_lds(ctc_kernel, dim3(B), dim3(256), shm, s, p);
 }
 
 // ---------------------------------------------------------------------------

@@ -62,16 +62,6 @@ __device__ __forceinline__ Best block_best(Best x, Best *red, int parity) {
   return r;
 }
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 
 // order-preserving map float -> uint32 (larger float = larger integer); -inf and NaN map to 0 = "dead"
@@ -574,9 +564,8 @@ __global__ __launch_bounds__(DT) void beam_scores_kernel(int N, float lpw, const
   out_len[i] = lengths[i];
 }
 
-static int set_lds(const void *fn, size_t bytes, const char *what) {
+static int lds_fits(size_t bytes, const char *what) {
   if (bytes > 160 * 1024) return fail(NABU_EUNSUP, "%s: needs %zu bytes of LDS (160 KiB per workgroup)", what, bytes);
-  if (bytes > 48 * 1024) NABU_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   return 0;
 }
 
@@ -860,7 +849,7 @@ extern "C" int nabu_ctc_beam_search(int B, int T, int C, int beam_width, int mer
   const size_t need = nabu_ctc_beam_ws_bytes(B, T, C, beam_width);
   if (ws_bytes < need) return fail(NABU_EWS, "ctc_beam_search: workspace too small");
   const size_t lds = ctc_beam_lds(C, beam_width);
-  NABU_TRY(set_lds(reinterpret_cast<const void *>(ctc_beam_kernel), lds, "ctc_beam_search"));
+  NABU_TRY(lds_fits(lds, "ctc_beam_search"));
   hipStream_t s = static_cast<hipStream_t>(stream);
   NABU_HIP(hipMemsetAsync(ws, 0xFF, need, s));   // every tree pointer = -1
   CtcBeamArgs a;
@@ -869,9 +858,7 @@ extern "C" int nabu_ctc_beam_search(int B, int T, int C, int beam_width, int mer
   a.logits = logits; a.len = logit_len; a.out_ids = out_ids; a.out_len = out_len; a.out_lp = out_logprob;
   a.nodes = static_cast<int32_t *>(ws);
   a.per_utt = (size_t)a.NN * (3 + (size_t)C - 1);
-  hipLaunchKernelGGL(ctc_beam_kernel, dim3(B), dim3(DT), lds, s, a);
-  NABU_LAUNCH_CHECK();
-  return 0;
+  return launch_lds(ctc_beam_kernel, dim3(B), dim3(DT), lds, s, a);
 }
 
 extern "C" int nabu_edit_distance(int B, const int32_t *hyp, int ldh, const int32_t *hyp_len, const int32_t *truth,
@@ -879,11 +866,9 @@ extern "C" int nabu_edit_distance(int B, const int32_t *hyp, int ldh, const int3
   NABU_CHECK_ARG(B > 0 && ldh >= 0 && ldt >= 0, "edit_distance: bad dimensions");
   NABU_CHECK_ARG(hyp_len && truth_len && dist && (hyp || ldh == 0) && (truth || ldt == 0), "edit_distance: null pointer");
   const size_t lds = 3 * ((size_t)ldh + 1) * 4;
-  NABU_TRY(set_lds(reinterpret_cast<const void *>(edit_distance_kernel), lds, "edit_distance"));
-  hipLaunchKernelGGL(edit_distance_kernel, dim3(B), dim3(DT), lds, static_cast<hipStream_t>(stream), B, hyp, ldh,
-                     hyp_len, truth, ldt, truth_len, dist);
-  NABU_LAUNCH_CHECK();
-  return 0;
+  NABU_TRY(lds_fits(lds, "edit_distance"));
+  return launch_lds(edit_distance_kernel, dim3(B), dim3(DT), lds, static_cast<hipStream_t>(stream), B, hyp, ldh, hyp_len,
+                    truth, ldt, truth_len, dist);
 }
 
 extern "C" int nabu_beam_prune(int B, int W, int C, const float *logits, float temperature, float length_penalty_w,
@@ -894,12 +879,10 @@ extern "C" int nabu_beam_prune(int B, int W, int C, const float *logits, float t
   NABU_CHECK_ARG(logits && logprobs && lengths && finished && seen && pred_ids && parent && stay && all_seen && scratch,
                  "beam_prune: null pointer");
   const size_t lds = 5 * (size_t)W * 4;
-  NABU_TRY(set_lds(reinterpret_cast<const void *>(beam_prune_kernel), lds, "beam_prune"));
+  NABU_TRY(lds_fits(lds, "beam_prune"));
   PruneArgs a = {B, W, C, logits, 1.f / temperature, length_penalty_w, logprobs, lengths, finished, seen,
                  pred_ids, parent, stay, all_seen, scratch};
-  hipLaunchKernelGGL(beam_prune_kernel, dim3(B), dim3(DT), lds, static_cast<hipStream_t>(stream), a);
-  NABU_LAUNCH_CHECK();
-  return 0;
+  return launch_lds(beam_prune_kernel, dim3(B), dim3(DT), lds, static_cast<hipStream_t>(stream), a);
 }
 
 extern "C" int nabu_beam_gather(int B, int W, int F, const float *fresh, const float *old, const int32_t *parent,

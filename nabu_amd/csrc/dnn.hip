@@ -24,18 +24,6 @@ __device__ __forceinline__ long long row_offset(const int32_t *__restrict__ len,
   return off;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // ---------------------------------------------------------------------------------------------- splice + stack
 // out[off_b + t, j*F + f] = x[b, t + s_j, f] if 0 <= t + s_j < T else 0, for t < len[b]; s = 0, +1, -1, +2, -2, ...
 // out[r, c'F .. ld) = 0.  One wave per output row, four consecutive columns per lane (ld % 4 == 0: 16-byte stores).

@@ -638,16 +638,6 @@ static bool fast_f32_ok(bool ta, bool tb, int M, int N, int K, const void *A, in
          b_seg % 4 == 0 && (!ta || M % 4 == 0) && (tb || N % 4 == 0);
 }
 
-// hipFuncSetAttribute is a per-device setting: remember, per calling thread, the devices a kernel family was
-// configured on (a process-wide flag would skip the second GPU of a multi-device process, and an unsynchronised one
-// races between threads)
-static bool configured_on_current_device(unsigned long long &mask, int *dev_out) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-  *dev_out = dev;
-  return dev < 64 && ((mask >> dev) & 1ull);
-}
-
 extern "C" int nabu_gemm_ex(int precision, int transA, int transB, int M, int N, int K, float alpha,
                             const float *A, int lda, const float *B, int ldb, float beta,
                             float *C, int ldc, const float *bias, int kseg,
@@ -713,8 +703,7 @@ static int gemm_run(int precision, int transA, int transB, int M, int N, int K, 
   auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   a.vecA = al16(A) && lda % 4 == 0 && (a_seg_stride % 4 == 0);
   a.vecB = al16(B) && ldb % 4 == 0 && (b_seg_stride % 4 == 0);
-  static int swz_env = -2;
-  if (swz_env == -2) { const char *e = getenv("NABU_GEMM_SWIZZLE"); swz_env = e ? atoi(e) : -1; }
+  static const int swz_env = env_int("NABU_GEMM_SWIZZLE", -1);
   a.swz = swz_env >= 0 ? swz_env : 0;
   if (const char *e = getenv("NABU_GEMM_NOSTAGE")) a.vecA |= 2 * atoi(e);   // timing experiments: 1 nothing, 2 no loads, 4 no LDS stores
   dim3 grid((N + BN - 1) / BN, (M + BM - 1) / BM, a.nsplit), block(256);
@@ -723,18 +712,7 @@ static int gemm_run(int precision, int transA, int transB, int M, int N, int K, 
   const bool fast32 = fast_f32_ok(transA != 0, transB != 0, M, N, K, A, lda, B, ldb, a_seg_stride, b_seg_stride);
   if ((precision == NABU_GEMM_F32 || K % FBK != 0) && smallk_ok(transA != 0, transB != 0, M, N, K, A, lda, B, ldb, kseg, C, ldc, bias)) {
     a.nsplit = 1; a.partial = nullptr;
-    const size_t lds = smallk_lds(K);
-    static thread_local unsigned long long configured = 0;
-    int dev;
-    if (!configured_on_current_device(configured, &dev)) {
-      NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_smallk_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)smallk_lds(SMALLK_MAX)));
-      if (dev < 64) configured |= 1ull << dev;
-    }
-    hipLaunchKernelGGL(gemm_smallk_kernel, dim3((N + BN - 1) / BN, (M + BM - 1) / BM), block, lds, s, a);
-    NABU_LAUNCH_CHECK();
-    return 0;
+    return launch_lds(gemm_smallk_kernel, dim3((N + BN - 1) / BN, (M + BM - 1) / BM), block, smallk_lds(K), s, a);
   }
   if (skinny_kc) {
     if (int e = gemm_skinny_launch(a, s)) return e;
@@ -744,20 +722,10 @@ static int gemm_run(int precision, int transA, int transB, int M, int N, int K, 
   } else
   if (fast32) {
     const size_t lds = 4 * (size_t)(FKT * LDT > 128 * (FKT + 2) ? FKT * LDT : 128 * (FKT + 2)) * sizeof(float);
-    static thread_local unsigned long long configured = 0;
-    int dev;
-    if (!configured_on_current_device(configured, &dev)) {
-      const void *fns[4] = {reinterpret_cast<const void *>(gemm_f32_fast_kernel<true, true>),
-                            reinterpret_cast<const void *>(gemm_f32_fast_kernel<true, false>),
-                            reinterpret_cast<const void *>(gemm_f32_fast_kernel<false, true>),
-                            reinterpret_cast<const void *>(gemm_f32_fast_kernel<false, false>)};
-      for (const void *f : fns) NABU_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      if (dev < 64) configured |= 1ull << dev;
-    }
-    if (transA && transB) hipLaunchKernelGGL((gemm_f32_fast_kernel<true, true>), grid, block, lds, s, a);
-    else if (transA) hipLaunchKernelGGL((gemm_f32_fast_kernel<true, false>), grid, block, lds, s, a);
-    else if (transB) hipLaunchKernelGGL((gemm_f32_fast_kernel<false, true>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((gemm_f32_fast_kernel<false, false>), grid, block, lds, s, a);
+    NABU_TRY(transA && transB ? launch_lds(gemm_f32_fast_kernel<true, true>, grid, block, lds, s, a)
+             : transA         ? launch_lds(gemm_f32_fast_kernel<true, false>, grid, block, lds, s, a)
+             : transB         ? launch_lds(gemm_f32_fast_kernel<false, true>, grid, block, lds, s, a)
+                              : launch_lds(gemm_f32_fast_kernel<false, false>, grid, block, lds, s, a));
   } else
   if (transA && transB) hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, block, 0, s, a);
   else if (transA) hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, block, 0, s, a);

@@ -200,17 +200,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmArgs a) {
 template <int NP>
 static int launch_np(const GemmArgs &a, bool ta, bool tb, dim3 grid, hipStream_t s) {
   const size_t lds = 2 * (size_t)NP * PLANE;
-  auto go = [&](auto kernel) -> int {
-    static thread_local bool configured = false;
-    if (!configured && lds > 48 * 1024) {
-      NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      configured = true;
-    }
-    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, a);
-    NABU_LAUNCH_CHECK();
-    return 0;
-  };
+  auto go = [&](auto kernel) { return launch_lds(kernel, grid, dim3(256), lds, s, a); };
   if (ta && tb) return go(gemm_bf16_kernel<true, true, NP>);
   if (ta) return go(gemm_bf16_kernel<true, false, NP>);
   if (tb) return go(gemm_bf16_kernel<false, true, NP>);

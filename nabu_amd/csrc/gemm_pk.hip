@@ -741,42 +741,10 @@ __global__ void pk_fill_u32_kernel(unsigned *dst, int n, unsigned v) {
   if (i < n) dst[i] = v;
 }
 
-static int pk_cu_count() {
-  static thread_local int cached_dev = -1, cached = 256;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 256; }
-  if (dev != cached_dev) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) {
-      (void)hipGetLastError();
-      v = 256;
-    }
-    cached = v;
-    cached_dev = dev;
-  }
-  return cached;
-}
+static int pk_cu_count() { return device_cus() > 0 ? device_cus() : 256; }
 
 // the tile loop needs 144 KiB of LDS per workgroup: devices that do not offer it take the other GEMM kernels
-bool gemm_pk_device_ok() {
-  static thread_local int cached_dev = -1;
-  static thread_local bool cached = false;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return false; }
-  if (dev != cached_dev) {
-    int lds = 0;
-    const hipDeviceAttribute_t names[3] = {hipDeviceAttributeMaxSharedMemoryPerBlock, hipDeviceAttributeSharedMemPerBlockOptin,
-                                           hipDeviceAttributeMaxSharedMemoryPerMultiprocessor};
-    for (hipDeviceAttribute_t n : names) {
-      int v = 0;
-      if (hipDeviceGetAttribute(&v, n, dev) == hipSuccess && v > lds) lds = v;
-    }
-    (void)hipGetLastError();
-    cached = lds >= PK_LDS;
-    cached_dev = dev;
-  }
-  return cached;
-}
+bool gemm_pk_device_ok() { return device_lds_bytes() >= PK_LDS; }
 
 // split-K policy: one workgroup per CU; with few output tiles cut the reduction so that the number of
 // workgroups comes close to a multiple of the CU count (>= 24 stages per workgroup; 48 of f16x3's half-length stages)
@@ -1027,13 +995,7 @@ static int pk_fill(PkArgs &p, const nabu_pk_gemm_desc *d, int *planes) {
   p.nkb = d->nkb;
   p.ldc = d->ldc; p.n_split = d->n_split; p.bias = d->bias; p.bias2 = d->bias2;
   p.alpha = d->alpha; p.beta = d->beta; p.partial = nullptr;
-  static int force = -2, throttle = 0;
-  if (force == -2) {
-    const char *e = getenv("NABU_PK_SPLIT");
-    force = e ? atoi(e) : -1;
-    e = getenv("NABU_PK_THROTTLE");
-    throttle = e ? atoi(e) : 0;
-  }
+  static const int force = env_int("NABU_PK_SPLIT", -1), throttle = env_int("NABU_PK_THROTTLE", 0);
   p.throttle = throttle;
   p.nsplit = pk_choose_split(p.tiles_m * p.tiles_n * p.nbatch, p.nkb, kbs, d->planes == 2 ? 48 : 24, &p.kb_per_split);
   if (force > 0) {
@@ -1062,8 +1024,7 @@ extern "C" int nabu_gemm_pk(const nabu_pk_gemm_desc *d, void *ws, size_t ws_byte
     p.partial = static_cast<float *>(ws);
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  static int var_env = -2;
-  if (var_env == -2) { const char *e = getenv("NABU_PK_VAR"); var_env = e ? atoi(e) : -1; }
+  static const int var_env = env_int("NABU_PK_VAR", -1);
   // promoted accumulation unless the caller asks for the direct chain (planes = 2, d->direct) or the environment
   // overrides (A/B measurements).  direct = 2 decides by rounding count: the direct chain rounds 3 times per 16 k,
   // v_mfma_f32_32x32x2_f32 8 times — so it is taken when a workgroup's reduction here is at most twice as long as the
@@ -1077,20 +1038,13 @@ extern "C" int nabu_gemm_pk(const nabu_pk_gemm_desc *d, void *ws, size_t ws_byte
   }
   const int var = var_env >= 0 ? var_env : (direct ? 0 : 1);
   const int grid = p.tiles_m * p.tiles_n * p.nbatch * p.nsplit;
-#define PK_LAUNCH(NP_, VAR_)                                                                                         \
-  {                                                                                                                   \
-    const int lds = NP_ == 2 ? PK_LDS2 : PK_LDS;                                                                       \
-    NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_pk_kernel<NP_, VAR_>),                           \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));                                   \
-    hipLaunchKernelGGL((gemm_pk_kernel<NP_, VAR_>), dim3(grid), dim3(512), lds, s, p);                                 \
-  }
-  if (planes == 1) PK_LAUNCH(1, 0)
-  else if (planes == 2 && var == 0) PK_LAUNCH(2, 0)
-  else if (planes == 2) PK_LAUNCH(2, 1)
-  else if (var == 0) PK_LAUNCH(3, 0)
-  else PK_LAUNCH(3, 1)
+#define PK_LAUNCH(NP_, VAR_) launch_lds(gemm_pk_kernel<NP_, VAR_>, dim3(grid), dim3(512), NP_ == 2 ? PK_LDS2 : PK_LDS, s, p)
+  NABU_TRY(planes == 1               ? PK_LAUNCH(1, 0)
+           : planes == 2 && var == 0 ? PK_LAUNCH(2, 0)
+           : planes == 2             ? PK_LAUNCH(2, 1)
+           : var == 0                ? PK_LAUNCH(3, 0)
+                                     : PK_LAUNCH(3, 1));
 #undef PK_LAUNCH
-  NABU_LAUNCH_CHECK();
   if (p.nsplit > 1) {
     const size_t n4 = (size_t)p.M * p.N * p.nbatch / 4;
     int blocks = (int)((n4 + 255) / 256);

@@ -248,8 +248,7 @@ int gemm_skinny_fused(int M, int N, int K1, const float *A, int lda, const float
   a.alpha = 1.f; a.beta = beta; a.kseg = 0; a.a_seg = a.b_seg = 0;
   a.ksplit = kc; a.nsplit = (K1 + K2) / kc; a.vecA = a.vecB = 1; a.swz = 0;
   a.nbatch = 1; a.a_bs = a.b_bs = a.c_bs = 0;
-  static int heavy_env = -1;
-  if (heavy_env < 0) { const char *e = getenv("NABU_SKINNY_HEAVY"); heavy_env = e ? atoi(e) : 0; }
+  static const int heavy_env = env_int("NABU_SKINNY_HEAVY", 0);
   SkinnyFuse f = {A2, B2, lda2, ldb2, K1, tickets, heavy_env ? 1 : 0, {}, nullptr, 0, N, 0.f};
   if (ep) f.ep = *ep; else f.ep.kind = 0;
   if (split) {
@@ -261,16 +260,9 @@ int gemm_skinny_fused(int M, int N, int K1, const float *A, int lda, const float
   const size_t xt = (size_t)kc * 32 * MT * sizeof(float), red = (size_t)4 * MT * 1024 * sizeof(float);
   const size_t lds = xt > red ? xt : red;
   dim3 grid(N / 32, a.nsplit);
-  if (MT == 1) {
-    hipLaunchKernelGGL(gemm_skinny_fused_kernel<1>, grid, dim3(256), lds, s, a, f);
-  } else {
-    // per call (cheap): the attribute is per device and this path is entered from several host threads
-    NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_skinny_fused_kernel<2>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    hipLaunchKernelGGL(gemm_skinny_fused_kernel<2>, grid, dim3(256), lds, s, a, f);
-  }
-  NABU_LAUNCH_CHECK();
-  return 0;
+  // (MT = 2 with 256-wide chunks takes the 64 KiB a launch may have by default; this path is entered from several threads)
+  return MT == 1 ? launch_lds(gemm_skinny_fused_kernel<1>, grid, dim3(256), lds, s, a, f)
+                 : launch_lds(gemm_skinny_fused_kernel<2>, grid, dim3(256), lds, s, a, f);
 }
 
 // ---------------------------------------------------------------------------
@@ -518,15 +510,8 @@ int gemm_skinny_launch(const GemmArgs &a, hipStream_t s) {
   const size_t xt = (size_t)a.ksplit * 32 * MT * sizeof(float), red = (size_t)4 * MT * 1024 * sizeof(float);
   const size_t lds = xt > red ? xt : red;
   dim3 grid(a.N / 32, a.nsplit);
-  if (MT == 1) {
-    hipLaunchKernelGGL(gemm_skinny_kernel<1>, grid, dim3(256), lds, s, a);
-  } else {
-    NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_skinny_kernel<2>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    hipLaunchKernelGGL(gemm_skinny_kernel<2>, grid, dim3(256), lds, s, a);
-  }
-  NABU_LAUNCH_CHECK();
-  return 0;
+  return MT == 1 ? launch_lds(gemm_skinny_kernel<1>, grid, dim3(256), lds, s, a)
+                 : launch_lds(gemm_skinny_kernel<2>, grid, dim3(256), lds, s, a);
 }
 
 }  // namespace nabu

@@ -231,8 +231,7 @@ static PersistPlan plan_of(const nabu_blstm_desc *d) {
 // planes of the packed-operand path for this layer (0 = not taken): bf16x6 -> 3, f16x3 -> 2, bf16 -> 1
 static int pk_planes_of(const nabu_blstm_desc *d) {
   const int prec = d->gemm_precision == NABU_GEMM_DEFAULT ? nabu_gemm_get_default_precision() : d->gemm_precision;
-  static int env = -1;
-  if (env < 0) { const char *e = getenv("NABU_PK"); env = e ? atoi(e) : 1; }
+  static const int env = env_int("NABU_PK", 1);
   if (!env || !gemm_pk_device_ok()) return 0;
   const long long BT = (long long)d->B * d->T;
   if (BT < 1024 || BT >= (1ll << 31) - 512 || d->H % 64) return 0;   // n_split = 4H must be a multiple of 256
@@ -787,9 +786,7 @@ static int stepwise_fwd(const Call &c) {
   if (c.L.ln) return ln_recurrence_fwd(ln_args(c), c.s);
   const StepArgs p = step_args(c);
   const size_t shm = ((size_t)SB * c.H + SB * 4 * SU) * sizeof(float);
-  if (shm > 64 * 1024)
-    NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(lstm_step_fwd_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+  NABU_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(lstm_step_fwd_kernel), shm));
   NABU_TRY(c.mark(g_ev_begin));
   for (int t = 0; t < c.max_len; ++t) hipLaunchKernelGGL(lstm_step_fwd_kernel, step_grid(c), dim3(STEP_NT), shm, c.s, p, t);
   NABU_LAUNCH_CHECK();

@@ -260,12 +260,6 @@ __global__ __launch_bounds__(NT) void ln_param_grad_kernel(const float *part, in
 }
 
 // ---------------------------------------------------------------------------
-template <typename K>
-static int allow_lds(K kernel, size_t shm) {
-  if (shm > 64 * 1024)
-    NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  return 0;
-}
 static size_t shm_rec(size_t H) { return (SB * H + SB * 4 * SU) * sizeof(float); }
 static size_t shm_cell_fwd(size_t H) { return (5 * H + 16) * sizeof(float); }
 static size_t shm_cell_bwd(size_t H) { return (11 * H + 32) * sizeof(float); }
@@ -276,8 +270,8 @@ static dim3 grid_rec(const LnArgs &p) { return dim3((p.H + SU - 1) / SU, (p.B + 
 size_t ln_lds_bytes(int H) { return shm_rec(H) > shm_cell_bwd(H) ? shm_rec(H) : shm_cell_bwd(H); }
 
 int ln_recurrence_fwd(LnArgs p, hipStream_t s) {
-  NABU_TRY(allow_lds(ln_rec_fwd_kernel, shm_rec(p.H)));
-  NABU_TRY(allow_lds(ln_cell_fwd_kernel, shm_cell_fwd(p.H)));
+  NABU_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(ln_rec_fwd_kernel), shm_rec(p.H)));
+  NABU_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(ln_cell_fwd_kernel), shm_cell_fwd(p.H)));
   for (int t = 0; t < p.max_len; ++t) {
     if (t > 0) hipLaunchKernelGGL(ln_rec_fwd_kernel, grid_rec(p), dim3(NT), shm_rec(p.H), s, p, t);   // (h_{-1} = 0: z is x·Wx)
     hipLaunchKernelGGL(ln_cell_fwd_kernel, dim3(p.B, 2), dim3(NT), shm_cell_fwd(p.H), s, p, t);
@@ -287,7 +281,7 @@ int ln_recurrence_fwd(LnArgs p, hipStream_t s) {
 }
 
 int ln_recurrence_bwd(LnArgs p, hipStream_t s) {
-  NABU_TRY(allow_lds(ln_cell_bwd_kernel, shm_cell_bwd(p.H)));
+  NABU_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(ln_cell_bwd_kernel), shm_cell_bwd(p.H)));
   for (int t = p.max_len - 1; t >= 0; --t) {
     p.has_dh = t + 1 < p.max_len;
     if (p.has_dh) hipLaunchKernelGGL(ln_rec_bwd_kernel, grid_rec(p), dim3(NT), 0, s, p, t);

@@ -676,24 +676,6 @@ void lstm_persist_set_timeout_us(long long us) {
   g_timeout_ticks = us > 0 ? (unsigned long long)us * 100ull : 20000000ull;
 }
 
-// compute units of the CURRENT device as the runtime reports them (partitioned / CPX modes expose fewer than the 256
-// of a whole MI355X); 0: unknown
-static int device_cus() {
-  static thread_local int cached_dev = -1, cached = 0;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
-  if (dev != cached_dev) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) {
-      (void)hipGetLastError();
-      v = 0;
-    }
-    cached = v;
-    cached_dev = dev;
-  }
-  return cached;
-}
-
 // geometry constants of the fp16-plane families (pure functions of the shape)
 int lstm_mx_chunk_rows();                                  // lstm_persist_mxh.hip: 32 batch rows per launch (8 per unit)
 size_t lstm_mxh_ring_bytes(bool fwd, int H);
@@ -732,10 +714,9 @@ static size_t f32_ring_bytes(bool fwd, int BS, int nshard, int H) {
 //   exact fp32 otherwise: at H = 512 a forward launch takes up to 64 rows (BS = 8, two workgroups per CU), B = 96 is a
 //     launch of 64 and one of 32.
 PersistPlan lstm_persist_plan(int B, int T, int D, int H, int max_len, bool exact) {
-  const auto env = [](const char *e, int dflt) { return e ? atoi(e) : dflt; };
-  static const int env_mx = env(getenv("NABU_PERSIST_MX"), 1), env_mxf = env(getenv("NABU_PERSIST_MXF"), 1);
-  static const int env_fuse = env(getenv("NABU_PERSIST_FUSE_INPUT"), 1), env_emit = env(getenv("NABU_PERSIST_EMIT"), 1);
-  const int dbg = env(getenv("NABU_PERSIST_DEBUG"), 0);     // per call: a debug variant writes no companions
+  static const int env_mx = env_int("NABU_PERSIST_MX", 1), env_mxf = env_int("NABU_PERSIST_MXF", 1);
+  static const int env_fuse = env_int("NABU_PERSIST_FUSE_INPUT", 1), env_emit = env_int("NABU_PERSIST_EMIT", 1);
+  const int dbg = env_int("NABU_PERSIST_DEBUG", 0);     // per call: a debug variant writes no companions
   PersistPlan p = {};
   p.B = B; p.T = T; p.D = D; p.H = H; p.max_len = max_len;
   const int cus = device_cus();
@@ -806,39 +787,22 @@ PersistPlan lstm_persist_plan(int B, int T, int D, int H, int max_len, bool exac
   return p;
 }
 
-// Co-residency is a REQUIREMENT of these kernels (every workgroup of a unit polls its peers): the grid is
-// validated against the runtime's occupancy answer for this kernel, block size and LDS request on the current
-// device before it is launched — what hipLaunchCooperativeKernel would check, without its +15-19 us per launch
-// (MI355X_MICROARCH.md, coop-launch row).  The answer can be one block per CU too high at 81-112 SGPRs with
-// 256-thread blocks (same guide); the grids here need at most 2 per CU where the register file admits 2 and the
-// LDS request is sized for exactly that, and every spin is bounded, so an optimistic answer costs a time-out,
-// never a hang.  NABU_EUNSUP makes LSTM_AUTO take the step-wise kernels.
+// Co-residency is a REQUIREMENT of these kernels (every workgroup of a unit polls its peers: launch_coresident of
+// common.h).  The occupancy answer can be one block per CU too high at 81-112 SGPRs with 256-thread blocks
+// (MI355X_MICROARCH.md); the grids here need at most 2 per CU where the register file admits 2 and the LDS request is
+// sized for exactly that, and every spin is bounded, so an optimistic answer costs a time-out, never a hang.
+// NABU_EUNSUP makes LSTM_AUTO take the step-wise kernels.
 // dry: validate only (every chunk of a call is validated BEFORE the first one is enqueued: a later chunk that cannot be
 // co-resident must not leave the earlier chunks' in-place updates of the gate buffers behind — the step-wise fallback
 // of LSTM_AUTO restarts from the untouched buffers)
 template <typename K>
 static int launch(K kernel, const PersistArgs &a, int grid, int threads, size_t lds, int ncu, hipStream_t stream, bool dry) {
-  const void *fn = reinterpret_cast<const void *>(kernel);
-  struct Seen { const void *fn; int dev, threads, blocks; size_t lds; };
-  static thread_local Seen seen[32] = {};
-  int dev = 0;
-  NABU_HIP(hipGetDevice(&dev));
-  int blocks = -1;
-  for (const Seen &c : seen)
-    if (c.fn == fn && c.dev == dev && c.threads == threads && c.lds == lds) blocks = c.blocks;
-  if (blocks < 0) {
-    NABU_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    NABU_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, threads, lds));
-    for (Seen &c : seen)
-      if (!c.fn) { c = Seen{fn, dev, threads, blocks, lds}; break; }
-  }
-  if ((long long)blocks * ncu < grid)
+  const auto admit = [=](int blocks) {
+    if ((long long)blocks * ncu >= grid) return 0;
     return fail(NABU_EUNSUP, "persistent LSTM: %d workgroups cannot be co-resident (%d per CU x %d CUs on this device)",
                 grid, blocks, ncu);
-  if (dry) return 0;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, stream, a);
-  NABU_LAUNCH_CHECK();
-  return 0;
+  };
+  return launch_coresident(kernel, a, grid, threads, lds, admit, stream, dry);
 }
 
 // exchange ring + XCC table back to 0xFF bytes: one small kernel (a hipMemsetAsync is its own kind of dispatch and
@@ -877,7 +841,7 @@ static int run_chunk(bool fwd, const PersistPlan &plan, const PersistPlan::Launc
     a.emit.b0 = b0;
   }
   a.rowmax_part = nullptr; a.rowmax_stride = 0;
-  { const char *e = getenv("NABU_PERSIST_DEBUG"); a.dbg = e ? atoi(e) : 0; }
+  a.dbg = env_int("NABU_PERSIST_DEBUG", 0);
   a.B = B; a.T = T; a.D = plan.D; a.H = H; a.max_len = plan.max_len; a.nshard = (B + ln.bs - 1) / ln.bs;
   a.len = t.len;
   for (int i = 0; i < 2; ++i) { a.kernel[i] = t.kernel[i]; a.gates[i] = t.gates[i]; a.cs[i] = t.cs[i]; a.bias[i] = nullptr; }

@@ -3,12 +3,12 @@
 // v_mfma_f32_16x16x32_bf16, 8 rows per unit).  Protocol description: header of lstm_persist.hip.
 #pragma once
 #include "lstm_persist.h"
+#include "persist_dev.h"
 
 #include <stdlib.h>
 
 namespace nabu {
 
-constexpr unsigned SENT = 0xFFFFFFFFu;
 constexpr unsigned OOB = 0xFFFFFFF0u;   // buffer offset beyond every exchange ring / tensor: access dropped
 constexpr int UC = 16;    // hidden units per workgroup
 #ifndef NABU_RING_BWD
@@ -22,7 +22,6 @@ constexpr int RINGB = NABU_RING_BWD;  // ... backward (reduce-scatter of dh)
 constexpr int NCU = 256;  // MI355X
 constexpr size_t TABLE_BYTES = 4096;   // XCC-id table in front of the ring
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -70,41 +69,6 @@ __device__ __forceinline__ float dpp_f(float v, const int ctrl_sel) {
 #define QUAD_XOR2(v) dpp_f(v, 1)
 #define QUAD_BCAST(v, i) dpp_f(v, 2 + (i))
 
-// Gate functions.  v_rcp_f32 is good to one unit in the last place but not centred (mean -0.06 .. -0.08 ulp on [1, 2),
-// tools/experiments/ub/rcp_bias.hip), and 2 r - 1 turns that into a RELATIVE bias of tanh that grows as tanh shrinks: one
-// cell update came out 3e-8 low in h on average (tools/experiments/ub/cell_bias.hip; the step kernels' true divisions:
-// 4e-9) — invisible in any single value, but a sum over 32 000 frames (a bias gradient) or a thousand dependent steps
-// collects it: at T = 1000 the persistent kernels' gradients stood at 1.4-5 x the step kernels' error against float64.
-// So: one Newton step behind the reciprocal (two fused multiply-adds: centred again, mean as the division's), and tanh
-// as (1 - e) / (1 + e), whose numerator cancels nothing behind the reciprocal (half the rms error of 2 r - 1 besides);
-// the clamp keeps e = exp(-2x) finite (|tanh| = 1 to the last bit beyond |x| = 9 already).
-// The Newton step cannot take d = inf (r = 0, and -inf * 0 + 1 is NaN), and exp(-x) is inf below x = -88.73: a gate
-// pre-activation that low (a large negative bias, a saturating weight column) turned the gate, the rest of the sequence
-// and every gradient into NaN where the function is 0 (tests/test_hip_recurrence_range.py).  So x < -88.7 (exp still
-// finite there: 3.3e38, sigmoid 3.0e-39) takes 0 — the input the select is for is a gate pre-activation below -88.7,
-// -inf included.  A compare that fails for NaN, so a NaN argument stays NaN, and every x >= -88.7 gives the bits it always
-// gave.  The RESULT is selected, not the argument clamped: the compare then runs beside the exponential and one
-// v_cndmask_b32 per gate is all the chain sees; compare + select in front of v_exp_f32 cost 0.2 ms of cfg2's 12.0 ms
-// step (LABNOTES section 23).  speller_persist.hip (fsig) has a copy: keep the two in step.
-__device__ __forceinline__ float rcp_newton(float d) {
-  const float r = __builtin_amdgcn_rcpf(d);
-  return fmaf(fmaf(-d, r, 1.0f), r, r);
-}
-__device__ __forceinline__ float fast_sigmoid(float x) {
-  const float s = rcp_newton(1.0f + __expf(-x));
-  return x < -88.7f ? 0.0f : s;
-}
-__device__ __forceinline__ float fast_tanh(float x) {
-  const float e = __expf(-2.0f * __builtin_amdgcn_fmed3f(x, -30.0f, 30.0f));
-  return (1.0f - e) * rcp_newton(1.0f + e);
-}
-
-__device__ __forceinline__ bool has_sentinel(const u32x4 v) {
-  return v.x == SENT || v.y == SENT || v.z == SENT || v.w == SENT;
-}
-__device__ __forceinline__ bool all_sentinel(const u32x4 v) {
-  return v.x == SENT && v.y == SENT && v.z == SENT && v.w == SENT;
-}
 __device__ __forceinline__ float sel4(int q, float a, float b, float c, float d) {
   return q == 0 ? a : q == 1 ? b : q == 2 ? c : d;
 }
@@ -136,12 +100,6 @@ __device__ __forceinline__ void prefetch_lds_b128(i32x4 rsrc, unsigned off, cons
 template <int N>
 __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// publish 16 bytes: plain store when the whole unit shares one L2, else write-through
-__device__ __forceinline__ void xstore(const u32x4 v, __amdgpu_buffer_rsrc_t rs, unsigned off, bool coloc) {
-  if (coloc) __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, 0);
-  else       __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, 16);
 }
 
 // Bounded spin bookkeeping: returns true when the caller must give up.

@@ -647,35 +647,12 @@ size_t lstm_mxf_ring_bytes(bool fwd, int H) {
   return fwd ? (size_t)MXF_NU * RING * 16 * H * 2 : (size_t)MXF_NU * MXHRINGB * P * P * MXR * MXF_UC * 4;
 }
 
-template <typename K>
-static int mxf_launch(K kernel, const PersistArgs &a, int grid, size_t lds, hipStream_t stream, bool dry) {
-  const void *fn = reinterpret_cast<const void *>(kernel);
-  struct Seen { const void *fn; int dev, blocks; };
-  static thread_local Seen seen[8] = {};
-  int dev = 0;
-  NABU_HIP(hipGetDevice(&dev));
-  int blocks = -1;
-  for (const Seen &c : seen)
-    if (c.fn == fn && c.dev == dev) blocks = c.blocks;
-  if (blocks < 0) {
-    NABU_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, 256, lds));
-    for (Seen &c : seen)
-      if (!c.fn) { c = Seen{fn, dev, blocks}; break; }
-  }
-  if (blocks < 1 || grid > NCU)
-    return fail(NABU_EUNSUP, "persistent LSTM (mxf): %d workgroups cannot be co-resident (%d per CU)", grid, blocks);
-  if (dry) return 0;          // validation pass (lstm_persist.hip, run)
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, stream, a);
-  NABU_LAUNCH_CHECK();
-  return 0;
-}
-
 // one launch over 33 .. 64 rows; `a` comes filled from run_chunk (nshard = ceil(B / 8))
 int lstm_mxf_launch(bool fwd, int H, const PersistArgs &a, hipStream_t stream, bool dry) {
   if (H != 512) return fail(NABU_EUNSUP, "persistent LSTM (mxf): unsupported H=%d", H);
   const int grid = 8 * 2 * (H / MXF_UC);
-  return fwd ? mxf_launch(lstm_mxf_fwd_kernel<512>, a, grid, MxfFwdLds<512>::TOTAL * sizeof(float), stream, dry)
-             : mxf_launch(lstm_mxf_bwd_kernel<512>, a, grid, MxfBwdLds<512>::TOTAL * sizeof(float), stream, dry);
+  return fwd ? mxh_launch(lstm_mxf_fwd_kernel<512>, a, grid, MxfFwdLds<512>::TOTAL * sizeof(float), stream, dry, "mxf")
+             : mxh_launch(lstm_mxf_bwd_kernel<512>, a, grid, MxfBwdLds<512>::TOTAL * sizeof(float), stream, dry, "mxf");
 }
 
 }  // namespace nabu

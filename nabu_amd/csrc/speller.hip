@@ -14,17 +14,11 @@
 #include "common.h"
 #include "gemm_args.h"
 #include "speller_attn.h"
+#include "speller_attn_dev.h"
 
 namespace nabu {
 
 typedef float f32x4_ __attribute__((ext_vector_type(4)));
-constexpr int AT = 512;   // threads per attention workgroup (8 wave64)
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // ---------------------------------------------------------------------------
 // LSTM cell (tf.contrib.rnn.LSTMCell: gate order i,j,f,o, forget_bias 1)
@@ -100,52 +94,10 @@ struct AttnArgs {
                             // the launch (no finish kernel); nullptr = separate finish kernel
 };
 
-// store / load of data handed from one workgroup to another inside a launch: write-through store, L1-bypassing
-// load (MI355X_MICROARCH.md "sc1 stores AND sc1 loads"); plain when the hand-off is a kernel boundary
-__device__ __forceinline__ void xst(float *p, float v, bool x) {
-  if (x) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else   *p = v;
-}
-__device__ __forceinline__ float xld(const float *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// every wave has drained its stores; returns true in the workgroup that arrives last of n
-__device__ __forceinline__ bool last_arriver(unsigned *ticket, unsigned n, int *flag) {
-  __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *flag = old == n - 1;
-    if (old == n - 1) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for reuse
-  }
-  __syncthreads();
-  return *flag != 0;
-}
-
 // LDS carve for the attention kernels (floats): al[Te] prev alignment (padded conv input),
 // sc[Te] scores / alignments, cf[Te*F] location features, red[...] reductions
 // the conv kernel [K*F] is staged at the start of the dynamic LDS (ck_floats, 16-byte multiple)
-__device__ __forceinline__ int ck_floats(const AttnArgs &p) { return p.kind == 1 ? (p.K * p.F + 3) & ~3 : 0; }
-__device__ __forceinline__ void conv_features(const AttnArgs &p, const float *al_prev, float *cf, int lo, int hi,
-                                              const float *ck_s) {
-  // cf[t,f] = sum_d a[t + d - pb] ck[d,f], 'same' padding, pb = (K-1)/2 (tf.layers.conv1d); frames [lo,hi)
-  const int pb = (p.K - 1) / 2;
-  for (int i = lo * p.F + threadIdx.x; i < hi * p.F; i += AT) {
-    const int t = i / p.F, f = i % p.F;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;     // independent chains: the loop is LDS-latency bound
-    const int d0 = max(0, pb - t), d1 = min(p.K, p.Te + pb - t);
-    const float *a = al_prev + t - pb, *c = ck_s + f;
-    int d = d0;
-    for (; d + 3 < d1; d += 4) {
-      s0 = fmaf(a[d], c[d * p.F], s0);
-      s1 = fmaf(a[d + 1], c[(d + 1) * p.F], s1);
-      s2 = fmaf(a[d + 2], c[(d + 2) * p.F], s2);
-      s3 = fmaf(a[d + 3], c[(d + 3) * p.F], s3);
-    }
-    for (; d < d1; ++d) s0 = fmaf(a[d], c[d * p.F], s0);
-    cf[i] = (s0 + s1) + (s2 + s3);
-  }
-}
+__device__ __forceinline__ int ck_floats(const AttnArgs &p) { return ck_floats(p.kind, p.K, p.F); }
 
 // REG = location-aware attention with U <= 512 and F <= 12: the Dense weights of the location
 // features (conv_proj) stay in registers for the whole kernel (forward), and their gradient is
@@ -183,7 +135,7 @@ __global__ __launch_bounds__(AT) void attn_fwd_kernel(AttnArgs p) {
     for (int t = tid; t < Te; t += AT) alp[t] = p.align_prev[(size_t)b * Te + t];
     for (int i = tid; i < p.K * p.F; i += AT) smem[i] = p.ck[i];
     __syncthreads();
-    conv_features(p, alp, cf, lo, n, smem);
+    conv_features(p.K, p.F, p.Te, alp, cf, lo, n, smem);
     __syncthreads();
   }
   // WindowedAttention (attention.py:294-396): only frames in [m - left - 1, m + right) may be attended,
@@ -292,8 +244,7 @@ __global__ __launch_bounds__(AT) void attn_fwd_kernel(AttnArgs p) {
     float m = -3.0e38f;
     if (p.prob_fn == 0) {
       for (int t = lo + tid; t < n; t += AT) m = fmaxf(m, sc[t]);
-      m = fmaxf(m, __shfl_xor(m, 32)); m = fmaxf(m, __shfl_xor(m, 16)); m = fmaxf(m, __shfl_xor(m, 8));
-      m = fmaxf(m, __shfl_xor(m, 4)); m = fmaxf(m, __shfl_xor(m, 2)); m = fmaxf(m, __shfl_xor(m, 1));
+      m = wave_max_unrolled(m);
       if (lane == 0) red[w] = m;
       __syncthreads();
       m = red[0];
@@ -340,8 +291,7 @@ __global__ __launch_bounds__(AT) void attn_fwd_kernel(AttnArgs p) {
   // softmax over the valid frames (score_mask_value = -inf past the length)
   float m = -3.0e38f;
   for (int t = tid; t < n; t += AT) m = fmaxf(m, sc[t]);
-  m = fmaxf(m, __shfl_xor(m, 32)); m = fmaxf(m, __shfl_xor(m, 16)); m = fmaxf(m, __shfl_xor(m, 8));
-  m = fmaxf(m, __shfl_xor(m, 4)); m = fmaxf(m, __shfl_xor(m, 2)); m = fmaxf(m, __shfl_xor(m, 1));
+  m = wave_max_unrolled(m);
   if (lane == 0) red[w] = m;
   __syncthreads();
   m = red[0];
@@ -577,8 +527,7 @@ __global__ __launch_bounds__(AT) void attn_fwd_loc_mfma_kernel(AttnArgs p) {
   // ---- partial result of this slice: e[t] = exp(score - local max), the local max and sum
   float m = -3.0e38f;
   for (int t = lo + tid; t < n; t += AT) m = fmaxf(m, sc[t]);
-  m = fmaxf(m, __shfl_xor(m, 32)); m = fmaxf(m, __shfl_xor(m, 16)); m = fmaxf(m, __shfl_xor(m, 8));
-  m = fmaxf(m, __shfl_xor(m, 4)); m = fmaxf(m, __shfl_xor(m, 2)); m = fmaxf(m, __shfl_xor(m, 1));
+  m = wave_max_unrolled(m);
   if (lane == 0) red[w] = m;
   __syncthreads();
   m = red[0];
@@ -729,7 +678,7 @@ __global__ __launch_bounds__(AT) void attn_bwd_kernel(AttnArgs p) {
     for (int t = tid; t < Te; t += AT) alp[t] = p.align_prev[(size_t)b * Te + t];
     for (int i = tid; i < p.K * F; i += AT) smem[i] = p.ck[i];
     __syncthreads();
-    conv_features(p, alp, cf, lo, hi, smem);
+    conv_features(p.K, p.F, p.Te, alp, cf, lo, hi, smem);
   }
   // d alignment[t] = dctx · values[t] (+ the gradient arriving through next step's location features):
   // waves over frames (4 in flight), lanes over 16-byte groups of the encoder dimension
@@ -1817,11 +1766,7 @@ int nabu::attn_fwd_impl(const nabu_attn_desc *d, int step, const int32_t *dec_le
     kern = UT <= 1 ? attn_fwd_loc_mfma_kernel<1> : UT == 2 ? attn_fwd_loc_mfma_kernel<2> : UT == 3 ? attn_fwd_loc_mfma_kernel<3>
                                                                                                    : attn_fwd_loc_mfma_kernel<4>;
   }
-  if (shm > 64 * 1024)
-    NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  hipLaunchKernelGGL(kern, dim3(d->B, S), dim3(AT), shm, s, p);
-  NABU_LAUNCH_CHECK();
+  NABU_TRY(launch_lds(kern, dim3(d->B, S), dim3(AT), shm, s, p));
   if (S > 1 && !tickets) {
     hipLaunchKernelGGL(attn_fwd_finish_kernel, dim3(d->B), dim3(256), 0, s, p, S);
     NABU_LAUNCH_CHECK();
@@ -1903,11 +1848,7 @@ int nabu::attn_bwd_impl(const nabu_attn_desc *d, int step, const int32_t *dec_le
     const size_t need = ((((size_t)d->K * d->F + 3) & ~(size_t)3) + 2 * (size_t)d->Te + (size_t)d->Te * d->F + 4 + (AT / 64) * 512) * sizeof(float);
     if (need > shm) shm = need;
   }
-  if (shm > 64 * 1024)
-    NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  hipLaunchKernelGGL(kern, dim3(d->B, S), dim3(AT), shm, s, p);
-  NABU_LAUNCH_CHECK();
+  NABU_TRY(launch_lds(kern, dim3(d->B, S), dim3(AT), shm, s, p));
 #ifdef ATTN_STAMPS
   {
     static int calls = 0;
@@ -1923,12 +1864,7 @@ int nabu::attn_bwd_impl(const nabu_attn_desc *d, int step, const int32_t *dec_le
 #endif
   if (p.tickets) return 0;
   const size_t shm2 = ((size_t)d->Te + (d->kind == 1 ? (size_t)d->Te * d->F + (size_t)d->K * d->F : 0) + 4) * sizeof(float);
-  if (shm2 > 64 * 1024)
-    NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_finish_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm2));
-  hipLaunchKernelGGL(attn_bwd_finish_kernel, dim3(d->B, d->kind == 1 ? FPA + FPK : 1), dim3(d->kind == 1 ? FT : 256), shm2, s, p, S);
-  NABU_LAUNCH_CHECK();
-  return 0;
+  return launch_lds(attn_bwd_finish_kernel, dim3(d->B, d->kind == 1 ? FPA + FPK : 1), dim3(d->kind == 1 ? FT : 256), shm2, s, p, S);
 }
 extern "C" int nabu_attn_bwd(const nabu_attn_desc *d, int step, const int32_t *dec_len,
                              const int32_t *enc_len, const float *keys, const float *values,
@@ -1969,12 +1905,8 @@ int nabu::attn_param_grads(const nabu_attn_desc *d, int S, int L, const int32_t 
     const size_t need = (size_t)PSB * (32 + 32 * d->F + 4) * sizeof(float);
     if (need > shm) shm = need;
   }
-  if (shm > 64 * 1024)
-    NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  hipLaunchKernelGGL(kern, dim3(d->B, S), dim3(PT), shm, s, d->B, d->Te, d->U, d->kind == 1 ? d->F : 0, L, dec_len, enc_len,
-                     keys, q_all, v, wf, ds_all, cf_all, dkeys, dv_part, dwf_part);
-  NABU_LAUNCH_CHECK();
-  return 0;
+  return launch_lds(kern, dim3(d->B, S), dim3(PT), shm, s, d->B, d->Te, d->U, d->kind == 1 ? d->F : 0, L, dec_len, enc_len,
+                    keys, q_all, v, wf, ds_all, cf_all, dkeys, dv_part, dwf_part);
 }
 
 extern "C" int nabu_mask_time_f32(int B, int L, int F, float *x, const int32_t *len, nabu_stream_t stream) {

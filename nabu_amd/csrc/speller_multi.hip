@@ -14,64 +14,13 @@
 #include "common.h"
 #include "gemm_args.h"
 #include "speller_multi.h"
+#include "speller_attn_dev.h"
 
 namespace nabu {
 
 namespace {
 
-constexpr int AT = 512;   // threads per attention workgroup (8 wave64)
 constexpr int MM = NABU_SPELLER_MAX_MEMORIES;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float m) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  return m;
-}
-
-
-// hand-off between workgroups inside a launch: write-through store, L1-bypassing load
-__device__ __forceinline__ void xst(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float xld(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// every wave has drained its stores; true in the workgroup that arrives last of n (the counter is left zero)
-__device__ __forceinline__ bool last_arriver(unsigned *ticket, unsigned n, int *flag) {
-  __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *flag = old == n - 1;
-    if (old == n - 1) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  return *flag != 0;
-}
-
-__host__ __device__ __forceinline__ int ck_floats(int kind, int K, int F) { return kind == 1 ? (K * F + 3) & ~3 : 0; }
-
-// cf[t,f] = sum_d a[t + d - pb] ck[d,f], 'same' padding, pb = (K-1)/2 (tf.layers.conv1d); frames [lo,hi)
-__device__ __forceinline__ void conv_features(int K, int F, int Te, const float *al_prev, float *cf, int lo, int hi,
-                                              const float *ck_s) {
-  const int pb = (K - 1) / 2;
-  for (int i = lo * F + threadIdx.x; i < hi * F; i += AT) {
-    const int t = i / F, f = i % F;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    const int d0 = max(0, pb - t), d1 = min(K, Te + pb - t);
-    const float *a = al_prev + t - pb, *c = ck_s + f;
-    int d = d0;
-    for (; d + 3 < d1; d += 4) {
-      s0 = fmaf(a[d], c[d * F], s0);
-      s1 = fmaf(a[d + 1], c[(d + 1) * F], s1);
-      s2 = fmaf(a[d + 2], c[(d + 2) * F], s2);
-      s3 = fmaf(a[d + 3], c[(d + 3) * F], s3);
-    }
-    for (; d < d1; ++d) s0 = fmaf(a[d], c[d * F], s0);
-    cf[i] = (s0 + s1) + (s2 + s3);
-  }
-}
 
 // ---------------------------------------------------------------------------
 // forward: grid (B, Smax, M).  LDS (floats): conv kernel [ck_floats] | alp[Te] | sc[Te] | cf[Te F] | red[64] | part[4 AT]
@@ -588,19 +537,6 @@ int multi_attn_geo(const nabu_speller_multi_desc *d, MultiAttnGeo *g) {
   return 0;
 }
 
-namespace {
-
-template <typename Kern>
-static int launch_attn(Kern kern, const MultiAttnGeo &g, int B, size_t shm, const MArgs &a, hipStream_t s) {
-  if (shm > 64 * 1024)
-    NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  hipLaunchKernelGGL(kern, dim3(B, g.Smax, g.M), dim3(AT), shm, s, a);
-  NABU_LAUNCH_CHECK();
-  return 0;
-}
-
-}  // namespace
-
 int put_cols(int R, int Cn, const float *src, float *dst, int ldd, int c0, hipStream_t s) {
   hipLaunchKernelGGL(put_cols_kernel, dim3((R * Cn + 255) / 256), dim3(256), 0, s, R, Cn, src, dst, ldd, c0);
   NABU_LAUNCH_CHECK();
@@ -614,12 +550,13 @@ size_t multi_attn_part_floats(int B, int Te, int E, int U, int kind, int K, int 
 }
 
 int multi_attn_launch(bool backward, const MultiAttnGeo &g, const MArgs &a, hipStream_t s) {
+  const dim3 grid(a.B, g.Smax, g.M);
   if (backward) {
-    if (a.kind == 1) return launch_attn(attn_multi_bwd_kernel<true>, g, a.B, g.lds_b, a, s);
-    return launch_attn(attn_multi_bwd_kernel<false>, g, a.B, g.lds_b, a, s);
+    if (a.kind == 1) return launch_lds(attn_multi_bwd_kernel<true>, grid, dim3(AT), g.lds_b, s, a);
+    return launch_lds(attn_multi_bwd_kernel<false>, grid, dim3(AT), g.lds_b, s, a);
   }
-  if (a.kind == 1) return launch_attn(attn_multi_fwd_kernel<true>, g, a.B, g.lds_f, a, s);
-  return launch_attn(attn_multi_fwd_kernel<false>, g, a.B, g.lds_f, a, s);
+  if (a.kind == 1) return launch_lds(attn_multi_fwd_kernel<true>, grid, dim3(AT), g.lds_f, s, a);
+  return launch_lds(attn_multi_fwd_kernel<false>, grid, dim3(AT), g.lds_f, s, a);
 }
 
 int multi_attn_fwd(int M, int B, int U, int kind, int K, int F, int prob_fn, int step, const int32_t *dec_len, const float *q,

@@ -33,11 +33,11 @@
 #include <stdlib.h>
 
 #include "lstm_persist.h"
+#include "persist_dev.h"
 
 namespace nabu {
 namespace {
 
-constexpr unsigned SENT = 0xFFFFFFFFu;
 constexpr unsigned OOB = 0xFFFFFFF0u;
 #ifndef SP_NW
 #define SP_NW 4
@@ -48,7 +48,6 @@ constexpr int R = 4, S = 8;          // utterances per unit, frame slices per ut
 constexpr int RING = 4;
 constexpr size_t TABLE_BYTES = 4096;
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct Args {
@@ -74,9 +73,6 @@ struct Args {
   int dbg;
 };
 
-__device__ __forceinline__ bool has_sentinel(const u32x4 v) {
-  return v.x == SENT || v.y == SENT || v.z == SENT || v.w == SENT;
-}
 // wave64 reductions on the DPP network (no LDS round trips); every lane gets the result
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dppf(float old, float v) {
@@ -117,26 +113,9 @@ __device__ __forceinline__ float quad_bcast(float v, int i) {
     default: return dppf<0xFF, 0xF>(v, v);
   }
 }
-// gate functions as in lstm_persist_dev.h (round 5): v_rcp_f32 is not centred and 2 r - 1 amplifies its bias into a relative
-// bias of tanh — one Newton step behind the reciprocal, tanh as (1 - e) / (1 + e); the sigmoid takes 0 for a gate
-// pre-activation below -88.7 (below -88.73 exp(-x) is inf, and the Newton step makes NaN of 1 + inf, not 0): a select of
-// the result by a compare that fails for NaN, so NaN stays NaN and every x >= -88.7 gives the bits it always gave — keep
-// in step with fast_sigmoid (lstm_persist_dev.h: why the result and not the argument)
-__device__ __forceinline__ float rcpn(float d) {
-  const float r = __builtin_amdgcn_rcpf(d);
-  return fmaf(fmaf(-d, r, 1.0f), r, r);
-}
-__device__ __forceinline__ float fsig(float x) {
-  const float s = rcpn(1.0f + __expf(-x));
-  return x < -88.7f ? 0.0f : s;
-}
-__device__ __forceinline__ float ftanh(float x) {
-  const float e = __expf(-2.0f * __builtin_amdgcn_fmed3f(x, -30.0f, 30.0f));
-  return (1.0f - e) * rcpn(1.0f + e);
-}
-// the tanh inside the attention score v . tanh(keys + q + ...): not part of a recurrent state (nothing accumulates its
-// ~1e-7 bias over the steps), and FS x U of them per workgroup and step — the centred form above costs the forward
-// kernel 14 % (cfg3) to 19 % (cfg5) of its time there
+// the gates take fast_sigmoid / fast_tanh of persist_dev.h.  The tanh inside the attention score v . tanh(keys + q + ...)
+// is not part of a recurrent state (nothing accumulates its ~1e-7 bias over the steps), and there are FS x U of them per
+// workgroup and step — the centred form costs the forward kernel 14 % (cfg3) to 19 % (cfg5) of its time there
 __device__ __forceinline__ float ftanh_s(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f; }
 
 struct Spin {
@@ -152,18 +131,6 @@ struct Spin {
   }
 };
 
-// stores of the exchange: plain when the unit shares one L2, else write-through
-__device__ __forceinline__ void xst4(const u32x4 v, __amdgpu_buffer_rsrc_t rs, unsigned off, bool coloc) {
-  if (coloc) __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, 0);
-  else       __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, 16);
-}
-__device__ __forceinline__ void xst1(unsigned v, __amdgpu_buffer_rsrc_t rs, unsigned off, bool coloc) {
-  if (coloc) __builtin_amdgcn_raw_buffer_store_b32(v, rs, off, 0, 0);
-  else       __builtin_amdgcn_raw_buffer_store_b32(v, rs, off, 0, 16);
-}
-__device__ __forceinline__ u32x4 xld4(__amdgpu_buffer_rsrc_t rs, unsigned off) {
-  return __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 16);
-}
 __device__ __forceinline__ unsigned fbits(float x) { return __builtin_bit_cast(unsigned, x); }
 
 #define SP_TIMEOUT(code)                                                                                    \
@@ -222,7 +189,7 @@ __device__ __attribute__((noinline)) int sample_row(const SampleRow q) {
       bool ok = true;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const u32x4 a = xld4(q.rc, isc[j] ? offs[j] : OOB), b = xld4(q.rh, isc[j] ? OOB : offs[j]);
+        const u32x4 a = xload(q.rc, isc[j] ? offs[j] : OOB), b = xload(q.rh, isc[j] ? OOB : offs[j]);
         v[j] = isc[j] ? a : b;
         ok = ok && !has_sentinel(v[j]);
       }
@@ -527,7 +494,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
         bool ok = true;
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
-          const u32x4 a = xld4(rc, fc[i] ? off[i] : OOB), b = xld4(rh, fc[i] ? OOB : off[i]);
+          const u32x4 a = xload(rc, fc[i] ? off[i] : OOB), b = xload(rh, fc[i] ? OOB : off[i]);
           v[i] = fc[i] ? a : b;
           ok = ok && !has_sentinel(v[i]);
         }
@@ -599,20 +566,20 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
       }
       if (gate_thr) {
         z += gbias + p.emb[(size_t)my_id * 4 * U + gg * U + gunit];
-        a = gg == 1 ? ftanh(z) : fsig(gg == 2 ? z + 1.0f : z);
+        a = gg == 1 ? fast_tanh(z) : fast_sigmoid(gg == 2 ? z + 1.0f : z);
       }
       const float gi = quad_bcast(a, 0), gj = quad_bcast(a, 1), gf = quad_bcast(a, 2), go = quad_bcast(a, 3);
       const bool act = t < glen;
       if (gate_thr && act) {
         c_state = c_state * gf + gi * gj;
-        h_state = ftanh(c_state) * go;
+        h_state = fast_tanh(c_state) * go;
       }
       a_last = act ? a : 0.f;        // saved tensors of this step go to HBM under the NEXT step's product
       if (drop && gate_thr && gg == 0)     // what the query and the output projection see of h_t (the recurrence keeps h_t)
         ho_last = h_state * p.dscale[((size_t)t * B + gb) * U + gunit];
       const bool pub = gate_thr && gg == 0;
-      xst1(fbits(h_state), rh, pub ? so * hb + (unsigned)((grow * U + gunit) * 4) : OOB, coloc);
-      xst1(SENT, rh, (pub && t >= 2) ? sr * hb + (unsigned)((grow * U + gunit) * 4) : OOB, coloc);
+      xstore1(fbits(h_state), rh, pub ? so * hb + (unsigned)((grow * U + gunit) * 4) : OOB, coloc);
+      xstore1(SENT, rh, (pub && t >= 2) ? sr * hb + (unsigned)((grow * U + gunit) * 4) : OOB, coloc);
     }
     SP_STAMP(3);
     __syncthreads();     // the partial tiles have been read: the scratch is free for h_t
@@ -632,8 +599,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
       Spin g;
       g.start();
       for (;;) {
-        v0 = xld4(rh, so * hb + (unsigned)(q0 * 16));
-        v1 = xld4(rh, so * hb + (unsigned)(q1 * 16));
+        v0 = xload(rh, so * hb + (unsigned)(q0 * 16));
+        v1 = xload(rh, so * hb + (unsigned)(q1 * 16));
         if (__all(!has_sentinel(v0) && !has_sentinel(v1))) break;
         if (g.expired(p)) { SP_TIMEOUT(1); break; }
       }
@@ -680,8 +647,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
         for (int ww = 0; ww < NW; ww += 2) s += qred[(ww * 16 + c) * 4 + row] + qred[((ww + 1) * 16 + c) * 4 + row];
       const bool pub = tid < R * UW;
       q_last = s;
-      xst1(fbits(s), rq, pub ? so * hb + (unsigned)((row * U + UW * slot + c) * 4) : OOB, coloc);
-      xst1(SENT, rq, (pub && t >= 2) ? sr * hb + (unsigned)((row * U + UW * slot + c) * 4) : OOB, coloc);
+      xstore1(fbits(s), rq, pub ? so * hb + (unsigned)((row * U + UW * slot + c) * 4) : OOB, coloc);
+      xstore1(SENT, rq, (pub && t >= 2) ? sr * hb + (unsigned)((row * U + UW * slot + c) * 4) : OOB, coloc);
     }
     SP_STAMP(5);
     // =========================== C: scores, partial context ========
@@ -693,7 +660,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
       Spin g;
       g.start();
       for (;;) {
-        v = xld4(rq, off);
+        v = xload(rq, off);
         if (__all(!has_sentinel(v))) break;
         if (g.expired(p)) { SP_TIMEOUT(1); break; }
       }
@@ -709,7 +676,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
       Spin g;
       g.start();
       for (;;) {
-        v = xld4(rl, off);
+        v = xload(rl, off);
         if (__all(!has_sentinel(v))) break;
         if (g.expired(p)) { SP_TIMEOUT(1); break; }
       }
@@ -854,13 +821,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
               if (fb + i < nf) a += es_w[fb + i] * vv[i];
           }
         }
-        xst4(__builtin_bit_cast(u32x4, a), rp, so * pb + (unsigned)(((ci * S + cs) * (E + 4) + 4 * c4) * 4), coloc);
-        xst4(sent4, rp, t >= 2 ? sr * pb + (unsigned)(((ci * S + cs) * (E + 4) + 4 * c4) * 4) : OOB, coloc);
+        xstore(__builtin_bit_cast(u32x4, a), rp, so * pb + (unsigned)(((ci * S + cs) * (E + 4) + 4 * c4) * 4), coloc);
+        xstore(sent4, rp, t >= 2 ? sr * pb + (unsigned)(((ci * S + cs) * (E + 4) + 4 * c4) * 4) : OOB, coloc);
       }
       if (tid == 0) {
         const f32x4 ms = {frozen ? -3.0e38f : m_loc, frozen ? 0.f : z_loc, 0.f, 0.f};
-        xst4(__builtin_bit_cast(u32x4, ms), rp, so * pb + (unsigned)(((ci * S + cs) * (E + 4) + E) * 4), coloc);
-        xst4(sent4, rp, t >= 2 ? sr * pb + (unsigned)(((ci * S + cs) * (E + 4) + E) * 4) : OOB, coloc);
+        xstore(__builtin_bit_cast(u32x4, ms), rp, so * pb + (unsigned)(((ci * S + cs) * (E + 4) + E) * 4), coloc);
+        xstore(sent4, rp, t >= 2 ? sr * pb + (unsigned)(((ci * S + cs) * (E + 4) + E) * 4) : OOB, coloc);
       }
     }
     SP_STAMP(8);
@@ -883,8 +850,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
       Spin g;
       g.start();
       for (;;) {
-        v[0] = xld4(rp, off[0]);
-        v[1] = xld4(rp, off[1]);
+        v[0] = xload(rp, off[0]);
+        v[1] = xload(rp, off[1]);
         if (__all(!has_sentinel(v[0]) && !has_sentinel(v[1]))) break;
         if (g.expired(p)) { SP_TIMEOUT(1); break; }
       }
@@ -916,16 +883,16 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
         if (frozen) c = ctx_prev;
         ctx_prev = c;
       }
-      xst1(fbits(ctx_prev), rc, tid < CB ? so * cb + (unsigned)((ci * E + cs * CB + tid) * 4) : OOB, coloc);
-      xst1(SENT, rc, (tid < CB && t >= 2) ? sr * cb + (unsigned)((ci * E + cs * CB + tid) * 4) : OOB, coloc);
+      xstore1(fbits(ctx_prev), rc, tid < CB ? so * cb + (unsigned)((ci * E + cs * CB + tid) * 4) : OOB, coloc);
+      xstore1(SENT, rc, (tid < CB && t >= 2) ? sr * cb + (unsigned)((ci * E + cs * CB + tid) * 4) : OOB, coloc);
       if (tid < FS) {
         float a = frozen ? al_prev : es[tid] * __expf(m_loc - M) * inv;     // (tid < FS <= 64: wave 0's copy)
         if (!frozen && f0 + tid >= cn) a = 0.f;
         al_prev = a;
       }
       if (LOC) {
-        xst1(fbits(al_prev), rl, tid < FS ? so * lb + (unsigned)((ci * TeP + f0 + tid) * 4) : OOB, coloc);
-        xst1(SENT, rl, (tid < FS && t >= 2) ? sr * lb + (unsigned)((ci * TeP + f0 + tid) * 4) : OOB, coloc);
+        xstore1(fbits(al_prev), rl, tid < FS ? so * lb + (unsigned)((ci * TeP + f0 + tid) * 4) : OOB, coloc);
+        xstore1(SENT, rl, (tid < FS && t >= 2) ? sr * lb + (unsigned)((ci * TeP + f0 + tid) * 4) : OOB, coloc);
       }
     }
     SP_STAMP(10);
@@ -953,8 +920,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
         }
         if (tid == 0) {
           p.ids_w[(size_t)(t + 1) * B + cbg] = id;
-          xst1((unsigned)id, ri, so * 16 + (unsigned)(ci * 4), coloc);
-          xst1(SENT, ri, t >= 2 ? sr * 16 + (unsigned)(ci * 4) : OOB, coloc);
+          xstore1((unsigned)id, ri, so * 16 + (unsigned)(ci * 4), coloc);
+          xstore1(SENT, ri, t >= 2 ? sr * 16 + (unsigned)(ci * 4) : OOB, coloc);
         }
       }
     }
@@ -1206,7 +1173,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
         SpinB g;
         g.start();
         for (;;) {
-          v = xld4(rk, off);
+          v = xload(rk, off);
           if (__all(off == OOB || !has_sentinel(v))) break;
           if (g.expired(p)) { SPB_TIMEOUT(); break; }
         }
@@ -1229,8 +1196,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
           SpinB g;
           g.start();
           for (;;) {
-            v[0] = xld4(rf, off[0]);
-            v[1] = xld4(rf, off[1]);
+            v[0] = xload(rf, off[0]);
+            v[1] = xload(rf, off[1]);
             if (__all(!has_sentinel(v[0]) && !has_sentinel(v[1]))) break;
             if (g.expired(p)) { SPB_TIMEOUT(); break; }
           }
@@ -1405,8 +1372,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
             const int e = 4 * q4 + k;
             o[k] = e < FF ? dcf_s[e] : (e == FF ? rp : 0.f);
           }
-          xst4(__builtin_bit_cast(u32x4, o), rf, so * fbz + (unsigned)(((ci * S + cs) * PF + 4 * q4) * 4), coloc);
-          xst4(sent4, rf, n >= 2 ? sr * fbz + (unsigned)(((ci * S + cs) * PF + 4 * q4) * 4) : OOB, coloc);
+          xstore(__builtin_bit_cast(u32x4, o), rf, so * fbz + (unsigned)(((ci * S + cs) * PF + 4 * q4) * 4), coloc);
+          xstore(sent4, rf, n >= 2 ? sr * fbz + (unsigned)(((ci * S + cs) * PF + 4 * q4) * 4) : OOB, coloc);
         }
       }
       // conv kernel's gradient of my frames: d ck[d][c] += sum_f d features[f][c] a_{t-1}[f0 + f + d - pb]
@@ -1466,8 +1433,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
       const int NH = LOCB ? NW : NFH;
       f32x4 s4 = *reinterpret_cast<const f32x4 *>(dqh + 4 * tid);
       for (int h = 1; h < NH; ++h) s4 += *reinterpret_cast<const f32x4 *>(dqh + (size_t)h * U + 4 * tid);
-      xst4(__builtin_bit_cast(u32x4, s4), ra, so * ab + (unsigned)(((ci * S + cs) * U + 4 * tid) * 4), coloc);
-      xst4(sent4, ra, n >= 2 ? sr * ab + (unsigned)(((ci * S + cs) * U + 4 * tid) * 4) : OOB, coloc);
+      xstore(__builtin_bit_cast(u32x4, s4), ra, so * ab + (unsigned)(((ci * S + cs) * U + 4 * tid) * 4), coloc);
+      xstore(sent4, ra, n >= 2 ? sr * ab + (unsigned)(((ci * S + cs) * U + 4 * tid) * 4) : OOB, coloc);
     }
     SPB_STAMP(5);
     // =========================== D1b: my block of dq ===========================
@@ -1479,7 +1446,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
       SpinB g;
       g.start();
       for (;;) {
-        v = xld4(ra, off);
+        v = xload(ra, off);
         if (__all(!has_sentinel(v))) break;
         if (g.expired(p)) { SPB_TIMEOUT(); break; }
       }
@@ -1493,8 +1460,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
       if (tid < UB)
         for (int i = 0; i < S; ++i) s += blk[i * UB + tid];
       dq_last = s;
-      xst1(fbits(s), rq, tid < UB ? so * qb + (unsigned)((ci * U + cs * UB + tid) * 4) : OOB, coloc);
-      xst1(SENT, rq, (tid < UB && n >= 2) ? sr * qb + (unsigned)((ci * U + cs * UB + tid) * 4) : OOB, coloc);
+      xstore1(fbits(s), rq, tid < UB ? so * qb + (unsigned)((ci * U + cs * UB + tid) * 4) : OOB, coloc);
+      xstore1(SENT, rq, (tid < UB && n >= 2) ? sr * qb + (unsigned)((ci * U + cs * UB + tid) * 4) : OOB, coloc);
     }
     __syncthreads();          // blk read: the scratch is free for dq / carry
     SPB_STAMP(6);
@@ -1511,9 +1478,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
       SpinB g;
       g.start();
       for (;;) {
-        v0 = xld4(rq, so * qb + (unsigned)(q0 * 16));
-        v1 = xld4(rq, so * qb + (unsigned)(q1 * 16));
-        vc = xld4(rk, coff);
+        v0 = xload(rq, so * qb + (unsigned)(q0 * 16));
+        v1 = xload(rq, so * qb + (unsigned)(q1 * 16));
+        vc = xload(rk, coff);
         bool ok = !has_sentinel(v0) && !has_sentinel(v1);
         if (cthr) {      // only the words of my units count (UW may not fill the last piece)
           const int nw = min(4, UW - 4 * cpc);
@@ -1570,7 +1537,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
           if (DROP && p.keep < 1.f) dho *= p.dscale[sidx];      // (the forward call's scale factors, [L, B, U])
           const float dh = dho + chs[grow * 16 + gu];          // + the recurrent carry (not dropped)
           const float cnew = p.Cs[sidx + (size_t)B * U], cprev = p.Cs[sidx];
-          const float tc = ftanh(cnew);
+          const float tc = fast_tanh(cnew);
           const float dct = dc_state + dh * go * (1.f - tc * tc);
           dzv = gg == 0 ? dct * gj * gi * (1.f - gi)
               : gg == 1 ? dct * gi * (1.f - gj * gj)
@@ -1580,8 +1547,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
         }
       }
       dz_last = dzv;
-      xst1(fbits(dzv), rz, gate_thr ? so * zb + (unsigned)((grow * 4 * U + gg * U + gunit) * 4) : OOB, coloc);
-      xst1(SENT, rz, (gate_thr && n >= 2) ? sr * zb + (unsigned)((grow * 4 * U + gg * U + gunit) * 4) : OOB, coloc);
+      xstore1(fbits(dzv), rz, gate_thr ? so * zb + (unsigned)((grow * 4 * U + gg * U + gunit) * 4) : OOB, coloc);
+      xstore1(SENT, rz, (gate_thr && n >= 2) ? sr * zb + (unsigned)((grow * 4 * U + gg * U + gunit) * 4) : OOB, coloc);
     }
     __syncthreads();          // dqs / qred read: the scratch is free for the staged dz
     SPB_STAMP(8);
@@ -1608,7 +1575,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
           bool ok = true;
 #pragma unroll
           for (int i = 0; i < NQ; ++i) {
-            v[i] = xld4(rz, off[i]);
+            v[i] = xload(rz, off[i]);
             ok = ok && !has_sentinel(v[i]);
           }
           if (__all(ok)) break;
@@ -1665,8 +1632,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NW / 4, NW /
       const bool pub = tid < R * NC;
       if (pub) s = (ored[((size_t)0 * NC + col) * 4 + row] + ored[((size_t)1 * NC + col) * 4 + row]) +
                    (ored[((size_t)2 * NC + col) * 4 + row] + ored[((size_t)3 * NC + col) * 4 + row]);
-      xst1(fbits(s), rk, pub ? so * kb + (unsigned)((row * (E + U) + NC * slot + col) * 4) : OOB, coloc);
-      xst1(SENT, rk, (pub && n >= 2) ? sr * kb + (unsigned)((row * (E + U) + NC * slot + col) * 4) : OOB, coloc);
+      xstore1(fbits(s), rk, pub ? so * kb + (unsigned)((row * (E + U) + NC * slot + col) * 4) : OOB, coloc);
+      xstore1(SENT, rk, (pub && n >= 2) ? sr * kb + (unsigned)((row * (E + U) + NC * slot + col) * 4) : OOB, coloc);
     }
     SPB_STAMP(10);
     __syncthreads();
@@ -1741,17 +1708,10 @@ static bool device_fits() {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return false; }
   if (dev != cached_dev) {
-    int cus = 0, xcc = 0, lds = 0;
-    bool ok = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus >= NU * P;
-    ok = ok && hipDeviceGetAttribute(&xcc, hipDeviceAttributeNumberOfXccs, dev) == hipSuccess && xcc == NU;
-    // the runtime reports the LDS a block may use under one of these names depending on its version
-    const hipDeviceAttribute_t names[3] = {hipDeviceAttributeMaxSharedMemoryPerBlock, hipDeviceAttributeSharedMemPerBlockOptin,
-                                           hipDeviceAttributeMaxSharedMemoryPerMultiprocessor};
-    for (hipDeviceAttribute_t n : names) {
-      int v = 0;
-      if (hipDeviceGetAttribute(&v, n, dev) == hipSuccess && v > lds) lds = v;
-    }
-    ok = ok && lds >= 160 * 1024 - 512;
+    const int cus = device_cus(), lds = device_lds_bytes();
+    int xcc = 0;
+    const bool ok = cus >= NU * P && hipDeviceGetAttribute(&xcc, hipDeviceAttributeNumberOfXccs, dev) == hipSuccess && xcc == NU &&
+                    lds >= 160 * 1024 - 512;
     (void)hipGetLastError();
     if (getenv("NABU_PERSIST_DEBUG")) fprintf(stderr, "nabu: persistent decoder device check: %d CUs, %d XCCs, %d B LDS -> %s\n", cus, xcc, lds, ok ? "fits" : "step chain");
     cached = ok;
@@ -1878,8 +1838,7 @@ int speller_persist_bwd(const SpPersistDesc &d, const int32_t *dec_len, const in
   a.xbuf = static_cast<char *>(ws) + TABLE_BYTES;
   a.status = status;
   a.timeout_ticks = lstm_persist_timeout_ticks();
-  const char *e = getenv("NABU_PERSIST_DEBUG");
-  a.dbg = e ? atoi(e) : 0;
+  a.dbg = env_int("NABU_PERSIST_DEBUG", 0);
   const size_t lds = bwd_lds_floats(d, a.stream_vals != 0) * 4;
   const bool ks4 = bwd_ks4(d), drop = d.keep_prob < 1.f;
   auto kern = ks4 ? speller_persist_bwd_kernel<3, 128, 4, 8, false, false> : speller_persist_bwd_kernel<3, 8, 16, 8, false, false>;
@@ -1888,8 +1847,7 @@ int speller_persist_bwd(const SpPersistDesc &d, const int32_t *dec_len, const in
     kern = ks4 ? speller_persist_bwd_kernel<3, 128, 4, 1, false, true> : speller_persist_bwd_kernel<3, 8, 16, 1, false, true>;
     if (drop) kern = ks4 ? speller_persist_bwd_kernel<3, 128, 4, 1, true, true> : speller_persist_bwd_kernel<3, 8, 16, 1, true, true>;
   }
-  // per call: the attribute is per device, a cache keyed by the function alone would miss a second device
-  NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
+  NABU_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 160 * 1024 - 512));
   // 32 utterances per launch (4 per XCD): a batch of 64 runs as two launches on the stream
   for (int b0 = 0; b0 < d.B; b0 += NU * R) {
     a.b0 = b0;
@@ -1941,8 +1899,7 @@ int speller_persist_fwd(const SpPersistDesc &d, const int32_t *dec_len, const in
   a.xbuf = static_cast<char *>(ws) + TABLE_BYTES;
   a.status = status;
   a.timeout_ticks = lstm_persist_timeout_ticks();
-  const char *e = getenv("NABU_PERSIST_DEBUG");
-  a.dbg = e ? atoi(e) : 0;
+  a.dbg = env_int("NABU_PERSIST_DEBUG", 0);
   const size_t lds = lds_floats(d, a.FS, a.stream_vals != 0) * 4;
   const int KW = (d.E + d.U) / NW;
   const bool loc = d.kind == 1;
@@ -1952,7 +1909,7 @@ int speller_persist_fwd(const SpPersistDesc &d, const int32_t *dec_len, const in
   if (reg)
     kern = loc ? (KW <= 64 ? speller_persist_fwd_kernel<64, true, true> : KW <= 192 ? speller_persist_fwd_kernel<192, true, true> : speller_persist_fwd_kernel<384, true, true>)
                : (KW <= 64 ? speller_persist_fwd_kernel<64, false, true> : KW <= 192 ? speller_persist_fwd_kernel<192, false, true> : speller_persist_fwd_kernel<384, false, true>);
-  NABU_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
+  NABU_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 160 * 1024 - 512));
   if (reg) {
     // every random number of the call in one small launch in front of it (the Philox rounds cost the decoder kernels
     // registers they do not have: 114 spilled in the hot loops with the generator inside)

@@ -141,10 +141,6 @@ SpReserve sp_reserve(const SpGeo &g) {
 
 // ---------------------------------------------------------------------------
 // THE PLAN (speller_plan.h)
-int env_int(const char *name, int dflt) {
-  const char *e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
 // shapes gemm_skinny_fused takes: C[M,N] = A·B + A2·B2 in ONE launch with the split-K reduction inside it
 bool fused_shape(int M, int N, int K1, int lda, int K2, int lda2) {
   return M <= 64 && N % 32 == 0 && K1 > 0 && K1 % 64 == 0 && K2 % 64 == 0 && lda % 4 == 0 && (K2 == 0 || lda2 % 4 == 0);

@@ -38,12 +38,14 @@ K_NLL = 16.0
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# which kernel nabu_ctc_loss_grad takes (csrc/ctc.hip: ctc_wave_lds_bytes and the dispatch condition; held to the
-# source text by tests/test_ctc_cases.py::test_lds_formula_is_the_one_in_the_source)
+# which kernel nabu_ctc_loss_grad takes (csrc/ctc.hip: ctc_wave_lds_bytes and the dispatch condition) and from which
+# request on its launch raises the LDS attribute (csrc/common.hip: ensure_dynamic_lds, behind launch_lds); held to the
+# source text by tests/test_ctc_cases.py::test_lds_formula_is_the_one_in_the_source
 WAVE_LDS_FORMULA = ('((size_t)T * C + (size_t)T * Smax + C + 64 + 2 + 3 * 64 + 3 * (size_t)C) * sizeof(float) '
                     '+ (128 + 2) * sizeof(int)')
 WAVE_DISPATCH = '!force_wg && Lmax <= 63 && wshm <= 150 * 1024'
-WAVE_ATTR = 'wshm > 64 * 1024'
+WAVE_ATTR = 'if (bytes > 64 * 1024) {'
+WAVE_LAUNCH = 'return launch_lds(ctc_wave_kernel, dim3(B), dim3(256), wshm, s, p);'
 
 
 def wave_lds_bytes(T, C, Lmax):

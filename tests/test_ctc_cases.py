@@ -17,8 +17,13 @@ IDS = [e['id'] for e in cc.CASES]
 def test_lds_formula_is_the_one_in_the_source():
     """which kernel a shape reaches is decided in csrc/ctc.hip; ctc_cases restates it — hold the two together"""
     src = open(os.path.join(ROOT, 'nabu_amd', 'csrc', 'ctc.hip')).read()
-    for text in (cc.WAVE_LDS_FORMULA, cc.WAVE_DISPATCH, cc.WAVE_ATTR):
+    for text in (cc.WAVE_LDS_FORMULA, cc.WAVE_DISPATCH, cc.WAVE_LAUNCH):
         assert text in src, text
+    # the launch helper raises the attribute above 64 KiB and not below
+    helper = open(os.path.join(ROOT, 'nabu_amd', 'csrc', 'common.hip')).read()
+    assert cc.WAVE_ATTR in helper and 'hipFuncSetAttribute' not in src
+    raise_at, set_at = helper.index(cc.WAVE_ATTR), helper.index('hipFuncSetAttribute(')
+    assert helper.count('hipFuncSetAttribute(') == 1 and raise_at < set_at < helper.index('\n  }\n', raise_at)
     assert (cc.T64, cc.T150) == (98, 235)
     assert cc.wave_lds_bytes(cc.T64, 40, 60) <= 64 * 1024 < cc.wave_lds_bytes(cc.T64 + 1, 40, 60)
     assert cc.wave_lds_bytes(cc.T150, 40, 60) <= 150 * 1024 < cc.wave_lds_bytes(cc.T150 + 1, 40, 60)

@@ -214,8 +214,9 @@ def test_persistent_decoder_forward(U, E, Te):
 def test_persistent_decoder_with_saturated_gates(attention, K, F):
     """the decoder cell's bias holds, for each gate on ten units of its own, -88, -89, -104, -300, -690 and the same
     positive (tests/test_hip_recurrence_range.py, case a): below -88.73 exp(-z) is inf in float32, and the persistent
-    kernels' sigmoid (fsig: a Newton step behind v_rcp_f32) made NaN of it where the step chain's division gives 0 —
-    logits, loss and every gradient against the oracle at check_speller's tolerances, on the persistent kernels"""
+    kernels' sigmoid (fast_sigmoid: a Newton step behind v_rcp_f32) made NaN of it where the step chain's division
+    gives 0 — logits, loss and every gradient against the oracle at check_speller's tolerances, on the persistent
+    kernels"""
     import ctypes
     from nabu_amd import _hip, ops as hip
     from nabu_amd.neuralnetworks.models.ed_decoders import rnn_decoder
