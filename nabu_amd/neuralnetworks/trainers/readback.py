@@ -1,9 +1,11 @@
-"""The lagged read-back of the overlapped training loop (Trainer._train_overlapped).
+"""When Trainer.train() reads a step's words from the device: at once (ReadNow, the reference's loop) or one step late
+(ReadLate, prefetch_batches >= 1).
 
-What the synchronous loop reads from the device after every step — the loss, one status word per CTC kernel
+What the loop reads from the device after every step — the loss, one status word per CTC kernel
 (loss_functions.pending_status) and the status word of every persistent-kernel workspace (ops.check_persist_status) —
-lands in ONE pinned record per step: a few asynchronous copies on the launch stream, closed by an event.  The record of
-step s is read after step s + 1 has been enqueued, so the host never waits for the step it has just launched."""
+lands, for the late read, in ONE pinned record per step: a few asynchronous copies on the launch stream, closed by an
+event.  The record of step s is read after step s + 1 has been enqueued, so the host never waits for the step it has
+just launched."""
 import numpy as np
 import torch
 
@@ -57,3 +59,44 @@ class StepRecord(object):
                 err = hip.persist_status_error(tag, int(code))
                 raise type(err)('%s [step %d]' % (err, self.step))
         return float(words[0:1].view(np.float32)[0])
+
+
+class ReadNow(object):
+    '''lag 0: a step's status words are checked and its loss is read as soon as the step is enqueued.  `reduce(loss)`
+    is the loss summed over the replicas (the status check precedes that collective), `report(step, loss_sum, lr,
+    start)` takes what was read.'''
+    lag = 0
+
+    def __init__(self, reduce, report):
+        self.reduce, self.report = reduce, report
+
+    def push(self, step, loss, lr, start):
+        loss_functions.check_status()
+        self.report(step, float(self.reduce(loss).item()), lr, start)
+
+    def drain(self, keep=0):
+        pass
+
+
+class ReadLate(ReadNow):
+    '''lag 1: push() enqueues the copies of a step's words into a StepRecord, drain(keep) reads and reports all but the
+    latest `keep` records — the loop keeps one while it runs and none before a validation point, before a checkpoint
+    and at the end.  A non-zero status word raises when its record is read, naming its step.'''
+    lag = 1
+
+    def __init__(self, reduce, report, pinned):
+        ReadNow.__init__(self, reduce, report)
+        self.pinned, self.pending, self.spare = pinned, [], []     # records not read yet / read and free to reuse
+
+    def push(self, step, loss, lr, start):
+        loss = self.reduce(loss)
+        rec = self.spare.pop() if self.spare else StepRecord(pinned=self.pinned)
+        rec.fill(step, loss, loss_functions.take_pending_status(), hip.persist_workspaces())
+        rec.lr, rec.start = lr, start
+        self.pending.append(rec)
+
+    def drain(self, keep=0):
+        while len(self.pending) > keep:
+            rec = self.pending.pop(0)
+            self.report(rec.step, rec.read(), rec.lr, rec.start)
+            self.spare.append(rec)

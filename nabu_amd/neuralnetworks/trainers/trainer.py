@@ -26,7 +26,11 @@ underneath:
     (``allreduce_buckets = True``, an extension key; default False): the same sum
     exchanged as one bucket per encoder layer (+ one for the decoder), each started
     as soon as its gradients are final and overlapped with the dense products of the
-    next layer's backward pass — never with a persistent recurrent kernel."""
+    next layer's backward pass — never with a persistent recurrent kernel;
+  * ``train()`` is ONE loop around ``step`` / ``step_accumulated`` (one body, ``_run_update``, and one ``_update`` for
+    every A and every exchange).  Two small objects say where a device batch comes from (DirectFeed | AheadFeed) and
+    when a step's words are read (readback.ReadNow | ReadLate); ``prefetch_batches`` >= 1 (an extension key,
+    DESIGN.md section 8) selects the second of each."""
 import math
 import sys
 import os
@@ -40,7 +44,7 @@ import torch
 from nabu_amd import ops as hip
 from nabu_amd.autodiff import Tape, SeqLen
 from nabu_amd.neuralnetworks.models.model import Model
-from nabu_amd.neuralnetworks.trainers import loss_functions
+from nabu_amd.neuralnetworks.trainers import loss_functions, readback
 from nabu_amd.tools.default_conf import apply_defaults, defaults_path
 
 ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-8      # tf.train.AdamOptimizer defaults
@@ -137,6 +141,40 @@ class ValidationSaveHook(object):
         self.trainer.load_state(self._mem)
 
 
+class DirectFeed(object):
+    '''the batches of an update, read and uploaded on the loop's thread when the update asks for them'''
+
+    def __init__(self, trainer):
+        self.trainer = trainer
+
+    def batches(self, first, n):
+        tr = self.trainer
+        return [tr.to_device(tr.data.batch(first + j * tr.world)) for j in range(n)]
+
+    def close(self):
+        pass
+
+
+class AheadFeed(DirectFeed):
+    '''the same batches staged by a BatchPrefetcher (Trainer.stage on its threads, `depth` ahead of the loop), uploaded
+    with one copy and unpacked by one launch (Trainer.to_device_staged)'''
+
+    def __init__(self, trainer, first, depth, pinned):
+        from nabu_amd.processing.prefetch import BatchPrefetcher, PinnedRing
+        DirectFeed.__init__(self, trainer)
+        trainer._prefetcher = self.prefetcher = BatchPrefetcher(
+            trainer.data, first, trainer.world, depth, int(trainer.conf.get('prefetch_workers', 2)), trainer.stage,
+            PinnedRing(depth + 1) if pinned else None)
+
+    def batches(self, first, n):
+        if self.prefetcher.next_step != first:                  # a go-back restored an earlier global step
+            self.prefetcher.reset(first)
+        return [self.trainer.to_device_staged(self.prefetcher.get()) for _ in range(n)]
+
+    def close(self):
+        self.prefetcher.close()
+
+
 class Trainer(object, metaclass=ABCMeta):
     '''General class outlining the training environment of a model.'''
 
@@ -161,6 +199,7 @@ class Trainer(object, metaclass=ABCMeta):
         self.evaluatorconf = evaluatorconf
         self.expdir = expdir
         self.server = server
+        self.world = server.world_size if server is not None else 1
         self.task_index = task_index
         if 'norm_constraint' in self.conf and self.conf['norm_constraint'] != 'None':
             raise Exception('norm_constraint (MaxNorm) is off by default in the reference '
@@ -180,7 +219,7 @@ class Trainer(object, metaclass=ABCMeta):
         self.weight_noise, self.weight_noise_start_step = weight_noise_keys(self.conf)
         self.flat_clean = self.noise_table = None
         # numbatches_to_aggregate: A batches per replica and update (1: the plain step), validated here as well
-        self.accumulate = aggregate_key(self.conf, server.world_size if server is not None else 1)
+        self.accumulate = aggregate_key(self.conf, self.world)
         self.flat_acc = None               # the sum of an update's clipped micro-batch gradients (allocated when A > 1)
         self._micro = 0                    # micro-batches of the current update already in flat_acc
         self.last_weight_noise = None      # the (seed, offset) of the latest noisy step
@@ -191,9 +230,8 @@ class Trainer(object, metaclass=ABCMeta):
             # recurrent kernels need every CU of the device for their own workgroups, two processes' launches would each
             # hold a part of it and spin into the bounded time-out — decided HERE, where the process group is known, for
             # every layer this process builds (training and validation alike)
-            from nabu_amd import ops as _hip_ops
             from nabu_amd.neuralnetworks.components import layer as _layer
-            _layer.LSTM_MODE[0] = _hip_ops.LSTM_STEPWISE
+            _layer.LSTM_MODE[0] = hip.LSTM_STEPWISE
         self._graph = None
         self.schedule_log = None       # a list here records the bucketed exchange: (bucket key, 'hook' | 'final')
 
@@ -212,7 +250,6 @@ class Trainer(object, metaclass=ABCMeta):
         if self.accumulate > 1:            # updates, A batches each: the data seen stays that of num_epochs
             outputs['num_steps'] = max(1, outputs['num_steps'] // self.accumulate)
         self.loss_fn = loss_functions.factory(self.conf['loss'], self.label_smoothing)
-        self.world = self.server.world_size if self.server is not None else 1
         self.flat = self.flat_grad = self.adam_m = self.adam_v = None
         self.buckets = None
         # validation part (reference trainer.py:189-265): bookkeeping 'variables' of the
@@ -268,7 +305,6 @@ class Trainer(object, metaclass=ABCMeta):
         from nabu_amd.processing import input_pipeline
         input_names = [n for n in self.model.conf.get('io', 'inputs').split(' ') if n]
         target_names = [n for n in self.conf['targets'].split(' ') if n]
-        world = self.server.world_size if self.server is not None else 1
         return input_pipeline.from_sections(
             d, input_names, [self.conf[i].split(' ') for i in input_names],
             target_names, [self.conf[o].split(' ') for o in target_names],
@@ -305,26 +341,11 @@ class Trainer(object, metaclass=ABCMeta):
         '''one training update on a device batch; returns the loss as a 1-element
         device tensor (no host synchronisation)'''
         self._create_graph()
-        if self.weight_noise > 0 and self.global_step >= self.weight_noise_start_step:
-            self._add_weight_noise(batch)
-        try:
-            with Tape() as tape:
-                logits, logit_seq_length = self.model(
-                    inputs=batch['inputs'], input_seq_length=batch['input_seq_length'],
-                    targets=batch['targets'], target_seq_length=batch['target_seq_length'],
-                    is_training=True)
-                loss = self.loss_fn(batch['targets'], logits, logit_seq_length, batch['target_seq_length'])
-                extra = self.aditional_loss()
-                if extra is not None:
-                    loss = hip.axpy_(loss, extra)
-            if self.flat is None:
-                self._init_optimizer()
-            self._backward_and_update(tape, loss)
-        finally:
-            if self._noisy:            # raised between the noise launch and the optimiser: back to the clean parameters
-                self._noisy = False
-                self.flat.copy_(self.flat_clean)
-        return loss
+        if self.accumulate > 1:
+            raise ValueError('step takes one batch per update; this trainer takes %d (numbatches_to_aggregate = %s with '
+                             '%d replicas): call step_accumulated()'
+                             % (self.accumulate, self.conf['numbatches_to_aggregate'], self.world))
+        return self._run_update([batch])
 
     def step_accumulated(self, batches):
         '''one training update on numbatches_to_aggregate / replicas = A device batches (A > 1), taken one after another:
@@ -342,28 +363,39 @@ class Trainer(object, metaclass=ABCMeta):
                                                     len(batches)))
         if self._micro:
             raise Exception('an update is under way (%d micro-batches accumulated)' % self._micro)
+        return self._run_update(batches)
+
+    def _forward_loss(self, batch):
+        '''the forward pass and the loss of one device batch -> (tape, loss)'''
+        with Tape() as tape:
+            logits, logit_seq_length = self.model(
+                inputs=batch['inputs'], input_seq_length=batch['input_seq_length'],
+                targets=batch['targets'], target_seq_length=batch['target_seq_length'],
+                is_training=True)
+            loss = self.loss_fn(batch['targets'], logits, logit_seq_length, batch['target_seq_length'])
+            extra = self.aditional_loss()
+            if extra is not None:
+                loss = hip.axpy_(loss, extra)
+        return tape, loss
+
+    def _run_update(self, batches):
+        '''the body of step ([batch]) and step_accumulated (A batches): every batch but the last accumulates, the last
+        one updates (_backward_and_update); returns the loss, of several batches their mean'''
         if self.weight_noise > 0 and self.global_step >= self.weight_noise_start_step:
             self._add_weight_noise(batches[0])
         total = None
         try:
             for batch in batches:
-                with Tape() as tape:
-                    logits, logit_seq_length = self.model(
-                        inputs=batch['inputs'], input_seq_length=batch['input_seq_length'],
-                        targets=batch['targets'], target_seq_length=batch['target_seq_length'],
-                        is_training=True)
-                    loss = self.loss_fn(batch['targets'], logits, logit_seq_length, batch['target_seq_length'])
-                    extra = self.aditional_loss()
-                    if extra is not None:
-                        loss = hip.axpy_(loss, extra)
+                tape, loss = self._forward_loss(batch)
                 if self.flat is None:
                     self._init_optimizer()
-                self._backward_and_update(tape, loss)          # accumulates; the last one updates
-                total = loss if total is None else hip.axpy_(total, loss)
-            return hip.sum_(total, 1.0 / self.accumulate)
+                self._backward_and_update(tape, loss)
+                if len(batches) > 1:
+                    total = loss if total is None else hip.axpy_(total, loss)
+            return loss if total is None else hip.sum_(total, 1.0 / len(batches))
         finally:
             self._micro = 0            # (an exception: the partial sum is dropped, micro-batch 0 overwrites flat_acc)
-            if self._noisy:
+            if self._noisy:            # raised between the noise launch and the optimiser: back to the clean parameters
                 self._noisy = False
                 self.flat.copy_(self.flat_clean)
 
@@ -488,15 +520,20 @@ class Trainer(object, metaclass=ABCMeta):
                 continue
             if not everything and not all(id(v) in self._ready and id(v) in self._declared for v in b['vars']):
                 continue
-            view = self.flat_grad[b['start']:b['end']]
-            if self.accumulate > 1:        # the local sum of A clipped gradients, left in the gradient buffer
-                hip.clip_accumulate(view, self.flat_acc[b['start']:b['end']], view, CLIP)
-            else:
-                hip.clip_(view, CLIP)
-            self._works.append(self.server.all_reduce_sum_async(view))
+            self._works.append(self.server.all_reduce_sum_async(self._clip_local(b['start'], b['end'])))
             self._sent.add(i)
             if self.schedule_log is not None:       # (bench.py / tests: which bucket went on the wire at which call)
                 self.schedule_log.append((b['key'], 'final' if everything else 'hook'))
+
+    def _clip_local(self, start, end):
+        '''what this replica sends of flat_grad[start:end], left there: the clipped gradient (clip per replica, before the
+        aggregation), with A > 1 the local sum of A clipped gradients; returns the view'''
+        view = self.flat_grad[start:end]
+        if self.accumulate > 1:
+            hip.clip_accumulate(view, self.flat_acc[start:end], view, CLIP)
+        else:
+            hip.clip_(view, CLIP)
+        return view
 
     def _join_comm(self):
         '''the launch stream waits for every exchange in flight (before a recurrent launch and
@@ -507,73 +544,48 @@ class Trainer(object, metaclass=ABCMeta):
                 w.wait()
 
     def _update(self):
-        '''clip + Adam (reference trainer.py:512-580), with the gradient exchange of
-        the data-parallel mode in between'''
-        if self.accumulate > 1:
-            return self._update_accumulated()
-        lr = self.learning_rate()
-        self.adam_step += 1
-        t = self.adam_step
-        lr_t = lr * math.sqrt(1.0 - ADAM_B2 ** t) / (1.0 - ADAM_B1 ** t)
-        if self.world > 1 and self.buckets is not None:
-            ev = self._allreduce_events()                        # exposed part of the exchange only
-            self._launch_ready_buckets(everything=True)
-            self._join_comm()
-            if ev is not None:
-                ev[1].record()
-            self._adam(lr_t, 1.0 / self.world)
-        elif self.world > 1:
-            hip.clip_(self.flat_grad, CLIP)                      # clip per replica ...
-            ev = self._allreduce_events()
-            self.server.all_reduce_sum_(self.flat_grad)          # ... sum over xGMI ...
-            if ev is not None:
-                ev[1].record()
-            self._adam(lr_t, 1.0 / self.world)                   # ... mean, Adam
-        else:
-            self._adam(lr_t, 1.0)
-        self.last_lr = lr
-
-    def _update_accumulated(self):
-        '''_update for the last of A > 1 micro-batches: flat_acc holds the first A - 1 clipped gradients, flat_grad the
-        last one as the backward pass left it.  One replica: ONE launch clips it, adds it and applies Adam.  Several:
-        the local sum is completed in flat_grad (per bucket by _launch_ready_buckets), exchanged ONCE, and Adam runs at
-        1 / (A * world): the mean of A * world clipped gradients, what A * world replicas compute.'''
+        '''clip + Adam (reference trainer.py:512-580) behind the last (without accumulation: the only) micro-batch of an
+        update, with the gradient exchange of the data-parallel mode in between.  flat_grad holds that micro-batch's
+        gradient as the backward pass left it, flat_acc the A - 1 clipped ones before it.  One replica: ONE launch clips,
+        adds and applies Adam.  Several: every replica completes its clipped local sum in flat_grad (_clip_local; per
+        bucket under the backward pass and here for the rest), the sums are exchanged ONCE, and Adam runs on
+        1 / (A * world) of the total: the mean of A * world clipped gradients, what A * world replicas compute.'''
         A = self.accumulate
         if self._micro != A - 1:
             raise Exception('the update needs %d accumulated micro-batches, %d are in' % (A - 1, self._micro))
         lr = self.learning_rate()
         self.adam_step += 1
-        t = self.adam_step
-        lr_t = lr * math.sqrt(1.0 - ADAM_B2 ** t) / (1.0 - ADAM_B1 ** t)
-        scale = 1.0 / (A * self.world)
+        lr_t = lr * math.sqrt(1.0 - ADAM_B2 ** self.adam_step) / (1.0 - ADAM_B1 ** self.adam_step)
+        acc = self.flat_acc if A > 1 else None
         if self.world > 1:
-            ev = self._allreduce_events()
-            if self.buckets is not None:
+            if self.buckets is None:
+                self._clip_local(0, self.flat_grad.numel())      # a local launch: outside the timed exchange
+            ev = self._allreduce_events()                        # exposed part of the exchange only
+            if self.buckets is None:
+                self.server.all_reduce_sum_(self.flat_grad)      # sum over xGMI
+            else:
                 self._launch_ready_buckets(everything=True)
                 self._join_comm()
-            else:
-                hip.clip_accumulate(self.flat_grad, self.flat_acc, self.flat_grad, CLIP)
-                self.server.all_reduce_sum_(self.flat_grad)
             if ev is not None:
                 ev[1].record()
-            self._adam(lr_t, scale)
-        else:
-            hip.adam_clip_step_acc(self.flat, self.flat_clean if self._noisy else None, self.flat_acc, self.flat_grad,
-                                   self.adam_m, self.adam_v, lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, CLIP, scale)
-            self._noisy = False
+            acc = None                                           # (in the exchanged sum)
+        self._adam(lr_t, 1.0 / (A * self.world), acc)
         self._micro = 0
         self.last_lr = lr
 
-    def _adam(self, lr_t, grad_scale):
-        '''the fused clip + Adam launch; after a noisy step (_add_weight_noise) the parameter is read from the clean
-        copy, so the noise leaves with the update and nothing has to be subtracted again'''
-        if self._noisy:
-            hip.adam_clip_step_from(self.flat, self.flat_clean, self.flat_grad, self.adam_m, self.adam_v, lr_t,
-                                    ADAM_B1, ADAM_B2, ADAM_EPS, CLIP, grad_scale)
-            self._noisy = False
+    def _adam(self, lr_t, scale, acc):
+        '''the fused clip + Adam launch on scale * flat_grad, with `acc` on scale * (acc + clip(flat_grad)); after a noisy
+        step (_add_weight_noise) the parameter is read from the clean copy, so the noise leaves with the update and
+        nothing has to be subtracted again'''
+        src = self.flat_clean if self._noisy else None
+        rest = (self.adam_m, self.adam_v, lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, CLIP, scale)
+        if acc is not None:
+            hip.adam_clip_step_acc(self.flat, src, acc, self.flat_grad, *rest)
+        elif src is not None:
+            hip.adam_clip_step_from(self.flat, src, self.flat_grad, *rest)
         else:
-            hip.adam_clip_step(self.flat, self.flat_grad, self.adam_m, self.adam_v, lr_t,
-                               ADAM_B1, ADAM_B2, ADAM_EPS, CLIP, grad_scale)
+            hip.adam_clip_step(self.flat, self.flat_grad, *rest)
+        self._noisy = False
 
     def _allreduce_events(self):
         '''bench.py sets ``time_allreduce``: a pair of events on the launch stream around the
@@ -682,52 +694,64 @@ class Trainer(object, metaclass=ABCMeta):
             self._ensure_variables()
             self.load_state(torch.load(ckpt, weights_only=False))
             print('WORKER %d: resumed from %s at step %d' % (self.task_index, ckpt, self.global_step))
-        if int(self.conf.get('prefetch_batches', 0)) > 0:      # extension key: batches staged ahead, losses read one step late
-            return self._train_overlapped(num_steps, ckpt, history, int(self.conf['prefetch_batches']))
-        last_ckpt = time.time()
-        while self.global_step < num_steps:
-            if (self.evaluator is not None
-                    and self.global_step - self.validated_step >= int(self.conf['valid_frequency'])):
-                self._ensure_variables()
-                if self._validation_point():
-                    break
-            start = time.time()
-            # each replica reads its own shard of the epoch (replaces the shared
-            # filename queue on ps:0, trainer.py:342-351)
-            if self.accumulate == 1:
-                batch = self.to_device(self.data.batch(self.global_step * self.world + self.task_index))
-                loss = self.step(batch)
-            else:
-                # update s, micro-batch j, rank r: batch (s * A + j) * world + r, what A * world replicas read
-                first = self.global_step * self.accumulate * self.world + self.task_index
-                loss = self.step_accumulated([self.to_device(self.data.batch(first + j * self.world))
-                                              for j in range(self.accumulate)])
-            loss_functions.check_status()
-            if self.world > 1:
-                loss = self.server.all_reduce_sum_(loss.clone())
-                loss_value = float(loss.item()) / self.world
-            else:
-                loss_value = float(loss.item())
-            on_gpu = torch.cuda.is_available()
+        on_gpu = torch.cuda.is_available()
+        mem_total = torch.cuda.get_device_properties(torch.cuda.current_device()).total_memory if on_gpu else 0
+
+        def shard():
+            # each replica reads its own shard of the epoch (replaces the shared filename queue on ps:0,
+            # trainer.py:342-351).  Update s, micro-batch j, rank r: batch (s * A + j) * world + r, what A * world
+            # replicas read; this is the first of update global_step, the others follow `world` apart
+            return self.global_step * self.accumulate * self.world + self.task_index
+
+        def reduce(loss):
+            return self.server.all_reduce_sum_(loss.clone()) if self.world > 1 else loss
+
+        def report(step, loss_sum, lr, start):
+            loss_value = loss_sum / self.world
             mem_used = torch.cuda.max_memory_allocated() if on_gpu else 0
-            mem_total = torch.cuda.get_device_properties(0).total_memory if on_gpu else 0
             print(('WORKER %d: step %d/%d loss: %f, learning rate: %f \n\t time elapsed: %f sec'
                    '\n\t peak memory usage: %d/%d MB')
-                  % (self.task_index, self.global_step, num_steps, loss_value, self.last_lr,
-                     time.time() - start, mem_used / 1e6, mem_total / 1e6))
-            history.append((self.global_step, loss_value, self.last_lr))
-            self.global_step += 1
-            every = getattr(self, 'checkpoint_steps', None)
-            if is_chief and ckpt is not None and (
-                    time.time() - last_ckpt > CHECKPOINT_SECS or (every and self.global_step % every == 0)):
-                self.save_checkpoint(ckpt)
-                last_ckpt = time.time()
+                  % (self.task_index, step, num_steps, loss_value, lr, time.time() - start, mem_used / 1e6,
+                     mem_total / 1e6))
+            history.append((step, loss_value, lr))
+
+        # the reference's loop reads a batch when the step asks for it and the loss at once; the extension key
+        # prefetch_batches = N >= 1 has batches staged N ahead and reads a step's words one step late (DESIGN.md
+        # section 8): history, validation decisions and checkpoints are the same, an infeasible CTC batch or a
+        # persistent kernel's time-out raises one iteration late, naming its step
+        depth = int(self.conf.get('prefetch_batches', 0))
+        feed = AheadFeed(self, shard(), depth, on_gpu) if depth > 0 else DirectFeed(self)
+        reader = readback.ReadLate(reduce, report, on_gpu) if depth > 0 else readback.ReadNow(reduce, report)
+        last_ckpt = time.time()
+        try:
+            while self.global_step < num_steps:
+                if (self.evaluator is not None
+                        and self.global_step - self.validated_step >= int(self.conf['valid_frequency'])):
+                    reader.drain()
+                    self._ensure_variables()
+                    if self._validation_point():
+                        break
+                start = time.time()
+                batches = feed.batches(shard(), self.accumulate)
+                loss = self.step(batches[0]) if self.accumulate == 1 else self.step_accumulated(batches)
+                reader.push(self.global_step, loss, self.last_lr, start)
+                self.global_step += 1
+                reader.drain(reader.lag)                        # with a lag: read step s now that step s + 1 is enqueued
+                every = getattr(self, 'checkpoint_steps', None)
+                if is_chief and ckpt is not None and (
+                        time.time() - last_ckpt > CHECKPOINT_SECS or (every and self.global_step % every == 0)):
+                    reader.drain()
+                    self.save_checkpoint(ckpt)
+                    last_ckpt = time.time()
+            reader.drain()
+        finally:
+            feed.close()
         if is_chief and self.expdir is not None:
             self.save_checkpoint(ckpt)
             self.save()
         return history
 
-    # ------------------------------------------------- overlapped loop (prefetch_batches >= 1)
+    # ------------------------------------------------- staged batches (prefetch_batches >= 1)
     def stage(self, batch, slot=None):
         '''numpy batch -> packed batch (processing/prefetch.py), written into the pinned `slot` when one is given.
         Runs on a prefetcher thread: no device call in here.'''
@@ -759,82 +783,6 @@ class Trainer(object, metaclass=ABCMeta):
         for i in range(0, len(segs), 8):                  # NABU_BATCH_MAX_SEGS per launch
             hip.batch_unpack(segs[i:i + 8], packed, n)
         return out
-
-    def _train_overlapped(self, num_steps, ckpt, history, depth):
-        '''train()'s loop with the host work taken off the step's critical path: batches come staged from a
-        BatchPrefetcher (`depth` ahead), are uploaded with one copy and unpacked by one launch, and the loss and
-        status words of step s are read after step s + 1 has been enqueued (trainers/readback.py); with
-        numbatches_to_aggregate a step is an update of A batches and its record holds the status words of all of them.
-        Pending records
-        are drained before every validation point, before every checkpoint and at the end, so history, validation
-        decisions and checkpoints are those of the synchronous loop; an infeasible CTC batch or a persistent kernel's
-        time-out raises one iteration late, naming its step.'''
-        from nabu_amd.processing.prefetch import BatchPrefetcher, PinnedRing
-        from nabu_amd.neuralnetworks.trainers.readback import StepRecord
-        is_chief = self.task_index == 0
-        on_gpu = torch.cuda.is_available()
-        pending, spare = [], []                # records enqueued and not read yet / read and free to reuse
-
-        def finish(rec):
-            loss_value = rec.read() / self.world
-            mem_used = torch.cuda.max_memory_allocated() if on_gpu else 0
-            mem_total = torch.cuda.get_device_properties(0).total_memory if on_gpu else 0
-            print(('WORKER %d: step %d/%d loss: %f, learning rate: %f \n\t time elapsed: %f sec'
-                   '\n\t peak memory usage: %d/%d MB')
-                  % (self.task_index, rec.step, num_steps, loss_value, rec.lr,
-                     time.time() - rec.start, mem_used / 1e6, mem_total / 1e6))
-            history.append((rec.step, loss_value, rec.lr))
-            spare.append(rec)
-
-        def drain(keep=0):
-            while len(pending) > keep:
-                finish(pending.pop(0))
-
-        def shard():                          # the first batch of update global_step (A batches each, `world` apart)
-            return self.global_step * self.accumulate * self.world + self.task_index
-
-        self._prefetcher = BatchPrefetcher(self.data, shard(), self.world, depth,
-                                           int(self.conf.get('prefetch_workers', 2)), self.stage,
-                                           PinnedRing(depth + 1) if on_gpu else None)
-        try:
-            last_ckpt = time.time()
-            while self.global_step < num_steps:
-                if (self.evaluator is not None
-                        and self.global_step - self.validated_step >= int(self.conf['valid_frequency'])):
-                    drain()
-                    self._ensure_variables()
-                    if self._validation_point():
-                        break
-                if self._prefetcher.next_step != shard():      # a go-back restored an earlier global step
-                    self._prefetcher.reset(shard())
-                start = time.time()
-                if self.accumulate == 1:
-                    batch = self.to_device_staged(self._prefetcher.get())
-                    loss = self.step(batch)
-                else:
-                    loss = self.step_accumulated([self.to_device_staged(self._prefetcher.get())
-                                                  for _ in range(self.accumulate)])
-                if self.world > 1:
-                    loss = self.server.all_reduce_sum_(loss.clone())
-                rec = spare.pop() if spare else StepRecord(pinned=on_gpu)
-                rec.fill(self.global_step, loss, loss_functions.take_pending_status(), hip.persist_workspaces())
-                rec.lr, rec.start = self.last_lr, start
-                pending.append(rec)
-                self.global_step += 1
-                drain(keep=1)                                   # read step s now that step s + 1 is enqueued
-                every = getattr(self, 'checkpoint_steps', None)
-                if is_chief and ckpt is not None and (
-                        time.time() - last_ckpt > CHECKPOINT_SECS or (every and self.global_step % every == 0)):
-                    drain()
-                    self.save_checkpoint(ckpt)
-                    last_ckpt = time.time()
-            drain()
-        finally:
-            self._prefetcher.close()
-        if is_chief and self.expdir is not None:
-            self.save_checkpoint(ckpt)
-            self.save()
-        return history
 
     def save_checkpoint(self, path):
         os.makedirs(os.path.dirname(path), exist_ok=True)
