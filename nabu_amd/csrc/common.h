@@ -125,6 +125,10 @@ __device__ __forceinline__ float wave_max_unrolled(float v) {
   return v;
 }
 
+// relu that keeps NaN (fmaxf returns the non-NaN operand: a diverged pre-activation would become an ordinary zero and the
+// layer norm behind it finite numbers); every other value is fmaxf(x, 0)'s, bit for bit
+__device__ __forceinline__ float relu_value(float x) { return x != x ? x : fmaxf(x, 0.f); }
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 // tanh through one exp: 2*sigmoid(2x)-1 (abs error ~1e-7)
 __device__ __forceinline__ float tanhf_(float x) { return 2.0f / (1.0f + __expf(-2.0f * x)) - 1.0f; }

@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void relu_ln_fwd_kernel(int N, int F, const fl
     v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (q < F4) {
       const float4 a = zr[q];
-      v[i] = make_float4(fmaxf(a.x, 0.f), fmaxf(a.y, 0.f), fmaxf(a.z, 0.f), fmaxf(a.w, 0.f));
+      v[i] = make_float4(relu_value(a.x), relu_value(a.y), relu_value(a.z), relu_value(a.w));
       s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
   }
@@ -165,8 +165,8 @@ __global__ __launch_bounds__(64) void relu_ln_bwd_kernel(int N, int F, const flo
       if (q < F4) {
         zv[i] = zr[q];
         const float4 d = dr[q], g = g4[q];
-        const float4 xh = make_float4((fmaxf(zv[i].x, 0.f) - mu) * rs, (fmaxf(zv[i].y, 0.f) - mu) * rs,
-                                      (fmaxf(zv[i].z, 0.f) - mu) * rs, (fmaxf(zv[i].w, 0.f) - mu) * rs);
+        const float4 xh = make_float4((relu_value(zv[i].x) - mu) * rs, (relu_value(zv[i].y) - mu) * rs,
+                                      (relu_value(zv[i].z) - mu) * rs, (relu_value(zv[i].w) - mu) * rs);
         ag[i].x += d.x * xh.x; ag[i].y += d.y * xh.y; ag[i].z += d.z * xh.z; ag[i].w += d.w * xh.w;
         ab[i].x += d.x; ab[i].y += d.y; ab[i].z += d.z; ab[i].w += d.w;
         gv[i] = make_float4(d.x * g.x, d.y * g.y, d.z * g.z, d.w * g.w);

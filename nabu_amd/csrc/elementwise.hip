@@ -336,7 +336,7 @@ __global__ __launch_bounds__(256) void axpy_kernel(size_t n, float a, const floa
 
 __global__ __launch_bounds__(256) void relu_kernel(size_t n, const float *__restrict__ x, float *__restrict__ y) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
-    y[i] = fmaxf(x[i], 0.f);
+    y[i] = relu_value(x[i]);
 }
 __global__ __launch_bounds__(256) void relu_bwd_kernel(size_t n, const float *__restrict__ y,
                                                        const float *__restrict__ dy, float *__restrict__ dx) {

@@ -1651,10 +1651,11 @@ __global__ __launch_bounds__(256) void permute_gates_kernel(int R, int U, const 
 // dst[r][c] += src[r][c] for row-strided operands
 __global__ __launch_bounds__(256) void add_rows_kernel(int R, int Cn, const float *__restrict__ src, int lds_,
                                                       float *__restrict__ dst, int ldd) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= R * Cn) return;
-  const int r = i / Cn, c = i % Cn;
-  dst[(size_t)r * ldd + c] += src[(size_t)r * lds_ + c];
+  const size_t n = (size_t)R * Cn;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const size_t r = i / Cn, c = i % Cn;
+    dst[r * ldd + c] += src[r * lds_ + c];
+  }
 }
 
 static int grid1(size_t n) {

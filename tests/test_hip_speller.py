@@ -136,6 +136,34 @@ def test_speller_step_on_the_fused_and_multi_stream_paths(attention, nl, K, F):
     np.testing.assert_array_equal(got, one)
 
 
+def test_fused_unsplit_backward_chain_carries_more_context_than_one_launch_covers():
+    """carry_context() of the fused, non-split backward chain (speller_train.hip: fuse_b && !split_b) adds the d context
+    carried from step t + 1 with add_rows over Bn x E elements.  64 utterances as ONE sub-batch at E = 8256 are
+    528 384 of them, 4096 more than the 2048 x 256 work items of a capped launch: the last 4096 belong to utterance 63,
+    whose three target steps carry context twice.  speller_plan() for this geometry: NS = 1 (NABU_SPELLER_STREAMS=1),
+    no persistent launch (both switches 0), fuse_shapes holds (one layer, Bn = 64 <= 64, U = 64 and 4U = 256 multiples
+    of 64, E + U = 8320 = 260 x 32), r16 is off and split_b false because NABU_SPELLER_SPLIT=0, no dropout: fuse_b &&
+    !split_b.  Logits, loss and every gradient against the oracle (check_speller)."""
+    import os
+    from nabu_amd.neuralnetworks.models.ed_decoders import rnn_decoder
+    B, E = 64, 8256
+    assert B * E == 528384 and B * E - 2048 * 256 == 4096
+    rng = np.random.default_rng(63)
+    enc_len = rng.integers(3, 7, B).astype(np.int32)
+    enc_len[0] = 6
+    tlen = rng.integers(2, 4, B).astype(np.int32)
+    tlen[63] = 3
+    env = {'NABU_SPELLER_SPLIT': '0', 'NABU_SPELLER_STREAMS': '1', 'NABU_SPELLER_PERSIST': '0',
+           'NABU_SPELLER_PERSIST_BWD': '0'}
+    os.environ.update(env)
+    try:
+        check_speller('vanilla', 1, 64, 0, 0, enc_len, tlen, E=E)
+        assert rnn_decoder.dynamic_decode.last_paths == (0, 0)
+    finally:
+        for k in env:
+            os.environ.pop(k, None)
+
+
 def test_persistent_decoder_location_aware_even_filter_width_and_many_filters():
     """'same' padding of an even filter width (left pad (K - 1) // 2), 12 filters (the kernel's register limit), 70
     frames — both persistent passes against the oracle"""
