@@ -710,6 +710,30 @@ int nabu_adam_clip_step_acc(size_t n, float *param_out, const float *src, const 
                             float *m, float *v, float lr_t, float b1, float b2, float eps,
                             float clip, float grad_scale, nabu_stream_t stream);
 
+/* Global-norm gradient clipping (the [trainer] key clip_gradient_norm; a build addition: the reference clips elements).
+ * nabu_grad_norm_f32: S = sum_i x_i^2 over x = g, or x = acc + g (an fp32 add, what nabu_adam_scaled_step forms) when acc
+ * is given; every term is squared and summed in double, in two launches inside the call (per-block partials into ws,
+ * then one block), in an order that depends on n alone: two calls on the same data give the same bits, no atomics.
+ * ws >= nabu_grad_norm_ws_bytes(n), 8-byte aligned.  g and acc are only read.  stats: four 32-bit words, 16-byte aligned:
+ *   [0] float norm   = (float)((double)scale * sqrt(S))
+ *   [1] float factor = norm > max_norm ? scale * (max_norm / norm) : scale   (fp32, this order; NaN when the norm is
+ *                      NaN or inf) — what the update multiplies g (or acc + g) by
+ *   [2] int32 skipped: incremented when the norm is NaN or inf, never cleared by the call (the caller zeroes it once)
+ *   [3] 0
+ * NABU_EINVAL before any launch: a null g or stats, an unaligned g / acc / stats / ws, max_norm not > 0, scale not finite
+ * and > 0, acc overlapping g; NABU_EWS: a workspace that is missing or too small. */
+size_t nabu_grad_norm_ws_bytes(size_t n);
+int nabu_grad_norm_f32(size_t n, const float *g, const float *acc, float scale, float max_norm, float *stats,
+                       void *ws, size_t ws_bytes, nabu_stream_t stream);
+/* nabu_adam_clip_step{,_from,_acc} without a clamp and with grad_scale = stats[1] read on the device (stats as written
+ * by nabu_grad_norm_f32 earlier on the same stream): src and acc are optional as in nabu_adam_clip_step_acc, the gradient
+ * with acc is acc + g.  For a finite factor the results are, bit for bit, those of the clipping entry points called with
+ * clip = +inf and grad_scale = that factor.  A NaN factor skips the update on the device: m and v keep their values and
+ * so does the parameter — with src, param_out = src (after a weight-noise step param_out holds the noisy values). */
+int nabu_adam_scaled_step(size_t n, float *param_out, const float *src, const float *acc, const float *g,
+                          float *m, float *v, float lr_t, float b1, float b2, float eps, const float *stats,
+                          nabu_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Regularisation noise (Philox4x32-10, counter = element index, key = seed):
  *   dropout: y = x * mask / keep_prob, mask ~ Bernoulli(keep_prob) —

@@ -171,6 +171,9 @@ SIGNATURES = {
     'nabu_clip_f32': (_i, [_sz, _vp, _f, _vp]),
     'nabu_clip_accumulate_f32': (_i, [_sz, _vp, _vp, _vp, _f, _vp]),
     'nabu_adam_clip_step_acc': (_i, [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp]),
+    'nabu_grad_norm_ws_bytes': (_sz, [_sz]),
+    'nabu_grad_norm_f32': (_i, [_sz, _vp, _vp, _f, _f, _vp, _vp, _sz, _vp]),
+    'nabu_adam_scaled_step': (_i, [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _vp]),
     'nabu_dropout_f32': (_i, [_sz, _vp, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _vp]),
     'nabu_gaussian_noise_f32': (_i, [_sz, _vp, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _vp]),
     'nabu_weight_noise_f32': (_i, [_sz, _vp, _vp, _vp, _vp, _i, _f, _c.c_ulonglong, _c.c_ulonglong, _vp]),

@@ -121,6 +121,140 @@ __global__ __launch_bounds__(256) void clip_accumulate_kernel(size_t n, float *o
 }
 
 // ---------------------------------------------------------------------------
+// global-norm clipping (the [trainer] key clip_gradient_norm): the L2 norm of the flat gradient in two launches, and the
+// Adam update that reads its scale factor from the device.
+// block-wide sum of one double (fixed tree: deterministic); the result is red[0]
+__device__ __forceinline__ void block_sum_f64(double s, double *red) {
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+}
+
+// stage 1: partial[block] = sum of x^2 over the block's grid-stride share, x = g or (fp32) acc + g, what
+// adam_scaled_kernel forms.  A product of two floats is exact in double and every term is >= 0, so the sum carries a
+// relative error of (additions in the longest chain) * 2^-53 whatever the magnitudes: 1e30 does not overflow, 1e-30 does
+// not vanish.  4 or 8 bytes read per parameter; the conversions and double FMAs are far below the vector rate.  A thread
+// keeps one chain per lane of its 16-byte groups and joins them in a fixed order.
+template <bool ACC>
+__global__ __launch_bounds__(256) void grad_norm_stage1(size_t n, const float *__restrict__ g,
+                                                        const float *__restrict__ acc, double *__restrict__ partial) {
+  __shared__ double red[256];
+  const size_t n4 = n / 4;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  // (two groups per iteration, twice the bytes in flight, measured no faster: 29.8 against 30.4 us over cfg2's buffer)
+  for (size_t i = tid; i < n4; i += stride) {
+    float4 x = reinterpret_cast<const float4 *>(g)[i];
+    if (ACC) {
+      const float4 a = reinterpret_cast<const float4 *>(acc)[i];
+      x.x = a.x + x.x;
+      x.y = a.y + x.y;
+      x.z = a.z + x.z;
+      x.w = a.w + x.w;
+    }
+    s0 = fma((double)x.x, (double)x.x, s0);
+    s1 = fma((double)x.y, (double)x.y, s1);
+    s2 = fma((double)x.z, (double)x.z, s2);
+    s3 = fma((double)x.w, (double)x.w, s3);
+  }
+  double s = (s0 + s1) + (s2 + s3);
+  for (size_t i = n4 * 4 + tid; i < n; i += stride) {      // (n % 4 elements: threads 0..2 of block 0)
+    const float x = ACC ? acc[i] + g[i] : g[i];
+    s = fma((double)x, (double)x, s);
+  }
+  block_sum_f64(s, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+// stage 2, one block behind a kernel boundary (the partials of other XCDs are visible): S = sum of the partials in a
+// fixed order, then the four words of `stats`.  norm = (float)(scale * sqrt(S)); factor = what the update multiplies the
+// gradient sum by: scale, times max_norm / norm when the norm exceeds max_norm (a norm of 0 never divides); a norm that
+// is NaN or inf gives factor = NaN, which adam_scaled_kernel takes as "skip", and counts in stats[2].
+__global__ __launch_bounds__(256) void grad_norm_stage2(int nparts, const double *__restrict__ partial, float scale,
+                                                        float max_norm, float *__restrict__ stats) {
+  __shared__ double red[256];
+  double s = 0.0;
+  for (int p = threadIdx.x; p < nparts; p += 256) s += partial[p];
+  block_sum_f64(s, red);
+  if (threadIdx.x != 0) return;
+  const float norm = (float)((double)scale * sqrt(red[0]));
+  const bool finite = fabsf(norm) <= FLT_MAX;               // (false for NaN)
+  const float factor = norm > max_norm ? scale * (max_norm / norm) : scale;
+  int32_t *words = reinterpret_cast<int32_t *>(stats);
+  stats[0] = norm;
+  stats[1] = finite ? factor : __int_as_float(0x7fc00000);
+  if (!finite) words[2] += 1;
+  words[3] = 0;
+}
+
+// adam_clip_kernel without a clamp and with gscale = stats[1], read on the device: the update of a step whose gradient is
+// clipped by its global norm (nabu_grad_norm_f32 ran before it on the same stream).  FROM and ACC as there, the gradient
+// with ACC is acc + g.  A NaN factor is a skipped update: m and v are not touched and the parameter is not updated —
+// with FROM param_out still becomes src, because it holds the noisy values of a weight-noise step at this point.
+// Bit for bit adam_clip_kernel at clip = +inf and the same gscale.  That kernel's NABU_ADAM1 cannot simply be reused
+// without its clamp: under -ffp-contract=fast the compiler picks the product it fuses by the shape of the expression, and
+// with x a plain product it fuses (1 - b1) * x where adam_clip_kernel fuses b1 * m.  So the 16-byte body spells out the
+// roundings adam_clip_kernel's has (m = fma(b1, m, (1 - b1) x), v = fma(x, (1 - b2) x, b2 v)), which fmaf pins; the
+// tail keeps the source form of that kernel's tail, which compiles without fusion in both.
+// tests/test_hip_grad_norm.py compares the two kernels at every size and argument combination.
+#define NABU_ADAM_SCALED1(c)                                    \
+  {                                                             \
+    const float x = gg.c * gscale;                              \
+    mm.c = fmaf(b1, mm.c, (1.f - b1) * x);                      \
+    vv.c = fmaf(x, (1.f - b2) * x, b2 * vv.c);                  \
+    pp.c -= lr_t * mm.c / (sqrtf(vv.c) + eps);                  \
+  }
+template <bool FROM, bool ACC>
+__global__ __launch_bounds__(256) void adam_scaled_kernel(size_t n, float *__restrict__ p, const float *__restrict__ src,
+                                                          const float *__restrict__ acc, const float *__restrict__ g,
+                                                          float *__restrict__ m, float *__restrict__ v, float lr_t,
+                                                          float b1, float b2, float eps,
+                                                          const float *__restrict__ stats) {
+  const float gscale = stats[1];
+  const size_t n4 = n / 4;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gscale != gscale) {
+    if (FROM) {
+      for (size_t i = tid; i < n4; i += stride) reinterpret_cast<float4 *>(p)[i] = reinterpret_cast<const float4 *>(src)[i];
+      for (size_t i = n4 * 4 + tid; i < n; i += stride) p[i] = src[i];
+    }
+    return;
+  }
+  for (size_t i = tid; i < n4; i += stride) {
+    float4 pp = FROM ? reinterpret_cast<const float4 *>(src)[i] : reinterpret_cast<float4 *>(p)[i];
+    float4 gg = reinterpret_cast<const float4 *>(g)[i];
+    if (ACC) {
+      const float4 aa = reinterpret_cast<const float4 *>(acc)[i];
+      gg.x = aa.x + gg.x;
+      gg.y = aa.y + gg.y;
+      gg.z = aa.z + gg.z;
+      gg.w = aa.w + gg.w;
+    }
+    float4 mm = reinterpret_cast<float4 *>(m)[i];
+    float4 vv = reinterpret_cast<float4 *>(v)[i];
+    NABU_ADAM_SCALED1(x) NABU_ADAM_SCALED1(y) NABU_ADAM_SCALED1(z) NABU_ADAM_SCALED1(w)
+    reinterpret_cast<float4 *>(p)[i] = pp;
+    reinterpret_cast<float4 *>(m)[i] = mm;
+    reinterpret_cast<float4 *>(v)[i] = vv;
+  }
+  for (size_t i = n4 * 4 + tid; i < n; i += stride) {
+    float x = (ACC ? acc[i] + g[i] : g[i]) * gscale;
+    float mm = b1 * m[i] + (1.f - b1) * x;
+    float vv = b2 * v[i] + (1.f - b2) * x * x;
+    m[i] = mm;
+    v[i] = vv;
+    float pp = FROM ? src[i] : p[i];
+    pp -= lr_t * mm / (sqrtf(vv) + eps);
+    p[i] = pp;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // column sums: stage 1 -> partial[rs][N], stage 2 -> out[N].  Fixed summation
 // order => bitwise reproducible bias gradients.
 constexpr int CS_ROWS = 512;  // rows per stage-1 block
@@ -519,6 +653,57 @@ extern "C" int nabu_adam_clip_step_acc(size_t n, float *param_out, const float *
     hipLaunchKernelGGL((adam_clip_kernel<false, float>), dim3(grid_for(n / 4 + 1)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), n, param_out, (const float *)nullptr, g, m, v, lr_t, b1, b2, eps,
                        clip, grad_scale, acc);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t nabu_grad_norm_ws_bytes(size_t n) { return n ? (size_t)grid_for(n / 4 + 1) * sizeof(double) : 0; }
+
+extern "C" int nabu_grad_norm_f32(size_t n, const float *g, const float *acc, float scale, float max_norm, float *stats,
+                                  void *ws, size_t ws_bytes, nabu_stream_t stream) {
+  NABU_CHECK_ARG(stats && (n == 0 || g), "grad_norm: null pointer (only acc may be NULL)");
+  NABU_CHECK_ARG(((uintptr_t)g | (uintptr_t)acc | (uintptr_t)stats) % 16 == 0 && (uintptr_t)ws % 8 == 0,
+                 "grad_norm: g, acc and stats must be 16-byte aligned, the workspace 8-byte aligned");
+  NABU_CHECK_ARG(max_norm > 0.f, "grad_norm: max_norm must be > 0");                                       // (false for NaN)
+  NABU_CHECK_ARG(scale > 0.f && scale <= FLT_MAX, "grad_norm: scale must be finite and > 0");
+  NABU_CHECK_ARG(!acc || !n || acc + n <= g || g + n <= acc, "grad_norm: acc and g overlap");
+  const size_t need = nabu_grad_norm_ws_bytes(n);
+  if (need && (!ws || ws_bytes < need)) return fail(NABU_EWS, "grad_norm: workspace %zu < %zu", ws_bytes, need);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int parts = (int)(need / sizeof(double));           // a function of n alone: the same n sums in the same order
+  if (parts > 0) {
+    if (acc)
+      hipLaunchKernelGGL(grad_norm_stage1<true>, dim3(parts), dim3(256), 0, s, n, g, acc, static_cast<double *>(ws));
+    else
+      hipLaunchKernelGGL(grad_norm_stage1<false>, dim3(parts), dim3(256), 0, s, n, g, (const float *)nullptr,
+                         static_cast<double *>(ws));
+    NABU_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(grad_norm_stage2, dim3(1), dim3(256), 0, s, parts, static_cast<const double *>(ws), scale, max_norm,
+                     stats);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int nabu_adam_scaled_step(size_t n, float *param_out, const float *src, const float *acc, const float *g,
+                                     float *m, float *v, float lr_t, float b1, float b2, float eps, const float *stats,
+                                     nabu_stream_t stream) {
+  if (n == 0) return 0;
+  NABU_CHECK_ARG(param_out && g && m && v && stats, "adam_scaled: null pointer (only src and acc may be NULL)");
+  NABU_CHECK_ARG(((uintptr_t)param_out | (uintptr_t)src | (uintptr_t)acc | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v |
+                  (uintptr_t)stats) % 16 == 0, "adam_scaled: buffers must be 16-byte aligned");
+  NABU_CHECK_ARG(!src || src + n <= param_out || param_out + n <= src,
+                 "adam_scaled: src and param_out overlap (src = NULL is the in-place update)");
+  NABU_CHECK_ARG(!acc || acc + n <= g || g + n <= acc, "adam_scaled: acc and g overlap");
+  const dim3 grid(grid_for(n / 4 + 1)), block(256);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+#define NABU_ADAM_SCALED(FROM, ACC) \
+  hipLaunchKernelGGL((adam_scaled_kernel<FROM, ACC>), grid, block, 0, s, n, param_out, src, acc, g, m, v, lr_t, b1, b2, eps, stats)
+  if (src && acc) NABU_ADAM_SCALED(true, true);
+  else if (src) NABU_ADAM_SCALED(true, false);
+  else if (acc) NABU_ADAM_SCALED(false, true);
+  else NABU_ADAM_SCALED(false, false);
+#undef NABU_ADAM_SCALED
   NABU_LAUNCH_CHECK();
   return 0;
 }

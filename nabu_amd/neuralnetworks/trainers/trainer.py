@@ -27,6 +27,10 @@ underneath:
     exchanged as one bucket per encoder layer (+ one for the decoder), each started
     as soon as its gradients are final and overlapped with the dense products of the
     next layer's backward pass — never with a persistent recurrent kernel;
+  * ``clip_gradient_norm = c`` (an extension key; off when absent or 0) replaces the element clip by global-norm
+    clipping after the aggregation: the mean of the update's A * replicas unclipped gradients times min(1, c / norm),
+    the norm reduced on the device (nabu_grad_norm_f32) and the factor read there by the Adam launch
+    (nabu_adam_scaled_step); an update whose norm is NaN or inf is skipped on the device (DESIGN.md section 6.2);
   * ``train()`` is ONE loop around ``step`` / ``step_accumulated`` (one body, ``_run_update``, and one ``_update`` for
     every A and every exchange).  Two small objects say where a device batch comes from (DirectFeed | AheadFeed) and
     when a step's words are read (readback.ReadNow | ReadLate); ``prefetch_batches`` >= 1 (an extension key,
@@ -71,6 +75,21 @@ def weight_noise_keys(conf):
     if start < 0:
         raise ValueError('weight_noise_start_step must be >= 0, got %r' % text)
     return stddev, start
+
+
+def clip_norm_key(conf):
+    """the `clip_gradient_norm` key of the [trainer] section (a build addition like label_smoothing: absent from
+    defaults/standardtrainer.cfg, off when absent or 0) -> c.  With c > 0 the update is clipped by the global L2 norm of
+    its gradient instead of element by element: the mean over the update's A * world micro-batch gradients, unclipped,
+    times min(1, c / its norm); an update whose norm is NaN or inf is skipped on the device."""
+    text = str(conf.get('clip_gradient_norm', '0')).strip()
+    try:
+        c = float(text)
+    except ValueError:
+        raise ValueError('clip_gradient_norm must be a number, got %r' % text)
+    if not (0.0 <= c < float('inf')):                           # (false for NaN)
+        raise ValueError('clip_gradient_norm must be a finite norm >= 0 (0: off), got %r' % text)
+    return c
 
 
 def aggregate_key(conf, world):
@@ -222,6 +241,13 @@ class Trainer(object, metaclass=ABCMeta):
         self.accumulate = aggregate_key(self.conf, self.world)
         self.flat_acc = None               # the sum of an update's clipped micro-batch gradients (allocated when A > 1)
         self._micro = 0                    # micro-batches of the current update already in flat_acc
+        # clip_gradient_norm (an extension key as well, validated here too): c > 0 clips the update's mean gradient by its
+        # global norm and switches the element clip off.  The existing kernels then receive clip = +inf, with which
+        # clip_value is the identity bit for bit: fminf(fmaxf(x, -inf), inf) == x, and NaN passes through as always.
+        self.clip_norm = clip_norm_key(self.conf)
+        self.clip = math.inf if self.clip_norm > 0 else CLIP
+        self.clip_stats = self.clip_ws = None     # device words (norm, factor, skipped, 0) and the reduction's workspace
+        self._skipped_reported = 0
         self.last_weight_noise = None      # the (seed, offset) of the latest noisy step
         self._noisy = False                # True from a step's noise launch until its optimiser has run
         self.model = Model(conf=modelconf, trainlabels=int(self.conf['trainlabels']), constraint=None)
@@ -448,7 +474,7 @@ class Trainer(object, metaclass=ABCMeta):
                             % (j, self._micro, self.accumulate))
         if self.flat_acc is None:
             self.flat_acc = torch.empty_like(self.flat_grad)
-        hip.clip_accumulate(self.flat_acc, self.flat_acc if j else None, self.flat_grad, CLIP)
+        hip.clip_accumulate(self.flat_acc, self.flat_acc if j else None, self.flat_grad, self.clip)
         self._micro = j + 1
 
     def _init_optimizer(self):
@@ -467,6 +493,8 @@ class Trainer(object, metaclass=ABCMeta):
             if self.noise_table.n > hip.WEIGHT_NOISE_MAX_RANGES:
                 raise ValueError('weight_noise: the matrices form %d separate ranges of the flat parameter buffer, the '
                                  'kernel takes %d' % (self.noise_table.n, hip.WEIGHT_NOISE_MAX_RANGES))
+        if self.clip_norm > 0:             # (nor these two)
+            self.clip_stats, self.clip_ws = hip.grad_norm_buffers(self.flat_grad.numel(), self.flat_grad.device)
 
     # ----------------------------------------------------- bucketed gradient exchange
     @staticmethod
@@ -527,11 +555,13 @@ class Trainer(object, metaclass=ABCMeta):
 
     def _clip_local(self, start, end):
         '''what this replica sends of flat_grad[start:end], left there: the clipped gradient (clip per replica, before the
-        aggregation), with A > 1 the local sum of A clipped gradients; returns the view'''
+        aggregation), with A > 1 the local sum of A clipped gradients; returns the view.  With clip_gradient_norm the
+        element clip is off (self.clip is +inf): the sum is that of the plain gradients, and a single one is sent as it
+        is, without a launch'''
         view = self.flat_grad[start:end]
         if self.accumulate > 1:
-            hip.clip_accumulate(view, self.flat_acc[start:end], view, CLIP)
-        else:
+            hip.clip_accumulate(view, self.flat_acc[start:end], view, self.clip)
+        elif not self.clip_norm > 0:
             hip.clip_(view, CLIP)
         return view
 
@@ -549,7 +579,10 @@ class Trainer(object, metaclass=ABCMeta):
         gradient as the backward pass left it, flat_acc the A - 1 clipped ones before it.  One replica: ONE launch clips,
         adds and applies Adam.  Several: every replica completes its clipped local sum in flat_grad (_clip_local; per
         bucket under the backward pass and here for the rest), the sums are exchanged ONCE, and Adam runs on
-        1 / (A * world) of the total: the mean of A * world clipped gradients, what A * world replicas compute.'''
+        1 / (A * world) of the total: the mean of A * world clipped gradients, what A * world replicas compute.
+        With clip_gradient_norm = c the same path runs with the element clip off (self.clip = +inf; a single replica's
+        lone gradient is not touched before the exchange) and one grad_norm call behind the exchange: Adam then runs on
+        the plain mean times min(1, c / its L2 norm), or not at all when that norm is not finite (_adam).'''
         A = self.accumulate
         if self._micro != A - 1:
             raise Exception('the update needs %d accumulated micro-batches, %d are in' % (A - 1, self._micro))
@@ -569,6 +602,10 @@ class Trainer(object, metaclass=ABCMeta):
             if ev is not None:
                 ev[1].record()
             acc = None                                           # (in the exchanged sum)
+        if self.clip_norm > 0:
+            # the norm of the mean gradient and the factor the update applies, left on the device: behind the exchange,
+            # so every replica reduces the same sum in the same order and gets the same bits
+            hip.grad_norm(self.flat_grad, acc, 1.0 / (A * self.world), self.clip_norm, self.clip_stats, self.clip_ws)
         self._adam(lr_t, 1.0 / (A * self.world), acc)
         self._micro = 0
         self.last_lr = lr
@@ -576,16 +613,41 @@ class Trainer(object, metaclass=ABCMeta):
     def _adam(self, lr_t, scale, acc):
         '''the fused clip + Adam launch on scale * flat_grad, with `acc` on scale * (acc + clip(flat_grad)); after a noisy
         step (_add_weight_noise) the parameter is read from the clean copy, so the noise leaves with the update and
-        nothing has to be subtracted again'''
+        nothing has to be subtracted again.  With clip_gradient_norm: ONE entry point for the same src / acc choice,
+        no clamp, and the scale is the factor grad_norm left on the device (scale * min(1, c / norm)); a factor of NaN
+        (a norm that is not finite) skips the update there: m, v and the clean parameters stay as they are, nothing is
+        read back, and adam_step has advanced all the same, so the bias correction of later updates is that of one
+        more step'''
         src = self.flat_clean if self._noisy else None
         rest = (self.adam_m, self.adam_v, lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, CLIP, scale)
-        if acc is not None:
+        if self.clip_norm > 0:
+            hip.adam_scaled_step(self.flat, src, acc, self.flat_grad, self.adam_m, self.adam_v, lr_t, ADAM_B1, ADAM_B2,
+                                 ADAM_EPS, self.clip_stats)
+        elif acc is not None:
             hip.adam_clip_step_acc(self.flat, src, acc, self.flat_grad, *rest)
         elif src is not None:
             hip.adam_clip_step_from(self.flat, src, self.flat_grad, *rest)
         else:
             hip.adam_clip_step(self.flat, self.flat_grad, *rest)
         self._noisy = False
+
+    def grad_stats(self):
+        '''(norm, factor, skipped) of the latest update with clip_gradient_norm: the L2 norm of its mean gradient, the
+        factor the gradient sum was multiplied by (NaN: the update was skipped) and the number of updates skipped so far.
+        Copies four words to the host, so it synchronises; train() does not call it per step.'''
+        if self.clip_stats is None:
+            raise Exception('grad_stats needs clip_gradient_norm > 0 and a first update')
+        return hip.read_grad_stats(self.clip_stats)
+
+    def _report_skipped(self):
+        '''called where train() has synchronised anyway (a validation point, the end): says so when updates were skipped
+        since the last report'''
+        if self.clip_stats is None:
+            return
+        skipped = hip.read_grad_stats(self.clip_stats)[2]
+        if skipped != self._skipped_reported:
+            print('WORKER %d: %d updates skipped (non-finite gradient norm)' % (self.task_index, skipped))
+            self._skipped_reported = skipped
 
     def _allreduce_events(self):
         '''bench.py sets ``time_allreduce``: a pair of events on the launch stream around the
@@ -728,6 +790,7 @@ class Trainer(object, metaclass=ABCMeta):
                 if (self.evaluator is not None
                         and self.global_step - self.validated_step >= int(self.conf['valid_frequency'])):
                     reader.drain()
+                    self._report_skipped()
                     self._ensure_variables()
                     if self._validation_point():
                         break
@@ -744,6 +807,7 @@ class Trainer(object, metaclass=ABCMeta):
                     self.save_checkpoint(ckpt)
                     last_ckpt = time.time()
             reader.drain()
+            self._report_skipped()
         finally:
             feed.close()
         if is_chief and self.expdir is not None:

@@ -390,6 +390,49 @@ def adam_clip_step_acc(param_out, src, acc, g, m, v, lr_t, b1=0.9, b2=0.999, eps
                                              clip, grad_scale, stream()), 'nabu_adam_clip_step_acc')
 
 
+def grad_norm_buffers(n, device):
+    """(stats, ws) of grad_norm for a gradient of n elements: the four zeroed 32-bit words (float norm, float factor,
+    int32 skipped, 0) and the workspace of the per-block partial sums"""
+    ws_bytes = _hip.lib().nabu_grad_norm_ws_bytes(n)
+    return (torch.zeros(4, dtype=torch.int32, device=device),
+            torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=device))
+
+
+def grad_norm(g, acc, scale, max_norm, stats, ws):
+    """stats = (norm, factor, skipped += norm not finite, 0) of the gradient scale * g, with acc of scale * (acc + g):
+    norm = its L2 norm, summed in double in a fixed order, factor = scale * min(1, max_norm / norm) or NaN when the norm
+    is NaN or inf (nabu_grad_norm_f32).  stats and ws come from grad_norm_buffers; nothing is read back."""
+    if acc is not None and acc.numel() != g.numel():
+        raise _hip.NabuHipError('grad_norm: acc holds %d elements, g %d' % (acc.numel(), g.numel()))
+    if stats is not None and (stats.dtype != torch.int32 or stats.numel() != 4):
+        raise _hip.NabuHipError('grad_norm: stats must be 4 int32 words (grad_norm_buffers)')
+    check(_hip.lib().nabu_grad_norm_f32(g.numel(), ptr(_f32(g, 'g')), ptr(acc if acc is None else _f32(acc, 'acc')),
+                                        scale, max_norm, ptr(stats), ptr(ws),
+                                        0 if ws is None else ws.numel() * ws.element_size(), stream()),
+          'nabu_grad_norm_f32')
+    return stats
+
+
+def read_grad_stats(stats):
+    """(norm, factor, skipped) of a stats buffer of grad_norm; copies to the host, so it synchronises"""
+    words = stats.cpu()
+    f = words.view(torch.float32)
+    return float(f[0]), float(f[1]), int(words[2])
+
+
+def adam_scaled_step(param_out, src, acc, g, m, v, lr_t, b1, b2, eps, stats):
+    """adam_clip_step (src None) / _from (src: the clean parameters) / _acc (acc: the sum of the earlier micro-batch
+    gradients) without a clamp, on factor * g or factor * (acc + g) with factor = stats[1] read on the device; a NaN
+    factor leaves m, v and the parameters alone (with src: param_out = src) (nabu_adam_scaled_step)"""
+    for name, t in (('src', src), ('acc', acc), ('g', g)):
+        if t is not None and t.numel() != param_out.numel():
+            raise _hip.NabuHipError('adam_scaled_step: %s holds %d elements, param_out %d'
+                                    % (name, t.numel(), param_out.numel()))
+    check(_hip.lib().nabu_adam_scaled_step(param_out.numel(), ptr(_f32(param_out, 'param_out')), ptr(src), ptr(acc),
+                                           ptr(_f32(g, 'g')), ptr(m), ptr(v), lr_t, b1, b2, eps, ptr(stats), stream()),
+          'nabu_adam_scaled_step')
+
+
 def dropout(x, keep_prob, seed, offset):
     y = torch.empty_like(x)
     check(_hip.lib().nabu_dropout_f32(x.numel(), ptr(x), ptr(y), keep_prob, seed, offset, stream()),
