@@ -714,19 +714,33 @@ __global__ __launch_bounds__(AT) void attn_bwd_kernel(AttnArgs p) {
   // softmax backward: dscore = a * (da - sum a*da)
   // sum_t a[t] da[t] over ALL frames of the utterance without visiting them:
   //   da[t] = dctx·values[t] + dalign_in[t]  =>  sum_t a[t] da[t] = dctx·context + sum_t a[t] dalign_in[t]
-  float r = 0.f;
+  // The dot product is summed exactly as a frame's is above (every wave on its own: lanes over the 16-byte groups, the
+  // same fma chain, wave_sum), and the dalign_in part joins it in one add as it joins da[t]: where the alignment is
+  // one-hot (one attendable frame, a saturated softmax: context = that frame's values) r equals da[t] to the bit and
+  // d score is exactly 0 instead of the rounding of one dot product summed in two orders.
+  float rc = 0.f;
   {
-    const float *cx = p.ctx + (size_t)b * E;
-    for (int e = tid; e < E; e += AT) r = fmaf(dctx[e], cx[e], r);
-    if (p.dalign_in)
-      for (int t = tid; t < n; t += AT) r = fmaf(al[t], p.dalign_in[(size_t)b * Te + t], r);
+    const int E4 = E / 4;
+    const float4 *dctx4 = reinterpret_cast<const float4 *>(dctx);
+    const float4 *cx4 = reinterpret_cast<const float4 *>(p.ctx + (size_t)b * E);
+    for (int e4 = lane; e4 < E4; e4 += 64) {
+      const float4 dc = dctx4[e4], cv = cx4[e4];
+      rc = fmaf(dc.x, cv.x, rc); rc = fmaf(dc.y, cv.y, rc);
+      rc = fmaf(dc.z, cv.z, rc); rc = fmaf(dc.w, cv.w, rc);
+    }
+    rc = wave_sum(rc);
   }
-  r = wave_sum(r);
-  if (lane == 0) red[w] = r;
-  __syncthreads();
-  r = 0.f;
-  for (int i = 0; i < NW; ++i) r += red[i];
-  __syncthreads();
+  float r = 0.f;
+  if (p.dalign_in) {
+    for (int t = tid; t < n; t += AT) r = fmaf(al[t], p.dalign_in[(size_t)b * Te + t], r);
+    r = wave_sum(r);
+    if (lane == 0) red[w] = r;
+    __syncthreads();
+    r = 0.f;
+    for (int i = 0; i < NW; ++i) r += red[i];
+    __syncthreads();
+  }
+  r = rc + r;
   if (p.prob_fn == 0) {
     for (int t = lo + tid; t < hi; t += AT) ds[t] = al[t] * (ds[t] - r);
   } else if (p.prob_fn == 1) {        // a = sigmoid(s): ds = da a (1 - a)

@@ -136,6 +136,30 @@ def test_speller_step_on_the_fused_and_multi_stream_paths(attention, nl, K, F):
     np.testing.assert_array_equal(got, one)
 
 
+@pytest.mark.parametrize('switch', ['NABU_SPELLER_DEFER', 'NABU_SPELLER_ATTN_FUSED'])
+@pytest.mark.parametrize('attention,nl,U,K,F', [('vanilla', 1, 32, 0, 0), ('windowed:normalized_sigmoid', 1, 32, 1, 3),
+                                                ('location_aware', 1, 32, 5, 3)])
+def test_step_chain_without_deferred_sums_and_without_tickets(attention, nl, U, K, F, switch):
+    """The step chain (persistent decoder off) with one of its two attention switches off, at 70 encoder frames (five
+    frame slices): NABU_SPELLER_DEFER=0 runs the backward kernels that accumulate d keys, d attention_v and d conv_proj
+    step by step (attn_bwd_kernel<.., false>), NABU_SPELLER_ATTN_FUSED=0 the finish kernels instead of the slice that
+    arrives last — what a caller of nabu_attn_fwd / nabu_attn_bwd gets.  Against the oracle (check_speller), and within
+    1e-5 of the default switches' logits (the additions are ordered differently, so the bits may differ)."""
+    import os
+    enc_len, tlen = np.array([70, 33, 70, 15, 52], np.int32), np.array([6, 3, 5, 6, 1], np.int32)
+    chain = ('NABU_SPELLER_PERSIST', 'NABU_SPELLER_PERSIST_BWD')
+    for k in chain:
+        os.environ[k] = '0'
+    try:
+        ref = check_speller(attention, nl, U, K, F, enc_len, tlen)
+        os.environ[switch] = '0'
+        got = check_speller(attention, nl, U, K, F, enc_len, tlen)
+    finally:
+        for k in chain + (switch,):
+            os.environ.pop(k, None)
+    assert np.abs(got - ref).max() < 1e-5
+
+
 def test_fused_unsplit_backward_chain_carries_more_context_than_one_launch_covers():
     """carry_context() of the fused, non-split backward chain (speller_train.hip: fuse_b && !split_b) adds the d context
     carried from step t + 1 with add_rows over Bn x E elements.  64 utterances as ONE sub-batch at E = 8256 are
