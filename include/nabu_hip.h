@@ -170,6 +170,23 @@ size_t nabu_colsum_ws_bytes(int M, int N);
 int nabu_colsum_f32(int M, int N, const float *A, int lda, float beta, float *out,
                     void *ws, size_t ws_bytes, nabu_stream_t stream);
 
+/* A linear layer with a narrow output, y[M,N] = x[M,K]·W[K,N] + b with N <= 64 (the DNNDecoder's outlayer,
+ * models/ed_decoders/dnn_decoder.py:53-57), exact fp32 (linear_narrow.hip).
+ * Forward: nabu_gemm_ex / nabu_gemm_f32 take the narrow kernel by themselves when the arithmetic is fp32, N <= 64,
+ * K % 4 == 0, lda % 4 == 0, A, B and C are 16-byte aligned, nothing is transposed, beta == 0 and kseg == 0: one launch,
+ * no workspace, and a row's result does not depend on the rows it is computed with.
+ * Backward: all three gradients from ONE pass over x and dy plus one small reduce launch,
+ *   dx[M,K] = dy·W^T (dx may be NULL: skipped),  dW[K,N] = x^T·dy,  db[N] = colsum(dy),
+ * dW (contiguous) and db OVERWRITTEN, as the beta = 0 calls they replace do.  Partial sums of dW and db go through ws
+ * (nabu_linear_bwd_ws_bytes) and are added in a fixed order: bitwise repeatable, no float atomics.
+ * NABU_EUNSUP: N > 64, K % 4 != 0, ldx or lddx % 4 != 0, an operand that is not 16-byte aligned, or NABU_LINEAR_NARROW=0
+ * — the caller then makes the three calls (nabu_gemm_f32 twice, nabu_colsum_f32).
+ * NABU_LINEAR_NARROW=0 (environment, read once) switches both kernels off: the products take the general tiles again. */
+size_t nabu_linear_bwd_ws_bytes(int M, int K, int N);
+int nabu_linear_bwd_f32(int M, int K, int N, const float *x, int ldx, const float *dy, int ldy,
+                        const float *W, int ldw, float *dx, int lddx, float *dW, float *db, void *ws,
+                        size_t ws_bytes, nabu_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * One bidirectional LSTM layer — layer.blstm
  * (nabu/neuralnetworks/components/layer.py:8-51): two

@@ -113,6 +113,8 @@ SIGNATURES = {
     'nabu_gemm_get_default_precision': (_i, []),
     'nabu_colsum_ws_bytes': (_sz, [_i, _i]),
     'nabu_colsum_f32': (_i, [_i, _i, _vp, _i, _f, _vp, _vp, _sz, _vp]),
+    'nabu_linear_bwd_ws_bytes': (_sz, [_i, _i, _i]),
+    'nabu_linear_bwd_f32': (_i, [_i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     'nabu_blstm_reserve_bytes': (_sz, [_c.POINTER(BlstmDesc)]),
     'nabu_blstm_ws_bytes': (_sz, [_c.POINTER(BlstmDesc)]),
     'nabu_blstm_fwd': (_i, [_c.POINTER(BlstmDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

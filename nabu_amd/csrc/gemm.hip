@@ -653,6 +653,11 @@ extern "C" int nabu_gemm_ex(int precision, int transA, int transB, int M, int N,
   NABU_CHECK_ARG(A && B && C, "gemm: null pointer");
   NABU_CHECK_ARG(kseg == 0 || (transA && !transB && K % kseg == 0),
                  "gemm: segmented K needs transA=1, transB=0 and K %% kseg == 0");
+  // a narrow output (N <= 64: the DNNDecoder's outlayer) has a kernel shaped for it (linear_narrow.hip): one launch, no
+  // split-K, a row's k order independent of its row block
+  if (precision == NABU_GEMM_F32 && !transA && !transB && beta == 0.f && kseg == 0 &&
+      linear_narrow_fwd_ok(M, N, K, A, lda, B, C))
+    return linear_narrow_fwd(M, N, K, alpha, A, lda, B, ldb, C, ldc, bias, static_cast<hipStream_t>(stream));
   // Reduction lengths that are not a multiple of the fast kernel's k-tile (B*T of real batches): the
   // fast kernel takes the first K - K % 16 indices, the generic kernel adds the rest.  With segmented K
   // the rest must lie inside the last segment (it does unless a segment is shorter than 16).

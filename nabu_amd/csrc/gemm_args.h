@@ -106,6 +106,13 @@ int gemm_batched_f32(bool transA, bool transB, int M, int N, int K, const float 
                      const float *B, int ldb, long long b_bs, float beta, float *C, int ldc, long long c_bs, int nbatch,
                      hipStream_t s);
 
+// narrow-output products (linear_narrow.hip): C = alpha * A·B + bias for N <= 64 columns in one launch, no workspace.
+// _ok: N <= 64, K % 4 == 0, lda % 4 == 0, 16-byte aligned A, B and C, and NABU_LINEAR_NARROW != 0 (read once)
+bool linear_narrow_enabled();
+bool linear_narrow_fwd_ok(int M, int N, int K, const float *A, int lda, const float *B, const float *C);
+int linear_narrow_fwd(int M, int N, int K, float alpha, const float *A, int lda, const float *B, int ldb, float *C,
+                      int ldc, const float *bias, hipStream_t s);
+
 // split-K policy shared by the tile kernels: >= target workgroups, k-range a multiple of kmult
 int gemm_split_for(int M, int N, int K, int kmult, int target, int *ksplit);
 int gemm_splitk_reduce(const GemmArgs &a, hipStream_t s);

@@ -29,11 +29,13 @@ def linear(inputs, num_outputs, scope):
         for v in (W, b):
             if v.grad is None:
                 v.grad = torch.zeros_like(v.data)
+        dx = torch.empty_like(x) if need_dx else None
+        # a narrow output (the outlayer's classes): all three gradients from one pass over x and dout
+        if hip.linear_bwd(x2, d2, W.data, W.grad, b.grad, dx.view(B * T, F) if need_dx else None):
+            return [dx]
         hip.gemm(x2, d2, W.grad, trans_a=True)              # dW = x^T dout
         hip.colsum(d2, b.grad)
-        dx = None
         if need_dx:
-            dx = torch.empty_like(x)
             hip.gemm(d2, W.data, dx.view(B * T, F), trans_b=True)   # dx = dout W^T
         return [dx]
     record([inputs], [out], backward, params=(W, b))

@@ -170,6 +170,28 @@ def colsum(a, out, beta=0.0):
     return out
 
 
+def linear_bwd(x, dy, w, dw, db, dx=None):
+    """All gradients of y = x @ w + b for a narrow output (w.shape[1] <= 64) from one pass over x and dy
+    (nabu_linear_bwd_f32): dw = x^T dy and db = colsum(dy) overwritten, dx = dy w^T when dx is given.  Returns False,
+    with nothing written, when the shape is not supported there (NABU_EUNSUP): the caller then makes the three calls."""
+    L = _hip.lib()
+    M, K = x.shape
+    N = w.shape[1]
+    if not (dw.is_contiguous() and x.stride(1) == 1 and dy.stride(1) == 1 and w.stride(1) == 1 and
+            (dx is None or dx.stride(1) == 1)):
+        return False
+    ws_bytes = L.nabu_linear_bwd_ws_bytes(M, K, N)
+    ws = Workspace.get(ws_bytes, x.device, 'gemm')
+    rc = L.nabu_linear_bwd_f32(M, K, N, _f32(x, 'x').data_ptr(), x.stride(0), _f32(dy, 'dy').data_ptr(), dy.stride(0),
+                               _f32(w, 'w').data_ptr(), w.stride(0), _f32(dx, 'dx').data_ptr() if dx is not None else None,
+                               dx.stride(0) if dx is not None else 0, ptr(_f32(dw, 'dw')), ptr(_f32(db, 'db')),
+                               ptr(ws), ws_bytes, stream())
+    if rc == NABU_EUNSUP:
+        return False
+    check(rc, 'nabu_linear_bwd_f32')
+    return True
+
+
 class BlstmPlan(object):
     """Shape descriptor + buffers of one BLSTM layer call (plain cell: the nabu_blstm_* entry points)."""
     ENTRY, WS_TAG, LAYER_NORM = 'nabu_blstm', 'blstm', False
