@@ -1028,6 +1028,65 @@ int nabu_speller_sample(const nabu_beam_desc *d, const float *values, const int3
 int nabu_beam_gather(int B, int W, int F, const float *fresh, const float *old, const int32_t *parent,
                      const int32_t *stay, float *dst, nabu_stream_t stream);
 
+/* Joint CTC/attention beam search (Watanabe, Hori, Kim, Hershey, Hayashi 2017: hybrid CTC/attention decoding): every
+ * candidate of a step also gets the CTC prefix score of the encoder's CTC head, and the beam is pruned on
+ *   (1 - ctc_weight) * log p_att + ctc_weight * log p_ctc.
+ * logits [B,T,C]: the head's logits on the first encoded input, enc_len [B] its lengths (clamped to 0..T); the blank
+ * is C-1, which is also the Speller's end label.  y_t(k) is the log-softmax of frame t.  For a hypothesis g (its labels
+ * without the start symbol, `last` its final label, -1 for the empty one) the state is r_n(t,g), r_b(t,g), t < enc_len:
+ * the log-probabilities of all paths of frames 0..t that collapse to g and end in a label / in the blank, stored as
+ * pairs in state [B,W,T,2]; psi [B,W] is log P_ctc(g followed by anything), 0 for the empty g.  All sums are
+ * log-sum-exp in fp32; log 0 is the finite -1e30 of nabu_ctc_loss_grad, so no inf - inf arises.
+ *   r_n(t, {}) = log 0, r_b(t, {}) = sum_{tau <= t} y_tau(blank);
+ *   h = g.c, c != blank:  r_n(0,h) = y_0(c) if g is empty else log 0, r_b(0,h) = log 0, psi = r_n(0,h), and for t >= 1
+ *     phi = r_b(t-1,g) if c == last else r_n(t-1,g) (+) r_b(t-1,g);
+ *     r_n(t,h) = (r_n(t-1,h) (+) phi) + y_t(c);  r_b(t,h) = (r_b(t-1,h) (+) r_n(t-1,h)) + y_t(blank);  psi (+)= phi + y_t(c);
+ *   psi(g.eos) = r_n(T-1,g) (+) r_b(T-1,g): the probability of g exactly.
+ * A hypothesis that does not fit into its utterance (longer than enc_len, or repeats without room for their blanks)
+ * has psi = log 0, and so has every extension of it.
+ *   nabu_ctc_prefix_prepare: once per search.  Writes norm [B,T,2] (frame maximum and log of the sum of exp(x - max):
+ *     y = (x - max) - log sum), and the state, psi = 0 and last = -1 of the empty hypothesis in all W slots.
+ *   nabu_ctc_prefix_score: per step.  delta [B,W,C] = psi(g.c) - psi(g) for every class (c = C-1: psi(g.eos)); the row
+ *     of a finished beam is zero and its state is not read.
+ *   nabu_ctc_prefix_advance: per step, after pruning.  Survivor k of utterance b (parent, stay, pred as
+ *     nabu_beam_prune writes them): stay -> its parent's state, psi and last; pred == C-1 -> psi(g.eos), state and last
+ *     kept; otherwise the state of parent.pred, RECOMPUTED (the W*C candidate states of a step are never stored).  The
+ *     new state must not overwrite the old one.
+ * LDS: 4 T floats per workgroup at most; NABU_EUNSUP with a message when the device has less. */
+int nabu_ctc_prefix_prepare(int B, int W, int T, int C, const float *logits, const int32_t *enc_len, float *norm,
+                            float *state, float *psi, int32_t *last, nabu_stream_t stream);
+int nabu_ctc_prefix_score(int B, int W, int T, int C, const float *logits, const int32_t *enc_len, const float *norm,
+                          const float *state, const float *psi, const int32_t *last, const int32_t *finished,
+                          float *delta, nabu_stream_t stream);
+int nabu_ctc_prefix_advance(int B, int W, int T, int C, const float *logits, const int32_t *enc_len, const float *norm,
+                            const float *state_in, const float *psi_in, const int32_t *last_in, const int32_t *parent,
+                            const int32_t *stay, const int32_t *pred, float *state_out, float *psi_out,
+                            int32_t *last_out, nabu_stream_t stream);
+/* nabu_beam_prune with the CTC term: a live beam's candidate log-probability is
+ *   logprobs[w] + (1 - ctc_weight) * (logits[w,c] / temperature - logsumexp) + ctc_weight * delta[w,c];
+ * finished beams, "stay" candidates, the length penalty, the tie rule and every output as nabu_beam_prune (one kernel
+ * body).  0 <= ctc_weight < 1; with 0 the outputs are those of nabu_beam_prune, bit for bit. */
+int nabu_beam_prune_joint(int B, int W, int C, const float *logits, const float *delta, float ctc_weight,
+                          float temperature, float length_penalty, float *logprobs, int32_t *lengths,
+                          int32_t *finished, int32_t *seen, int32_t *pred_ids, int32_t *parent, int32_t *stay,
+                          int32_t *all_seen, float *scratch, nabu_stream_t stream);
+/* nabu_speller_beam_search / nabu_speller_multi_beam_search with the optional CTC operand: ctc_logits [B,Te,C] (Te of
+ * the FIRST encoded input) and ctc_weight in [0, 1).  With ctc_logits NULL or ctc_weight 0 the search makes exactly the
+ * launches of the plain entry point.  Otherwise: nabu_ctc_prefix_prepare before the loop, and per step
+ * nabu_ctc_prefix_score before and nabu_ctc_prefix_advance after nabu_beam_prune_joint, which stands for
+ * nabu_beam_prune; scores are the joint log-probabilities under the same length penalty. */
+size_t nabu_speller_beam_joint_ws_bytes(const nabu_beam_desc *d);
+int nabu_speller_beam_search_joint(const nabu_beam_desc *d, const float *values, const int32_t *enc_len,
+                                   const nabu_speller_params *p, const float *ctc_logits, float ctc_weight,
+                                   int32_t *sequences, int32_t *lengths, float *scores, float *alignments,
+                                   int32_t *num_steps, void *ws, size_t ws_bytes, nabu_stream_t stream);
+size_t nabu_speller_multi_beam_joint_ws_bytes(const nabu_multi_beam_desc *d);
+int nabu_speller_multi_beam_search_joint(const nabu_multi_beam_desc *d, const float *const *values_host,
+                                         const int32_t *const *enc_len_host, const nabu_speller_multi_params *p,
+                                         const float *ctc_logits, float ctc_weight, int32_t *sequences,
+                                         int32_t *lengths, float *scores, float *const *alignments_host,
+                                         int32_t *num_steps, void *ws, size_t ws_bytes, nabu_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Host-side helper of the on-disk data path (host memory, as the `_host` feature queries below):
  * CRC-32C (Castagnoli) of `n` bytes, continuing from `crc` (0 to start) — the checksum of the

@@ -191,6 +191,14 @@ SIGNATURES = {
     'nabu_speller_beam_search': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nabu_beam_prune': (_i, [_i, _i, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'nabu_beam_gather': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'nabu_ctc_prefix_prepare': (_i, [_i, _i, _i, _i] + [_vp] * 6 + [_vp]),
+    'nabu_ctc_prefix_score': (_i, [_i, _i, _i, _i] + [_vp] * 8 + [_vp]),
+    'nabu_ctc_prefix_advance': (_i, [_i, _i, _i, _i] + [_vp] * 12 + [_vp]),
+    'nabu_beam_prune_joint': (_i, [_i, _i, _i, _vp, _vp, _f, _f, _f] + [_vp] * 9 + [_vp]),
+    'nabu_speller_beam_joint_ws_bytes': (_sz, [_vp]),
+    'nabu_speller_beam_search_joint': (_i, [_vp] * 5 + [_f] + [_vp] * 6 + [_sz, _vp]),
+    'nabu_speller_multi_beam_joint_ws_bytes': (_sz, [_vp]),
+    'nabu_speller_multi_beam_search_joint': (_i, [_vp] * 5 + [_f] + [_vp] * 6 + [_sz, _vp]),
     'nabu_sample_advance': (_i, [_i, _i, _vp, _c.c_ulonglong, _c.c_ulonglong, _i, _i] + [_vp] * 6 + [_vp]),
     'nabu_speller_sample_ws_bytes': (_sz, [_vp]),
     'nabu_speller_sample': (_i, [_vp] * 4 + [_c.c_ulonglong, _c.c_ulonglong] + [_vp] * 6 + [_sz, _vp]),

@@ -356,12 +356,17 @@ struct PruneArgs {
   float *logprobs;
   int32_t *lengths, *finished, *seen, *pred, *parent, *stay, *all_seen;
   float *scratch;
+  const float *delta;      // JOINT: [B,W,C] CTC prefix score differences (ctc_prefix.hip), and their weight
+  float ctcw;
 };
 
 __device__ __forceinline__ float length_penalty(int len, float w, float pen6) {
   return w == 0.f ? 1.f : powf(5.f + (float)len, w) / pen6;
 }
 
+// JOINT: a live beam's candidate adds (1 - ctcw) * attention log-probability + ctcw * delta instead of the
+// attention log-probability (nabu_beam_prune_joint); everything else is the one body
+template <bool JOINT>
 __global__ __launch_bounds__(DT) void beam_prune_kernel(PruneArgs p) {
   extern __shared__ __attribute__((aligned(16))) float dsm[];
   __shared__ Best red[2 * (DT / 64)];
@@ -394,7 +399,8 @@ __global__ __launch_bounds__(DT) void beam_prune_kernel(PruneArgs p) {
   auto candidate = [&](int idx, float &lp, int &len, int &id) {
     if (idx < W * C) {
       const int w = idx / C, c = idx - w * C;
-      const float nl = pfin[w] ? -FLT_MAX : lg[idx] * p.inv_temp - lz[w];
+      float nl = pfin[w] ? -FLT_MAX : lg[idx] * p.inv_temp - lz[w];
+      if (JOINT && !pfin[w]) nl = (1.f - p.ctcw) * nl + p.ctcw * p.delta[(size_t)b * W * C + idx];
       lp = plp[w] + nl;
       len = plen[w] + (c != end ? 1 : 0);
       id = c;
@@ -585,6 +591,8 @@ struct BeamGeo {
   bool multi;                 // the step's attention is multi_attn_fwd
   bool sample;                // sampled decoding (W = 1): nabu_sample_advance where the search prunes and gathers
   unsigned long long seed, offset0;
+  bool ctc;                   // joint CTC/attention scoring: BeamIO::ctc_logits weighted by ctcw in (0, 1)
+  float ctcw;
 };
 struct BeamIO {
   const float *values[MM];
@@ -594,6 +602,7 @@ struct BeamIO {
   float *alignments[MM];      // all null: not wanted
   int32_t *sequences, *lengths, *num_steps;
   float *scores;              // (sampled decoding: nll)
+  const float *ctc_logits;    // [B, Te[0], C] logits of the CTC head on the first encoded input, or null
 };
 
 // workspace, offsets in 32-bit words
@@ -604,6 +613,7 @@ struct BeamWs {
   size_t big, z, q, logits, acts, ids, logprobs, lengths, finished, seen, parent, stay, all_seen, scratch, hist_pred,
       hist_parent, src, gemm, gemm_bytes, total;
   size_t h[3][NABU_SPELLER_MAX_LAYERS], c[3][NABU_SPELLER_MAX_LAYERS], ctx[3];
+  size_t cnorm, cstate[2], cpsi[2], clast[2], cdelta;      // joint scoring only (ctc_prefix.hip), behind everything else
 };
 
 static BeamWs beam_ws(const BeamGeo &g) {
@@ -642,9 +652,16 @@ static BeamWs beam_ws(const BeamGeo &g) {
   mx(nabu_gemm_ws_bytes((int)N, (int)C, (int)SE));
   s.gemm_bytes = (gb + 255) / 256 * 256;
   s.gemm = take(s.gemm_bytes / 4 + 4);
+  if (g.ctc) {
+    const size_t T0 = g.Te[0];
+    s.cnorm = take(B * T0 * 2); s.cdelta = take(N * C);
+    for (int k = 0; k < 2; ++k) { s.cstate[k] = take(N * T0 * 2); s.cpsi[k] = take(N); s.clast[k] = take(N); }
+  }
   s.total = o;
   return s;
 }
+
+int ctc_prefix_lds_ok(int T);      // ctc_prefix.hip: the LDS of its kernels at T frames, NABU_EUNSUP with a message
 
 static int check_beam(const BeamGeo &g) {
   if (g.B <= 0 || g.U <= 0 || g.C <= 1) return fail(NABU_EINVAL, "beam search: bad dimensions");
@@ -664,6 +681,15 @@ static int check_beam(const BeamGeo &g) {
   return 0;
 }
 
+// The optional CTC operand of the *_joint entry points: absent (null) or weight 0 leaves g as it is — the loop then makes
+// exactly the launches of the plain search; otherwise g.ctc is set.
+static int beam_ctc(BeamGeo *g, const float *ctc_logits, float ctc_weight) {
+  if (!(ctc_weight >= 0.f && ctc_weight < 1.f)) return fail(NABU_EINVAL, "beam search: ctc_weight must be in [0, 1)");
+  if (!ctc_logits || ctc_weight == 0.f) return 0;
+  g->ctc = true; g->ctcw = ctc_weight;
+  return ctc_prefix_lds_ok(g->Te[0]);
+}
+
 static int beam_run(const BeamGeo &g, const BeamIO &io, void *ws, size_t ws_bytes, nabu_stream_t stream) {
   NABU_CHECK_ARG(io.out_kernel && io.out_bias && io.sequences && io.lengths && io.scores && io.num_steps && ws,
                  "beam search: null pointer");
@@ -671,6 +697,7 @@ static int beam_run(const BeamGeo &g, const BeamIO &io, void *ws, size_t ws_byte
     NABU_CHECK_ARG(io.values[m] && io.enc_len[m] && io.memory_kernel[m] && io.query_kernel[m] && io.attention_v[m] &&
                    (g.kind != 1 || (io.conv_kernel[m] && io.conv_proj[m])) && (!io.alignments[0] || io.alignments[m]),
                    "beam search: null pointer for an encoded input");
+  NABU_CHECK_ARG(!g.ctc || io.ctc_logits, "beam search: null pointer for the CTC logits");
   const BeamWs L = beam_ws(g);
   if (ws_bytes < L.total * 4) return fail(NABU_EWS, "beam search: workspace too small");
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -721,6 +748,12 @@ static int beam_run(const BeamGeo &g, const BeamIO &io, void *ws, size_t ws_byte
     NABU_HIP(hipMemsetAsync(w + L.align[cur][m], 0, (size_t)N * g.Te[m] * 4, s));
     if (g.kind == 2) NABU_TRY(first_col_one(N, g.Te[m], w + L.align[cur][m], s));
   }
+  // joint scoring: the CTC prefix state of the empty hypothesis in every slot; set cc is the current one
+  int cc = 0;
+  const int T0 = g.Te[0];
+  if (g.ctc)
+    NABU_TRY(nabu_ctc_prefix_prepare(B, W, T0, C, io.ctc_logits, io.enc_len[0], w + L.cnorm, w + L.cstate[0], w + L.cpsi[0],
+                                     wi + L.clast[0], stream));
   float *z = w + L.z, *lg = w + L.logits;
   const int32_t *big = wi + L.big;
   int32_t *par = wi + L.parent, *stay = wi + L.stay;
@@ -769,8 +802,21 @@ static int beam_run(const BeamGeo &g, const BeamIO &io, void *ws, size_t ws_byte
                                    wi + L.finished, io.scores, wi + L.ids, wi + L.all_seen, stream));
     } else {
       // expand + prune; the predicted ids are the next step's inputs
-      NABU_TRY(nabu_beam_prune(B, W, C, lg, g.temperature, g.lpw, w + L.logprobs, wi + L.lengths, wi + L.finished,
-                               wi + L.seen, wi + L.ids, par, stay, wi + L.all_seen, w + L.scratch, stream));
+      if (g.ctc) {
+        // the CTC prefix score of every (hypothesis, label), mixed into the candidates; then the survivors' states
+        NABU_TRY(nabu_ctc_prefix_score(B, W, T0, C, io.ctc_logits, io.enc_len[0], w + L.cnorm, w + L.cstate[cc], w + L.cpsi[cc],
+                                       wi + L.clast[cc], wi + L.finished, w + L.cdelta, stream));
+        NABU_TRY(nabu_beam_prune_joint(B, W, C, lg, w + L.cdelta, g.ctcw, g.temperature, g.lpw, w + L.logprobs,
+                                       wi + L.lengths, wi + L.finished, wi + L.seen, wi + L.ids, par, stay,
+                                       wi + L.all_seen, w + L.scratch, stream));
+        NABU_TRY(nabu_ctc_prefix_advance(B, W, T0, C, io.ctc_logits, io.enc_len[0], w + L.cnorm, w + L.cstate[cc],
+                                         w + L.cpsi[cc], wi + L.clast[cc], par, stay, wi + L.ids, w + L.cstate[cc ^ 1],
+                                         w + L.cpsi[cc ^ 1], wi + L.clast[cc ^ 1], stream));
+        cc ^= 1;
+      } else {
+        NABU_TRY(nabu_beam_prune(B, W, C, lg, g.temperature, g.lpw, w + L.logprobs, wi + L.lengths, wi + L.finished,
+                                 wi + L.seen, wi + L.ids, par, stay, wi + L.all_seen, w + L.scratch, stream));
+      }
       for (int n = 0; n < nl; ++n) {
         NABU_TRY(nabu_beam_gather(B, W, U, w + L.h[fresh][n], w + L.h[cur][n], par, stay, w + L.h[nxt][n], stream));
         NABU_TRY(nabu_beam_gather(B, W, U, w + L.c[fresh][n], w + L.c[cur][n], par, stay, w + L.c[nxt][n], stream));
@@ -881,8 +927,23 @@ extern "C" int nabu_beam_prune(int B, int W, int C, const float *logits, float t
   const size_t lds = 5 * (size_t)W * 4;
   NABU_TRY(lds_fits(lds, "beam_prune"));
   PruneArgs a = {B, W, C, logits, 1.f / temperature, length_penalty_w, logprobs, lengths, finished, seen,
-                 pred_ids, parent, stay, all_seen, scratch};
-  return launch_lds(beam_prune_kernel, dim3(B), dim3(DT), lds, static_cast<hipStream_t>(stream), a);
+                 pred_ids, parent, stay, all_seen, scratch, nullptr, 0.f};
+  return launch_lds(beam_prune_kernel<false>, dim3(B), dim3(DT), lds, static_cast<hipStream_t>(stream), a);
+}
+
+extern "C" int nabu_beam_prune_joint(int B, int W, int C, const float *logits, const float *delta, float ctc_weight,
+                                     float temperature, float length_penalty_w, float *logprobs, int32_t *lengths,
+                                     int32_t *finished, int32_t *seen, int32_t *pred_ids, int32_t *parent,
+                                     int32_t *stay, int32_t *all_seen, float *scratch, nabu_stream_t stream) {
+  NABU_CHECK_ARG(B > 0 && W > 0 && C > 1 && temperature > 0.f, "beam_prune_joint: bad arguments");
+  NABU_CHECK_ARG(ctc_weight >= 0.f && ctc_weight < 1.f, "beam_prune_joint: ctc_weight must be in [0, 1)");   // (false for NaN)
+  NABU_CHECK_ARG(logits && delta && logprobs && lengths && finished && seen && pred_ids && parent && stay && all_seen &&
+                 scratch, "beam_prune_joint: null pointer");
+  const size_t lds = 5 * (size_t)W * 4;
+  NABU_TRY(lds_fits(lds, "beam_prune_joint"));
+  PruneArgs a = {B, W, C, logits, 1.f / temperature, length_penalty_w, logprobs, lengths, finished, seen,
+                 pred_ids, parent, stay, all_seen, scratch, delta, ctc_weight};
+  return launch_lds(beam_prune_kernel<true>, dim3(B), dim3(DT), lds, static_cast<hipStream_t>(stream), a);
 }
 
 extern "C" int nabu_beam_gather(int B, int W, int F, const float *fresh, const float *old, const int32_t *parent,
@@ -919,11 +980,11 @@ extern "C" size_t nabu_speller_beam_ws_bytes(const nabu_beam_desc *d) {
 // the search (sample = false: scores) or the sampled decode (nll) of one encoded input
 static int decode_one(BeamGeo &g, const float *values, const int32_t *enc_len, const nabu_speller_params *p,
                       int32_t *sequences, int32_t *lengths, float *scores, float *alignments, int32_t *num_steps, void *ws,
-                      size_t ws_bytes, nabu_stream_t stream) {
+                      size_t ws_bytes, nabu_stream_t stream, const float *ctc_logits = nullptr) {
   NABU_CHECK_ARG(p, "speller_beam_search: null pointer");
   const BeamIO io = {{values}, {enc_len}, {p->memory_kernel}, {p->query_kernel}, {p->attention_v}, {p->conv_kernel},
                      {p->conv_proj}, p->out_kernel, p->out_bias, p->lstm_kernel, p->lstm_bias, {alignments},
-                     sequences, lengths, num_steps, scores};
+                     sequences, lengths, num_steps, scores, ctc_logits};
   return beam_run(g, io, ws, ws_bytes, stream);
 }
 
@@ -934,6 +995,24 @@ extern "C" int nabu_speller_beam_search(const nabu_beam_desc *d, const float *va
   BeamGeo g;
   if (int e = beam_geo(d, &g)) return e;
   return decode_one(g, values, enc_len, p, sequences, lengths, scores, alignments, num_steps, ws, ws_bytes, stream);
+}
+
+extern "C" size_t nabu_speller_beam_joint_ws_bytes(const nabu_beam_desc *d) {
+  BeamGeo g;
+  if (beam_geo(d, &g)) return 0;
+  g.ctc = true;
+  return ctc_prefix_lds_ok(g.Te[0]) ? 0 : beam_ws(g).total * 4;
+}
+
+extern "C" int nabu_speller_beam_search_joint(const nabu_beam_desc *d, const float *values, const int32_t *enc_len,
+                                              const nabu_speller_params *p, const float *ctc_logits, float ctc_weight,
+                                              int32_t *sequences, int32_t *lengths, float *scores, float *alignments,
+                                              int32_t *num_steps, void *ws, size_t ws_bytes, nabu_stream_t stream) {
+  BeamGeo g;
+  if (int e = beam_geo(d, &g)) return e;
+  if (int e = beam_ctc(&g, ctc_logits, ctc_weight)) return e;
+  return decode_one(g, values, enc_len, p, sequences, lengths, scores, alignments, num_steps, ws, ws_bytes, stream,
+                    ctc_logits);
 }
 
 extern "C" size_t nabu_speller_sample_ws_bytes(const nabu_beam_desc *d) {
@@ -959,10 +1038,11 @@ extern "C" size_t nabu_speller_multi_beam_ws_bytes(const nabu_multi_beam_desc *d
 // the same over M encoded inputs
 static int decode_multi(BeamGeo &g, const float *const *values, const int32_t *const *enc_len,
                         const nabu_speller_multi_params *p, int32_t *sequences, int32_t *lengths, float *scores,
-                        float *const *alignments, int32_t *num_steps, void *ws, size_t ws_bytes, nabu_stream_t stream) {
+                        float *const *alignments, int32_t *num_steps, void *ws, size_t ws_bytes, nabu_stream_t stream,
+                        const float *ctc_logits = nullptr) {
   NABU_CHECK_ARG(values && enc_len && p, "speller_multi_beam_search: null pointer");
   BeamIO io = {{}, {}, {}, {}, {}, {}, {}, p->out_kernel, p->out_bias, p->lstm_kernel, p->lstm_bias, {},
-               sequences, lengths, num_steps, scores};
+               sequences, lengths, num_steps, scores, ctc_logits};
   for (int m = 0; m < g.M; ++m) {
     io.values[m] = values[m]; io.enc_len[m] = enc_len[m];
     io.memory_kernel[m] = p->memory_kernel[m]; io.query_kernel[m] = p->query_kernel[m];
@@ -983,6 +1063,26 @@ extern "C" int nabu_speller_multi_beam_search(const nabu_multi_beam_desc *d, con
   BeamGeo g;
   if (int e = beam_geo(d, &g)) return e;
   return decode_multi(g, values, enc_len, p, sequences, lengths, scores, alignments, num_steps, ws, ws_bytes, stream);
+}
+
+extern "C" size_t nabu_speller_multi_beam_joint_ws_bytes(const nabu_multi_beam_desc *d) {
+  BeamGeo g;
+  if (beam_geo(d, &g)) return 0;
+  g.ctc = true;
+  return ctc_prefix_lds_ok(g.Te[0]) ? 0 : beam_ws(g).total * 4;
+}
+
+extern "C" int nabu_speller_multi_beam_search_joint(const nabu_multi_beam_desc *d, const float *const *values,
+                                                    const int32_t *const *enc_len, const nabu_speller_multi_params *p,
+                                                    const float *ctc_logits, float ctc_weight, int32_t *sequences,
+                                                    int32_t *lengths, float *scores, float *const *alignments,
+                                                    int32_t *num_steps, void *ws, size_t ws_bytes,
+                                                    nabu_stream_t stream) {
+  BeamGeo g;
+  if (int e = beam_geo(d, &g)) return e;
+  if (int e = beam_ctc(&g, ctc_logits, ctc_weight)) return e;
+  return decode_multi(g, values, enc_len, p, sequences, lengths, scores, alignments, num_steps, ws, ws_bytes, stream,
+                      ctc_logits);
 }
 
 extern "C" size_t nabu_speller_multi_sample_ws_bytes(const nabu_multi_beam_desc *d) {

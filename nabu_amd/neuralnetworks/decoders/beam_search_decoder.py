@@ -14,6 +14,7 @@ from nabu_amd import variables as vs
 from nabu_amd.autodiff import SeqLen
 from nabu_amd.neuralnetworks.decoders import decoder
 from nabu_amd.neuralnetworks.models.ed_decoders import rnn_decoder
+from nabu_amd.neuralnetworks.trainers import loss_functions
 
 
 class BeamSearchDecoder(decoder.Decoder):
@@ -23,6 +24,12 @@ class BeamSearchDecoder(decoder.Decoder):
     def __init__(self, conf, model):
         super(BeamSearchDecoder, self).__init__(conf, model)
         self.alphabet = self.conf['alphabet'].split(' ')
+        # ctc_weight (an extension key like the trainer's: absent from the defaults file, 0 when absent): the weight of
+        # the CTC prefix score of the model's CTC head in every hypothesis' score (joint CTC/attention decoding)
+        self.ctc_weight = loss_functions.ctc_weight_key(self.conf)
+        if self.ctc_weight and not getattr(model.decoder, 'ctc_head', False):
+            raise ValueError('ctc_weight = %g needs a model with a CTC head: set ctc_head = True in the [decoder] '
+                             'section of the model' % self.ctc_weight)
 
     def _keep_alignments(self):
         return self.conf.get('visualize_alignments') == 'True'
@@ -41,10 +48,14 @@ class BeamSearchDecoder(decoder.Decoder):
                 cell = model.decoder.create_cell(encoded, encoded_seq_length, False)
                 # every encoded input, in the order of the cell's attention mechanisms
                 names = list(encoded.keys())
+                joint = {}
+                if self.ctc_weight > 0:        # (without the key: the call it always was)
+                    joint = dict(ctc_logits=model.decoder.ctc_logits(encoded, encoded_seq_length)[0],
+                                 ctc_weight=self.ctc_weight)
                 res = rnn_decoder.beam_search(
                     cell, [encoded[e] for e in names], [encoded_seq_length[e] for e in names], beam_width=int(self.conf['beam_width']),
                     max_steps=int(self.conf['max_steps']), length_penalty=float(self.conf['length_penalty']),
-                    temperature=float(self.conf['temperature']), with_alignments=self._keep_alignments())
+                    temperature=float(self.conf['temperature']), with_alignments=self._keep_alignments(), **joint)
         if isinstance(res[3], list):       # several inputs: the alignments per input name
             res = res[:3] + ({n: a for n, a in zip(names, res[3])},)
         return {output_name: res}

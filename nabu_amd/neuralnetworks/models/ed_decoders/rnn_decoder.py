@@ -211,7 +211,8 @@ dynamic_decode.events = None
 def _free_run(which, cell, encoded, encoded_seq_length, beam_width, max_steps, length_penalty, temperature,
               with_alignments, *extra):
     """The call beam_search and sample share: `which` is 'beam' (nabu_speller[_multi]_beam_search) or 'sample'
-    (nabu_speller[_multi]_sample, beam_width 1, `extra` = seed, offset).  Returns (sequences [B,W,time] int32,
+    (nabu_speller[_multi]_sample, beam_width 1, `extra` = seed, offset) or 'beam_joint'
+    (nabu_speller[_multi]_beam_search_joint, `extra` = the CTC head's logits, ctc_weight).  Returns (sequences [B,W,time] int32,
     lengths [B,W] int32, scores or nll [B,W], [alignments [B,W,time,Te_m] per memory] or None, the binding)."""
     abi, encoded, encoded_seq_length = _memories(encoded, encoded_seq_length)
     dev = encoded[0].device
@@ -224,7 +225,7 @@ def _free_run(which, cell, encoded, encoded_seq_length, beam_width, max_steps, l
     desc = abi.desc(abi.beam_desc_cls, Tes, Es, B=B, U=U, C=C, num_layers=nl, kind=mech.kind, K=mech.filtersize,
                     F=mech.numfilt, prob_fn=mech.prob_fn, beam_width=W, max_steps=S,
                     length_penalty=float(length_penalty), temperature=float(temperature))
-    name = 'beam_search' if which == 'beam' else which
+    name = {'beam': 'beam_search', 'beam_joint': 'beam_search_joint'}.get(which, which)
     ws_bytes = abi.fn(which + '_ws_bytes')(ctypes.byref(desc))
     if ws_bytes == 0:
         raise _hip.NabuHipError('%s: unsupported shape: %s' % (name, _hip.lib().nabu_last_error().decode()))
@@ -245,16 +246,29 @@ def _free_run(which, cell, encoded, encoded_seq_length, beam_width, max_steps, l
 
 
 def beam_search(cell, encoded, encoded_seq_length, beam_width, max_steps, length_penalty=0.0,
-                temperature=1.0, with_alignments=True):
+                temperature=1.0, with_alignments=True, ctc_logits=None, ctc_weight=0.0):
     """Beam search over the projected attention cell (components/beam_search_decoder.py:68-451
     under dynamic_decode): ONE call into the C ABI (nabu_speller_beam_search), whose C++ driver runs
     the cell kernels on B*beam_width rows, prunes and gathers on the device, and stops as the
     reference's dynamic_decode does.  encoded [B,Te,E] (rows >= length zero).
     Returns (sequences [B,W,time] int32, lengths [B,W] int32, scores [B,W], alignments
     [B,W,time,Te] or None).  encoded / encoded_seq_length may be lists (one entry per attention mechanism): several
-    memories run nabu_speller_multi_beam_search and return the alignments as a list of [B,W,time,Te_m], one per memory."""
-    seq, lengths, scores, aligns, abi = _free_run('beam', cell, encoded, encoded_seq_length, beam_width, max_steps,
-                                                  length_penalty, temperature, with_alignments)
+    memories run nabu_speller_multi_beam_search and return the alignments as a list of [B,W,time,Te_m], one per memory.
+    ctc_logits [B,Te,C] (the CTC head's logits on the FIRST encoded input) with ctc_weight in (0, 1): the joint
+    CTC/attention search of nabu_speller[_multi]_beam_search_joint; without them the plain entry point is called."""
+    ctc_weight = float(ctc_weight)
+    if not 0.0 <= ctc_weight < 1.0:
+        raise ValueError('ctc_weight must be in [0, 1), got %r' % ctc_weight)
+    if ctc_weight > 0 and ctc_logits is None:
+        raise ValueError('ctc_weight %g needs the logits of a CTC head (ctc_logits)' % ctc_weight)
+    which, extra = 'beam', ()
+    if ctc_logits is not None:
+        if ctc_logits.dtype != torch.float32:
+            raise _hip.NabuHipError('ctc_logits must be float32, got %s' % ctc_logits.dtype)
+        ctc_logits = ctc_logits.contiguous()
+        which, extra = 'beam_joint', (_hip.ptr(ctc_logits), ctypes.c_float(ctc_weight))
+    seq, lengths, scores, aligns, abi = _free_run(which, cell, encoded, encoded_seq_length, beam_width, max_steps,
+                                                  length_penalty, temperature, with_alignments, *extra)
     return seq, lengths, scores, (abi.per_memory(aligns) if with_alignments else None)
 
 
@@ -286,6 +300,20 @@ def decoder_inputs():
 class RNNDecoder(ed_decoder.EDDecoder, metaclass=ABCMeta):
     '''a recurrent decoder: _decode runs the cell built by create_cell over the targets'''
 
+    supports_ctc_head = True
+
+    def ctc_logits(self, encoded, encoded_seq_length):
+        '''the CTC head (ctc_head = True in [decoder]) on the first encoded input: one linear layer to the output's
+        classes, whose last one — the end-of-sequence label of the cell — is the CTC blank.  Called inside the
+        decoder's scope (the variables are <scope>/ctc_outlayer/{weights,biases}); needs no targets, so a decoder
+        can run it next to the cell.  Returns (logits [B,Te,C], their lengths).'''
+        if not self.ctc_head:
+            raise ValueError('this decoder has no CTC head (ctc_head = True in the [decoder] section)')
+        from nabu_amd.neuralnetworks.models.ed_decoders import dnn_decoder
+        first = list(encoded.keys())[0]
+        return (dnn_decoder.linear(encoded[first], list(self.output_dims.values())[0], 'ctc_outlayer'),
+                encoded_seq_length[first])
+
     def _decode(self, encoded, encoded_seq_length, targets, target_seq_length, is_training):
         # only the first target / output is used (rnn_decoder.py:40-47)
         tname = list(targets.keys())[0]
@@ -296,7 +324,11 @@ class RNNDecoder(ed_decoder.EDDecoder, metaclass=ABCMeta):
         logits, logit_seq_length = dynamic_decode(
             rnn_cell, [encoded[e] for e in enames], [encoded_seq_length[e] for e in enames], targets[tname],
             target_seq_length[tname], float(self.conf['sample_prob']), is_training)
-        return {output_name: logits}, {output_name: logit_seq_length}, ()
+        outputs, lengths = {output_name: logits}, {output_name: logit_seq_length}
+        if self.ctc_head:
+            # beside the output: losses and decoders index by target name and never see this key
+            outputs[output_name + '_ctc'], lengths[output_name + '_ctc'] = self.ctc_logits(encoded, encoded_seq_length)
+        return outputs, lengths, ()
 
     @abstractmethod
     def create_cell(self, encoded, encoded_seq_length, is_training):

@@ -44,28 +44,49 @@ def label_smoothing_key(conf):
     return value
 
 
-def factory(loss_function, label_smoothing=0.0):
+def ctc_weight_key(conf):
+    """the `ctc_weight` key of the [trainer] section (a build addition like label_smoothing: absent from the defaults
+    file, 0 when absent): the weight w of the auxiliary CTC loss on the model's CTC head (ctc_head = True in the model's
+    [decoder] section), loss = (1 - w) * attention loss + w * CTC loss, 0 <= w < 1"""
+    text = str(conf.get('ctc_weight', '0')).strip()
+    try:
+        value = float(text)
+    except ValueError:
+        raise ValueError('ctc_weight must be a number, got %r' % text)
+    if not 0.0 <= value < 1.0:                     # (false for nan)
+        raise ValueError('ctc_weight must be in [0, 1), got %r' % text)
+    return value
+
+
+def factory(loss_function, label_smoothing=0.0, ctc_weight=0.0):
     '''get a callable loss(targets, logits, logit_seq_length, target_seq_length)
     (reference loss_functions.py:7-28).  label_smoothing (not the reference's: the [trainer] key of that name) is
     bound into the cross-entropy losses: every output is scored against (1 - e) * onehot + e / C over its own C
     classes.  The LossEvaluator asks for its loss without it, so validation losses are the unsmoothed quantity
-    whatever the training run smooths with.'''
-    label_smoothing = float(label_smoothing)
+    whatever the training run smooths with.  ctc_weight (the [trainer] key of that name) is bound into them the same
+    way: (1 - w) * the loss + w * the CTC loss of the model's CTC head; the LossEvaluator asks without it as well, so
+    validation is the attention loss, comparable across weights.'''
+    label_smoothing, ctc_weight = float(label_smoothing), float(ctc_weight)
     if not 0.0 <= label_smoothing < 1.0:
         raise ValueError('label_smoothing must be in [0, 1), got %r' % label_smoothing)
+    if not 0.0 <= ctc_weight < 1.0:
+        raise ValueError('ctc_weight must be in [0, 1), got %r' % ctc_weight)
+    # (without the keys: the function itself, as ever)
+    extra = dict(label_smoothing=label_smoothing) if label_smoothing else {}
+    if ctc_weight:
+        extra['ctc_weight'] = ctc_weight
     if loss_function == 'average_cross_entropy':
-        if label_smoothing:
-            return functools.partial(average_cross_entropy, label_smoothing=label_smoothing)
-        return average_cross_entropy
+        return functools.partial(average_cross_entropy, **extra) if extra else average_cross_entropy
     elif loss_function == 'CTC':
         if label_smoothing:
             raise ValueError('label_smoothing is defined for the cross-entropy losses only (average_cross_entropy, '
                              'sum_cross_entropy), not for CTC')
+        if ctc_weight:
+            raise ValueError('ctc_weight adds a CTC term to the cross-entropy losses (average_cross_entropy, '
+                             'sum_cross_entropy); loss = CTC is that term alone')
         return CTC
     elif loss_function == 'sum_cross_entropy':
-        if label_smoothing:
-            return functools.partial(sum_cross_entropy, label_smoothing=label_smoothing)
-        return sum_cross_entropy
+        return functools.partial(sum_cross_entropy, **extra) if extra else sum_cross_entropy
     elif loss_function in ('average_sigmoid_cross_entropy', 'marigin'):
         raise Exception('loss function %s is outside the MI355X hot path' % loss_function)
     else:
@@ -91,6 +112,25 @@ def _total(losses):
     return total
 
 
+def _ctc_term(t, targets, logits, logit_seq_length, target_seq_length, ctc_weight):
+    '''w * mean_b(-log p_ctc(targets[b, :target_len[b] - 1] | the CTC head's logits)): the targets without their end
+    label, which is the head's blank.  The status word goes on pending_status, so an utterance whose targets do not fit
+    into its encoded length raises like any CTC loss.'''
+    key = t + '_ctc'
+    if key not in logits:
+        raise ValueError('ctc_weight needs a model with a CTC head (ctc_head = True in the [decoder] section): no '
+                         'output %r' % key)
+    lg = logits[key]
+    B = lg.shape[0]
+    lsl, tsl = SeqLen.wrap(logit_seq_length[key], lg.device), SeqLen.wrap(target_seq_length[t], lg.device)
+    no_eos = (tsl.dev - 1).clamp_(min=0)
+    nll, dlogits, status = hip.ctc_loss_grad(lg.contiguous(), lsl.dev, _labels(targets[t]), no_eos, ctc_weight / B)
+    pending_status.append(status)
+    loss = hip.sum_(nll, ctc_weight / B)
+    record([lg], [loss], lambda g, d=dlogits: [d])
+    return loss
+
+
 def CTC(targets, logits, logit_seq_length, target_seq_length):
     '''CTC loss (reference loss_functions.py:180-214): mean over the batch of
     -log p(targets | logits), summed over the outputs; blank = last class.'''
@@ -108,35 +148,43 @@ def CTC(targets, logits, logit_seq_length, target_seq_length):
     return _total(losses)
 
 
-def average_cross_entropy(targets, logits, logit_seq_length, target_seq_length, label_smoothing=0.0):
+def average_cross_entropy(targets, logits, logit_seq_length, target_seq_length, label_smoothing=0.0, ctc_weight=0.0):
     '''cross entropy averaged over timesteps (reference loss_functions.py:155-165):
-    mean_b( sum_{t<logit_len} xent / target_len ), summed over the outputs.  label_smoothing: see factory.'''
+    mean_b( sum_{t<logit_len} xent / target_len ), summed over the outputs.  label_smoothing, ctc_weight: see
+    factory.'''
     losses = []
     for t in targets:
         lg = logits[t]
         B = lg.shape[0]
         lsl, tsl = SeqLen.wrap(logit_seq_length[t], lg.device), SeqLen.wrap(target_seq_length[t], lg.device)
-        per_utt, dlogits = _xent(lg.contiguous(), _labels(targets[t]), lsl.dev, tsl.dev, 1.0 / B, label_smoothing)
-        loss = hip.sum_(per_utt, 1.0 / B)
+        scale = (1.0 - ctc_weight) / B if ctc_weight else 1.0 / B
+        per_utt, dlogits = _xent(lg.contiguous(), _labels(targets[t]), lsl.dev, tsl.dev, scale, label_smoothing)
+        loss = hip.sum_(per_utt, scale)
         record([lg], [loss], lambda g, d=dlogits: [d])
         losses.append(loss)
+        if ctc_weight:
+            losses.append(_ctc_term(t, targets, logits, logit_seq_length, target_seq_length, ctc_weight))
     return _total(losses)
 
 
-def sum_cross_entropy(targets, logits, logit_seq_length, target_seq_length, label_smoothing=0.0):
+def sum_cross_entropy(targets, logits, logit_seq_length, target_seq_length, label_smoothing=0.0, ctc_weight=0.0):
     '''cross entropy summed over timesteps (reference loss_functions.py:142-153): the mask is the
     TARGET length here and nothing is divided: mean_b( sum_{t<target_len} xent ), summed over the
-    outputs.  Same kernel as average_cross_entropy with a divisor of one.  label_smoothing: see factory.'''
+    outputs.  Same kernel as average_cross_entropy with a divisor of one.  label_smoothing, ctc_weight: see
+    factory.'''
     losses = []
     for t in targets:
         lg = logits[t]
         B = lg.shape[0]
         tsl = SeqLen.wrap(target_seq_length[t], lg.device)
         ones = torch.ones_like(tsl.dev)
-        per_utt, dlogits = _xent(lg.contiguous(), _labels(targets[t]), tsl.dev, ones, 1.0 / B, label_smoothing)
-        loss = hip.sum_(per_utt, 1.0 / B)
+        scale = (1.0 - ctc_weight) / B if ctc_weight else 1.0 / B
+        per_utt, dlogits = _xent(lg.contiguous(), _labels(targets[t]), tsl.dev, ones, scale, label_smoothing)
+        loss = hip.sum_(per_utt, scale)
         record([lg], [loss], lambda g, d=dlogits: [d])
         losses.append(loss)
+        if ctc_weight:
+            losses.append(_ctc_term(t, targets, logits, logit_seq_length, target_seq_length, ctc_weight))
     return _total(losses)
 
 

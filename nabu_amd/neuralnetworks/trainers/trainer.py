@@ -234,6 +234,11 @@ class Trainer(object, metaclass=ABCMeta):
         self.label_smoothing = loss_functions.label_smoothing_key(self.conf)
         if self.label_smoothing:
             loss_functions.factory(self.conf['loss'], self.label_smoothing)
+        # ctc_weight (an extension key as well): the weight of the auxiliary CTC loss on the model's CTC head, validated
+        # here with the loss it cannot apply to (CTC) and, below, with the model that must carry the head
+        self.ctc_weight = loss_functions.ctc_weight_key(self.conf)
+        if self.ctc_weight:
+            loss_functions.factory(self.conf['loss'], self.label_smoothing, self.ctc_weight)
         # weight_noise / weight_noise_start_step (extension keys as well): validated here for the same reason
         self.weight_noise, self.weight_noise_start_step = weight_noise_keys(self.conf)
         self.flat_clean = self.noise_table = None
@@ -251,6 +256,9 @@ class Trainer(object, metaclass=ABCMeta):
         self.last_weight_noise = None      # the (seed, offset) of the latest noisy step
         self._noisy = False                # True from a step's noise launch until its optimiser has run
         self.model = Model(conf=modelconf, trainlabels=int(self.conf['trainlabels']), constraint=None)
+        if self.ctc_weight and not self.model.decoder.ctc_head:
+            raise ValueError('ctc_weight = %g needs a model with a CTC head: set ctc_head = True in the [decoder] '
+                             'section of the model' % self.ctc_weight)
         if bool(getattr(server, 'shared_devices', False)):
             # ranks that share a GPU (more ranks than devices on this node: first-contact runs, tests): the persistent
             # recurrent kernels need every CU of the device for their own workgroups, two processes' launches would each
@@ -275,7 +283,7 @@ class Trainer(object, metaclass=ABCMeta):
         outputs['num_steps'] = self.data.num_batches() * int(self.conf['num_epochs'])
         if self.accumulate > 1:            # updates, A batches each: the data seen stays that of num_epochs
             outputs['num_steps'] = max(1, outputs['num_steps'] // self.accumulate)
-        self.loss_fn = loss_functions.factory(self.conf['loss'], self.label_smoothing)
+        self.loss_fn = loss_functions.factory(self.conf['loss'], self.label_smoothing, self.ctc_weight)
         self.flat = self.flat_grad = self.adam_m = self.adam_v = None
         self.buckets = None
         # validation part (reference trainer.py:189-265): bookkeeping 'variables' of the

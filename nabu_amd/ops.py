@@ -979,6 +979,69 @@ def beam_prune(logits, logprobs, lengths, finished, seen, temperature=1.0, lengt
     return pred, parent, stay, all_seen
 
 
+def beam_prune_joint(logits, delta, ctc_weight, logprobs, lengths, finished, seen, temperature=1.0, length_penalty=0.0):
+    """beam_prune with the CTC term: delta [B,W,C] from ctc_prefix_score, weighted by ctc_weight in [0, 1)"""
+    B, W, C = logits.shape
+    dev = logits.device
+    pred = torch.empty((B, W), dtype=torch.int32, device=dev)
+    parent, stay = torch.empty_like(pred), torch.empty_like(pred)
+    all_seen = torch.empty((B,), dtype=torch.int32, device=dev)
+    scratch = torch.empty((B, W * C + W), dtype=torch.float32, device=dev)
+    check(_hip.lib().nabu_beam_prune_joint(B, W, C, ptr(logits.contiguous()), ptr(_f32(delta, 'delta').contiguous()),
+                                           float(ctc_weight), float(temperature), float(length_penalty), ptr(logprobs),
+                                           ptr(lengths), ptr(finished), ptr(seen), ptr(pred), ptr(parent), ptr(stay),
+                                           ptr(all_seen), ptr(scratch), stream()), 'nabu_beam_prune_joint')
+    return pred, parent, stay, all_seen
+
+
+class CtcPrefixState(object):
+    """The CTC prefix-scoring state of a beam (ctc_prefix.hip): state [B,W,T,2] = (r_n, r_b) per frame, psi [B,W],
+    last [B,W] (-1: the empty hypothesis), with the logits [B,T,C], their lengths and the per-frame normalisers
+    norm [B,T,2] they belong to"""
+
+    def __init__(self, logits, enc_len, norm, W, state=None, psi=None, last=None):
+        B, T, _ = logits.shape
+        dev = logits.device
+        self.logits, self.enc_len, self.norm, self.W = logits, enc_len, norm, int(W)
+        self.state = torch.empty((B, W, T, 2), dtype=torch.float32, device=dev) if state is None else state
+        self.psi = torch.empty((B, W), dtype=torch.float32, device=dev) if psi is None else psi
+        self.last = torch.empty((B, W), dtype=torch.int32, device=dev) if last is None else last
+
+    def _dims(self):
+        B, T, C = self.logits.shape
+        return B, self.W, T, C
+
+
+def ctc_prefix_prepare(logits, enc_len, beam_width):
+    """once per search: the normalisers of logits [B,T,C] and the state of the empty hypothesis in all beam slots"""
+    logits = _f32(logits, 'logits').contiguous()
+    B, T, _ = logits.shape
+    norm = torch.empty((B, T, 2), dtype=torch.float32, device=logits.device)
+    s = CtcPrefixState(logits, enc_len, norm, beam_width)
+    check(_hip.lib().nabu_ctc_prefix_prepare(*s._dims(), ptr(logits), ptr(enc_len), ptr(norm), ptr(s.state), ptr(s.psi),
+                                             ptr(s.last), stream()), 'nabu_ctc_prefix_prepare')
+    return s
+
+
+def ctc_prefix_score(s, finished):
+    """delta [B,W,C] = psi(g.c) - psi(g) of every hypothesis of the beam and every class (C-1: the end label)"""
+    B, W, T, C = s._dims()
+    delta = torch.empty((B, W, C), dtype=torch.float32, device=s.logits.device)
+    check(_hip.lib().nabu_ctc_prefix_score(B, W, T, C, ptr(s.logits), ptr(s.enc_len), ptr(s.norm), ptr(s.state), ptr(s.psi),
+                                           ptr(s.last), ptr(finished), ptr(delta), stream()), 'nabu_ctc_prefix_score')
+    return delta
+
+
+def ctc_prefix_advance(s, parent, stay, pred):
+    """the state of the survivors of a pruning step (parent, stay, pred [B,W] as beam_prune returns them): a new
+    CtcPrefixState, `s` is left as it was"""
+    n = CtcPrefixState(s.logits, s.enc_len, s.norm, s.W)
+    check(_hip.lib().nabu_ctc_prefix_advance(*s._dims(), ptr(s.logits), ptr(s.enc_len), ptr(s.norm), ptr(s.state),
+                                             ptr(s.psi), ptr(s.last), ptr(parent), ptr(stay), ptr(pred), ptr(n.state),
+                                             ptr(n.psi), ptr(n.last), stream()), 'nabu_ctc_prefix_advance')
+    return n
+
+
 def beam_gather(fresh, old, parent, stay):
     B, W, F = fresh.shape
     dst = torch.empty_like(fresh)
