@@ -956,6 +956,28 @@ int nabu_ctc_beam_search(int B, int T, int C, int beam_width, int merge_repeated
                          const int32_t *logit_len, int32_t *out_ids, int32_t *out_len,
                          float *out_logprob, void *ws, size_t ws_bytes, nabu_stream_t stream);
 
+/* Label n-gram language model fusion (both beam searches).  The model is a dense table of log-probabilities
+ * lm_table [C^(lm_order-1), C] float32 on the device: row ctx = the previous lm_order-1 symbols as a base-C number, the
+ * most recent symbol least significant; symbol C-1 is the boundary (as a context symbol the start, as a predicted
+ * symbol the end of the sequence — the index of the CTC blank and of the Speller's start/end label).  The context of
+ * the empty hypothesis is every digit C-1; next(ctx, c) = (ctx*C + c) mod C^(lm_order-1); lm_order 1 has one row.
+ * lm_order < 1 is NABU_EINVAL, a table of more than 2^24 entries (64 MiB) NABU_EUNSUP; weights must be finite, >= 0.
+ *
+ * nabu_ctc_beam_search_lm: nabu_ctc_beam_search with the semantics of TensorFlow's CTC beam scorer hooks
+ * (GetStateExpansionScore / GetStateEndExpansionScore), alpha = lm_weight, beta = insertion_bonus (finite):
+ *   a transition that APPENDS label c to prefix g adds alpha * lm_table[ctx(g), c] + beta — the expansion candidates
+ *   and the parent's contribution to a prefix already in the beam;
+ *   staying in a prefix (blank, the repeated-label self loop) adds nothing;
+ *   after the last frame the beam is ranked by total + alpha * lm_table[ctx, C-1], which is out_logprob.
+ * merge_repeated acts on the output labelling only; the LM context is the unmerged prefix.  A tree node keeps two more
+ * words (context, the term it entered with): nabu_ctc_beam_lm_ws_bytes.  With lm_weight = insertion_bonus = 0 the
+ * outputs are those of nabu_ctc_beam_search, bit for bit.  The kernel is a second instantiation of the same body. */
+size_t nabu_ctc_beam_lm_ws_bytes(int B, int T, int C, int beam_width);
+int nabu_ctc_beam_search_lm(int B, int T, int C, int beam_width, int merge_repeated, const float *logits,
+                            const int32_t *logit_len, const float *lm_table, int lm_order, float lm_weight,
+                            float insertion_bonus, int32_t *out_ids, int32_t *out_len, float *out_logprob, void *ws,
+                            size_t ws_bytes, nabu_stream_t stream);
+
 /* tf.edit_distance(hyp, truth, normalize=False) per utterance (ctc_decoder.py:112-118,
  * decoders/beam_search_decoder.py:176-179): Levenshtein distance of hyp[b,:hyp_len[b]] and
  * truth[b,:truth_len[b]] (negative lengths count as 0); dist [B] int32. */
@@ -1086,6 +1108,43 @@ int nabu_speller_multi_beam_search_joint(const nabu_multi_beam_desc *d, const fl
                                          const float *ctc_logits, float ctc_weight, int32_t *sequences,
                                          int32_t *lengths, float *scores, float *const *alignments_host,
                                          int32_t *num_steps, void *ws, size_t ws_bytes, nabu_stream_t stream);
+
+/* nabu_beam_prune with the label n-gram term (shallow fusion, ESPnet's lm_weight) and, with delta non-NULL, the CTC
+ * term of nabu_beam_prune_joint: a live beam's candidate log-probability is
+ *   logprobs[w] + (1 - ctc_weight) * att + ctc_weight * delta[w,c] + lm_weight * lm_table[ctx_in[w], c]
+ * (att = logits[w,c] / temperature - logsumexp; delta NULL: att alone).  Finished beams, "stay" candidates, the length
+ * penalty, the tie rule and every output as nabu_beam_prune (one kernel body).  ctx_in [B,W] are the beams' contexts;
+ * ctx_out [B,W] (another buffer) receives the survivors': a "stay" survivor keeps its parent's, any other gets
+ * next(ctx_in[parent], pred).  With lm_weight 0 the outputs are those of nabu_beam_prune_joint (delta NULL:
+ * nabu_beam_prune), bit for bit. */
+int nabu_beam_prune_lm(int B, int W, int C, const float *logits, const float *delta, float ctc_weight,
+                       const float *lm_table, int lm_order, float lm_weight, const int32_t *ctx_in, int32_t *ctx_out,
+                       float temperature, float length_penalty, float *logprobs, int32_t *lengths, int32_t *finished,
+                       int32_t *seen, int32_t *pred_ids, int32_t *parent, int32_t *stay, int32_t *all_seen,
+                       float *scratch, nabu_stream_t stream);
+/* The beam searches with every optional operand in one struct: the CTC operand of the *_joint entry points and the
+ * label n-gram.  An operand that is NULL or has weight 0 is off, and the search then makes exactly the launches it
+ * makes without it; the LM adds no launch per step (the lookup is in the prune, which also carries the contexts in a
+ * double-buffered [B,W] int32 pair).  Scores are the fused log-probabilities under the same length penalty. */
+typedef struct {
+  uint32_t size;
+  const float *ctc_logits;   /* [B,Te,C] of the first encoded input, or NULL */
+  float ctc_weight;          /* in [0, 1) */
+  const float *lm_table;     /* [C^(lm_order-1), C], or NULL */
+  int32_t lm_order;
+  float lm_weight;           /* finite, >= 0 */
+} nabu_beam_search_opts;
+size_t nabu_speller_beam_ex_ws_bytes(const nabu_beam_desc *d, const nabu_beam_search_opts *o);
+int nabu_speller_beam_search_ex(const nabu_beam_desc *d, const float *values, const int32_t *enc_len,
+                                const nabu_speller_params *p, const nabu_beam_search_opts *o, int32_t *sequences,
+                                int32_t *lengths, float *scores, float *alignments, int32_t *num_steps, void *ws,
+                                size_t ws_bytes, nabu_stream_t stream);
+size_t nabu_speller_multi_beam_ex_ws_bytes(const nabu_multi_beam_desc *d, const nabu_beam_search_opts *o);
+int nabu_speller_multi_beam_search_ex(const nabu_multi_beam_desc *d, const float *const *values_host,
+                                      const int32_t *const *enc_len_host, const nabu_speller_multi_params *p,
+                                      const nabu_beam_search_opts *o, int32_t *sequences, int32_t *lengths,
+                                      float *scores, float *const *alignments_host, int32_t *num_steps, void *ws,
+                                      size_t ws_bytes, nabu_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Host-side helper of the on-disk data path (host memory, as the `_host` feature queries below):

@@ -199,6 +199,13 @@ SIGNATURES = {
     'nabu_speller_beam_search_joint': (_i, [_vp] * 5 + [_f] + [_vp] * 6 + [_sz, _vp]),
     'nabu_speller_multi_beam_joint_ws_bytes': (_sz, [_vp]),
     'nabu_speller_multi_beam_search_joint': (_i, [_vp] * 5 + [_f] + [_vp] * 6 + [_sz, _vp]),
+    'nabu_ctc_beam_lm_ws_bytes': (_sz, [_i, _i, _i, _i]),
+    'nabu_ctc_beam_search_lm': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'nabu_beam_prune_lm': (_i, [_i, _i, _i, _vp, _vp, _f, _vp, _i, _f, _vp, _vp, _f, _f] + [_vp] * 9 + [_vp]),
+    'nabu_speller_beam_ex_ws_bytes': (_sz, [_vp, _vp]),
+    'nabu_speller_beam_search_ex': (_i, [_vp] * 11 + [_sz, _vp]),
+    'nabu_speller_multi_beam_ex_ws_bytes': (_sz, [_vp, _vp]),
+    'nabu_speller_multi_beam_search_ex': (_i, [_vp] * 11 + [_sz, _vp]),
     'nabu_sample_advance': (_i, [_i, _i, _vp, _c.c_ulonglong, _c.c_ulonglong, _i, _i] + [_vp] * 6 + [_vp]),
     'nabu_speller_sample_ws_bytes': (_sz, [_vp]),
     'nabu_speller_sample': (_i, [_vp] * 4 + [_c.c_ulonglong, _c.c_ulonglong] + [_vp] * 6 + [_sz, _vp]),
@@ -313,6 +320,15 @@ class BeamDesc(_c.Structure):
                                           ('B', 'Te', 'E', 'U', 'C', 'num_layers', 'kind', 'K', 'F', 'prob_fn',
                                            'beam_width', 'max_steps')] + \
                [('length_penalty', _c.c_float), ('temperature', _c.c_float)]
+
+
+class BeamSearchOpts(_c.Structure):
+    """nabu_beam_search_opts: the optional operands of nabu_speller[_multi]_beam_search_ex"""
+    _fields_ = [('size', _c.c_uint32), ('ctc_logits', _c.c_void_p), ('ctc_weight', _c.c_float),
+                ('lm_table', _c.c_void_p), ('lm_order', _c.c_int32), ('lm_weight', _c.c_float)]
+
+
+LM_MAX_ENTRIES = 1 << 24        # entries of a label n-gram table the C side accepts (64 MiB)
 
 
 class SpellerPtrs(_c.Structure):

@@ -20,6 +20,7 @@
 #include <float.h>
 #include <limits.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -74,7 +75,7 @@ __device__ __forceinline__ unsigned key_image(float x) {
 // The `want` best of keys[0..n) by (value desc, index asc), dead keys (-inf/NaN) never: writes their
 // indices best-first to sel[] and returns how many there are (uniform).  One barrier-synchronised
 // routine for the whole workgroup; scratch: hist[256], list_u/list_i[want], ties[n], sc[8].
-__device__ int select_best(const float *keys, int n, int want, int *hist, unsigned *list_u, int *list_i,
+__device__ __forceinline__ int select_best(const float *keys, int n, int want, int *hist, unsigned *list_u, int *list_i,
                            int *ties, int *sel, int *sc) {
   const int tid = threadIdx.x, lane = tid & 63;
   unsigned prefix = 0;
@@ -169,11 +170,27 @@ struct CtcBeamArgs {
   const int32_t *len;
   int32_t *out_ids, *out_len;
   float *out_lp;
-  int32_t *nodes;   // per utterance: parent[NN], label[NN], slot[NN], children[NN*(C-1)]
+  int32_t *nodes;   // per utterance: parent[NN], label[NN], slot[NN], children[NN*(C-1)]; LM: then ctx[NN], term[NN]
   size_t per_utt;   // int32 words per utterance
 };
+// LM: the label n-gram table [nctx, C] (log-probabilities), nctx = C^(order-1) contexts, and its weights.  The plain
+// instantiation takes CtcBeamArgs as it always did.
+struct CtcBeamLmArgs : CtcBeamArgs {
+  const float *lm;
+  int nctx;
+  float alpha, beta;
+};
+template <bool LM> using CtcArgs = std::conditional_t<LM, CtcBeamLmArgs, CtcBeamArgs>;
 
-__global__ __launch_bounds__(DT) void ctc_beam_kernel(CtcBeamArgs p) {
+// the context after label c: the previous order-1 symbols as a base-C number, the most recent least significant
+__device__ __forceinline__ int lm_next(int ctx, int c, int C, int nctx) { return (ctx * C + c) % nctx; }
+
+// LM: label n-gram fusion with the semantics of TF's scorer hooks (nabu_ctc_beam_search_lm).  A transition that APPENDS
+// label c to prefix g carries alpha * lm[ctx(g), c] + beta — the expansion candidates of (2) and the parent's
+// contribution to a leaf in (1) —, staying in a prefix (blank, the repeated-label self loop) carries nothing.  A node
+// keeps its context and the term it entered with; after the last frame the leaves are ranked with the end term.
+template <bool LM>
+__global__ __launch_bounds__(DT) void ctc_beam_kernel(CtcArgs<LM> p) {
   extern __shared__ __attribute__((aligned(16))) float dsm[];
   __shared__ int s_nl, s_nnodes;
   const int b = blockIdx.x, tid = threadIdx.x, W = p.W, C = p.C, C1 = p.C - 1, blank = p.C - 1;
@@ -192,6 +209,8 @@ __global__ __launch_bounds__(DT) void ctc_beam_kernel(CtcBeamArgs p) {
   __shared__ int s_sc[8];
   int32_t *parent = p.nodes + (size_t)b * p.per_utt, *label = parent + p.NN, *slot = label + p.NN,
           *child = slot + p.NN;
+  [[maybe_unused]] int32_t *nctx = child + (size_t)p.NN * C1;                  // LM only: context index of a node,
+  [[maybe_unused]] float *nterm = reinterpret_cast<float *>(nctx + p.NN);      //          the term it entered with
   int Tb = p.len[b];
   Tb = Tb < 0 ? 0 : (Tb > p.T ? p.T : Tb);
   if (tid == 0) {
@@ -200,6 +219,7 @@ __global__ __launch_bounds__(DT) void ctc_beam_kernel(CtcBeamArgs p) {
     s_node[0] = 0; s_lbl[0] = -1;
     s_tot[0] = 0.f; s_blk[0] = 0.f; s_lab[0] = -INFINITY;
     s_nl = 1; s_nnodes = 1;
+    if constexpr (LM) nctx[0] = p.nctx - 1;         // the empty hypothesis: every digit the boundary C-1
   }
   __syncthreads();
   const float *lg = p.logits + (size_t)b * p.T * C;
@@ -225,7 +245,11 @@ __global__ __launch_bounds__(DT) void ctc_beam_kernel(CtcBeamArgs p) {
       const int node = s_node[tid], par = parent[node], lab = s_lbl[tid];
       if (par >= 0) {
         const int ps = slot[par];
-        if (ps >= 0) nlb = lse2d(nlb, lab == s_lbl[ps] ? s_blk[ps] : s_tot[ps]);   // parent still in the beam
+        if constexpr (LM) {
+          if (ps >= 0) nlb = lse2d(nlb, (lab == s_lbl[ps] ? s_blk[ps] : s_tot[ps]) + nterm[node]);
+        } else {
+          if (ps >= 0) nlb = lse2d(nlb, lab == s_lbl[ps] ? s_blk[ps] : s_tot[ps]);   // parent still in the beam
+        }
         nlb += inp[lab];
       }
       nb = ot + inp[blank];
@@ -244,7 +268,13 @@ __global__ __launch_bounds__(DT) void ctc_beam_kernel(CtcBeamArgs p) {
       const int i = idx / C1, c = idx - i * C1;
       const int ch = child[(size_t)s_node[i] * C1 + c];
       float sc = -INFINITY;
-      if (!(ch >= 0 && slot[ch] >= 0) && o_tot[i] > -INFINITY) sc = inp[c] + (c == s_lbl[i] ? o_blk[i] : o_tot[i]);
+      if constexpr (LM) {
+        if (!(ch >= 0 && slot[ch] >= 0) && o_tot[i] > -INFINITY)
+          sc = inp[c] + ((c == s_lbl[i] ? o_blk[i] : o_tot[i]) +
+                         __fmaf_rn(p.alpha, p.lm[(size_t)nctx[s_node[i]] * C + c], p.beta));
+      } else {
+        if (!(ch >= 0 && slot[ch] >= 0) && o_tot[i] > -INFINITY) sc = inp[c] + (c == s_lbl[i] ? o_blk[i] : o_tot[i]);
+      }
       keys[nl + idx] = sc;
     }
     __syncthreads();
@@ -264,13 +294,17 @@ __global__ __launch_bounds__(DT) void ctc_beam_kernel(CtcBeamArgs p) {
         const int idx = g - nl, i = idx / C1, c = idx - i * C1;
         int32_t *cp = child + (size_t)s_node[i] * C1 + c;
         int ch = *cp;
+        [[maybe_unused]] float term = 0.f;
+        if constexpr (LM) term = __fmaf_rn(p.alpha, p.lm[(size_t)nctx[s_node[i]] * C + c], p.beta);
         if (ch < 0) {
           ch = atomicAdd(&s_nnodes, 1);
           *cp = ch;
           parent[ch] = s_node[i];
           label[ch] = c;
+          if constexpr (LM) { nctx[ch] = lm_next(nctx[s_node[i]], c, C, p.nctx); nterm[ch] = term; }
         }
-        const float sc = inp[c] + (c == s_lbl[i] ? o_blk[i] : o_tot[i]);
+        float sc = inp[c] + (c == s_lbl[i] ? o_blk[i] : o_tot[i]);
+        if constexpr (LM) sc = inp[c] + ((c == s_lbl[i] ? o_blk[i] : o_tot[i]) + term);
         n_node[tid] = ch; n_lbl[tid] = c;
         n_tot[tid] = sc; n_lab[tid] = sc; n_blk[tid] = -INFINITY;
       }
@@ -286,25 +320,42 @@ __global__ __launch_bounds__(DT) void ctc_beam_kernel(CtcBeamArgs p) {
   }
   // the labelling of the best leaf (BeamEntry::LabelSeq): walk to the root
   __shared__ int s_len;
+  [[maybe_unused]] int top = 0;                     // the slot of the best leaf
+  [[maybe_unused]] float top_lp = -INFINITY;
+  if constexpr (LM) {
+    if (s_nl > 0) {
+      // rank the leaves once more with the end term (GetStateEndExpansionScore); ties to the better slot
+      __shared__ Best s_red[2 * (DT / 64)];
+      Best mine = {-INFINITY, INT_MAX};
+      if (tid < s_nl) mine = Best{s_tot[tid] + p.alpha * p.lm[(size_t)nctx[s_node[tid]] * C + blank], tid};
+      const Best g = block_best(mine, s_red, 0);
+      top_lp = s_tot[0];
+      if (g.i != INT_MAX) { top = g.i; top_lp = g.v; }
+    }
+  }
   if (tid == 0) {
     int n = 0;
     if (s_nl > 0) {
       int prev = -1;
-      for (int x = s_node[0]; x > 0; x = parent[x]) {
+      for (int x = s_node[LM ? top : 0]; x > 0; x = parent[x]) {
         const int l = label[x];
         if (!p.merge || l != prev) ++n;
         prev = l;
       }
       int k = n;
       prev = -1;
-      for (int x = s_node[0]; x > 0; x = parent[x]) {
+      for (int x = s_node[LM ? top : 0]; x > 0; x = parent[x]) {
         const int l = label[x];
         if (!p.merge || l != prev) p.out_ids[(size_t)b * p.T + --k] = l;
         prev = l;
       }
     }
     p.out_len[b] = n;
-    if (p.out_lp) p.out_lp[b] = s_nl > 0 ? s_tot[0] : -INFINITY;
+    if constexpr (LM) {
+      if (p.out_lp) p.out_lp[b] = top_lp;
+    } else {
+      if (p.out_lp) p.out_lp[b] = s_nl > 0 ? s_tot[0] : -INFINITY;
+    }
     s_len = n;
   }
   __syncthreads();
@@ -359,6 +410,16 @@ struct PruneArgs {
   const float *delta;      // JOINT: [B,W,C] CTC prefix score differences (ctc_prefix.hip), and their weight
   float ctcw;
 };
+// LM: the label n-gram table [nctx, C], its weight, and the beams' contexts [B,W] before / after.  The instantiations
+// without the LM take PruneArgs as they always did.
+struct PruneLmArgs : PruneArgs {
+  const float *lm;
+  int nctx;
+  float lmw;
+  const int32_t *ctx_in;
+  int32_t *ctx_out;
+};
+template <bool LM> using PruneArgsOf = std::conditional_t<LM, PruneLmArgs, PruneArgs>;
 
 __device__ __forceinline__ float length_penalty(int len, float w, float pen6) {
   return w == 0.f ? 1.f : powf(5.f + (float)len, w) / pen6;
@@ -366,8 +427,10 @@ __device__ __forceinline__ float length_penalty(int len, float w, float pen6) {
 
 // JOINT: a live beam's candidate adds (1 - ctcw) * attention log-probability + ctcw * delta instead of the
 // attention log-probability (nabu_beam_prune_joint); everything else is the one body
-template <bool JOINT>
-__global__ __launch_bounds__(DT) void beam_prune_kernel(PruneArgs p) {
+// LM: a live beam's candidate also adds lmw * lm[ctx[w], c] (shallow fusion, nabu_beam_prune_lm), and the survivors'
+// contexts are written: a "stay" survivor keeps its parent's, any other gets lm_next(ctx[parent], pred)
+template <bool JOINT, bool LM>
+__global__ __launch_bounds__(DT) void beam_prune_kernel(PruneArgsOf<LM> p) {
   extern __shared__ __attribute__((aligned(16))) float dsm[];
   __shared__ Best red[2 * (DT / 64)];
   __shared__ int s_all;
@@ -375,6 +438,7 @@ __global__ __launch_bounds__(DT) void beam_prune_kernel(PruneArgs p) {
   const int n = W * C + W;
   float *lz = dsm, *plp = lz + W;
   int *plen = reinterpret_cast<int *>(plp + W), *pfin = plen + W, *sel = pfin + W;
+  [[maybe_unused]] int *pctx = sel + W;                 // LM only
   float *sc = p.scratch + (size_t)b * n;
   const float *lg = p.logits + (size_t)b * W * C;
   for (int w = tid >> 6; w < W; w += DT / 64) {
@@ -392,6 +456,7 @@ __global__ __launch_bounds__(DT) void beam_prune_kernel(PruneArgs p) {
     plp[w] = p.logprobs[(size_t)b * W + w];
     plen[w] = p.lengths[(size_t)b * W + w];
     pfin[w] = p.finished[(size_t)b * W + w];
+    if constexpr (LM) pctx[w] = min(max(p.ctx_in[(size_t)b * W + w], 0), p.nctx - 1);     // (a table row, whatever the caller wrote)
   }
   if (tid == 0) s_all = 1;
   __syncthreads();
@@ -401,6 +466,9 @@ __global__ __launch_bounds__(DT) void beam_prune_kernel(PruneArgs p) {
       const int w = idx / C, c = idx - w * C;
       float nl = pfin[w] ? -FLT_MAX : lg[idx] * p.inv_temp - lz[w];
       if (JOINT && !pfin[w]) nl = (1.f - p.ctcw) * nl + p.ctcw * p.delta[(size_t)b * W * C + idx];
+      if constexpr (LM) {
+        if (!pfin[w]) nl = __fmaf_rn(p.lmw, p.lm[(size_t)pctx[w] * C + c], nl);
+      }
       lp = plp[w] + nl;
       len = plen[w] + (c != end ? 1 : 0);
       id = c;
@@ -437,6 +505,7 @@ __global__ __launch_bounds__(DT) void beam_prune_kernel(PruneArgs p) {
     const size_t o = (size_t)b * W + k;
     const int st = g >= W * C;
     p.parent[o] = st ? g - W * C : g / C;
+    if constexpr (LM) p.ctx_out[o] = st ? pctx[g - W * C] : lm_next(pctx[g / C], id, C, p.nctx);
     p.stay[o] = st;
     p.pred[o] = id;
     p.logprobs[o] = lp;
@@ -593,6 +662,9 @@ struct BeamGeo {
   unsigned long long seed, offset0;
   bool ctc;                   // joint CTC/attention scoring: BeamIO::ctc_logits weighted by ctcw in (0, 1)
   float ctcw;
+  bool lm;                    // label n-gram fusion: BeamIO::lm_table [C^(lm_order-1), C] weighted by lmw > 0
+  int lm_order;
+  float lmw;
 };
 struct BeamIO {
   const float *values[MM];
@@ -603,6 +675,7 @@ struct BeamIO {
   int32_t *sequences, *lengths, *num_steps;
   float *scores;              // (sampled decoding: nll)
   const float *ctc_logits;    // [B, Te[0], C] logits of the CTC head on the first encoded input, or null
+  const float *lm_table;      // the label n-gram's log-probabilities, or null
 };
 
 // workspace, offsets in 32-bit words
@@ -614,6 +687,7 @@ struct BeamWs {
       hist_parent, src, gemm, gemm_bytes, total;
   size_t h[3][NABU_SPELLER_MAX_LAYERS], c[3][NABU_SPELLER_MAX_LAYERS], ctx[3];
   size_t cnorm, cstate[2], cpsi[2], clast[2], cdelta;      // joint scoring only (ctc_prefix.hip), behind everything else
+  size_t lctx[2];                                          // LM fusion only: the beams' contexts, behind that
 };
 
 static BeamWs beam_ws(const BeamGeo &g) {
@@ -657,6 +731,8 @@ static BeamWs beam_ws(const BeamGeo &g) {
     s.cnorm = take(B * T0 * 2); s.cdelta = take(N * C);
     for (int k = 0; k < 2; ++k) { s.cstate[k] = take(N * T0 * 2); s.cpsi[k] = take(N); s.clast[k] = take(N); }
   }
+  if (g.lm)
+    for (int k = 0; k < 2; ++k) s.lctx[k] = take(N);
   s.total = o;
   return s;
 }
@@ -690,6 +766,32 @@ static int beam_ctc(BeamGeo *g, const float *ctc_logits, float ctc_weight) {
   return ctc_prefix_lds_ok(g->Te[0]);
 }
 
+// The dense label n-gram of the *_lm / *_ex entry points: [C^(order-1), C] log-probabilities, C^order entries, at most
+// 2^24 of them (64 MiB).  *nctx = C^(order-1).
+constexpr long long LM_MAX_ENTRIES = 1ll << 24;
+static int lm_contexts(const char *what, int C, int order, int *nctx) {
+  if (order < 1) return fail(NABU_EINVAL, "%s: lm_order must be at least 1, got %d", what, order);
+  long long n = 1;
+  for (int k = 0; k < order; ++k) {
+    n *= C;
+    if (n > LM_MAX_ENTRIES)
+      return fail(NABU_EUNSUP, "%s: a table of %d^%d entries exceeds the limit of 2^24 entries (64 MiB)", what, C, order);
+  }
+  *nctx = (int)(n / C);
+  return 0;
+}
+
+// The optional LM operand of the *_ex entry points: absent (null) or weight 0 leaves g as it is — the loop then makes
+// exactly the launches it makes without one; otherwise g.lm is set.
+static int beam_lm(BeamGeo *g, const float *lm_table, int lm_order, float lm_weight) {
+  if (!(lm_weight >= 0.f && lm_weight <= FLT_MAX)) return fail(NABU_EINVAL, "beam search: lm_weight must be finite and >= 0");
+  if (!lm_table || lm_weight == 0.f) return 0;
+  int nctx;
+  if (int e = lm_contexts("beam search", g->C, lm_order, &nctx)) return e;
+  g->lm = true; g->lm_order = lm_order; g->lmw = lm_weight;
+  return 0;
+}
+
 static int beam_run(const BeamGeo &g, const BeamIO &io, void *ws, size_t ws_bytes, nabu_stream_t stream) {
   NABU_CHECK_ARG(io.out_kernel && io.out_bias && io.sequences && io.lengths && io.scores && io.num_steps && ws,
                  "beam search: null pointer");
@@ -698,6 +800,7 @@ static int beam_run(const BeamGeo &g, const BeamIO &io, void *ws, size_t ws_byte
                    (g.kind != 1 || (io.conv_kernel[m] && io.conv_proj[m])) && (!io.alignments[0] || io.alignments[m]),
                    "beam search: null pointer for an encoded input");
   NABU_CHECK_ARG(!g.ctc || io.ctc_logits, "beam search: null pointer for the CTC logits");
+  NABU_CHECK_ARG(!g.lm || (io.lm_table && !g.sample), "beam search: null pointer for the LM table");
   const BeamWs L = beam_ws(g);
   if (ws_bytes < L.total * 4) return fail(NABU_EWS, "beam search: workspace too small");
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -754,6 +857,13 @@ static int beam_run(const BeamGeo &g, const BeamIO &io, void *ws, size_t ws_byte
   if (g.ctc)
     NABU_TRY(nabu_ctc_prefix_prepare(B, W, T0, C, io.ctc_logits, io.enc_len[0], w + L.cnorm, w + L.cstate[0], w + L.cpsi[0],
                                      wi + L.clast[0], stream));
+  // LM fusion: the context of the empty hypothesis (every digit the boundary C-1) in every slot; set lc is the current one
+  int lc = 0, nctx = 1;
+  if (g.lm) {
+    NABU_TRY(lm_contexts("beam search", C, g.lm_order, &nctx));
+    hipLaunchKernelGGL(fill_i32_kernel, dim3(gN), dim3(DT), 0, s, (size_t)N, nctx - 1, wi + L.lctx[0]);
+    NABU_LAUNCH_CHECK();
+  }
   float *z = w + L.z, *lg = w + L.logits;
   const int32_t *big = wi + L.big;
   int32_t *par = wi + L.parent, *stay = wi + L.stay;
@@ -802,7 +912,23 @@ static int beam_run(const BeamGeo &g, const BeamIO &io, void *ws, size_t ws_byte
                                    wi + L.finished, io.scores, wi + L.ids, wi + L.all_seen, stream));
     } else {
       // expand + prune; the predicted ids are the next step's inputs
-      if (g.ctc) {
+      if (g.lm) {
+        // the LM term is looked up inside the prune (no launch of its own), which also writes the survivors' contexts
+        if (g.ctc)
+          NABU_TRY(nabu_ctc_prefix_score(B, W, T0, C, io.ctc_logits, io.enc_len[0], w + L.cnorm, w + L.cstate[cc], w + L.cpsi[cc],
+                                         wi + L.clast[cc], wi + L.finished, w + L.cdelta, stream));
+        NABU_TRY(nabu_beam_prune_lm(B, W, C, lg, g.ctc ? w + L.cdelta : nullptr, g.ctc ? g.ctcw : 0.f, io.lm_table, g.lm_order,
+                                    g.lmw, wi + L.lctx[lc], wi + L.lctx[lc ^ 1], g.temperature, g.lpw, w + L.logprobs,
+                                    wi + L.lengths, wi + L.finished, wi + L.seen, wi + L.ids, par, stay, wi + L.all_seen,
+                                    w + L.scratch, stream));
+        lc ^= 1;
+        if (g.ctc) {
+          NABU_TRY(nabu_ctc_prefix_advance(B, W, T0, C, io.ctc_logits, io.enc_len[0], w + L.cnorm, w + L.cstate[cc],
+                                           w + L.cpsi[cc], wi + L.clast[cc], par, stay, wi + L.ids, w + L.cstate[cc ^ 1],
+                                           w + L.cpsi[cc ^ 1], wi + L.clast[cc ^ 1], stream));
+          cc ^= 1;
+        }
+      } else if (g.ctc) {
         // the CTC prefix score of every (hypothesis, label), mixed into the candidates; then the survivors' states
         NABU_TRY(nabu_ctc_prefix_score(B, W, T0, C, io.ctc_logits, io.enc_len[0], w + L.cnorm, w + L.cstate[cc], w + L.cpsi[cc],
                                        wi + L.clast[cc], wi + L.finished, w + L.cdelta, stream));
@@ -886,25 +1012,56 @@ extern "C" size_t nabu_ctc_beam_ws_bytes(int B, int T, int C, int beam_width) {
   return (size_t)B * NN * (3 + (size_t)C - 1) * 4;
 }
 
-extern "C" int nabu_ctc_beam_search(int B, int T, int C, int beam_width, int merge_repeated, const float *logits,
-                                    const int32_t *logit_len, int32_t *out_ids, int32_t *out_len,
-                                    float *out_logprob, void *ws, size_t ws_bytes, nabu_stream_t stream) {
-  NABU_CHECK_ARG(B > 0 && T > 0 && C > 1 && beam_width > 0, "ctc_beam_search: bad dimensions");
-  NABU_CHECK_ARG(logits && logit_len && out_ids && out_len && ws, "ctc_beam_search: null pointer");
-  if (beam_width > DT) return fail(NABU_EUNSUP, "ctc_beam_search: beam_width <= %d", DT);
-  const size_t need = nabu_ctc_beam_ws_bytes(B, T, C, beam_width);
-  if (ws_bytes < need) return fail(NABU_EWS, "ctc_beam_search: workspace too small");
+// the prefix trees with the two words a node keeps for the LM (context, the term it entered with)
+extern "C" size_t nabu_ctc_beam_lm_ws_bytes(int B, int T, int C, int beam_width) {
+  if (B <= 0 || T <= 0 || C <= 1 || beam_width <= 0) return 0;
+  const size_t NN = 1 + (size_t)T * beam_width;
+  return (size_t)B * NN * (5 + (size_t)C - 1) * 4;
+}
+
+// both searches: lm_table null is the plain one
+static int ctc_beam(const char *what, int B, int T, int C, int beam_width, int merge_repeated, const float *logits,
+                    const int32_t *logit_len, const float *lm_table, int nctx, float alpha, float beta, int32_t *out_ids,
+                    int32_t *out_len, float *out_logprob, void *ws, size_t ws_bytes, nabu_stream_t stream) {
+  if (B <= 0 || T <= 0 || C <= 1 || beam_width <= 0) return fail(NABU_EINVAL, "%s: bad dimensions", what);
+  if (!(logits && logit_len && out_ids && out_len && ws)) return fail(NABU_EINVAL, "%s: null pointer", what);
+  if (beam_width > DT) return fail(NABU_EUNSUP, "%s: beam_width <= %d", what, DT);
+  const size_t need = lm_table ? nabu_ctc_beam_lm_ws_bytes(B, T, C, beam_width) : nabu_ctc_beam_ws_bytes(B, T, C, beam_width);
+  if (ws_bytes < need) return fail(NABU_EWS, "%s: workspace too small", what);
   const size_t lds = ctc_beam_lds(C, beam_width);
-  NABU_TRY(lds_fits(lds, "ctc_beam_search"));
+  NABU_TRY(lds_fits(lds, what));
   hipStream_t s = static_cast<hipStream_t>(stream);
   NABU_HIP(hipMemsetAsync(ws, 0xFF, need, s));   // every tree pointer = -1
-  CtcBeamArgs a;
+  CtcBeamLmArgs a;
   a.B = B; a.T = T; a.C = C; a.W = beam_width; a.merge = merge_repeated ? 1 : 0;
   a.NN = 1 + T * beam_width;
   a.logits = logits; a.len = logit_len; a.out_ids = out_ids; a.out_len = out_len; a.out_lp = out_logprob;
   a.nodes = static_cast<int32_t *>(ws);
-  a.per_utt = (size_t)a.NN * (3 + (size_t)C - 1);
-  return launch_lds(ctc_beam_kernel, dim3(B), dim3(DT), lds, s, a);
+  a.per_utt = (size_t)a.NN * ((lm_table ? 5 : 3) + (size_t)C - 1);
+  a.lm = lm_table; a.nctx = nctx; a.alpha = alpha; a.beta = beta;
+  if (lm_table) return launch_lds(ctc_beam_kernel<true>, dim3(B), dim3(DT), lds, s, a);
+  return launch_lds(ctc_beam_kernel<false>, dim3(B), dim3(DT), lds, s, static_cast<const CtcBeamArgs &>(a));
+}
+
+extern "C" int nabu_ctc_beam_search(int B, int T, int C, int beam_width, int merge_repeated, const float *logits,
+                                    const int32_t *logit_len, int32_t *out_ids, int32_t *out_len,
+                                    float *out_logprob, void *ws, size_t ws_bytes, nabu_stream_t stream) {
+  return ctc_beam("ctc_beam_search", B, T, C, beam_width, merge_repeated, logits, logit_len, nullptr, 1, 0.f, 0.f, out_ids,
+                  out_len, out_logprob, ws, ws_bytes, stream);
+}
+
+extern "C" int nabu_ctc_beam_search_lm(int B, int T, int C, int beam_width, int merge_repeated, const float *logits,
+                                       const int32_t *logit_len, const float *lm_table, int lm_order, float lm_weight,
+                                       float insertion_bonus, int32_t *out_ids, int32_t *out_len, float *out_logprob,
+                                       void *ws, size_t ws_bytes, nabu_stream_t stream) {
+  NABU_CHECK_ARG(B > 0 && T > 0 && C > 1 && beam_width > 0, "ctc_beam_search_lm: bad dimensions");
+  NABU_CHECK_ARG(lm_table, "ctc_beam_search_lm: null pointer");
+  NABU_CHECK_ARG(lm_weight >= 0.f && lm_weight <= FLT_MAX, "ctc_beam_search_lm: lm_weight must be finite and >= 0");
+  NABU_CHECK_ARG(insertion_bonus >= -FLT_MAX && insertion_bonus <= FLT_MAX, "ctc_beam_search_lm: insertion_bonus must be finite");
+  int nctx;
+  if (int e = lm_contexts("ctc_beam_search_lm", C, lm_order, &nctx)) return e;
+  return ctc_beam("ctc_beam_search_lm", B, T, C, beam_width, merge_repeated, logits, logit_len, lm_table, nctx, lm_weight,
+                  insertion_bonus, out_ids, out_len, out_logprob, ws, ws_bytes, stream);
 }
 
 extern "C" int nabu_edit_distance(int B, const int32_t *hyp, int ldh, const int32_t *hyp_len, const int32_t *truth,
@@ -928,7 +1085,7 @@ extern "C" int nabu_beam_prune(int B, int W, int C, const float *logits, float t
   NABU_TRY(lds_fits(lds, "beam_prune"));
   PruneArgs a = {B, W, C, logits, 1.f / temperature, length_penalty_w, logprobs, lengths, finished, seen,
                  pred_ids, parent, stay, all_seen, scratch, nullptr, 0.f};
-  return launch_lds(beam_prune_kernel<false>, dim3(B), dim3(DT), lds, static_cast<hipStream_t>(stream), a);
+  return launch_lds(beam_prune_kernel<false, false>, dim3(B), dim3(DT), lds, static_cast<hipStream_t>(stream), a);
 }
 
 extern "C" int nabu_beam_prune_joint(int B, int W, int C, const float *logits, const float *delta, float ctc_weight,
@@ -943,7 +1100,30 @@ extern "C" int nabu_beam_prune_joint(int B, int W, int C, const float *logits, c
   NABU_TRY(lds_fits(lds, "beam_prune_joint"));
   PruneArgs a = {B, W, C, logits, 1.f / temperature, length_penalty_w, logprobs, lengths, finished, seen,
                  pred_ids, parent, stay, all_seen, scratch, delta, ctc_weight};
-  return launch_lds(beam_prune_kernel<true>, dim3(B), dim3(DT), lds, static_cast<hipStream_t>(stream), a);
+  return launch_lds(beam_prune_kernel<true, false>, dim3(B), dim3(DT), lds, static_cast<hipStream_t>(stream), a);
+}
+
+extern "C" int nabu_beam_prune_lm(int B, int W, int C, const float *logits, const float *delta, float ctc_weight,
+                                  const float *lm_table, int lm_order, float lm_weight, const int32_t *ctx_in,
+                                  int32_t *ctx_out, float temperature, float length_penalty_w, float *logprobs,
+                                  int32_t *lengths, int32_t *finished, int32_t *seen, int32_t *pred_ids, int32_t *parent,
+                                  int32_t *stay, int32_t *all_seen, float *scratch, nabu_stream_t stream) {
+  NABU_CHECK_ARG(B > 0 && W > 0 && C > 1 && temperature > 0.f, "beam_prune_lm: bad arguments");
+  NABU_CHECK_ARG(ctc_weight >= 0.f && ctc_weight < 1.f, "beam_prune_lm: ctc_weight must be in [0, 1)");      // (false for NaN)
+  NABU_CHECK_ARG(lm_weight >= 0.f && lm_weight <= FLT_MAX, "beam_prune_lm: lm_weight must be finite and >= 0");
+  NABU_CHECK_ARG(logits && lm_table && ctx_in && ctx_out && ctx_in != ctx_out && logprobs && lengths && finished && seen &&
+                 pred_ids && parent && stay && all_seen && scratch, "beam_prune_lm: null pointer");
+  int nctx;
+  if (int e = lm_contexts("beam_prune_lm", C, lm_order, &nctx)) return e;
+  const size_t lds = 6 * (size_t)W * 4;
+  NABU_TRY(lds_fits(lds, "beam_prune_lm"));
+  PruneLmArgs a;
+  static_cast<PruneArgs &>(a) = PruneArgs{B, W, C, logits, 1.f / temperature, length_penalty_w, logprobs, lengths, finished,
+                                          seen, pred_ids, parent, stay, all_seen, scratch, delta, delta ? ctc_weight : 0.f};
+  a.lm = lm_table; a.nctx = nctx; a.lmw = lm_weight; a.ctx_in = ctx_in; a.ctx_out = ctx_out;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (delta) return launch_lds(beam_prune_kernel<true, true>, dim3(B), dim3(DT), lds, s, a);
+  return launch_lds(beam_prune_kernel<false, true>, dim3(B), dim3(DT), lds, s, a);
 }
 
 extern "C" int nabu_beam_gather(int B, int W, int F, const float *fresh, const float *old, const int32_t *parent,
@@ -980,11 +1160,12 @@ extern "C" size_t nabu_speller_beam_ws_bytes(const nabu_beam_desc *d) {
 // the search (sample = false: scores) or the sampled decode (nll) of one encoded input
 static int decode_one(BeamGeo &g, const float *values, const int32_t *enc_len, const nabu_speller_params *p,
                       int32_t *sequences, int32_t *lengths, float *scores, float *alignments, int32_t *num_steps, void *ws,
-                      size_t ws_bytes, nabu_stream_t stream, const float *ctc_logits = nullptr) {
+                      size_t ws_bytes, nabu_stream_t stream, const float *ctc_logits = nullptr,
+                      const float *lm_table = nullptr) {
   NABU_CHECK_ARG(p, "speller_beam_search: null pointer");
   const BeamIO io = {{values}, {enc_len}, {p->memory_kernel}, {p->query_kernel}, {p->attention_v}, {p->conv_kernel},
                      {p->conv_proj}, p->out_kernel, p->out_bias, p->lstm_kernel, p->lstm_bias, {alignments},
-                     sequences, lengths, num_steps, scores, ctc_logits};
+                     sequences, lengths, num_steps, scores, ctc_logits, lm_table};
   return beam_run(g, io, ws, ws_bytes, stream);
 }
 
@@ -1015,6 +1196,29 @@ extern "C" int nabu_speller_beam_search_joint(const nabu_beam_desc *d, const flo
                     ctc_logits);
 }
 
+// the options of the *_ex entry points as flags of the geometry (checked)
+static int beam_opts(BeamGeo *g, const nabu_beam_search_opts *o) {
+  if (!o || o->size != sizeof(nabu_beam_search_opts)) return fail(NABU_EINVAL, "beam search: bad options size");
+  if (int e = beam_ctc(g, o->ctc_logits, o->ctc_weight)) return e;
+  return beam_lm(g, o->lm_table, o->lm_order, o->lm_weight);
+}
+
+extern "C" size_t nabu_speller_beam_ex_ws_bytes(const nabu_beam_desc *d, const nabu_beam_search_opts *o) {
+  BeamGeo g;
+  return beam_geo(d, &g) || beam_opts(&g, o) ? 0 : beam_ws(g).total * 4;
+}
+
+extern "C" int nabu_speller_beam_search_ex(const nabu_beam_desc *d, const float *values, const int32_t *enc_len,
+                                           const nabu_speller_params *p, const nabu_beam_search_opts *o,
+                                           int32_t *sequences, int32_t *lengths, float *scores, float *alignments,
+                                           int32_t *num_steps, void *ws, size_t ws_bytes, nabu_stream_t stream) {
+  BeamGeo g;
+  if (int e = beam_geo(d, &g)) return e;
+  if (int e = beam_opts(&g, o)) return e;
+  return decode_one(g, values, enc_len, p, sequences, lengths, scores, alignments, num_steps, ws, ws_bytes, stream,
+                    o->ctc_logits, o->lm_table);
+}
+
 extern "C" size_t nabu_speller_sample_ws_bytes(const nabu_beam_desc *d) {
   BeamGeo g;
   return beam_geo(d, &g, true) ? 0 : beam_ws(g).total * 4;
@@ -1039,10 +1243,10 @@ extern "C" size_t nabu_speller_multi_beam_ws_bytes(const nabu_multi_beam_desc *d
 static int decode_multi(BeamGeo &g, const float *const *values, const int32_t *const *enc_len,
                         const nabu_speller_multi_params *p, int32_t *sequences, int32_t *lengths, float *scores,
                         float *const *alignments, int32_t *num_steps, void *ws, size_t ws_bytes, nabu_stream_t stream,
-                        const float *ctc_logits = nullptr) {
+                        const float *ctc_logits = nullptr, const float *lm_table = nullptr) {
   NABU_CHECK_ARG(values && enc_len && p, "speller_multi_beam_search: null pointer");
   BeamIO io = {{}, {}, {}, {}, {}, {}, {}, p->out_kernel, p->out_bias, p->lstm_kernel, p->lstm_bias, {},
-               sequences, lengths, num_steps, scores, ctc_logits};
+               sequences, lengths, num_steps, scores, ctc_logits, lm_table};
   for (int m = 0; m < g.M; ++m) {
     io.values[m] = values[m]; io.enc_len[m] = enc_len[m];
     io.memory_kernel[m] = p->memory_kernel[m]; io.query_kernel[m] = p->query_kernel[m];
@@ -1083,6 +1287,23 @@ extern "C" int nabu_speller_multi_beam_search_joint(const nabu_multi_beam_desc *
   if (int e = beam_ctc(&g, ctc_logits, ctc_weight)) return e;
   return decode_multi(g, values, enc_len, p, sequences, lengths, scores, alignments, num_steps, ws, ws_bytes, stream,
                       ctc_logits);
+}
+
+extern "C" size_t nabu_speller_multi_beam_ex_ws_bytes(const nabu_multi_beam_desc *d, const nabu_beam_search_opts *o) {
+  BeamGeo g;
+  return beam_geo(d, &g) || beam_opts(&g, o) ? 0 : beam_ws(g).total * 4;
+}
+
+extern "C" int nabu_speller_multi_beam_search_ex(const nabu_multi_beam_desc *d, const float *const *values,
+                                                 const int32_t *const *enc_len, const nabu_speller_multi_params *p,
+                                                 const nabu_beam_search_opts *o, int32_t *sequences, int32_t *lengths,
+                                                 float *scores, float *const *alignments, int32_t *num_steps, void *ws,
+                                                 size_t ws_bytes, nabu_stream_t stream) {
+  BeamGeo g;
+  if (int e = beam_geo(d, &g)) return e;
+  if (int e = beam_opts(&g, o)) return e;
+  return decode_multi(g, values, enc_len, p, sequences, lengths, scores, alignments, num_steps, ws, ws_bytes, stream,
+                      o->ctc_logits, o->lm_table);
 }
 
 extern "C" size_t nabu_speller_multi_sample_ws_bytes(const nabu_multi_beam_desc *d) {

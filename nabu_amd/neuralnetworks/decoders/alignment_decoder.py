@@ -17,6 +17,7 @@ import torch
 from nabu_amd import ops
 from nabu_amd.autodiff import SeqLen
 from nabu_amd.neuralnetworks.decoders import decoder
+from nabu_amd.processing import ngram_lm
 
 
 class AlignmentDecoder(decoder.Decoder):
@@ -24,6 +25,7 @@ class AlignmentDecoder(decoder.Decoder):
 
     def __init__(self, conf, model):
         super(AlignmentDecoder, self).__init__(conf, model)
+        ngram_lm.refuse_keys(self.conf, 'AlignmentDecoder')
         self._logprior = None
 
     def log_prior(self):

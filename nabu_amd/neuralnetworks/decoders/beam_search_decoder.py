@@ -15,6 +15,7 @@ from nabu_amd.autodiff import SeqLen
 from nabu_amd.neuralnetworks.decoders import decoder
 from nabu_amd.neuralnetworks.models.ed_decoders import rnn_decoder
 from nabu_amd.neuralnetworks.trainers import loss_functions
+from nabu_amd.processing import ngram_lm
 
 
 class BeamSearchDecoder(decoder.Decoder):
@@ -30,6 +31,12 @@ class BeamSearchDecoder(decoder.Decoder):
         if self.ctc_weight and not getattr(model.decoder, 'ctc_head', False):
             raise ValueError('ctc_weight = %g needs a model with a CTC head: set ctc_head = True in the [decoder] '
                              'section of the model' % self.ctc_weight)
+        # lm_file, lm_weight (extension keys as well, off when absent): shallow fusion of a label n-gram
+        # (processing/ngram_lm.py); combines with ctc_weight.  The file is read here, once.
+        lm_file, self.lm_weight, _ = ngram_lm.decoder_keys(self.conf, with_bonus=False)
+        self.lm = None
+        if lm_file is not None:
+            self.lm = ngram_lm.load(lm_file, list(model.output_dims.values())[0], self.alphabet)
 
     def _keep_alignments(self):
         return self.conf.get('visualize_alignments') == 'True'
@@ -52,6 +59,8 @@ class BeamSearchDecoder(decoder.Decoder):
                 if self.ctc_weight > 0:        # (without the key: the call it always was)
                     joint = dict(ctc_logits=model.decoder.ctc_logits(encoded, encoded_seq_length)[0],
                                  ctc_weight=self.ctc_weight)
+                if self.lm is not None and self.lm_weight > 0:
+                    joint.update(lm=self.lm, lm_weight=self.lm_weight)
                 res = rnn_decoder.beam_search(
                     cell, [encoded[e] for e in names], [encoded_seq_length[e] for e in names], beam_width=int(self.conf['beam_width']),
                     max_steps=int(self.conf['max_steps']), length_penalty=float(self.conf['length_penalty']),

@@ -9,6 +9,7 @@ import torch
 from nabu_amd import ops
 from nabu_amd.autodiff import SeqLen
 from nabu_amd.neuralnetworks.decoders import decoder
+from nabu_amd.processing import ngram_lm
 
 BEAM_WIDTH = 100          # tf.nn.ctc_beam_search_decoder's default, which the reference relies on
 
@@ -19,6 +20,14 @@ class CTCDecoder(decoder.Decoder):
     def __init__(self, conf, model):
         super(CTCDecoder, self).__init__(conf, model)
         self.alphabets = {o: self.conf['%s_alphabet' % o].split(' ') for o in model.output_names}
+        # lm_file, lm_weight, insertion_bonus (extension keys: absent from the defaults, off when absent): a label
+        # n-gram (processing/ngram_lm.py) fused into the search with the semantics of TF's scorer hooks.  The file is
+        # read here, once, and must be a model over every output's alphabet; the table is uploaded once per device.
+        lm_file, self.lm_weight, self.insertion_bonus = ngram_lm.decoder_keys(self.conf, with_bonus=True)
+        self.lm = None
+        if lm_file is not None:
+            for o in model.output_names:
+                self.lm = ngram_lm.load(lm_file, model.output_dims[o], self.alphabets[o])
 
     def __call__(self, inputs, input_seq_length):
         '''Returns {output: (ids [B,T'] int32 padded with -1, lengths [B] int32)} — the dense form
@@ -29,7 +38,12 @@ class CTCDecoder(decoder.Decoder):
             outputs = {}
             for o in logits:
                 lens = SeqLen.wrap(logit_len[o], logits[o].device)
-                ids, out_len, _ = ops.ctc_beam_search(logits[o], lens.dev, BEAM_WIDTH, merge_repeated=True)
+                if self.lm is None:        # (without the keys: the call it always was)
+                    ids, out_len, _ = ops.ctc_beam_search(logits[o], lens.dev, BEAM_WIDTH, merge_repeated=True)
+                else:
+                    ids, out_len, _ = ops.ctc_beam_search_lm(logits[o], lens.dev, self.lm.device_table(logits[o].device),
+                                                             self.lm.order, self.lm_weight, self.insertion_bonus,
+                                                             BEAM_WIDTH, merge_repeated=True)
                 outputs[o] = (ids, out_len)
         return outputs
 

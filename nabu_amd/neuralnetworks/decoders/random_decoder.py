@@ -20,6 +20,7 @@ from nabu_amd.autodiff import SeqLen
 from nabu_amd.neuralnetworks.components import ops as nops
 from nabu_amd.neuralnetworks.decoders import decoder
 from nabu_amd.neuralnetworks.models.ed_decoders import rnn_decoder
+from nabu_amd.processing import ngram_lm
 
 # the sampling streams of the decoder calls are `offset * OFFSET_STRIDE + step` (as rnn_decoder.dynamic_decode's)
 OFFSET_STRIDE = 1000003
@@ -31,6 +32,7 @@ class RandomDecoder(decoder.Decoder):
 
     def __init__(self, conf, model):
         super(RandomDecoder, self).__init__(conf, model)
+        ngram_lm.refuse_keys(self.conf, 'RandomDecoder')
         self.alphabet = self.conf['alphabet'].split(' ')
 
     def __call__(self, inputs, input_seq_length):

@@ -212,7 +212,8 @@ def _free_run(which, cell, encoded, encoded_seq_length, beam_width, max_steps, l
               with_alignments, *extra):
     """The call beam_search and sample share: `which` is 'beam' (nabu_speller[_multi]_beam_search) or 'sample'
     (nabu_speller[_multi]_sample, beam_width 1, `extra` = seed, offset) or 'beam_joint'
-    (nabu_speller[_multi]_beam_search_joint, `extra` = the CTC head's logits, ctc_weight).  Returns (sequences [B,W,time] int32,
+    (nabu_speller[_multi]_beam_search_joint, `extra` = the CTC head's logits, ctc_weight) or 'beam_ex'
+    (nabu_speller[_multi]_beam_search_ex, `extra` = a _hip.BeamSearchOpts).  Returns (sequences [B,W,time] int32,
     lengths [B,W] int32, scores or nll [B,W], [alignments [B,W,time,Te_m] per memory] or None, the binding)."""
     abi, encoded, encoded_seq_length = _memories(encoded, encoded_seq_length)
     dev = encoded[0].device
@@ -225,8 +226,12 @@ def _free_run(which, cell, encoded, encoded_seq_length, beam_width, max_steps, l
     desc = abi.desc(abi.beam_desc_cls, Tes, Es, B=B, U=U, C=C, num_layers=nl, kind=mech.kind, K=mech.filtersize,
                     F=mech.numfilt, prob_fn=mech.prob_fn, beam_width=W, max_steps=S,
                     length_penalty=float(length_penalty), temperature=float(temperature))
-    name = {'beam': 'beam_search', 'beam_joint': 'beam_search_joint'}.get(which, which)
-    ws_bytes = abi.fn(which + '_ws_bytes')(ctypes.byref(desc))
+    name = {'beam': 'beam_search', 'beam_joint': 'beam_search_joint', 'beam_ex': 'beam_search_ex'}.get(which, which)
+    if which == 'beam_ex':          # the options decide the workspace, and go to the call by reference
+        extra = (ctypes.byref(extra[0]),)
+        ws_bytes = abi.fn(which + '_ws_bytes')(ctypes.byref(desc), extra[0])
+    else:
+        ws_bytes = abi.fn(which + '_ws_bytes')(ctypes.byref(desc))
     if ws_bytes == 0:
         raise _hip.NabuHipError('%s: unsupported shape: %s' % (name, _hip.lib().nabu_last_error().decode()))
     values = [e if e.is_contiguous() else e.contiguous() for e in encoded]
@@ -246,7 +251,7 @@ def _free_run(which, cell, encoded, encoded_seq_length, beam_width, max_steps, l
 
 
 def beam_search(cell, encoded, encoded_seq_length, beam_width, max_steps, length_penalty=0.0,
-                temperature=1.0, with_alignments=True, ctc_logits=None, ctc_weight=0.0):
+                temperature=1.0, with_alignments=True, ctc_logits=None, ctc_weight=0.0, lm=None, lm_weight=0.0):
     """Beam search over the projected attention cell (components/beam_search_decoder.py:68-451
     under dynamic_decode): ONE call into the C ABI (nabu_speller_beam_search), whose C++ driver runs
     the cell kernels on B*beam_width rows, prunes and gathers on the device, and stops as the
@@ -255,8 +260,15 @@ def beam_search(cell, encoded, encoded_seq_length, beam_width, max_steps, length
     [B,W,time,Te] or None).  encoded / encoded_seq_length may be lists (one entry per attention mechanism): several
     memories run nabu_speller_multi_beam_search and return the alignments as a list of [B,W,time,Te_m], one per memory.
     ctc_logits [B,Te,C] (the CTC head's logits on the FIRST encoded input) with ctc_weight in (0, 1): the joint
-    CTC/attention search of nabu_speller[_multi]_beam_search_joint; without them the plain entry point is called."""
-    ctc_weight = float(ctc_weight)
+    CTC/attention search of nabu_speller[_multi]_beam_search_joint; without them the plain entry point is called.
+    lm (a processing.ngram_lm.NgramLM over the cell's C symbols) with lm_weight > 0: shallow fusion, every candidate of a
+    live beam adds lm_weight * log p_lm(label | the hypothesis' last n-1 labels) (nabu_speller[_multi]_beam_search_ex,
+    which also takes the CTC operand); without an LM the calls are the ones above."""
+    ctc_weight, lm_weight = float(ctc_weight), float(lm_weight)
+    if not (0.0 <= lm_weight < float('inf')):
+        raise ValueError('lm_weight must be finite and >= 0, got %r' % lm_weight)
+    if lm_weight > 0 and lm is None:
+        raise ValueError('lm_weight %g needs a language model (lm)' % lm_weight)
     if not 0.0 <= ctc_weight < 1.0:
         raise ValueError('ctc_weight must be in [0, 1), got %r' % ctc_weight)
     if ctc_weight > 0 and ctc_logits is None:
@@ -267,6 +279,14 @@ def beam_search(cell, encoded, encoded_seq_length, beam_width, max_steps, length
             raise _hip.NabuHipError('ctc_logits must be float32, got %s' % ctc_logits.dtype)
         ctc_logits = ctc_logits.contiguous()
         which, extra = 'beam_joint', (_hip.ptr(ctc_logits), ctypes.c_float(ctc_weight))
+    if lm is not None and lm_weight > 0:
+        if lm.num_labels != cell.output_size:
+            raise ValueError('the language model has %d symbols, the decoder %d' % (lm.num_labels, cell.output_size))
+        dev = (encoded[0] if isinstance(encoded, (list, tuple)) else encoded).device
+        opts = _hip.BeamSearchOpts(size=ctypes.sizeof(_hip.BeamSearchOpts),
+                                   ctc_logits=None if ctc_logits is None else _hip.ptr(ctc_logits), ctc_weight=ctc_weight,
+                                   lm_table=_hip.ptr(lm.device_table(dev)), lm_order=lm.order, lm_weight=lm_weight)
+        which, extra = 'beam_ex', (opts,)
     seq, lengths, scores, aligns, abi = _free_run(which, cell, encoded, encoded_seq_length, beam_width, max_steps,
                                                   length_penalty, temperature, with_alignments, *extra)
     return seq, lengths, scores, (abi.per_memory(aligns) if with_alignments else None)

@@ -952,6 +952,41 @@ def ctc_beam_search(logits, logit_len, beam_width=100, merge_repeated=True):
     return ids, lens, lp
 
 
+def _lm_table(table, C, lm_order):
+    """the device table [C^(order-1), C] of a label n-gram (processing/ngram_lm.py), checked"""
+    table = _f32(table, 'lm_table')
+    lm_order = int(lm_order)
+    if lm_order < 1:
+        raise _hip.NabuHipError('lm_order must be at least 1, got %d' % lm_order)
+    if C ** lm_order > _hip.LM_MAX_ENTRIES:
+        raise _hip.NabuHipError('an n-gram table of %d^%d entries exceeds the limit of 2^24 entries (64 MiB)' % (C, lm_order))
+    if tuple(table.shape) != (C ** (lm_order - 1), C):
+        raise _hip.NabuHipError('lm_table has shape %r, order %d over %d symbols needs %r'
+                                % (tuple(table.shape), lm_order, C, (C ** (lm_order - 1), C)))
+    return table.contiguous()
+
+
+def ctc_beam_search_lm(logits, logit_len, lm_table, lm_order, lm_weight, insertion_bonus=0.0, beam_width=100,
+                       merge_repeated=True):
+    """ctc_beam_search with a label n-gram (nabu_ctc_beam_search_lm: the scorer hooks of TF's CTC beam search).
+    lm_table [C^(lm_order-1), C] float32 log-probabilities on the device, symbol C-1 the boundary; appending a label
+    adds lm_weight * lm_table[ctx, label] + insertion_bonus, the end adds lm_weight * lm_table[ctx, C-1].
+    Returns (ids, lengths, log-probabilities) as ctc_beam_search; the log-probabilities include the LM terms."""
+    B, T, C = logits.shape
+    logits = logits.contiguous()
+    table = _lm_table(lm_table, C, lm_order)
+    lib = _hip.lib()
+    nbytes = lib.nabu_ctc_beam_lm_ws_bytes(B, T, C, int(beam_width))
+    ws = _hip.Workspace.get(nbytes, logits.device, 'ctc_beam')
+    ids = torch.empty((B, T), dtype=torch.int32, device=logits.device)
+    lens = torch.empty((B,), dtype=torch.int32, device=logits.device)
+    lp = torch.empty((B,), dtype=torch.float32, device=logits.device)
+    check(lib.nabu_ctc_beam_search_lm(B, T, C, int(beam_width), int(bool(merge_repeated)), ptr(logits), ptr(logit_len),
+                                      ptr(table), int(lm_order), float(lm_weight), float(insertion_bonus), ptr(ids),
+                                      ptr(lens), ptr(lp), ptr(ws), nbytes, stream()), 'nabu_ctc_beam_search_lm')
+    return ids, lens, lp
+
+
 def edit_distance(hyp, hyp_len, truth, truth_len):
     """Levenshtein distance per row: hyp [B,Lh], truth [B,Lt] int32 with their lengths -> [B] int32"""
     B = hyp.shape[0]
@@ -992,6 +1027,29 @@ def beam_prune_joint(logits, delta, ctc_weight, logprobs, lengths, finished, see
                                            ptr(lengths), ptr(finished), ptr(seen), ptr(pred), ptr(parent), ptr(stay),
                                            ptr(all_seen), ptr(scratch), stream()), 'nabu_beam_prune_joint')
     return pred, parent, stay, all_seen
+
+
+def beam_prune_lm(logits, delta, ctc_weight, lm_table, lm_order, lm_weight, ctx, logprobs, lengths, finished, seen,
+                  temperature=1.0, length_penalty=0.0):
+    """beam_prune with the label n-gram term lm_weight * lm_table[ctx[w], c] on every live beam's candidates, and with
+    the CTC term of beam_prune_joint where delta is not None.  ctx [B,W] int32: the beams' contexts (not changed).
+    Returns (pred_ids, parent, stay, all_seen, the survivors' contexts [B,W] int32)"""
+    B, W, C = logits.shape
+    dev = logits.device
+    table = _lm_table(lm_table, C, lm_order)
+    pred = torch.empty((B, W), dtype=torch.int32, device=dev)
+    parent, stay, ctx_out = torch.empty_like(pred), torch.empty_like(pred), torch.empty_like(pred)
+    all_seen = torch.empty((B,), dtype=torch.int32, device=dev)
+    scratch = torch.empty((B, W * C + W), dtype=torch.float32, device=dev)
+    if ctx.dtype != torch.int32 or tuple(ctx.shape) != (B, W):
+        raise _hip.NabuHipError('ctx must be int32 [B,W], got %s %r' % (ctx.dtype, tuple(ctx.shape)))
+    check(_hip.lib().nabu_beam_prune_lm(B, W, C, ptr(logits.contiguous()),
+                                        None if delta is None else ptr(_f32(delta, 'delta').contiguous()),
+                                        float(ctc_weight), ptr(table), int(lm_order), float(lm_weight),
+                                        ptr(ctx.contiguous()), ptr(ctx_out), float(temperature), float(length_penalty),
+                                        ptr(logprobs), ptr(lengths), ptr(finished), ptr(seen), ptr(pred), ptr(parent),
+                                        ptr(stay), ptr(all_seen), ptr(scratch), stream()), 'nabu_beam_prune_lm')
+    return pred, parent, stay, all_seen, ctx_out
 
 
 class CtcPrefixState(object):
