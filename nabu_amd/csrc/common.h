@@ -97,13 +97,15 @@ int sample_ids_rows(int B, int C, const float *logits, float prob, unsigned long
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// elementwise.hip: up to 8 regions set to a 32-bit pattern each by ONE launch (ptr 16-byte aligned, a whole number of
-// 4-byte words).  Stands where a layer call needs several hipMemsetAsync in a row — exchange rings (0xFF), row-maximum
-// arrays (0 or an a-priori bound): every memset is its own dispatch and costs ~6 us of queue gap behind a kernel.
+// elementwise.hip: up to 8 regions set to a 32-bit pattern each — or, a region with `from`, copied from a kept array of
+// the same length — by ONE launch (ptr 16-byte aligned, a whole number of 4-byte words).  Stands where a layer call
+// needs several hipMemsetAsync in a row — exchange rings (0xFF), row-maximum arrays (0 or an a-priori bound): every
+// memset is its own dispatch and costs ~6 us of queue gap behind a kernel.
 // elementwise.hip: out0[c] = sum_r part[r * ld + c], out1[c] = sum_r part[r * ld + N + c] for a FEW rows (the per-unit
 // bias-gradient partials of the persistent backward kernel, both cells): one launch, fixed order
 int colsum_pair(int rows, int N, const float *part, int ld, float *out0, float *out1, hipStream_t stream);
-struct FillSeg { void *ptr; size_t words; unsigned value; };
+// (from: the region is a COPY of `words` words found there — a kept array moved into place by the same launch — not `value`)
+struct FillSeg { void *ptr; size_t words; unsigned value; const void *from = nullptr; };
 int multi_fill(const FillSeg *segs, int n, hipStream_t stream);
 
 // wave64 reductions through the lane exchange; every lane gets the result

@@ -394,7 +394,178 @@ __global__ __launch_bounds__(256) void ctc_wave_kernel(CtcArgs p) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// The same lattice with the two sweeps SIDE BY SIDE: alpha and beta do not depend on each other, so wave 0 runs the
+// alpha recursion while wave 1 runs the beta recursion, each with nothing but the lattice update on its chain (the
+// DPP neighbour fetch and the frame's log-sum-exp, emissions prefetched one frame ahead).  Both lattices stay in LDS.
+// After ONE workgroup barrier every frame's gradient is independent of the others: all CTC_SPLIT_WAVES waves take
+// frames t = wave, wave + CTC_SPLIT_WAVES, ... and do what ctc_wave_kernel's workers do — occupations, the class
+// sums along the same occurrence chains, softmax, the stores.  Every expression is the one of ctc_wave_kernel, in
+// the same order: the two kernels give the same bits (tests/test_hip_ctc_split.py).  The chain is T frames, not 2 T,
+// and no wave polls another.  For the shapes whose second lattice still fits (ctc_split_lds_bytes; cfg2: 145 KiB);
+// the others keep ctc_wave_kernel.
+constexpr int CTC_SPLIT_WAVES = 16;
+__global__ __launch_bounds__(64 * CTC_SPLIT_WAVES) void ctc_wave_split_kernel(CtcArgs p) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int NT = 64 * CTC_SPLIT_WAVES;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int T = p.T, C = p.C, Smax = p.Smax, blank = p.C - 1;
+  float *xs = smem;                          // [T*C] logits, then base-2 log-softmax in place (as in ctc_wave_kernel)
+  float *as = xs + (size_t)T * C;            // [T*Smax] alpha
+  float *bs = as + (size_t)T * Smax;         // [T*Smax] beta
+  float *gamw = bs + (size_t)T * Smax;       // [CTC_SPLIT_WAVES][64] occupation of the label states, per wave
+  float *csumw = gamw + CTC_SPLIT_WAVES * 64;   // [CTC_SPLIT_WAVES][C] class sums of the wave's current frame
+  float *llp = csumw + (size_t)CTC_SPLIT_WAVES * C;   // [2] the log-likelihood (base 2)
+  int *lbl = reinterpret_cast<int *>(llp + 2);    // [64] labels
+  int *nxtl = lbl + 64;                           // [64] next lane with the same label
+
+  int Tb = p.logit_len[b];
+  Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+  int L = p.label_len[b];
+  L = L < 0 ? 0 : (L > p.Lmax ? p.Lmax : L);
+  const float *lg = p.logits + (size_t)b * T * C;
+  float *dl = p.dlogits + (size_t)b * T * C;
+
+  // prologue, all waves: stage the logits, zero the gradient of the padding frames, per-frame log-sum-exp
+  {
+    const int n = Tb * C;
+    if ((reinterpret_cast<uintptr_t>(lg) & 15) == 0 && (n & 3) == 0) {
+      const float4 *src = reinterpret_cast<const float4 *>(lg);
+      float4 *dst = reinterpret_cast<float4 *>(xs);
+#pragma unroll 4
+      for (int i = tid; i < n / 4; i += NT) dst[i] = src[i];
+    } else {
+#pragma unroll 4
+      for (int i = tid; i < n; i += NT) xs[i] = lg[i];
+    }
+    for (int i = n + tid; i < T * C; i += NT) dl[i] = 0.f;
+    for (int i = tid; i < CTC_SPLIT_WAVES * C; i += NT) csumw[i] = 0.f;
+  }
+  const int lab = lane < L ? p.labels[(size_t)b * p.Lmax + lane] : -1;
+  if (tid < 64) lbl[lane] = lab;
+  __syncthreads();
+  constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
+  for (int t = tid; t < Tb; t += NT) {
+    float *x = xs + (size_t)t * C;
+    float m = x[0];
+    for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
+    float z = 0.f;
+    for (int c = 0; c < C; ++c) z += __expf(x[c] - m);
+    const float lz = __logf(z);
+    for (int c = 0; c < C; ++c) x[c] = ((x[c] - m) - lz) * LOG2E;
+  }
+  const int lab_up = lane >= 1 ? lbl[lane - 1] : -1, lab_dn = lane < 63 ? lbl[lane + 1] : -1;
+  const bool badl = lane < L && (lab < 0 || lab >= blank);
+  const int rep = (int)wave_sum((lane >= 1 && lane < L && lab == lab_up) ? 1.f : 0.f);
+  const bool bad = __any(badl) || Tb <= 0 || L + rep > Tb;   // (every wave reaches the same verdict from the same LDS contents)
+  if (bad) {
+    for (int i = tid; i < Tb * C; i += NT) dl[i] = 0.f;
+    if (tid == 0) {
+      p.nll[b] = __builtin_inff();
+      atomicCAS(p.status, 0, b + 1);
+    }
+    return;
+  }
+  // occurrence chains of the labels (fixed order -> deterministic class sums); every wave keeps its own copy in registers
+  bool first = lane < L;
+  int nxt = -1;
+  if (lane < L) {
+    for (int j = 0; j < lane; ++j) first = first && lbl[j] != lab;
+    for (int j = L - 1; j > lane; --j) nxt = lbl[j] == lab ? j : nxt;
+  }
+  if (wv == 0) nxtl[lane] = nxt;
+  __syncthreads();
+  const bool hasB = lane <= L, hasL = lane < L;
+  const int labc = hasL ? lab : blank;                          // a valid column for idle lanes
+  // the first links of the lane's occurrence chain in registers: their occupations are fetched side by side in the
+  // gradient loop below (a walk through nxtl costs two dependent LDS reads per link), and added in chain order
+  const int n1 = nxt, n2 = n1 >= 0 ? nxtl[n1] : -1, n3 = n2 >= 0 ? nxtl[n2] : -1, n4 = n3 >= 0 ? nxtl[n3] : -1;
+
+  if (wv == 0) {          // ---- alpha sweep --------------------------------------------------------
+    const bool skipA = lane >= 1 && lane < L && lab != lab_up;   // 2i-1 -> 2i+1
+    float aB = CTC_NEG, aL = CTC_NEG;
+    float yB = xs[blank], yL = xs[labc];
+    for (int t = 0; t < Tb; ++t) {
+      const int tn = t + 1 < Tb ? t + 1 : t;
+      const float yBn = xs[(size_t)tn * C + blank], yLn = xs[(size_t)tn * C + labc];
+      if (t == 0) {
+        aB = lane == 0 ? yB : CTC_NEG;
+        aL = (lane == 0 && hasL) ? yL : CTC_NEG;
+      } else {
+        const float up = dpp_up(aL, CTC_NEG);
+        const float nB = lse2_fast(aB, up) + yB;
+        const float nL = lse3_fast(aL, aB, skipA ? up : CTC_NEG) + yL;
+        aB = hasB ? nB : CTC_NEG;
+        aL = hasL ? nL : CTC_NEG;
+      }
+      if (hasB) as[(size_t)t * Smax + 2 * lane] = aB;
+      if (hasL) as[(size_t)t * Smax + 2 * lane + 1] = aL;
+      yB = yBn;
+      yL = yLn;
+    }
+    const float ll = L >= 1 ? lse2_fast(__shfl(aB, L), __shfl(aL, L - 1)) : __shfl(aB, 0);
+    if (lane == 0) {
+      p.nll[b] = -ll * LN2;
+      llp[0] = ll;
+    }
+  } else if (wv == 1) {   // ---- beta sweep ---------------------------------------------------------
+    const bool skipB = lane + 1 < L && lab_dn != lab;            // 2i+1 -> 2i+3
+    float bB = CTC_NEG, bL = CTC_NEG;
+    float yB = xs[(size_t)(Tb - 1) * C + blank], yL = xs[(size_t)(Tb - 1) * C + labc];
+    for (int t = Tb - 1; t >= 0; --t) {
+      const int tn = t >= 1 ? t - 1 : t;
+      const float yBn = xs[(size_t)tn * C + blank], yLn = xs[(size_t)tn * C + labc];
+      if (t == Tb - 1) {
+        bB = lane == L ? yB : CTC_NEG;
+        bL = (hasL && lane == L - 1) ? yL : CTC_NEG;
+      } else {
+        const float dnB = dpp_dn(bB, CTC_NEG), dnL = dpp_dn(bL, CTC_NEG);
+        const float nB = lse2_fast(bB, hasL ? bL : CTC_NEG) + yB;
+        const float nL = lse3_fast(bL, dnB, skipB ? dnL : CTC_NEG) + yL;
+        bB = hasB ? nB : CTC_NEG;
+        bL = hasL ? nL : CTC_NEG;
+      }
+      if (hasB) bs[(size_t)t * Smax + 2 * lane] = bB;
+      if (hasL) bs[(size_t)t * Smax + 2 * lane + 1] = bL;
+      yB = yBn;
+      yL = yLn;
+    }
+  }
+  __syncthreads();
+
+  // ---- gradient: frames dealt out to the waves --------------------------------------------------
+  const float ll = llp[0];
+  float *gam = gamw + wv * 64, *csum_w = csumw + (size_t)wv * C;
+  for (int t = wv; t < Tb; t += CTC_SPLIT_WAVES) {
+    const float yB = xs[(size_t)t * C + blank], yL = xs[(size_t)t * C + labc];
+    const size_t o = (size_t)t * Smax + 2 * lane;
+    const float gB = hasB ? __builtin_amdgcn_exp2f((as[o] - ll) + (bs[o] - yB)) : 0.f;
+    const float gL = hasL ? __builtin_amdgcn_exp2f((as[o + 1] - ll) + (bs[o + 1] - yL)) : 0.f;
+    const float sumB = wave_sum_dpp(gB);
+    gam[lane] = gL;
+    WSYNC();
+    if (first) {
+      float v = gL;
+      const float g1 = n1 >= 0 ? gam[n1] : 0.f, g2 = n2 >= 0 ? gam[n2] : 0.f, g3 = n3 >= 0 ? gam[n3] : 0.f;
+      if (n1 >= 0) v += g1;
+      if (n2 >= 0) v += g2;
+      if (n3 >= 0) v += g3;
+      for (int j = n4; j >= 0; j = nxtl[j]) v += gam[j];
+      csum_w[lab] = v;
+    }
+    if (lane == 0) csum_w[blank] = sumB;
+    WSYNC();
+    for (int c = lane; c < C; c += 64)
+      dl[(size_t)t * C + c] = p.scale * (__builtin_amdgcn_exp2f(xs[(size_t)t * C + c]) - csum_w[c]);
+    WSYNC();
+  }
+}
+
 #undef WSYNC
+static size_t ctc_split_lds_bytes(int T, int C, int Smax) {
+  return ((size_t)T * C + 2 * (size_t)T * Smax + CTC_SPLIT_WAVES * (64 + (size_t)C) + 2) * sizeof(float) + 128 * sizeof(int);
+}
+
 static size_t ctc_wave_lds_bytes(int T, int C, int Smax) {
   return ((size_t)T * C + (size_t)T * Smax + C + 64 + 2 + 3 * 64 + 3 * (size_t)C) * sizeof(float) + (128 + 2) * sizeof(int);
 }
@@ -431,6 +602,11 @@ extern "C" int nabu_ctc_loss_grad(int B, int T, int C, int Lmax, const float *lo
   p.alpha = static_cast<float *>(ws);
   NABU_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
   static const int force_wg = env_int("NABU_CTC_WORKGROUP", 0);   // 1: the workgroup kernel for every shape (A/B tests)
+  // 1: the wave kernel with one wave running both sweeps for every shape it takes (A/B tests)
+  static const int serial = env_int("NABU_CTC_WAVE_SERIAL", 0);
+  const size_t sshm = ctc_split_lds_bytes(T, C, Smax);
+  if (!force_wg && !serial && Lmax <= 63 && sshm <= 150 * 1024)    // the sweeps side by side where both lattices fit
+    return launch_lds(ctc_wave_split_kernel, dim3(B), dim3(64 * CTC_SPLIT_WAVES), sshm, s, p);
   const size_t wshm = ctc_wave_lds_bytes(T, C, Smax);
   if (!force_wg && Lmax <= 63 && wshm <= 150 * 1024)     // wave-synchronous kernel: one wave64 per utterance
     return launch_lds(ctc_wave_kernel, dim3(B), dim3(256), wshm, s, p);

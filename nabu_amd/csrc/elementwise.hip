@@ -574,6 +574,7 @@ struct FillArgs {
   unsigned *ptr[FILL_MAX];
   unsigned long long words[FILL_MAX];
   unsigned value[FILL_MAX];
+  const unsigned *from[FILL_MAX];     // non-null: the region is copied from here
   unsigned first_block[FILL_MAX + 1];
   int n;
 };
@@ -584,6 +585,10 @@ __global__ __launch_bounds__(256) void multi_fill_kernel(FillArgs a) {
   const unsigned long long w1 = w0 + FILL_CHUNK < a.words[i] ? w0 + FILL_CHUNK : a.words[i];
   const unsigned v = a.value[i];
   unsigned *p = a.ptr[i];
+  if (const unsigned *q = a.from[i]) {
+    for (unsigned long long w = w0 + threadIdx.x; w < w1; w += 256) p[w] = q[w];
+    return;
+  }
   for (unsigned long long w = w0 + 4ull * threadIdx.x; w < w1; w += 1024) {
     if (w + 3 < w1) *reinterpret_cast<uint4 *>(p + w) = make_uint4(v, v, v, v);
     else
@@ -832,6 +837,7 @@ int multi_fill(const FillSeg *segs, int n, hipStream_t stream) {
     a.ptr[a.n] = static_cast<unsigned *>(segs[i].ptr);
     a.words[a.n] = segs[i].words;
     a.value[a.n] = segs[i].value;
+    a.from[a.n] = static_cast<const unsigned *>(segs[i].from);
     a.first_block[a.n] = blocks;
     blocks += (unsigned)((segs[i].words + FILL_CHUNK - 1) / FILL_CHUNK);
     ++a.n;

@@ -688,6 +688,84 @@ __global__ __launch_bounds__(256) void pk_amax_kernel(const float *src, long lon
   }
 }
 
+// The same maxima without atomics, for sources wide enough that pk_amax_kernel's workgroups would meet many times on
+// every destination word (pk_amax_owned: the routing).  Every destination word has ONE owner, which reads all it needs
+// and folds it into the word once — dst = max(dst, measured), a plain read-modify-write, so zeroed and seeded arrays
+// both keep their meaning.  The source is read twice where rows and columns are both asked for (from cache).
+//   blocks [0, nb_col):  32 columns of one source over all R rows (8 threads x float4 across, 128 rows per pass)
+//   the others:          16 rows over all C columns of both sources (a wave per row)
+// 1024 threads with 8 (columns) resp. 16 (rows) 16-byte loads each in flight: one workgroup per CU has to keep the
+// whole device's loads in the air, and what bounds either maxima kernel is the bytes in flight, not the atomics.
+// Integer maxima of the same bit patterns as pk_amax_kernel's: the two kernels agree bit for bit.
+constexpr int PK_AMAX_OC = 32, PK_AMAX_OR = 16, PK_AMAX_ONT = 1024;
+__device__ __forceinline__ unsigned pk_abs_bits(float v) { return __builtin_bit_cast(unsigned, v) & 0x7FFFFFFFu; }
+__device__ __forceinline__ unsigned pk_abs_bits4(float4 v) {
+  return max(max(pk_abs_bits(v.x), pk_abs_bits(v.y)), max(pk_abs_bits(v.z), pk_abs_bits(v.w)));
+}
+__device__ __forceinline__ float4 pk_amax_load4(const float *s, int c, int C) {   // columns [c, c + 4) of a row, 0 beyond C
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (c + 3 < C) v = *reinterpret_cast<const float4 *>(s + c);
+  else {
+    if (c < C) v.x = s[c];
+    if (c + 1 < C) v.y = s[c + 1];
+    if (c + 2 < C) v.z = s[c + 2];
+  }
+  return v;
+}
+__global__ __launch_bounds__(PK_AMAX_ONT) void pk_amax_owner_kernel(const float *src0, const float *src1, long long ld, int R, int C,
+                                                                    int nb_col, int nb_col0, unsigned *rows, unsigned *cols0,
+                                                                    unsigned *cols1, unsigned *cols_b) {
+  const int tid = threadIdx.x;
+  if ((int)blockIdx.x < nb_col) {
+    constexpr int RP = PK_AMAX_ONT / 8;       // rows per pass
+    __shared__ unsigned cm[RP][PK_AMAX_OC];
+    const bool second = (int)blockIdx.x >= nb_col0;
+    const float *src = second ? src1 : src0;
+    unsigned *cols = second ? cols1 : cols0;
+    const int c0 = ((int)blockIdx.x - (second ? nb_col0 : 0)) * PK_AMAX_OC, c4 = (tid & 7) * 4, rl = tid >> 3;
+    unsigned m[4] = {0u, 0u, 0u, 0u};
+    for (int r0 = 0; r0 < R; r0 += 8 * RP) {
+      float4 v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int r = r0 + rl + RP * j;
+        v[j] = r < R ? pk_amax_load4(src + (size_t)r * ld, c0 + c4, C) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        m[0] = max(m[0], pk_abs_bits(v[j].x)); m[1] = max(m[1], pk_abs_bits(v[j].y));
+        m[2] = max(m[2], pk_abs_bits(v[j].z)); m[3] = max(m[3], pk_abs_bits(v[j].w));
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) cm[rl][c4 + q] = m[q];
+    __syncthreads();
+    if (tid < PK_AMAX_OC && c0 + tid < C) {
+      unsigned t = 0;
+#pragma unroll 16
+      for (int q = 0; q < RP; ++q) t = max(t, cm[q][tid]);
+      cols[c0 + tid] = max(cols[c0 + tid], t);
+      if (cols_b && !second) cols_b[c0 + tid] = max(cols_b[c0 + tid], t);
+    }
+    return;
+  }
+  const int lane = tid & 63, r = ((int)blockIdx.x - nb_col) * PK_AMAX_OR + (tid >> 6);
+  if (r >= R) return;                 // (wave-uniform)
+  const float *s0 = src0 + (size_t)r * ld, *s1 = src1 ? src1 + (size_t)r * ld : s0;
+  const int C1 = src1 ? C : 0;        // (no second source: its loads fall beyond C1 and read nothing)
+  unsigned m = 0;
+  for (int c = lane * 4; c < C; c += 8 * 256) {
+    float4 v[16];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { v[j] = pk_amax_load4(s0, c + 256 * j, C); v[8 + j] = pk_amax_load4(s1, c + 256 * j, C1); }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) m = max(m, pk_abs_bits4(v[j]));
+  }
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+  if (lane == 0) rows[r] = max(rows[r], m);
+}
+
 // row maxima from per-unit partial maxima (the backward recurrence keeps the largest |dz| of every gate column per
 // unit): dst[n] = bits of max_r src[r][n]
 __global__ void pk_colmax_kernel(int rows, int N, const float *src, int ld, unsigned *dst) {
@@ -739,6 +817,22 @@ __global__ __launch_bounds__(256) void pk_amax_persist_kernel(int nb_rows, int B
 __global__ void pk_fill_u32_kernel(unsigned *dst, int n, unsigned v) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) dst[i] = v;
+}
+
+// Which maxima kernel a shape takes.  pk_amax_kernel issues one atomicMax per 64-column piece of a row and one per
+// 256-row piece of a column; where that comes to more than PK_AMAX_PER_WORD per destination word on average, the
+// workgroups queue on the words (two [2048 x 2048] kernels: 164 000 onto 6 144 words) and pk_amax_owner_kernel takes
+// the shape.  A tall, narrow source (the features, [32000 x 40]: 1.2 per word) keeps the atomic kernel, and so does
+// any whose columns are longer than PK_AMAX_MAX_COL rows (a column owner walks its 32 columns alone) or that has fewer
+// than PK_AMAX_MIN_C columns to hand out (cfg1's features, [1600 x 40]: two owners took 8 us longer than the atomics).
+// NABU_PK_AMAX_ATOMIC=1 (read once per process): the atomic kernel for every shape (A/B tests).
+constexpr int PK_AMAX_PER_WORD = 2, PK_AMAX_MAX_COL = 8192, PK_AMAX_MIN_C = 256;
+static bool pk_amax_owned(int R, int C, bool rows, bool cols, int nsrc) {
+  static const int atomic_only = env_int("NABU_PK_AMAX_ATOMIC", 0);
+  if (atomic_only || (cols && (R > PK_AMAX_MAX_COL || C < PK_AMAX_MIN_C))) return false;
+  const long long atomics = (long long)nsrc * ((rows ? (long long)R * ((C + 63) / 64) : 0) + (cols ? (long long)C * ((R + 255) / 256) : 0));
+  const long long words = (rows ? R : 0) + (cols ? (long long)nsrc * C : 0);
+  return atomics > PK_AMAX_PER_WORD * words;
 }
 
 static int pk_cu_count() { return device_cus() > 0 ? device_cus() : 256; }
@@ -835,11 +929,7 @@ extern "C" int nabu_pk_amax(const float *src, long long ld, int R, int C, uint32
                             nabu_stream_t stream) {
   NABU_CHECK_ARG(src && R >= 0 && C >= 0 && ld >= 0 && (rows || cols), "pk_amax: bad arguments");
   if (ld % 4 || (reinterpret_cast<uintptr_t>(src) & 15)) return fail(NABU_EUNSUP, "pk_amax: source rows must be 16-byte aligned");
-  if (R == 0 || C == 0) return 0;
-  hipLaunchKernelGGL(pk_amax_kernel, dim3((C + 63) / 64, (R + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), src,
-                     ld, R, C, rows, cols);
-  NABU_LAUNCH_CHECK();
-  return 0;
+  return pk_amax_pair(src, nullptr, ld, R, C, rows, cols, nullptr, nullptr, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int nabu_pk_amax_fill(uint32_t *dst, int n, float value, nabu_stream_t stream) {
@@ -896,8 +986,16 @@ int pk_amax_pair(const float *src0, const float *src1, long long ld, int R, int 
   if (ld % 4 || (reinterpret_cast<uintptr_t>(src0) & 15) || (reinterpret_cast<uintptr_t>(src1) & 15))
     return fail(NABU_EUNSUP, "pk_amax_pair: source rows must be 16-byte aligned");
   if (R == 0 || C == 0) return 0;
-  hipLaunchKernelGGL(pk_amax_kernel, dim3((C + 63) / 64, (R + 255) / 256, src1 ? 2 : 1), dim3(256), 0, s, src0, ld, R, C, rows,
-                     cols0, src1, cols1, cols_b);
+  const bool pair_ok = !src1 || ((cols0 != nullptr) == (cols1 != nullptr) && !cols_b);    // one owner per column word
+  if (pair_ok && pk_amax_owned(R, C, rows != nullptr, cols0 != nullptr, src1 ? 2 : 1)) {
+    const int nb_col0 = cols0 ? (C + PK_AMAX_OC - 1) / PK_AMAX_OC : 0, nb_col = nb_col0 * (src1 ? 2 : 1);
+    const int nb_row = rows ? (R + PK_AMAX_OR - 1) / PK_AMAX_OR : 0;
+    hipLaunchKernelGGL(pk_amax_owner_kernel, dim3(nb_col + nb_row), dim3(PK_AMAX_ONT), 0, s, src0, src1, ld, R, C, nb_col, nb_col0, rows,
+                       cols0, cols1, cols_b);
+  } else {
+    hipLaunchKernelGGL(pk_amax_kernel, dim3((C + 63) / 64, (R + 255) / 256, src1 ? 2 : 1), dim3(256), 0, s, src0, ld, R, C, rows,
+                       cols0, src1, cols1, cols_b);
+  }
   NABU_LAUNCH_CHECK();
   return 0;
 }

@@ -150,6 +150,12 @@ struct Layout {
   size_t res_xT_off;         // 0: none.  x^T as a packed operand (the weight-gradient product's), written by the forward
                              // call from the read of x that packs its own operand (one pass over x less per step)
   size_t res_ahT_off;        // 0: none.  The known row bound of h^T (|h| <= 1), written by the forward call's one fill
+  bool x_colmax_kept;        // the whole-kernel form on f16x3 operands: EVERY forward call leaves the columns' maxima of x
+                             // at res_axT_off (a region this form has no other use for) — the backward pass's row maxima
+                             // of x^T.  A forward launch that reads x as planes measures them for its own scale anyway
+                             // (one measurement per step); any other forward path measures them behind its recurrence.
+                             // Decided by fields the reserve tag records (planes, pk_whole, flags) and a switch read
+                             // once per process: never by the mode or the launch plan, which may differ between the passes
   // per-workgroup row maxima of dz written by the persistent backward kernel ([2 directions x H / 16][BT] bit patterns;
   // 0 bytes where the layer has no input gradient): the row scales of dZ as [BT, 8H] without a pass over dz
   size_t pk_rowmax, pk_rowmax_bytes;
@@ -368,6 +374,9 @@ static Layout make_layout(const nabu_blstm_desc *d, bool ln) {
           L.reserve_bytes += aW;
         }
       }
+      // (NABU_PK_AMAX_ATOMIC=1, the A/B switch of the maxima kernels, also has the backward pass measure again)
+      static const int measure_twice = env_int("NABU_PK_AMAX_ATOMIC", 0);
+      L.x_colmax_kept = !measure_twice && !L.fwd_only && L.pk_whole;
       L.pk_ax = take(fwd, aBT); L.pk_aw = take(fwd, aG);
       L.pk_adz = take(bwd, aBT);
       L.pk_ahT[0] = take(bwd, aW); L.pk_ahT[1] = take(bwd, aW);
@@ -808,6 +817,14 @@ static int stepwise_bwd(const Call &c) {
 // stage: the forward recurrence and the companions behind it.  Persistent where the plan has a kernel for the shape;
 // a grid that cannot be co-resident on this device (the occupancy check before the launch says NABU_EUNSUP) steps
 // instead under NABU_LSTM_AUTO
+// (x_colmax_kept, for a forward path whose launch did not measure them)
+static int keep_x_colmax(const Call &c) {
+  uint32_t *keep = c.in_reserve<uint32_t>(c.L.res_axT_off);
+  const FillSeg fill = {keep, (size_t)c.D, 0u};
+  NABU_TRY(multi_fill(&fill, 1, c.s));
+  return nabu_pk_amax(c.x, c.D, c.B * c.T, c.D, nullptr, keep, c.stream);
+}
+
 static int recurrence_fwd(const Call &c, bool projected, bool ring_cleared) {
   const Layout &L = c.L;
   const Companions m = plan_companions(c);
@@ -816,10 +833,13 @@ static int recurrence_fwd(const Call &c, bool projected, bool ring_cleared) {
     NABU_TRY(c.mark(g_ev_begin));
     const int e = lstm_persist_fwd(L.plan, c.len, c.kern, c.gates, c.cs, c.out, reinterpret_cast<int *>(c.w), c.w + L.persist_off,
                                    L.persist_bytes, c.s, ring_cleared, fuse_in ? c.x : nullptr, fuse_in ? c.cell.bias : nullptr,
-                                   L.xws_bytes ? c.w + L.xws_off : nullptr, m.by_kernel ? &m.em : nullptr);
+                                   L.xws_bytes ? c.w + L.xws_off : nullptr, m.by_kernel ? &m.em : nullptr,
+                                   L.x_colmax_kept ? c.in_reserve<uint32_t>(L.res_axT_off) : nullptr);
     if (!(e == NABU_EUNSUP && c.d->mode == NABU_LSTM_AUTO)) {
       if (e) return e;
       NABU_TRY(c.mark(g_ev_end));
+      // (the launch prepared x as planes, and measured it, exactly where it fused the input and has a plane copy)
+      if (L.x_colmax_kept && !(fuse_in && L.plan.xws_bytes)) NABU_TRY(keep_x_colmax(c));
       return companions_by_pack_kernels(c, m, 7 & ~m.by_kernel);
     }
     if (!projected) {   // the step kernels read the projection from the gate buffers
@@ -828,6 +848,7 @@ static int recurrence_fwd(const Call &c, bool projected, bool ring_cleared) {
     }
   }
   NABU_TRY(stepwise_fwd(c));
+  if (L.x_colmax_kept) NABU_TRY(keep_x_colmax(c));
   return companions_by_pack_kernels(c, m, 7);
 }
 
@@ -987,13 +1008,15 @@ static int packed_dWh(const Call &c, const PackedBwd &k) {
   uint32_t *ahT[2] = {k.ahT[0], k.ahT[1]};
   if (P == 2 && L.res_ahT_off) {   // |h| <= 1: the bound sits in the reserve since the forward call (both cells share it)
     ahT[0] = ahT[1] = c.in_reserve<uint32_t>(L.res_ahT_off);
-  } else if (P == 2) {   // |h| <= 1 by construction (o · tanh c): one fill for both cells; the input features are measured
+  } else if (P == 2) {   // |h| <= 1 by construction (o · tanh c): one fill for both cells; the input features' maxima
+    // are the ones every forward call keeps (x_colmax_kept: copied into place by the same fill) or are measured here
     const unsigned hb = L.hT_ext ? CMP_AMAX_BITS : bound_bits(1.0f);
-    const FillSeg fill[4] = {{ahT[0], (size_t)r0, 0u}, {ahT[0] + r0, (size_t)(rpW - r0), hb},
-                             {ahT[1], (size_t)r0, 0u}, {ahT[1] + r0, (size_t)(rpW - r0), hb}};
+    const uint32_t *kept = L.x_colmax_kept ? c.in_reserve<uint32_t>(L.res_axT_off) : nullptr;
+    const FillSeg fill[4] = {{ahT[0], (size_t)r0, 0u, kept}, {ahT[0] + r0, (size_t)(rpW - r0), hb},
+                             {ahT[1], (size_t)r0, 0u, kept}, {ahT[1] + r0, (size_t)(rpW - r0), hb}};
     // (r0 = D is a multiple of 4: every region starts 16-byte aligned)
     NABU_TRY(multi_fill(fill, 4, c.s));
-    if (L.pk_whole) NABU_TRY(pk_amax_pair(x, nullptr, D, M, D, nullptr, ahT[0], nullptr, ahT[1], c.s));
+    if (L.pk_whole && !kept) NABU_TRY(pk_amax_pair(x, nullptr, D, M, D, nullptr, ahT[0], nullptr, ahT[1], c.s));
   }
   {   // [x^T ;] h^T of both cells: one launch
     PkPackReq rq[4];

@@ -46,12 +46,14 @@ PersistPlan lstm_persist_plan(int B, int T, int D, int H, int max_len, bool exac
 void lstm_persist_set_timeout_us(long long us);
 unsigned long long lstm_persist_timeout_ticks();   // bound of every in-kernel wait (wall_clock64 ticks)
 // x, bias given (plan.fuses_input only): gates[] need NOT hold the input projection; the kernel still leaves the
-// activations there.  xws: plan.xws_bytes bytes.  emit (plan.emits only): the companions to write.
+// activations there.  xws: plan.xws_bytes bytes.  emit (plan.emits only): the companions to write.  x_colmax (optional,
+// D words, 16-byte aligned; used where plan.xws_bytes > 0): the launch's preparation of x leaves the bit patterns of
+// the columns' largest |x| there as well (it measures them for its own scale)
 int lstm_persist_fwd(const PersistPlan &plan, const int32_t *len,
                      const float *const kernel[2], float *const gates[2], float *const cs[2],
                      float *out, int *status, void *ws, size_t ws_bytes, hipStream_t stream, bool ring_cleared,
                      const float *x = nullptr, const float *const bias[2] = nullptr, void *xws = nullptr,
-                     const EmitArgs *emit = nullptr);
+                     const EmitArgs *emit = nullptr, uint32_t *x_colmax = nullptr);
 int lstm_persist_bwd(const PersistPlan &plan, const int32_t *len,
                      const float *const kernel[2], float *const gates[2], float *const cs[2],
                      const float *dout, int *status, void *ws, size_t ws_bytes, float **db_part, int *db_rows,

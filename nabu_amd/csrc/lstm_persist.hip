@@ -681,7 +681,7 @@ int lstm_mx_chunk_rows();                                  // lstm_persist_mxh.h
 size_t lstm_mxh_ring_bytes(bool fwd, int H);
 int lstm_mxh_launch(bool fwd, int H, const PersistArgs &a, hipStream_t stream, bool dry);
 size_t lstm_mxh_xws_bytes(int B, int T);
-int lstm_mxh_prepare_x(int B, int T, int D, const float *x, void *ws, hipStream_t stream, const FillSeg *also);
+int lstm_mxh_prepare_x(int B, int T, int D, const float *x, void *ws, hipStream_t stream, const FillSeg *also, uint32_t *keep);
 size_t lstm_mxf_ring_bytes(bool fwd, int H);               // lstm_persist_mxf.hip
 int lstm_mxf_launch(bool fwd, int H, const PersistArgs &a, hipStream_t stream, bool dry);
 
@@ -826,6 +826,7 @@ struct PassArgs {
   const float *const *bias;
   void *xws;
   const EmitArgs *emit;
+  uint32_t *x_colmax;     // optional: where the columns' maxima of x stay for the caller (lstm_mxh_prepare_x)
 };
 
 // one launch of ln.rows batch rows starting at row b0 of the batch
@@ -918,7 +919,7 @@ static int run(bool fwd, const PersistPlan &plan, const PassArgs &t, int *status
     shards = 0;
     if (pass == 1 && t.x && plan.xws_bytes) {     // the fp16-plane kernels read x as planes; the fill clears the ring too
       const FillSeg ring = {ws, plan.caller_ring_words, 0xFFFFFFFFu};
-      if (int e = lstm_mxh_prepare_x(B, T, plan.D, t.x, t.xws, stream, ring.words ? &ring : nullptr)) return e;
+      if (int e = lstm_mxh_prepare_x(B, T, plan.D, t.x, t.xws, stream, ring.words ? &ring : nullptr, t.x_colmax)) return e;
       ring_cleared = ring.words > 0;
     }
     for (int b0 = 0; b0 < B; b0 += ps.full.rows) {
@@ -944,8 +945,8 @@ static int run(bool fwd, const PersistPlan &plan, const PassArgs &t, int *status
 int lstm_persist_fwd(const PersistPlan &plan, const int32_t *len,
                      const float *const kernel[2], float *const gates[2], float *const cs[2],
                      float *out, int *status, void *ws, size_t ws_bytes, hipStream_t stream, bool ring_cleared,
-                     const float *x, const float *const bias[2], void *xws, const EmitArgs *emit) {
-  const PassArgs t = {len, kernel, {gates[0], gates[1]}, {cs[0], cs[1]}, out, nullptr, x, bias, xws, emit};
+                     const float *x, const float *const bias[2], void *xws, const EmitArgs *emit, uint32_t *x_colmax) {
+  const PassArgs t = {len, kernel, {gates[0], gates[1]}, {cs[0], cs[1]}, out, nullptr, x, bias, xws, emit, x_colmax};
   return run(true, plan, t, status, ws, ws_bytes, nullptr, nullptr, stream, ring_cleared, nullptr, nullptr);
 }
 

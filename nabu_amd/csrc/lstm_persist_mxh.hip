@@ -26,6 +26,7 @@
 // lstm_persist_mxh.h; the bf16-plane predecessors of these kernels (rounds 4a: lstm_persist_mx.hip, lstm_persist_mx16.hip)
 // are parked under tools/experiments/variants/.
 #include "lstm_persist_mxh.h"
+#include "gemm_args.h"      // pk_amax_pair
 
 #include <assert.h>
 
@@ -531,12 +532,15 @@ __global__ __launch_bounds__(256) void mxh_xplanes_kernel(int frames, int D, con
   *reinterpret_cast<u32x4 *>(dst + 128) = l;
 }
 size_t lstm_mxh_xws_bytes(int B, int T) { return 1024 + (size_t)B * T * 256; }
-// x [B, T, D] -> ws (lstm_mxh_xws_bytes): three small launches (zero the maxima, measure, convert)
-int lstm_mxh_prepare_x(int B, int T, int D, const float *x, void *ws, hipStream_t stream, const FillSeg *also) {
+// x [B, T, D] -> ws (lstm_mxh_xws_bytes): three small launches (zero the maxima, measure, convert).  keep (optional, D
+// words, 16-byte aligned): receives the columns' maxima as well, for a caller that needs them after the workspace is gone
+// (the layer's backward pass: the row scales of x^T)
+int lstm_mxh_prepare_x(int B, int T, int D, const float *x, void *ws, hipStream_t stream, const FillSeg *also, uint32_t *keep) {
   if (D > 64 || D % 8) return fail(NABU_EUNSUP, "persistent LSTM (mxh): in-kernel input projection takes D <= 64, D %% 8 == 0 (lstm_persist_fuses_input)");
-  const FillSeg seg[2] = {{ws, 256, 0u}, also ? *also : FillSeg{nullptr, 0, 0u}};    // (also: the exchange ring)
-  if (int e = multi_fill(seg, 2, stream)) return e;
-  if (int e = nabu_pk_amax(x, D, B * T, D, nullptr, static_cast<uint32_t *>(ws) + 16, stream)) return e;
+  const FillSeg seg[3] = {{ws, 256, 0u}, also ? *also : FillSeg{nullptr, 0, 0u},     // (also: the exchange ring)
+                          {keep, keep ? (size_t)D : 0, 0u}};
+  if (int e = multi_fill(seg, 3, stream)) return e;
+  if (int e = pk_amax_pair(x, nullptr, D, B * T, D, nullptr, static_cast<uint32_t *>(ws) + 16, nullptr, keep, stream)) return e;
   const size_t n = (size_t)B * T * 8;
   hipLaunchKernelGGL(mxh_xplanes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, B * T, D, x, static_cast<char *>(ws));
   NABU_LAUNCH_CHECK();
