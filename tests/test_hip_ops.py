@@ -348,11 +348,12 @@ def test_gemm_bf16_split_precisions(ta, tb, prec, tol):
         assert out[prec] > 1e-4                  # really the low-precision path
 
 
-def test_gemm_bf16x6_split_k_and_segmented_k():
-    """the weight-gradient shapes: deterministic split-K and the shifted h^T dz product"""
+def test_gemm_bf16x6_split_k_and_default_precision_switch():
+    """a weight-gradient shape (x^T dz, K = 4096 unsegmented: bf16x6 on 8 k-slices): against float64, deterministic
+    split-K, and the process-wide default precision selects the same kernel.  (Segmented K on the plane kernels:
+    tests/test_hip_gemm_routes.py, case seg96-bf16x6.)"""
     from nabu_amd import ops
     rng = np.random.default_rng(5)
-    Bn, T, H, G = 8, 64, 64, 256                 # K = Bn*(T-1) = 504 -> not a multiple of 32: exact-fp32 fallback
     x = rng.normal(size=(4096, 128)).astype(np.float32)
     dz = rng.normal(size=(4096, 256)).astype(np.float32)
     ref = x.astype(np.float64).T @ dz.astype(np.float64)
