@@ -420,6 +420,45 @@ int nabu_ctc_loss_grad(int B, int T, int C, int Lmax, const float *logits,
                        float *dlogits, int32_t *status, void *ws, size_t ws_bytes,
                        nabu_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Forced alignment with a CTC model (ctc_align.hip): the best path through the lattice nabu_ctc_loss_grad sums over.
+ * Same operands and conventions: raw batch-major logits [B,T,C], blank = C-1, labels [B,Lmax], frames >= logit_len
+ * ignored.
+ *
+ * Definition.  ext[s] is the blank for even s and labels[s>>1] for odd s; S = 2L+1.  The recursion runs on the RAW
+ * logits x, not on log-probabilities: every path visits every frame once, so the frame normalisers cannot change the
+ * arg-max; leaving them out keeps exp and log out of the frame loop and makes ties well defined.
+ *   v[0][0] = x[0][blank], v[0][1] = x[0][ext[1]], the rest unreachable;
+ *   v[t][s] = x[t][ext[s]] + max over  stay s | step s-1 | skip s-2 (odd s with ext[s] != ext[s-2] only).
+ * A tie keeps the SMALLER move: the step wins only if strictly greater than the stay, the skip only if strictly
+ * greater than both.  The path ends in state S-1, unless S >= 2 and v[Tb-1][S-2] > v[Tb-1][S-1] strictly.
+ * Unreachable is the finite -1e30 of nabu_ctc_loss_grad: it never wins against a reachable value, and no inf - inf
+ * arises.
+ *   state [B,T] int32     lattice state 0..2L of every frame, -1 from logit_len[b] on
+ *   seg [B,Lmax,2] int32  first frame and last frame + 1 of label i; -1 beyond L
+ *   conf [B,Lmax]         mean over the segment's frames of log softmax(x[t])[label] (0 beyond L)
+ *   score [B]             sum over the frames of log softmax(x[t])[ext[state[t]]]
+ * with log softmax evaluated as (x - mx) - lz, maximum and log-sum kept apart as in the loss.  score is summed in a
+ * fixed order (a tree over frames) and conf in frame order, without floating-point atomics: identical calls give
+ * identical bits.
+ * An utterance with a label < 0 or >= C-1, logit_len <= 0, or label_len + adjacent repeats > logit_len (the loss's
+ * test) gets score = -inf, state and seg -1, conf 0, and sets status [1] (device) to 1+b through
+ * atomicCAS(status, 0, b+1), repeated while a later utterance holds the word: status names the FIRST such utterance
+ * of the batch.  The other utterances are aligned normally.  L = 0 is valid: every frame is in state 0.
+ * Routes: Lmax <= 63: one wave64 per utterance, two states per lane, no barrier in the frame loop; otherwise 256
+ * threads with the states strided over them.  Back-pointers live in LDS while they fit and in ws otherwise;
+ * NABU_CTC_ALIGN_WORKGROUP=1 forces the second route.  Every shape nabu_ctc_loss_grad's workgroup kernel takes is
+ * taken.
+ * NABU_EINVAL: a null pointer (labels may be null for Lmax = 0), B or T <= 0, C <= 1, Lmax < 0.  NABU_EWS:
+ * ws_bytes < nabu_ctc_align_ws_bytes(B,T,Lmax) (0 for B or T <= 0 or Lmax < 0).  NABU_EUNSUP: more LDS than a
+ * workgroup has, with the byte count in the message.  All three return before any launch. */
+size_t nabu_ctc_align_ws_bytes(int B, int T, int Lmax);
+int nabu_ctc_align(int B, int T, int C, int Lmax, const float *logits,
+                   const int32_t *logit_len, const int32_t *labels,
+                   const int32_t *label_len, int32_t *state, int32_t *seg, float *conf,
+                   float *score, int32_t *status, void *ws, size_t ws_bytes,
+                   nabu_stream_t stream);
+
 /* Masked sparse softmax cross-entropy averaged over the target length —
  * loss_functions.average_cross_entropy / cross_entropy
  * (nabu/neuralnetworks/trainers/loss_functions.py:78-109,155-165):

@@ -4,14 +4,23 @@ nabu_ctc_beam_search, one workgroup per utterance on the device — and the erro
 label edit distance summed over the batch divided by the number of reference labels."""
 import os
 
+import numpy as np
 import torch
 
 from nabu_amd import ops
 from nabu_amd.autodiff import SeqLen
-from nabu_amd.neuralnetworks.decoders import decoder
+from nabu_amd.neuralnetworks.decoders import ctc_alignment_decoder, decoder
 from nabu_amd.processing import ngram_lm
 
 BEAM_WIDTH = 100          # tf.nn.ctc_beam_search_decoder's default, which the reference relies on
+
+
+def timestamps_key(conf):
+    """the `timestamps` key of the [decoder] section (an extension key: absent from the defaults, off when absent)"""
+    text = str(conf.get('timestamps', 'False')).strip()
+    if text not in ('True', 'False'):
+        raise ValueError('timestamps must be True or False, got %r' % text)
+    return text == 'True'
 
 
 class CTCDecoder(decoder.Decoder):
@@ -28,10 +37,16 @@ class CTCDecoder(decoder.Decoder):
         if lm_file is not None:
             for o in model.output_names:
                 self.lm = ngram_lm.load(lm_file, model.output_dims[o], self.alphabets[o])
+        # timestamps (extension key): after the search the recognised labels are aligned to the same logits
+        # (nabu_ctc_align) and `write` adds <output>.ctm — name 1 start duration symbol confidence per label, in encoded
+        # frames, or in seconds with frame_seconds > 0 (seconds per ENCODED frame; ctc_alignment_decoder.py)
+        self.timestamps = timestamps_key(self.conf)
+        self.frame_seconds = ctc_alignment_decoder.frame_seconds_key(self.conf) if self.timestamps else 0.0
 
     def __call__(self, inputs, input_seq_length):
         '''Returns {output: (ids [B,T'] int32 padded with -1, lengths [B] int32)} — the dense form
-        of the reference's SparseTensor'''
+        of the reference's SparseTensor; with timestamps = True the tuple goes on with (seg [B,T',2], conf [B,T'],
+        score [B]) of ops.ctc_align'''
         with torch.no_grad():
             logits, logit_len = self.model(inputs, input_seq_length, targets=[], target_seq_length=[],
                                            is_training=False)
@@ -45,22 +60,35 @@ class CTCDecoder(decoder.Decoder):
                                                              self.lm.order, self.lm_weight, self.insertion_bonus,
                                                              BEAM_WIDTH, merge_repeated=True)
                 outputs[o] = (ids, out_len)
+                if self.timestamps:
+                    _, seg, conf, score, _ = ops.ctc_align(logits[o].contiguous(), lens.dev, ids.clamp(min=0).contiguous(),
+                                                           out_len)
+                    outputs[o] += (seg, conf, score)
         return outputs
 
     def write(self, outputs, directory, names):
         '''one line "<name> <symbols>" per utterance appended to <directory>/<output>'''
-        for o, (ids, lens) in outputs.items():
-            ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
+        for o, out in outputs.items():
+            ids, lens = out[0].cpu().numpy(), out[1].cpu().numpy()
             with open(os.path.join(directory, o), 'a') as fid:
                 for i, name in enumerate(names):
                     text = ' '.join(self.alphabets[o][j] for j in ids[i, :lens[i]])
                     fid.write('%s %s\n' % (name, text))
+            if len(out) > 2:        # timestamps: a hypothesis that does not fit its frames (score -inf) gets no lines
+                seg, conf, score = (a.cpu().numpy() for a in out[2:5])
+                with open(os.path.join(directory, o + '.ctm'), 'a') as fid:
+                    for i, name in enumerate(names):
+                        if np.isfinite(score[i]):
+                            symbols = [self.alphabets[o][j] for j in ids[i, :lens[i]]]
+                            fid.writelines(ctc_alignment_decoder.ctm_lines(name, seg[i, :lens[i]], conf[i, :lens[i]],
+                                                                           symbols, self.frame_seconds))
 
     def update_evaluation_loss(self, loss, outputs, references, reference_seq_length):
         '''label error rate: sum of edit distances / number of reference labels, running over
         the batches seen since reset()'''
         errors, batch_targets = 0, 0
-        for o, (ids, lens) in outputs.items():
+        for o, out in outputs.items():
+            ids, lens = out[0], out[1]
             dev = ids.device
             ref = torch.as_tensor(references[o]).to(torch.int32).to(dev)
             ref_len = SeqLen.wrap(reference_seq_length[o], dev)

@@ -6,5 +6,6 @@ factory = Registry('decoder', {
     'beam_search_decoder': 'nabu_amd.neuralnetworks.decoders.beam_search_decoder:BeamSearchDecoder',
     'alignment_decoder': 'nabu_amd.neuralnetworks.decoders.alignment_decoder:AlignmentDecoder',
     'random_decoder': 'nabu_amd.neuralnetworks.decoders.random_decoder:RandomDecoder',
+    'ctc_alignment_decoder': 'nabu_amd.neuralnetworks.decoders.ctc_alignment_decoder:CTCAlignmentDecoder',
 }, outside=('max_decoder', 'threshold_decoder', 'feature_decoder'),
     undefined='Undefined %s type: %s')

@@ -367,6 +367,32 @@ def ctc_loss_grad(logits, logit_len_dev, labels_dev, label_len_dev, grad_scale):
     return nll, dlogits, status
 
 
+def ctc_align(logits, logit_len_dev, labels_dev, label_len_dev, raise_on_status=False):
+    """Forced alignment (nabu_ctc_align): returns (state [B,T] int32, seg [B,Lmax,2] int32, conf [B,Lmax],
+    score [B], status [1] int32) — all on device.  status is 1+b for the first utterance b without a valid alignment;
+    raise_on_status: read it back (a synchronisation) and raise what the CTC loss raises for such an utterance."""
+    L = _hip.lib()
+    B, T, C = logits.shape
+    Lmax = labels_dev.shape[1]
+    dev = logits.device
+    state = torch.empty((B, T), dtype=torch.int32, device=dev)
+    seg = torch.empty((B, Lmax, 2), dtype=torch.int32, device=dev)
+    conf = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = L.nabu_ctc_align_ws_bytes(B, T, Lmax)
+    ws = Workspace.get(ws_bytes, dev, 'ctc_align')
+    check(L.nabu_ctc_align(B, T, C, Lmax, ptr(_f32(logits, 'logits')), ptr(logit_len_dev),
+                           ptr(labels_dev) if Lmax else None, ptr(label_len_dev), ptr(state), ptr(seg), ptr(conf),
+                           ptr(score), ptr(status), ptr(ws), ws_bytes, stream()), 'nabu_ctc_align')
+    if raise_on_status:
+        code = int(status.item())
+        if code:
+            from nabu_amd.neuralnetworks.trainers import loss_functions
+            raise loss_functions.ctc_status_error(code)
+    return state, seg, conf, score, status
+
+
 def adam_clip_step(param, grad, m, v, lr_t, b1=0.9, b2=0.999, eps=1e-8, clip=1.0, grad_scale=1.0):
     check(_hip.lib().nabu_adam_clip_step(param.numel(), ptr(param), ptr(grad), ptr(m), ptr(v), lr_t, b1, b2,
                                          eps, clip, grad_scale, stream()), 'nabu_adam_clip_step')
