@@ -12,87 +12,101 @@ __device__ __forceinline__ float clip_value(float x, float clip) {
   return x != x ? x : fminf(fmaxf(x, -clip), clip);
 }
 
-// the trailing `acc` argument of adam_clip_kernel, when it has one
-__device__ __forceinline__ const float *acc_of() { return nullptr; }
-__device__ __forceinline__ const float *acc_of(const float *acc) { return acc; }
-
 // ---------------------------------------------------------------------------
 // fused clip + TF-style Adam: 4 streams read (param, grad, m, v), 3 written.
 // 16-byte accesses, grid-stride, 7*4 = 28 algorithmic bytes per parameter.
-// FROM: the parameter is read from `src` instead of p (nabu_adam_clip_step_from: the update of a step whose forward and
-// backward passes ran at p = src + noise); the one difference, every other expression is the plain kernel's.
-// ACC...: empty, or one `float` for a trailing argument `acc`: the gradient is then acc + clamp(g, +-clip), the sum of an
-// update's earlier clipped micro-batch gradients and the last one (nabu_adam_clip_step_acc): one more stream read,
-// 32 bytes per parameter, and no accumulate pass before it.  A pack, not a bool: with it empty the kernel has the
-// arguments, and so the code, it always had.
-template <bool FROM, typename... ACC>
-__global__ __launch_bounds__(256) void adam_clip_kernel(size_t n, float *__restrict__ p,
-                                                        const float *__restrict__ src,
-                                                        const float *__restrict__ g,
-                                                        float *__restrict__ m,
-                                                        float *__restrict__ v, float lr_t,
-                                                        float b1, float b2, float eps,
-                                                        float clip, float gscale,
-                                                        const ACC *__restrict__... acc_arg) {
-  constexpr bool WITH_ACC = sizeof...(ACC) == 1;
-  const float *__restrict__ acc = acc_of(acc_arg...);
+struct AdamHyper {
+  float lr_t, b1, b2, eps;
+};
+
+// rn(a * b) as a value of its own.  Under -ffp-contract=fast the backend fuses any product into a sum it feeds, whatever the
+// source says (`#pragma clang fp contract(off)` is disregarded in that mode, and __fmul_rn is a plain product here); a
+// value that has passed an asm statement is no product to it.  The statement emits no instruction.
+__device__ __forceinline__ float rounded_product(float a, float b) {
+  float ab = a * b;
+  asm("" : "+v"(ab));
+  return ab;
+}
+
+// The Adam update of one element on the gradient x, every rounding of m and v written down: the bits of a training
+// trajectory must not depend on which product a compiler chooses to contract.
+// FUSED (the 16-byte groups, which is all a training buffer has: Variables.flatten pads every variable to a multiple of
+// 4): one rounding each for b1 m + ((1 - b1) x) and for x ((1 - b2) x) + (b2 v).
+// !FUSED (the n % 4 elements after them, which only tests reach): every product and sum rounded.  The form exists only to
+// keep the bits this tail has always had.
+// lr_t m / (sqrt(v) + eps) has no product feeding a sum, so nothing there can be contracted.
+// tests/test_hip_update_bits.py holds both forms to bits recorded on the device.
+template <bool FUSED>
+__device__ __forceinline__ void adam1(float &p, float &m, float &v, float x, const AdamHyper &h) {
+  if (FUSED) {
+    m = fmaf(h.b1, m, (1.f - h.b1) * x);
+    v = fmaf(x, (1.f - h.b2) * x, h.b2 * v);
+  } else {
+    m = rounded_product(h.b1, m) + rounded_product(1.f - h.b1, x);
+    v = rounded_product(h.b2, v) + rounded_product((1.f - h.b2) * x, x);
+  }
+  p -= h.lr_t * m / (sqrtf(v) + h.eps);
+}
+
+// the gradient adam_kernel's update takes, from the last micro-batch's g and the sum `a` of the earlier ones (ACC)
+template <bool ACC, bool NORM>
+__device__ __forceinline__ float adam_gradient(float a, float g, float gscale, float clip) {
+  if (NORM) return (ACC ? a + g : g) * gscale;
+  return clip_value((ACC ? a + clip_value(g, clip) : g) * gscale, clip);
+}
+
+// FROM: the parameter is read from `src` instead of p (the update of a step whose forward and backward passes ran at
+// p = src + noise).
+// ACC: the gradient is the sum of `acc`, an update's earlier micro-batch gradients, and g, the last one: one more stream
+// read, 32 bytes per parameter, and no accumulate pass before the update.
+// NORM false: clipping by value.  x = clamp((ACC ? acc + clamp(g) : g) * gscale), both clamps to +-clip.
+// NORM true: clipping by the global norm (nabu_grad_norm_f32 ran before on the same stream).  x = (ACC ? acc + g : g) *
+// stats[1], read on the device, no clamp; clip and gscale are not read.  A NaN factor is a skipped update: m and v are
+// not touched and the parameter is not updated — with FROM p still becomes src, because it holds the noisy values of a
+// weight-noise step at this point.  Bit for bit the NORM = false kernel at clip = +inf and gscale = stats[1].
+template <bool FROM, bool ACC, bool NORM>
+__global__ __launch_bounds__(256) void adam_kernel(size_t n, float *__restrict__ p, const float *__restrict__ src,
+                                                   const float *__restrict__ acc, const float *__restrict__ g,
+                                                   float *__restrict__ m, float *__restrict__ v, AdamHyper h, float clip,
+                                                   float gscale, const float *__restrict__ stats) {
+  if (NORM) gscale = stats[1];
   const size_t n4 = n / 4;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (NORM && gscale != gscale) {
+    if (FROM) {
+      for (size_t i = tid; i < n4; i += stride) reinterpret_cast<float4 *>(p)[i] = reinterpret_cast<const float4 *>(src)[i];
+      for (size_t i = n4 * 4 + tid; i < n; i += stride) p[i] = src[i];
+    }
+    return;
+  }
   for (size_t i = tid; i < n4; i += stride) {
     float4 pp = FROM ? reinterpret_cast<const float4 *>(src)[i] : reinterpret_cast<float4 *>(p)[i];
-    float4 gg = reinterpret_cast<const float4 *>(g)[i];
-    if (WITH_ACC) {
-      const float4 aa = reinterpret_cast<const float4 *>(acc)[i];
-      gg.x = aa.x + clip_value(gg.x, clip);
-      gg.y = aa.y + clip_value(gg.y, clip);
-      gg.z = aa.z + clip_value(gg.z, clip);
-      gg.w = aa.w + clip_value(gg.w, clip);
-    }
+    const float4 gg = reinterpret_cast<const float4 *>(g)[i];
+    const float4 aa = ACC ? reinterpret_cast<const float4 *>(acc)[i] : float4{};
     float4 mm = reinterpret_cast<float4 *>(m)[i];
     float4 vv = reinterpret_cast<float4 *>(v)[i];
-#define NABU_ADAM1(c)                                           \
-  {                                                             \
-    float x = clip_value(gg.c * gscale, clip);                  \
-    mm.c = b1 * mm.c + (1.f - b1) * x;                          \
-    vv.c = b2 * vv.c + (1.f - b2) * x * x;                      \
-    pp.c -= lr_t * mm.c / (sqrtf(vv.c) + eps);                  \
-  }
-    NABU_ADAM1(x) NABU_ADAM1(y) NABU_ADAM1(z) NABU_ADAM1(w)
+    adam1<true>(pp.x, mm.x, vv.x, adam_gradient<ACC, NORM>(aa.x, gg.x, gscale, clip), h);
+    adam1<true>(pp.y, mm.y, vv.y, adam_gradient<ACC, NORM>(aa.y, gg.y, gscale, clip), h);
+    adam1<true>(pp.z, mm.z, vv.z, adam_gradient<ACC, NORM>(aa.z, gg.z, gscale, clip), h);
+    adam1<true>(pp.w, mm.w, vv.w, adam_gradient<ACC, NORM>(aa.w, gg.w, gscale, clip), h);
     reinterpret_cast<float4 *>(p)[i] = pp;
     reinterpret_cast<float4 *>(m)[i] = mm;
     reinterpret_cast<float4 *>(v)[i] = vv;
   }
   for (size_t i = n4 * 4 + tid; i < n; i += stride) {
-    float x = clip_value((WITH_ACC ? acc[i] + clip_value(g[i], clip) : g[i]) * gscale, clip);
-    float mm = b1 * m[i] + (1.f - b1) * x;
-    float vv = b2 * v[i] + (1.f - b2) * x * x;
+    float pp = FROM ? src[i] : p[i], mm = m[i], vv = v[i];
+    adam1<false>(pp, mm, vv, adam_gradient<ACC, NORM>(ACC ? acc[i] : 0.f, g[i], gscale, clip), h);
     m[i] = mm;
     v[i] = vv;
-    float pp = FROM ? src[i] : p[i];
-    pp -= lr_t * mm / (sqrtf(vv) + eps);
     p[i] = pp;
   }
 }
 
-__global__ __launch_bounds__(256) void clip_kernel(size_t n, float *__restrict__ g, float clip) {
-  const size_t n4 = n / 4;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (size_t i = tid; i < n4; i += stride) {
-    float4 x = reinterpret_cast<float4 *>(g)[i];
-    x.x = clip_value(x.x, clip);
-    x.y = clip_value(x.y, clip);
-    x.z = clip_value(x.z, clip);
-    x.w = clip_value(x.w, clip);
-    reinterpret_cast<float4 *>(g)[i] = x;
-  }
-  for (size_t i = n4 * 4 + tid; i < n; i += stride) g[i] = clip_value(g[i], clip);
-}
-
 // out = clamp(g, +-clip) (+ acc): one micro-batch's clipped gradient added to the sum of the earlier ones.  ACC false is
 // the first micro-batch: a pure write, the accumulator is neither cleared nor read (8 bytes per parameter, 12 with acc).
-// out may BE acc or g (no __restrict__: every thread reads its elements before it writes them, nobody else touches them).
+// out may BE acc or g (no __restrict__: every thread reads its elements before it writes them, nobody else touches them);
+// ACC false with out = g is the clamp in place of nabu_clip_f32.
 template <bool ACC>
 __global__ __launch_bounds__(256) void clip_accumulate_kernel(size_t n, float *out, const float *acc, const float *g,
                                                               float clip) {
@@ -122,7 +136,7 @@ __global__ __launch_bounds__(256) void clip_accumulate_kernel(size_t n, float *o
 
 // ---------------------------------------------------------------------------
 // global-norm clipping (the [trainer] key clip_gradient_norm): the L2 norm of the flat gradient in two launches, and the
-// Adam update that reads its scale factor from the device.
+// Adam update that reads its scale factor from the device (adam_kernel with NORM).
 // block-wide sum of one double (fixed tree: deterministic); the result is red[0]
 __device__ __forceinline__ void block_sum_f64(double s, double *red) {
   red[threadIdx.x] = s;
@@ -134,7 +148,7 @@ __device__ __forceinline__ void block_sum_f64(double s, double *red) {
 }
 
 // stage 1: partial[block] = sum of x^2 over the block's grid-stride share, x = g or (fp32) acc + g, what
-// adam_scaled_kernel forms.  A product of two floats is exact in double and every term is >= 0, so the sum carries a
+// adam_kernel forms with NORM.  A product of two floats is exact in double and every term is >= 0, so the sum carries a
 // relative error of (additions in the longest chain) * 2^-53 whatever the magnitudes: 1e30 does not overflow, 1e-30 does
 // not vanish.  4 or 8 bytes read per parameter; the conversions and double FMAs are far below the vector rate.  A thread
 // keeps one chain per lane of its 16-byte groups and joins them in a fixed order.
@@ -173,7 +187,7 @@ __global__ __launch_bounds__(256) void grad_norm_stage1(size_t n, const float *_
 // stage 2, one block behind a kernel boundary (the partials of other XCDs are visible): S = sum of the partials in a
 // fixed order, then the four words of `stats`.  norm = (float)(scale * sqrt(S)); factor = what the update multiplies the
 // gradient sum by: scale, times max_norm / norm when the norm exceeds max_norm (a norm of 0 never divides); a norm that
-// is NaN or inf gives factor = NaN, which adam_scaled_kernel takes as "skip", and counts in stats[2].
+// is NaN or inf gives factor = NaN, which adam_kernel takes as "skip", and counts in stats[2].
 __global__ __launch_bounds__(256) void grad_norm_stage2(int nparts, const double *__restrict__ partial, float scale,
                                                         float max_norm, float *__restrict__ stats) {
   __shared__ double red[256];
@@ -189,69 +203,6 @@ __global__ __launch_bounds__(256) void grad_norm_stage2(int nparts, const double
   stats[1] = finite ? factor : __int_as_float(0x7fc00000);
   if (!finite) words[2] += 1;
   words[3] = 0;
-}
-
-// adam_clip_kernel without a clamp and with gscale = stats[1], read on the device: the update of a step whose gradient is
-// clipped by its global norm (nabu_grad_norm_f32 ran before it on the same stream).  FROM and ACC as there, the gradient
-// with ACC is acc + g.  A NaN factor is a skipped update: m and v are not touched and the parameter is not updated —
-// with FROM param_out still becomes src, because it holds the noisy values of a weight-noise step at this point.
-// Bit for bit adam_clip_kernel at clip = +inf and the same gscale.  That kernel's NABU_ADAM1 cannot simply be reused
-// without its clamp: under -ffp-contract=fast the compiler picks the product it fuses by the shape of the expression, and
-// with x a plain product it fuses (1 - b1) * x where adam_clip_kernel fuses b1 * m.  So the 16-byte body spells out the
-// roundings adam_clip_kernel's has (m = fma(b1, m, (1 - b1) x), v = fma(x, (1 - b2) x, b2 v)), which fmaf pins; the
-// tail keeps the source form of that kernel's tail, which compiles without fusion in both.
-// tests/test_hip_grad_norm.py compares the two kernels at every size and argument combination.
-#define NABU_ADAM_SCALED1(c)                                    \
-  {                                                             \
-    const float x = gg.c * gscale;                              \
-    mm.c = fmaf(b1, mm.c, (1.f - b1) * x);                      \
-    vv.c = fmaf(x, (1.f - b2) * x, b2 * vv.c);                  \
-    pp.c -= lr_t * mm.c / (sqrtf(vv.c) + eps);                  \
-  }
-template <bool FROM, bool ACC>
-__global__ __launch_bounds__(256) void adam_scaled_kernel(size_t n, float *__restrict__ p, const float *__restrict__ src,
-                                                          const float *__restrict__ acc, const float *__restrict__ g,
-                                                          float *__restrict__ m, float *__restrict__ v, float lr_t,
-                                                          float b1, float b2, float eps,
-                                                          const float *__restrict__ stats) {
-  const float gscale = stats[1];
-  const size_t n4 = n / 4;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gscale != gscale) {
-    if (FROM) {
-      for (size_t i = tid; i < n4; i += stride) reinterpret_cast<float4 *>(p)[i] = reinterpret_cast<const float4 *>(src)[i];
-      for (size_t i = n4 * 4 + tid; i < n; i += stride) p[i] = src[i];
-    }
-    return;
-  }
-  for (size_t i = tid; i < n4; i += stride) {
-    float4 pp = FROM ? reinterpret_cast<const float4 *>(src)[i] : reinterpret_cast<float4 *>(p)[i];
-    float4 gg = reinterpret_cast<const float4 *>(g)[i];
-    if (ACC) {
-      const float4 aa = reinterpret_cast<const float4 *>(acc)[i];
-      gg.x = aa.x + gg.x;
-      gg.y = aa.y + gg.y;
-      gg.z = aa.z + gg.z;
-      gg.w = aa.w + gg.w;
-    }
-    float4 mm = reinterpret_cast<float4 *>(m)[i];
-    float4 vv = reinterpret_cast<float4 *>(v)[i];
-    NABU_ADAM_SCALED1(x) NABU_ADAM_SCALED1(y) NABU_ADAM_SCALED1(z) NABU_ADAM_SCALED1(w)
-    reinterpret_cast<float4 *>(p)[i] = pp;
-    reinterpret_cast<float4 *>(m)[i] = mm;
-    reinterpret_cast<float4 *>(v)[i] = vv;
-  }
-  for (size_t i = n4 * 4 + tid; i < n; i += stride) {
-    float x = (ACC ? acc[i] + g[i] : g[i]) * gscale;
-    float mm = b1 * m[i] + (1.f - b1) * x;
-    float vv = b2 * v[i] + (1.f - b2) * x * x;
-    m[i] = mm;
-    v[i] = vv;
-    float pp = FROM ? src[i] : p[i];
-    pp -= lr_t * mm / (sqrtf(vv) + eps);
-    p[i] = pp;
-  }
 }
 
 // ---------------------------------------------------------------------------
@@ -607,59 +558,51 @@ static int grid_for(size_t work_items) {
 
 using namespace nabu;
 
+// true when [a, a + n) and [b, b + n) are the same range or share no element
+static bool same_or_disjoint(const float *a, const float *b, size_t n) { return a == b || a + n <= b || b + n <= a; }
+
+// The launch behind the four Adam entry points.  src, acc and stats may be NULL and choose FROM, ACC and NORM; an entry
+// point that demands one of them says in `demanded` whether it got it, and reports under its own name `who`.
+static int adam_launch(const char *who, bool demanded, size_t n, float *param_out, const float *src, const float *acc,
+                       const float *g, float *m, float *v, AdamHyper h, float clip, float gscale, const float *stats,
+                       nabu_stream_t stream) {
+  if (n == 0) return 0;
+  NABU_CHECK_ARG(demanded && param_out && g && m && v, "%s: null pointer", who);
+  NABU_CHECK_ARG(((uintptr_t)param_out | (uintptr_t)src | (uintptr_t)acc | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v |
+                  (uintptr_t)stats) % 16 == 0, "%s: buffers must be 16-byte aligned", who);
+  NABU_CHECK_ARG(!src || src + n <= param_out || param_out + n <= src,
+                 "%s: src and param_out overlap (the in-place update passes no src)", who);
+  NABU_CHECK_ARG(!acc || acc + n <= g || g + n <= acc, "%s: acc and g overlap", who);
+  static const decltype(&adam_kernel<false, false, false>) kernels[2][2][2] = {
+      {{adam_kernel<false, false, false>, adam_kernel<false, false, true>},
+       {adam_kernel<false, true, false>, adam_kernel<false, true, true>}},
+      {{adam_kernel<true, false, false>, adam_kernel<true, false, true>},
+       {adam_kernel<true, true, false>, adam_kernel<true, true, true>}}};
+  hipLaunchKernelGGL(kernels[src != nullptr][acc != nullptr][stats != nullptr], dim3(grid_for(n / 4 + 1)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), n, param_out, src, acc, g, m, v, h, clip, gscale, stats);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int nabu_adam_clip_step(size_t n, float *param, const float *grad, float *m, float *v,
                                    float lr_t, float b1, float b2, float eps, float clip,
                                    float grad_scale, nabu_stream_t stream) {
-  if (n == 0) return 0;
-  NABU_CHECK_ARG(param && grad && m && v, "adam: null pointer");
-  NABU_CHECK_ARG(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)m | (uintptr_t)v) % 16 == 0,
-                 "adam: buffers must be 16-byte aligned");
-  hipLaunchKernelGGL(adam_clip_kernel<false>, dim3(grid_for(n / 4 + 1)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), n, param, (const float *)nullptr, grad, m, v, lr_t, b1, b2, eps,
-                     clip, grad_scale);
-  NABU_LAUNCH_CHECK();
-  return 0;
+  return adam_launch("adam", true, n, param, nullptr, nullptr, grad, m, v, {lr_t, b1, b2, eps}, clip, grad_scale, nullptr,
+                     stream);
 }
 
 extern "C" int nabu_adam_clip_step_from(size_t n, float *param_out, const float *src, const float *grad, float *m,
                                         float *v, float lr_t, float b1, float b2, float eps, float clip,
                                         float grad_scale, nabu_stream_t stream) {
-  if (n == 0) return 0;
-  NABU_CHECK_ARG(param_out && src && grad && m && v, "adam_from: null pointer");
-  NABU_CHECK_ARG(((uintptr_t)param_out | (uintptr_t)src | (uintptr_t)grad | (uintptr_t)m | (uintptr_t)v) % 16 == 0,
-                 "adam_from: buffers must be 16-byte aligned");
-  NABU_CHECK_ARG(src + n <= param_out || param_out + n <= src,
-                 "adam_from: src and param_out overlap (the in-place update is nabu_adam_clip_step)");
-  hipLaunchKernelGGL(adam_clip_kernel<true>, dim3(grid_for(n / 4 + 1)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), n, param_out, src, grad, m, v, lr_t, b1, b2, eps, clip,
-                     grad_scale);
-  NABU_LAUNCH_CHECK();
-  return 0;
+  return adam_launch("adam_from", src, n, param_out, src, nullptr, grad, m, v, {lr_t, b1, b2, eps}, clip, grad_scale,
+                     nullptr, stream);
 }
-
-// true when [a, a + n) and [b, b + n) are the same range or share no element
-static bool same_or_disjoint(const float *a, const float *b, size_t n) { return a == b || a + n <= b || b + n <= a; }
 
 extern "C" int nabu_adam_clip_step_acc(size_t n, float *param_out, const float *src, const float *acc, const float *g,
                                        float *m, float *v, float lr_t, float b1, float b2, float eps, float clip,
                                        float grad_scale, nabu_stream_t stream) {
-  if (n == 0) return 0;
-  NABU_CHECK_ARG(param_out && acc && g && m && v, "adam_acc: null pointer");
-  NABU_CHECK_ARG(((uintptr_t)param_out | (uintptr_t)src | (uintptr_t)acc | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0,
-                 "adam_acc: buffers must be 16-byte aligned");
-  NABU_CHECK_ARG(!src || src + n <= param_out || param_out + n <= src,
-                 "adam_acc: src and param_out overlap (src = NULL is the in-place update)");
-  NABU_CHECK_ARG(acc + n <= g || g + n <= acc, "adam_acc: acc and g overlap");
-  if (src)
-    hipLaunchKernelGGL((adam_clip_kernel<true, float>), dim3(grid_for(n / 4 + 1)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), n, param_out, src, g, m, v, lr_t, b1, b2, eps, clip, grad_scale,
-                       acc);
-  else
-    hipLaunchKernelGGL((adam_clip_kernel<false, float>), dim3(grid_for(n / 4 + 1)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), n, param_out, (const float *)nullptr, g, m, v, lr_t, b1, b2, eps,
-                       clip, grad_scale, acc);
-  NABU_LAUNCH_CHECK();
-  return 0;
+  return adam_launch("adam_acc", acc, n, param_out, src, acc, g, m, v, {lr_t, b1, b2, eps}, clip, grad_scale, nullptr,
+                     stream);
 }
 
 extern "C" size_t nabu_grad_norm_ws_bytes(size_t n) { return n ? (size_t)grid_for(n / 4 + 1) * sizeof(double) : 0; }
@@ -693,24 +636,7 @@ extern "C" int nabu_grad_norm_f32(size_t n, const float *g, const float *acc, fl
 extern "C" int nabu_adam_scaled_step(size_t n, float *param_out, const float *src, const float *acc, const float *g,
                                      float *m, float *v, float lr_t, float b1, float b2, float eps, const float *stats,
                                      nabu_stream_t stream) {
-  if (n == 0) return 0;
-  NABU_CHECK_ARG(param_out && g && m && v && stats, "adam_scaled: null pointer (only src and acc may be NULL)");
-  NABU_CHECK_ARG(((uintptr_t)param_out | (uintptr_t)src | (uintptr_t)acc | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v |
-                  (uintptr_t)stats) % 16 == 0, "adam_scaled: buffers must be 16-byte aligned");
-  NABU_CHECK_ARG(!src || src + n <= param_out || param_out + n <= src,
-                 "adam_scaled: src and param_out overlap (src = NULL is the in-place update)");
-  NABU_CHECK_ARG(!acc || acc + n <= g || g + n <= acc, "adam_scaled: acc and g overlap");
-  const dim3 grid(grid_for(n / 4 + 1)), block(256);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-#define NABU_ADAM_SCALED(FROM, ACC) \
-  hipLaunchKernelGGL((adam_scaled_kernel<FROM, ACC>), grid, block, 0, s, n, param_out, src, acc, g, m, v, lr_t, b1, b2, eps, stats)
-  if (src && acc) NABU_ADAM_SCALED(true, true);
-  else if (src) NABU_ADAM_SCALED(true, false);
-  else if (acc) NABU_ADAM_SCALED(false, true);
-  else NABU_ADAM_SCALED(false, false);
-#undef NABU_ADAM_SCALED
-  NABU_LAUNCH_CHECK();
-  return 0;
+  return adam_launch("adam_scaled", stats, n, param_out, src, acc, g, m, v, {lr_t, b1, b2, eps}, 0.f, 0.f, stats, stream);
 }
 
 extern "C" int nabu_weight_noise_f32(size_t n, float *param, float *clean, const int32_t *ranges,
@@ -743,8 +669,8 @@ extern "C" int nabu_weight_noise_f32(size_t n, float *param, float *clean, const
 extern "C" int nabu_clip_f32(size_t n, float *g, float clip, nabu_stream_t stream) {
   if (n == 0) return 0;
   NABU_CHECK_ARG(g && (uintptr_t)g % 16 == 0, "clip: null or unaligned pointer");
-  hipLaunchKernelGGL(clip_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), n, g, clip);
+  hipLaunchKernelGGL(clip_accumulate_kernel<false>, dim3(grid_for(n / 4 + 1)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), n, g, (const float *)nullptr, g, clip);
   NABU_LAUNCH_CHECK();
   return 0;
 }

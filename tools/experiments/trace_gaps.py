@@ -1,10 +1,10 @@
-"""Idle time between the kernels of a training step from a rocprofv3 --kernel-trace CSV (steps delimited by adam_clip_kernel).
+"""Idle time between the kernels of a training step from a rocprofv3 --kernel-trace CSV (steps delimited by adam_kernel).
 usage: rocprofv3 --kernel-trace --output-format csv -d /tmp/tr -o t -- python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-alt --no-gemm-roofline; python tools/experiments/trace_gaps.py /tmp/tr/*/*kernel_trace.csv"""
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
-# find step boundaries: adam_clip_kernel ends a step
-ends = [i for i, r in enumerate(rows) if 'adam_clip' in r['Kernel_Name']]
+# find step boundaries: adam_kernel (adam_clip_kernel in older traces) ends a step
+ends = [i for i, r in enumerate(rows) if 'adam_kernel' in r['Kernel_Name'] or 'adam_clip' in r['Kernel_Name']]
 print('kernels', len(rows), 'adam launches', len(ends))
 for a, b in zip(ends[:-1], ends[1:]):
     seg = rows[a + 1:b + 1]

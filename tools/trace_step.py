@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Timeline of ONE training step out of a rocprofv3 --kernel-trace CSV (the last complete step between two
-adam_clip_kernel launches): start (us), duration, gap to the previous kernel, name; then totals per kernel name.
+adam_kernel launches): start (us), duration, gap to the previous kernel, name; then totals per kernel name.
 
     python tools/trace_step.py gpurun_out/<tag>_kernel_trace.csv [--summary]
 """
@@ -18,7 +18,7 @@ def short(n):
 def main():
     rows = list(csv.DictReader(open(sys.argv[1])))
     rows.sort(key=lambda r: int(r['Start_Timestamp']))
-    idx = [i for i, r in enumerate(rows) if 'adam_clip' in r['Kernel_Name']]
+    idx = [i for i, r in enumerate(rows) if 'adam_kernel' in r['Kernel_Name'] or 'adam_clip' in r['Kernel_Name']]   # (adam_clip: traces from before the one kernel)
     step = rows[idx[-2] + 1:idx[-1] + 1]
     t0 = int(step[0]['Start_Timestamp'])
     prev = None
