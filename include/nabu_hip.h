@@ -1023,6 +1023,45 @@ int nabu_ctc_beam_search_lm(int B, int T, int C, int beam_width, int merge_repea
 int nabu_edit_distance(int B, const int32_t *hyp, int ldh, const int32_t *hyp_len, const int32_t *truth,
                        int ldt, const int32_t *truth_len, int32_t *dist, nabu_stream_t stream);
 
+/* Minimum word error rate training of the Speller (Prabhavalkar et al. 2018; mwer.hip, trainers/mwer.py): the expected
+ * number of label errors over the N-best list of the attention beam search, plus ce_weight times the reference's
+ * cross-entropy.  Rows are stacked slot-major: row n*B + b is hypothesis n of utterance b for n < N, and slot N is the
+ * reference, so every slot is a block of B rows and the encoder output is tiled by repetition.
+ *
+ * nabu_mwer_prepare: beam output -> teacher-forcing targets.
+ *   sequences [B,N,lds >= S] int32, lengths [B,N] (labels before the end label C-1, clamped to 0..S), scores [B,N]:
+ *   what nabu_speller_beam_search returns; targets [B,ldr] with target_len [B], which counts the end label.
+ *   stk_targets [(N+1)*B, ldt > S] (every word written): the hypothesis followed by C-1, then zeros; slot N: the first
+ *     min(target_len, ldr, ldt) reference labels.  stk_len [(N+1)*B]: length + 1, the reference's clamped target_len.
+ *   hyp_len [N*B]: the lengths without the end label.  valid [N*B]: 1 when the score is a real one (> -1e30; the search
+ *     fills spare slots with -FLT_MAX) and no lower slot of the utterance with a real score holds the same labels
+ *     [:length] (an unfinished "a b" and a finished "a b <end>" are one target).  An invalid row is the target [C-1] of
+ *     length 1 with hyp_len 0.  NABU_EUNSUP: N > 16.
+ * nabu_rows_tile_f32: y[r*B + b, :] = x[b, :] for r < R (x [B,F], y [R*B,F]).  nabu_rows_tile_bwd_f32: dx[b, :] =
+ *   sum_r dy[r*B + b, :] in the order r = 0..R-1.  float4 accesses where an address allows, single words elsewhere: any
+ *   4-byte aligned operands and any F.
+ * nabu_mwer_loss_grad: logits [(N+1)*B, L, C] of the stacked targets (ldt >= L), errors [N*B] (edit distance of each
+ *   hypothesis to the reference without its end label: nabu_edit_distance), valid [N*B].
+ *     nll_n   = sum_{t < stk_len} (logsumexp(x[n,t,:]) - x[n,t,y_n[t]])
+ *     p_n     = softmax over the valid n of -nll_n (maximum subtracted)
+ *     risk[b] = sum_n p_n e_n,   nll_ref[b] = nll_N,   loss[b] = risk + ce_weight * nll_ref
+ *     dlogits[n,t,:]   = -grad_scale * (p_n * sum_m p_m (e_n - e_m)) * (softmax(x[n,t,:]) - onehot(y_n[t]))
+ *     dlogits[ref,t,:] =  grad_scale * ce_weight * (softmax - onehot)
+ *   dlogits is exactly 0 past stk_len, on the rows of an invalid hypothesis, on all hypothesis rows when the valid
+ *   error counts are equal, and on the reference rows when ce_weight == 0.  One launch, one workgroup per utterance,
+ *   fixed-order sums: two calls give the same bits.  logits and dlogits must not overlap.
+ *   NABU_EUNSUP (before any launch): N > 16, C < 2 or C > 1023.  NABU_EINVAL: a null pointer, B, N, L or C <= 0,
+ *   ldt < L, ce_weight negative or not finite, grad_scale not finite. */
+int nabu_mwer_prepare(int B, int N, int S, int lds, int C, const int32_t *sequences, const int32_t *lengths,
+                      const float *scores, int ldr, const int32_t *targets, const int32_t *target_len, int ldt,
+                      int32_t *stk_targets, int32_t *stk_len, int32_t *hyp_len, int32_t *valid, nabu_stream_t stream);
+int nabu_rows_tile_f32(int R, int B, int F, const float *x, float *y, nabu_stream_t stream);
+int nabu_rows_tile_bwd_f32(int R, int B, int F, const float *dy, float *dx, nabu_stream_t stream);
+int nabu_mwer_loss_grad(int B, int N, int L, int C, int ldt, const float *logits, const int32_t *stk_targets,
+                        const int32_t *stk_len, const int32_t *errors, const int32_t *valid, float ce_weight,
+                        float grad_scale, float *loss, float *risk, float *nll_ref, float *dlogits,
+                        nabu_stream_t stream);
+
 /* Attention beam search — BeamSearchDecoder.__call__ (decoders/beam_search_decoder.py:31-114)
  * over components/beam_search_decoder.py:141-451 driven by dynamic_decode(maximum_iterations =
  * max_steps): the encoder output is tiled beam_width times, every step runs the Speller cell

@@ -189,6 +189,10 @@ SIGNATURES = {
     'nabu_ctc_beam_ws_bytes': (_sz, [_i, _i, _i, _i]),
     'nabu_ctc_beam_search': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nabu_edit_distance': (_i, [_i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    'nabu_mwer_prepare': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    'nabu_rows_tile_f32': (_i, [_i, _i, _i, _vp, _vp, _vp]),
+    'nabu_rows_tile_bwd_f32': (_i, [_i, _i, _i, _vp, _vp, _vp]),
+    'nabu_mwer_loss_grad': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     'nabu_speller_beam_ws_bytes': (_sz, [_vp]),
     'nabu_speller_beam_search': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nabu_beam_prune': (_i, [_i, _i, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -153,6 +153,18 @@ def spec_augment(x, lengths, policy, rng_state):
     return y
 
 
+def tile_rows(x, R):
+    """x [B, ...] repeated R times along the batch, replica-major: y[r * B + b] = x[b] (one encoder pass under several
+    decoder rows: trainers/mwer.py).  The gradient is the sum over the replicas in the order r = 0..R-1.  Lengths are
+    tiled on the host by the caller."""
+    y = hip.rows_tile(x, R)
+    if value_bound(x):
+        set_value_bound(y, value_bound(x))
+    if requires_grad(x):
+        record([x], [y], lambda dy: [hip.rows_tile_bwd(dy, R)])
+    return y
+
+
 class RngState(object):
     """Seed + running offset for the counter-based device RNG."""
 

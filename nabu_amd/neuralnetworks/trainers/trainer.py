@@ -31,6 +31,9 @@ underneath:
     clipping after the aggregation: the mean of the update's A * replicas unclipped gradients times min(1, c / norm),
     the norm reduced on the device (nabu_grad_norm_f32) and the factor read there by the Adam launch
     (nabu_adam_scaled_step); an update whose norm is NaN or inf is skipped on the device (DESIGN.md section 6.2);
+  * ``mwer_nbest = N`` (an extension key with ``mwer_max_steps``, ``mwer_ce_weight``, ``mwer_start_step``; off when absent
+    or 0) replaces the forward pass and the loss of a step by minimum word error rate training over the N-best list of
+    the model's own beam search (trainers/mwer.py, DESIGN.md section 12); everything behind the loss is the same;
   * ``train()`` is ONE loop around ``step`` / ``step_accumulated`` (one body, ``_run_update``, and one ``_update`` for
     every A and every exchange).  Two small objects say where a device batch comes from (DirectFeed | AheadFeed) and
     when a step's words are read (readback.ReadNow | ReadLate); ``prefetch_batches`` >= 1 (an extension key,
@@ -48,7 +51,7 @@ import torch
 from nabu_amd import ops as hip
 from nabu_amd.autodiff import Tape, SeqLen
 from nabu_amd.neuralnetworks.models.model import Model
-from nabu_amd.neuralnetworks.trainers import loss_functions, readback
+from nabu_amd.neuralnetworks.trainers import loss_functions, mwer, readback
 from nabu_amd.tools.default_conf import apply_defaults, defaults_path
 
 ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-8      # tf.train.AdamOptimizer defaults
@@ -242,6 +245,19 @@ class Trainer(object, metaclass=ABCMeta):
         # weight_noise / weight_noise_start_step (extension keys as well): validated here for the same reason
         self.weight_noise, self.weight_noise_start_step = weight_noise_keys(self.conf)
         self.flat_clean = self.noise_table = None
+        # mwer_nbest / mwer_max_steps / mwer_ce_weight / mwer_start_step (extension keys as well, validated here too):
+        # from global step mwer_start_step on, the step's loss is the expected number of label errors over the N-best
+        # list of the model's own beam search (trainers/mwer.py); None without mwer_nbest
+        self.mwer = mwer.mwer_keys(self.conf)
+        self._mwer_stats = None            # device tensors of the latest MWER step (mwer_stats)
+        if self.mwer is not None:
+            if self.conf['loss'] == 'CTC':
+                raise ValueError('mwer_nbest fine-tunes a model trained on a cross-entropy loss through its recurrent '
+                                 'decoder; loss = CTC has no such decoder')
+            if self.label_smoothing:
+                raise ValueError('mwer_nbest does not combine with label_smoothing yet')
+            if self.ctc_weight:
+                raise ValueError('mwer_nbest does not combine with ctc_weight yet')
         # numbatches_to_aggregate: A batches per replica and update (1: the plain step), validated here as well
         self.accumulate = aggregate_key(self.conf, self.world)
         self.flat_acc = None               # the sum of an update's clipped micro-batch gradients (allocated when A > 1)
@@ -259,6 +275,8 @@ class Trainer(object, metaclass=ABCMeta):
         if self.ctc_weight and not self.model.decoder.ctc_head:
             raise ValueError('ctc_weight = %g needs a model with a CTC head: set ctc_head = True in the [decoder] '
                              'section of the model' % self.ctc_weight)
+        if self.mwer is not None:
+            mwer.check_model(self.model)
         if bool(getattr(server, 'shared_devices', False)):
             # ranks that share a GPU (more ranks than devices on this node: first-contact runs, tests): the persistent
             # recurrent kernels need every CU of the device for their own workgroups, two processes' launches would each
@@ -400,7 +418,16 @@ class Trainer(object, metaclass=ABCMeta):
         return self._run_update(batches)
 
     def _forward_loss(self, batch):
-        '''the forward pass and the loss of one device batch -> (tape, loss)'''
+        '''the forward pass and the loss of one device batch -> (tape, loss).  With mwer_nbest, from global step
+        mwer_start_step on, the pass is trainers/mwer.py's; before it, and without the key, the calls below are the ones
+        they always were'''
+        if self.mwer is not None and self.global_step >= self.mwer[3]:
+            with Tape() as tape:
+                loss, self._mwer_stats = mwer.forward_loss(self.model, batch, *self.mwer[:3])
+                extra = self.aditional_loss()
+                if extra is not None:
+                    loss = hip.axpy_(loss, extra)
+            return tape, loss
         with Tape() as tape:
             logits, logit_seq_length = self.model(
                 inputs=batch['inputs'], input_seq_length=batch['input_seq_length'],
@@ -646,6 +673,13 @@ class Trainer(object, metaclass=ABCMeta):
         if self.clip_stats is None:
             raise Exception('grad_stats needs clip_gradient_norm > 0 and a first update')
         return hip.read_grad_stats(self.clip_stats)
+
+    def mwer_stats(self):
+        '''(mean expected errors, mean reference nll, share of valid hypotheses) of the latest MWER step.  Copies three
+        words to the host, so it synchronises; train() does not call it per step.'''
+        if self._mwer_stats is None:
+            raise Exception('mwer_stats needs mwer_nbest > 0 and a first MWER step (global step >= mwer_start_step)')
+        return mwer.read_stats(self._mwer_stats)
 
     def _report_skipped(self):
         '''called where train() has synchronised anyway (a validation point, the end): says so when updates were skipped

@@ -1024,6 +1024,78 @@ def edit_distance(hyp, hyp_len, truth, truth_len):
     return dist
 
 
+MWER_MAX_NBEST = 16
+
+
+def mwer_prepare(sequences, lengths, scores, targets, target_len, C, ldt=None):
+    """beams of the attention beam search -> stacked teacher-forcing targets (nabu_mwer_prepare), slot-major: row
+    n * B + b is hypothesis n of utterance b, slot N the reference.  sequences [B,N,S] int32 (a view with a longer row
+    stride is taken as it is), lengths [B,N], scores [B,N], targets [B,ldr] int32, target_len [B] (counts the end label).
+    Returns (stk_targets [(N+1)*B, ldt], stk_len [(N+1)*B], hyp_len [N*B], valid [N*B]); ldt defaults to
+    max(S + 1, ldr)."""
+    B, N, S = sequences.shape
+    if not sequences.is_cuda or sequences.dtype != torch.int32:
+        raise _hip.NabuHipError('sequences must be an int32 tensor on the GPU, got %s on %s'
+                                % (sequences.dtype, sequences.device))
+    if S and sequences.stride(2) == 1 and sequences.stride(0) == N * sequences.stride(1) and sequences.stride(1) >= S:
+        lds = sequences.stride(1)               # the beam search's [B,N,max_steps] buffer cut to the steps it took
+    else:
+        sequences, lds = sequences.contiguous(), S
+    seq_ptr = sequences.data_ptr() if S else None
+    targets = targets.contiguous()
+    ldr = targets.shape[1]
+    ldt = max(S + 1, ldr) if ldt is None else int(ldt)
+    dev = sequences.device
+    stk_targets = torch.empty(((N + 1) * B, ldt), dtype=torch.int32, device=dev)
+    stk_len = torch.empty((N + 1) * B, dtype=torch.int32, device=dev)
+    hyp_len = torch.empty(N * B, dtype=torch.int32, device=dev)
+    valid = torch.empty(N * B, dtype=torch.int32, device=dev)
+    check(_hip.lib().nabu_mwer_prepare(B, N, S, lds, int(C), seq_ptr, ptr(lengths.contiguous()),
+                                       ptr(_f32(scores, 'scores').contiguous()), ldr, ptr(targets), ptr(target_len), ldt,
+                                       ptr(stk_targets), ptr(stk_len), ptr(hyp_len), ptr(valid), stream()),
+          'nabu_mwer_prepare')
+    return stk_targets, stk_len, hyp_len, valid
+
+
+def rows_tile(x, R):
+    """y[r * B + b] = x[b] for r < R: x [B, ...] -> [R * B, ...] (nabu_rows_tile_f32)"""
+    x = _f32(x, 'x').contiguous()
+    B = x.shape[0]
+    y = torch.empty((R * B,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    check(_hip.lib().nabu_rows_tile_f32(int(R), B, x.numel() // B, ptr(x), ptr(y), stream()), 'nabu_rows_tile_f32')
+    return y
+
+
+def rows_tile_bwd(dy, R):
+    """dx[b] = sum_r dy[r * B + b] in the order r = 0..R-1: dy [R * B, ...] -> [B, ...] (nabu_rows_tile_bwd_f32)"""
+    dy = _f32(dy, 'dy').contiguous()
+    B = dy.shape[0] // R
+    if B * R != dy.shape[0]:
+        raise ValueError('rows_tile_bwd: %d rows are no multiple of R = %d' % (dy.shape[0], R))
+    dx = torch.empty((B,) + tuple(dy.shape[1:]), dtype=torch.float32, device=dy.device)
+    check(_hip.lib().nabu_rows_tile_bwd_f32(int(R), B, dx.numel() // B, ptr(dy), ptr(dx), stream()),
+          'nabu_rows_tile_bwd_f32')
+    return dx
+
+
+def mwer_loss_grad(logits, stk_targets, stk_len, errors, valid, ce_weight, grad_scale):
+    """the MWER objective and its gradient in one launch (nabu_mwer_loss_grad): logits [(N+1)*B, L, C] of the stacked
+    targets of mwer_prepare, errors / valid [N*B] int32.  Returns (loss [B], risk [B], nll_ref [B], dlogits)."""
+    rows, L, C = logits.shape
+    NB = valid.numel()
+    B = rows - NB
+    if B <= 0 or NB % B:
+        raise ValueError('mwer_loss_grad: %d logit rows and %d hypotheses do not stack' % (rows, NB))
+    dev = logits.device
+    loss, risk, nll_ref = (torch.empty(B, dtype=torch.float32, device=dev) for _ in range(3))
+    dlogits = torch.empty_like(logits)
+    check(_hip.lib().nabu_mwer_loss_grad(B, NB // B, L, C, stk_targets.shape[1], ptr(_f32(logits, 'logits')),
+                                         ptr(stk_targets), ptr(stk_len), ptr(errors), ptr(valid), float(ce_weight),
+                                         float(grad_scale), ptr(loss), ptr(risk), ptr(nll_ref), ptr(dlogits), stream()),
+          'nabu_mwer_loss_grad')
+    return loss, risk, nll_ref, dlogits
+
+
 def beam_prune(logits, logprobs, lengths, finished, seen, temperature=1.0, length_penalty=0.0):
     """one expand+prune step of the attention beam search; logits [B,W,C]; the [B,W] state tensors
     are updated in place.  Returns (pred_ids, parent, stay, all_seen)"""
