@@ -459,6 +459,60 @@ int nabu_ctc_align(int B, int T, int C, int Lmax, const float *logits,
                    float *score, int32_t *status, void *ws, size_t ws_bytes,
                    nabu_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * RNN transducer (Graves 2012, "Sequence Transduction with Recurrent Neural Networks") with the additive joint
+ * (transducer.hip).  f [B,T,C] are the transcription logits, g [B,U1,C] the prediction logits (row u: the history
+ * start symbol + labels[0..u)), blank = C-1, enc_len [B] the frames T_b (1..T), labels [B,ldl] (ldl >= U1-1; may be
+ * null when U1 = 1), label_len [B] the labels U_b (0..U1-1).
+ *
+ * Definition.  h[t,u,k] = f[t,k] + g[u,k] (one float32 addition); log p(k|t,u) = (h[t,u,k] - mx[t,u]) - lz[t,u] with
+ * mx the node's own maximum over k and lz = log sum_k exp(h - mx), kept apart as in the CTC loss; lb = log p(blank),
+ * ly = log p(labels[u]).  h [B,T,U1,C] is never materialised.
+ *   alpha[0,0] = 0,  alpha[t,u] = logadd(alpha[t-1,u] + lb[t-1,u], alpha[t,u-1] + ly[t,u-1])
+ *   beta[T_b-1,U_b] = lb[T_b-1,U_b],  beta[t,u] = logadd(beta[t+1,u] + lb[t,u], beta[t,u+1] + ly[t,u])
+ * Unreachable is the finite -1e30 of nabu_ctc_loss_grad.
+ *   nll [B]        -beta[0,0] = -log sum over the monotone paths from (0,0) through the final blank at (T_b-1, U_b)
+ *   df [B,T,C]     grad_scale * sum_u G[t,u,k]        dg [B,U1,C]   grad_scale * sum_t G[t,u,k]
+ *   G[t,u,k] = exp(alpha[t,u] + beta[t,u] + nll) p(k|t,u) - [k = blank] exp(alpha[t,u] + lb[t,u] + beta[t+1,u] + nll)
+ *                                                       - [k = labels[u]] exp(alpha[t,u] + ly[t,u] + beta[t,u+1] + nll)
+ * with beta[T_b,U_b] read as 0 and every other beta outside the lattice as unreachable.  Rows of df from T_b on and
+ * rows of dg past U_b are written as zeros: the caller need not clear anything.  Every sum runs in a fixed order
+ * without floating-point atomics: identical calls give identical bits.
+ * An utterance with a label < 0 or >= C-1, enc_len <= 0 or > T, or label_len < 0 or > U1-1 gets nll = 0 and zero
+ * rows in df and dg, and sets status [1] (device) to 1+b through atomicCAS(status, 0, b+1), repeated while a later
+ * utterance holds the word: status names the FIRST such utterance; the others are unaffected.  Any T_b >= 1 admits
+ * every U_b: there is no "not enough frames" case.
+ * Launches: emission terms (mx, lz, lb, ly of every node), the alpha and beta sweeps side by side, the gradients.
+ * Routes of the sweeps: U1 <= 64: one wave64 per sweep and utterance walking anti-diagonals, lane u on node (d-u, u),
+ * no barrier in the loop; otherwise 256 threads with u strided over them and a barrier per diagonal.  Both evaluate
+ * the same per-node expression: same bits.  NABU_TRANSDUCER_WORKGROUP=1 (read once per process) forces the second.
+ * NABU_TRANSDUCER_LAUNCHES (read on every call; for measurements only) is a mask of the launches to make: 1 emission
+ * terms, 2 sweeps, 4 gradients; anything but 7 needs a workspace that a complete call on the same operands has filled.
+ * NABU_EINVAL: a null pointer (labels may be null for U1 = 1), B, T or U1 <= 0, C <= 1, ldl < U1-1, B > 65535, or
+ * T*U1 or B*(T+U1) >= 2^31.  NABU_EWS: ws_bytes < nabu_transducer_ws_bytes(B,T,U1) (0 for B, T or U1 <= 0).
+ * NABU_EUNSUP: the second route with more than 150 KiB of LDS (8 U1 bytes).  All three return before any launch. */
+size_t nabu_transducer_ws_bytes(int B, int T, int U1);
+int nabu_transducer_loss_grad(int B, int T, int U1, int C, const float *f, const float *g,
+                              const int32_t *enc_len, const int32_t *labels, int ldl,
+                              const int32_t *label_len, float grad_scale, float *nll, float *df,
+                              float *dg, int32_t *status, void *ws, size_t ws_bytes,
+                              nabu_stream_t stream);
+/* One step of the greedy transducer search for B rows in lock-step: one launch, one wave per row.  g_row [B,C] are
+ * the prediction logits of each row's current history; t_pos, out_len [B], ids [B,S], last_id [B] and score [B] are
+ * the search state, S the cap on labels per row.  step = 0 starts a search: the kernel itself sets t_pos = 0,
+ * out_len = 0, score = 0, last_id = C-1 and ids = -1 before it decides, so the state needs no clearing; step > 0
+ * continues from the state as found.
+ * A row with t_pos >= enc_len or out_len >= S is finished: emit = 0 and nothing else is written.  Otherwise
+ * k = argmax_k (f[b,t_pos,k] + g_row[b,k]) (one float32 addition; the smallest index among equal maxima),
+ * score += (x_k - max) - log sum exp(x - max); k = blank: t_pos += 1, emit = 0; else ids[b,out_len++] = k,
+ * last_id = k, emit = 1.  emit [B] can be passed as the seq_len of nabu_lstm_cell_fwd with step = 0: rows that
+ * emitted advance the prediction network, the others copy their state through.
+ * NABU_EINVAL before the launch: a null pointer, B, T or S <= 0, C <= 1, step < 0. */
+int nabu_transducer_greedy_step(int B, int T, int C, int S, int step, const float *f,
+                                const float *g_row, const int32_t *enc_len, int32_t *t_pos,
+                                int32_t *out_len, int32_t *ids, int32_t *emit, int32_t *last_id,
+                                float *score, nabu_stream_t stream);
+
 /* Masked sparse softmax cross-entropy averaged over the target length —
  * loss_functions.average_cross_entropy / cross_entropy
  * (nabu/neuralnetworks/trainers/loss_functions.py:78-109,155-165):

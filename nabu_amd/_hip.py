@@ -142,6 +142,9 @@ SIGNATURES = {
     'nabu_ctc_loss_grad': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nabu_ctc_align_ws_bytes': (_sz, [_i, _i, _i]),
     'nabu_ctc_align': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'nabu_transducer_ws_bytes': (_sz, [_i, _i, _i]),
+    'nabu_transducer_loss_grad': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'nabu_transducer_greedy_step': (_i, [_i, _i, _i, _i, _i] + [_vp] * 9 + [_vp]),
     'nabu_xent_loss_grad': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     'nabu_xent_smooth_loss_grad': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp]),
     'nabu_lstm_cell_fwd': (_i, [_i, _i, _i] + [_vp] * 10 + [_vp]),

@@ -7,5 +7,6 @@ factory = Registry('decoder', {
     'alignment_decoder': 'nabu_amd.neuralnetworks.decoders.alignment_decoder:AlignmentDecoder',
     'random_decoder': 'nabu_amd.neuralnetworks.decoders.random_decoder:RandomDecoder',
     'ctc_alignment_decoder': 'nabu_amd.neuralnetworks.decoders.ctc_alignment_decoder:CTCAlignmentDecoder',
+    'transducer_decoder': 'nabu_amd.neuralnetworks.decoders.transducer_decoder:TransducerDecoder',
 }, outside=('max_decoder', 'threshold_decoder', 'feature_decoder'),
     undefined='Undefined %s type: %s')

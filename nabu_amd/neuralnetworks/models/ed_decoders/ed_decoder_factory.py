@@ -5,4 +5,5 @@ _PKG = 'nabu_amd.neuralnetworks.models.ed_decoders.'
 factory = Registry('decoder', {
     'speller': _PKG + 'speller:Speller',
     'dnn_decoder': _PKG + 'dnn_decoder:DNNDecoder',
+    'transducer': _PKG + 'transducer:Transducer',
 }, outside=('hotstart_decoder',))

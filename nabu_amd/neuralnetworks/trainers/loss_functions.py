@@ -11,7 +11,7 @@ from nabu_amd import ops as hip
 from nabu_amd.autodiff import record, SeqLen, UNIT
 from nabu_amd.neuralnetworks.components import ops
 
-# device status words of the CTC kernels launched since the last check
+# device status words of the CTC and transducer kernels launched since the last check
 pending_status = []
 
 # class counts from which the cross-entropy losses run nabu_xent_wide_loss_grad (one wave per frame) instead of
@@ -87,6 +87,14 @@ def factory(loss_function, label_smoothing=0.0, ctc_weight=0.0):
         return CTC
     elif loss_function == 'sum_cross_entropy':
         return functools.partial(sum_cross_entropy, **extra) if extra else sum_cross_entropy
+    elif loss_function == 'transducer':
+        if label_smoothing:
+            raise ValueError('label_smoothing is defined for the cross-entropy losses only (average_cross_entropy, '
+                             'sum_cross_entropy), not for the transducer loss')
+        if ctc_weight:
+            raise ValueError('ctc_weight adds a CTC term to the cross-entropy losses (average_cross_entropy, '
+                             'sum_cross_entropy); a transducer model has no CTC head')
+        return transducer
     elif loss_function in ('average_sigmoid_cross_entropy', 'marigin'):
         raise Exception('loss function %s is outside the MI355X hot path' % loss_function)
     else:
@@ -97,6 +105,13 @@ def _labels(t):
     if t.dtype != torch.int32 or not t.is_contiguous():
         t = t.to(torch.int32).contiguous()
     return t
+
+
+def _single_logits(name, logits, t):
+    '''the losses over ONE logit tensor per output refuse the outputs of a transducer model'''
+    if t + '_pred' in logits:
+        raise ValueError('loss = %s on the outputs of a transducer model (decoder = transducer): its transcription logits '
+                         'alone are no model of the labels; use loss = transducer' % name)
 
 
 def _total(losses):
@@ -136,6 +151,7 @@ def CTC(targets, logits, logit_seq_length, target_seq_length):
     -log p(targets | logits), summed over the outputs; blank = last class.'''
     losses = []
     for t in targets:
+        _single_logits('CTC', logits, t)
         lg = logits[t]
         B = lg.shape[0]
         lsl, tsl = SeqLen.wrap(logit_seq_length[t], lg.device), SeqLen.wrap(target_seq_length[t], lg.device)
@@ -148,12 +164,52 @@ def CTC(targets, logits, logit_seq_length, target_seq_length):
     return _total(losses)
 
 
+def transducer(targets, logits, logit_seq_length, target_seq_length):
+    '''RNN transducer loss with the additive joint (not in the reference; nabu_transducer_loss_grad): mean over the
+    batch of -log p(targets | f, g), summed over the outputs, with f = logits[o] the transcription logits and
+    g = logits[o + '_pred'] the prediction logits of a `decoder = transducer` model; blank = last class.  One tape node
+    with two inputs.  The status word goes on pending_status: an utterance with a label outside the classes or a
+    length outside its tensor raises at the next check.'''
+    losses = []
+    for t in targets:
+        key = t + '_pred'
+        if key not in logits:
+            raise ValueError('loss = transducer needs the prediction logits of a transducer model (decoder = transducer '
+                             'in the [decoder] section): no output %r' % key)
+        f, g = logits[t], logits[key]
+        B = f.shape[0]
+        lsl, tsl = SeqLen.wrap(logit_seq_length[t], f.device), SeqLen.wrap(target_seq_length[t], f.device)
+        labels = _labels(torch.as_tensor(targets[t]).to(f.device))
+        nll, df, dg, status = hip.transducer_loss_grad(f.contiguous(), g.contiguous(), lsl.dev,
+                                                       labels if labels.numel() else None, tsl.dev, 1.0 / B)
+        status.error = transducer_status_error
+        pending_status.append(status)
+        loss = hip.sum_(nll, 1.0 / B)
+        record([f, g], [loss], lambda gr, a=df, b=dg: [a, b])
+        losses.append(loss)
+    return _total(losses)
+
+
+def check_model(loss_function, decoder):
+    '''loss and decoder belong together: loss = transducer reads the two outputs of `decoder = transducer`, and the other
+    losses read a single logit tensor, which that decoder does not give.  Raises ValueError at construction.'''
+    from nabu_amd.neuralnetworks.models.ed_decoders import transducer as transducer_model
+    is_transducer = isinstance(decoder, transducer_model.Transducer)
+    if loss_function == 'transducer' and not is_transducer:
+        raise ValueError('loss = transducer needs a transducer model (decoder = transducer in the [decoder] section), '
+                         'got %s' % type(decoder).__name__)
+    if is_transducer and loss_function != 'transducer':
+        raise ValueError('a transducer model (decoder = transducer) is trained with loss = transducer, not loss = %s: '
+                         'its transcription logits alone are no model of the labels' % loss_function)
+
+
 def average_cross_entropy(targets, logits, logit_seq_length, target_seq_length, label_smoothing=0.0, ctc_weight=0.0):
     '''cross entropy averaged over timesteps (reference loss_functions.py:155-165):
     mean_b( sum_{t<logit_len} xent / target_len ), summed over the outputs.  label_smoothing, ctc_weight: see
     factory.'''
     losses = []
     for t in targets:
+        _single_logits('average_cross_entropy', logits, t)
         lg = logits[t]
         B = lg.shape[0]
         lsl, tsl = SeqLen.wrap(logit_seq_length[t], lg.device), SeqLen.wrap(target_seq_length[t], lg.device)
@@ -174,6 +230,7 @@ def sum_cross_entropy(targets, logits, logit_seq_length, target_seq_length, labe
     factory.'''
     losses = []
     for t in targets:
+        _single_logits('sum_cross_entropy', logits, t)
         lg = logits[t]
         B = lg.shape[0]
         tsl = SeqLen.wrap(target_seq_length[t], lg.device)
@@ -194,6 +251,17 @@ def ctc_status_error(code):
                      '(utterance %d of the batch)' % (code - 1))
 
 
+def transducer_status_error(code):
+    '''the exception a non-zero status word of the transducer kernel stands for'''
+    return Exception('transducer: invalid utterance %d of the batch' % (code - 1))
+
+
+def status_error(status, code):
+    '''the exception for a non-zero `code` read from the status word `status`: the kernel that owns the word says what
+    it means (an `error` attribute on the tensor); a word without one is a CTC kernel's'''
+    return getattr(status, 'error', ctc_status_error)(code)
+
+
 def take_pending_status():
     '''the status words of the CTC kernels launched since the last check; the caller reads them (the overlapped
     training loop does, one step late: trainers/readback.py)'''
@@ -207,7 +275,7 @@ def check_status():
     for s in take_pending_status():
         code = int(s.item())
         if code:
-            raise ctc_status_error(code)
+            raise status_error(s, code)
     # a persistent recurrent kernel that gave up (bounded-spin timeout) leaves the results of the
     # step invalid and its status word set: raise here, where the training / validation loops
     # already synchronise

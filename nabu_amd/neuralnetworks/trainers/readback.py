@@ -23,7 +23,7 @@ class StepRecord(object):
     def __init__(self, pinned=False):
         self.host = torch.zeros(WORDS, dtype=torch.int32, pin_memory=pinned)
         self.event = None
-        self.step, self.n_ctc, self.workspaces = None, 0, []
+        self.step, self.n_ctc, self.workspaces, self.errors = None, 0, [], []
 
     def fill(self, step, loss, ctc_status, workspaces):
         '''enqueue the copies of this step's words behind the step (device tensors: asynchronous, closed by an event)'''
@@ -31,6 +31,7 @@ class StepRecord(object):
         if need > self.host.numel():       # an accumulated update brings the CTC words of all its micro-batches
             self.host = torch.zeros((need + WORDS - 1) // WORDS * WORDS, dtype=torch.int32, pin_memory=self.host.is_pinned())
         self.step, self.n_ctc, self.workspaces = step, len(ctc_status), list(workspaces)
+        self.errors = [getattr(s, 'error', loss_functions.ctc_status_error) for s in ctc_status]    # what each word means
         self.host[0:1].view(torch.float32).copy_(loss.detach().reshape(1).to(torch.float32), non_blocking=True)
         for i, s in enumerate(ctc_status):
             self.host[1 + i:2 + i].copy_(s.reshape(1), non_blocking=True)
@@ -49,9 +50,9 @@ class StepRecord(object):
             self.event.synchronize()
             self.event = None
         words = self.host.numpy()
-        for code in words[1:1 + self.n_ctc]:
+        for error, code in zip(self.errors, words[1:1 + self.n_ctc]):
             if code:
-                raise Exception('%s [step %d]' % (loss_functions.ctc_status_error(int(code)), self.step))
+                raise Exception('%s [step %d]' % (error(int(code)), self.step))
         for (tag, buf), code in zip(self.workspaces, words[1 + self.n_ctc:]):
             if code:
                 if buf is not None:

@@ -254,6 +254,9 @@ class Trainer(object, metaclass=ABCMeta):
             if self.conf['loss'] == 'CTC':
                 raise ValueError('mwer_nbest fine-tunes a model trained on a cross-entropy loss through its recurrent '
                                  'decoder; loss = CTC has no such decoder')
+            if self.conf['loss'] == 'transducer':
+                raise ValueError('mwer_nbest fine-tunes a model trained on a cross-entropy loss through its recurrent '
+                                 'attention decoder; loss = transducer has no such decoder')
             if self.label_smoothing:
                 raise ValueError('mwer_nbest does not combine with label_smoothing yet')
             if self.ctc_weight:
@@ -272,6 +275,7 @@ class Trainer(object, metaclass=ABCMeta):
         self.last_weight_noise = None      # the (seed, offset) of the latest noisy step
         self._noisy = False                # True from a step's noise launch until its optimiser has run
         self.model = Model(conf=modelconf, trainlabels=int(self.conf['trainlabels']), constraint=None)
+        loss_functions.check_model(self.conf['loss'], self.model.decoder)
         if self.ctc_weight and not self.model.decoder.ctc_head:
             raise ValueError('ctc_weight = %g needs a model with a CTC head: set ctc_head = True in the [decoder] '
                              'section of the model' % self.ctc_weight)

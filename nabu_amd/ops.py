@@ -393,6 +393,41 @@ def ctc_align(logits, logit_len_dev, labels_dev, label_len_dev, raise_on_status=
     return state, seg, conf, score, status
 
 
+def transducer_loss_grad(f, g, enc_len_dev, labels_dev, label_len_dev, grad_scale):
+    """Transducer loss with the additive joint (nabu_transducer_loss_grad): f [B,T,C], g [B,U1,C], labels [B,>=U1-1]
+    int32 (None when U1 = 1).  Returns (nll [B], df [B,T,C], dg [B,U1,C], status [1] int32) — all on device."""
+    L = _hip.lib()
+    B, T, C = f.shape
+    U1 = g.shape[1]
+    if g.shape[0] != B or g.shape[2] != C:
+        raise _hip.NabuHipError('transducer_loss_grad: f %s and g %s do not agree' % (tuple(f.shape), tuple(g.shape)))
+    if labels_dev is not None and labels_dev.stride(1) != 1:
+        raise _hip.NabuHipError('transducer_loss_grad: labels must be contiguous in their rows')
+    dev = f.device
+    nll = torch.empty(B, dtype=torch.float32, device=dev)
+    df, dg = torch.empty_like(f), torch.empty_like(g)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = L.nabu_transducer_ws_bytes(B, T, U1)
+    ws = Workspace.get(ws_bytes, dev, 'transducer')
+    check(L.nabu_transducer_loss_grad(B, T, U1, C, ptr(_f32(f, 'f')), ptr(_f32(g, 'g')), ptr(enc_len_dev),
+                                      ptr(labels_dev) if labels_dev is not None and labels_dev.numel() else None,
+                                      labels_dev.stride(0) if labels_dev is not None and labels_dev.numel() else 0,
+                                      ptr(label_len_dev), grad_scale, ptr(nll), ptr(df), ptr(dg), ptr(status), ptr(ws),
+                                      ws_bytes, stream()), 'nabu_transducer_loss_grad')
+    return nll, df, dg, status
+
+
+def transducer_greedy_step(step, f, g_row, enc_len_dev, t_pos, out_len, ids, emit, last_id, score):
+    """One lock-step iteration of the greedy transducer search (nabu_transducer_greedy_step), in place on the search
+    state t_pos / out_len / last_id / score [B], ids [B,S]; emit [B] says which rows emitted a label.  step = 0 starts
+    a search: the kernel sets the state up itself."""
+    B, T, C = f.shape
+    check(_hip.lib().nabu_transducer_greedy_step(B, T, C, ids.shape[1], step, ptr(_f32(f, 'f')), ptr(_f32(g_row, 'g_row')),
+                                                 ptr(enc_len_dev), ptr(t_pos), ptr(out_len), ptr(ids), ptr(emit),
+                                                 ptr(last_id), ptr(_f32(score, 'score')), stream()),
+          'nabu_transducer_greedy_step')
+
+
 def adam_clip_step(param, grad, m, v, lr_t, b1=0.9, b2=0.999, eps=1e-8, clip=1.0, grad_scale=1.0):
     check(_hip.lib().nabu_adam_clip_step(param.numel(), ptr(param), ptr(grad), ptr(m), ptr(v), lr_t, b1, b2,
                                          eps, clip, grad_scale, stream()), 'nabu_adam_clip_step')
