@@ -512,6 +512,56 @@ int nabu_transducer_greedy_step(int B, int T, int C, int S, int step, const floa
                                 const float *g_row, const int32_t *enc_len, int32_t *t_pos,
                                 int32_t *out_len, int32_t *ids, int32_t *emit, int32_t *last_id,
                                 float *score, nabu_stream_t stream);
+/* One iteration of the alignment-length synchronous beam search of the transducer (Saon, Tueske and Audhkhasi 2020,
+ * "Alignment-length synchronous decoding for RNN transducer"; transducer_beam.hip): one launch, one workgroup per
+ * utterance.  At iteration i = step every active hypothesis with u labels sits at frame t = i - u (the frame is not
+ * stored), so the whole beam of every utterance takes exactly one joint evaluation per iteration, and hypotheses that
+ * spell the same labels meet at the same lattice node in the same iteration, where their probabilities are ADDED.
+ *
+ * Definition, per utterance b: el = min(max(enc_len[b], 0), T), blank = C-1, S the most labels a hypothesis may hold,
+ * W the beam width.  step = 0 starts from the state as found, whatever it holds: the beam is the empty hypothesis in
+ * slot 0 with score 0 and there are no finals; with el = 0 that hypothesis is complete at once: finals = [((), 0)] and
+ * nothing is active.  Iteration i over the active hypotheses (y_w, s_w) in slots w = 0..n-1, each at t_w = i - |y_w| < el:
+ *   1. log-probabilities: x = f[b,t_w,:] + g_rows[b,w,:] (one float32 addition), lp_w[k] = (x[k] - max x) - log sum exp(x - max x);
+ *   2. candidates: v[w,k] = s_w + lp_w[k] for every class; a hypothesis with |y_w| = S has only its blank candidate;
+ *   3. merge: for every pair of active hypotheses (a, c) with y_a = y_c + (k) — decided on the label sequences
+ *      themselves — v[a,blank] = logadd(v[a,blank], v[c,k]) and candidate (c,k) is dropped;
+ *      logadd(p, q) = max + log1p(exp(min - max)).  Active hypotheses are pairwise distinct: an a has one partner at most;
+ *   4. order: the remaining candidates by value, largest first, equal values by flat index w C + k, smallest first; the
+ *      first W are taken, or fewer if fewer exist;
+ *   5. placement, in that order: a blank candidate with t_w + 1 = el COMPLETES y_w: it is offered to the finals and takes
+ *      no active slot (the beam shrinks); any other blank gives the active (y_w, v) with parent = w, emit = 0,
+ *      last_id = blank; a label gives (y_w + k, v) with parent = w, emit = 1, last_id = k.  New actives fill slots
+ *      0, 1, .. in selection order; every other slot is empty: out_len = -1, ids = -1, score = -inf, parent = its own
+ *      index, emit = 0, last_id = blank;
+ *   6. finals: at most W are kept, best score first, in slots 0, 1, ..; a completed hypothesis goes in behind finals of
+ *      equal score, what falls past W is dropped; empty slots have fin_len = -1, fin_ids = -1, fin_score = -inf.
+ * An utterance is done when it has no active hypothesis, after at most el + S iterations (one still active at iteration
+ * el + S would need t >= el); at least one final exists by then.  The result is the best final, fin_*[b,0].
+ * Consequences (each checked with the float64 restatement, tests/transducer_beam_ref.py):
+ *   - unpruned search gives exact scores: with W at least the number of label sequences of length <= S the final score
+ *     of every y is log P(y | x), what nabu_transducer_loss_grad returns as -nll;
+ *   - W = 1 takes the decisions of nabu_transducer_greedy_step (the same tie rule: the blank has the largest index):
+ *     labels and lengths are equal, and the score wherever the row ran out of frames.  A row that the greedy search
+ *     stops at S labels with frames left goes on through blanks here, which the greedy search never pays for;
+ *   - merging matters: it changes which hypothesis is best, not only the scores.
+ * ids [B,W,S] (padded with -1), out_len, score [B,W] are the beam, updated in place; the survivors' label rows are made
+ * from the parents' rows as found (staged in LDS), so a parent may feed several children and slots may permute.  parent,
+ * emit, last_id [B,W] are what the prediction network needs next: gather its state rows by parent, then advance the
+ * rows with emit = 1 on last_id (emit can be the seq_len of nabu_lstm_cell_fwd at step 0).  g_rows [B,W,C] holds the
+ * prediction logits of the hypothesis in each slot.  f and g_rows of empty slots are never read, nor is f beyond el.
+ * A slot whose out_len is outside 0..S or whose frame step - out_len is outside 0..el-1 counts as empty.
+ * The log-sum-exp of a hypothesis is taken by one wave, lane-strided over C; the selection is W rounds of a block-wide
+ * arg-max over the candidates in LDS; no sum is atomic: two calls give the same bits.
+ * ws: the finals' label rows while they are reordered, nabu_transducer_beam_ws_bytes(B,W,C,S) bytes (0 for a dimension <= 0).
+ * NABU_EINVAL: W outside 1..32, B outside 1..65535, T < 1, S < 1, C < 2, step < 0, a null pointer.  NABU_EWS: ws_bytes too
+ * small.  NABU_EUNSUP: 4 W (C + S) bytes of LDS are more than a CU has.  All three return before any launch. */
+size_t nabu_transducer_beam_ws_bytes(int B, int W, int C, int S);
+int nabu_transducer_beam_step(int B, int T, int C, int S, int W, int step, const float *f,
+                              const float *g_rows, const int32_t *enc_len, int32_t *ids,
+                              int32_t *out_len, float *score, int32_t *parent, int32_t *emit,
+                              int32_t *last_id, int32_t *fin_ids, int32_t *fin_len, float *fin_score,
+                              void *ws, size_t ws_bytes, nabu_stream_t stream);
 
 /* Masked sparse softmax cross-entropy averaged over the target length —
  * loss_functions.average_cross_entropy / cross_entropy

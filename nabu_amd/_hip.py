@@ -145,6 +145,8 @@ SIGNATURES = {
     'nabu_transducer_ws_bytes': (_sz, [_i, _i, _i]),
     'nabu_transducer_loss_grad': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nabu_transducer_greedy_step': (_i, [_i, _i, _i, _i, _i] + [_vp] * 9 + [_vp]),
+    'nabu_transducer_beam_ws_bytes': (_sz, [_i, _i, _i, _i]),
+    'nabu_transducer_beam_step': (_i, [_i] * 6 + [_vp] * 12 + [_vp, _sz, _vp]),
     'nabu_xent_loss_grad': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     'nabu_xent_smooth_loss_grad': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp]),
     'nabu_lstm_cell_fwd': (_i, [_i, _i, _i] + [_vp] * 10 + [_vp]),

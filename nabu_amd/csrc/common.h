@@ -127,6 +127,35 @@ __device__ __forceinline__ float wave_max_unrolled(float v) {
   return v;
 }
 
+// block-wide arg-max of the selection kernels (decode.hip, transducer_beam.hip): W rounds of block_best take the W
+// best of the candidates the threads hold
+struct Best {
+  float v;
+  int i;
+};
+// larger value wins, equal values go to the smaller index; NaN never wins
+__device__ __forceinline__ Best better(Best a, Best b) { return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a; }
+
+// NT threads per workgroup.  `red` holds two sets of NT / 64 per-wave results used alternately (parity = round & 1), so
+// that one barrier per round suffices: round k+1 writes the other set while stragglers still read set k.
+template <int NT>
+__device__ __forceinline__ Best block_best(Best x, Best *red, int parity) {
+  red += parity * (NT / 64);
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    Best y;
+    y.v = __shfl_xor(x.v, o);
+    y.i = __shfl_xor(x.i, o);
+    x = better(x, y);
+  }
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+  __syncthreads();
+  Best r = red[0];
+#pragma unroll
+  for (int w = 1; w < NT / 64; ++w) r = better(r, red[w]);
+  return r;
+}
+
 // relu that keeps NaN (fmaxf returns the non-NaN operand: a diverged pre-activation would become an ordinary zero and the
 // layer norm behind it finite numbers); every other value is fmaxf(x, 0)'s, bit for bit
 __device__ __forceinline__ float relu_value(float x) { return x != x ? x : fmaxf(x, 0.f); }

@@ -37,34 +37,6 @@ __device__ __forceinline__ float lse2d(float a, float b) {
   return m + log1pf(expf(n - m));
 }
 
-struct Best {
-  float v;
-  int i;
-};
-// larger value wins, equal values go to the smaller index; NaN never wins
-__device__ __forceinline__ Best better(Best a, Best b) { return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a; }
-
-// `red` holds two sets of per-wave results used alternately (parity = round & 1), so that one
-// barrier per round suffices: round k+1 writes the other set while stragglers still read set k.
-__device__ __forceinline__ Best block_best(Best x, Best *red, int parity) {
-  red += parity * (DT / 64);
-#pragma unroll
-  for (int o = 32; o; o >>= 1) {
-    Best y;
-    y.v = __shfl_xor(x.v, o);
-    y.i = __shfl_xor(x.i, o);
-    x = better(x, y);
-  }
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-  __syncthreads();
-  Best r = red[0];
-#pragma unroll
-  for (int w = 1; w < DT / 64; ++w) r = better(r, red[w]);
-  return r;
-}
-
-
-
 // order-preserving map float -> uint32 (larger float = larger integer); -inf and NaN map to 0 = "dead"
 __device__ __forceinline__ unsigned key_image(float x) {
   if (!(x > -INFINITY)) return 0u;
@@ -328,7 +300,7 @@ __global__ __launch_bounds__(DT) void ctc_beam_kernel(CtcArgs<LM> p) {
       __shared__ Best s_red[2 * (DT / 64)];
       Best mine = {-INFINITY, INT_MAX};
       if (tid < s_nl) mine = Best{s_tot[tid] + p.alpha * p.lm[(size_t)nctx[s_node[tid]] * C + blank], tid};
-      const Best g = block_best(mine, s_red, 0);
+      const Best g = block_best<DT>(mine, s_red, 0);
       top_lp = s_tot[0];
       if (g.i != INT_MAX) { top = g.i; top_lp = g.v; }
     }
@@ -488,7 +460,7 @@ __global__ __launch_bounds__(DT) void beam_prune_kernel(PruneArgsOf<LM> p) {
   Best mine = {-INFINITY, INT_MAX};
   for (int idx = tid; idx < n; idx += DT) mine = better(mine, Best{sc[idx], idx});
   for (int k = 0; k < W; ++k) {
-    Best g = block_best(mine, red, k & 1);
+    Best g = block_best<DT>(mine, red, k & 1);
     if (g.i == INT_MAX) g.i = k;                         // only NaNs left (NaN logits): any slot
     if (tid == 0) sel[k] = g.i;
     if ((g.i % DT) == tid) {

@@ -1,13 +1,23 @@
-"""TransducerDecoder (not in the reference): greedy search with an RNN transducer model (decoder = transducer), all
-utterances of the batch in lock-step on the device.
+"""TransducerDecoder (not in the reference): greedy or beam search with an RNN transducer model (decoder = transducer),
+all utterances of the batch in lock-step on the device.
 
 Every iteration is one nabu_transducer_greedy_step launch — each row takes the arg-max of f[b, t_pos] + g_row[b]; the
 blank moves it to the next frame, a label is appended — then one step of the prediction network for the rows that
 emitted (the others keep their state: `emit` is the step's seq_len) and the output product that gives the next g_row.
 A row is finished after at most T' + max_steps iterations; every 32 iterations the host reads ONE word saying whether
-all rows are, and does not synchronise otherwise.  Beam search and language-model fusion are out of scope here.
+all rows are, and does not synchronise otherwise.
 
-conf: <output>_alphabet as for ctc_decoder; max_steps (required): the most labels an utterance gets."""
+With beam_width = W in 2..32 the search is the alignment-length synchronous beam search (Saon, Tueske and Audhkhasi
+2020; the definition is nabu_transducer_beam_step's in include/nabu_hip.h): B W rows of the prediction network, and per
+iteration one nabu_transducer_beam_step launch for the whole beam of every utterance — hypotheses that spell the same
+labels meet there and their probabilities are added — then predict_reorder (the survivors take their parents' state)
+and predict_step (those that emitted advance).  An utterance is done when no hypothesis of its beam is active, after at
+most T' + max_steps iterations; every 32 iterations the host reads ONE word saying whether all are.  The result is the
+best completed hypothesis; self.nbest keeps all W of them.  Language-model fusion and score normalisation are out of
+scope here.
+
+conf: <output>_alphabet as for ctc_decoder; max_steps (required): the most labels an utterance gets; beam_width
+(optional, 1..32; absent or 1: the greedy search)."""
 import torch
 
 from nabu_amd import ops
@@ -21,7 +31,7 @@ REFUSED = ('lm_file', 'lm_weight', 'insertion_bonus', 'ctc_weight', 'timestamps'
 
 
 class TransducerDecoder(decoder.Decoder):
-    '''greedy transducer search; the outputs, the written files and the error rate are CTCDecoder's'''
+    '''greedy or beam transducer search; the outputs, the written files and the error rate are CTCDecoder's'''
 
     def __init__(self, conf, model):
         super(TransducerDecoder, self).__init__(conf, model)
@@ -30,17 +40,23 @@ class TransducerDecoder(decoder.Decoder):
                              '[decoder] section), got %s' % type(model.decoder).__name__)
         for key in REFUSED:
             if key in self.conf:
-                raise ValueError('transducer_decoder is a plain greedy search: the key %s is not supported' % key)
+                raise ValueError('transducer_decoder searches with the model alone: the key %s is not supported' % key)
         self.max_steps = int(self.conf['max_steps'])
         if self.max_steps < 1:
             raise ValueError('max_steps must be positive, got %d' % self.max_steps)
+        width = self.conf.get('beam_width', '1').strip()
+        if not width.isdigit() or not 1 <= int(width) <= 32:
+            raise ValueError('beam_width must be an integer in 1..32, got %r' % width)
+        self.beam_width = int(width)
         self.alphabets = {o: self.conf['%s_alphabet' % o].split(' ') for o in model.output_names}
 
     def __call__(self, inputs, input_seq_length):
         '''Returns {output: (ids [B,max_steps] int32 padded with -1, lengths [B] int32)}, as CTCDecoder does; self.scores
-        keeps {output: log p of the path taken [B]}'''
+        keeps {output: log p of the path taken [B]} (beam search: of the best hypothesis, all its alignments that the
+        beam kept added up) and, for the beam search, self.nbest {output: (ids [B,W,max_steps], lengths [B,W], log p
+        [B,W])}: the completed hypotheses, best first, lengths -1 where there are fewer than W'''
         net = self.model.decoder
-        outputs, self.scores = {}, {}
+        outputs, self.scores, self.nbest = {}, {}, {}
         with torch.no_grad():
             logits, logit_len = self.model(inputs, input_seq_length, targets=[], target_seq_length=[], is_training=False)
             for o in self.model.output_names:
@@ -48,6 +64,9 @@ class TransducerDecoder(decoder.Decoder):
                 B, T, C = f.shape
                 dev, S = f.device, self.max_steps
                 lens = SeqLen.wrap(logit_len[o], dev)
+                if self.beam_width > 1:
+                    outputs[o], self.scores[o], self.nbest[o] = self._beam(net, o, f, lens)
+                    continue
                 t_pos, out_len, emit, last_id = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(4))
                 ids = torch.empty((B, S), dtype=torch.int32, device=dev)
                 score = torch.empty(B, dtype=torch.float32, device=dev)
@@ -64,6 +83,25 @@ class TransducerDecoder(decoder.Decoder):
                 outputs[o] = (ids, out_len)
                 self.scores[o] = score
         return outputs
+
+    def _beam(self, net, o, f, lens):
+        '''((ids [B,max_steps], lengths [B]), log p [B], (all finals)) of output o'''
+        B, T, C = f.shape
+        dev, S, W = f.device, self.max_steps, self.beam_width
+        beam = ops.transducer_beam_state(B, W, S, dev)
+        with vs.as_default(self.model.store):
+            state = net.predict_start(o, B * W, dev)
+        # the empty history: every row reads the start symbol (the blank's class)
+        g_rows = net.predict_step(state, torch.full((B * W,), C - 1, dtype=torch.int32, device=dev),
+                                  torch.ones(B * W, dtype=torch.int32, device=dev))
+        for it in range(T + S):
+            ops.transducer_beam_step(it, f, g_rows, lens.dev, beam)
+            net.predict_reorder(state, beam.parent)
+            g_rows = net.predict_step(state, beam.last_id.view(B * W), beam.emit.view(B * W))
+            if it % POLL == POLL - 1 and bool((beam.out_len < 0).all().item()):
+                break
+        return ((beam.fin_ids[:, 0].contiguous(), beam.fin_len[:, 0].contiguous()), beam.fin_score[:, 0].contiguous(),
+                (beam.fin_ids, beam.fin_len, beam.fin_score))
 
     # one line "<name> <symbols>" per utterance; sum of edit distances / number of reference labels
     write = ctc_decoder.CTCDecoder.write

@@ -2,7 +2,8 @@
 a transcription network — one linear layer on the first encoded input — and a prediction network — a unidirectional
 LSTM over the label history followed by a linear layer.  Their logits f [B,T,C] and g [B,U1,C] meet in the additive
 joint h[t,u,k] = f[t,k] + g[u,k], which only the loss (loss = transducer, nabu_transducer_loss_grad) and the search
-(decoder = transducer_decoder, nabu_transducer_greedy_step) evaluate: h is never materialised.
+(decoder = transducer_decoder, nabu_transducer_greedy_step or, with beam_width, nabu_transducer_beam_step) evaluate: h is
+never materialised.
 
 Variables of output o (blank = start symbol = C-1, the class `trainlabels = 1` adds):
     Transducer/o/transcription/{weights,biases}                      dnn_decoder.linear
@@ -12,7 +13,8 @@ Variables of output o (blank = start symbol = C-1, the class `trainlabels = 1` a
 With targets the prediction network reads the start symbol followed by the targets, one-hot, for U1 = Lmax + 1 steps
 with seq_len = target_len + 1: a step chain of nabu_lstm_cell_fwd, the first layer's input product being the row gather
 of that kernel; its backward pass is one tape node.  Without targets (every inference decoder calls the model with
-targets = []) only f is returned, and predict_start / predict_step run the network one label at a time."""
+targets = []) only f is returned, and predict_start / predict_step run the network one label at a time; the beam search
+runs B W rows and moves their states to the survivors with predict_reorder."""
 import torch
 
 from nabu_amd import ops as hip
@@ -159,6 +161,23 @@ class Transducer(ed_decoder.EDDecoder):
             x = h[0]
         hip.gemm(x, state['W'].data, state['g'], bias=state['b'].data)
         return state['g']
+
+    def predict_reorder(self, state, parent):
+        '''the beam search's survivors take their parents' state: row b W + w of every layer's c and h becomes row
+        b W + parent[b,w] (parent [B,W] int32 as nabu_transducer_beam_step writes it; the state has B W rows).  Call it
+        before predict_step(state, last_id, emit) advances the rows that emitted.  The rows are gathered into the
+        buffers the next predict_step would overwrite anyway, which then change places with the current ones — the
+        same flip predict_step makes — so a parent may feed several children.'''
+        B, W = parent.shape
+        for l in range(len(state['layers'])):
+            for bufs in (state['c'][l], state['h'][l]):
+                U = bufs[0].shape[1]
+                # nabu_beam_gather picks `old` or `fresh` by its stay argument: with both the same tensor it is a
+                # plain gather, and any int32 array serves as stay
+                hip.check(hip._hip.lib().nabu_beam_gather(B, W, U, hip.ptr(bufs[0]), hip.ptr(bufs[0]), hip.ptr(parent),
+                                                          hip.ptr(parent), hip.ptr(bufs[1]), hip.stream()),
+                          'nabu_beam_gather')
+                bufs.reverse()
 
     def zero_state(self, encoded_dim, batch_size):
         return ()

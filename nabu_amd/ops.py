@@ -428,6 +428,54 @@ def transducer_greedy_step(step, f, g_row, enc_len_dev, t_pos, out_len, ids, emi
           'nabu_transducer_greedy_step')
 
 
+class TransducerBeamState(object):
+    """the state of nabu_transducer_beam_step: the beam ids [B,W,S], out_len, score [B,W]; parent, emit, last_id [B,W] for
+    the prediction network; the finals fin_ids [B,W,S], fin_len, fin_score [B,W] (best first); the workspace.  Nothing
+    is cleared: step 0 sets everything up."""
+
+    def __init__(self, B, W, S, device):
+        self.B, self.W, self.S = int(B), int(W), int(S)
+
+        def i32(*shape):
+            return torch.empty(shape, dtype=torch.int32, device=device)
+
+        def f32(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=device)
+        self.ids, self.out_len, self.score = i32(B, W, S), i32(B, W), f32(B, W)
+        self.parent, self.emit, self.last_id = i32(B, W), i32(B, W), i32(B, W)
+        self.fin_ids, self.fin_len, self.fin_score = i32(B, W, S), i32(B, W), f32(B, W)
+        self.ws = torch.empty(max(self.ws_bytes(2), 16), dtype=torch.uint8, device=device)
+
+    def ws_bytes(self, C):
+        return _hip.lib().nabu_transducer_beam_ws_bytes(self.B, self.W, C, self.S)
+
+
+def transducer_beam_state(B, W, S, device):
+    """the tensors and the workspace of a beam search over B utterances with W slots of at most S labels each"""
+    return TransducerBeamState(B, W, S, device)
+
+
+def transducer_beam_step(step, f, g_rows, enc_len_dev, state):
+    """One iteration of the alignment-length synchronous beam search (nabu_transducer_beam_step), in place on `state`:
+    f [B,T,C], g_rows [B,W,C] (or [B*W,C]) the prediction logits of the hypothesis in each slot.  step = 0 starts a
+    search."""
+    B, T, C = f.shape
+    st = state
+    if st.B != B or g_rows.numel() != B * st.W * C:
+        raise _hip.NabuHipError('transducer_beam_step: f %s, g_rows %s and a state of [%d,%d] slots do not agree'
+                                % (tuple(f.shape), tuple(g_rows.shape), st.B, st.W))
+    if g_rows.dtype != torch.float32 or not g_rows.is_contiguous():
+        raise _hip.NabuHipError('transducer_beam_step: g_rows must be contiguous float32')
+    need = st.ws_bytes(C)
+    if st.ws.numel() < need:
+        st.ws = torch.empty(need, dtype=torch.uint8, device=f.device)
+    check(_hip.lib().nabu_transducer_beam_step(B, T, C, st.S, st.W, step, ptr(_f32(f, 'f')), ptr(g_rows),
+                                               ptr(enc_len_dev), ptr(st.ids), ptr(st.out_len), ptr(st.score),
+                                               ptr(st.parent), ptr(st.emit), ptr(st.last_id), ptr(st.fin_ids),
+                                               ptr(st.fin_len), ptr(st.fin_score), ptr(st.ws), st.ws.numel(), stream()),
+          'nabu_transducer_beam_step')
+
+
 def adam_clip_step(param, grad, m, v, lr_t, b1=0.9, b2=0.999, eps=1e-8, clip=1.0, grad_scale=1.0):
     check(_hip.lib().nabu_adam_clip_step(param.numel(), ptr(param), ptr(grad), ptr(m), ptr(v), lr_t, b1, b2,
                                          eps, clip, grad_scale, stream()), 'nabu_adam_clip_step')
