@@ -497,6 +497,49 @@ int nabu_transducer_loss_grad(int B, int T, int U1, int C, const float *f, const
                               const int32_t *label_len, float grad_scale, float *nll, float *df,
                               float *dg, int32_t *status, void *ws, size_t ws_bytes,
                               nabu_stream_t stream);
+/* Forced alignment with a transducer model (transducer_align.hip): the best monotone path through the lattice
+ * nabu_transducer_loss_grad sums over.  Same operands and conventions: f [B,T,C], g [B,U1,C], blank = C-1, enc_len
+ * 1..T, labels [B,ldl] (may be null for U1 = 1), label_len 0..U1-1.
+ *
+ * Definition.  lb[t,u] and ly[t,u] are the loss's, made by the loss's own node expression: h = f + g is one float32
+ * addition, log p = (h - mx) - lz with the node's own maximum and log-sum kept apart.  The frame normalisers depend on
+ * (t,u), so the recursion runs on log-probabilities (nabu_ctc_align could use raw logits; this cannot):
+ *   v[0,0] = 0,  v[t,u] = max(v[t-1,u] + lb[t-1,u], v[t,u-1] + ly[t,u-1])
+ * with each candidate one float32 addition and unreachable the finite -1e30.  A tie keeps the BLANK move: the label
+ * move wins only if strictly greater (nabu_ctc_align's "smaller move" rule).  A move that does not exist — the label
+ * move in column 0, the blank move at frame 0 — is never taken whatever the back-pointer's comparison says, so with -inf or NaN terms (a
+ * masked blank, a diverged model) the path still stays inside the lattice; its score, the sum of its terms, is then
+ * -inf or NaN with status 0, as the loss returns nll = inf for such input.  The path ends with the blank at (T_b-1, U_b); the backtrace runs
+ * from there to (0,0).
+ *   state [B,T] int32     the u at which frame t's blank is taken = the labels emitted up to and including frame t;
+ *                         -1 from enc_len[b] on; non-decreasing, state[T_b-1] = U_b
+ *   frame [B,U1-1] int32  the frame at which label i is emitted = the first t with state[t] > i; -1 beyond U_b
+ *   conf [B,U1-1]         ly[frame[i], i], the log-probability of label i at its emission node; 0 beyond U_b
+ *   score [B]             the sum of the path's T_b + U_b terms: the log-probability of the best alignment
+ * score is summed in a fixed order (a tree over the path's nodes) without floating-point atomics: identical calls give
+ * identical bits.  frame and conf may be null for U1 = 1.
+ * An utterance the loss rejects (a label < 0 or >= C-1, enc_len <= 0 or > T, label_len < 0 or > U1-1; the same test)
+ * gets score = -inf, state and frame -1, conf 0, and sets status [1] (device) to 1+b through the loss's
+ * atomicCAS rule: status names the FIRST such utterance; the others are aligned normally.  U_b = 0 is valid: every
+ * state is 0.
+ * Launches: emission terms (lb and ly only), then sweep, backtrace and outputs in one.  Routes of the sweep: U1 <= 64:
+ * one wave64 per utterance walking anti-diagonals, lane u on node (d-u, u), the neighbour through DPP, no barrier in
+ * the loop; otherwise 256 threads with u strided over them and a barrier per diagonal.  Both evaluate the same
+ * per-node expression: same bits.  NABU_TRANSDUCER_ALIGN_WORKGROUP=1 (read once per process) forces the second.
+ * Back-pointers (one bit per node) and the path live in LDS while they fit — nabu_transducer_align_lds_bytes(T, U1,
+ * workgroup_route) <= 150 KiB — and in ws otherwise.  NABU_TRANSDUCER_ALIGN_LAUNCHES (read on every call; for
+ * measurements only) is a mask of the launches to make: 1 emission terms, 2 sweep and backtrace; 2 alone needs a
+ * workspace that a complete call on the same operands has filled.
+ * NABU_EINVAL, NABU_EWS (ws_bytes < nabu_transducer_align_ws_bytes(B,T,U1), 0 for B, T or U1 <= 0) and NABU_EUNSUP
+ * under nabu_transducer_loss_grad's conditions; all three return before any launch.  Every shape the loss takes is
+ * taken. */
+size_t nabu_transducer_align_ws_bytes(int B, int T, int U1);
+size_t nabu_transducer_align_lds_bytes(int T, int U1, int workgroup_route);
+int nabu_transducer_align(int B, int T, int U1, int C, const float *f, const float *g,
+                          const int32_t *enc_len, const int32_t *labels, int ldl,
+                          const int32_t *label_len, int32_t *state, int32_t *frame, float *conf,
+                          float *score, int32_t *status, void *ws, size_t ws_bytes,
+                          nabu_stream_t stream);
 /* One step of the greedy transducer search for B rows in lock-step: one launch, one wave per row.  g_row [B,C] are
  * the prediction logits of each row's current history; t_pos, out_len [B], ids [B,S], last_id [B] and score [B] are
  * the search state, S the cap on labels per row.  step = 0 starts a search: the kernel itself sets t_pos = 0,

@@ -144,6 +144,9 @@ SIGNATURES = {
     'nabu_ctc_align': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nabu_transducer_ws_bytes': (_sz, [_i, _i, _i]),
     'nabu_transducer_loss_grad': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'nabu_transducer_align_ws_bytes': (_sz, [_i, _i, _i]),
+    'nabu_transducer_align_lds_bytes': (_sz, [_i, _i, _i]),
+    'nabu_transducer_align': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nabu_transducer_greedy_step': (_i, [_i, _i, _i, _i, _i] + [_vp] * 9 + [_vp]),
     'nabu_transducer_beam_ws_bytes': (_sz, [_i, _i, _i, _i]),
     'nabu_transducer_beam_step': (_i, [_i] * 6 + [_vp] * 12 + [_vp, _sz, _vp]),

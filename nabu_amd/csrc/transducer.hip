@@ -18,13 +18,9 @@
 // contiguous: the sweeps' loads and stores are coalesced and their addresses known ahead.
 #include <stdlib.h>
 
-#include "common.h"
+#include "transducer_dev.h"
 
 namespace nabu {
-
-constexpr float TR_NEG = -1e30f;    // unreachable (CTC_NEG of ctc.hip): -1e30 + x is -1e30 again, never inf - inf
-constexpr int TR_NT = 256;
-constexpr int TR_AHEAD = 8;         // diagonals per group of loads of the wave route
 
 struct TransArgs {
   int B, T, U1, C, ldl;
@@ -39,11 +35,7 @@ struct TransArgs {
 };
 
 __device__ __forceinline__ size_t tr_slab(const TransArgs &p, int b) { return (size_t)b * (p.T + p.U1) * p.U1; }
-__device__ __forceinline__ int tr_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-__device__ __forceinline__ float tr_up(float v, float fill) {     // lane i <- lane i-1 (lane 0 <- fill)
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
 __device__ __forceinline__ float tr_dn(float v, float fill) {     // lane i <- lane i+1 (lane 63 <- fill)
   return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x130, 0xf, 0xf, false));
 }
@@ -69,45 +61,23 @@ __global__ __launch_bounds__(TR_NT) void transducer_emit_kernel(TransArgs p) {
   const int Tb = tr_clamp(p.enc_len[b], 0, p.T), Ub = tr_clamp(p.label_len[b], 0, p.U1 - 1);
   if (t >= Tb || u > Ub) return;
   const float *fr = p.f + ((size_t)b * p.T + t) * C, *gr = p.g + ((size_t)b * p.U1 + u) * C;
-  float m = fr[0] + gr[0];
-  for (int k = 1; k < C; ++k) m = fmaxf(m, fr[k] + gr[k]);
-  float z = 0.f;
-  for (int k = 0; k < C; ++k) z += expf((fr[k] + gr[k]) - m);
-  const float l = logf(z);
   int lab = u < Ub ? p.labels[(size_t)b * p.ldl + u] : -1;
   if (lab >= blank) lab = -1;
   const size_t at = tr_slab(p, b) + (size_t)(t + u) * p.U1 + u;
-  p.mx[at] = m;
-  p.lz[at] = l;
-  p.lb[at] = ((fr[blank] + gr[blank]) - m) - l;     // maximum and log-sum kept apart, as in ctc_kernel
-  p.ly[at] = lab >= 0 ? ((fr[lab] + gr[lab]) - m) - l : TR_NEG;
+  tr_node_terms(fr, gr, C, lab, p.mx + at, p.lz + at, p.lb + at, p.ly + at);     // (transducer_dev.h)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // (b) the verdict on utterance b, the same in every thread of the workgroup (one barrier)
 __device__ bool tr_utt_bad(const TransArgs &p, int b, int tid, int nt) {
-  const int Tb = p.enc_len[b], Ub = p.label_len[b];
-  int bad = (Tb <= 0 || Tb > p.T || Ub < 0 || Ub > p.U1 - 1) ? 1 : 0;
-  if (!bad)
-    for (int u = tid; u < Ub; u += nt) {
-      const int l = p.labels[(size_t)b * p.ldl + u];
-      if (l < 0 || l >= p.C - 1) bad = 1;
-    }
-  return __syncthreads_or(bad) != 0;
+  return tr_lengths_labels_bad(p.T, p.U1, p.C, p.enc_len, p.labels, p.ldl, p.label_len, b, tid, nt);
 }
 
 // a rejected utterance: nll 0, its verdict for (c), and its number in the status word (the beta workgroup's thread 0)
 __device__ void tr_reject(const TransArgs &p, int b) {
   p.nll[b] = 0.f;
   p.bad[b] = 1;
-  // ctc_align's rule: atomicCAS(status, 0, b + 1), repeated while a LATER utterance holds the word
-  const int want = b + 1;
-  int old = atomicCAS(p.status, 0, want);
-  while (old != 0 && old > want) {
-    const int seen = atomicCAS(p.status, old, want);
-    if (seen == old) break;
-    old = seen;
-  }
+  tr_status_first(p.status, b);
 }
 
 // wave route: grid (B, 2), 64 threads.  blockIdx.y: 0 alpha, 1 beta

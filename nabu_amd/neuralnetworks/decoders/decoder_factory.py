@@ -8,5 +8,7 @@ factory = Registry('decoder', {
     'random_decoder': 'nabu_amd.neuralnetworks.decoders.random_decoder:RandomDecoder',
     'ctc_alignment_decoder': 'nabu_amd.neuralnetworks.decoders.ctc_alignment_decoder:CTCAlignmentDecoder',
     'transducer_decoder': 'nabu_amd.neuralnetworks.decoders.transducer_decoder:TransducerDecoder',
+    'transducer_alignment_decoder':
+        'nabu_amd.neuralnetworks.decoders.transducer_alignment_decoder:TransducerAlignmentDecoder',
 }, outside=('max_decoder', 'threshold_decoder', 'feature_decoder'),
     undefined='Undefined %s type: %s')

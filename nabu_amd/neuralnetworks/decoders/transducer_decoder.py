@@ -16,18 +16,36 @@ most T' + max_steps iterations; every 32 iterations the host reads ONE word sayi
 best completed hypothesis; self.nbest keeps all W of them.  Language-model fusion and score normalisation are out of
 scope here.
 
+With emission_times = True (an extension key: absent from the defaults, off when absent) the recognised labels — the
+greedy path's, or the best final's of the beam search — are then aligned to the SAME f (nabu_transducer_align): the
+prediction network runs teacher-forced on the recognised ids for g, the encoder does not run again.  `write` adds
+<output>.ctm — name 1 start duration symbol confidence per label, as ctc_decoder does for `timestamps`: a label starts
+at its emission frame and lasts until the next label's (the end of the utterance for the last), at least one frame — a
+convention, a transducer emits at instants (transducer_alignment_decoder.py); confidence = exp(log-probability of the
+label at its emission node); in encoded frames, or in seconds with frame_seconds > 0, which is honoured only together
+with the key.  The forced alignment is the BEST path of the recognised labels, which need not be the path the greedy
+search walked.  The key is not called `timestamps`: that one stays refused.
+
 conf: <output>_alphabet as for ctc_decoder; max_steps (required): the most labels an utterance gets; beam_width
-(optional, 1..32; absent or 1: the greedy search)."""
+(optional, 1..32; absent or 1: the greedy search); emission_times, frame_seconds (optional)."""
 import torch
 
 from nabu_amd import ops
 from nabu_amd import variables as vs
 from nabu_amd.autodiff import SeqLen
-from nabu_amd.neuralnetworks.decoders import ctc_decoder, decoder
+from nabu_amd.neuralnetworks.decoders import ctc_alignment_decoder, ctc_decoder, decoder, transducer_alignment_decoder
 from nabu_amd.neuralnetworks.models.ed_decoders import transducer
 
 POLL = 32                 # iterations between two reads of the "all rows finished" word
 REFUSED = ('lm_file', 'lm_weight', 'insertion_bonus', 'ctc_weight', 'timestamps', 'frame_seconds')
+
+
+def emission_times_key(conf):
+    """the `emission_times` key of the [decoder] section (an extension key: absent from the defaults, off when absent)"""
+    text = str(conf.get('emission_times', 'False')).strip()
+    if text not in ('True', 'False'):
+        raise ValueError('emission_times must be True or False, got %r' % text)
+    return text == 'True'
 
 
 class TransducerDecoder(decoder.Decoder):
@@ -38,8 +56,9 @@ class TransducerDecoder(decoder.Decoder):
         if not isinstance(model.decoder, transducer.Transducer):
             raise ValueError('transducer_decoder searches with a transducer model (decoder = transducer in the model\'s '
                              '[decoder] section), got %s' % type(model.decoder).__name__)
+        self.emission_times = emission_times_key(self.conf)
         for key in REFUSED:
-            if key in self.conf:
+            if key in self.conf and not (key == 'frame_seconds' and self.emission_times):
                 raise ValueError('transducer_decoder searches with the model alone: the key %s is not supported' % key)
         self.max_steps = int(self.conf['max_steps'])
         if self.max_steps < 1:
@@ -49,12 +68,15 @@ class TransducerDecoder(decoder.Decoder):
             raise ValueError('beam_width must be an integer in 1..32, got %r' % width)
         self.beam_width = int(width)
         self.alphabets = {o: self.conf['%s_alphabet' % o].split(' ') for o in model.output_names}
+        self.frame_seconds = ctc_alignment_decoder.frame_seconds_key(self.conf) if self.emission_times else 0.0
 
     def __call__(self, inputs, input_seq_length):
         '''Returns {output: (ids [B,max_steps] int32 padded with -1, lengths [B] int32)}, as CTCDecoder does; self.scores
         keeps {output: log p of the path taken [B]} (beam search: of the best hypothesis, all its alignments that the
         beam kept added up) and, for the beam search, self.nbest {output: (ids [B,W,max_steps], lengths [B,W], log p
-        [B,W])}: the completed hypotheses, best first, lengths -1 where there are fewer than W'''
+        [B,W])}: the completed hypotheses, best first, lengths -1 where there are fewer than W.  With emission_times =
+        True the tuple goes on with (seg [B,max_steps,2], conf [B,max_steps], score [B]): first frame and last frame + 1
+        of every label by the module's convention, ops.transducer_align's conf and score'''
         net = self.model.decoder
         outputs, self.scores, self.nbest = {}, {}, {}
         with torch.no_grad():
@@ -66,6 +88,8 @@ class TransducerDecoder(decoder.Decoder):
                 lens = SeqLen.wrap(logit_len[o], dev)
                 if self.beam_width > 1:
                     outputs[o], self.scores[o], self.nbest[o] = self._beam(net, o, f, lens)
+                    if self.emission_times:
+                        outputs[o] += self._emission_times(net, o, f, lens, *outputs[o])
                     continue
                 t_pos, out_len, emit, last_id = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(4))
                 ids = torch.empty((B, S), dtype=torch.int32, device=dev)
@@ -82,7 +106,26 @@ class TransducerDecoder(decoder.Decoder):
                         break
                 outputs[o] = (ids, out_len)
                 self.scores[o] = score
+                if self.emission_times:
+                    outputs[o] += self._emission_times(net, o, f, lens, ids, out_len)
         return outputs
+
+    def _emission_times(self, net, o, f, lens, ids, out_len):
+        '''(seg [B,max_steps,2], conf [B,max_steps], score [B]) of the recognised labels aligned to f.  The labels are cut
+        to the longest row (one host read) so that the lattice is no wider than it must be'''
+        B, S = ids.shape
+        none = out_len < 0                                   # (the beam search's utterance without a completed hypothesis)
+        out_len = out_len.clamp(min=0)
+        L = int(out_len.max().item())
+        labels = ids[:, :L].clamp(min=0).contiguous()
+        with vs.as_default(self.model.store):
+            g = net.predict_sequence(o, labels, out_len)
+        _, frame, conf, score, _ = ops.transducer_align(f, g, lens.dev, labels if L else None, out_len)
+        seg = torch.full((B, S, 2), -1, dtype=torch.int32, device=f.device)
+        cf = torch.zeros((B, S), dtype=torch.float32, device=f.device)
+        seg[:, :L] = transducer_alignment_decoder.emission_segments(frame, out_len, lens.dev)
+        cf[:, :L] = conf
+        return seg, cf, score.masked_fill(none, float('-inf'))          # (-inf: `write` gives the row no lines)
 
     def _beam(self, net, o, f, lens):
         '''((ids [B,max_steps], lengths [B]), log p [B], (all finals)) of output o'''

@@ -128,6 +128,18 @@ class Transducer(ed_decoder.EDDecoder):
         record([], [top], backward, params=tuple(v for pair in layers for v in pair))
         return top
 
+    def predict_sequence(self, o, targets, target_seq_length):
+        '''the prediction logits g [B,Lmax+1,C] of output o for the histories of targets [B,Lmax] — what the model
+        returns as <output>_pred when it is called with targets — without running the encoder (transducer_decoder aligns
+        what it has recognised to the f it already has).  Call with the model's store as the default.'''
+        C = self.output_dims[o]
+        with vs.variable_scope(self.scope), vs.variable_scope(o):
+            layers = self._net(C)
+            top = self._teacher_forced(layers, C, targets, SeqLen.wrap(target_seq_length, targets.device))
+            with vs.variable_scope('prediction'):
+                g_steps = dnn_decoder.linear(top, C, 'outlayer')                         # [U1,B,C]
+        return g_steps.transpose(0, 1).contiguous()
+
     # ------------------------------------------------------------------ one label at a time (transducer_decoder)
     def predict_start(self, o, B, device):
         '''the search state of output o for B rows: the variables, zero LSTM states and the step's buffers.  Call with

@@ -6,7 +6,7 @@ allow_smaller_final_batch; here the same sections of database.conf are read thro
 processing.input_pipeline.RecordData in file order, ceil(N / batch_size) batches, the last one
 smaller.  Decoding itself is the decoder's business (device kernels, decoders/).
 
-A decoder class with `needs_targets = True` (CTCAlignmentDecoder) also gets references: for every output of the model
+A decoder class with `needs_targets = True` (CTCAlignmentDecoder, TransducerAlignmentDecoder) also gets references: for every output of the model
 the key `<output> = <database sections>` of [recognizer] names its target sections, as a trainer conf names its
 targets, and every call receives targets=, target_seq_length=.  Other decoders are built and called as ever."""
 import math

@@ -417,6 +417,40 @@ def transducer_loss_grad(f, g, enc_len_dev, labels_dev, label_len_dev, grad_scal
     return nll, df, dg, status
 
 
+def transducer_align(f, g, enc_len_dev, labels_dev, label_len_dev, raise_on_status=False):
+    """Forced alignment with the transducer (nabu_transducer_align), operands as in transducer_loss_grad.  Returns
+    (state [B,T] int32, frame [B,U1-1] int32, conf [B,U1-1], score [B], status [1] int32) — all on device.  status is
+    1+b for the first utterance b the loss would reject; raise_on_status: read it back (a synchronisation) and raise
+    what the transducer loss raises for such an utterance."""
+    L = _hip.lib()
+    B, T, C = f.shape
+    U1 = g.shape[1]
+    if g.shape[0] != B or g.shape[2] != C:
+        raise _hip.NabuHipError('transducer_align: f %s and g %s do not agree' % (tuple(f.shape), tuple(g.shape)))
+    if labels_dev is not None and labels_dev.stride(1) != 1:
+        raise _hip.NabuHipError('transducer_align: labels must be contiguous in their rows')
+    dev = f.device
+    state = torch.empty((B, T), dtype=torch.int32, device=dev)
+    frame = torch.empty((B, U1 - 1), dtype=torch.int32, device=dev)
+    conf = torch.empty((B, U1 - 1), dtype=torch.float32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = L.nabu_transducer_align_ws_bytes(B, T, U1)
+    ws = Workspace.get(ws_bytes, dev, 'transducer_align')
+    has_labels = labels_dev is not None and labels_dev.numel()
+    check(L.nabu_transducer_align(B, T, U1, C, ptr(_f32(f, 'f')), ptr(_f32(g, 'g')), ptr(enc_len_dev),
+                                  ptr(labels_dev) if has_labels else None, labels_dev.stride(0) if has_labels else 0,
+                                  ptr(label_len_dev), ptr(state), ptr(frame) if U1 > 1 else None,
+                                  ptr(conf) if U1 > 1 else None, ptr(score), ptr(status), ptr(ws), ws_bytes, stream()),
+          'nabu_transducer_align')
+    if raise_on_status:
+        code = int(status.item())
+        if code:
+            from nabu_amd.neuralnetworks.trainers import loss_functions
+            raise loss_functions.transducer_status_error(code)
+    return state, frame, conf, score, status
+
+
 def transducer_greedy_step(step, f, g_row, enc_len_dev, t_pos, out_len, ids, emit, last_id, score):
     """One lock-step iteration of the greedy transducer search (nabu_transducer_greedy_step), in place on the search
     state t_pos / out_len / last_id / score [B], ids [B,S]; emit [B] says which rows emitted a label.  step = 0 starts
