@@ -13,8 +13,11 @@
 //           input-to-hidden GEMMs".
 //   NP = 2  "f16x3": every operand ROW (an M resp. N index: all its k) carries a power-of-two scale s that
 //           puts the row's largest magnitude into [2^14, 2^15); the scaled value is held as two fp16 planes
-//           x·s = h + l (h = rne(x·s), l = rne(x·s - h): 22-24 significant bits, absolute error below
-//           2^-40 of the row's maximum) and a product is the three plane products l·h, h·l, h·h on
+//           x·s = h + l (h = rne(x·s), l = rne(x·s - h): |h + l - x·s| <= max(2^-23 |x·s|, 2^-25), the second term
+//           half the spacing of fp16 subnormals — 23 significant bits down to 2^-16 below the power of two of the
+//           row's maximum, 39 - d bits at 2^-d below it, an absolute error of at most 2^-39 of the maximum;
+//           tests/test_gemm_pk_cases.py derives and pins it) and a product is the three plane products l·h, h·l, h·h
+//           (the dropped l·l is at most 2^-22 of a term) on
 //           v_mfma_f32_32x32x16_f16, promoted to the fp32 accumulators per 16 k as for NP = 3; the epilogue
 //           multiplies by 1 / (s_a[m] s_b[n]).  Half the matrix instructions of bf16x6 at the same error
 //           level against float64 (tests/test_hip_gemm_pk.py); a stage is 4 pieces (32 KiB), ring of three.

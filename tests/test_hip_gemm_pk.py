@@ -5,41 +5,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests.gemm_pk_cases import bf16_rne, pack_ref, pack_ref_f16          # the packs' restatement lives with the cases
+
 pytestmark = pytest.mark.gpu
-
-
-def bf16_rne(x):
-    """float32 array -> (uint16 bf16 bits, float32 value of the rounded number)"""
-    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
-    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint32)
-    return r.astype(np.uint16), (r << 16).astype(np.uint32).view(np.float32)
-
-
-def split_planes(x, planes):
-    out = []
-    rest = np.ascontiguousarray(x, dtype=np.float32)
-    for _ in range(planes):
-        bits, val = bf16_rne(rest)
-        out.append(bits)
-        rest = (rest - val).astype(np.float32)
-    return out, rest
-
-
-def pack_ref(mat, planes, rows_pad, nkb):
-    """mat [rows, K] float32 -> uint16 [nkb, planes, rows_pad, 16] in the layout of include/nabu_hip.h"""
-    rows, K = mat.shape
-    full = np.zeros((rows_pad, nkb * 16), np.float32)
-    full[:rows, :K] = mat
-    pl, rest = split_planes(full, planes)
-    if planes == 3:
-        assert not rest.any()                      # the three planes hold the fp32 value exactly
-    out = np.zeros((nkb, planes, rows_pad, 16), np.uint16)
-    swap = ((np.arange(rows_pad) >> 3) & 1).astype(bool)
-    for p in range(planes):
-        blk = pl[p].reshape(rows_pad, nkb, 2, 8).copy()
-        blk[swap] = blk[swap][:, :, ::-1, :]
-        out[:, p] = blk.reshape(rows_pad, nkb, 16).transpose(1, 0, 2)
-    return out
 
 
 @pytest.mark.parametrize('planes', [3, 1])
@@ -188,35 +156,6 @@ def test_gemm_pk_x6_error_not_above_exact_fp32(K):
 
 # ---------------------------------------------------------------------------------------------------------------
 # f16x3: two scaled fp16 planes, three plane products
-
-def f16_scale_exp(amax):
-    """exponent field -> (scale, inverse) as gemm_pk.hip derives them from the row maximum's bit pattern"""
-    bits = np.ascontiguousarray(amax, dtype=np.float32).view(np.uint32)
-    e = ((bits >> 23) & 0xFF).astype(np.int64)
-    e = np.where((bits & 0x7FFFFFFF) == 0, 127, e)
-    e = np.clip(e, 15, 253)
-    return np.exp2(141.0 - e).astype(np.float32), np.exp2(e - 141.0).astype(np.float32)
-
-
-def pack_ref_f16(mat, amax, rows_pad, nkb):
-    """mat [rows, K] float32, amax [rows] -> uint16 [nkb, 2, rows_pad, 16]"""
-    rows, K = mat.shape
-    full = np.zeros((rows_pad, nkb * 16), np.float32)
-    full[:rows, :K] = mat
-    am = np.zeros(rows_pad, np.float32)
-    am[:rows] = amax
-    scale = f16_scale_exp(am)[0]
-    xs = (full * scale[:, None]).astype(np.float32)
-    h = xs.astype(np.float16)
-    l = (xs - h.astype(np.float32)).astype(np.float16)
-    out = np.zeros((nkb, 2, rows_pad, 16), np.uint16)
-    swap = ((np.arange(rows_pad) >> 3) & 1).astype(bool)
-    for p, pl in enumerate((h, l)):
-        blk = pl.view(np.uint16).reshape(rows_pad, nkb, 2, 8).copy()
-        blk[swap] = blk[swap][:, :, ::-1, :]
-        out[:, p] = blk.reshape(rows_pad, nkb, 16).transpose(1, 0, 2)
-    return out, h, l, scale
-
 
 @pytest.mark.parametrize('transposed', [False, True])
 @pytest.mark.parametrize('rows,K', [(256, 64), (300, 1000), (72, 40), (515, 130)])

@@ -52,7 +52,7 @@ class StandardTrainer(base.StandardTrainer):
                 return {'step': step, 'batch': data.batch(step)}
         self.dataconf = Source()
 
-    def stage(self, batch):
+    def stage(self, batch, slot=None):
         self.log.append(('stage', batch['step'], threading.current_thread() is threading.main_thread()))
         return batch
 
