@@ -1443,6 +1443,48 @@ int nabu_feat_compute(const nabu_feat_desc *d, int n_utt, int max_frames, const 
                       const int32_t *sample_offsets, const int32_t *kept, const int32_t *frame_offsets,
                       float *out, const void *ws, size_t ws_bytes, nabu_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Convolutional front end of the BLSTM encoders (conv2d.hip): the VGG-style blocks of Zhang, Chan and Jaitly
+ * (2017) — two 3x3 convolutions with ReLU and a 2x2 max-pool per block — over the features seen as a
+ * [time x frequency x channel] image.  All tensors are channels-last float32, x [B, T, F, C]; len [B] (int32)
+ * says how many frames of each row exist (values outside 0..T are clamped).
+ * THE LENGTH RULE, for every entry point: a frame at or past len[b] READS as zero whatever the buffer holds,
+ * and is WRITTEN as zero for every t in len[b] .. T-1; an utterance's result is the one it gets alone, unpadded.
+ *
+ * nabu_conv3x3_relu_fwd: y[b,t,f,co] = relu(bias[co] + sum_{kt,kf,ci} w[kt,kf,ci,co] x[b,t+kt-1,f+kf-1,ci]),
+ *   zero "same" padding in both axes; w [3,3,Cin,Cout] (16-byte aligned), bias [Cout].
+ *   plain != 0: no bias and no ReLU (bias may be NULL).
+ *   mask (may be NULL): a tensor of x's shape; the operand is x . [mask > 0] instead of x.
+ *   An implicit GEMM on v_mfma_f32_32x32x2_f32 (a k-ordered fmaf chain per output: taps in (kt, kf) order,
+ *   channels ascending); Cout must be a multiple of 32 (the instruction's N side), Cin is any value >= 1.
+ *   The data gradient of a layer is this call: dx = conv(dy . [y > 0], w') with plain = 1, x = dy, mask = y and
+ *   w' [3,3,Cout,Cin] from nabu_conv3x3_flip_weights (w'[kt,kf,co,ci] = w[2-kt,2-kf,ci,co]).
+ * nabu_conv_tile_t: frames of one output tile (tests place their sizes around it).
+ * nabu_conv3x3_bwd_weights: dw[kt,kf,ci,co] = sum_{b,t,f} x[b,t+kt-1,f+kf-1,ci] (dy . [y > 0])[b,t,f,co] and
+ *   dbias[co] = sum (dy . [y > 0]) over the valid frames, both OVERWRITTEN.  Split-K over (b, time tile) into ws
+ *   (nabu_conv_ws_bytes; its size / ((9 Cin Cout + Cout) * 4) is the number of partial sums), summed in split order by
+ *   a second launch: no float atomics, two calls give the same bits.  dy, y and ws 16-byte aligned.
+ * nabu_maxpool2x2_fwd: [B,T,F,C] -> [B,ceil(T/2),ceil(F/2),C]; a window takes only frames < len[b] and bins < F;
+ *   frames at or past ceil(len[b]/2) are written as zero.  nabu_maxpool2x2_bwd (x: the pool's input, len: ITS
+ *   lengths, dy [B,ceil(T/2),ceil(F/2),C]) sends the gradient to the first maximum in (t, f) order.
+ * nabu_blocks_to_channels_f32: y[n, f, c] = x[n, c F + f] for n < N — the C equal column blocks of a feature vector
+ *   (static, delta, delta-delta of ddelta features) become the input channels of the first convolution.
+ * Argument errors (null pointer, Cout not a multiple of 32, F < 1) are NABU_EINVAL before any launch. */
+int nabu_conv_tile_t(void);
+int nabu_blocks_to_channels_f32(size_t N, int C, int F, const float *x, float *y, nabu_stream_t stream);
+int nabu_conv3x3_relu_fwd(int B, int T, int F, int Cin, int Cout, const float *x, const float *mask,
+                          const int32_t *len, const float *w, const float *bias, int plain, float *y,
+                          nabu_stream_t stream);
+int nabu_conv3x3_flip_weights(int Cin, int Cout, const float *w, float *w_flipped, nabu_stream_t stream);
+size_t nabu_conv_ws_bytes(int B, int T, int F, int Cin, int Cout);
+int nabu_conv3x3_bwd_weights(int B, int T, int F, int Cin, int Cout, const float *x, const float *dy,
+                             const float *y, const int32_t *len, float *dw, float *dbias, void *ws,
+                             size_t ws_bytes, nabu_stream_t stream);
+int nabu_maxpool2x2_fwd(int B, int T, int F, int C, const float *x, const int32_t *len, float *y,
+                        nabu_stream_t stream);
+int nabu_maxpool2x2_bwd(int B, int T, int F, int C, const float *x, const int32_t *len, const float *dy,
+                        float *dx, nabu_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -246,6 +246,14 @@ SIGNATURES = {
     'nabu_feat_ws_bytes': (_sz, [_c.POINTER(FeatDesc)]),
     'nabu_feat_tables_host': (_i, [_c.POINTER(FeatDesc), _vp, _sz]),
     'nabu_feat_compute': (_i, [_c.POINTER(FeatDesc), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'nabu_conv_tile_t': (_i, []),
+    'nabu_blocks_to_channels_f32': (_i, [_sz, _i, _i, _vp, _vp, _vp]),
+    'nabu_conv3x3_relu_fwd': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    'nabu_conv3x3_flip_weights': (_i, [_i, _i, _vp, _vp, _vp]),
+    'nabu_conv_ws_bytes': (_sz, [_i, _i, _i, _i, _i]),
+    'nabu_conv3x3_bwd_weights': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'nabu_maxpool2x2_fwd': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'nabu_maxpool2x2_bwd': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

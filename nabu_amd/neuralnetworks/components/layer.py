@@ -185,6 +185,64 @@ def blstm(inputs, sequence_length, num_units, layer_norm=False, scope=None, out_
     return out
 
 
+def conv_block(inputs, sequence_length, channels, in_channels, scope=None):
+    """One block of the convolutional front end (Zhang, Chan and Jaitly 2017; ESPnet's VGG2L): two 3x3 convolutions
+    with ReLU, then a 2x2 max-pool in ceil mode, as ONE tape node (conv2d.hip).
+
+    inputs [B,T,F,in_channels] channels-last fp32; returns ([B,ceil(T/2),ceil(F/2),channels], SeqLen of ceil(len/2)).
+    Variables: <scope>/conv{0,1}/kernel [3,3,Cin,channels] (scope-default initialiser), conv{0,1}/bias (zeros).
+    Frames past an utterance's length are zero in every tensor of the block (include/nabu_hip.h: the length rule)."""
+    lens = SeqLen.wrap(sequence_length, inputs.device)
+    C = int(channels)
+    if inputs.shape[3] != in_channels:
+        raise ValueError('conv_block: inputs have %d channels, in_channels = %d' % (inputs.shape[3], in_channels))
+    with vs.variable_scope(scope or 'conv_block'):
+        w0 = vs.get_variable('conv0/kernel', [3, 3, int(in_channels), C])
+        b0 = vs.get_variable('conv0/bias', [C], initializer=vs.zeros)
+        w1 = vs.get_variable('conv1/kernel', [3, 3, C, C])
+        b1 = vs.get_variable('conv1/bias', [C], initializer=vs.zeros)
+    variables = (w0, b0, w1, b1)
+    x = inputs if inputs.is_contiguous() else inputs.contiguous()
+    y0 = hip.conv3x3_relu(x, lens.dev, w0.data, b0.data)
+    y1 = hip.conv3x3_relu(y0, lens.dev, w1.data, b1.data)
+    out = hip.maxpool2x2(y1, lens.dev)
+    need_dx = requires_grad(inputs)
+
+    def backward(dout):
+        for v in variables:
+            if v.grad is None:
+                v.grad = torch.zeros_like(v.data)
+        dy1 = hip.maxpool2x2_bwd(y1, lens.dev, dout.reshape(out.shape).contiguous())
+        hip.conv3x3_bwd_weights(y0, dy1, y1, lens.dev, w1.grad, b1.grad)
+        dy0 = hip.conv3x3_bwd_data(dy1, y1, lens.dev, w1.data)
+        hip.conv3x3_bwd_weights(x, dy0, y0, lens.dev, w0.grad, b0.grad)
+        # (features are leaves: the first block computes no data gradient)
+        return [hip.conv3x3_bwd_data(dy0, y0, lens.dev, w0.data) if need_dx else None]
+    record([inputs], [out], backward, params=variables)
+    return out, ops.stacked_lengths(lens, 2)
+
+
+def conv_frontend(inputs, sequence_length, channels, feature_blocks=1):
+    """The VGG-style front end under the BLSTM layers: inputs [B,T,D], whose `feature_blocks` equal column blocks are
+    the input channels, through one conv_block per entry of `channels` (variables frontend/block{i}/...).  Returns
+    ([B,T'',F''*C], lengths) with T'' and the lengths halved (ceil) once per block, column f*C + c — the view of what
+    the last pool wrote.  No value bound is attached: the consumer's packed products take their own maxima."""
+    if inputs.shape[2] % feature_blocks:
+        raise ValueError('feature_blocks = %d does not divide the feature dimension %d' % (feature_blocks, inputs.shape[2]))
+    x = hip.blocks_to_channels(inputs if inputs.is_contiguous() else inputs.contiguous(), feature_blocks)
+    if requires_grad(inputs):
+        raise Exception('conv_frontend: the features depend on a parameter; the channel split computes no input gradient')
+    lengths, cin = sequence_length, feature_blocks
+    with vs.variable_scope('frontend'):
+        for i, c in enumerate(channels):
+            x, lengths = conv_block(x, lengths, c, cin, scope='block%d' % i)
+            cin = c
+    B, T2, F2, C = x.shape
+    out = x.view(B, T2, F2 * C)
+    record([x], [out], lambda dout: [dout.reshape(B, T2, F2, C)])
+    return out, lengths
+
+
 def pblstm(inputs, sequence_length, num_units, num_steps=2, layer_norm=False, scope=None):
     """A pyramidal BLSTM layer (reference layer.py:53-94): blstm, then stack
     ``num_steps`` consecutive output frames.  Returns (outputs, new lengths)."""

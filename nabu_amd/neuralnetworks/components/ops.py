@@ -94,6 +94,11 @@ def pyramid_stack(inputs, sequence_lengths, numsteps, axis=2, scope=None):
         d = dout.reshape(B, Tp, F)
         return [d if Tp == T else hip.unpad_time(d, T)]
     record([inputs], [outputs], backward)
+    return outputs, stacked_lengths(sequence_lengths, numsteps)
+
+
+def stacked_lengths(sequence_lengths, numsteps):
+    """ceil(len / numsteps) as a SeqLen (pyramid_stack, and the 2x2 pool of layer.conv_block)"""
     lens = SeqLen.wrap(sequence_lengths)
     # (a length vector is immutable: the stacked lengths of a SeqLen OBJECT that comes round again — a batch kept on the
     # device, the layers of one step sharing it — are derived once)
@@ -102,7 +107,7 @@ def pyramid_stack(inputs, sequence_lengths, numsteps, axis=2, scope=None):
         new_host = -(-lens.host // numsteps)
         # the device copy is derived on the device: an upload here would block the host on the stream
         cache[numsteps] = SeqLen(new_host.astype(np.int32), dev_tensor=hip.ceil_div_i32(lens.dev, numsteps))
-    return outputs, cache[numsteps]
+    return cache[numsteps]
 
 
 def dense_sequence_to_sparse(sequences, sequence_lengths):

@@ -3,12 +3,17 @@ nabu/neuralnetworks/models/ed_encoders/dblstm.py:11-59); one C-ABI call per laye
 from nabu_amd import variables as vs
 from nabu_amd.neuralnetworks.components import layer, ops
 from nabu_amd.neuralnetworks.models.ed_encoders import ed_encoder
-from nabu_amd.neuralnetworks.models.ed_encoders.listener import augment, layer_norm_key
+from nabu_amd.neuralnetworks.models.ed_encoders.listener import augment, conv_channels_key, frontend, layer_norm_key
 
 
 class DBLSTM(ed_encoder.EDEncoder):
-    """cfg keys: num_layers, num_units, input_noise, dropout (keep probability), gemm_precision, layer_norm and the
-    SpecAugment keys (see listener.py)"""
+    """cfg keys: num_layers, num_units, input_noise, dropout (keep probability), gemm_precision, layer_norm, the
+    SpecAugment keys and conv_channels (see listener.py).  With conv_channels the layers run at a quarter (two blocks)
+    of the frame rate and the returned lengths are the pooled ones."""
+
+    def __init__(self, conf, constraint, name=None):
+        super(DBLSTM, self).__init__(conf, constraint, name)
+        conv_channels_key(self.conf)
 
     def encode(self, inputs, input_seq_length, is_training):
         layer.GEMM_PRECISION[0] = self.conf.get('gemm_precision', 'default')
@@ -16,14 +21,17 @@ class DBLSTM(ed_encoder.EDEncoder):
         keep = float(self.conf['dropout'])
         units = int(self.conf['num_units'])
         layer_norm = layer_norm_key(self.conf)
-        encoded = {}
+        encoded, encoded_seq_length = {}, dict(input_seq_length)
         for name, x in inputs.items():
             with vs.variable_scope(name):
                 x, lengths = augment(self.conf, x, input_seq_length[name], is_training)   # dblstm.py:37-42
+                if conv_channels_key(self.conf):
+                    x, lengths = frontend(self.conf, x, lengths)
+                    encoded_seq_length[name] = lengths
                 for index in range(int(self.conf['num_layers'])):          # dblstm.py:44-54
                     x = layer.blstm(inputs=x, sequence_length=lengths, num_units=units,
                                     layer_norm=layer_norm, scope='layer%d' % index)
                     if is_training and keep < 1:
                         x = ops.seq_dropout(x, keep, ops.global_rng())
                 encoded[name] = x
-        return encoded, dict(input_seq_length)
+        return encoded, encoded_seq_length

@@ -119,6 +119,9 @@ class DNN(ed_encoder.EDEncoder):
         if found:
             raise Exception('DNN encoder: the SpecAugment keys (%s) are not supported: the targets are alignments, one '
                             'per frame, and the augmentation moves and masks frames' % ', '.join(found))
+        if 'conv_channels' in self.conf:
+            raise Exception('DNN encoder: conv_channels is not supported: the targets are alignments, one per frame, and '
+                            'the convolutional front end pools the frames')
 
     def encode(self, inputs, input_seq_length, is_training):
         precision = self.conf.get('gemm_precision', 'default')

@@ -53,6 +53,37 @@ def spec_augment_keys(conf):
         freq_mask_width=integer('freq_mask_width', 0), feature_blocks=integer('feature_blocks', 1, low=1))
 
 
+CONV_MAX_BLOCKS = 3
+
+
+def conv_channels_key(conf):
+    """the `conv_channels` cfg key (a build addition: absent from the defaults files, no front end when absent): the
+    output channels of the convolutional front end's blocks, one entry per block (1..3), each a positive multiple of 32
+    — `conv_channels = 64 128` is ESPnet's VGG2L.  Returns a tuple, () when the key is absent."""
+    if 'conv_channels' not in conf:
+        return ()
+    text = str(conf['conv_channels'])
+    try:
+        channels = tuple(int(tok) for tok in text.split())
+    except ValueError:
+        raise ValueError('conv_channels must be a list of integers, got %r' % text)
+    if not 1 <= len(channels) <= CONV_MAX_BLOCKS:
+        raise ValueError('conv_channels must name 1..%d blocks, got %r' % (CONV_MAX_BLOCKS, text))
+    for c in channels:
+        if c <= 0 or c % 32:
+            raise ValueError('conv_channels: %d is not a positive multiple of 32 (the matrix instruction\'s N side)' % c)
+    return channels
+
+
+def frontend(conf, x, lengths):
+    """the convolutional front end (layer.conv_frontend) when `conv_channels` asks for one: after augment(), before
+    layer0; the lengths every later layer sees are the pooled ones"""
+    channels = conv_channels_key(conf)
+    if not channels:
+        return x, lengths
+    return layer.conv_frontend(x, lengths, channels, spec_augment_keys(conf).feature_blocks)
+
+
 def augment(conf, x, lengths, is_training):
     """the encoders' input regularisation: input_noise, then SpecAugment (its own RngState.next(), after the noise's, so
     that a configuration without the new keys keeps its offsets); the lengths come back as the SeqLen the kernel read"""
@@ -70,7 +101,12 @@ class Listener(ed_encoder.EDEncoder):
     """cfg keys: num_layers (pyramidal layers), num_units, pyramid_steps, input_noise, dropout (keep
     probability), gemm_precision (build addition), layer_norm (build addition, default False: every layer's cells
     normalise their gates and state — layer.blstm(layer_norm=True)), the SpecAugment keys (build additions, default
-    off: spec_augment_keys)"""
+    off: spec_augment_keys), conv_channels (build addition, default absent: the convolutional front end under layer0,
+    conv_channels_key; its input channels are the feature_blocks column blocks)"""
+
+    def __init__(self, conf, constraint, name=None):
+        super(Listener, self).__init__(conf, constraint, name)
+        conv_channels_key(self.conf)
 
     def _regularise(self, x, is_training):
         keep = float(self.conf['dropout'])
@@ -78,6 +114,7 @@ class Listener(ed_encoder.EDEncoder):
 
     def _encode_one(self, x, lengths, is_training):
         x, lengths = augment(self.conf, x, lengths, is_training)
+        x, lengths = frontend(self.conf, x, lengths)
         units, depth = int(self.conf['num_units']), int(self.conf['num_layers'])
         layer_norm = layer_norm_key(self.conf)
         for index in range(depth):                                      # listener.py:49-59

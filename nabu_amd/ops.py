@@ -1050,6 +1050,86 @@ def log_softmax_prior(x, len_dev, logprior):
     return out
 
 
+def conv_tile_t():
+    """frames of one output tile of the convolution kernels (nabu_conv_tile_t)"""
+    return _hip.lib().nabu_conv_tile_t()
+
+
+def blocks_to_channels(x, blocks):
+    """x [B,T,D] whose columns are `blocks` equal blocks -> [B,T,D/blocks,blocks] channels-last (a view for blocks = 1)"""
+    B, T, D = x.shape
+    F = D // blocks
+    if blocks == 1:
+        return x.view(B, T, F, 1)
+    y = torch.empty((B, T, F, blocks), dtype=torch.float32, device=x.device)
+    check(_hip.lib().nabu_blocks_to_channels_f32(B * T, blocks, F, ptr(_f32(x, 'x')), ptr(y), stream()),
+          'nabu_blocks_to_channels_f32')
+    return y
+
+
+def conv3x3_relu(x, len_dev, w, bias=None, mask=None, plain=False):
+    """relu(conv3x3(x) + bias) of x [B,T,F,Cin] channels-last with w [3,3,Cin,Cout], "same" padding, frames >= len zero
+    (nabu_conv3x3_relu_fwd).  plain: no bias, no ReLU; mask: the operand is x . [mask > 0]."""
+    B, T, F, Cin = x.shape
+    Cout = w.shape[3]
+    if tuple(w.shape) != (3, 3, Cin, Cout):
+        raise _hip.NabuHipError('conv3x3_relu: w %s does not fit x %s' % (tuple(w.shape), tuple(x.shape)))
+    if mask is not None and mask.shape != x.shape:
+        raise _hip.NabuHipError('conv3x3_relu: mask %s, x %s' % (tuple(mask.shape), tuple(x.shape)))
+    y = torch.empty((B, T, F, Cout), dtype=torch.float32, device=x.device)
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (Cout,)):
+        raise _hip.NabuHipError('conv3x3_relu: bias must be float32 [%d], got %s %s' % (Cout, bias.dtype, tuple(bias.shape)))
+    check(_hip.lib().nabu_conv3x3_relu_fwd(B, T, F, Cin, Cout, ptr(_f32(x, 'x')), ptr(mask if mask is None else _f32(mask, 'mask')),
+                                           ptr(len_dev), ptr(_f32(w, 'w')), ptr(bias), int(plain), ptr(y), stream()),
+          'nabu_conv3x3_relu_fwd')
+    return y
+
+
+def conv3x3_flip_weights(w):
+    """w' [3,3,Cout,Cin] with w'[kt,kf,co,ci] = w[2-kt,2-kf,ci,co]: the weights of the data-gradient convolution"""
+    Cin, Cout = w.shape[2], w.shape[3]
+    wf = torch.empty((3, 3, Cout, Cin), dtype=torch.float32, device=w.device)
+    check(_hip.lib().nabu_conv3x3_flip_weights(Cin, Cout, ptr(_f32(w, 'w')), ptr(wf), stream()),
+          'nabu_conv3x3_flip_weights')
+    return wf
+
+
+def conv3x3_bwd_data(dy, y, len_dev, w):
+    """dx = conv(dy . [y > 0], w') of y = conv3x3_relu(x, w): the forward kernel in its masked-operand mode"""
+    return conv3x3_relu(dy, len_dev, conv3x3_flip_weights(w), mask=y, plain=True)
+
+
+def conv3x3_bwd_weights(x, dy, y, len_dev, dw, dbias):
+    """dw [3,3,Cin,Cout] and dbias [Cout] of y = conv3x3_relu(x, w, bias), overwritten (nabu_conv3x3_bwd_weights)"""
+    B, T, F, Cin = x.shape
+    Cout = y.shape[3]
+    L = _hip.lib()
+    ws_bytes = L.nabu_conv_ws_bytes(B, T, F, Cin, Cout)
+    ws = Workspace.get(ws_bytes, x.device, 'conv')
+    check(L.nabu_conv3x3_bwd_weights(B, T, F, Cin, Cout, ptr(_f32(x, 'x')), ptr(_f32(dy, 'dy')), ptr(_f32(y, 'y')), ptr(len_dev),
+                                     ptr(_f32(dw, 'dw')), ptr(_f32(dbias, 'dbias')), ptr(ws), ws_bytes, stream()),
+          'nabu_conv3x3_bwd_weights')
+    return dw, dbias
+
+
+def maxpool2x2(x, len_dev):
+    """[B,T,F,C] -> [B,ceil(T/2),ceil(F/2),C], windows over frames < len and bins < F only (nabu_maxpool2x2_fwd)"""
+    B, T, F, C = x.shape
+    y = torch.empty((B, (T + 1) // 2, (F + 1) // 2, C), dtype=torch.float32, device=x.device)
+    check(_hip.lib().nabu_maxpool2x2_fwd(B, T, F, C, ptr(_f32(x, 'x')), ptr(len_dev), ptr(y), stream()),
+          'nabu_maxpool2x2_fwd')
+    return y
+
+
+def maxpool2x2_bwd(x, len_dev, dy):
+    """gradient of maxpool2x2 at its input x: dy goes to the first maximum of each window in (t, f) order"""
+    B, T, F, C = x.shape
+    dx = torch.empty_like(x)
+    check(_hip.lib().nabu_maxpool2x2_bwd(B, T, F, C, ptr(_f32(x, 'x')), ptr(len_dev), ptr(_f32(dy, 'dy')), ptr(dx), stream()),
+          'nabu_maxpool2x2_bwd')
+    return dx
+
+
 def ceil_div_i32(x, d):
     out = torch.empty_like(x)
     check(_hip.lib().nabu_ceil_div_i32(x.numel(), ptr(x), int(d), ptr(out), stream()), 'nabu_ceil_div_i32')
