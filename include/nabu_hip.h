@@ -1485,6 +1485,39 @@ int nabu_maxpool2x2_fwd(int B, int T, int F, int C, const float *x, const int32_
 int nabu_maxpool2x2_bwd(int B, int T, int F, int C, const float *x, const int32_t *len, const float *dy,
                         float *dx, nabu_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Self-attention encoder (self_attn.hip): multi-head scaled dot-product attention of a padded batch over all pairs
+ * of frames of an utterance (Vaswani et al. 2017), fp32 in and out on v_mfma_f32_32x32x2_f32; the T x T score matrix
+ * is never written to memory.
+ * qkv [B, T, 3 D] float32 with row stride ld >= 3 D (ld % 4 == 0, 16-byte aligned): Q, K and V are its three D-wide
+ * column blocks, head h is columns h dk .. (h+1) dk of each, D = H dk.  dk is 32 or 64 and D <= 1024; anything else
+ * is NABU_EINVAL with a message, before any launch, like a null pointer or ld < 3 D.  len [B] int32 (values outside
+ * 0..T are clamped).
+ * THE LENGTH RULE: keys at or past len[b] do not exist, whatever the buffer holds; rows t >= len[b] of every output
+ * (o, lse, dqkv) are written as +0.0; len[b] = 0 writes zeros and no NaN; the tiles walked for utterance b depend on
+ * len[b] only, never on T, so an utterance's result is the bits it gets alone, unpadded.
+ *
+ * nabu_self_attn_fwd: o[b,t,h,:] = sum_{j < len[b]} softmax_j(q . k_j / sqrt(dk)) v_j into o [B, T, D] (contiguous,
+ *   16-byte aligned) and lse[b,h,t] = log sum_j exp(q . k_j / sqrt(dk)) into lse [B, H, T].  Operation order per query:
+ *   a d-ordered fmaf chain of dk terms per score, one multiply by fl(1/sqrt(dk)); keys in tiles of
+ *   nabu_self_attn_tile_k() = 32 with an online softmax (running maximum, one rescale of the sums per tile); one
+ *   division by the sum at the end.  A workgroup owns nabu_self_attn_tile_q() = 128 queries of one (b, h).
+ * nabu_self_attn_bwd: dqkv [B, T, 3 D] at the same ld from qkv, o, lse (the forward call's), do [B, T, D] and len;
+ *   the columns ld > 3 D leaves over are not touched.  Probabilities are recomputed as exp(s - lse);
+ *   delta = rowsum(do . o), dV = P^T dO, dS = P . (dO V^T - delta), dQ = dS K / sqrt(dk), dK = dS^T Q / sqrt(dk).
+ *   Two launches (key tiles owned: dK, dV; query tiles owned: dQ), no float atomics, no workspace: two calls give
+ *   the same bits.
+ * nabu_add_positions_f32: x[b,t,:] += pe[t,:] for t < len[b]; x [B, T, D], pe [>= T, D] (the encoder's sinusoidal
+ *   table).  Its gradient is the identity. */
+int nabu_self_attn_tile_q(void);
+int nabu_self_attn_tile_k(void);
+int nabu_self_attn_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len, float *o,
+                       float *lse, nabu_stream_t stream);
+int nabu_self_attn_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o, const float *lse,
+                       const float *d_o, const int32_t *len, float *dqkv, nabu_stream_t stream);
+int nabu_add_positions_f32(int B, int T, int D, float *x, const float *pe, const int32_t *len,
+                           nabu_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -254,6 +254,11 @@ SIGNATURES = {
     'nabu_conv3x3_bwd_weights': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'nabu_maxpool2x2_fwd': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'nabu_maxpool2x2_bwd': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'nabu_self_attn_tile_q': (_i, []),
+    'nabu_self_attn_tile_k': (_i, []),
+    'nabu_self_attn_fwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    'nabu_self_attn_bwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'nabu_add_positions_f32': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

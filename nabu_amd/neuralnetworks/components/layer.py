@@ -243,6 +243,82 @@ def conv_frontend(inputs, sequence_length, channels, feature_blocks=1):
     return out, lengths
 
 
+LN_EPS = 1e-5       # variance epsilon of the self-attention block's layer norms (moments per frame over D)
+
+
+def self_attention_block(inputs, sequence_length, num_heads, ff_units, keep=1.0, scope=None):
+    """One pre-norm self-attention block (Vaswani et al. 2017 with the norm in front, as ESPnet's and Lingvo's encoders
+    run it) as ONE tape node:
+        a = LN(h); qkv = a Wqkv + b (one product to 3D columns); c = self_attn(qkv); h = h + drop(c Wo + bo)
+        f = LN(h); h = h + drop(relu(f W1 + b1) W2 + b2)
+    inputs [B,T,D] fp32; the attention (self_attn.hip) sees the frames < sequence_length of each row only.  The products
+    run at GEMM_PRECISION (nabu_gemm_ex falls back to exact fp32 where the 16-bit kernels do not take a shape), the
+    attention itself is exact fp32.  keep: dropout keep probability, applied under a tape only; no dropout on the
+    attention probabilities.  Frames past a length carry finite values that no valid frame reads; the encoder masks them.
+    Variables: <scope>/{ln1,ln2}/{gamma,beta} [D], attention/{qkv,out}/{weights,biases}, ffn/{fc1,fc2}/{weights,biases}."""
+    lens = SeqLen.wrap(sequence_length, inputs.device)
+    B, T, D = inputs.shape
+    H, FF, N = int(num_heads), int(ff_units), B * T
+    if D % H or D // H not in (32, 64):
+        raise ValueError('self_attention_block: %d units in %d heads; the head width must be 32 or 64' % (D, H))
+    with vs.variable_scope(scope or 'self_attention_block'):
+        norms = [(vs.get_variable('%s/gamma' % n, [D], initializer=vs.ones), vs.get_variable('%s/beta' % n, [D], initializer=vs.zeros))
+                 for n in ('ln1', 'ln2')]
+        dense = [(vs.get_variable('%s/weights' % n, [i, o]), vs.get_variable('%s/biases' % n, [o], initializer=vs.zeros))
+                 for n, i, o in (('attention/qkv', D, 3 * D), ('attention/out', D, D), ('ffn/fc1', D, FF), ('ffn/fc2', FF, D))]
+    variables = tuple(v for pair in norms + dense for v in pair)
+    precision = GEMM_PRECISION[0]
+    training = Tape.current is not None
+    rng = [ops.global_rng().next() for _ in range(2)] if training and keep < 1 else None
+
+    def linear(x, i, width):
+        W, b = dense[i]
+        return hip.gemm(x, W.data, torch.empty((N, width), dtype=torch.float32, device=x.device), bias=b.data, precision=precision)
+
+    def drop(x, i):
+        return hip.dropout(x, keep, *rng[i]) if rng else x
+
+    x = (inputs if inputs.is_contiguous() else inputs.contiguous()).view(N, D)
+    a, mean1, rstd1 = hip.layer_norm_fwd(x, norms[0][0].data, norms[0][1].data, LN_EPS)
+    qkv = linear(a, 0, 3 * D).view(B, T, 3 * D)
+    c, lse = hip.self_attn_fwd(qkv, lens.dev, H)
+    h1 = hip.axpy_(drop(linear(c.view(N, D), 1, D), 0), x)
+    f, mean2, rstd2 = hip.layer_norm_fwd(h1, norms[1][0].data, norms[1][1].data, LN_EPS)
+    r = hip.relu(linear(f, 2, FF))
+    out = hip.axpy_(drop(linear(r, 3, D), 1), h1).view(B, T, D)
+    need_dx = requires_grad(inputs)
+
+    def backward(dout):
+        for v in variables:
+            if v.grad is None:
+                v.grad = torch.zeros_like(v.data)
+
+        def linear_bwd(x, dy, i):
+            """gradients of dense[i] (overwritten) at input x; returns dx"""
+            W, b = dense[i]
+            hip.gemm(x, dy, W.grad, trans_a=True, precision=precision)
+            hip.colsum(dy, b.grad)
+            return hip.gemm(dy, W.data, torch.empty_like(x), trans_b=True, precision=precision)
+
+        def norm_bwd(x, dy, i, mean, rstd):
+            dx, dgp, dbp = hip.layer_norm_bwd(x, norms[i][0].data, dy, mean, rstd)
+            hip.colsum(dgp, norms[i][0].grad)
+            hip.colsum(dbp, norms[i][1].grad)
+            return dx
+        dout = dout.reshape(N, D).contiguous()
+        du = hip.relu_bwd(r, linear_bwd(r, drop(dout, 1), 3))
+        dh1 = hip.axpy_(norm_bwd(h1, linear_bwd(f, du, 2), 1, mean2, rstd2), dout)
+        dc = linear_bwd(c.view(N, D), drop(dh1, 0), 1)
+        dqkv = hip.self_attn_bwd(qkv, c, lse, dc.view(B, T, D), lens.dev, H)
+        da = linear_bwd(a, dqkv.reshape(N, 3 * D), 0)
+        if not need_dx:                                  # (the norm's own gradients are still due)
+            norm_bwd(x, da, 0, mean1, rstd1)
+            return [None]
+        return [hip.axpy_(norm_bwd(x, da, 0, mean1, rstd1), dh1).view(B, T, D)]
+    record([inputs], [out], backward, params=variables)
+    return out
+
+
 def pblstm(inputs, sequence_length, num_units, num_steps=2, layer_norm=False, scope=None):
     """A pyramidal BLSTM layer (reference layer.py:53-94): blstm, then stack
     ``num_steps`` consecutive output frames.  Returns (outputs, new lengths)."""

@@ -6,4 +6,5 @@ factory = Registry('encoder', {
     'listener': _PKG + 'listener:Listener',
     'dblstm': _PKG + 'dblstm:DBLSTM',
     'dnn': _PKG + 'dnn:DNN',
+    'transformer': _PKG + 'transformer:Transformer',
 }, outside=('dummy_encoder', 'hotstart_encoder'))

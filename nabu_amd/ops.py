@@ -1130,6 +1130,58 @@ def maxpool2x2_bwd(x, len_dev, dy):
     return dx
 
 
+def self_attn_tiles():
+    """(rows a workgroup owns, rows of a streamed tile) of the self-attention kernels; tests place their sizes around them"""
+    return _hip.lib().nabu_self_attn_tile_q(), _hip.lib().nabu_self_attn_tile_k()
+
+
+def _attn_shape(qkv, heads):
+    """(B, T, H, dk, ld) of qkv [B,T,3D]: a tensor or a view whose rows are ld >= 3D apart (the batch rows T*ld)"""
+    B, T, W = qkv.shape
+    # (the stride of an axis of size 1 says nothing)
+    ld = qkv.stride(1) if T > 1 else qkv.stride(0) if B > 1 else W
+    if _f32(qkv, 'qkv').stride(2) != 1 or (B > 1 and qkv.stride(0) != T * ld) or not qkv.is_cuda:
+        raise _hip.NabuHipError('self_attn: qkv must be a GPU tensor [B,T,3D] with unit column stride and evenly spaced '
+                                'rows, got strides %s' % (tuple(qkv.stride()),))
+    if heads < 1 or W % (3 * heads):
+        raise _hip.NabuHipError('self_attn: %d columns are not 3 x %d heads of equal width' % (W, heads))
+    return B, T, int(heads), W // (3 * heads), ld
+
+
+def self_attn_fwd(qkv, len_dev, heads):
+    """(o [B,T,D], lse [B,H,T]) of multi-head self-attention over the frames < len of each row (nabu_self_attn_fwd)"""
+    B, T, H, dk, ld = _attn_shape(qkv, heads)
+    o = torch.empty((B, T, H * dk), dtype=torch.float32, device=qkv.device)
+    lse = torch.empty((B, H, T), dtype=torch.float32, device=qkv.device)
+    check(_hip.lib().nabu_self_attn_fwd(B, T, H, dk, qkv.data_ptr(), ld, ptr(len_dev), ptr(o), ptr(lse), stream()),
+          'nabu_self_attn_fwd')
+    return o, lse
+
+
+def self_attn_bwd(qkv, o, lse, do, len_dev, heads):
+    """dqkv, of qkv's shape and strides, from the forward call's o and lse and do [B,T,D] (nabu_self_attn_bwd)"""
+    B, T, H, dk, ld = _attn_shape(qkv, heads)
+    if tuple(do.shape) != tuple(o.shape) or tuple(o.shape) != (B, T, H * dk) or tuple(lse.shape) != (B, H, T):
+        raise _hip.NabuHipError('self_attn_bwd: o %s, do %s, lse %s do not fit qkv %s' %
+                                (tuple(o.shape), tuple(do.shape), tuple(lse.shape), tuple(qkv.shape)))
+    # (the columns past 3D of a strided view belong to nobody: zeros, so that the buffer is defined)
+    buf = torch.empty((B, T, ld), dtype=torch.float32, device=qkv.device) if ld == 3 * H * dk else \
+        torch.zeros((B, T, ld), dtype=torch.float32, device=qkv.device)
+    check(_hip.lib().nabu_self_attn_bwd(B, T, H, dk, qkv.data_ptr(), ld, ptr(_f32(o, 'o')), ptr(_f32(lse, 'lse')),
+                                        ptr(_f32(do, 'do')), ptr(len_dev), ptr(buf), stream()), 'nabu_self_attn_bwd')
+    return buf[:, :, :3 * H * dk]
+
+
+def add_positions_(x, pe, len_dev):
+    """x[b,t,:] += pe[t,:] for t < len[b], in place (nabu_add_positions_f32); pe [>= T, D]"""
+    B, T, D = x.shape
+    if pe.shape[0] < T or pe.shape[1] != D:
+        raise _hip.NabuHipError('add_positions_: table %s does not cover x %s' % (tuple(pe.shape), tuple(x.shape)))
+    check(_hip.lib().nabu_add_positions_f32(B, T, D, ptr(_f32(x, 'x')), ptr(_f32(pe, 'pe')), ptr(len_dev), stream()),
+          'nabu_add_positions_f32')
+    return x
+
+
 def ceil_div_i32(x, d):
     out = torch.empty_like(x)
     check(_hip.lib().nabu_ceil_div_i32(x.numel(), ptr(x), int(d), ptr(out), stream()), 'nabu_ceil_div_i32')

@@ -1,0 +1,112 @@
+"""The self-attention kernels (self_attn.hip) against the best alternative a user of this stack has today, at B 32, H 4,
+dk 64 and T 250 (the transformer_ctc recipe behind its front end) and T 1000 (without it):
+
+  forward   nabu_self_attn_fwd against torch.nn.functional.scaled_dot_product_attention in fp32 on the same operands
+            (given as contiguous [B,H,T,dk] tensors), the padding expressed as its boolean key mask
+  backward  nabu_self_attn_bwd (both launches) against torch.autograd.grad of that call (graph retained, backward only)
+  step      one training step of the transformer_ctc recipe with feature_blocks = 3 at cfg1's size (8 x 200 x 123) against
+            vgg_dblstm_ctc on the same batches — for information, no bar
+
+The bar, forward and backward: no slower.  Lengths are drawn uniformly from T/2 .. T (one row at T).
+Protocol of the other tools: warm-up, then medians of --rounds rounds of --calls calls between device events, the two
+sides of a comparison alternating round by round in the same run; the spread of the round times is reported with them.
+Prints one JSON line (and writes it to --out).
+
+    python tools/self_attn_bench.py [--rounds 5] [--calls 200] [--out profiles/self_attn.json]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from nabu_amd import ops as hip, recipes                                      # noqa: E402
+from nabu_amd.processing.synthetic import SyntheticData                       # noqa: E402
+from tools.conv_frontend_bench import rounds_ms                               # noqa: E402
+
+B, H, DK = 32, 4, 64
+
+
+def attn_bench(T, rounds, calls):
+    D = H * DK
+    g = torch.Generator(device='cuda').manual_seed(1)
+    qkv = torch.randn((B, T, 3 * D), device='cuda', generator=g)
+    do = torch.randn((B, T, D), device='cuda', generator=g)
+    host_lens = np.random.default_rng(1).integers(T // 2, T + 1, B).astype(np.int32)
+    host_lens[0] = T
+    lens = torch.from_numpy(host_lens).cuda()
+    q, k, v = (t.contiguous().requires_grad_() for t in qkv.view(B, T, 3, H, DK).permute(2, 0, 3, 1, 4))
+    valid = torch.arange(T, device='cuda')[None, :] < lens[:, None]          # [B,T]
+    mask = valid[:, None, None, :]
+    sdpa = torch.nn.functional.scaled_dot_product_attention
+    ref = sdpa(q, k, v, attn_mask=mask)
+    do_ref = (do * valid[:, :, None]).view(B, T, H, DK).transpose(1, 2).contiguous()       # (no gradient enters a padding row)
+    o, lse = hip.self_attn_fwd(qkv, lens, H)
+    dqkv = hip.self_attn_bwd(qkv, o, lse, do, lens, H)
+    grads = torch.autograd.grad(ref, (q, k, v), do_ref, retain_graph=True)
+    want = ref.detach().transpose(1, 2).reshape(B, T, D) * valid[:, :, None]
+    worst_fwd = float((want - o).abs().max())
+    want = torch.stack([t.transpose(1, 2).reshape(B, T, D) for t in grads], dim=2).reshape(B, T, 3 * D)
+    worst_bwd = float((want - dqkv).abs().max())
+    (f, fs), (rf, rfs), (bw, bs), (rb, rbs) = rounds_ms(
+        [lambda: hip.self_attn_fwd(qkv, lens, H), lambda: sdpa(q, k, v, attn_mask=mask),
+         lambda: hip.self_attn_bwd(qkv, o, lse, do, lens, H),
+         lambda: torch.autograd.grad(ref, (q, k, v), do_ref, retain_graph=True)], rounds, calls)
+    pairs = float((host_lens.astype(np.float64) ** 2).sum()) * H
+
+    def r(x):
+        return round(x, 4)
+    return {'shape': [B, T, H, DK], 'fwd_ms': r(f), 'fwd_spread': [r(x) for x in fs], 'sdpa_fwd_ms': r(rf),
+            'sdpa_fwd_spread': [r(x) for x in rfs], 'fwd_over_sdpa': round(f / rf, 3), 'fwd_bar': 'met' if f <= rf else 'missed',
+            'fwd_tflops': round(4 * pairs * DK / f / 1e9, 1), 'bwd_ms': r(bw), 'bwd_spread': [r(x) for x in bs],
+            'sdpa_bwd_ms': r(rb), 'sdpa_bwd_spread': [r(x) for x in rbs], 'bwd_over_sdpa': round(bw / rb, 3),
+            'bwd_bar': 'met' if bw <= rb else 'missed', 'bwd_tflops_useful': round(10 * pairs * DK / bw / 1e9, 1),
+            'max_abs_diff_fwd': worst_fwd, 'max_abs_diff_bwd': worst_bwd}
+
+
+def step_bench(rounds, calls):
+    from nabu_amd.neuralnetworks.trainers import trainer_factory
+    data = SyntheticData(8, 200, 123, min_frames=120, min_labels=5, max_labels=20, time_reduction=4, seed=2234)
+    trainers = []
+    for recipe in ('transformer_ctc', 'vgg_dblstm_ctc'):
+        mc, tc, ec = recipes.load_recipe(recipe, **{'encoder.feature_blocks': 3})
+        trainers.append(trainer_factory.factory('standard')(conf=tc, dataconf=data, modelconf=mc, evaluatorconf=ec,
+                                                            expdir=None, server=None, task_index=0))
+    batches = [[tr.to_device(data.batch(i)) for i in range(4)] for tr in trainers]
+    count = [0, 0]
+
+    def stepper(k):
+        def fn():
+            trainers[k].step(batches[k][count[k] % 4])
+            count[k] += 1
+        return fn
+    (tf, ts), (vgg, vs_) = rounds_ms([stepper(0), stepper(1)], rounds, calls)
+    return {'shape': [8, 200, 123], 'transformer_ctc_step_ms': round(tf, 3), 'transformer_spread': [round(v, 3) for v in ts],
+            'vgg_dblstm_step_ms': round(vgg, 3), 'vgg_spread': [round(v, 3) for v in vs_],
+            'transformer_over_vgg_dblstm': round(tf / vgg, 3)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--rounds', type=int, default=5)
+    ap.add_argument('--calls', type=int, default=200)
+    ap.add_argument('--out', default=None, help='also write the JSON line to this file')
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), 'self_attn_bench needs a GPU'
+    torch.cuda.set_device(0)
+    res = {'bench': 'self_attn', 'rounds': args.rounds, 'calls': args.calls, 'device': torch.cuda.get_device_name(0),
+           'attention': [attn_bench(T, args.rounds, args.calls) for T in (250, 1000)],
+           'step': step_bench(args.rounds, args.calls)}
+    line = json.dumps(res)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as fid:
+            fid.write(line + '\n')
+
+
+if __name__ == '__main__':
+    main()
