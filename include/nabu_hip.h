@@ -1518,6 +1518,45 @@ int nabu_self_attn_bwd(int B, int T, int H, int dk, const float *qkv, int ld, co
 int nabu_add_positions_f32(int B, int T, int D, float *x, const float *pe, const int32_t *len,
                            nabu_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Conformer encoder (conv_module.hip): the core of the block's convolution module (Gulati et al. 2020) between its two
+ * pointwise products, on a ragged padded batch, fp32.  u [B, T, 2 D] with row stride ld >= 2 D (ld % 4 == 0, 16-byte
+ * aligned) is the first pointwise product's output; w [K, D] and bw [D] are the depthwise taps and bias, gamma and
+ * beta [D] the norm's parameters.  For t < len[b]:
+ *     g[t,c] = u[t,c] sigmoid(u[t,D+c])                          GLU; g[t] = 0 for t < 0 and t >= len[b]
+ *     z[t,c] = bw[c] + sum_{k<K} w[k,c] g[t + k - (K-1)/2, c]    "same" depthwise convolution along time
+ *     n[t,:] = gamma (z[t,:] - mean_c z[t,:]) rstd[t] + beta     layer norm per frame over the D channels
+ *     y[t,c] = n[t,c] sigmoid(n[t,c])                            Swish
+ * The norm is a layer norm per frame (WeNet's cnn_module_norm: layer_norm), not a batch norm: batch statistics over a
+ * padded batch would make an utterance's result depend on its neighbours.
+ * D is a multiple of 64, at most 1024; K is odd, 3..31; anything else is NABU_EINVAL with a message, before any launch,
+ * like a null pointer, a misaligned u, ld < 2 D or ld % 4 != 0.  len [B] int32 (values outside 0..T are clamped).
+ * THE LENGTH RULE: frames at or past len[b] are never read (they may hold anything); rows t >= len[b] of y, mean, rstd
+ * and du are written as +0.0; the tiles walked for utterance b depend on len[b] only, so an utterance's result is the
+ * bits it gets alone, unpadded.
+ *
+ * nabu_conv_module_fwd: y [B, T, D] contiguous, mean and rstd [B, T] (of z; kept for the backward call).  One launch;
+ *   a workgroup owns nabu_conv_module_tile_t() = 32 frames of one utterance and all channels.  Operation order: z is a
+ *   k-ordered fmaf chain that starts at bw; mean and variance (biased, two passes) are a chain of D / 64 terms per lane
+ *   and a fixed butterfly; rstd = 1 / sqrt(var + eps); both sigmoids are 1 / (1 + expf(-x)).
+ * nabu_conv_module_bwd: from u, the parameters, the forward call's mean and rstd, and dy [B, T, D]:
+ *   du [B, T, 2 D] at u's ld (the columns past 2 D are not touched), and the partial sums
+ *   part_ln [parts, 3 D] = [dgamma | dbeta | dbw] and part_dw [parts, K D], parts = nabu_conv_module_parts(B, T) (one
+ *   row per workgroup; reduce them with nabu_colsum_f32).  dz [B, T, D] is workspace, the only intermediate in memory.
+ *   Two launches, no float atomics: two calls give the same bits.
+ * nabu_swish_f32: y = x sigmoid(x); nabu_swish_bwd_f32: dx = dy s (1 + x (1 - s)), s = sigmoid(x), from x (not y);
+ *   in place allowed.  (elementwise.hip; the feed-forward layers of the block) */
+int nabu_conv_module_tile_t(void);
+int nabu_conv_module_parts(int B, int T);
+int nabu_conv_module_fwd(int B, int T, int D, int K, const float *u, int ld, const int32_t *len, const float *w,
+                         const float *bw, const float *gamma, const float *beta, float eps, float *y, float *mean,
+                         float *rstd, nabu_stream_t stream);
+int nabu_conv_module_bwd(int B, int T, int D, int K, const float *u, int ld, const int32_t *len, const float *w,
+                         const float *bw, const float *gamma, const float *beta, const float *mean, const float *rstd,
+                         const float *dy, float *du, float *dz, float *part_ln, float *part_dw, nabu_stream_t stream);
+int nabu_swish_f32(size_t n, const float *x, float *y, nabu_stream_t stream);
+int nabu_swish_bwd_f32(size_t n, const float *x, const float *dy, float *dx, nabu_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

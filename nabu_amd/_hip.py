@@ -259,6 +259,12 @@ SIGNATURES = {
     'nabu_self_attn_fwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     'nabu_self_attn_bwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'nabu_add_positions_f32': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+    'nabu_conv_module_tile_t': (_i, []),
+    'nabu_conv_module_parts': (_i, [_i, _i]),
+    'nabu_conv_module_fwd': (_i, [_i, _i, _i, _i, _vp, _i] + [_vp] * 5 + [_f] + [_vp] * 4),
+    'nabu_conv_module_bwd': (_i, [_i, _i, _i, _i, _vp, _i] + [_vp] * 13),
+    'nabu_swish_f32': (_i, [_sz, _vp, _vp, _vp]),
+    'nabu_swish_bwd_f32': (_i, [_sz, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -428,6 +428,19 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(size_t n, const float *__
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
     dx[i] = y[i] > 0.f ? dy[i] : 0.f;
 }
+// Swish (the Conformer block's feed-forward layers): the full-precision expf, as conv_module.hip's sigmoids
+__global__ __launch_bounds__(256) void swish_kernel(size_t n, const float *x, float *y) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const float v = x[i];
+    y[i] = v * (1.0f / (1.0f + expf(-v)));
+  }
+}
+__global__ __launch_bounds__(256) void swish_bwd_kernel(size_t n, const float *x, const float *dy, float *dx) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const float v = x[i], s = 1.0f / (1.0f + expf(-v));
+    dx[i] = dy[i] * (s * fmaf(v, 1.0f - s, 1.0f));
+  }
+}
 
 // block-wide sums of two values (fixed tree: deterministic)
 __device__ __forceinline__ void block_sum2(float &a, float &b, float *red) {
@@ -858,6 +871,22 @@ extern "C" int nabu_relu_bwd_f32(size_t n, const float *y, const float *dy, floa
   if (n == 0) return 0;
   NABU_CHECK_ARG(y && dy && dx, "relu_bwd: null pointer");
   hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, static_cast<hipStream_t>(stream), n, y, dy, dx);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int nabu_swish_f32(size_t n, const float *x, float *y, nabu_stream_t stream) {
+  if (n == 0) return 0;
+  NABU_CHECK_ARG(x && y, "swish: null pointer");
+  hipLaunchKernelGGL(swish_kernel, dim3(grid_for(n)), dim3(256), 0, static_cast<hipStream_t>(stream), n, x, y);
+  NABU_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int nabu_swish_bwd_f32(size_t n, const float *x, const float *dy, float *dx, nabu_stream_t stream) {
+  if (n == 0) return 0;
+  NABU_CHECK_ARG(x && dy && dx, "swish_bwd: null pointer");
+  hipLaunchKernelGGL(swish_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, static_cast<hipStream_t>(stream), n, x, dy, dx);
   NABU_LAUNCH_CHECK();
   return 0;
 }

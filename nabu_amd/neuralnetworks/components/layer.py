@@ -319,6 +319,115 @@ def self_attention_block(inputs, sequence_length, num_heads, ff_units, keep=1.0,
     return out
 
 
+def conformer_block(inputs, sequence_length, num_heads, ff_units, conv_kernel, keep=1.0, scope=None):
+    """One Conformer block (Gulati et al. 2020; pre-norm, ESPnet's order) as ONE tape node:
+        h = h + 1/2 drop(swish(LN(h) W1 + b1) W2 + b2)                   ffn1
+        h = h + drop(self_attn(LN(h) Wqkv + b) Wo + bo)                  attention
+        h = h + drop(conv_module(LN(h) Wp1 + bp1) Wp2 + bp2)             conv   (Wp1: D -> 2D, Wp2: D -> D)
+        h = h + 1/2 drop(swish(LN(h) W3 + b3) W4 + b4)                   ffn2
+        h = LN(h)                                                        out
+    conv_module (conv_module.hip) is GLU, a depthwise convolution of `conv_kernel` taps along time, a layer norm per frame
+    and Swish, over the frames < sequence_length of each row; its norm is a layer norm, not the paper's batch norm (the
+    README says why).  inputs [B,T,D] fp32, D a multiple of 64.  The products run at GEMM_PRECISION, attention and
+    convolution module are exact fp32.  keep: dropout keep probability (four draws per block under a tape, none on the
+    attention probabilities).  Frames past a length carry finite values that no valid frame reads; the encoder masks them.
+    Variables: <scope>/{ln_ff1,ln_att,ln_conv,ln_ff2,ln_out}/{gamma,beta}, ffn1/{fc1,fc2}/{weights,biases},
+    attention/{qkv,out}/..., conv/{pw1,pw2}/..., conv/dw/{kernel [K,D],bias}, conv/norm/{gamma,beta}, ffn2/{fc1,fc2}/..."""
+    lens = SeqLen.wrap(sequence_length, inputs.device)
+    B, T, D = inputs.shape
+    H, FF, K, N = int(num_heads), int(ff_units), int(conv_kernel), B * T
+    if D % H or D // H not in (32, 64):
+        raise ValueError('conformer_block: %d units in %d heads; the head width must be 32 or 64' % (D, H))
+    if D % 64 or D > 1024 or K % 2 == 0 or not 3 <= K <= 31:
+        raise ValueError('conformer_block: %d units and conv_kernel = %d; the convolution module takes a multiple of 64 '
+                         'units up to 1024 and an odd kernel in 3..31' % (D, K))
+    with vs.variable_scope(scope or 'conformer_block'):
+        norms = [(vs.get_variable('%s/gamma' % n, [D], initializer=vs.ones), vs.get_variable('%s/beta' % n, [D], initializer=vs.zeros))
+                 for n in ('ln_ff1', 'ln_att', 'ln_conv', 'ln_ff2', 'ln_out', 'conv/norm')]
+        dense = [(vs.get_variable('%s/weights' % n, [i, o]), vs.get_variable('%s/biases' % n, [o], initializer=vs.zeros))
+                 for n, i, o in (('ffn1/fc1', D, FF), ('ffn1/fc2', FF, D), ('attention/qkv', D, 3 * D), ('attention/out', D, D),
+                                 ('conv/pw1', D, 2 * D), ('conv/pw2', D, D), ('ffn2/fc1', D, FF), ('ffn2/fc2', FF, D))]
+        taps = vs.get_variable('conv/dw/kernel', [K, D])
+        tap_bias = vs.get_variable('conv/dw/bias', [D], initializer=vs.zeros)
+    variables = tuple(v for pair in norms + dense for v in pair) + (taps, tap_bias)
+    cg, cb = norms[5]
+    precision = GEMM_PRECISION[0]
+    training = Tape.current is not None
+    rng = [ops.global_rng().next() for _ in range(4)] if training and keep < 1 else None
+
+    def linear(x, i, width):
+        W, b = dense[i]
+        return hip.gemm(x, W.data, torch.empty((N, width), dtype=torch.float32, device=x.device), bias=b.data, precision=precision)
+
+    def drop(x, i):
+        return hip.dropout(x, keep, *rng[i]) if rng else x
+
+    def norm(x, i):
+        return hip.layer_norm_fwd(x, norms[i][0].data, norms[i][1].data, LN_EPS)
+
+    def ffn(h, ni, di, ri):
+        """(h + 1/2 drop(swish(LN(h) Wa + ba) Wb + bb), what its backward pass needs)"""
+        a, mean, rstd = norm(h, ni)
+        p = linear(a, di, FF)
+        s = hip.swish(p)
+        return hip.axpy_(h.clone(), drop(linear(s, di + 1, D), ri), a=0.5), (h, a, mean, rstd, p, s)
+
+    x = (inputs if inputs.is_contiguous() else inputs.contiguous()).view(N, D)
+    h1, ffn1 = ffn(x, 0, 0, 0)
+    a2, mean2, rstd2 = norm(h1, 1)
+    qkv = linear(a2, 2, 3 * D).view(B, T, 3 * D)
+    c, lse = hip.self_attn_fwd(qkv, lens.dev, H)
+    h2 = hip.axpy_(drop(linear(c.view(N, D), 3, D), 1), h1)
+    a3, mean3, rstd3 = norm(h2, 2)
+    u = linear(a3, 4, 2 * D).view(B, T, 2 * D)
+    v, cmean, crstd = hip.conv_module_fwd(u, lens.dev, taps.data, tap_bias.data, cg.data, cb.data, LN_EPS)
+    h3 = hip.axpy_(drop(linear(v.view(N, D), 5, D), 2), h2)
+    h4, ffn2 = ffn(h3, 3, 6, 3)
+    out, mean5, rstd5 = norm(h4, 4)
+    out = out.view(B, T, D)
+    need_dx = requires_grad(inputs)
+
+    def backward(dout):
+        for var in variables:
+            if var.grad is None:
+                var.grad = torch.zeros_like(var.data)
+
+        def linear_bwd(x, dy, i):
+            """gradients of dense[i] (overwritten) at input x; returns dx"""
+            W, b = dense[i]
+            hip.gemm(x, dy, W.grad, trans_a=True, precision=precision)
+            hip.colsum(dy, b.grad)
+            return hip.gemm(dy, W.data, torch.empty_like(x), trans_b=True, precision=precision)
+
+        def norm_bwd(x, dy, i, mean, rstd):
+            dx, dgp, dbp = hip.layer_norm_bwd(x, norms[i][0].data, dy, mean, rstd)
+            hip.colsum(dgp, norms[i][0].grad)
+            hip.colsum(dbp, norms[i][1].grad)
+            return dx
+
+        def ffn_bwd(dh, kept, ni, di, ri):
+            """dh at the sublayer's output -> dh at its input"""
+            h, a, mean, rstd, p, s = kept
+            half = hip.axpy_(torch.zeros_like(dh), drop(dh, ri), a=0.5)
+            dp = hip.swish_bwd(p, linear_bwd(s, half, di + 1))
+            return hip.axpy_(norm_bwd(h, linear_bwd(a, dp, di), ni, mean, rstd), dh)
+        dh4 = norm_bwd(h4, dout.reshape(N, D).contiguous(), 4, mean5, rstd5)
+        dh3 = ffn_bwd(dh4, ffn2, 3, 6, 3)
+        dv = linear_bwd(v.view(N, D), drop(dh3, 2), 5)
+        du, dw, dbw, dg, db = hip.conv_module_bwd(u, lens.dev, taps.data, tap_bias.data, cg.data, cb.data, cmean, crstd,
+                                                  dv.view(B, T, D))
+        for var, g in ((taps, dw), (tap_bias, dbw), (cg, dg), (cb, db)):
+            var.grad.copy_(g)
+        dh2 = hip.axpy_(norm_bwd(h2, linear_bwd(a3, du.reshape(N, 2 * D), 4), 2, mean3, rstd3), dh3)
+        dc = linear_bwd(c.view(N, D), drop(dh2, 1), 3)
+        dqkv = hip.self_attn_bwd(qkv, c, lse, dc.view(B, T, D), lens.dev, H)
+        dh1 = hip.axpy_(norm_bwd(h1, linear_bwd(a2, dqkv.reshape(N, 3 * D), 2), 1, mean2, rstd2), dh2)
+        dx = ffn_bwd(dh1, ffn1, 0, 0, 0)                 # (the sublayer's own gradients are due either way)
+        return [dx.view(B, T, D) if need_dx else None]
+    record([inputs], [out], backward, params=variables)
+    return out
+
+
 def pblstm(inputs, sequence_length, num_units, num_steps=2, layer_norm=False, scope=None):
     """A pyramidal BLSTM layer (reference layer.py:53-94): blstm, then stack
     ``num_steps`` consecutive output frames.  Returns (outputs, new lengths)."""

@@ -7,4 +7,5 @@ factory = Registry('encoder', {
     'dblstm': _PKG + 'dblstm:DBLSTM',
     'dnn': _PKG + 'dnn:DNN',
     'transformer': _PKG + 'transformer:Transformer',
+    'conformer': _PKG + 'conformer:Conformer',
 }, outside=('dummy_encoder', 'hotstart_encoder'))

@@ -116,6 +116,10 @@ class Transformer(ed_encoder.EDEncoder):
                 lens = SeqLen.wrap(lengths, x.device)
                 x = embed(x, lens, units, precision)
                 for index in range(int(self.conf['num_layers'])):
-                    x = layer.self_attention_block(x, lens, heads, ff, keep if is_training else 1.0, scope='block%d' % index)
+                    x = self.block(x, lens, heads, ff, keep if is_training else 1.0, 'block%d' % index)
                 encoded[name] = final_norm(x, lens)
         return encoded, encoded_seq_length
+
+    def block(self, x, lens, heads, ff, keep, scope):
+        """one block of the stack (conformer.py puts its own here)"""
+        return layer.self_attention_block(x, lens, heads, ff, keep, scope=scope)

@@ -1182,6 +1182,71 @@ def add_positions_(x, pe, len_dev):
     return x
 
 
+def conv_module_tile_t():
+    """frames a workgroup of the convolution-module kernels owns; tests place their sizes around it"""
+    return _hip.lib().nabu_conv_module_tile_t()
+
+
+def _conv_module_shape(u, w):
+    """(B, T, D, K, ld) of u [B,T,2D] (a tensor or a view whose rows are ld >= 2D apart) and the taps w [K,D]"""
+    B, T, W = u.shape
+    ld = u.stride(1) if T > 1 else u.stride(0) if B > 1 else W
+    if _f32(u, 'u').stride(2) != 1 or (B > 1 and u.stride(0) != T * ld) or not u.is_cuda:
+        raise _hip.NabuHipError('conv_module: u must be a GPU tensor [B,T,2D] with unit column stride and evenly spaced '
+                                'rows, got strides %s' % (tuple(u.stride()),))
+    if W % 2 or w.dim() != 2 or w.shape[1] != W // 2:
+        raise _hip.NabuHipError('conv_module: taps %s do not fit u %s' % (tuple(w.shape), tuple(u.shape)))
+    return B, T, W // 2, w.shape[0], ld
+
+
+def conv_module_fwd(u, len_dev, w, bw, gamma, beta, eps):
+    """(y [B,T,D], mean [B,T], rstd [B,T]): GLU, depthwise convolution along time, layer norm per frame and Swish of
+    u [B,T,2D] over the frames < len of each row, in one launch (nabu_conv_module_fwd); w [K,D], bw, gamma, beta [D]"""
+    B, T, D, K, ld = _conv_module_shape(u, w)
+    y = torch.empty((B, T, D), dtype=torch.float32, device=u.device)
+    mean = torch.empty((B, T), dtype=torch.float32, device=u.device)
+    rstd = torch.empty((B, T), dtype=torch.float32, device=u.device)
+    check(_hip.lib().nabu_conv_module_fwd(B, T, D, K, u.data_ptr(), ld, ptr(len_dev), ptr(_f32(w, 'w')), ptr(bw), ptr(gamma),
+                                          ptr(beta), eps, ptr(y), ptr(mean), ptr(rstd), stream()), 'nabu_conv_module_fwd')
+    return y, mean, rstd
+
+
+def conv_module_bwd(u, len_dev, w, bw, gamma, beta, mean, rstd, dy):
+    """(du of u's shape and strides, dw [K,D], dbw, dgamma, dbeta [D]) from the forward call's mean and rstd and
+    dy [B,T,D] (nabu_conv_module_bwd: two launches, then the workgroups' partial sums through colsum)"""
+    B, T, D, K, ld = _conv_module_shape(u, w)
+    if tuple(dy.shape) != (B, T, D) or tuple(mean.shape) != (B, T) or tuple(rstd.shape) != (B, T):
+        raise _hip.NabuHipError('conv_module_bwd: dy %s, mean %s, rstd %s do not fit u %s' %
+                                (tuple(dy.shape), tuple(mean.shape), tuple(rstd.shape), tuple(u.shape)))
+    dev, parts = u.device, max(_hip.lib().nabu_conv_module_parts(B, T), 1)
+    buf = torch.empty((B, T, ld), dtype=torch.float32, device=dev) if ld == 2 * D else \
+        torch.zeros((B, T, ld), dtype=torch.float32, device=dev)
+    dz = torch.empty((B, T, D), dtype=torch.float32, device=dev)
+    # (every workgroup writes its row; a call without frames launches nothing and the sums are then zero)
+    alloc = torch.empty if B * T else torch.zeros
+    part_ln = alloc((parts, 3 * D), dtype=torch.float32, device=dev)
+    part_dw = alloc((parts, K * D), dtype=torch.float32, device=dev)
+    check(_hip.lib().nabu_conv_module_bwd(B, T, D, K, u.data_ptr(), ld, ptr(len_dev), ptr(_f32(w, 'w')), ptr(bw), ptr(gamma),
+                                          ptr(beta), ptr(mean), ptr(rstd), ptr(_f32(dy, 'dy')), ptr(buf), ptr(dz), ptr(part_ln),
+                                          ptr(part_dw), stream()), 'nabu_conv_module_bwd')
+    ln = colsum(part_ln, torch.empty(3 * D, dtype=torch.float32, device=dev))
+    dw = colsum(part_dw, torch.empty(K * D, dtype=torch.float32, device=dev)).view(K, D)
+    return buf[:, :, :2 * D], dw, ln[2 * D:], ln[:D], ln[D:2 * D]
+
+
+def swish(x):
+    y = torch.empty_like(x)
+    check(_hip.lib().nabu_swish_f32(x.numel(), ptr(x), ptr(y), stream()), 'nabu_swish_f32')
+    return y
+
+
+def swish_bwd(x, dy):
+    """gradient of swish at its INPUT x"""
+    dx = torch.empty_like(x)
+    check(_hip.lib().nabu_swish_bwd_f32(x.numel(), ptr(x), ptr(dy), ptr(dx), stream()), 'nabu_swish_bwd_f32')
+    return dx
+
+
 def ceil_div_i32(x, d):
     out = torch.empty_like(x)
     check(_hip.lib().nabu_ceil_div_i32(x.numel(), ptr(x), int(d), ptr(out), stream()), 'nabu_ceil_div_i32')
