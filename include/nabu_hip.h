@@ -1518,6 +1518,31 @@ int nabu_self_attn_bwd(int B, int T, int H, int dk, const float *qkv, int ld, co
 int nabu_add_positions_f32(int B, int T, int D, float *x, const float *pe, const int32_t *len,
                            nabu_stream_t stream);
 
+/* The same attention on the bf16 matrix pipe (self_attn_bf16.hip, v_mfma_f32_32x32x16_bf16; attention_precision = bf16).
+ * Operands, refusals (the messages name these functions), THE LENGTH RULE and the guarantees of nabu_self_attn_fwd /
+ * nabu_self_attn_bwd hold word for word: fp32 qkv, o, lse, do and dqkv in memory, rows t >= len[b] written as +0.0, the
+ * tiles walked depend on len[b] only, two launches backward, no float atomics, no workspace, equal bits over two calls,
+ * the score matrix never in memory.  nabu_self_attn_bf16_tile_q() = 128 rows per workgroup, nabu_self_attn_bf16_tile_k()
+ * = 64 rows per streamed tile.  o and lse of EITHER forward call are valid inputs of this backward call by type, but
+ * the pair of one precision belongs together: the layers never mix them.
+ * WHERE THE 16-BIT ROUNDINGS ARE (bf16, round to nearest even):
+ *   - Q, K, V and dO, when they become matrix operands (on the way into LDS or into operand registers);
+ *   - P, as the operand of O = P V and of dV = P^T dO;
+ *   - dS, as the operand of dQ = dS K and of dK = dS^T Q.
+ * Everything else is fp32: the accumulators of all products; the multiply by fl(1/sqrt(dk)), applied to the fp32 score;
+ * the running maximum; the running sum, taken over the UNROUNDED probabilities; the one rescale per tile of 64 keys;
+ * lse = m + log(l); delta = rowsum(do . o), from the fp32 do and o; dS = P . (dP - delta) from the unrounded P; the
+ * final division by the sum and the final multiplies by 1/sqrt(dk).  exp(x) is the hardware's 2^(x log2 e) (1 ulp and
+ * |x| u from the product).  Inputs already representable in bf16 are used exactly, so on such inputs the forward
+ * call differs from exact arithmetic by the rounding of P, the fp32 roundings of nabu_self_attn_fwd's order (with 64
+ * for 32) and nothing else. */
+int nabu_self_attn_bf16_tile_q(void);
+int nabu_self_attn_bf16_tile_k(void);
+int nabu_self_attn_bf16_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len, float *o,
+                            float *lse, nabu_stream_t stream);
+int nabu_self_attn_bf16_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o, const float *lse,
+                            const float *d_o, const int32_t *len, float *dqkv, nabu_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Conformer encoder (conv_module.hip): the core of the block's convolution module (Gulati et al. 2020) between its two
  * pointwise products, on a ragged padded batch, fp32.  u [B, T, 2 D] with row stride ld >= 2 D (ld % 4 == 0, 16-byte

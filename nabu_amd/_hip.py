@@ -258,6 +258,10 @@ SIGNATURES = {
     'nabu_self_attn_tile_k': (_i, []),
     'nabu_self_attn_fwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     'nabu_self_attn_bwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'nabu_self_attn_bf16_tile_q': (_i, []),
+    'nabu_self_attn_bf16_tile_k': (_i, []),
+    'nabu_self_attn_bf16_fwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    'nabu_self_attn_bf16_bwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'nabu_add_positions_f32': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     'nabu_conv_module_tile_t': (_i, []),
     'nabu_conv_module_parts': (_i, [_i, _i]),

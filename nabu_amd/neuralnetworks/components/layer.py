@@ -15,6 +15,10 @@ LSTM_MODE = [hip.LSTM_AUTO]      # tests flip this to compare the two recurrent 
 # arithmetic of the input-to-hidden GEMMs of the layers built next ('default' | 'f32' | 'bf16' |
 # 'bf16x3' | 'bf16x6'); set by the encoders from their `gemm_precision` cfg key
 GEMM_PRECISION = ['default']
+# arithmetic of the attention products of the self-attention and conformer blocks built next ('f32' = self_attn.hip |
+# 'bf16' = self_attn_bf16.hip, the four products on the bf16 matrix pipe); set by the transformer encoder from its
+# `attention_precision` cfg key
+ATTENTION_PRECISION = ['f32']
 # arithmetic of the recurrent product h.W_h of the layers built next ('default' = three fp16 plane products of row-scaled
 # operands, fp32-equivalent | 'f32' = the exact-fp32 kernels); set by the encoders from their `recurrent_precision` key
 RECURRENT_PRECISION = ['default']
@@ -253,7 +257,7 @@ def self_attention_block(inputs, sequence_length, num_heads, ff_units, keep=1.0,
         f = LN(h); h = h + drop(relu(f W1 + b1) W2 + b2)
     inputs [B,T,D] fp32; the attention (self_attn.hip) sees the frames < sequence_length of each row only.  The products
     run at GEMM_PRECISION (nabu_gemm_ex falls back to exact fp32 where the 16-bit kernels do not take a shape), the
-    attention itself is exact fp32.  keep: dropout keep probability, applied under a tape only; no dropout on the
+    attention itself at ATTENTION_PRECISION (exact fp32 unless set to 'bf16'; read once, for forward and backward call).  keep: dropout keep probability, applied under a tape only; no dropout on the
     attention probabilities.  Frames past a length carry finite values that no valid frame reads; the encoder masks them.
     Variables: <scope>/{ln1,ln2}/{gamma,beta} [D], attention/{qkv,out}/{weights,biases}, ffn/{fc1,fc2}/{weights,biases}."""
     lens = SeqLen.wrap(sequence_length, inputs.device)
@@ -267,7 +271,7 @@ def self_attention_block(inputs, sequence_length, num_heads, ff_units, keep=1.0,
         dense = [(vs.get_variable('%s/weights' % n, [i, o]), vs.get_variable('%s/biases' % n, [o], initializer=vs.zeros))
                  for n, i, o in (('attention/qkv', D, 3 * D), ('attention/out', D, D), ('ffn/fc1', D, FF), ('ffn/fc2', FF, D))]
     variables = tuple(v for pair in norms + dense for v in pair)
-    precision = GEMM_PRECISION[0]
+    precision, attn_precision = GEMM_PRECISION[0], ATTENTION_PRECISION[0]
     training = Tape.current is not None
     rng = [ops.global_rng().next() for _ in range(2)] if training and keep < 1 else None
 
@@ -281,7 +285,7 @@ def self_attention_block(inputs, sequence_length, num_heads, ff_units, keep=1.0,
     x = (inputs if inputs.is_contiguous() else inputs.contiguous()).view(N, D)
     a, mean1, rstd1 = hip.layer_norm_fwd(x, norms[0][0].data, norms[0][1].data, LN_EPS)
     qkv = linear(a, 0, 3 * D).view(B, T, 3 * D)
-    c, lse = hip.self_attn_fwd(qkv, lens.dev, H)
+    c, lse = hip.self_attn_fwd(qkv, lens.dev, H, attn_precision)
     h1 = hip.axpy_(drop(linear(c.view(N, D), 1, D), 0), x)
     f, mean2, rstd2 = hip.layer_norm_fwd(h1, norms[1][0].data, norms[1][1].data, LN_EPS)
     r = hip.relu(linear(f, 2, FF))
@@ -309,7 +313,7 @@ def self_attention_block(inputs, sequence_length, num_heads, ff_units, keep=1.0,
         du = hip.relu_bwd(r, linear_bwd(r, drop(dout, 1), 3))
         dh1 = hip.axpy_(norm_bwd(h1, linear_bwd(f, du, 2), 1, mean2, rstd2), dout)
         dc = linear_bwd(c.view(N, D), drop(dh1, 0), 1)
-        dqkv = hip.self_attn_bwd(qkv, c, lse, dc.view(B, T, D), lens.dev, H)
+        dqkv = hip.self_attn_bwd(qkv, c, lse, dc.view(B, T, D), lens.dev, H, attn_precision)
         da = linear_bwd(a, dqkv.reshape(N, 3 * D), 0)
         if not need_dx:                                  # (the norm's own gradients are still due)
             norm_bwd(x, da, 0, mean1, rstd1)
@@ -328,8 +332,8 @@ def conformer_block(inputs, sequence_length, num_heads, ff_units, conv_kernel, k
         h = LN(h)                                                        out
     conv_module (conv_module.hip) is GLU, a depthwise convolution of `conv_kernel` taps along time, a layer norm per frame
     and Swish, over the frames < sequence_length of each row; its norm is a layer norm, not the paper's batch norm (the
-    README says why).  inputs [B,T,D] fp32, D a multiple of 64.  The products run at GEMM_PRECISION, attention and
-    convolution module are exact fp32.  keep: dropout keep probability (four draws per block under a tape, none on the
+    README says why).  inputs [B,T,D] fp32, D a multiple of 64.  The products run at GEMM_PRECISION, the attention at
+    ATTENTION_PRECISION (exact fp32 by default), the convolution module is exact fp32.  keep: dropout keep probability (four draws per block under a tape, none on the
     attention probabilities).  Frames past a length carry finite values that no valid frame reads; the encoder masks them.
     Variables: <scope>/{ln_ff1,ln_att,ln_conv,ln_ff2,ln_out}/{gamma,beta}, ffn1/{fc1,fc2}/{weights,biases},
     attention/{qkv,out}/..., conv/{pw1,pw2}/..., conv/dw/{kernel [K,D],bias}, conv/norm/{gamma,beta}, ffn2/{fc1,fc2}/..."""
@@ -351,7 +355,7 @@ def conformer_block(inputs, sequence_length, num_heads, ff_units, conv_kernel, k
         tap_bias = vs.get_variable('conv/dw/bias', [D], initializer=vs.zeros)
     variables = tuple(v for pair in norms + dense for v in pair) + (taps, tap_bias)
     cg, cb = norms[5]
-    precision = GEMM_PRECISION[0]
+    precision, attn_precision = GEMM_PRECISION[0], ATTENTION_PRECISION[0]
     training = Tape.current is not None
     rng = [ops.global_rng().next() for _ in range(4)] if training and keep < 1 else None
 
@@ -376,7 +380,7 @@ def conformer_block(inputs, sequence_length, num_heads, ff_units, conv_kernel, k
     h1, ffn1 = ffn(x, 0, 0, 0)
     a2, mean2, rstd2 = norm(h1, 1)
     qkv = linear(a2, 2, 3 * D).view(B, T, 3 * D)
-    c, lse = hip.self_attn_fwd(qkv, lens.dev, H)
+    c, lse = hip.self_attn_fwd(qkv, lens.dev, H, attn_precision)
     h2 = hip.axpy_(drop(linear(c.view(N, D), 3, D), 1), h1)
     a3, mean3, rstd3 = norm(h2, 2)
     u = linear(a3, 4, 2 * D).view(B, T, 2 * D)
@@ -420,7 +424,7 @@ def conformer_block(inputs, sequence_length, num_heads, ff_units, conv_kernel, k
             var.grad.copy_(g)
         dh2 = hip.axpy_(norm_bwd(h2, linear_bwd(a3, du.reshape(N, 2 * D), 4), 2, mean3, rstd3), dh3)
         dc = linear_bwd(c.view(N, D), drop(dh2, 1), 3)
-        dqkv = hip.self_attn_bwd(qkv, c, lse, dc.view(B, T, D), lens.dev, H)
+        dqkv = hip.self_attn_bwd(qkv, c, lse, dc.view(B, T, D), lens.dev, H, attn_precision)
         dh1 = hip.axpy_(norm_bwd(h1, linear_bwd(a2, dqkv.reshape(N, 3 * D), 2), 1, mean2, rstd2), dh2)
         dx = ffn_bwd(dh1, ffn1, 0, 0, 0)                 # (the sublayer's own gradients are due either way)
         return [dx.view(B, T, D) if need_dx else None]

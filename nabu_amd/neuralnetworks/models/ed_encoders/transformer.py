@@ -8,10 +8,11 @@ layer.self_attention_block's (block<i>/...), a final layer norm (final_ln/{gamma
 length are zero in the result and take no gradient.
 
 cfg keys: num_layers, num_units (D), num_heads, ff_units, dropout (keep probability, on the two sublayer outputs of a
-block; none on the attention probabilities), input_noise, gemm_precision (the dense products; the attention itself is
-exact fp32), the SpecAugment keys and conv_channels / feature_blocks (listener.py).  Refused at construction: num_units
-not divisible by num_heads, a head width other than 32 or 64 (self_attn.hip), and the keys `layer_norm` and
-`recurrent_precision`, which mean nothing here."""
+block; none on the attention probabilities), input_noise, gemm_precision (the dense products), attention_precision (`f32`,
+the default when the key is absent: the attention is exact fp32, self_attn.hip | `bf16`: its four products run on the
+bf16 matrix pipe, self_attn_bf16.hip), the SpecAugment keys and conv_channels / feature_blocks (listener.py).  Refused at
+construction: num_units not divisible by num_heads, a head width other than 32 or 64 (self_attn.hip), any other value of
+attention_precision, and the keys `layer_norm` and `recurrent_precision`, which mean nothing here."""
 import numpy as np
 import torch
 
@@ -85,6 +86,14 @@ def final_norm(x, lens):
     return y
 
 
+def attention_precision_key(conf):
+    """the `attention_precision` cfg key (a build addition like layer_norm: absent from the defaults files, f32 when absent)"""
+    value = str(conf.get('attention_precision', 'f32')).strip()
+    if value not in ('f32', 'bf16'):
+        raise ValueError("transformer encoder: attention_precision must be 'f32' or 'bf16', got %r" % value)
+    return value
+
+
 class Transformer(ed_encoder.EDEncoder):
     """cfg keys: see the module's docstring"""
 
@@ -101,9 +110,11 @@ class Transformer(ed_encoder.EDEncoder):
         if units // heads not in (32, 64) or units > 1024:
             raise ValueError('transformer encoder: num_units / num_heads = %d: the attention kernels take a head width of '
                              '32 or 64 and at most 1024 units' % (units // heads))
+        attention_precision_key(self.conf)
 
     def encode(self, inputs, input_seq_length, is_training):
         layer.GEMM_PRECISION[0] = precision = self.conf.get('gemm_precision', 'default')
+        layer.ATTENTION_PRECISION[0] = attention_precision_key(self.conf)
         units, heads, ff = (int(self.conf[k]) for k in ('num_units', 'num_heads', 'ff_units'))
         keep = float(self.conf['dropout'])
         encoded, encoded_seq_length = {}, dict(input_seq_length)

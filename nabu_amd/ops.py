@@ -1130,9 +1130,21 @@ def maxpool2x2_bwd(x, len_dev, dy):
     return dx
 
 
-def self_attn_tiles():
+_ATTN_ENTRY = {'f32': 'nabu_self_attn', 'bf16': 'nabu_self_attn_bf16'}
+
+
+def _attn_entry(precision, what):
+    """the C entry point `what` (tile_q, tile_k, fwd, bwd) of the attention kernels at `precision`, and its name"""
+    if precision not in _ATTN_ENTRY:
+        raise _hip.NabuHipError("self_attn: precision %r is not one of 'f32' (self_attn.hip) and 'bf16' "
+                                "(self_attn_bf16.hip)" % (precision,))
+    name = '%s_%s' % (_ATTN_ENTRY[precision], what)
+    return getattr(_hip.lib(), name), name
+
+
+def self_attn_tiles(precision='f32'):
     """(rows a workgroup owns, rows of a streamed tile) of the self-attention kernels; tests place their sizes around them"""
-    return _hip.lib().nabu_self_attn_tile_q(), _hip.lib().nabu_self_attn_tile_k()
+    return _attn_entry(precision, 'tile_q')[0](), _attn_entry(precision, 'tile_k')[0]()
 
 
 def _attn_shape(qkv, heads):
@@ -1148,18 +1160,21 @@ def _attn_shape(qkv, heads):
     return B, T, int(heads), W // (3 * heads), ld
 
 
-def self_attn_fwd(qkv, len_dev, heads):
-    """(o [B,T,D], lse [B,H,T]) of multi-head self-attention over the frames < len of each row (nabu_self_attn_fwd)"""
+def self_attn_fwd(qkv, len_dev, heads, precision='f32'):
+    """(o [B,T,D], lse [B,H,T]) of multi-head self-attention over the frames < len of each row (nabu_self_attn_fwd, or
+    nabu_self_attn_bf16_fwd at precision 'bf16': the products on the bf16 matrix pipe, include/nabu_hip.h)"""
+    fn, name = _attn_entry(precision, 'fwd')
     B, T, H, dk, ld = _attn_shape(qkv, heads)
     o = torch.empty((B, T, H * dk), dtype=torch.float32, device=qkv.device)
     lse = torch.empty((B, H, T), dtype=torch.float32, device=qkv.device)
-    check(_hip.lib().nabu_self_attn_fwd(B, T, H, dk, qkv.data_ptr(), ld, ptr(len_dev), ptr(o), ptr(lse), stream()),
-          'nabu_self_attn_fwd')
+    check(fn(B, T, H, dk, qkv.data_ptr(), ld, ptr(len_dev), ptr(o), ptr(lse), stream()), name)
     return o, lse
 
 
-def self_attn_bwd(qkv, o, lse, do, len_dev, heads):
-    """dqkv, of qkv's shape and strides, from the forward call's o and lse and do [B,T,D] (nabu_self_attn_bwd)"""
+def self_attn_bwd(qkv, o, lse, do, len_dev, heads, precision='f32'):
+    """dqkv, of qkv's shape and strides, from the forward call's o and lse and do [B,T,D] (nabu_self_attn_bwd, or
+    nabu_self_attn_bf16_bwd at precision 'bf16'; the precision of the forward call that made o and lse)"""
+    fn, name = _attn_entry(precision, 'bwd')
     B, T, H, dk, ld = _attn_shape(qkv, heads)
     if tuple(do.shape) != tuple(o.shape) or tuple(o.shape) != (B, T, H * dk) or tuple(lse.shape) != (B, H, T):
         raise _hip.NabuHipError('self_attn_bwd: o %s, do %s, lse %s do not fit qkv %s' %
@@ -1167,8 +1182,8 @@ def self_attn_bwd(qkv, o, lse, do, len_dev, heads):
     # (the columns past 3D of a strided view belong to nobody: zeros, so that the buffer is defined)
     buf = torch.empty((B, T, ld), dtype=torch.float32, device=qkv.device) if ld == 3 * H * dk else \
         torch.zeros((B, T, ld), dtype=torch.float32, device=qkv.device)
-    check(_hip.lib().nabu_self_attn_bwd(B, T, H, dk, qkv.data_ptr(), ld, ptr(_f32(o, 'o')), ptr(_f32(lse, 'lse')),
-                                        ptr(_f32(do, 'do')), ptr(len_dev), ptr(buf), stream()), 'nabu_self_attn_bwd')
+    check(fn(B, T, H, dk, qkv.data_ptr(), ld, ptr(_f32(o, 'o')), ptr(_f32(lse, 'lse')), ptr(_f32(do, 'do')), ptr(len_dev),
+             ptr(buf), stream()), name)
     return buf[:, :, :3 * H * dk]
 
 

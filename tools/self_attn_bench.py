@@ -7,12 +7,18 @@ dk 64 and T 250 (the transformer_ctc recipe behind its front end) and T 1000 (wi
   step      one training step of the transformer_ctc recipe with feature_blocks = 3 at cfg1's size (8 x 200 x 123) against
             vgg_dblstm_ctc on the same batches — for information, no bar
 
+  --bf16    instead of all of the above: nabu_self_attn_bf16_fwd / _bwd (self_attn_bf16.hip) against the fp32 kernels on the
+            same operands, and against scaled_dot_product_attention on bf16 tensors (its conversions not timed,
+            torch.autograd.grad as its backward side), the three sides alternating in one run.  The bar: no slower than
+            the fp32 kernels; the ratio against bf16 SDPA is for information
+
 The bar, forward and backward: no slower.  Lengths are drawn uniformly from T/2 .. T (one row at T).
 Protocol of the other tools: warm-up, then medians of --rounds rounds of --calls calls between device events, the two
 sides of a comparison alternating round by round in the same run; the spread of the round times is reported with them.
 Prints one JSON line (and writes it to --out).
 
-    python tools/self_attn_bench.py [--rounds 5] [--calls 200] [--out profiles/self_attn.json]"""
+    python tools/self_attn_bench.py [--rounds 5] [--calls 200] [--out profiles/self_attn.json]
+    python tools/self_attn_bench.py --bf16 --out profiles/self_attn_bf16.json"""
 import argparse
 import json
 import os
@@ -67,6 +73,43 @@ def attn_bench(T, rounds, calls):
             'max_abs_diff_fwd': worst_fwd, 'max_abs_diff_bwd': worst_bwd}
 
 
+def attn_bf16_bench(T, rounds, calls):
+    """the bf16 kernels, the fp32 kernels and bf16 SDPA on the operands of attn_bench, alternating in one run"""
+    D = H * DK
+    g = torch.Generator(device='cuda').manual_seed(1)
+    qkv = torch.randn((B, T, 3 * D), device='cuda', generator=g)
+    do = torch.randn((B, T, D), device='cuda', generator=g)
+    host_lens = np.random.default_rng(1).integers(T // 2, T + 1, B).astype(np.int32)
+    host_lens[0] = T
+    lens = torch.from_numpy(host_lens).cuda()
+    q, k, v = (t.contiguous().bfloat16().requires_grad_() for t in qkv.view(B, T, 3, H, DK).permute(2, 0, 3, 1, 4))
+    valid = torch.arange(T, device='cuda')[None, :] < lens[:, None]
+    mask = valid[:, None, None, :]
+    sdpa = torch.nn.functional.scaled_dot_product_attention
+    ref = sdpa(q, k, v, attn_mask=mask)
+    do_ref = (do * valid[:, :, None]).view(B, T, H, DK).transpose(1, 2).contiguous().bfloat16()
+    o, lse = hip.self_attn_fwd(qkv, lens, H)
+    o16, lse16 = hip.self_attn_fwd(qkv, lens, H, 'bf16')
+    dqkv = hip.self_attn_bwd(qkv, o, lse, do, lens, H)
+    dqkv16 = hip.self_attn_bwd(qkv, o16, lse16, do, lens, H, 'bf16')
+    sides = rounds_ms(
+        [lambda: hip.self_attn_fwd(qkv, lens, H, 'bf16'), lambda: hip.self_attn_fwd(qkv, lens, H),
+         lambda: sdpa(q, k, v, attn_mask=mask),
+         lambda: hip.self_attn_bwd(qkv, o16, lse16, do, lens, H, 'bf16'), lambda: hip.self_attn_bwd(qkv, o, lse, do, lens, H),
+         lambda: torch.autograd.grad(ref, (q, k, v), do_ref, retain_graph=True)], rounds, calls)
+    pairs = float((host_lens.astype(np.float64) ** 2).sum()) * H
+    res = {'shape': [B, T, H, DK], 'max_abs_diff_fwd_bf16_f32': float((o16 - o).abs().max()),
+           'max_abs_diff_bwd_bf16_f32': float((dqkv16 - dqkv).abs().max())}
+    for name, (ms, spread) in zip(('fwd_bf16', 'fwd_f32', 'sdpa_bf16_fwd', 'bwd_bf16', 'bwd_f32', 'sdpa_bf16_bwd'), sides):
+        res[name + '_ms'], res[name + '_spread'] = round(ms, 4), [round(x, 4) for x in spread]
+    for d, flops in (('fwd', 4), ('bwd', 10)):
+        new, f32, ref_ms = res[d + '_bf16_ms'], res[d + '_f32_ms'], res['sdpa_bf16_%s_ms' % d]
+        res[d + '_bf16_over_f32'], res[d + '_bar'] = round(new / f32, 3), 'met' if new <= f32 else 'missed'
+        res[d + '_bf16_over_sdpa_bf16'] = round(new / ref_ms, 3)
+        res[d + '_bf16_tflops' + ('_useful' if d == 'bwd' else '')] = round(flops * pairs * DK / new / 1e9, 1)
+    return res
+
+
 def step_bench(rounds, calls):
     from nabu_amd.neuralnetworks.trainers import trainer_factory
     data = SyntheticData(8, 200, 123, min_frames=120, min_labels=5, max_labels=20, time_reduction=4, seed=2234)
@@ -94,12 +137,17 @@ def main():
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--calls', type=int, default=200)
     ap.add_argument('--out', default=None, help='also write the JSON line to this file')
+    ap.add_argument('--bf16', action='store_true', help='the bf16 kernels against the fp32 kernels and bf16 SDPA, nothing else')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'self_attn_bench needs a GPU'
     torch.cuda.set_device(0)
-    res = {'bench': 'self_attn', 'rounds': args.rounds, 'calls': args.calls, 'device': torch.cuda.get_device_name(0),
-           'attention': [attn_bench(T, args.rounds, args.calls) for T in (250, 1000)],
-           'step': step_bench(args.rounds, args.calls)}
+    if args.bf16:
+        res = {'bench': 'self_attn_bf16', 'rounds': args.rounds, 'calls': args.calls, 'device': torch.cuda.get_device_name(0),
+               'attention': [attn_bf16_bench(T, args.rounds, args.calls) for T in (250, 1000)]}
+    else:
+        res = {'bench': 'self_attn', 'rounds': args.rounds, 'calls': args.calls, 'device': torch.cuda.get_device_name(0),
+               'attention': [attn_bench(T, args.rounds, args.calls) for T in (250, 1000)],
+               'step': step_bench(args.rounds, args.calls)}
     line = json.dumps(res)
     print(line, flush=True)
     if args.out:
