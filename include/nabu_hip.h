@@ -1543,6 +1543,45 @@ int nabu_self_attn_bf16_fwd(int B, int T, int H, int dk, const float *qkv, int l
 int nabu_self_attn_bf16_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o, const float *lse,
                             const float *d_o, const int32_t *len, float *dqkv, nabu_stream_t stream);
 
+/* Dropout on the attention probabilities, inside the kernels of both precisions (the DROP instantiations of
+ * self_attn.hip and self_attn_bf16.hip; the mask helper is csrc/attn_drop.h).  With keep probability `keep` and the mask
+ * d[b,h,q,k] in {0, fl(1 / keep)}:
+ *     P = softmax_k(q . k / sqrt(dk)) over k < len[b]     unchanged; lse unchanged: the running sum is over the
+ *                                                         UNDROPPED probabilities
+ *     O = (d . P) V
+ *     delta = rowsum(dO . O)  (= rowsum(P . dP), since O carries d);   dP = d . (dO V^T)
+ *     dS = P . (dP - delta);  dQ = dS K / sqrt(dk);  dK = dS^T Q / sqrt(dk);  dV = (d . P)^T dO
+ * A query whose kept set is empty gets an output row of +0.0, never NaN: lse stays finite.
+ * THE MASK is a function of (seed, offset, b, h, q, k) only — not of T, of a tile size, of the kernel that asks or of
+ * the precision.  Element (b, h, q, k) is word k & 3 of the Philox4x32-10 block with counter (g_lo, g_hi, offset_lo,
+ * offset_hi) and key (seed_lo, seed_hi), g = ((b H + h) << 38) | (q << 18) | (k >> 2); it is kept when
+ * u01(word) = (word >> 8) 2^-24 < keep, compared in float32, and then scaled by fl(1.0f / keep) — the rule of
+ * nabu_dropout_f32.  Because T is not in the counter, an utterance at batch row b gets the same mask alone at T = len as
+ * inside a longer padded batch; forward, dQ and dK/dV kernels of both precisions see the same mask, so the backward call
+ * takes the (keep, seed, offset) of the forward call that made o and lse.
+ * WHERE THE MASK SITS: in the forward kernels p is added to the running sum first and multiplied by d second, then
+ * fed to O = (d . P) V; in the dQ kernels d multiplies dP = dO V^T before delta is subtracted; in the dK/dV kernels d
+ * multiplies P for dV and dP before dS, and the P inside dS stays undropped.  In the bf16 kernels every one of these
+ * multiplies is fp32 and comes BEFORE the rounding of its product's operand: bf16(d . P) is the operand of O and dV,
+ * bf16(dS) of dQ and dK; Q, K, V and dO are rounded as without dropout.
+ * Operands, THE LENGTH RULE and every guarantee of the plain entry points hold word for word (rows >= len are +0.0, the
+ * tiles walked depend on len only, no float atomics, no workspace, two calls give equal bits), and so does every
+ * refusal, with these functions' names in the messages; two refusals are added: T > 2^20 (the counter holds 20 bits of
+ * the frame index) and a keep that is not a finite number in (0, 1].  keep == 1 launches the plain kernels: the plain
+ * entry points' bits. */
+int nabu_self_attn_drop_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len, float keep,
+                            unsigned long long seed, unsigned long long offset, float *o, float *lse,
+                            nabu_stream_t stream);
+int nabu_self_attn_drop_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o, const float *lse,
+                            const float *d_o, const int32_t *len, float keep, unsigned long long seed,
+                            unsigned long long offset, float *dqkv, nabu_stream_t stream);
+int nabu_self_attn_bf16_drop_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len, float keep,
+                                 unsigned long long seed, unsigned long long offset, float *o, float *lse,
+                                 nabu_stream_t stream);
+int nabu_self_attn_bf16_drop_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o,
+                                 const float *lse, const float *d_o, const int32_t *len, float keep,
+                                 unsigned long long seed, unsigned long long offset, float *dqkv, nabu_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Conformer encoder (conv_module.hip): the core of the block's convolution module (Gulati et al. 2020) between its two
  * pointwise products, on a ragged padded batch, fp32.  u [B, T, 2 D] with row stride ld >= 2 D (ld % 4 == 0, 16-byte

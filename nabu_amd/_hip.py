@@ -262,6 +262,12 @@ SIGNATURES = {
     'nabu_self_attn_bf16_tile_k': (_i, []),
     'nabu_self_attn_bf16_fwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     'nabu_self_attn_bf16_bwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the same with dropout on the attention probabilities: (keep, seed, offset) after len
+    'nabu_self_attn_drop_fwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _vp, _vp, _vp]),
+    'nabu_self_attn_drop_bwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _vp, _vp]),
+    'nabu_self_attn_bf16_drop_fwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _vp, _vp, _vp]),
+    'nabu_self_attn_bf16_drop_bwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _c.c_ulonglong, _c.c_ulonglong,
+                                          _vp, _vp]),
     'nabu_add_positions_f32': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     'nabu_conv_module_tile_t': (_i, []),
     'nabu_conv_module_parts': (_i, [_i, _i]),

@@ -34,6 +34,7 @@
 // Built with packed fp32 VALU instructions switched off (build.py, as conv2d.hip).
 #include <float.h>
 
+#include "attn_drop.h"
 #include "gemm_args.h"
 
 namespace nabu {
@@ -47,6 +48,7 @@ struct AttnArgs {
   const int32_t *len;
   int B, T, H, ld;
   float scale;                                   // 1 / sqrt(dk)
+  AttnDrop drop;                                 // read by the DROP instantiations only (attn_drop.h)
 };
 
 // row index of accumulator register r within a 32 x 32 tile, for the half-wave lk
@@ -125,7 +127,7 @@ __device__ __forceinline__ void store_acc_t(float *dst, const f32x16 (&acc)[DK /
     }
 }
 
-template <int DK>
+template <int DK, bool DROP>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
   constexpr int TILE = ATTN_K * (DK + 1);
   __shared__ float Ks[2][TILE], Vs[2][TILE];
@@ -167,6 +169,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
       kr.load(base + D + (size_t)(k0 + ATTN_K) * a.ld, a.ld, len - k0 - ATTN_K, tid);
       vr.load(base + 2 * D + (size_t)(k0 + ATTN_K) * a.ld, a.ld, len - k0 - ATTN_K, tid);
     }
+    unsigned kept = 0;                                       // DROP: made here, ahead of the S product it is independent of
+    if constexpr (DROP) kept = attn_keep16_query(a.drop, b * a.H + h, qi, k0, lk);
     const f32x16 s = tile_times_regs<DK>(Ks[cur], qreg, li, lk);
     float p[16], mt = -FLT_MAX;
 #pragma unroll
@@ -181,7 +185,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       p[r] = k0 + acc_row(r, lk) < len ? expf(p[r] - mn) : 0.f;
-      ps += p[r];
+      ps += p[r];                                            // the undropped probability
+      if constexpr (DROP) p[r] *= attn_drop_scale(a.drop, kept, r);
     }
     ps += __shfl_xor(ps, 32);
     l = l * alpha + ps;
@@ -203,7 +208,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
   if (lk == 0) *lse_p = pad ? 0.f : m + logf(l);
 }
 
-template <int DK>
+template <int DK, bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
   constexpr int TILE = ATTN_K * (DK + 1);
   __shared__ float Ks[2][TILE], Vs[2][TILE];
@@ -251,13 +256,16 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
       kr.load(base + D + (size_t)(k0 + ATTN_K) * a.ld, a.ld, len - k0 - ATTN_K, tid);
       vr.load(base + 2 * D + (size_t)(k0 + ATTN_K) * a.ld, a.ld, len - k0 - ATTN_K, tid);
     }
+    unsigned kept = 0;
+    if constexpr (DROP) kept = attn_keep16_query(a.drop, b * a.H + h, qi, k0, lk);
     const f32x16 s = tile_times_regs<DK>(Ks[cur], qreg, li, lk);
     const f32x16 dp = tile_times_regs<DK>(Vs[cur], doreg, li, lk);
     float ds[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const float p = k0 + acc_row(r, lk) < len ? expf(s[r] * a.scale - lse) : 0.f;
-      ds[r] = p * (dp[r] - delta);
+      if constexpr (DROP) ds[r] = p * (dp[r] * attn_drop_scale(a.drop, kept, r) - delta);   // dP = d . (dO V^T)
+      else ds[r] = p * (dp[r] - delta);
     }
     tile_t_times_acc<DK>(Ks[cur], ds, dq, li, lk);
     if (more) {
@@ -269,7 +277,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
   if (qi < a.T) store_acc_t<DK>(dqrow, dq, a.scale, qi >= len, lk);
 }
 
-template <int DK>
+template <int DK, bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
   constexpr int TILE = ATTN_K * (DK + 1);
   constexpr int PPR = DK / 4;                                // 16-byte pieces per row
@@ -336,6 +344,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
     const int t0 = it * ATTN_K, cur = it & 1;
     const bool more = it + 1 < ntiles;
     if (more) gload(t0 + ATTN_K);
+    unsigned kept = 0;
+    if constexpr (DROP) kept = attn_keep16_key(a.drop, b * a.H + h, t0, ki, lk, lane);
     const f32x16 s = tile_times_regs<DK>(Qs[cur], kreg, li, lk);       // S = Q K^T: lane = key, registers = queries
     const f32x16 dp = tile_times_regs<DK>(dOs[cur], vreg, li, lk);     // dP = dO V^T
     float p[16], ds[16];
@@ -343,7 +353,13 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
     for (int r = 0; r < 16; ++r) {
       const int qq = acc_row(r, lk);
       p[r] = (kvalid && t0 + qq < len) ? expf(s[r] * a.scale - lse_s[cur][qq]) : 0.f;
-      ds[r] = p[r] * (dp[r] - delta_s[cur][qq]);
+      if constexpr (DROP) {                                            // dS keeps the undropped P; dV takes d . P
+        const float d = attn_drop_scale(a.drop, kept, r);
+        ds[r] = p[r] * (dp[r] * d - delta_s[cur][qq]);
+        p[r] *= d;
+      } else {
+        ds[r] = p[r] * (dp[r] - delta_s[cur][qq]);
+      }
     }
     tile_t_times_acc<DK>(dOs[cur], p, dv, li, lk);                     // dV^T = dO^T P
     tile_t_times_acc<DK>(Qs[cur], ds, dk, li, lk);                     // dK^T = Q^T dS
@@ -384,44 +400,88 @@ using namespace nabu;
 extern "C" int nabu_self_attn_tile_q(void) { return ATTN_Q; }
 extern "C" int nabu_self_attn_tile_k(void) { return ATTN_K; }
 
-extern "C" int nabu_self_attn_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len, float *o,
-                                  float *lse, nabu_stream_t stream) {
-  NABU_TRY(attn_shape("self_attn_fwd", B, T, H, dk, ld));
-  NABU_CHECK_ARG(qkv && len && o && lse, "self_attn_fwd: null pointer");
-  NABU_CHECK_ARG(attn_al16(qkv) && attn_al16(o), "self_attn_fwd: qkv and o must be 16-byte aligned");
+// the forward launch of nabu_self_attn_fwd (drop == nullptr, or keep == 1: the plain instantiations) and nabu_self_attn_drop_fwd
+static int attn_fwd_launch(const char *what, int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len,
+                           const AttnDrop *drop, float *o, float *lse, nabu_stream_t stream) {
+  NABU_TRY(attn_shape(what, B, T, H, dk, ld));
+  NABU_CHECK_ARG(qkv && len && o && lse, "%s: null pointer", what);
+  NABU_CHECK_ARG(attn_al16(qkv) && attn_al16(o), "%s: qkv and o must be 16-byte aligned", what);
   if (B == 0 || T == 0) return 0;
   AttnArgs a = {};
   a.qkv = qkv; a.len = len; a.out = o; a.lse_out = lse;
   a.B = B; a.T = T; a.H = H; a.ld = ld; a.scale = 1.f / sqrtf((float)dk);
   const dim3 grid((T + ATTN_Q - 1) / ATTN_Q, H, B);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dk == 64) hipLaunchKernelGGL(attn_fwd_kernel<64>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(attn_fwd_kernel<32>, grid, dim3(256), 0, s, a);
+  if (drop && drop->keep < 1.f) {
+    a.drop = *drop;
+    if (dk == 64) hipLaunchKernelGGL((attn_fwd_kernel<64, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((attn_fwd_kernel<32, true>), grid, dim3(256), 0, s, a);
+  } else {
+    if (dk == 64) hipLaunchKernelGGL((attn_fwd_kernel<64, false>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((attn_fwd_kernel<32, false>), grid, dim3(256), 0, s, a);
+  }
   NABU_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int nabu_self_attn_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o, const float *lse,
-                                  const float *d_o, const int32_t *len, float *dqkv, nabu_stream_t stream) {
-  NABU_TRY(attn_shape("self_attn_bwd", B, T, H, dk, ld));
-  NABU_CHECK_ARG(qkv && o && lse && d_o && len && dqkv, "self_attn_bwd: null pointer");
+static int attn_bwd_launch(const char *what, int B, int T, int H, int dk, const float *qkv, int ld, const float *o,
+                           const float *lse, const float *d_o, const int32_t *len, const AttnDrop *drop, float *dqkv,
+                           nabu_stream_t stream) {
+  NABU_TRY(attn_shape(what, B, T, H, dk, ld));
+  NABU_CHECK_ARG(qkv && o && lse && d_o && len && dqkv, "%s: null pointer", what);
   NABU_CHECK_ARG(attn_al16(qkv) && attn_al16(o) && attn_al16(d_o) && attn_al16(dqkv),
-                 "self_attn_bwd: qkv, o, do and dqkv must be 16-byte aligned");
+                 "%s: qkv, o, do and dqkv must be 16-byte aligned", what);
   if (B == 0 || T == 0) return 0;
   AttnArgs a = {};
   a.qkv = qkv; a.o = o; a.lse = lse; a.d_o = d_o; a.len = len; a.dqkv = dqkv;
   a.B = B; a.T = T; a.H = H; a.ld = ld; a.scale = 1.f / sqrtf((float)dk);
   const dim3 grid((T + ATTN_Q - 1) / ATTN_Q, H, B);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dk == 64) {
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<64>, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<64>, grid, dim3(256), 0, s, a);
+  if (drop && drop->keep < 1.f) {
+    a.drop = *drop;
+    if (dk == 64) {
+      hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, true>), grid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<64, true>), grid, dim3(256), 0, s, a);
+    } else {
+      hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, true>), grid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<32, true>), grid, dim3(256), 0, s, a);
+    }
+  } else if (dk == 64) {
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, false>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<64, false>), grid, dim3(256), 0, s, a);
   } else {
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<32>, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<32>, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, false>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<32, false>), grid, dim3(256), 0, s, a);
   }
   NABU_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int nabu_self_attn_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len, float *o,
+                                  float *lse, nabu_stream_t stream) {
+  return attn_fwd_launch("self_attn_fwd", B, T, H, dk, qkv, ld, len, nullptr, o, lse, stream);
+}
+
+extern "C" int nabu_self_attn_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o, const float *lse,
+                                  const float *d_o, const int32_t *len, float *dqkv, nabu_stream_t stream) {
+  return attn_bwd_launch("self_attn_bwd", B, T, H, dk, qkv, ld, o, lse, d_o, len, nullptr, dqkv, stream);
+}
+
+extern "C" int nabu_self_attn_drop_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len, float keep,
+                                       unsigned long long seed, unsigned long long offset, float *o, float *lse,
+                                       nabu_stream_t stream) {
+  AttnDrop d;
+  NABU_TRY(attn_drop_args("self_attn_drop_fwd", T, keep, seed, offset, &d));
+  return attn_fwd_launch("self_attn_drop_fwd", B, T, H, dk, qkv, ld, len, &d, o, lse, stream);
+}
+
+extern "C" int nabu_self_attn_drop_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o,
+                                       const float *lse, const float *d_o, const int32_t *len, float keep,
+                                       unsigned long long seed, unsigned long long offset, float *dqkv,
+                                       nabu_stream_t stream) {
+  AttnDrop d;
+  NABU_TRY(attn_drop_args("self_attn_drop_bwd", T, keep, seed, offset, &d));
+  return attn_bwd_launch("self_attn_drop_bwd", B, T, H, dk, qkv, ld, o, lse, d_o, len, &d, dqkv, stream);
 }
 
 extern "C" int nabu_add_positions_f32(int B, int T, int D, float *x, const float *pe, const int32_t *len,

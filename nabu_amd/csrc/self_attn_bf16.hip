@@ -49,6 +49,7 @@
 // Built with packed fp32 VALU instructions switched off (build.py, as self_attn.hip).
 #include <float.h>
 
+#include "attn_drop.h"
 #include "gemm_args.h"
 
 namespace nabu {
@@ -80,6 +81,7 @@ struct Attn16Args {
   const int32_t *len;
   int B, T, H, ld;
   float scale;                                   // 1 / sqrt(dk)
+  AttnDrop drop;                                 // read by the DROP instantiations only (attn_drop.h)
 };
 
 // row index of accumulator register r within a 32 x 32 tile, for the half-wave lk
@@ -212,7 +214,7 @@ __device__ __forceinline__ void store_acc_t(float *dst, const f32x16 (&acc)[DK /
     }
 }
 
-template <int DK>
+template <int DK, bool DROP>
 __global__ __launch_bounds__(256) void attn_bf16_fwd_kernel(Attn16Args a) {
   __shared__ __attribute__((aligned(16))) char Ks[2][A16<DK>::ROWS], Vt[2][A16<DK>::COLS];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lk = lane >> 5;
@@ -255,6 +257,11 @@ __global__ __launch_bounds__(256) void attn_bf16_fwd_kernel(Attn16Args a) {
       vb.load(base + 2 * D + (size_t)(k0 + A16_K) * a.ld, a.ld, len - k0 - A16_K, tid);
     }
     float p[2][16], mt = -FLT_MAX;
+    unsigned kept[2] = {0, 0};                               // DROP: eight blocks per lane and 64-key tile, ahead of the S products
+    if constexpr (DROP) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) kept[j] = attn_keep16_query(a.drop, b * a.H + h, qi, k0 + 32 * j, lk);
+    }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const f32x16 s = rows_times_regs<DK>(Ks[cur] + 32 * j * A16<DK>::RS, qreg, li, lk);
@@ -273,7 +280,8 @@ __global__ __launch_bounds__(256) void attn_bf16_fwd_kernel(Attn16Args a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         p[j][r] = k0 + 32 * j + acc_row(r, lk) < len ? exp_fast(p[j][r] - mn) : 0.f;
-        ps += p[j][r];                                       // the unrounded probability
+        ps += p[j][r];                                       // the unrounded, undropped probability
+        if constexpr (DROP) p[j][r] *= attn_drop_scale(a.drop, kept[j], r);     // in fp32, before the rounding
       }
     ps += __shfl_xor(ps, 32);
     l = l * alpha + ps;
@@ -296,7 +304,7 @@ __global__ __launch_bounds__(256) void attn_bf16_fwd_kernel(Attn16Args a) {
   if (lk == 0) *lse_p = pad ? 0.f : m + logf(l);
 }
 
-template <int DK>
+template <int DK, bool DROP>
 __global__ __launch_bounds__(256) void attn_bf16_bwd_dq_kernel(Attn16Args a) {
   __shared__ __attribute__((aligned(16))) char Ks[2][A16<DK>::ROWS], Kt[2][A16<DK>::COLS], Vs[2][A16<DK>::ROWS];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lk = lane >> 5;
@@ -351,13 +359,16 @@ __global__ __launch_bounds__(256) void attn_bf16_bwd_dq_kernel(Attn16Args a) {
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
+      unsigned kept = 0;
+      if constexpr (DROP) kept = attn_keep16_query(a.drop, b * a.H + h, qi, k0 + 32 * j, lk);
       const f32x16 s = rows_times_regs<DK>(Ks[cur] + 32 * j * A16<DK>::RS, qreg, li, lk);
       const f32x16 dp = rows_times_regs<DK>(Vs[cur] + 32 * j * A16<DK>::RS, doreg, li, lk);
       float ds[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float p = k0 + 32 * j + acc_row(r, lk) < len ? exp_fast(s[r] * a.scale - lse) : 0.f;
-        ds[r] = p * (dp[r] - delta);
+        if constexpr (DROP) ds[r] = p * (dp[r] * attn_drop_scale(a.drop, kept, r) - delta);   // dP = d . (dO V^T), fp32
+        else ds[r] = p * (dp[r] - delta);
       }
       cols_times_acc<DK>(Kt[cur], j, ds, dq, li, lk);
     }
@@ -370,7 +381,7 @@ __global__ __launch_bounds__(256) void attn_bf16_bwd_dq_kernel(Attn16Args a) {
   if (qi < a.T) store_acc_t<DK>(dqrow, dq, a.scale, qi >= len, lk);
 }
 
-template <int DK>
+template <int DK, bool DROP>
 __global__ __launch_bounds__(256) void attn_bf16_bwd_dkv_kernel(Attn16Args a) {
   constexpr int PPR = A16<DK>::PPR;
   __shared__ __attribute__((aligned(16))) char Qs[A16<DK>::ROWS], Qt[A16<DK>::COLS], dOs[A16<DK>::ROWS], dOt[A16<DK>::COLS];
@@ -438,6 +449,8 @@ __global__ __launch_bounds__(256) void attn_bf16_bwd_dkv_kernel(Attn16Args a) {
     if (it + 1 < ntiles) gload(t0 + A16_K);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
+      unsigned kept = 0;
+      if constexpr (DROP) kept = attn_keep16_key(a.drop, b * a.H + h, t0 + 32 * j, ki, lk, lane);
       const f32x16 s = rows_times_regs<DK>(Qs + 32 * j * A16<DK>::RS, kreg, li, lk);       // S = Q K^T: lane = key, registers = queries
       const f32x16 dp = rows_times_regs<DK>(dOs + 32 * j * A16<DK>::RS, vreg, li, lk);     // dP = dO V^T
       float p[16], ds[16];
@@ -445,7 +458,13 @@ __global__ __launch_bounds__(256) void attn_bf16_bwd_dkv_kernel(Attn16Args a) {
       for (int r = 0; r < 16; ++r) {
         const int qq = 32 * j + acc_row(r, lk);
         p[r] = (kvalid && t0 + qq < len) ? exp_fast(s[r] * a.scale - lse_s[qq]) : 0.f;
-        ds[r] = p[r] * (dp[r] - delta_s[qq]);
+        if constexpr (DROP) {                                  // dS keeps the undropped P; dV takes d . P, rounded after the multiply
+          const float d = attn_drop_scale(a.drop, kept, r);
+          ds[r] = p[r] * (dp[r] * d - delta_s[qq]);
+          p[r] *= d;
+        } else {
+          ds[r] = p[r] * (dp[r] - delta_s[qq]);
+        }
       }
       cols_times_acc<DK>(dOt, j, p, dv, li, lk);                                           // dV^T = dO^T P
       cols_times_acc<DK>(Qt, j, ds, dk, li, lk);                                           // dK^T = Q^T dS
@@ -477,43 +496,87 @@ using namespace nabu;
 extern "C" int nabu_self_attn_bf16_tile_q(void) { return A16_Q; }
 extern "C" int nabu_self_attn_bf16_tile_k(void) { return A16_K; }
 
-extern "C" int nabu_self_attn_bf16_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len, float *o,
-                                       float *lse, nabu_stream_t stream) {
-  NABU_TRY(attn_shape("self_attn_bf16_fwd", B, T, H, dk, ld));
-  NABU_CHECK_ARG(qkv && len && o && lse, "self_attn_bf16_fwd: null pointer");
-  NABU_CHECK_ARG(al16(qkv) && al16(o), "self_attn_bf16_fwd: qkv and o must be 16-byte aligned");
+// the forward launch of nabu_self_attn_bf16_fwd (drop == nullptr, or keep == 1: the plain instantiations) and of
+// nabu_self_attn_bf16_drop_fwd
+static int attn16_fwd_launch(const char *what, int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len,
+                             const AttnDrop *drop, float *o, float *lse, nabu_stream_t stream) {
+  NABU_TRY(attn_shape(what, B, T, H, dk, ld));
+  NABU_CHECK_ARG(qkv && len && o && lse, "%s: null pointer", what);
+  NABU_CHECK_ARG(al16(qkv) && al16(o), "%s: qkv and o must be 16-byte aligned", what);
   if (B == 0 || T == 0) return 0;
   Attn16Args a = {};
   a.qkv = qkv; a.len = len; a.out = o; a.lse_out = lse;
   a.B = B; a.T = T; a.H = H; a.ld = ld; a.scale = 1.f / sqrtf((float)dk);
   const dim3 grid((T + A16_Q - 1) / A16_Q, H, B);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dk == 64) hipLaunchKernelGGL(attn_bf16_fwd_kernel<64>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(attn_bf16_fwd_kernel<32>, grid, dim3(256), 0, s, a);
+  if (drop && drop->keep < 1.f) {
+    a.drop = *drop;
+    if (dk == 64) hipLaunchKernelGGL((attn_bf16_fwd_kernel<64, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((attn_bf16_fwd_kernel<32, true>), grid, dim3(256), 0, s, a);
+  } else {
+    if (dk == 64) hipLaunchKernelGGL((attn_bf16_fwd_kernel<64, false>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((attn_bf16_fwd_kernel<32, false>), grid, dim3(256), 0, s, a);
+  }
   NABU_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int nabu_self_attn_bf16_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o,
-                                       const float *lse, const float *d_o, const int32_t *len, float *dqkv,
-                                       nabu_stream_t stream) {
-  NABU_TRY(attn_shape("self_attn_bf16_bwd", B, T, H, dk, ld));
-  NABU_CHECK_ARG(qkv && o && lse && d_o && len && dqkv, "self_attn_bf16_bwd: null pointer");
-  NABU_CHECK_ARG(al16(qkv) && al16(o) && al16(d_o) && al16(dqkv),
-                 "self_attn_bf16_bwd: qkv, o, do and dqkv must be 16-byte aligned");
+static int attn16_bwd_launch(const char *what, int B, int T, int H, int dk, const float *qkv, int ld, const float *o,
+                             const float *lse, const float *d_o, const int32_t *len, const AttnDrop *drop, float *dqkv,
+                             nabu_stream_t stream) {
+  NABU_TRY(attn_shape(what, B, T, H, dk, ld));
+  NABU_CHECK_ARG(qkv && o && lse && d_o && len && dqkv, "%s: null pointer", what);
+  NABU_CHECK_ARG(al16(qkv) && al16(o) && al16(d_o) && al16(dqkv), "%s: qkv, o, do and dqkv must be 16-byte aligned", what);
   if (B == 0 || T == 0) return 0;
   Attn16Args a = {};
   a.qkv = qkv; a.o = o; a.lse = lse; a.d_o = d_o; a.len = len; a.dqkv = dqkv;
   a.B = B; a.T = T; a.H = H; a.ld = ld; a.scale = 1.f / sqrtf((float)dk);
   const dim3 grid((T + A16_Q - 1) / A16_Q, H, B);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dk == 64) {
-    hipLaunchKernelGGL(attn_bf16_bwd_dkv_kernel<64>, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(attn_bf16_bwd_dq_kernel<64>, grid, dim3(256), 0, s, a);
+  if (drop && drop->keep < 1.f) {
+    a.drop = *drop;
+    if (dk == 64) {
+      hipLaunchKernelGGL((attn_bf16_bwd_dkv_kernel<64, true>), grid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((attn_bf16_bwd_dq_kernel<64, true>), grid, dim3(256), 0, s, a);
+    } else {
+      hipLaunchKernelGGL((attn_bf16_bwd_dkv_kernel<32, true>), grid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((attn_bf16_bwd_dq_kernel<32, true>), grid, dim3(256), 0, s, a);
+    }
+  } else if (dk == 64) {
+    hipLaunchKernelGGL((attn_bf16_bwd_dkv_kernel<64, false>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((attn_bf16_bwd_dq_kernel<64, false>), grid, dim3(256), 0, s, a);
   } else {
-    hipLaunchKernelGGL(attn_bf16_bwd_dkv_kernel<32>, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(attn_bf16_bwd_dq_kernel<32>, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((attn_bf16_bwd_dkv_kernel<32, false>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((attn_bf16_bwd_dq_kernel<32, false>), grid, dim3(256), 0, s, a);
   }
   NABU_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int nabu_self_attn_bf16_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len, float *o,
+                                       float *lse, nabu_stream_t stream) {
+  return attn16_fwd_launch("self_attn_bf16_fwd", B, T, H, dk, qkv, ld, len, nullptr, o, lse, stream);
+}
+
+extern "C" int nabu_self_attn_bf16_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o,
+                                       const float *lse, const float *d_o, const int32_t *len, float *dqkv,
+                                       nabu_stream_t stream) {
+  return attn16_bwd_launch("self_attn_bf16_bwd", B, T, H, dk, qkv, ld, o, lse, d_o, len, nullptr, dqkv, stream);
+}
+
+extern "C" int nabu_self_attn_bf16_drop_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len,
+                                            float keep, unsigned long long seed, unsigned long long offset, float *o,
+                                            float *lse, nabu_stream_t stream) {
+  AttnDrop d;
+  NABU_TRY(attn_drop_args("self_attn_bf16_drop_fwd", T, keep, seed, offset, &d));
+  return attn16_fwd_launch("self_attn_bf16_drop_fwd", B, T, H, dk, qkv, ld, len, &d, o, lse, stream);
+}
+
+extern "C" int nabu_self_attn_bf16_drop_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o,
+                                            const float *lse, const float *d_o, const int32_t *len, float keep,
+                                            unsigned long long seed, unsigned long long offset, float *dqkv,
+                                            nabu_stream_t stream) {
+  AttnDrop d;
+  NABU_TRY(attn_drop_args("self_attn_bf16_drop_bwd", T, keep, seed, offset, &d));
+  return attn16_bwd_launch("self_attn_bf16_drop_bwd", B, T, H, dk, qkv, ld, o, lse, d_o, len, &d, dqkv, stream);
 }

@@ -28,4 +28,5 @@ class Conformer(Transformer):
             raise ValueError('conformer encoder: conv_kernel = %d, must be odd in 3..31' % kernel)
 
     def block(self, x, lens, heads, ff, keep, scope):
-        return layer.conformer_block(x, lens, heads, ff, int(self.conf['conv_kernel']), keep, scope=scope)
+        return layer.conformer_block(x, lens, heads, ff, int(self.conf['conv_kernel']), keep, scope=scope,
+                                     attention_keep=self.attention_keep)

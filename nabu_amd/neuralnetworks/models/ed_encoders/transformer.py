@@ -8,11 +8,13 @@ layer.self_attention_block's (block<i>/...), a final layer norm (final_ln/{gamma
 length are zero in the result and take no gradient.
 
 cfg keys: num_layers, num_units (D), num_heads, ff_units, dropout (keep probability, on the two sublayer outputs of a
-block; none on the attention probabilities), input_noise, gemm_precision (the dense products), attention_precision (`f32`,
+block), attention_dropout (KEEP probability of the dropout on the attention probabilities, like `dropout`: ESPnet's
+1 - attention_dropout_rate, Lingvo's 1 - atten_dropout_prob; 1.0 when the key is absent; applied in training only, inside
+the attention kernels, one more draw per block), input_noise, gemm_precision (the dense products), attention_precision (`f32`,
 the default when the key is absent: the attention is exact fp32, self_attn.hip | `bf16`: its four products run on the
 bf16 matrix pipe, self_attn_bf16.hip), the SpecAugment keys and conv_channels / feature_blocks (listener.py).  Refused at
 construction: num_units not divisible by num_heads, a head width other than 32 or 64 (self_attn.hip), any other value of
-attention_precision, and the keys `layer_norm` and `recurrent_precision`, which mean nothing here."""
+attention_precision, an attention_dropout that is no finite number in (0, 1], and the keys `layer_norm` and `recurrent_precision`, which mean nothing here."""
 import numpy as np
 import torch
 
@@ -94,6 +96,19 @@ def attention_precision_key(conf):
     return value
 
 
+def attention_dropout_key(conf):
+    """the `attention_dropout` cfg key: the KEEP probability of the dropout on the attention probabilities, like `dropout`
+    (a build addition like attention_precision: absent from the defaults files, 1.0 when absent)"""
+    text = str(conf.get('attention_dropout', '1.0')).strip()
+    try:
+        value = float(text)
+    except ValueError:
+        value = float('nan')
+    if not (np.isfinite(value) and 0 < value <= 1):
+        raise ValueError('transformer encoder: attention_dropout is a keep probability, a number in (0, 1]; got %r' % text)
+    return value
+
+
 class Transformer(ed_encoder.EDEncoder):
     """cfg keys: see the module's docstring"""
 
@@ -111,12 +126,14 @@ class Transformer(ed_encoder.EDEncoder):
             raise ValueError('transformer encoder: num_units / num_heads = %d: the attention kernels take a head width of '
                              '32 or 64 and at most 1024 units' % (units // heads))
         attention_precision_key(self.conf)
+        attention_dropout_key(self.conf)
 
     def encode(self, inputs, input_seq_length, is_training):
         layer.GEMM_PRECISION[0] = precision = self.conf.get('gemm_precision', 'default')
         layer.ATTENTION_PRECISION[0] = attention_precision_key(self.conf)
         units, heads, ff = (int(self.conf[k]) for k in ('num_units', 'num_heads', 'ff_units'))
         keep = float(self.conf['dropout'])
+        self.attention_keep = attention_dropout_key(self.conf) if is_training else 1.0
         encoded, encoded_seq_length = {}, dict(input_seq_length)
         for name, x in inputs.items():
             with vs.variable_scope(name):
@@ -133,4 +150,4 @@ class Transformer(ed_encoder.EDEncoder):
 
     def block(self, x, lens, heads, ff, keep, scope):
         """one block of the stack (conformer.py puts its own here)"""
-        return layer.self_attention_block(x, lens, heads, ff, keep, scope=scope)
+        return layer.self_attention_block(x, lens, heads, ff, keep, scope=scope, attention_keep=self.attention_keep)

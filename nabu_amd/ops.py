@@ -1134,7 +1134,8 @@ _ATTN_ENTRY = {'f32': 'nabu_self_attn', 'bf16': 'nabu_self_attn_bf16'}
 
 
 def _attn_entry(precision, what):
-    """the C entry point `what` (tile_q, tile_k, fwd, bwd) of the attention kernels at `precision`, and its name"""
+    """the C entry point `what` (tile_q, tile_k, fwd, bwd, drop_fwd, drop_bwd) of the attention kernels at `precision`,
+    and its name"""
     if precision not in _ATTN_ENTRY:
         raise _hip.NabuHipError("self_attn: precision %r is not one of 'f32' (self_attn.hip) and 'bf16' "
                                 "(self_attn_bf16.hip)" % (precision,))
@@ -1160,21 +1161,31 @@ def _attn_shape(qkv, heads):
     return B, T, int(heads), W // (3 * heads), ld
 
 
-def self_attn_fwd(qkv, len_dev, heads, precision='f32'):
+def _attn_drop(keep, rng):
+    """the (keep, seed, offset) arguments of the dropout entry points, or () for the plain ones: keep == 1 or no rng"""
+    return () if rng is None or keep == 1 else (float(keep), int(rng[0]), int(rng[1]))
+
+
+def self_attn_fwd(qkv, len_dev, heads, precision='f32', keep=1.0, rng=None):
     """(o [B,T,D], lse [B,H,T]) of multi-head self-attention over the frames < len of each row (nabu_self_attn_fwd, or
-    nabu_self_attn_bf16_fwd at precision 'bf16': the products on the bf16 matrix pipe, include/nabu_hip.h)"""
-    fn, name = _attn_entry(precision, 'fwd')
+    nabu_self_attn_bf16_fwd at precision 'bf16': the products on the bf16 matrix pipe, include/nabu_hip.h).  keep < 1 with
+    rng = (seed, offset): dropout on the attention probabilities inside the kernel (nabu_self_attn[_bf16]_drop_fwd); lse
+    is the undropped one.  keep == 1 or rng None is the plain call."""
+    drop = _attn_drop(keep, rng)
+    fn, name = _attn_entry(precision, 'drop_fwd' if drop else 'fwd')
     B, T, H, dk, ld = _attn_shape(qkv, heads)
     o = torch.empty((B, T, H * dk), dtype=torch.float32, device=qkv.device)
     lse = torch.empty((B, H, T), dtype=torch.float32, device=qkv.device)
-    check(fn(B, T, H, dk, qkv.data_ptr(), ld, ptr(len_dev), ptr(o), ptr(lse), stream()), name)
+    check(fn(B, T, H, dk, qkv.data_ptr(), ld, ptr(len_dev), *drop, ptr(o), ptr(lse), stream()), name)
     return o, lse
 
 
-def self_attn_bwd(qkv, o, lse, do, len_dev, heads, precision='f32'):
+def self_attn_bwd(qkv, o, lse, do, len_dev, heads, precision='f32', keep=1.0, rng=None):
     """dqkv, of qkv's shape and strides, from the forward call's o and lse and do [B,T,D] (nabu_self_attn_bwd, or
-    nabu_self_attn_bf16_bwd at precision 'bf16'; the precision of the forward call that made o and lse)"""
-    fn, name = _attn_entry(precision, 'bwd')
+    nabu_self_attn_bf16_bwd at precision 'bf16'; the precision, keep and rng of the forward call that made o and lse:
+    the kernels make the forward call's mask again)"""
+    drop = _attn_drop(keep, rng)
+    fn, name = _attn_entry(precision, 'drop_bwd' if drop else 'bwd')
     B, T, H, dk, ld = _attn_shape(qkv, heads)
     if tuple(do.shape) != tuple(o.shape) or tuple(o.shape) != (B, T, H * dk) or tuple(lse.shape) != (B, H, T):
         raise _hip.NabuHipError('self_attn_bwd: o %s, do %s, lse %s do not fit qkv %s' %
@@ -1183,7 +1194,7 @@ def self_attn_bwd(qkv, o, lse, do, len_dev, heads, precision='f32'):
     buf = torch.empty((B, T, ld), dtype=torch.float32, device=qkv.device) if ld == 3 * H * dk else \
         torch.zeros((B, T, ld), dtype=torch.float32, device=qkv.device)
     check(fn(B, T, H, dk, qkv.data_ptr(), ld, ptr(_f32(o, 'o')), ptr(_f32(lse, 'lse')), ptr(_f32(do, 'do')), ptr(len_dev),
-             ptr(buf), stream()), name)
+             *drop, ptr(buf), stream()), name)
     return buf[:, :, :3 * H * dk]
 
 

@@ -12,13 +12,21 @@ dk 64 and T 250 (the transformer_ctc recipe behind its front end) and T 1000 (wi
             torch.autograd.grad as its backward side), the three sides alternating in one run.  The bar: no slower than
             the fp32 kernels; the ratio against bf16 SDPA is for information
 
+  --dropout instead of all of the above: the kernels with dropout on the attention probabilities (keep 0.9), fp32 and
+            bf16, forward and whole backward call, against the plain kernels on the same operands and ONE nabu_dropout_f32
+            launch over B H T T floats.  The bars: forward no slower than plain + one such pass, backward no slower
+            than plain + two (the mask alone costs an unfused implementation at least that).  With --parent-lib, the
+            plain kernels of a library built from the parent commit run beside this build's: the ratio must lie inside
+            the spread
+
 The bar, forward and backward: no slower.  Lengths are drawn uniformly from T/2 .. T (one row at T).
 Protocol of the other tools: warm-up, then medians of --rounds rounds of --calls calls between device events, the two
 sides of a comparison alternating round by round in the same run; the spread of the round times is reported with them.
 Prints one JSON line (and writes it to --out).
 
     python tools/self_attn_bench.py [--rounds 5] [--calls 200] [--out profiles/self_attn.json]
-    python tools/self_attn_bench.py --bf16 --out profiles/self_attn_bf16.json"""
+    python tools/self_attn_bench.py --bf16 --out profiles/self_attn_bf16.json
+    python tools/self_attn_bench.py --dropout [--parent-lib PATH] --out profiles/self_attn_dropout.json"""
 import argparse
 import json
 import os
@@ -110,6 +118,50 @@ def attn_bf16_bench(T, rounds, calls):
     return res
 
 
+def attn_dropout_bench(T, rounds, calls, parent):
+    """the dropout kernels (keep 0.9) of both precisions, the plain kernels on the same operands and one nabu_dropout_f32
+    pass over B H T T floats (what the mask alone costs an unfused implementation, once forward and twice backward),
+    alternating in one run; with `parent` (a libnabu_hip.so built from the parent commit) its plain kernels too"""
+    D, keep, rng = H * DK, 0.9, (1234, 5)
+    g = torch.Generator(device='cuda').manual_seed(1)
+    qkv = torch.randn((B, T, 3 * D), device='cuda', generator=g)
+    do = torch.randn((B, T, D), device='cuda', generator=g)
+    host_lens = np.random.default_rng(1).integers(T // 2, T + 1, B).astype(np.int32)
+    host_lens[0] = T
+    lens = torch.from_numpy(host_lens).cuda()
+    probs = torch.rand((B * H * T * T,), device='cuda', generator=g)
+    names, fns, kept = [], [], {}
+    for p in ('f32', 'bf16'):
+        for tag, kw in (('drop', dict(keep=keep, rng=rng)), ('plain', {})):
+            o, lse = kept[p, tag] = hip.self_attn_fwd(qkv, lens, H, p, **kw)
+            names += ['fwd_%s_%s' % (tag, p), 'bwd_%s_%s' % (tag, p)]
+            fns += [lambda p=p, kw=kw: hip.self_attn_fwd(qkv, lens, H, p, **kw),
+                    lambda p=p, kw=kw, o=o, lse=lse: hip.self_attn_bwd(qkv, o, lse, do, lens, H, p, **kw)]
+    names.append('dropout_pass')
+    fns.append(lambda: hip.dropout(probs, keep, *rng))
+    if parent is not None:
+        from nabu_amd import _hip
+        out_o, out_lse, out_d = torch.empty_like(do), torch.empty((B, H, T), device='cuda'), torch.empty_like(qkv)
+        for p, stem in (('f32', 'nabu_self_attn'), ('bf16', 'nabu_self_attn_bf16')):
+            o, lse = kept[p, 'plain']
+            names += ['fwd_parent_%s' % p, 'bwd_parent_%s' % p]
+            fns += [lambda f=getattr(parent, stem + '_fwd'): f(B, T, H, DK, qkv.data_ptr(), 3 * D, lens.data_ptr(), out_o.data_ptr(),
+                                                                out_lse.data_ptr(), _hip.stream()),
+                    lambda f=getattr(parent, stem + '_bwd'), o=o, lse=lse: f(B, T, H, DK, qkv.data_ptr(), 3 * D, o.data_ptr(), lse.data_ptr(),
+                                                                             do.data_ptr(), lens.data_ptr(), out_d.data_ptr(), _hip.stream())]
+    res = {'shape': [B, T, H, DK], 'keep': keep}
+    for name, (ms, spread) in zip(names, rounds_ms(fns, rounds, calls)):
+        res[name + '_ms'], res[name + '_spread'] = round(ms, 4), [round(x, 4) for x in spread]
+    for p in ('f32', 'bf16'):
+        for d, passes in (('fwd', 1), ('bwd', 2)):
+            new, bar = res['%s_drop_%s_ms' % (d, p)], res['%s_plain_%s_ms' % (d, p)] + passes * res['dropout_pass_ms']
+            res['%s_%s_drop_over_plain' % (d, p)] = round(new / res['%s_plain_%s_ms' % (d, p)], 3)
+            res['%s_%s_bar_ms' % (d, p)], res['%s_%s_bar' % (d, p)] = round(bar, 4), 'met' if new <= bar else 'missed'
+            if parent is not None:
+                res['%s_%s_plain_over_parent' % (d, p)] = round(res['%s_plain_%s_ms' % (d, p)] / res['%s_parent_%s_ms' % (d, p)], 4)
+    return res
+
+
 def step_bench(rounds, calls):
     from nabu_amd.neuralnetworks.trainers import trainer_factory
     data = SyntheticData(8, 200, 123, min_frames=120, min_labels=5, max_labels=20, time_reduction=4, seed=2234)
@@ -138,10 +190,25 @@ def main():
     ap.add_argument('--calls', type=int, default=200)
     ap.add_argument('--out', default=None, help='also write the JSON line to this file')
     ap.add_argument('--bf16', action='store_true', help='the bf16 kernels against the fp32 kernels and bf16 SDPA, nothing else')
+    ap.add_argument('--dropout', action='store_true', help='the attention-dropout kernels against the plain kernels plus '
+                    'separate dropout passes, nothing else')
+    ap.add_argument('--parent-lib', default=None, help='with --dropout: a libnabu_hip.so built from the parent commit, whose '
+                    'plain kernels are timed beside this build\'s')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'self_attn_bench needs a GPU'
     torch.cuda.set_device(0)
-    if args.bf16:
+    if args.dropout:
+        parent = None
+        if args.parent_lib:
+            import ctypes
+            from nabu_amd import _hip
+            parent = ctypes.CDLL(os.path.abspath(args.parent_lib))
+            for stem in ('nabu_self_attn', 'nabu_self_attn_bf16'):
+                for what in ('_fwd', '_bwd'):
+                    getattr(parent, stem + what).restype, getattr(parent, stem + what).argtypes = _hip.SIGNATURES[stem + what]
+        res = {'bench': 'self_attn_dropout', 'rounds': args.rounds, 'calls': args.calls, 'device': torch.cuda.get_device_name(0),
+               'parent_lib': bool(parent), 'attention': [attn_dropout_bench(T, args.rounds, args.calls, parent) for T in (250, 1000)]}
+    elif args.bf16:
         res = {'bench': 'self_attn_bf16', 'rounds': args.rounds, 'calls': args.calls, 'device': torch.cuda.get_device_name(0),
                'attention': [attn_bf16_bench(T, args.rounds, args.calls) for T in (250, 1000)]}
     else:
