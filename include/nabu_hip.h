@@ -1582,6 +1582,41 @@ int nabu_self_attn_bf16_drop_bwd(int B, int T, int H, int dk, const float *qkv, 
                                  const float *lse, const float *d_o, const int32_t *len, float keep,
                                  unsigned long long seed, unsigned long long offset, float *dqkv, nabu_stream_t stream);
 
+/* Chunk-limited attention, inside the kernels of both precisions (the WIN instantiations of self_attn.hip and
+ * self_attn_bf16.hip; csrc/attn_win.h).  With chunk C >= 1 and left_chunks Lc >= -1 (-1: all chunks to the left), query
+ * i of an utterance of length len sees key j iff lo(i) <= j < hi(i), in integer division
+ *     hi(i) = min(len, (i / C + 1) C);     lo(i) = 0 if Lc < 0, else max(0, (i / C - Lc) C)
+ * — its own chunk and Lc chunks to its left (WeNet's static_chunk_size / num_decoding_left_chunks, ESPnet's chunk mask).
+ * C = 1, Lc = -1 is causal attention; C >= len is the attention of the plain entry points.  Every query i < len sees key
+ * i, so no row is empty.  The softmax, lse and every gradient run over the visible keys only: a key outside the window
+ * is left out exactly as a key at or past len is, by a select.  With keep < 1 the dropout mask of the _drop_ entry points
+ * is applied on top, the same function of (seed, offset, b, h, q, k); keep == 1 means no dropout (seed and offset are
+ * then ignored), and lse is over the visible, undropped probabilities.
+ * THE TILES WALKED depend on len[b], C and Lc only, never on T: a workgroup that owns queries q0 .. q0 + 127 walks the
+ * key tiles floor(lo(q0) / TK) .. ceil(hi(min(q0 + 127, len - 1)) / TK) - 1, and one that owns keys k0 .. k0 + 127 (dK,
+ * dV) the query tiles that hold a query seeing one of them; tile boundaries stay multiples of TK counted from row 0, so
+ * the order of summation is fixed and an utterance keeps the bits it gets alone.  At C >= T the walk and every select
+ * are the plain kernels': the plain entry points' bits.  Cost is O(T window) instead of O(T^2).
+ * Operands, THE LENGTH RULE, where bf16 rounds (a probability outside the window is +0.0 before it is rounded) and every
+ * guarantee of the _drop_ entry points hold word for word (rows >= len are +0.0, no float atomics, no workspace, two
+ * backward launches, two calls give equal bits), and so does every refusal, T > 2^20 and keep included, with these
+ * functions' names in the messages; two refusals are added: chunk < 1 and left_chunks < -1.  Larger values are clamped
+ * on the host so that nothing overflows an int in the kernels: C > T is C = T, and an Lc whose window reaches frame 0
+ * from the last chunk is -1. */
+int nabu_self_attn_win_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len, float keep,
+                           unsigned long long seed, unsigned long long offset, int chunk, int left_chunks, float *o,
+                           float *lse, nabu_stream_t stream);
+int nabu_self_attn_win_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o, const float *lse,
+                           const float *d_o, const int32_t *len, float keep, unsigned long long seed,
+                           unsigned long long offset, int chunk, int left_chunks, float *dqkv, nabu_stream_t stream);
+int nabu_self_attn_bf16_win_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len, float keep,
+                                unsigned long long seed, unsigned long long offset, int chunk, int left_chunks, float *o,
+                                float *lse, nabu_stream_t stream);
+int nabu_self_attn_bf16_win_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o,
+                                const float *lse, const float *d_o, const int32_t *len, float keep,
+                                unsigned long long seed, unsigned long long offset, int chunk, int left_chunks,
+                                float *dqkv, nabu_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Conformer encoder (conv_module.hip): the core of the block's convolution module (Gulati et al. 2020) between its two
  * pointwise products, on a ragged padded batch, fp32.  u [B, T, 2 D] with row stride ld >= 2 D (ld % 4 == 0, 16-byte

@@ -268,6 +268,13 @@ SIGNATURES = {
     'nabu_self_attn_bf16_drop_fwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _vp, _vp, _vp]),
     'nabu_self_attn_bf16_drop_bwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _c.c_ulonglong, _c.c_ulonglong,
                                           _vp, _vp]),
+    # the same under a chunk window: (chunk, left_chunks) after (keep, seed, offset); keep = 1 is no dropout
+    'nabu_self_attn_win_fwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _i, _i, _vp, _vp, _vp]),
+    'nabu_self_attn_win_bwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _i, _i,
+                                    _vp, _vp]),
+    'nabu_self_attn_bf16_win_fwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _i, _i, _vp, _vp, _vp]),
+    'nabu_self_attn_bf16_win_bwd': (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _c.c_ulonglong, _c.c_ulonglong, _i, _i,
+                                         _vp, _vp]),
     'nabu_add_positions_f32': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     'nabu_conv_module_tile_t': (_i, []),
     'nabu_conv_module_parts': (_i, [_i, _i]),

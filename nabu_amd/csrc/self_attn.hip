@@ -22,6 +22,19 @@
 //     consecutive words.  Rows at or past len[b] are staged as zeros, whatever memory holds.
 //   * The running maximum starts at -FLT_MAX and a masked key is left out by a select, never by an infinity: every tile
 //     walked has a key below len[b], so the maximum is finite from the first tile on and exp(m_old - m_new) is 0 or finite.
+// THE WINDOW (the WIN instantiations, nabu_self_attn_win_*; attn_win.h): query i sees keys lo(i) <= j < hi(i).  A lane
+// computes its interval once in the prologue and tests (unsigned)(j - lo) < hi - lo where the plain kernels test j < len.
+// A workgroup walks the key tiles from lo(its first query) / 32 to ceil(hi(its last query below len) / 32) - 1, tile
+// boundaries still multiples of 32 counted from key 0 and the double buffer primed at the first walked tile; the dK/dV
+// workgroup walks the query tiles from qlo(its first key) to qhi(its last key below len), and its predicate is the key's
+// interval of queries (the lane's, with the query index running over the registers).  The walk depends on len[b], C and
+// Lc only.  THE INVARIANT that replaces "every tile walked has a key below len": every query below len sees its own
+// key, and the walk covers lo..hi of every query the workgroup owns, so every lane meets at least one key it sees —
+// but not in every tile.  In a tile where a lane sees nothing, before its window or after it, the tile maximum stays
+// -FLT_MAX, so m_new = m_old and the rescale is exp(0) = 1 exactly, also while m is still -FLT_MAX; all sixteen
+// probabilities are selected to 0, so l and the accumulators keep their bits (l stays 0, m stays -FLT_MAX until the first
+// seen key, where the rescale exp(-FLT_MAX - m_new) is 0 and multiplies zeros).  Nothing is ever left out by an infinity,
+// and the backward kernels select P = exp(s - lse) to 0 outside the window whatever s is.  At the end l > 0 for every lane.
 // BACKWARD, two kernels, each recomputing its score tiles from lse; no float atomics, no workspace, no reduce pass.
 //   * attn_bwd_dq_kernel: the forward kernel's shape (queries owned, K and V tiles streamed).  S^T = K Q^T and
 //     dP^T = V dO^T share the lane = query layout, so lse and delta = rowsum(dO . O) (computed in the prologue from the
@@ -35,6 +48,7 @@
 #include <float.h>
 
 #include "attn_drop.h"
+#include "attn_win.h"
 #include "gemm_args.h"
 
 namespace nabu {
@@ -49,6 +63,7 @@ struct AttnArgs {
   int B, T, H, ld;
   float scale;                                   // 1 / sqrt(dk)
   AttnDrop drop;                                 // read by the DROP instantiations only (attn_drop.h)
+  AttnWin win;                                   // read by the WIN instantiations only (attn_win.h)
 };
 
 // row index of accumulator register r within a 32 x 32 tile, for the half-wave lk
@@ -127,7 +142,7 @@ __device__ __forceinline__ void store_acc_t(float *dst, const f32x16 (&acc)[DK /
     }
 }
 
-template <int DK, bool DROP>
+template <int DK, bool DROP, bool WIN>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
   constexpr int TILE = ATTN_K * (DK + 1);
   __shared__ float Ks[2][TILE], Vs[2][TILE];
@@ -156,14 +171,21 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
   float m = -FLT_MAX, l = 0.f;
 
   TileRegs<DK> kr, vr;
-  const int ntiles = (len + ATTN_K - 1) / ATTN_K;            // depends on len[b] only, never on T
-  kr.load(base + D, a.ld, len, tid);
-  vr.load(base + 2 * D, a.ld, len, tid);
+  int first = 0, ntiles = (len + ATTN_K - 1) / ATTN_K;   // depend on len[b] (and the window) only, never on T
+  WinSpan see = {};                                          // WIN: the keys this lane's query sees
+  if constexpr (WIN) {                                       // the tiles from lo(first query) to hi(last query below len)
+    see = win_keys(a.win, min(qi, len - 1), len);
+    first = win_keys(a.win, q0, len).start / ATTN_K;
+    ntiles = (win_keys(a.win, min(q0 + ATTN_Q, len) - 1, len).end() + ATTN_K - 1) / ATTN_K;
+  }
+  auto sees = [&](int k) { if constexpr (WIN) return see.has(k); else return k < len; };
+  kr.load(base + D + (size_t)first * ATTN_K * a.ld, a.ld, len - first * ATTN_K, tid);
+  vr.load(base + 2 * D + (size_t)first * ATTN_K * a.ld, a.ld, len - first * ATTN_K, tid);
   kr.store(Ks[0], tid);
   vr.store(Vs[0], tid);
   __syncthreads();
-  for (int it = 0; it < ntiles; ++it) {
-    const int k0 = it * ATTN_K, cur = it & 1;
+  for (int it = first; it < ntiles; ++it) {
+    const int k0 = it * ATTN_K, cur = (it - first) & 1;
     const bool more = it + 1 < ntiles;
     if (more) {
       kr.load(base + D + (size_t)(k0 + ATTN_K) * a.ld, a.ld, len - k0 - ATTN_K, tid);
@@ -176,7 +198,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       p[r] = s[r] * a.scale;
-      if (k0 + acc_row(r, lk) < len) mt = fmaxf(mt, p[r]);
+      if (sees(k0 + acc_row(r, lk))) mt = fmaxf(mt, p[r]);
     }
     mt = fmaxf(mt, __shfl_xor(mt, 32));
     const float mn = fmaxf(m, mt);
@@ -184,7 +206,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
     float ps = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      p[r] = k0 + acc_row(r, lk) < len ? expf(p[r] - mn) : 0.f;
+      p[r] = sees(k0 + acc_row(r, lk)) ? expf(p[r] - mn) : 0.f;
       ps += p[r];                                            // the undropped probability
       if constexpr (DROP) p[r] *= attn_drop_scale(a.drop, kept, r);
     }
@@ -208,7 +230,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
   if (lk == 0) *lse_p = pad ? 0.f : m + logf(l);
 }
 
-template <int DK, bool DROP>
+template <int DK, bool DROP, bool WIN>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
   constexpr int TILE = ATTN_K * (DK + 1);
   __shared__ float Ks[2][TILE], Vs[2][TILE];
@@ -243,14 +265,21 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
     for (int r = 0; r < 16; ++r) dq[blk][r] = 0.f;
 
   TileRegs<DK> kr, vr;
-  const int ntiles = (len + ATTN_K - 1) / ATTN_K;
-  kr.load(base + D, a.ld, len, tid);
-  vr.load(base + 2 * D, a.ld, len, tid);
+  int first = 0, ntiles = (len + ATTN_K - 1) / ATTN_K;
+  WinSpan see = {};                                          // WIN: the keys this lane's query sees
+  if constexpr (WIN) {                                       // the tiles from lo(first query) to hi(last query below len)
+    see = win_keys(a.win, min(qi, len - 1), len);
+    first = win_keys(a.win, q0, len).start / ATTN_K;
+    ntiles = (win_keys(a.win, min(q0 + ATTN_Q, len) - 1, len).end() + ATTN_K - 1) / ATTN_K;
+  }
+  auto sees = [&](int k) { if constexpr (WIN) return see.has(k); else return k < len; };
+  kr.load(base + D + (size_t)first * ATTN_K * a.ld, a.ld, len - first * ATTN_K, tid);
+  vr.load(base + 2 * D + (size_t)first * ATTN_K * a.ld, a.ld, len - first * ATTN_K, tid);
   kr.store(Ks[0], tid);
   vr.store(Vs[0], tid);
   __syncthreads();
-  for (int it = 0; it < ntiles; ++it) {
-    const int k0 = it * ATTN_K, cur = it & 1;
+  for (int it = first; it < ntiles; ++it) {
+    const int k0 = it * ATTN_K, cur = (it - first) & 1;
     const bool more = it + 1 < ntiles;
     if (more) {
       kr.load(base + D + (size_t)(k0 + ATTN_K) * a.ld, a.ld, len - k0 - ATTN_K, tid);
@@ -263,7 +292,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
     float ds[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float p = k0 + acc_row(r, lk) < len ? expf(s[r] * a.scale - lse) : 0.f;
+      const float p = sees(k0 + acc_row(r, lk)) ? expf(s[r] * a.scale - lse) : 0.f;
       if constexpr (DROP) ds[r] = p * (dp[r] * attn_drop_scale(a.drop, kept, r) - delta);   // dP = d . (dO V^T)
       else ds[r] = p * (dp[r] - delta);
     }
@@ -277,7 +306,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
   if (qi < a.T) store_acc_t<DK>(dqrow, dq, a.scale, qi >= len, lk);
 }
 
-template <int DK, bool DROP>
+template <int DK, bool DROP, bool WIN>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
   constexpr int TILE = ATTN_K * (DK + 1);
   constexpr int PPR = DK / 4;                                // 16-byte pieces per row
@@ -336,12 +365,20 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
     if (tid < ATTN_K) lse_s[buf][tid] = lse_r;
   };
 
-  const int ntiles = (len + ATTN_K - 1) / ATTN_K;
-  gload(0);
+  int first = 0, ntiles = (len + ATTN_K - 1) / ATTN_K;
+  WinSpan seen = {};                                         // WIN: the queries that see this lane's key (none past len)
+  if constexpr (WIN) {                                       // the query tiles from qlo(first key) to qhi(last key below len)
+    seen = win_queries(a.win, min(ki, len - 1), len);
+    if (!kvalid) seen.span = 0;
+    first = win_queries(a.win, k0, len).start / ATTN_K;
+    ntiles = (win_queries(a.win, min(k0 + ATTN_Q, len) - 1, len).end() + ATTN_K - 1) / ATTN_K;
+  }
+  auto seen_by = [&](int q) { if constexpr (WIN) return seen.has(q); else return kvalid && q < len; };
+  gload(first * ATTN_K);
   sstore(0);
   __syncthreads();
-  for (int it = 0; it < ntiles; ++it) {
-    const int t0 = it * ATTN_K, cur = it & 1;
+  for (int it = first; it < ntiles; ++it) {
+    const int t0 = it * ATTN_K, cur = (it - first) & 1;
     const bool more = it + 1 < ntiles;
     if (more) gload(t0 + ATTN_K);
     unsigned kept = 0;
@@ -352,7 +389,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int qq = acc_row(r, lk);
-      p[r] = (kvalid && t0 + qq < len) ? expf(s[r] * a.scale - lse_s[cur][qq]) : 0.f;
+      p[r] = seen_by(t0 + qq) ? expf(s[r] * a.scale - lse_s[cur][qq]) : 0.f;
       if constexpr (DROP) {                                            // dS keeps the undropped P; dV takes d . P
         const float d = attn_drop_scale(a.drop, kept, r);
         ds[r] = p[r] * (dp[r] * d - delta_s[cur][qq]);
@@ -400,9 +437,10 @@ using namespace nabu;
 extern "C" int nabu_self_attn_tile_q(void) { return ATTN_Q; }
 extern "C" int nabu_self_attn_tile_k(void) { return ATTN_K; }
 
-// the forward launch of nabu_self_attn_fwd (drop == nullptr, or keep == 1: the plain instantiations) and nabu_self_attn_drop_fwd
+// the forward launch of nabu_self_attn_fwd (drop == nullptr, or keep == 1: the plain instantiations), of
+// nabu_self_attn_drop_fwd and of nabu_self_attn_win_fwd (win != nullptr: the WIN instantiations, at every C)
 static int attn_fwd_launch(const char *what, int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len,
-                           const AttnDrop *drop, float *o, float *lse, nabu_stream_t stream) {
+                           const AttnDrop *drop, const AttnWin *win, float *o, float *lse, nabu_stream_t stream) {
   NABU_TRY(attn_shape(what, B, T, H, dk, ld));
   NABU_CHECK_ARG(qkv && len && o && lse, "%s: null pointer", what);
   NABU_CHECK_ARG(attn_al16(qkv) && attn_al16(o), "%s: qkv and o must be 16-byte aligned", what);
@@ -412,21 +450,17 @@ static int attn_fwd_launch(const char *what, int B, int T, int H, int dk, const 
   a.B = B; a.T = T; a.H = H; a.ld = ld; a.scale = 1.f / sqrtf((float)dk);
   const dim3 grid((T + ATTN_Q - 1) / ATTN_Q, H, B);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (drop && drop->keep < 1.f) {
-    a.drop = *drop;
-    if (dk == 64) hipLaunchKernelGGL((attn_fwd_kernel<64, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<32, true>), grid, dim3(256), 0, s, a);
-  } else {
-    if (dk == 64) hipLaunchKernelGGL((attn_fwd_kernel<64, false>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<32, false>), grid, dim3(256), 0, s, a);
-  }
+  const bool dropping = drop && drop->keep < 1.f;
+  if (dropping) a.drop = *drop;
+  if (win) a.win = *win;
+  ATTN_LAUNCH(attn_fwd_kernel, dk, dropping, win != nullptr, grid, s, a);
   NABU_LAUNCH_CHECK();
   return 0;
 }
 
 static int attn_bwd_launch(const char *what, int B, int T, int H, int dk, const float *qkv, int ld, const float *o,
-                           const float *lse, const float *d_o, const int32_t *len, const AttnDrop *drop, float *dqkv,
-                           nabu_stream_t stream) {
+                           const float *lse, const float *d_o, const int32_t *len, const AttnDrop *drop, const AttnWin *win,
+                           float *dqkv, nabu_stream_t stream) {
   NABU_TRY(attn_shape(what, B, T, H, dk, ld));
   NABU_CHECK_ARG(qkv && o && lse && d_o && len && dqkv, "%s: null pointer", what);
   NABU_CHECK_ARG(attn_al16(qkv) && attn_al16(o) && attn_al16(d_o) && attn_al16(dqkv),
@@ -437,34 +471,23 @@ static int attn_bwd_launch(const char *what, int B, int T, int H, int dk, const 
   a.B = B; a.T = T; a.H = H; a.ld = ld; a.scale = 1.f / sqrtf((float)dk);
   const dim3 grid((T + ATTN_Q - 1) / ATTN_Q, H, B);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (drop && drop->keep < 1.f) {
-    a.drop = *drop;
-    if (dk == 64) {
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, true>), grid, dim3(256), 0, s, a);
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<64, true>), grid, dim3(256), 0, s, a);
-    } else {
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, true>), grid, dim3(256), 0, s, a);
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<32, true>), grid, dim3(256), 0, s, a);
-    }
-  } else if (dk == 64) {
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, false>), grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<64, false>), grid, dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, false>), grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<32, false>), grid, dim3(256), 0, s, a);
-  }
+  const bool dropping = drop && drop->keep < 1.f;
+  if (dropping) a.drop = *drop;
+  if (win) a.win = *win;
+  ATTN_LAUNCH(attn_bwd_dkv_kernel, dk, dropping, win != nullptr, grid, s, a);
+  ATTN_LAUNCH(attn_bwd_dq_kernel, dk, dropping, win != nullptr, grid, s, a);
   NABU_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int nabu_self_attn_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len, float *o,
                                   float *lse, nabu_stream_t stream) {
-  return attn_fwd_launch("self_attn_fwd", B, T, H, dk, qkv, ld, len, nullptr, o, lse, stream);
+  return attn_fwd_launch("self_attn_fwd", B, T, H, dk, qkv, ld, len, nullptr, nullptr, o, lse, stream);
 }
 
 extern "C" int nabu_self_attn_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o, const float *lse,
                                   const float *d_o, const int32_t *len, float *dqkv, nabu_stream_t stream) {
-  return attn_bwd_launch("self_attn_bwd", B, T, H, dk, qkv, ld, o, lse, d_o, len, nullptr, dqkv, stream);
+  return attn_bwd_launch("self_attn_bwd", B, T, H, dk, qkv, ld, o, lse, d_o, len, nullptr, nullptr, dqkv, stream);
 }
 
 extern "C" int nabu_self_attn_drop_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len, float keep,
@@ -472,7 +495,7 @@ extern "C" int nabu_self_attn_drop_fwd(int B, int T, int H, int dk, const float 
                                        nabu_stream_t stream) {
   AttnDrop d;
   NABU_TRY(attn_drop_args("self_attn_drop_fwd", T, keep, seed, offset, &d));
-  return attn_fwd_launch("self_attn_drop_fwd", B, T, H, dk, qkv, ld, len, &d, o, lse, stream);
+  return attn_fwd_launch("self_attn_drop_fwd", B, T, H, dk, qkv, ld, len, &d, nullptr, o, lse, stream);
 }
 
 extern "C" int nabu_self_attn_drop_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o,
@@ -481,7 +504,28 @@ extern "C" int nabu_self_attn_drop_bwd(int B, int T, int H, int dk, const float 
                                        nabu_stream_t stream) {
   AttnDrop d;
   NABU_TRY(attn_drop_args("self_attn_drop_bwd", T, keep, seed, offset, &d));
-  return attn_bwd_launch("self_attn_drop_bwd", B, T, H, dk, qkv, ld, o, lse, d_o, len, &d, dqkv, stream);
+  return attn_bwd_launch("self_attn_drop_bwd", B, T, H, dk, qkv, ld, o, lse, d_o, len, &d, nullptr, dqkv, stream);
+}
+
+extern "C" int nabu_self_attn_win_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len, float keep,
+                                      unsigned long long seed, unsigned long long offset, int chunk, int left_chunks,
+                                      float *o, float *lse, nabu_stream_t stream) {
+  AttnDrop d;
+  AttnWin w;
+  NABU_TRY(attn_drop_args("self_attn_win_fwd", T, keep, seed, offset, &d));
+  NABU_TRY(attn_win_args("self_attn_win_fwd", T, chunk, left_chunks, &w));
+  return attn_fwd_launch("self_attn_win_fwd", B, T, H, dk, qkv, ld, len, &d, &w, o, lse, stream);
+}
+
+extern "C" int nabu_self_attn_win_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o,
+                                      const float *lse, const float *d_o, const int32_t *len, float keep,
+                                      unsigned long long seed, unsigned long long offset, int chunk, int left_chunks,
+                                      float *dqkv, nabu_stream_t stream) {
+  AttnDrop d;
+  AttnWin w;
+  NABU_TRY(attn_drop_args("self_attn_win_bwd", T, keep, seed, offset, &d));
+  NABU_TRY(attn_win_args("self_attn_win_bwd", T, chunk, left_chunks, &w));
+  return attn_bwd_launch("self_attn_win_bwd", B, T, H, dk, qkv, ld, o, lse, d_o, len, &d, &w, dqkv, stream);
 }
 
 extern "C" int nabu_add_positions_f32(int B, int T, int D, float *x, const float *pe, const int32_t *len,

@@ -46,10 +46,20 @@
 // per thread and 64-row tile against 32 to 64 fragment reads, and were left so.
 // Rows at or past len[b] are staged as zeros, whatever memory holds.  The running maximum starts at -FLT_MAX and a
 // masked key is left out by a select: every tile walked has a key below len[b], so no infinity and no NaN is ever made.
+// THE WINDOW (the WIN instantiations, nabu_self_attn_bf16_win_*; attn_win.h), as in self_attn.hip with the 64-key tile:
+// a lane's interval is computed once in the prologue and tested by one subtract and one unsigned compare per score, in
+// both halves of a tile; the walk runs from lo(first query) / 64 to ceil(hi(last query below len) / 64) - 1 (dK/dV: the
+// query tiles from qlo(first key) to qhi(last key below len)), boundaries multiples of 64 counted from row 0, the first
+// fetch at the first walked tile.  THE INVARIANT that replaces "every tile walked has a key below len": every lane meets
+// a key it sees somewhere on the walk (its own), but not in every tile; where it sees none, the tile maximum stays
+// -FLT_MAX, m_new = m_old, the rescale is 2^0 = 1 exactly (also while m is still -FLT_MAX), all 32 probabilities are
+// selected to +0.0 BEFORE v_cvt_pk_bf16_f32, and l and the accumulators keep their bits.  The backward kernels select
+// P = exp(s - lse) to 0 outside the window whatever s is.
 // Built with packed fp32 VALU instructions switched off (build.py, as self_attn.hip).
 #include <float.h>
 
 #include "attn_drop.h"
+#include "attn_win.h"
 #include "gemm_args.h"
 
 namespace nabu {
@@ -82,6 +92,7 @@ struct Attn16Args {
   int B, T, H, ld;
   float scale;                                   // 1 / sqrt(dk)
   AttnDrop drop;                                 // read by the DROP instantiations only (attn_drop.h)
+  AttnWin win;                                   // read by the WIN instantiations only (attn_win.h)
 };
 
 // row index of accumulator register r within a 32 x 32 tile, for the half-wave lk
@@ -214,7 +225,7 @@ __device__ __forceinline__ void store_acc_t(float *dst, const f32x16 (&acc)[DK /
     }
 }
 
-template <int DK, bool DROP>
+template <int DK, bool DROP, bool WIN>
 __global__ __launch_bounds__(256) void attn_bf16_fwd_kernel(Attn16Args a) {
   __shared__ __attribute__((aligned(16))) char Ks[2][A16<DK>::ROWS], Vt[2][A16<DK>::COLS];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lk = lane >> 5;
@@ -243,14 +254,21 @@ __global__ __launch_bounds__(256) void attn_bf16_fwd_kernel(Attn16Args a) {
 
   Block<DK, true, false> kb;
   Block<DK, false, true> vb;
-  const int ntiles = (len + A16_K - 1) / A16_K;              // depends on len[b] only, never on T
-  kb.load(base + D, a.ld, len, tid);
-  vb.load(base + 2 * D, a.ld, len, tid);
+  int first = 0, ntiles = (len + A16_K - 1) / A16_K;         // depend on len[b] (and the window) only, never on T
+  WinSpan see = {};                                          // WIN: the keys this lane's query sees
+  if constexpr (WIN) {                                       // the tiles from lo(first query) to hi(last query below len)
+    see = win_keys(a.win, min(qi, len - 1), len);
+    first = win_keys(a.win, q0, len).start / A16_K;
+    ntiles = (win_keys(a.win, min(q0 + A16_Q, len) - 1, len).end() + A16_K - 1) / A16_K;
+  }
+  auto sees = [&](int k) { if constexpr (WIN) return see.has(k); else return k < len; };
+  kb.load(base + D + (size_t)first * A16_K * a.ld, a.ld, len - first * A16_K, tid);
+  vb.load(base + 2 * D + (size_t)first * A16_K * a.ld, a.ld, len - first * A16_K, tid);
   kb.store(Ks[0], nullptr, tid);
   vb.store(nullptr, Vt[0], tid);
   __syncthreads();
-  for (int it = 0; it < ntiles; ++it) {
-    const int k0 = it * A16_K, cur = it & 1;
+  for (int it = first; it < ntiles; ++it) {
+    const int k0 = it * A16_K, cur = (it - first) & 1;
     const bool more = it + 1 < ntiles;
     if (more) {
       kb.load(base + D + (size_t)(k0 + A16_K) * a.ld, a.ld, len - k0 - A16_K, tid);
@@ -268,7 +286,7 @@ __global__ __launch_bounds__(256) void attn_bf16_fwd_kernel(Attn16Args a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         p[j][r] = s[r] * a.scale;
-        if (k0 + 32 * j + acc_row(r, lk) < len) mt = fmaxf(mt, p[j][r]);
+        if (sees(k0 + 32 * j + acc_row(r, lk))) mt = fmaxf(mt, p[j][r]);
       }
     }
     mt = fmaxf(mt, __shfl_xor(mt, 32));
@@ -279,7 +297,7 @@ __global__ __launch_bounds__(256) void attn_bf16_fwd_kernel(Attn16Args a) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        p[j][r] = k0 + 32 * j + acc_row(r, lk) < len ? exp_fast(p[j][r] - mn) : 0.f;
+        p[j][r] = sees(k0 + 32 * j + acc_row(r, lk)) ? exp_fast(p[j][r] - mn) : 0.f;
         ps += p[j][r];                                       // the unrounded, undropped probability
         if constexpr (DROP) p[j][r] *= attn_drop_scale(a.drop, kept[j], r);     // in fp32, before the rounding
       }
@@ -304,7 +322,7 @@ __global__ __launch_bounds__(256) void attn_bf16_fwd_kernel(Attn16Args a) {
   if (lk == 0) *lse_p = pad ? 0.f : m + logf(l);
 }
 
-template <int DK, bool DROP>
+template <int DK, bool DROP, bool WIN>
 __global__ __launch_bounds__(256) void attn_bf16_bwd_dq_kernel(Attn16Args a) {
   __shared__ __attribute__((aligned(16))) char Ks[2][A16<DK>::ROWS], Kt[2][A16<DK>::COLS], Vs[2][A16<DK>::ROWS];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lk = lane >> 5;
@@ -344,14 +362,21 @@ __global__ __launch_bounds__(256) void attn_bf16_bwd_dq_kernel(Attn16Args a) {
 
   Block<DK, true, true> kb;
   Block<DK, true, false> vb;
-  const int ntiles = (len + A16_K - 1) / A16_K;
-  kb.load(base + D, a.ld, len, tid);
-  vb.load(base + 2 * D, a.ld, len, tid);
+  int first = 0, ntiles = (len + A16_K - 1) / A16_K;
+  WinSpan see = {};                                          // WIN: the keys this lane's query sees
+  if constexpr (WIN) {                                       // the tiles from lo(first query) to hi(last query below len)
+    see = win_keys(a.win, min(qi, len - 1), len);
+    first = win_keys(a.win, q0, len).start / A16_K;
+    ntiles = (win_keys(a.win, min(q0 + A16_Q, len) - 1, len).end() + A16_K - 1) / A16_K;
+  }
+  auto sees = [&](int k) { if constexpr (WIN) return see.has(k); else return k < len; };
+  kb.load(base + D + (size_t)first * A16_K * a.ld, a.ld, len - first * A16_K, tid);
+  vb.load(base + 2 * D + (size_t)first * A16_K * a.ld, a.ld, len - first * A16_K, tid);
   kb.store(Ks[0], Kt[0], tid);
   vb.store(Vs[0], nullptr, tid);
   __syncthreads();
-  for (int it = 0; it < ntiles; ++it) {
-    const int k0 = it * A16_K, cur = it & 1;
+  for (int it = first; it < ntiles; ++it) {
+    const int k0 = it * A16_K, cur = (it - first) & 1;
     const bool more = it + 1 < ntiles;
     if (more) {
       kb.load(base + D + (size_t)(k0 + A16_K) * a.ld, a.ld, len - k0 - A16_K, tid);
@@ -366,7 +391,7 @@ __global__ __launch_bounds__(256) void attn_bf16_bwd_dq_kernel(Attn16Args a) {
       float ds[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float p = k0 + 32 * j + acc_row(r, lk) < len ? exp_fast(s[r] * a.scale - lse) : 0.f;
+        const float p = sees(k0 + 32 * j + acc_row(r, lk)) ? exp_fast(s[r] * a.scale - lse) : 0.f;
         if constexpr (DROP) ds[r] = p * (dp[r] * attn_drop_scale(a.drop, kept, r) - delta);   // dP = d . (dO V^T), fp32
         else ds[r] = p * (dp[r] - delta);
       }
@@ -381,7 +406,7 @@ __global__ __launch_bounds__(256) void attn_bf16_bwd_dq_kernel(Attn16Args a) {
   if (qi < a.T) store_acc_t<DK>(dqrow, dq, a.scale, qi >= len, lk);
 }
 
-template <int DK, bool DROP>
+template <int DK, bool DROP, bool WIN>
 __global__ __launch_bounds__(256) void attn_bf16_bwd_dkv_kernel(Attn16Args a) {
   constexpr int PPR = A16<DK>::PPR;
   __shared__ __attribute__((aligned(16))) char Qs[A16<DK>::ROWS], Qt[A16<DK>::COLS], dOs[A16<DK>::ROWS], dOt[A16<DK>::COLS];
@@ -440,9 +465,17 @@ __global__ __launch_bounds__(256) void attn_bf16_bwd_dkv_kernel(Attn16Args a) {
     if (tid < A16_K) lse_s[tid] = lse_r;
   };
 
-  const int ntiles = (len + A16_K - 1) / A16_K;
-  gload(0);
-  for (int it = 0; it < ntiles; ++it) {
+  int first = 0, ntiles = (len + A16_K - 1) / A16_K;
+  WinSpan seen = {};                                         // WIN: the queries that see this lane's key (none past len)
+  if constexpr (WIN) {                                       // the query tiles from qlo(first key) to qhi(last key below len)
+    seen = win_queries(a.win, min(ki, len - 1), len);
+    if (!kvalid) seen.span = 0;
+    first = win_queries(a.win, k0, len).start / A16_K;
+    ntiles = (win_queries(a.win, min(k0 + A16_Q, len) - 1, len).end() + A16_K - 1) / A16_K;
+  }
+  auto seen_by = [&](int q) { if constexpr (WIN) return seen.has(q); else return kvalid && q < len; };
+  gload(first * A16_K);
+  for (int it = first; it < ntiles; ++it) {
     const int t0 = it * A16_K;
     sstore();
     __syncthreads();
@@ -457,7 +490,7 @@ __global__ __launch_bounds__(256) void attn_bf16_bwd_dkv_kernel(Attn16Args a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int qq = 32 * j + acc_row(r, lk);
-        p[r] = (kvalid && t0 + qq < len) ? exp_fast(s[r] * a.scale - lse_s[qq]) : 0.f;
+        p[r] = seen_by(t0 + qq) ? exp_fast(s[r] * a.scale - lse_s[qq]) : 0.f;
         if constexpr (DROP) {                                  // dS keeps the undropped P; dV takes d . P, rounded after the multiply
           const float d = attn_drop_scale(a.drop, kept, r);
           ds[r] = p[r] * (dp[r] * d - delta_s[qq]);
@@ -496,10 +529,10 @@ using namespace nabu;
 extern "C" int nabu_self_attn_bf16_tile_q(void) { return A16_Q; }
 extern "C" int nabu_self_attn_bf16_tile_k(void) { return A16_K; }
 
-// the forward launch of nabu_self_attn_bf16_fwd (drop == nullptr, or keep == 1: the plain instantiations) and of
-// nabu_self_attn_bf16_drop_fwd
+// the forward launch of nabu_self_attn_bf16_fwd (drop == nullptr, or keep == 1: the plain instantiations), of
+// nabu_self_attn_bf16_drop_fwd and of nabu_self_attn_bf16_win_fwd (win != nullptr: the WIN instantiations, at every C)
 static int attn16_fwd_launch(const char *what, int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len,
-                             const AttnDrop *drop, float *o, float *lse, nabu_stream_t stream) {
+                             const AttnDrop *drop, const AttnWin *win, float *o, float *lse, nabu_stream_t stream) {
   NABU_TRY(attn_shape(what, B, T, H, dk, ld));
   NABU_CHECK_ARG(qkv && len && o && lse, "%s: null pointer", what);
   NABU_CHECK_ARG(al16(qkv) && al16(o), "%s: qkv and o must be 16-byte aligned", what);
@@ -509,21 +542,17 @@ static int attn16_fwd_launch(const char *what, int B, int T, int H, int dk, cons
   a.B = B; a.T = T; a.H = H; a.ld = ld; a.scale = 1.f / sqrtf((float)dk);
   const dim3 grid((T + A16_Q - 1) / A16_Q, H, B);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (drop && drop->keep < 1.f) {
-    a.drop = *drop;
-    if (dk == 64) hipLaunchKernelGGL((attn_bf16_fwd_kernel<64, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((attn_bf16_fwd_kernel<32, true>), grid, dim3(256), 0, s, a);
-  } else {
-    if (dk == 64) hipLaunchKernelGGL((attn_bf16_fwd_kernel<64, false>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((attn_bf16_fwd_kernel<32, false>), grid, dim3(256), 0, s, a);
-  }
+  const bool dropping = drop && drop->keep < 1.f;
+  if (dropping) a.drop = *drop;
+  if (win) a.win = *win;
+  ATTN_LAUNCH(attn_bf16_fwd_kernel, dk, dropping, win != nullptr, grid, s, a);
   NABU_LAUNCH_CHECK();
   return 0;
 }
 
 static int attn16_bwd_launch(const char *what, int B, int T, int H, int dk, const float *qkv, int ld, const float *o,
-                             const float *lse, const float *d_o, const int32_t *len, const AttnDrop *drop, float *dqkv,
-                             nabu_stream_t stream) {
+                             const float *lse, const float *d_o, const int32_t *len, const AttnDrop *drop,
+                             const AttnWin *win, float *dqkv, nabu_stream_t stream) {
   NABU_TRY(attn_shape(what, B, T, H, dk, ld));
   NABU_CHECK_ARG(qkv && o && lse && d_o && len && dqkv, "%s: null pointer", what);
   NABU_CHECK_ARG(al16(qkv) && al16(o) && al16(d_o) && al16(dqkv), "%s: qkv, o, do and dqkv must be 16-byte aligned", what);
@@ -533,35 +562,24 @@ static int attn16_bwd_launch(const char *what, int B, int T, int H, int dk, cons
   a.B = B; a.T = T; a.H = H; a.ld = ld; a.scale = 1.f / sqrtf((float)dk);
   const dim3 grid((T + A16_Q - 1) / A16_Q, H, B);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (drop && drop->keep < 1.f) {
-    a.drop = *drop;
-    if (dk == 64) {
-      hipLaunchKernelGGL((attn_bf16_bwd_dkv_kernel<64, true>), grid, dim3(256), 0, s, a);
-      hipLaunchKernelGGL((attn_bf16_bwd_dq_kernel<64, true>), grid, dim3(256), 0, s, a);
-    } else {
-      hipLaunchKernelGGL((attn_bf16_bwd_dkv_kernel<32, true>), grid, dim3(256), 0, s, a);
-      hipLaunchKernelGGL((attn_bf16_bwd_dq_kernel<32, true>), grid, dim3(256), 0, s, a);
-    }
-  } else if (dk == 64) {
-    hipLaunchKernelGGL((attn_bf16_bwd_dkv_kernel<64, false>), grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL((attn_bf16_bwd_dq_kernel<64, false>), grid, dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL((attn_bf16_bwd_dkv_kernel<32, false>), grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL((attn_bf16_bwd_dq_kernel<32, false>), grid, dim3(256), 0, s, a);
-  }
+  const bool dropping = drop && drop->keep < 1.f;
+  if (dropping) a.drop = *drop;
+  if (win) a.win = *win;
+  ATTN_LAUNCH(attn_bf16_bwd_dkv_kernel, dk, dropping, win != nullptr, grid, s, a);
+  ATTN_LAUNCH(attn_bf16_bwd_dq_kernel, dk, dropping, win != nullptr, grid, s, a);
   NABU_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int nabu_self_attn_bf16_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len, float *o,
                                        float *lse, nabu_stream_t stream) {
-  return attn16_fwd_launch("self_attn_bf16_fwd", B, T, H, dk, qkv, ld, len, nullptr, o, lse, stream);
+  return attn16_fwd_launch("self_attn_bf16_fwd", B, T, H, dk, qkv, ld, len, nullptr, nullptr, o, lse, stream);
 }
 
 extern "C" int nabu_self_attn_bf16_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o,
                                        const float *lse, const float *d_o, const int32_t *len, float *dqkv,
                                        nabu_stream_t stream) {
-  return attn16_bwd_launch("self_attn_bf16_bwd", B, T, H, dk, qkv, ld, o, lse, d_o, len, nullptr, dqkv, stream);
+  return attn16_bwd_launch("self_attn_bf16_bwd", B, T, H, dk, qkv, ld, o, lse, d_o, len, nullptr, nullptr, dqkv, stream);
 }
 
 extern "C" int nabu_self_attn_bf16_drop_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len,
@@ -569,7 +587,7 @@ extern "C" int nabu_self_attn_bf16_drop_fwd(int B, int T, int H, int dk, const f
                                             float *lse, nabu_stream_t stream) {
   AttnDrop d;
   NABU_TRY(attn_drop_args("self_attn_bf16_drop_fwd", T, keep, seed, offset, &d));
-  return attn16_fwd_launch("self_attn_bf16_drop_fwd", B, T, H, dk, qkv, ld, len, &d, o, lse, stream);
+  return attn16_fwd_launch("self_attn_bf16_drop_fwd", B, T, H, dk, qkv, ld, len, &d, nullptr, o, lse, stream);
 }
 
 extern "C" int nabu_self_attn_bf16_drop_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o,
@@ -578,5 +596,26 @@ extern "C" int nabu_self_attn_bf16_drop_bwd(int B, int T, int H, int dk, const f
                                             nabu_stream_t stream) {
   AttnDrop d;
   NABU_TRY(attn_drop_args("self_attn_bf16_drop_bwd", T, keep, seed, offset, &d));
-  return attn16_bwd_launch("self_attn_bf16_drop_bwd", B, T, H, dk, qkv, ld, o, lse, d_o, len, &d, dqkv, stream);
+  return attn16_bwd_launch("self_attn_bf16_drop_bwd", B, T, H, dk, qkv, ld, o, lse, d_o, len, &d, nullptr, dqkv, stream);
+}
+
+extern "C" int nabu_self_attn_bf16_win_fwd(int B, int T, int H, int dk, const float *qkv, int ld, const int32_t *len,
+                                           float keep, unsigned long long seed, unsigned long long offset, int chunk,
+                                           int left_chunks, float *o, float *lse, nabu_stream_t stream) {
+  AttnDrop d;
+  AttnWin w;
+  NABU_TRY(attn_drop_args("self_attn_bf16_win_fwd", T, keep, seed, offset, &d));
+  NABU_TRY(attn_win_args("self_attn_bf16_win_fwd", T, chunk, left_chunks, &w));
+  return attn16_fwd_launch("self_attn_bf16_win_fwd", B, T, H, dk, qkv, ld, len, &d, &w, o, lse, stream);
+}
+
+extern "C" int nabu_self_attn_bf16_win_bwd(int B, int T, int H, int dk, const float *qkv, int ld, const float *o,
+                                           const float *lse, const float *d_o, const int32_t *len, float keep,
+                                           unsigned long long seed, unsigned long long offset, int chunk, int left_chunks,
+                                           float *dqkv, nabu_stream_t stream) {
+  AttnDrop d;
+  AttnWin w;
+  NABU_TRY(attn_drop_args("self_attn_bf16_win_bwd", T, keep, seed, offset, &d));
+  NABU_TRY(attn_win_args("self_attn_bf16_win_bwd", T, chunk, left_chunks, &w));
+  return attn16_bwd_launch("self_attn_bf16_win_bwd", B, T, H, dk, qkv, ld, o, lse, d_o, len, &d, &w, dqkv, stream);
 }

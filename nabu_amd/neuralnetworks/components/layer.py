@@ -250,7 +250,8 @@ def conv_frontend(inputs, sequence_length, channels, feature_blocks=1):
 LN_EPS = 1e-5       # variance epsilon of the self-attention block's layer norms (moments per frame over D)
 
 
-def self_attention_block(inputs, sequence_length, num_heads, ff_units, keep=1.0, scope=None, attention_keep=1.0):
+def self_attention_block(inputs, sequence_length, num_heads, ff_units, keep=1.0, scope=None, attention_keep=1.0,
+                         attention_window=None):
     """One pre-norm self-attention block (Vaswani et al. 2017 with the norm in front, as ESPnet's and Lingvo's encoders
     run it) as ONE tape node:
         a = LN(h); qkv = a Wqkv + b (one product to 3D columns); c = self_attn(qkv); h = h + drop(c Wo + bo)
@@ -262,6 +263,9 @@ def self_attention_block(inputs, sequence_length, num_heads, ff_units, keep=1.0,
     atten_dropout_prob, as keep probabilities), made inside the attention kernels; under a tape and below 1 it takes ONE
     more draw from the global stream, after the block's other draws, and hands the same (seed, offset) to the forward and
     the backward call.  Without a tape no draw is taken and the plain kernels run.  Frames past a length carry finite values that no valid frame reads; the encoder masks them.
+    attention_window: None (every pair of frames), or (chunk, left_chunks): a frame attends to its own chunk of `chunk` frames
+    and `left_chunks` chunks to its left (-1: all), inside the kernels, with or without a tape; handed to the forward and
+    the backward call.
     Variables: <scope>/{ln1,ln2}/{gamma,beta} [D], attention/{qkv,out}/{weights,biases}, ffn/{fc1,fc2}/{weights,biases}."""
     lens = SeqLen.wrap(sequence_length, inputs.device)
     B, T, D = inputs.shape
@@ -289,7 +293,7 @@ def self_attention_block(inputs, sequence_length, num_heads, ff_units, keep=1.0,
     x = (inputs if inputs.is_contiguous() else inputs.contiguous()).view(N, D)
     a, mean1, rstd1 = hip.layer_norm_fwd(x, norms[0][0].data, norms[0][1].data, LN_EPS)
     qkv = linear(a, 0, 3 * D).view(B, T, 3 * D)
-    c, lse = hip.self_attn_fwd(qkv, lens.dev, H, attn_precision, attention_keep, attn_rng)
+    c, lse = hip.self_attn_fwd(qkv, lens.dev, H, attn_precision, attention_keep, attn_rng, attention_window)
     h1 = hip.axpy_(drop(linear(c.view(N, D), 1, D), 0), x)
     f, mean2, rstd2 = hip.layer_norm_fwd(h1, norms[1][0].data, norms[1][1].data, LN_EPS)
     r = hip.relu(linear(f, 2, FF))
@@ -317,7 +321,8 @@ def self_attention_block(inputs, sequence_length, num_heads, ff_units, keep=1.0,
         du = hip.relu_bwd(r, linear_bwd(r, drop(dout, 1), 3))
         dh1 = hip.axpy_(norm_bwd(h1, linear_bwd(f, du, 2), 1, mean2, rstd2), dout)
         dc = linear_bwd(c.view(N, D), drop(dh1, 0), 1)
-        dqkv = hip.self_attn_bwd(qkv, c, lse, dc.view(B, T, D), lens.dev, H, attn_precision, attention_keep, attn_rng)
+        dqkv = hip.self_attn_bwd(qkv, c, lse, dc.view(B, T, D), lens.dev, H, attn_precision, attention_keep, attn_rng,
+                                 attention_window)
         da = linear_bwd(a, dqkv.reshape(N, 3 * D), 0)
         if not need_dx:                                  # (the norm's own gradients are still due)
             norm_bwd(x, da, 0, mean1, rstd1)
@@ -327,7 +332,8 @@ def self_attention_block(inputs, sequence_length, num_heads, ff_units, keep=1.0,
     return out
 
 
-def conformer_block(inputs, sequence_length, num_heads, ff_units, conv_kernel, keep=1.0, scope=None, attention_keep=1.0):
+def conformer_block(inputs, sequence_length, num_heads, ff_units, conv_kernel, keep=1.0, scope=None, attention_keep=1.0,
+                    attention_window=None):
     """One Conformer block (Gulati et al. 2020; pre-norm, ESPnet's order) as ONE tape node:
         h = h + 1/2 drop(swish(LN(h) W1 + b1) W2 + b2)                   ffn1
         h = h + drop(self_attn(LN(h) Wqkv + b) Wo + bo)                  attention
@@ -339,7 +345,8 @@ def conformer_block(inputs, sequence_length, num_heads, ff_units, conv_kernel, k
     README says why).  inputs [B,T,D] fp32, D a multiple of 64.  The products run at GEMM_PRECISION, the attention at
     ATTENTION_PRECISION (exact fp32 by default), the convolution module is exact fp32.  keep: dropout keep probability (four draws per block under a tape).
     attention_keep: keep probability of the dropout on the attention probabilities, as in self_attention_block (one more
-    draw under a tape when below 1, after the four).  Frames past a length carry finite values that no valid frame reads; the encoder masks them.
+    draw under a tape when below 1, after the four).  attention_window: as in self_attention_block; it limits the attention
+    only, the convolution module still reads (conv_kernel - 1) / 2 frames ahead.  Frames past a length carry finite values that no valid frame reads; the encoder masks them.
     Variables: <scope>/{ln_ff1,ln_att,ln_conv,ln_ff2,ln_out}/{gamma,beta}, ffn1/{fc1,fc2}/{weights,biases},
     attention/{qkv,out}/..., conv/{pw1,pw2}/..., conv/dw/{kernel [K,D],bias}, conv/norm/{gamma,beta}, ffn2/{fc1,fc2}/..."""
     lens = SeqLen.wrap(sequence_length, inputs.device)
@@ -386,7 +393,7 @@ def conformer_block(inputs, sequence_length, num_heads, ff_units, conv_kernel, k
     h1, ffn1 = ffn(x, 0, 0, 0)
     a2, mean2, rstd2 = norm(h1, 1)
     qkv = linear(a2, 2, 3 * D).view(B, T, 3 * D)
-    c, lse = hip.self_attn_fwd(qkv, lens.dev, H, attn_precision, attention_keep, attn_rng)
+    c, lse = hip.self_attn_fwd(qkv, lens.dev, H, attn_precision, attention_keep, attn_rng, attention_window)
     h2 = hip.axpy_(drop(linear(c.view(N, D), 3, D), 1), h1)
     a3, mean3, rstd3 = norm(h2, 2)
     u = linear(a3, 4, 2 * D).view(B, T, 2 * D)
@@ -430,7 +437,8 @@ def conformer_block(inputs, sequence_length, num_heads, ff_units, conv_kernel, k
             var.grad.copy_(g)
         dh2 = hip.axpy_(norm_bwd(h2, linear_bwd(a3, du.reshape(N, 2 * D), 4), 2, mean3, rstd3), dh3)
         dc = linear_bwd(c.view(N, D), drop(dh2, 1), 3)
-        dqkv = hip.self_attn_bwd(qkv, c, lse, dc.view(B, T, D), lens.dev, H, attn_precision, attention_keep, attn_rng)
+        dqkv = hip.self_attn_bwd(qkv, c, lse, dc.view(B, T, D), lens.dev, H, attn_precision, attention_keep, attn_rng,
+                                 attention_window)
         dh1 = hip.axpy_(norm_bwd(h1, linear_bwd(a2, dqkv.reshape(N, 3 * D), 2), 1, mean2, rstd2), dh2)
         dx = ffn_bwd(dh1, ffn1, 0, 0, 0)                 # (the sublayer's own gradients are due either way)
         return [dx.view(B, T, D) if need_dx else None]

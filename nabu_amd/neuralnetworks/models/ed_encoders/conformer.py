@@ -7,7 +7,8 @@ The module's norm is a layer norm per frame (WeNet's `cnn_module_norm: layer_nor
 not the paper's batch norm: batch statistics over a ragged padded batch would make an utterance's result depend on its
 neighbours, and would add running averages outside the parameter buffer.
 
-cfg keys: the transformer's, and conv_kernel (taps of the depthwise convolution: odd, 3..31), which the [encoder] section
+cfg keys: the transformer's (attention_chunk / attention_left_chunks limit the attention only: the convolution module
+still reads (conv_kernel - 1) / 2 frames ahead), and conv_kernel (taps of the depthwise convolution: odd, 3..31), which the [encoder] section
 must set itself.  Refused at construction: everything Transformer refuses, num_units not a multiple of 64, and a missing,
 even or out-of-range conv_kernel."""
 from nabu_amd.neuralnetworks.components import layer
@@ -29,4 +30,4 @@ class Conformer(Transformer):
 
     def block(self, x, lens, heads, ff, keep, scope):
         return layer.conformer_block(x, lens, heads, ff, int(self.conf['conv_kernel']), keep, scope=scope,
-                                     attention_keep=self.attention_keep)
+                                     attention_keep=self.attention_keep, attention_window=self.attention_window)

@@ -12,9 +12,13 @@ block), attention_dropout (KEEP probability of the dropout on the attention prob
 1 - attention_dropout_rate, Lingvo's 1 - atten_dropout_prob; 1.0 when the key is absent; applied in training only, inside
 the attention kernels, one more draw per block), input_noise, gemm_precision (the dense products), attention_precision (`f32`,
 the default when the key is absent: the attention is exact fp32, self_attn.hip | `bf16`: its four products run on the
-bf16 matrix pipe, self_attn_bf16.hip), the SpecAugment keys and conv_channels / feature_blocks (listener.py).  Refused at
+bf16 matrix pipe, self_attn_bf16.hip), attention_chunk and attention_left_chunks (a frame attends to its own chunk of
+attention_chunk frames and attention_left_chunks chunks to its left, inside the attention kernels, in training and in
+evaluation alike: they describe the model; absent: the whole utterance, and -1 = all chunks to the left; the frames are
+those the attention sees, the pooled ones with conv_channels; attention_chunk = 1 is causal attention), the SpecAugment keys and conv_channels / feature_blocks (listener.py).  Refused at
 construction: num_units not divisible by num_heads, a head width other than 32 or 64 (self_attn.hip), any other value of
-attention_precision, an attention_dropout that is no finite number in (0, 1], and the keys `layer_norm` and `recurrent_precision`, which mean nothing here."""
+attention_precision, an attention_dropout that is no finite number in (0, 1], an attention_chunk that is no integer >= 1, an
+attention_left_chunks that is no integer >= -1 or comes without attention_chunk, and the keys `layer_norm` and `recurrent_precision`, which mean nothing here."""
 import numpy as np
 import torch
 
@@ -109,6 +113,25 @@ def attention_dropout_key(conf):
     return value
 
 
+def attention_window_key(conf):
+    """the `attention_chunk` and `attention_left_chunks` cfg keys (build additions, absent from the defaults files): None
+    without attention_chunk, else (chunk, left_chunks) with left_chunks = -1 (all chunks to the left) when absent"""
+    def integer(key, least):
+        text = str(conf[key]).strip()
+        try:
+            value = int(text)
+        except ValueError:
+            value = least - 1
+        if value < least:
+            raise ValueError('transformer encoder: %s must be an integer >= %d, got %r' % (key, least, text))
+        return value
+    if 'attention_chunk' not in conf:
+        if 'attention_left_chunks' in conf:
+            raise ValueError('transformer encoder: attention_left_chunks counts chunks of attention_chunk frames, which is not set')
+        return None
+    return integer('attention_chunk', 1), integer('attention_left_chunks', -1) if 'attention_left_chunks' in conf else -1
+
+
 class Transformer(ed_encoder.EDEncoder):
     """cfg keys: see the module's docstring"""
 
@@ -127,6 +150,7 @@ class Transformer(ed_encoder.EDEncoder):
                              '32 or 64 and at most 1024 units' % (units // heads))
         attention_precision_key(self.conf)
         attention_dropout_key(self.conf)
+        self.attention_window = attention_window_key(self.conf)
 
     def encode(self, inputs, input_seq_length, is_training):
         layer.GEMM_PRECISION[0] = precision = self.conf.get('gemm_precision', 'default')
@@ -150,4 +174,5 @@ class Transformer(ed_encoder.EDEncoder):
 
     def block(self, x, lens, heads, ff, keep, scope):
         """one block of the stack (conformer.py puts its own here)"""
-        return layer.self_attention_block(x, lens, heads, ff, keep, scope=scope, attention_keep=self.attention_keep)
+        return layer.self_attention_block(x, lens, heads, ff, keep, scope=scope, attention_keep=self.attention_keep,
+                                          attention_window=self.attention_window)

@@ -1134,7 +1134,7 @@ _ATTN_ENTRY = {'f32': 'nabu_self_attn', 'bf16': 'nabu_self_attn_bf16'}
 
 
 def _attn_entry(precision, what):
-    """the C entry point `what` (tile_q, tile_k, fwd, bwd, drop_fwd, drop_bwd) of the attention kernels at `precision`,
+    """the C entry point `what` (tile_q, tile_k, fwd, bwd, drop_fwd, drop_bwd, win_fwd, win_bwd) of the attention kernels at `precision`,
     and its name"""
     if precision not in _ATTN_ENTRY:
         raise _hip.NabuHipError("self_attn: precision %r is not one of 'f32' (self_attn.hip) and 'bf16' "
@@ -1161,18 +1161,26 @@ def _attn_shape(qkv, heads):
     return B, T, int(heads), W // (3 * heads), ld
 
 
-def _attn_drop(keep, rng):
-    """the (keep, seed, offset) arguments of the dropout entry points, or () for the plain ones: keep == 1 or no rng"""
-    return () if rng is None or keep == 1 else (float(keep), int(rng[0]), int(rng[1]))
+def _attn_variant(keep, rng, window):
+    """(the entry points' infix, their extra arguments): '' and () for the plain ones (keep == 1 or no rng, no window),
+    'drop_' and (keep, seed, offset), or with window = (chunk, left_chunks) 'win_' and (keep, seed, offset, chunk,
+    left_chunks), where keep = 1 stands for no dropout"""
+    drop = () if rng is None or keep == 1 else (float(keep), int(rng[0]), int(rng[1]))
+    if window is None:
+        return ('drop_', drop) if drop else ('', ())
+    chunk, left = window
+    return 'win_', (drop or (1.0, 0, 0)) + (int(chunk), int(left))
 
 
-def self_attn_fwd(qkv, len_dev, heads, precision='f32', keep=1.0, rng=None):
+def self_attn_fwd(qkv, len_dev, heads, precision='f32', keep=1.0, rng=None, window=None):
     """(o [B,T,D], lse [B,H,T]) of multi-head self-attention over the frames < len of each row (nabu_self_attn_fwd, or
     nabu_self_attn_bf16_fwd at precision 'bf16': the products on the bf16 matrix pipe, include/nabu_hip.h).  keep < 1 with
     rng = (seed, offset): dropout on the attention probabilities inside the kernel (nabu_self_attn[_bf16]_drop_fwd); lse
-    is the undropped one.  keep == 1 or rng None is the plain call."""
-    drop = _attn_drop(keep, rng)
-    fn, name = _attn_entry(precision, 'drop_fwd' if drop else 'fwd')
+    is the undropped one.  keep == 1 or rng None is the plain call.  window = (chunk, left_chunks): a query sees its own
+    chunk of `chunk` frames and `left_chunks` chunks to its left (-1: all of them), nabu_self_attn[_bf16]_win_fwd, with or
+    without dropout; None makes exactly the calls above."""
+    infix, drop = _attn_variant(keep, rng, window)
+    fn, name = _attn_entry(precision, infix + 'fwd')
     B, T, H, dk, ld = _attn_shape(qkv, heads)
     o = torch.empty((B, T, H * dk), dtype=torch.float32, device=qkv.device)
     lse = torch.empty((B, H, T), dtype=torch.float32, device=qkv.device)
@@ -1180,12 +1188,12 @@ def self_attn_fwd(qkv, len_dev, heads, precision='f32', keep=1.0, rng=None):
     return o, lse
 
 
-def self_attn_bwd(qkv, o, lse, do, len_dev, heads, precision='f32', keep=1.0, rng=None):
+def self_attn_bwd(qkv, o, lse, do, len_dev, heads, precision='f32', keep=1.0, rng=None, window=None):
     """dqkv, of qkv's shape and strides, from the forward call's o and lse and do [B,T,D] (nabu_self_attn_bwd, or
-    nabu_self_attn_bf16_bwd at precision 'bf16'; the precision, keep and rng of the forward call that made o and lse:
-    the kernels make the forward call's mask again)"""
-    drop = _attn_drop(keep, rng)
-    fn, name = _attn_entry(precision, 'drop_bwd' if drop else 'bwd')
+    nabu_self_attn_bf16_bwd at precision 'bf16'; the precision, keep, rng and window of the forward call that made o and
+    lse: the kernels make the forward call's masks again)"""
+    infix, drop = _attn_variant(keep, rng, window)
+    fn, name = _attn_entry(precision, infix + 'bwd')
     B, T, H, dk, ld = _attn_shape(qkv, heads)
     if tuple(do.shape) != tuple(o.shape) or tuple(o.shape) != (B, T, H * dk) or tuple(lse.shape) != (B, H, T):
         raise _hip.NabuHipError('self_attn_bwd: o %s, do %s, lse %s do not fit qkv %s' %

@@ -19,6 +19,13 @@ dk 64 and T 250 (the transformer_ctc recipe behind its front end) and T 1000 (wi
             plain kernels of a library built from the parent commit run beside this build's: the ratio must lie inside
             the spread
 
+  --window  instead of all of the above: the chunk-window kernels (nabu_self_attn[_bf16]_win_*), fp32 and bf16, forward
+            and whole backward call, at (chunk, left_chunks) = (1, -1), (16, -1), (16, 4) and (T, -1), against the plain
+            kernels on the same operands; (T, -1) walks every tile and shows what the predicate alone costs.  The bar:
+            every truly windowed side no slower than the plain kernel.  Reported beside each ratio: the fraction of
+            tiles walked; for information, fp32 scaled_dot_product_attention forward with the same boolean mask.
+            --parent-lib as with --dropout
+
 The bar, forward and backward: no slower.  Lengths are drawn uniformly from T/2 .. T (one row at T).
 Protocol of the other tools: warm-up, then medians of --rounds rounds of --calls calls between device events, the two
 sides of a comparison alternating round by round in the same run; the spread of the round times is reported with them.
@@ -26,7 +33,8 @@ Prints one JSON line (and writes it to --out).
 
     python tools/self_attn_bench.py [--rounds 5] [--calls 200] [--out profiles/self_attn.json]
     python tools/self_attn_bench.py --bf16 --out profiles/self_attn_bf16.json
-    python tools/self_attn_bench.py --dropout [--parent-lib PATH] --out profiles/self_attn_dropout.json"""
+    python tools/self_attn_bench.py --dropout [--parent-lib PATH] --out profiles/self_attn_dropout.json
+    python tools/self_attn_bench.py --window [--parent-lib PATH] --out profiles/self_attn_window.json"""
 import argparse
 import json
 import os
@@ -162,6 +170,87 @@ def attn_dropout_bench(T, rounds, calls, parent):
     return res
 
 
+def tiles_walked(lens, T, TQ, TK, window):
+    """(key tiles the forward and dQ workgroups walk, query tiles the dK/dV workgroups walk) over the batch, by the rule
+    of csrc/attn_win.h; window None: every tile below len"""
+    fwd = dkv = 0
+    for L in (int(x) for x in lens):
+        if window is not None:
+            C = min(window[0], max(T, 1))
+            Lc = -1 if window[1] >= (max(T, 1) - 1) // C else window[1]
+        for r0 in range(0, L, TQ):
+            last = min(r0 + TQ, L) - 1
+            if window is None:
+                fwd, dkv = fwd + -(-L // TK), dkv + -(-L // TK)
+                continue
+            lo = 0 if Lc < 0 else max(0, r0 // C * C - Lc * C)
+            fwd += -(-min(L, (last // C + 1) * C) // TK) - lo // TK
+            dkv += -(-(L if Lc < 0 else min(L, (last // C + Lc + 1) * C)) // TK) - (r0 // C * C) // TK
+    return fwd, dkv
+
+
+def attn_window_bench(T, rounds, calls, parent):
+    """the windowed kernels of both precisions at (C, Lc) = (1, -1), (16, -1), (16, 4) and (T, -1) — the last walks every
+    tile and shows what the predicate alone costs — and the plain kernels on the same operands, alternating in one run; for
+    information fp32 scaled_dot_product_attention forward with the same boolean masks; with `parent` (a libnabu_hip.so
+    built from the parent commit) its plain kernels too.  Each ratio stands beside the fraction of tiles walked."""
+    D = H * DK
+    g = torch.Generator(device='cuda').manual_seed(1)
+    qkv = torch.randn((B, T, 3 * D), device='cuda', generator=g)
+    do = torch.randn((B, T, D), device='cuda', generator=g)
+    host_lens = np.random.default_rng(1).integers(T // 2, T + 1, B).astype(np.int32)
+    host_lens[0] = T
+    lens = torch.from_numpy(host_lens).cuda()
+    windows = {'plain': None, 'c1': (1, -1), 'c16': (16, -1), 'c16_l4': (16, 4), 'cT': (T, -1)}
+    names, fns, kept = [], [], {}
+    for p in ('f32', 'bf16'):
+        for tag, win in windows.items():
+            o, lse = kept[p, tag] = hip.self_attn_fwd(qkv, lens, H, p, window=win)
+            names += ['fwd_%s_%s' % (tag, p), 'bwd_%s_%s' % (tag, p)]
+            fns += [lambda p=p, win=win: hip.self_attn_fwd(qkv, lens, H, p, window=win),
+                    lambda p=p, win=win, o=o, lse=lse: hip.self_attn_bwd(qkv, o, lse, do, lens, H, p, window=win)]
+    q, k, v = (t.contiguous() for t in qkv.view(B, T, 3, H, DK).permute(2, 0, 3, 1, 4))
+    i, j = torch.arange(T, device='cuda')[None, :, None], torch.arange(T, device='cuda')[None, None, :]
+    for tag in ('c1', 'c16', 'c16_l4'):
+        C, Lc = windows[tag]
+        hi = torch.minimum(lens[:, None, None], (i // C + 1) * C)
+        mask = ((j < hi) & (j >= (0 if Lc < 0 else (i // C - Lc) * C)) | (i == j))[:, None]      # (a padding row sees itself: no NaN)
+        names.append('sdpa_fwd_%s_f32' % tag)
+        fns.append(lambda mask=mask: torch.nn.functional.scaled_dot_product_attention(q, k, v, attn_mask=mask))
+    if parent is not None:
+        from nabu_amd import _hip
+        out_o, out_lse, out_d = torch.empty_like(do), torch.empty((B, H, T), device='cuda'), torch.empty_like(qkv)
+        for p, stem in (('f32', 'nabu_self_attn'), ('bf16', 'nabu_self_attn_bf16')):
+            o, lse = kept[p, 'plain']
+            names += ['fwd_parent_%s' % p, 'bwd_parent_%s' % p]
+            fns += [lambda f=getattr(parent, stem + '_fwd'): f(B, T, H, DK, qkv.data_ptr(), 3 * D, lens.data_ptr(), out_o.data_ptr(),
+                                                                out_lse.data_ptr(), _hip.stream()),
+                    lambda f=getattr(parent, stem + '_bwd'), o=o, lse=lse: f(B, T, H, DK, qkv.data_ptr(), 3 * D, o.data_ptr(), lse.data_ptr(),
+                                                                             do.data_ptr(), lens.data_ptr(), out_d.data_ptr(), _hip.stream())]
+    res, spreads = {'shape': [B, T, H, DK]}, {}
+    for name, (ms, spread) in zip(names, rounds_ms(fns, rounds, calls)):
+        res[name + '_ms'], res[name + '_spread'], spreads[name] = round(ms, 4), [round(x, 4) for x in spread], spread
+    for p in ('f32', 'bf16'):
+        full = tiles_walked(host_lens, T, *hip.self_attn_tiles(p), None)
+        for tag, win in windows.items():
+            if win is None:
+                continue
+            walked = tiles_walked(host_lens, T, *hip.self_attn_tiles(p), win)
+            # forward: key tiles; backward: the dQ kernel's key tiles and the dK/dV kernel's query tiles
+            for d, frac in (('fwd', walked[0] / full[0]), ('bwd', (walked[0] + walked[1]) / (full[0] + full[1]))):
+                key = '%s_%s_%s' % (d, tag, p)
+                res[key + '_over_plain'] = round(res[key + '_ms'] / res['%s_plain_%s_ms' % (d, p)], 3)
+                res[key + '_tiles_fraction'] = round(frac, 3)
+                if tag != 'cT':
+                    res[key + '_bar'] = 'met' if res[key + '_ms'] <= res['%s_plain_%s_ms' % (d, p)] else 'missed'
+        if parent is not None:
+            for d in ('fwd', 'bwd'):
+                (a, (alo, ahi)), (b, (blo, bhi)) = ((res['%s_%s_%s_ms' % (d, s, p)], spreads['%s_%s_%s' % (d, s, p)]) for s in ('plain', 'parent'))
+                res['%s_%s_plain_over_parent' % (d, p)] = round(a / b, 4)
+                res['%s_%s_plain_bar' % (d, p)] = 'met' if alo <= b <= ahi or blo <= a <= bhi else 'missed'
+    return res
+
+
 def step_bench(rounds, calls):
     from nabu_amd.neuralnetworks.trainers import trainer_factory
     data = SyntheticData(8, 200, 123, min_frames=120, min_labels=5, max_labels=20, time_reduction=4, seed=2234)
@@ -192,12 +281,14 @@ def main():
     ap.add_argument('--bf16', action='store_true', help='the bf16 kernels against the fp32 kernels and bf16 SDPA, nothing else')
     ap.add_argument('--dropout', action='store_true', help='the attention-dropout kernels against the plain kernels plus '
                     'separate dropout passes, nothing else')
-    ap.add_argument('--parent-lib', default=None, help='with --dropout: a libnabu_hip.so built from the parent commit, whose '
+    ap.add_argument('--window', action='store_true', help='the chunk-window kernels against the plain kernels on the same '
+                    'operands, nothing else')
+    ap.add_argument('--parent-lib', default=None, help='with --dropout or --window: a libnabu_hip.so built from the parent commit, whose '
                     'plain kernels are timed beside this build\'s')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'self_attn_bench needs a GPU'
     torch.cuda.set_device(0)
-    if args.dropout:
+    if args.dropout or args.window:
         parent = None
         if args.parent_lib:
             import ctypes
@@ -206,8 +297,10 @@ def main():
             for stem in ('nabu_self_attn', 'nabu_self_attn_bf16'):
                 for what in ('_fwd', '_bwd'):
                     getattr(parent, stem + what).restype, getattr(parent, stem + what).argtypes = _hip.SIGNATURES[stem + what]
-        res = {'bench': 'self_attn_dropout', 'rounds': args.rounds, 'calls': args.calls, 'device': torch.cuda.get_device_name(0),
-               'parent_lib': bool(parent), 'attention': [attn_dropout_bench(T, args.rounds, args.calls, parent) for T in (250, 1000)]}
+        bench = attn_window_bench if args.window else attn_dropout_bench
+        res = {'bench': 'self_attn_window' if args.window else 'self_attn_dropout', 'rounds': args.rounds, 'calls': args.calls,
+               'device': torch.cuda.get_device_name(0), 'parent_lib': bool(parent),
+               'attention': [bench(T, args.rounds, args.calls, parent) for T in (250, 1000)]}
     elif args.bf16:
         res = {'bench': 'self_attn_bf16', 'rounds': args.rounds, 'calls': args.calls, 'device': torch.cuda.get_device_name(0),
                'attention': [attn_bf16_bench(T, args.rounds, args.calls) for T in (250, 1000)]}
